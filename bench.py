@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the pyQSM hot path on MI355X (contract: see the task brief).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Primary metric (BASELINE.json): Mpoints/s of DBSCAN on the 1 M-point synthetic
@@ -68,7 +68,33 @@ def parse():
     ap.add_argument("--no-ransac", action="store_true")
     ap.add_argument("--no-config5", action="store_true",
                     help="skip the whole-pipeline section (configs[4] at its stated sizes, ~15 s)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed DBSCAN step returned (labels, core flags) to "
+                         "DIR/<name>.npy, float64 / float32; above 3 M points a fixed seeded "
+                         "sample of rows, with its indices")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+# --dump-outputs: labels as float64 + core as float32 (+ the row index as float64 when sampled)
+# = at most 20 B per row; 3 M rows stay under 64 MB
+DUMP_MAX_ROWS = 3_000_000
+
+
+def dump_outputs(directory: str, labels: np.ndarray, core: np.ndarray) -> None:
+    """The primary path's outputs as .npy files two builds can compare row for row. The inputs
+    are seeded (synth.forest), so the same arguments give the same points on every run."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {"dbscan_labels": labels.astype(np.float64), "dbscan_core": core.astype(np.float32)}
+    n = len(labels)
+    if n > DUMP_MAX_ROWS:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_ROWS, replace=False))
+        arrays = {name: a[rows] for name, a in arrays.items()}
+        arrays["dbscan_sample_rows"] = rows.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, f"{name}.npy"), a)
 
 
 def main():
@@ -130,6 +156,7 @@ def main():
         kernels[name] = {"avg_ms": ms / max(cnt, 1), "launches": cnt}
     hip.prof_enable(False, dev)
     labels = d_lab.download((n,), np.int64)
+    core = d_core.download((n,), np.uint8) if args.dump_outputs else None
     n_clusters = int(labels.max() + 1)
     value = world * n * args.steps / elapsed / 1e6
     # The neighbourhood kernels are timed individually (HIP events on the library stream around the
@@ -659,6 +686,8 @@ def main():
                                     f"to GPU: {bool(np.array_equal(skp.labels_, labels))}"}}
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, labels, core)
         print(json.dumps(out))
     if comm is not None:
         comm.close()
