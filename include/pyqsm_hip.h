@@ -421,6 +421,48 @@ int pyqsm_outside_halfspaces(const double* xyz, int64_t n, const double* eq, int
  */
 int pyqsm_mean_f64(const double* v, int64_t n, double* out);
 
+/* ---- cloud cleaning: voxel down-sampling and statistical outlier removal ---------- */
+/*
+ * Open3D's PointCloud.voxel_down_sample and remove_statistical_outlier as clean_cloud at
+ * pyQSM/geometry/point_cloud_processing.py:97-127 applies them (also qsm_generation.py:99-101,447,
+ * canopy_metrics.py:187,275,380). Open3D's source is not at hand: the semantics below are
+ * recollected from Open3D, parity unpinned; tests/clean_restatement.py defines them.
+ *
+ * pyqsm_voxel_down_sample: xyz f64 [n,3], colors f64 [n,3] or NULL, voxel_size > 0 and finite.
+ *   vmin = min_bound - voxel_size / 2; key = floor((p - vmin) / voxel_size) per axis (IEEE fp64
+ *   division); PYQSM_ERANGE when the three index ranges span more than 2^62 cells. One output
+ *   row per occupied voxel, ordered by the smallest input index it holds (Open3D's order is an
+ *   unordered_map's); its value is the sum of the members in ascending index order, from 0.0,
+ *   one add at a time, divided by their count (colours alike). *m = rows; *out_xyz (and
+ *   *out_colors when colors is given) are library buffers of m rows, released with pyqsm_free.
+ *   Optional trace: inverse i64 [n] = output row of every point; offsets i64 [capacity n+1] and
+ *   members i64 [n] = the members of row r, ascending, at members[offsets[r] .. offsets[r+1]).
+ */
+int pyqsm_voxel_down_sample(const double* xyz, int64_t n, const double* colors, double voxel_size,
+                            int64_t* m, double** out_xyz, double** out_colors, int64_t* inverse,
+                            int64_t* offsets, int64_t* members, int32_t device);
+/*
+ * pyqsm_stat_outlier: k = min(nb_neighbors, n) <= 192 nearest points of every point, the point
+ * itself included (d2 = ((dx*dx) + dy*dy) + dz*dz); avg[i] = (sum of sqrt(d2), ascending, one add
+ * at a time from 0.0) / k; mean = (sum of the positive avg) / n, std = sqrt(sum over positive avg
+ * of (avg - mean)^2 / (n - 1)), thr = mean + std_ratio * std (both sums fixed-order device
+ * reductions: the same bits on every run). Keeps i iff 0 < avg[i] < thr.
+ *   keep i64 [capacity n]: kept indices ascending, *n_keep of them; avg f64 [n] or NULL;
+ *   stats f64 [3] = (mean, std, thr) or NULL. nb_neighbors >= 1 and std_ratio > 0.
+ */
+int pyqsm_stat_outlier(const double* xyz, int64_t n, int32_t nb_neighbors, double std_ratio,
+                       int64_t* keep, int64_t* n_keep, double* avg, double* stats, int32_t device);
+/*
+ * pyqsm_clean_cloud: the loop of clean_cloud with the cloud resident in HBM: the voxel step
+ * when voxel_size > 0 (0: off), then `iters` rounds of statistical outlier removal with
+ * int(neighbors) neighbours, after each round neighbors *= 2 and ratio /= 1.5; the kept points
+ * are gathered into a fresh array between rounds. iters = 0 returns the voxel step alone (the
+ * Python clean_cloud returns its input instead when the statistical step is off, as pyQSM does).
+ *   *m = points left; *out_xyz = library buffer of m rows, released with pyqsm_free.
+ */
+int pyqsm_clean_cloud(const double* xyz, int64_t n, double voxel_size, double neighbors, double ratio,
+                      int32_t iters, int64_t* m, double** out_xyz, int32_t device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -77,6 +77,11 @@ SIGNATURES = {
     "pyqsm_pc_laplacian_seg": (ctypes.c_int, [vp, i64, vp, i64, i32, dbl, ctypes.POINTER(i64),
                                               ctypes.POINTER(vp), ctypes.POINTER(vp),
                                               ctypes.POINTER(vp), vp, i32]),
+    "pyqsm_voxel_down_sample": (ctypes.c_int, [vp, i64, vp, dbl, ctypes.POINTER(i64), ctypes.POINTER(vp),
+                                               ctypes.POINTER(vp), vp, vp, vp, i32]),
+    "pyqsm_stat_outlier": (ctypes.c_int, [vp, i64, i32, dbl, vp, ctypes.POINTER(i64), vp, vp, i32]),
+    "pyqsm_clean_cloud": (ctypes.c_int, [vp, i64, dbl, dbl, dbl, i32, ctypes.POINTER(i64),
+                                         ctypes.POINTER(vp), i32]),
     "pyqsm_mean_f64": (ctypes.c_int, [vp, i64, ctypes.POINTER(dbl)]),
     "pyqsm_extreme_points": (ctypes.c_int, [vp, i64, vp, i32, vp, i32]),
     "pyqsm_outside_halfspaces": (ctypes.c_int, [vp, i64, vp, i32, dbl, vp, ctypes.POINTER(i64), i32]),

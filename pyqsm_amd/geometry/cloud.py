@@ -11,6 +11,18 @@ from __future__ import annotations
 import numpy as np
 
 
+def _hip():
+    """The HIP bindings, imported on first use: this module imports without the library."""
+    try:
+        from .. import hip
+    except ImportError:  # flat import (pyqsm_amd/ on sys.path)
+        import os
+        import sys
+        sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+        from pyqsm_amd import hip
+    return hip
+
+
 def as_points(obj) -> np.ndarray:
     """float64 [n,3] view/copy of an array or of an object with ``.points``."""
     if hasattr(obj, "points"):
@@ -46,6 +58,26 @@ class PointCloud:
 
     def get_center(self):
         return self.points.mean(axis=0)
+
+    def voxel_down_sample(self, voxel_size, device: int = 0) -> "PointCloud":
+        """Open3D's ``voxel_down_sample`` on the GPU (``hip.voxel_down_sample``): the mean of every
+        occupied voxel, colours averaged the same way when present. Recollected from Open3D,
+        parity unpinned. Unlike Open3D (whose order comes from a hash map) the voxels are ordered
+        by the smallest input index they hold."""
+        col = None
+        if self.colors is not None and len(np.asarray(self.colors)) == len(self.points):
+            col = self.colors
+        xyz, rgb = _hip().voxel_down_sample(self.points, voxel_size, colors=col, device=device)
+        return PointCloud(xyz, rgb)
+
+    def remove_statistical_outlier(self, nb_neighbors, std_ratio, print_progress: bool = False,
+                                   device: int = 0):
+        """Open3D's ``remove_statistical_outlier`` on the GPU (``hip.stat_outlier``): returns
+        ``(cloud of the kept points, ind)``. ``ind`` is an int64 array of the kept indices in
+        ascending order, not Open3D's list; ``select_by_index(ind)`` takes it as it is.
+        Recollected from Open3D, parity unpinned. ``print_progress`` is accepted and ignored."""
+        ind = _hip().stat_outlier(self.points, nb_neighbors, std_ratio, device=device)
+        return self.select_by_index(ind), ind
 
     def get_min_bound(self):
         return self.points.min(axis=0)

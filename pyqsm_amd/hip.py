@@ -546,3 +546,96 @@ def extract_skeleton(points, lo, hi, k: int, moll: float, max_iter: int, termina
     log = [{"iters": int(iters[t]), "resid": [float(resid[t])] * 3, "ok": bool(ok[t])}
            for t in range(n_solves.value)]
     return out, total, steps, n_steps, log
+
+
+# ---------------------------------------------------------------- cloud cleaning
+
+def _voxel_size(voxel_size) -> float:
+    v = float(voxel_size)
+    if not (np.isfinite(v) and v > 0):
+        raise ValueError(f"voxel_size must be positive and finite, got {voxel_size!r}")
+    return v
+
+
+def _stat_args(nb_neighbors, std_ratio):
+    nb, r = int(nb_neighbors), float(std_ratio)
+    if nb < 1:
+        raise ValueError(f"nb_neighbors must be at least 1, got {nb_neighbors!r}")
+    if not r > 0:
+        raise ValueError(f"std_ratio must be positive, got {std_ratio!r}")
+    if nb > 2**31 - 1:
+        raise ValueError("nb_neighbors must fit in int32")
+    return nb, r
+
+
+def voxel_down_sample(points, voxel_size: float, colors=None, return_trace: bool = False,
+                      device: int = 0):
+    """``pyqsm_voxel_down_sample``: (means [m,3], colour means [m,3] or None) and, with
+    ``return_trace``, also (inverse int64 [n], offsets int64 [m+1], members int64 [n]).
+    Rows are ordered by the smallest input index of each voxel."""
+    pts = _points(points)
+    v = _voxel_size(voxel_size)
+    n = pts.shape[0]
+    col = None
+    if colors is not None:
+        col = np.ascontiguousarray(np.asarray(colors), dtype=np.float64)
+        if col.shape != pts.shape:
+            raise ValueError(f"colors must have the points' shape {pts.shape}, got {col.shape}")
+    lib = _lib.load()
+    m, px, pc = i64(0), vp(), vp()
+    inverse = np.empty(n, dtype=np.int64) if return_trace else None
+    offsets = np.empty(n + 1, dtype=np.int64) if return_trace else None
+    members = np.empty(n, dtype=np.int64) if return_trace else None
+    check(lib.pyqsm_voxel_down_sample(_p(pts), n, _p(col), v, ctypes.byref(m), ctypes.byref(px),
+                                      ctypes.byref(pc) if col is not None else None, _p(inverse),
+                                      _p(offsets), _p(members), int(device)))
+    M = m.value
+    xyz = _adopt(lib, px, ctypes.c_double, max(3 * M, 1), np.float64)[:3 * M].reshape(M, 3) \
+        if px.value else np.zeros((0, 3))
+    rgb = None
+    if col is not None:
+        rgb = _adopt(lib, pc, ctypes.c_double, max(3 * M, 1), np.float64)[:3 * M].reshape(M, 3) \
+            if pc.value else np.zeros((0, 3))
+    if return_trace:
+        return xyz, rgb, (inverse, offsets[:M + 1].copy(), members)
+    return xyz, rgb
+
+
+def stat_outlier(points, nb_neighbors: int, std_ratio: float, return_stats: bool = False,
+                 device: int = 0):
+    """``pyqsm_stat_outlier``: kept indices int64 (ascending); with ``return_stats`` also
+    ``avg`` float64 [n] and ``(mean, std, thr)``."""
+    pts = _points(points)
+    nb, r = _stat_args(nb_neighbors, std_ratio)
+    n = pts.shape[0]
+    keep = np.empty(n, dtype=np.int64)
+    cnt = i64(0)
+    avg = np.empty(n, dtype=np.float64) if return_stats else None
+    stats = np.full(3, np.nan) if return_stats else None
+    check(_lib.load().pyqsm_stat_outlier(_p(pts), n, nb, r, _p(keep), ctypes.byref(cnt), _p(avg),
+                                         _p(stats), int(device)))
+    keep = keep[:cnt.value].copy()
+    if return_stats:
+        return keep, avg, tuple(float(s) for s in stats)
+    return keep
+
+
+def clean_cloud(points, voxel_size: float, neighbors, ratio: float, iters: int, device: int = 0):
+    """``pyqsm_clean_cloud``: the voxel step (``voxel_size`` 0: off), then ``iters`` rounds of
+    statistical outlier removal, all in HBM. Returns the points left, float64 [m,3]."""
+    pts = _points(points)
+    v = 0.0 if not voxel_size else _voxel_size(voxel_size)
+    it = int(iters)
+    if it < 0:
+        raise ValueError(f"iters must be >= 0, got {iters!r}")
+    nb, r = float(neighbors), float(ratio)
+    if it:
+        _stat_args(int(nb), r)
+        if int(nb) * 2 ** (it - 1) > 2**31 - 1:
+            raise ValueError("neighbors doubled iters - 1 times must fit in int32")
+    lib = _lib.load()
+    m, px = i64(0), vp()
+    check(lib.pyqsm_clean_cloud(_p(pts), pts.shape[0], v, nb, r, it, ctypes.byref(m),
+                                ctypes.byref(px), int(device)))
+    M = m.value
+    return _adopt(lib, px, ctypes.c_double, max(3 * M, 1), np.float64)[:3 * M].reshape(M, 3)
