@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the pyQSM hot path on MI355X (contract: see the task brief).
 
-    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Primary metric (BASELINE.json): Mpoints/s of DBSCAN on the 1 M-point synthetic
@@ -10,18 +10,24 @@ full clustering (binning + core flags + union-find + labels). DBSCAN does not
 shard: at N > 1 every rank clusters its own forest (replicas, weak scaling) and
 `value` = all points of all ranks / max-over-ranks time.
 
-Secondary sections on the same JSON line:
+A plain run does only what that figure needs: set-up, W warm-up and K timed steps,
+the outputs of the last step if --dump-outputs is given, and one JSON line with the
+headline and the per-phase HIP-event times of the timed steps (`kernels`).
+
+Secondary sections, measured only with --full, on the same JSON line:
   ray_sweep   500 k-triangle canopy x R sun rays, Mray-tri/s (= R*T/t); rays are
               sharded over the ranks, the expanded mesh is broadcast and the per-shard
               results all-gathered by the library's own RCCL communicator (pyqsm_comm_*;
               strong scaling, R fixed)
   knn         k = 20 neighbours on the same cloud
   roofline    dominant kernel of the primary path, HIP-event timed live
+  binning     the binning phase of the primary path priced per pass over the points
   skeleton    the first --skel-iters Laplacian contractions of extract_skeleton on the
               same cloud with the time split Laplacian / solve (N = 1 only: replicas)
   ransac      1000 circle hypotheses x 50 k points (fit_shape_RANSAC's inner loop); the ten z-slices of
               a tree in one pyqsm_ransac_batch call and one by one
   fps         farthest-point sampling of 10 % of the cloud (what extract_topology does next)
+  config5     configs[4] end to end at its stated sizes (N = 1 only)
   cpu_baseline  scikit-learn DBSCAN (the reference's own call, fit.py:223) on the
               host cores of this box, rank 0, N = 1 only
 """
@@ -68,6 +74,10 @@ def parse():
     ap.add_argument("--no-ransac", action="store_true")
     ap.add_argument("--no-config5", action="store_true",
                     help="skip the whole-pipeline section (configs[4] at its stated sizes, ~15 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure every secondary section (roofline, binning, kNN, ray sweep, "
+                         "skeleton, RANSAC, FPS, config 5, CPU baselines); the --no-* options, "
+                         "--tris, --rays, --ray-steps and --skel-iters apply to these")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="write what the last timed DBSCAN step returned (labels, core flags) to "
                          "DIR/<name>.npy, float64 / float32; above 3 M points a fixed seeded "
@@ -159,86 +169,7 @@ def main():
     core = d_core.download((n,), np.uint8) if args.dump_outputs else None
     n_clusters = int(labels.max() + 1)
     value = world * n * args.steps / elapsed / 1e6
-    # The neighbourhood kernels are timed individually (HIP events on the library stream around the
-    # single launch); the phases above contain several small kernels each.
-    dom = max(("k_core_tiled", "k_hook_sub", "k_union_sub"), key=lambda k: kernels[k]["avg_ms"])
-    dom_ms = kernels[dom]["avg_ms"]
     step_ms = elapsed / args.steps * 1e3
-    # HBM bytes by the counters (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this same section,
-    # profiles/r03_traffic.json; FETCH_SIZE doubled as MI355X_MICROARCH.md prescribes for gfx950)
-    tj = {}
-    tpath = os.path.join(ROOT, "profiles", "r03_traffic.json")
-    if os.path.exists(tpath):
-        with open(tpath) as f:
-            tj = json.load(f)
-    dbt = tj.get("dbscan", {}) if tj.get("points") == n else {}
-    step_bytes = dbt.get("hbm_bytes_per_unit")
-    kern_traffic = {q: {"hbm_bytes_per_launch": v["hbm_bytes_per_launch"], "launches_per_step": v["launches_per_unit"]}
-                    for q, v in dbt.get("kernels", {}).items()}
-    dom_bytes = kern_traffic.get(dom, {}).get("hbm_bytes_per_launch")
-    # executed fp64 pair tests of the core pass (profiling level 2 adds a counter; one extra,
-    # untimed call) priced against the FP64 vector peak: SURVEY.md §8d names FP64 VALU as the
-    # binding roof of the neighbourhood kernels (8 flop + 1 compare per candidate pair)
-    hip.prof_enable(2, dev)
-    hip.prof_reset(dev)
-    hip.dbscan_dev(d_xyz.ptr, n, eps, min_pts, d_lab.ptr, d_core.ptr, dev)
-    _, lane_tests = hip.prof_get("core_pair_tests", dev)
-    _, f32_records = hip.prof_get("dbscan_f32_records", dev)
-    hip.prof_enable(False, dev)
-    core_ms = kernels["k_core_tiled"]["avg_ms"]
-    core_tflops = 9.0 * lane_tests / (core_ms * 1e-3) / 1e12 if core_ms > 0 else 0.0
-    achieved = step_bytes / (step_ms * 1e-3) / 1e9 if step_bytes else None
-    alg_step = DBSCAN_BYTES_PER_POINT * n / (step_ms * 1e-3) / 1e9
-    roofline = {
-        "kernel": "dbscan step (every kernel of one clustering)", "bound": "hbm",
-        "achieved": achieved if achieved is not None else alg_step, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-        "frac": (achieved if achieved is not None else alg_step) / HBM_PEAK_GBS,
-        "traffic": step_bytes, "avg_launch_ms": step_ms,
-        "step_hbm_frac": alg_step / HBM_PEAK_GBS,
-        "algorithmic_bytes_per_step": DBSCAN_BYTES_PER_POINT * n,
-        "dominant_kernel": {"kernel": dom, "avg_launch_ms": dom_ms, "traffic": dom_bytes,
-                            "traffic_GBs": dom_bytes / (dom_ms * 1e-3) / 1e9 if dom_bytes else None,
-                            "frac": dom_bytes / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if dom_bytes else None},
-        "per_kernel": {q: dict(v, avg_launch_ms=kernels[q]["avg_ms"],
-                               GBs=v["hbm_bytes_per_launch"] / (kernels[q]["avg_ms"] * 1e-3) / 1e9)
-                       for q, v in kern_traffic.items() if q in kernels and kernels[q]["avg_ms"] > 0},
-        "fp64_valu": {"kernel": "k_core_tiled", "lane_tests_per_launch": lane_tests,
-                      "flop_per_test": 9, "achieved": core_tflops, "peak": FP64_PEAK_TFLOPS,
-                      "unit": "TFLOP/s", "frac": core_tflops / FP64_PEAK_TFLOPS,
-                      "avg_launch_ms": core_ms,
-                      "note": "lane-tests EXECUTED (64 lanes x candidates staged per wave, "
-                              "counted on the device at profiling level 2), early exits "
-                              "included; SURVEY's stencil holds ~855 candidates per point"},
-        "fp32_records": bool(f32_records),
-        "note": "achieved = HBM bytes of ONE WHOLE STEP by the counters (sum over its ~20 kernels of 2 x FETCH_SIZE + "
-                "WRITE_SIZE per launch x launches per step, profiles/r03_traffic.json) / the step's time, live; frac = "
-                "that / 8 TB/s. step_hbm_frac prices the same step at SURVEY.md §8d's algorithmic 341 B/point instead. "
-                "The neighbourhood kernels are FP64-VALU / gather-latency bound, not HBM bound: fp64_valu prices the "
-                "core pass against the vector peak; dominant_kernel gives the slowest kernel's own counter bytes over "
-                "its own HIP-event time. " + ("" if step_bytes else "NO PMC summary for this size: achieved falls "
-                                              "back to the algorithmic figure and traffic is null.")}
-
-    # ---- binning class (passes x N x bytes; state the pass count)
-    ext = pts.max(0) - pts.min(0)
-    cell = eps * (1.0 + 1.0 / 1048576.0)
-    ncell = float(np.prod(np.floor(ext / cell) + 3.0))
-    rec_b = 28.0 if f32_records else 36.0           # sorted record: fp32 x,y,z,flag or three fp64 + order, cell, sub-cell
-    bin_alg = n * (24.0 + (24.0 + 4.0) + (24.0 + 4.0 + 32.0) + (32.0 + rec_b)) + 4.0 * ncell + 128.0 * (n / 5.0)
-    bin_ms = kernels["dbscan_bin"]["avg_ms"]
-    bin_names = ("k_bbox", "k_bbox_fold", "k_bk_hist", "k_bk_scan", "k_bk_scatter", "k_bk_sort", "k_order_big")
-    bin_bytes = sum(kern_traffic[q]["hbm_bytes_per_launch"] * kern_traffic[q]["launches_per_step"]
-                    for q in bin_names if q in kern_traffic) or None
-    binning = {"roofline": {
-        "kernel": "dbscan_bin: k_bbox, k_bk_hist, k_bk_scatter, k_bk_sort (+ 3 small kernels)", "bound": "hbm",
-        "passes_over_the_points": 4, "avg_launch_ms": bin_ms,
-        "algorithmic_bytes": bin_alg, "achieved": bin_alg / (bin_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
-        "unit": "GB/s", "frac": bin_alg / (bin_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": bin_bytes,
-        "traffic_over_algorithmic": bin_bytes / bin_alg if bin_bytes else None,
-        "note": "four passes over the points: bounding box (24 B read), bucket histogram (24 read + 4 written), "
-                "bucket scatter (28 read + 32 written), in-LDS sort of every bucket (32 read + the sorted record "
-                f"written: {rec_b:.0f} B) = {24 + 28 + 60 + 32 + rec_b:.0f} B per point, plus the dense cell directory "
-                f"written once (4 B x {ncell:.3g} cells) and 128 B of sub-cell records per occupied cell (~n / 5 cells); the phase "
-                "also holds one host round trip (the bounding box sizes the grid)"}}
     out = {
         "metric": "Mpoints/s DBSCAN (1M-pt synthetic forest, eps=0.1, min_neighbors=10)",
         "value": value, "unit": "Mpoints/s", "n_gpus": world, "steps": args.steps,
@@ -248,11 +179,23 @@ def main():
         "config": {"workload": f"{n}-point synthetic tree cloud (configs[1]), DBSCAN eps=0.1 "
                                f"min_neighbors=10, {n_clusters} clusters; replicas at N>1",
                    "points_per_gpu": n, "parallelism": f"replicas x{world}"},
-        "roofline": roofline, "binning": binning, "kernels": kernels,
+        "kernels": kernels,
     }
 
+    # Every section from here to the print is --full only: a plain run prints `out` as it stands.
+    tj = {}
+    if args.full:
+        # HBM bytes by the counters (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this same section,
+        # profiles/r03_traffic.json; FETCH_SIZE doubled as MI355X_MICROARCH.md prescribes for gfx950)
+        tpath = os.path.join(ROOT, "profiles", "r03_traffic.json")
+        if os.path.exists(tpath):
+            with open(tpath) as f:
+                tj = json.load(f)
+        out["roofline"], out["binning"] = dbscan_roofline(dev, d_xyz, d_lab, d_core, pts, eps, min_pts,
+                                                            kernels, step_ms, tj)
+
     # ------------------------------------------------------------- kNN (same cloud)
-    if not args.no_knn:
+    if args.full and not args.no_knn:
         k = 20
         d_idx = hip.DeviceBuffer(n * k * 4, dev)
         d_d2 = hip.DeviceBuffer(n * k * 8, dev)
@@ -321,7 +264,7 @@ def main():
         d_d2.free()
 
     # ------------------------------------------------------------- ray sweep
-    if not args.no_rays:
+    if args.full and not args.no_rays:
         T, R = args.tris, args.rays
         verts, tris = synth.canopy_mesh(T)           # same seed on every rank (rays need its bbox)
         b, e = shard_bounds(R, world, rank)
@@ -411,7 +354,7 @@ def main():
                           "(Open3D is not installable here)"}
 
     # ------------------------------------------------------------- skeleton (config 3)
-    if not args.no_skeleton and world == 1:
+    if args.full and not args.no_skeleton and world == 1:
         from pyqsm_amd.geometry import skeletonize as skel
         names = ("lap_knn", "lap_fans", "lap_assemble", "lbc_amg_iter", "lbc_amg_build",
                  "lbc_inner_iter", "lbc_outer_iter")
@@ -542,7 +485,7 @@ def main():
                 "points": base}
 
     # ------------------------------------------------------------- RANSAC circle fit
-    if not args.no_ransac and world == 1:
+    if args.full and not args.no_ransac and world == 1:
         nr, H = 50_000, 1000
         ring = synth.ring_cluster(nr, seed=3)
         ring[:, 2] = 0.0                                   # fit.py:274-276: circle fit in z = 0
@@ -617,7 +560,7 @@ def main():
                           f"{bool(np.array_equal(np.asarray(ref[3]), sub[3]))}"}
 
     # ------------------------------------------------------------- farthest-point sampling
-    if not args.no_skeleton and world == 1:
+    if args.full and not args.no_skeleton and world == 1:
         # extract_topology keeps 10 % of the contracted cloud (skeletonize.py:127-132): 1 M -> 100 k here,
         # on the bench's own forest (the pruned rounds do not depend on the cloud being contracted)
         s_fps = n // 10
@@ -645,7 +588,7 @@ def main():
                               "point and sample"}
 
     # ------------------------------------------------------------- config 5: the whole pipeline
-    if not args.no_config5 and not args.no_skeleton and world == 1:
+    if args.full and not args.no_config5 and not args.no_skeleton and world == 1:
         # BASELINE.json configs[4] at its stated sizes on this one GPU: 5 M points -> DBSCAN -> 100 trees
         # through extract_skeleton_batch (20 contractions each) -> every stem slice through
         # fit_shape_RANSAC_batch (H = 1000) -> 5 sun angles x 10 M culled rays; the driver is
@@ -667,7 +610,7 @@ def main():
             "ransac_thread_seconds": rec["ransac_thread_seconds"]}
 
     # ------------------------------------------------------------- CPU baseline (primary)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         from sklearn.cluster import DBSCAN
         t0 = time.perf_counter()
         sk = DBSCAN(eps=eps, min_samples=min_pts).fit(pts)
@@ -693,6 +636,86 @@ def main():
         comm.close()
     if dist is not None:
         dist.destroy_process_group()
+
+
+def dbscan_roofline(dev, d_xyz, d_lab, d_core, pts, eps, min_pts, kernels, step_ms, tj):
+    """--full: the DBSCAN step priced against HBM and the FP64 vector peak (one extra, untimed
+    clustering at profiling level 2), and its binning phase priced per pass over the points."""
+    from pyqsm_amd import hip
+    n = len(pts)
+    # The neighbourhood kernels are timed individually (HIP events on the library stream around the
+    # single launch); the phases in `kernels` contain several small kernels each.
+    dom = max(("k_core_tiled", "k_hook_sub", "k_union_sub"), key=lambda k: kernels[k]["avg_ms"])
+    dom_ms = kernels[dom]["avg_ms"]
+    dbt = tj.get("dbscan", {}) if tj.get("points") == n else {}
+    step_bytes = dbt.get("hbm_bytes_per_unit")
+    kern_traffic = {q: {"hbm_bytes_per_launch": v["hbm_bytes_per_launch"], "launches_per_step": v["launches_per_unit"]}
+                    for q, v in dbt.get("kernels", {}).items()}
+    dom_bytes = kern_traffic.get(dom, {}).get("hbm_bytes_per_launch")
+    # executed fp64 pair tests of the core pass (profiling level 2 adds a counter; one extra,
+    # untimed call) priced against the FP64 vector peak: SURVEY.md §8d names FP64 VALU as the
+    # binding roof of the neighbourhood kernels (8 flop + 1 compare per candidate pair)
+    hip.prof_enable(2, dev)
+    hip.prof_reset(dev)
+    hip.dbscan_dev(d_xyz.ptr, n, eps, min_pts, d_lab.ptr, d_core.ptr, dev)
+    _, lane_tests = hip.prof_get("core_pair_tests", dev)
+    _, f32_records = hip.prof_get("dbscan_f32_records", dev)
+    hip.prof_enable(False, dev)
+    core_ms = kernels["k_core_tiled"]["avg_ms"]
+    core_tflops = 9.0 * lane_tests / (core_ms * 1e-3) / 1e12 if core_ms > 0 else 0.0
+    achieved = step_bytes / (step_ms * 1e-3) / 1e9 if step_bytes else None
+    alg_step = DBSCAN_BYTES_PER_POINT * n / (step_ms * 1e-3) / 1e9
+    roofline = {
+        "kernel": "dbscan step (every kernel of one clustering)", "bound": "hbm",
+        "achieved": achieved if achieved is not None else alg_step, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+        "frac": (achieved if achieved is not None else alg_step) / HBM_PEAK_GBS,
+        "traffic": step_bytes, "avg_launch_ms": step_ms,
+        "step_hbm_frac": alg_step / HBM_PEAK_GBS,
+        "algorithmic_bytes_per_step": DBSCAN_BYTES_PER_POINT * n,
+        "dominant_kernel": {"kernel": dom, "avg_launch_ms": dom_ms, "traffic": dom_bytes,
+                            "traffic_GBs": dom_bytes / (dom_ms * 1e-3) / 1e9 if dom_bytes else None,
+                            "frac": dom_bytes / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if dom_bytes else None},
+        "per_kernel": {q: dict(v, avg_launch_ms=kernels[q]["avg_ms"],
+                               GBs=v["hbm_bytes_per_launch"] / (kernels[q]["avg_ms"] * 1e-3) / 1e9)
+                       for q, v in kern_traffic.items() if q in kernels and kernels[q]["avg_ms"] > 0},
+        "fp64_valu": {"kernel": "k_core_tiled", "lane_tests_per_launch": lane_tests,
+                      "flop_per_test": 9, "achieved": core_tflops, "peak": FP64_PEAK_TFLOPS,
+                      "unit": "TFLOP/s", "frac": core_tflops / FP64_PEAK_TFLOPS,
+                      "avg_launch_ms": core_ms,
+                      "note": "lane-tests EXECUTED (64 lanes x candidates staged per wave, "
+                              "counted on the device at profiling level 2), early exits "
+                              "included; SURVEY's stencil holds ~855 candidates per point"},
+        "fp32_records": bool(f32_records),
+        "note": "achieved = HBM bytes of ONE WHOLE STEP by the counters (sum over its ~20 kernels of 2 x FETCH_SIZE + "
+                "WRITE_SIZE per launch x launches per step, profiles/r03_traffic.json) / the step's time, live; frac = "
+                "that / 8 TB/s. step_hbm_frac prices the same step at SURVEY.md §8d's algorithmic 341 B/point instead. "
+                "The neighbourhood kernels are FP64-VALU / gather-latency bound, not HBM bound: fp64_valu prices the "
+                "core pass against the vector peak; dominant_kernel gives the slowest kernel's own counter bytes over "
+                "its own HIP-event time. " + ("" if step_bytes else "NO PMC summary for this size: achieved falls "
+                                              "back to the algorithmic figure and traffic is null.")}
+
+    # ---- binning class (SURVEY.md §8d: passes x N x bytes; state the pass count)
+    ext = pts.max(0) - pts.min(0)
+    cell = eps * (1.0 + 1.0 / 1048576.0)
+    ncell = float(np.prod(np.floor(ext / cell) + 3.0))
+    rec_b = 28.0 if f32_records else 36.0           # sorted record: fp32 x,y,z,flag or three fp64 + order, cell, sub-cell
+    bin_alg = n * (24.0 + (24.0 + 4.0) + (24.0 + 4.0 + 32.0) + (32.0 + rec_b)) + 4.0 * ncell + 128.0 * (n / 5.0)
+    bin_ms = kernels["dbscan_bin"]["avg_ms"]
+    bin_names = ("k_bbox", "k_bbox_fold", "k_bk_hist", "k_bk_scan", "k_bk_scatter", "k_bk_sort", "k_order_big")
+    bin_bytes = sum(kern_traffic[q]["hbm_bytes_per_launch"] * kern_traffic[q]["launches_per_step"]
+                    for q in bin_names if q in kern_traffic) or None
+    binning = {"roofline": {
+        "kernel": "dbscan_bin: k_bbox, k_bk_hist, k_bk_scatter, k_bk_sort (+ 3 small kernels)", "bound": "hbm",
+        "passes_over_the_points": 4, "avg_launch_ms": bin_ms,
+        "algorithmic_bytes": bin_alg, "achieved": bin_alg / (bin_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
+        "unit": "GB/s", "frac": bin_alg / (bin_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": bin_bytes,
+        "traffic_over_algorithmic": bin_bytes / bin_alg if bin_bytes else None,
+        "note": "four passes over the points: bounding box (24 B read), bucket histogram (24 read + 4 written), "
+                "bucket scatter (28 read + 32 written), in-LDS sort of every bucket (32 read + the sorted record "
+                f"written: {rec_b:.0f} B) = {24 + 28 + 60 + 32 + rec_b:.0f} B per point, plus the dense cell directory "
+                f"written once (4 B x {ncell:.3g} cells) and 128 B of sub-cell records per occupied cell (~n / 5 cells); the phase "
+                "also holds one host round trip (the bounding box sizes the grid)"}}
+    return roofline, binning
 
 
 if __name__ == "__main__":

@@ -127,7 +127,7 @@ def _run_ranks(world, body):
 @pytest.mark.parametrize("world", [2, 3, 8])
 @pytest.mark.parametrize("R", [1, 7, 1001, 300_000])
 def test_one_communicator_per_rank_sharded_sweep(gpu, mesh, logical, world, R):
-    """What bench.py --gpus N does per rank (ShardedSweep over a NativeComm), for ragged shards
+    """What bench.py --full --gpus N does per rank (ShardedSweep over a NativeComm), for ragged shards
     and for fewer rays than ranks."""
     verts, tris = mesh
     logical(world)

@@ -34,7 +34,7 @@ def plain(name):
 # 1. kernel stats of the whole default bench run
 rows = list(csv.DictReader(open(find("bench", "kernel_stats.csv"))))
 with open(f"{OUT}/{ROUND}_bench_kernel_stats.csv", "w") as f:
-    f.write("# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --no-cpu  (round 2;\n")
+    f.write("# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --no-cpu  (round 2;\n")
     f.write("# hipGraph replays are ON under the profiler: the library no longer looks at ROCP_TOOL_LIBRARIES)\n")
     f.write("kernel,calls,avg_us,total_ms,percent\n")
     for r in rows:
@@ -53,7 +53,7 @@ def pmc(sub, counters):
 
 
 # 2. HBM traffic of the DBSCAN kernels
-cmd = "python3 bench.py --steps 3 --warmup 1 --no-rays --no-knn --no-skeleton --no-ransac --no-cpu"
+cmd = "python3 bench.py --full --steps 3 --warmup 1 --no-rays --no-knn --no-skeleton --no-ransac --no-cpu"
 fetch, write = pmc("fetch", {"FETCH_SIZE"}), pmc("write", {"WRITE_SIZE"})
 for name, acc, cname in (("fetch_size", fetch, "FETCH_SIZE"), ("write_size", write, "WRITE_SIZE")):
     with open(f"{OUT}/{ROUND}_dbscan_pmc_{name}.csv", "w") as f:
@@ -110,9 +110,9 @@ def sq(sub, out_name, cmdline, keep):
 
 sq("sq_dbscan", "dbscan_sq_counters", cmd, None)
 sq("sq_rays", "rays_sq_counters",
-   "python3 bench.py --steps 2 --warmup 1 --no-knn --no-skeleton --no-ransac --no-cpu --ray-steps 1", ["k_cast", "k_dir"])
+   "python3 bench.py --full --steps 2 --warmup 1 --no-knn --no-skeleton --no-ransac --no-cpu --ray-steps 1", ["k_cast", "k_dir"])
 sq("sq_knn", "knn_sq_counters",
-   "python3 bench.py --steps 2 --warmup 1 --no-rays --no-skeleton --no-ransac --no-cpu", ["k_knn"])
+   "python3 bench.py --full --steps 2 --warmup 1 --no-rays --no-skeleton --no-ransac --no-cpu", ["k_knn"])
 # 4. graphs under the profiler
 log = open(f"{SRC}/graph_jacobi.log").read()
 open(f"{OUT}/{ROUND}_graph_under_rocprof.txt", "w").write(

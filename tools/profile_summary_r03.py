@@ -125,12 +125,12 @@ def sq(sub, out_name, cmdline, keep):
     return out
 
 
-DB = "python3 bench.py --steps 5 --warmup 1 --no-rays --no-knn --no-skeleton --no-ransac --no-cpu"
-KN = "python3 bench.py --steps 2 --warmup 1 --no-rays --no-skeleton --no-ransac --no-cpu"
+DB = "python3 bench.py --full --steps 5 --warmup 1 --no-rays --no-knn --no-skeleton --no-ransac --no-cpu"
+KN = "python3 bench.py --full --steps 2 --warmup 1 --no-rays --no-skeleton --no-ransac --no-cpu"
 
 # 1. kernel stats of the whole default bench run
 bench_stats = stats("bench", "bench_kernel_stats",
-      "# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --no-cpu --no-config5  (round 3;\n"
+      "# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --no-cpu --no-config5  (round 3;\n"
       "# hipGraph replays are ON under the profiler)\n")
 bj = last_json(f"{SRC}/bench.json")
 if bj:
