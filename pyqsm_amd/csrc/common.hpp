@@ -1,6 +1,7 @@
 // common.hpp — per-device context (stream, scratch arena, event timers) and
 // error plumbing shared by every translation unit of libpyqsm_hip.so.
 #pragma once
+#include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -79,6 +80,16 @@ struct Timer {
   std::vector<int> weights;  // launches represented by each pending pair
 };
 
+// The launch shapes a device-planned DBSCAN call is enqueued with (grid.hpp GridPlan): the exact plan
+// of the last host-planned call with some headroom. The bounding box's fold sets the plan's ok only
+// when the exact plan fits them — ncell and nbk no larger, bits = 12, the same side of the fused-scan
+// threshold — and needs no axis compression, no doubled cell and fp32 records, on finite
+// coordinates. valid == 0: no hint, ok stays 0. It decides which path runs, never what it computes.
+struct PlanHint {
+  int valid = 0;
+  int ncell = 0, nbk = 0, fused = 0;
+};
+
 struct Ctx {
   int device = -1;
   hipStream_t stream = nullptr;
@@ -88,6 +99,11 @@ struct Ctx {
   std::map<std::string, Timer> timers;
   std::vector<hipEvent_t> event_pool;
   int cu_count = 256;
+  // DBSCAN's grid plan: page-locked [read-back, upload] slots, the timing-disabled event the host
+  // waits on for the read-back, and the hint of the last host-planned call (dbscan.hip)
+  void* plan_pinned = nullptr;
+  hipEvent_t plan_ev = nullptr;
+  PlanHint plan_hint;
 };
 
 // Returns the context for `device`, creating it on first use. nullptr + error
@@ -105,6 +121,15 @@ class ProfScope {
   Ctx* c_;
   Timer* t_ = nullptr;
   hipEvent_t start_ = nullptr;
+};
+
+// The same for a scope of exactly one kernel: the pair of events (null when profiling is off) is
+// handed to hipExtLaunchKernelGGL, which records them with the kernel's own dispatch instead of
+// as two markers of their own on the stream.
+class ProfKernel {
+ public:
+  ProfKernel(Ctx* c, const char* name);
+  hipEvent_t start = nullptr, stop = nullptr;
 };
 
 // roctx range around a C-ABI entry point (tracing): shows up in

@@ -287,6 +287,21 @@ ProfScope::~ProfScope() {
   (void)hipEventRecord(t_->pending.back().second, c_->stream);
 }
 
+ProfKernel::ProfKernel(Ctx* c, const char* name) {
+  if (c->prof < 1) return;
+  hipEvent_t a = nullptr, b = nullptr;
+  if (hipEventCreate(&a) != hipSuccess) return;
+  if (hipEventCreate(&b) != hipSuccess) {
+    (void)hipEventDestroy(a);
+    return;
+  }
+  Timer& t = c->timers[name];
+  t.pending.emplace_back(a, b);
+  t.weights.push_back(1);
+  start = a;
+  stop = b;
+}
+
 static void drain_timers(Ctx* c) {
   (void)hipStreamSynchronize(c->stream);
   for (auto& kv : c->timers) {
@@ -334,6 +349,8 @@ int pyqsm_shutdown(void) {
         (void)hipStreamSynchronize(c->stream);
         drain_timers(c);
         c->arena.destroy();
+        if (c->plan_pinned) (void)hipHostFree(c->plan_pinned);
+        if (c->plan_ev) (void)hipEventDestroy(c->plan_ev);
         (void)hipStreamDestroy(c->stream);
       }
       delete c;

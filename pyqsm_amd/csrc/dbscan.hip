@@ -18,6 +18,7 @@
 // d2 = ((dx*dx) + dy*dy) + dz*dz with separately rounded products, compared
 // with fl(eps*eps). The library is compiled with -ffp-contract=off.
 #include "grid.hpp"
+#include <optional>
 #include <vector>
 
 namespace pyqsm {
@@ -72,7 +73,7 @@ static constexpr int kRestSegs = 64;  // segments (and counters) of the straggle
 __device__ constexpr int kRunOrder[9] = {4, 3, 5, 1, 7, 0, 2, 6, 8};
 
 template <class CO>
-__global__ __launch_bounds__(256) void k_core_tiled(int n, Stencil st, int ncell,
+__global__ __launch_bounds__(256) void k_core_tiled(int n, const GridPlan* __restrict__ plan,
                                                     const int32_t* __restrict__ start,
                                                     const int32_t* __restrict__ cell_of, CO co, double r2,
                                                     int min_pts, uint8_t* __restrict__ core,
@@ -87,7 +88,9 @@ __global__ __launch_bounds__(256) void k_core_tiled(int n, Stencil st, int ncell
   // wave-uniform quantities are forced into SGPRs so that the loops below are scalar
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int p0 = (blockIdx.x * 4 + w) * 64;
-  if (p0 >= n) return;  // whole wave
+  if (p0 >= n || !plan->ok) return;  // whole wave
+  const Stencil st = plan_stencil(plan);
+  const int ncell = plan->ncell;
   const int p = p0 + lane;
   const bool live = p < n;
   double x = 0.0, y = 0.0, z = 0.0;
@@ -219,10 +222,12 @@ __device__ __forceinline__ Runs9 stencil_runs(int c, Stencil st, const int32_t* 
 template <class CO>
 __global__ __launch_bounds__(256) void k_core_rest(const int32_t* __restrict__ rest,
                                                    const int32_t* __restrict__ rest_cnt /*[kRestSegs]*/,
-                                                   int seg_cap, Stencil st,
+                                                   int seg_cap, const GridPlan* __restrict__ plan,
                                                    const int32_t* __restrict__ start,
                                                    const int32_t* __restrict__ cell_of, CO co, double r2,
                                                    int min_pts, uint8_t* __restrict__ core) {
+  if (!plan->ok) return;
+  const Stencil st = plan_stencil(plan);
   const int lane = threadIdx.x & 63;
   // the list is kRestSegs segments: lane s holds segment s's count, an inclusive scan numbers the entries
   const int mine = rest_cnt[lane];
@@ -322,8 +327,10 @@ __global__ __launch_bounds__(1024) void k_sub_rep(int n, const int32_t* __restri
                                                  int4* __restrict__ rec,
                                                  int* __restrict__ run_min,
                                                  int4* __restrict__ list,
-                                                 int32_t* __restrict__ list_cnt, int nx, int ny,
+                                                 int32_t* __restrict__ list_cnt, const GridPlan* __restrict__ plan,
                                                  int4* __restrict__ list_xyz) {
+  if (!plan->ok) return;
+  const int nx = plan->nx, ny = plan->ny;
   int p = blockIdx.x * 1024 + threadIdx.x;
   int rep = -1, sid = 0, e = 0;
   if (p < n) {
@@ -410,12 +417,14 @@ __global__ __launch_bounds__(256) void k_flatten_reps(const int4* __restrict__ l
 template <int kSubPerWave, class CO>
 __global__ __launch_bounds__(256) void k_hook_sub(const int4* __restrict__ list,
                                                   const int4* __restrict__ list_xyz,
-                                                  const int32_t* __restrict__ m_ptr, int nx,
-                                                  int ny, const int32_t* __restrict__ start,
+                                                  const int32_t* __restrict__ m_ptr,
+                                                  const GridPlan* __restrict__ plan, const int32_t* __restrict__ start,
                                                   const int4* __restrict__ rec, CO co, double r2,
                                                   const uint8_t* __restrict__ core,
                                                   int* __restrict__ parent,
                                                   int32_t* __restrict__ nbr) {
+  if (!plan->ok) return;
+  const int nx = plan->nx, ny = plan->ny;
   const int m = *m_ptr;
   const int k = threadIdx.x & 63;
   const int o_dx = k < 62 ? kSubOffsets[k][0] : 0, o_dy = k < 62 ? kSubOffsets[k][1] : 0,
@@ -684,9 +693,10 @@ __global__ __launch_bounds__(256) void k_rep_min(const int4* __restrict__ list,
 __global__ __launch_bounds__(256) void k_flatten(int n, const uint8_t* __restrict__ core,
                                                  int* __restrict__ parent,
                                                  const int* __restrict__ min_orig /*may be null*/,
-                                                 int32_t* __restrict__ flag /*may be null*/) {
+                                                 int32_t* __restrict__ flag /*may be null*/,
+                                                 const GridPlan* __restrict__ plan) {
   int p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= n || !core[p]) return;
+  if (!plan->ok || p >= n || !core[p]) return;
   int r = p;
   for (int nx = parent[r]; nx != r; nx = parent[r]) r = nx;
   parent[p] = r;  // benign: r is still an ancestor for concurrent readers
@@ -713,7 +723,8 @@ __global__ __launch_bounds__(1024) void k_labels(int n, const uint8_t* __restric
                                                  int64_t* __restrict__ labels,
                                                  uint8_t* __restrict__ is_core,
                                                  int32_t* __restrict__ rest,
-                                                 int32_t* __restrict__ rest_cnt) {
+                                                 int32_t* __restrict__ rest_cnt, const GridPlan* __restrict__ plan) {
+  if (!plan->ok) return;  // block-uniform
   int p = blockIdx.x * 1024 + threadIdx.x;
   const bool live = p < n;
   const bool is_c = live && core[p];
@@ -742,7 +753,8 @@ __global__ __launch_bounds__(1024) void k_labels(int n, const uint8_t* __restric
 template <class CO>
 __global__ __launch_bounds__(256) void k_labels_border(const int32_t* __restrict__ rest,
                                                        const int32_t* __restrict__ rest_cnt,
-                                                       Stencil st, const int32_t* __restrict__ start,
+                                                       const GridPlan* __restrict__ plan,
+                                                       const int32_t* __restrict__ start,
                                                        const int32_t* __restrict__ cell_of, CO co, double r2,
                                                        const uint8_t* __restrict__ core,
                                                        const int* __restrict__ parent,
@@ -750,6 +762,8 @@ __global__ __launch_bounds__(256) void k_labels_border(const int32_t* __restrict
                                                        const int32_t* __restrict__ rank,
                                                        const int32_t* __restrict__ order,
                                                        int64_t* __restrict__ labels) {
+  if (!plan->ok) return;
+  const Stencil st = plan_stencil(plan);
   const int m = *rest_cnt;
   const int lane = threadIdx.x & 63;
   for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < m; i += gridDim.x * 4) {  // wave-uniform
@@ -778,33 +792,16 @@ __global__ __launch_bounds__(256) void k_labels_border(const int32_t* __restrict
   }
 }
 
-static int dbscan_device(Ctx* c, const double* xyz, int64_t n, double eps, int32_t min_pts,
-                         bool radius_inclusive, int64_t* labels, uint8_t* is_core, int64_t* n_clusters) {
-  if (!(eps > 0) || !std::isfinite(eps)) return fail(PYQSM_EINVAL, "eps must be positive");
-  if (n == 0) {
-    if (n_clusters) *n_clusters = 0;
-    return 0;
-  }
-  DevGrid g;
-  SubCells sub;
-  {
-    ProfScope ps(c, "dbscan_bin");
-    // a hair wider than eps: rounding of the cell index can then never put two
-    // points that are within eps of each other two cells apart
-    const char* old = getenv("PYQSM_DBSCAN_BIN");  // "2pass": the round-1 binning (A/B comparisons)
-    if (old && !strcmp(old, "2pass")) {
-      PQ_TRY(build_grid(c, xyz, n, eps * (1.0 + 1.0 / 1048576.0), int64_t(1) << 28, &g));
-      PQ_TRY(subsort_octants(c, &g, n, &sub));
-    } else {
-      PQ_TRY(build_grid_octants(c, xyz, n, eps * (1.0 + 1.0 / 1048576.0), int64_t(1) << 28, &g, &sub));
-    }
-  }
-  if (c->prof >= 1) c->timers["dbscan_f32_records"].launches += g.p4 ? 1 : 0;  // which storage form ran
+// Core flags, union-find and labels over a binned cloud. The kernels read the grid from d_plan.
+// *flag_out: the cluster numbering (flag[n] = the number of clusters once the step has run).
+static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool radius_inclusive, const DevGrid& g,
+                          const SubCells& sub, const GridPlan* d_plan, int64_t* labels, uint8_t* is_core,
+                          int32_t** flag_out) {
   // the sub-cell shortcuts need cells of edge eps (not doubled to fit the dense grid)
   const bool fine = g.cell <= eps * (1.0 + 1.0 / 524288.0);
   const int N = int(n);
   const dim3 grid(ceil_div(n, 256)), block(256);
-  const Stencil st{g.nx, g.nx * g.ny};
+  const Stencil st{g.nx, g.nx * g.ny};  // (host-planned grids only: k_union_points)
   // Every kernel tests d2 <= r2. The STRICT neighbourhood d2 < eps^2 (radius_inclusive = 0: what
   // Open3D's cluster_dbscan computes if nanoflann's radius search compares strictly; SURVEY.md
   // §8 a2) is the same test against the double just below eps^2 — no fp64 value lies between
@@ -826,12 +823,7 @@ static int dbscan_device(Ctx* c, const double* xyz, int64_t n, double eps, int32
   PQ_TRY(c->arena.get(size_t(n), &list_xyz));
   // [0] listed sub-cells, [1] stragglers of the core pass, [2] scratch of the union phase, [3] non-core
   // points of the label pass. The binning leaves four zeroed ints behind for this (no memset launches).
-  if (sub.zeroed4) {
-    list_cnt = sub.zeroed4;
-  } else {
-    PQ_TRY(c->arena.get(4 + kZeroedExtra, &list_cnt));
-    PQ_HIP(hipMemsetAsync(list_cnt, 0, (4 + kZeroedExtra) * 4, c->stream));
-  }
+  list_cnt = sub.zeroed4;
   int32_t* rest;
   // (the core pass's stragglers come in kRestSegs segments of seg_cap entries; the label pass reuses the
   // array as one list of at most n)
@@ -850,10 +842,11 @@ static int dbscan_device(Ctx* c, const double* xyz, int64_t n, double eps, int32
     // serve min_pts = 10, and in proportion beyond
     const int max_chunks = std::min(32, std::max(kMaxChunks, (kMaxChunks * min_pts + 9) / 10));
     {
-      ProfScope pk(c, "k_core_tiled");
+      const ProfKernel pk(c, "k_core_tiled");
       on_coords(g, [&](auto co) {
-        hipLaunchKernelGGL(k_core_tiled<decltype(co)>, grid, block, 0, c->stream, N, st, int(g.ncell), g.start,
-                           g.cell_of, co, r2, min_pts, core, rest, rest_segs, seg_cap, parent, min_orig, flag, max_chunks, d_tests);
+        hipExtLaunchKernelGGL(k_core_tiled<decltype(co)>, grid, block, 0, c->stream, pk.start, pk.stop, 0, N, d_plan,
+                              g.start, g.cell_of, co, r2, min_pts, core, rest, rest_segs, seg_cap, parent, min_orig,
+                              flag, max_chunks, d_tests);
       });
     }
     if (d_tests) {  // profiling level 2 only: read the counter back (synchronises)
@@ -866,7 +859,7 @@ static int dbscan_device(Ctx* c, const double* xyz, int64_t n, double eps, int32
     }
     on_coords(g, [&](auto co) {
       hipLaunchKernelGGL(k_core_rest<decltype(co)>, dim3(std::min<int64_t>(8192, ceil_div(n, 64))), block, 0,
-                         c->stream, rest, rest_segs, seg_cap, st, g.start, g.cell_of, co, r2, min_pts, core);
+                         c->stream, rest, rest_segs, seg_cap, d_plan, g.start, g.cell_of, co, r2, min_pts, core);
     });
     PQ_HIP(hipGetLastError());
   }
@@ -876,7 +869,7 @@ static int dbscan_device(Ctx* c, const double* xyz, int64_t n, double eps, int32
     // the binning left)
     if (fine) {
       hipLaunchKernelGGL(k_sub_rep, dim3(ceil_div(n, 1024)), dim3(1024), 0, c->stream, N, sub.sub_of, core,
-                         g.order, parent, g.cell_of, sub.rec, run_min, list, list_cnt, g.nx, g.ny, list_xyz);
+                         g.order, parent, g.cell_of, sub.rec, run_min, list, list_cnt, d_plan, list_xyz);
       // The number m of listed sub-cells stays on the device: the passes below are launched for the
       // upper bound (a sub-cell holds at least one point, in practice ~5) and read m themselves —
       // waves beyond it leave at once — which spares the host round trip in the middle of the step
@@ -907,10 +900,11 @@ static int dbscan_device(Ctx* c, const double* xyz, int64_t n, double eps, int32
         int32_t* nbr;  // [m][64] representatives of the neighbour sub-cells pass 1 resolved
         PQ_TRY(c->arena.get(size_t(rows) * 64, &nbr));
         {
-          ProfScope pk(c, "k_hook_sub");
+          const ProfKernel pk(c, "k_hook_sub");
           on_coords(g, [&](auto co) {
-            hipLaunchKernelGGL((k_hook_sub<kSubPerWaveDefault, decltype(co)>), gh, block, 0, c->stream, list,
-                               list_xyz, list_cnt, g.nx, g.ny, g.start, sub.rec, co, r2, core, parent, nbr);
+            hipExtLaunchKernelGGL((k_hook_sub<kSubPerWaveDefault, decltype(co)>), gh, block, 0, c->stream, pk.start,
+                                  pk.stop, 0, list, list_xyz, list_cnt, d_plan, g.start, sub.rec, co, r2, core, parent,
+                                  nbr);
           });
         }
         if (getenv("PYQSM_DBSCAN_TRACE")) {  // how deep are the chains the hook pass leaves?
@@ -946,23 +940,23 @@ static int dbscan_device(Ctx* c, const double* xyz, int64_t n, double eps, int32
         // what is left: joining the few trees per cluster. Almost every pair of neighbours
         // now shows the same root through two plain loads.
         {
-          ProfScope pk(c, "k_union_sub");
+          const ProfKernel pk(c, "k_union_sub");
           on_coords(g, [&](auto co) {
-            hipLaunchKernelGGL((k_union_sub<kSubPerWaveDefault, decltype(co)>), gu, block, 0, c->stream, list,
-                               list_cnt, nbr, sub.sub_of, sub.rec, co, r2, core, parent);
+            hipExtLaunchKernelGGL((k_union_sub<kSubPerWaveDefault, decltype(co)>), gu, block, 0, c->stream, pk.start,
+                                  pk.stop, 0, list, list_cnt, nbr, sub.sub_of, sub.rec, co, r2, core, parent);
           });
         }
         hipLaunchKernelGGL(k_rep_min, gl, block, 0, c->stream, list, list_cnt, parent, run_min, min_orig);
       }
       PQ_HIP(hipGetLastError());
-      hipLaunchKernelGGL(k_flatten, grid, block, 0, c->stream, N, core, parent, min_orig, flag);
+      hipLaunchKernelGGL(k_flatten, grid, block, 0, c->stream, N, core, parent, min_orig, flag, d_plan);
     } else {
       on_coords(g, [&](auto co) {
         hipLaunchKernelGGL(k_union_points<decltype(co)>, grid, block, 0, c->stream, N, st, g.start, g.cell_of, co,
                            r2, core, parent);
       });
       hipLaunchKernelGGL(k_flatten, grid, block, 0, c->stream, N, core, parent, static_cast<const int*>(nullptr),
-                         static_cast<int32_t*>(nullptr));
+                         static_cast<int32_t*>(nullptr), d_plan);
       hipLaunchKernelGGL(k_point_min, grid, block, 0, c->stream, N, core, parent, g.order, min_orig);
       hipLaunchKernelGGL(k_mark_roots, grid, block, 0, c->stream, N, core, parent, min_orig, flag);
     }
@@ -972,13 +966,81 @@ static int dbscan_device(Ctx* c, const double* xyz, int64_t n, double eps, int32
   {
     ProfScope ps(c, "dbscan_label");
     hipLaunchKernelGGL(k_labels, dim3(ceil_div(n, 1024)), dim3(1024), 0, c->stream, N, core, parent, min_orig, flag, g.order,
-                       labels, is_core, rest, list_cnt + 3);
+                       labels, is_core, rest, list_cnt + 3, d_plan);
     on_coords(g, [&](auto co) {
       hipLaunchKernelGGL(k_labels_border<decltype(co)>, dim3(std::min<int64_t>(8192, ceil_div(n, 64))), block, 0,
-                         c->stream, rest, list_cnt + 3, st, g.start, g.cell_of, co, r2, core, parent, min_orig,
+                         c->stream, rest, list_cnt + 3, d_plan, g.start, g.cell_of, co, r2, core, parent, min_orig,
                          flag, g.order, labels);
     });
     PQ_HIP(hipGetLastError());
+  }
+  *flag_out = flag;
+  return 0;
+}
+
+
+// The bounding box's fold plans the grid on the device. With a shape hint (the last host-planned call
+// of this context) the whole step is enqueued at once behind it, and the host waits only for the
+// plan's read-back: when the plan fits the hint (ok) the call returns with the step queued and
+// nothing synchronised. Otherwise the enqueued kernels leave without a write, and the step is
+// planned on the host from the box already read back (what every call did before), which also
+// covers axis-compressed and doubled grids, fp64 records, bits = 13 and non-finite input.
+// PYQSM_DBSCAN_PLAN=host: the host plans every call (A/B comparisons). A missed speculation records
+// its (empty) profiling scopes as well.
+static int dbscan_device(Ctx* c, const double* xyz, int64_t n, double eps, int32_t min_pts,
+                         bool radius_inclusive, int64_t* labels, uint8_t* is_core, int64_t* n_clusters) {
+  if (!(eps > 0) || !std::isfinite(eps)) return fail(PYQSM_EINVAL, "eps must be positive");
+  if (n == 0) {
+    if (n_clusters) *n_clusters = 0;
+    return 0;
+  }
+  // a hair wider than eps: rounding of the cell index can then never put two
+  // points that are within eps of each other two cells apart
+  const double cell = eps * (1.0 + 1.0 / 1048576.0);
+  const int64_t max_cells = int64_t(1) << 28;
+  if (!c->plan_pinned) {
+    PQ_HIP(hipHostMalloc(&c->plan_pinned, 2 * sizeof(GridPlan), hipHostMallocDefault));
+    PQ_HIP(hipEventCreateWithFlags(&c->plan_ev, hipEventDisableTiming));
+  }
+  GridPlan* const h_plan = static_cast<GridPlan*>(c->plan_pinned);  // [0] read-back, [1] upload
+  GridPlan* d_plan;  // [0] the fold's, [1] the host's
+  int32_t* zeroed;
+  PQ_TRY(c->arena.get(2, &d_plan));
+  PQ_TRY(c->arena.get(size_t(octant_zeroed_ints()), &zeroed));
+  const char* plan_env = getenv("PYQSM_DBSCAN_PLAN");
+  const char* bin_env = getenv("PYQSM_DBSCAN_BIN");
+  const char* f32_env = getenv("PYQSM_COORD_F32");
+  // (clouds beyond 2^25 points read the sub-cell count back in the union phase: planned on the host)
+  const bool speculate = c->plan_hint.valid && !(plan_env && !strcmp(plan_env, "host")) && !bin_env &&
+                         !(f32_env && !strcmp(f32_env, "0")) && n <= (int64_t(1) << 25);
+  const PlanHint hint = speculate ? c->plan_hint : PlanHint{};
+  DevGrid g;
+  SubCells sub;
+  int32_t* flag = nullptr;
+  std::optional<ProfScope> bin_scope(std::in_place, c, "dbscan_bin");
+  PQ_TRY(plan_grid_device(c, xyz, n, cell, max_cells, hint, d_plan, h_plan, c->plan_ev, zeroed, octant_zeroed_ints()));
+  const Arena::Mark mark = c->arena.mark();
+  if (speculate) {
+    PQ_TRY(bin_octants_planned(c, xyz, n, cell, hint, d_plan, zeroed, &g, &sub));
+    bin_scope.reset();
+    PQ_TRY(cluster_binned(c, n, eps, min_pts, radius_inclusive, g, sub, d_plan, labels, is_core, &flag));
+  }
+  PQ_HIP(hipEventSynchronize(c->plan_ev));
+  const bool hit = speculate && h_plan[0].ok;
+  if (!hit) {
+    // planned on the host; the kernels enqueued above (if any) left without a write, so their
+    // scratch memory can be handed out again
+    c->arena.rewind(mark);
+    PlanHint next;
+    if (!bin_scope) bin_scope.emplace(c, "dbscan_bin");
+    PQ_TRY(bin_octants_host(c, xyz, n, cell, max_cells, h_plan[0], zeroed, &h_plan[1], d_plan + 1, &g, &sub, &next));
+    bin_scope.reset();
+    if (next.valid) c->plan_hint = next;  // (a grid of another kind keeps the hint there is)
+    PQ_TRY(cluster_binned(c, n, eps, min_pts, radius_inclusive, g, sub, d_plan + 1, labels, is_core, &flag));
+  }
+  if (c->prof >= 1) {
+    c->timers["dbscan_f32_records"].launches += g.p4 ? 1 : 0;  // which storage form ran
+    c->timers[hit ? "dbscan_plan_hit" : "dbscan_plan_miss"].launches += 1;  // which planning ran
   }
   if (n_clusters) {
     int32_t h = 0;

@@ -79,10 +79,20 @@ __global__ __launch_bounds__(256) void k_bbox(const double* __restrict__ xyz, in
 // One block folds the per-block records (the fp32 flag as a minimum: 0 wins) and, while it is
 // there, clears `zero_n` ints for the caller (the bucket counters of the binning that follows:
 // two memset launches less on the critical path).
+// With `plan` (DBSCAN), the fold also writes the grid plan of edge `cell` (see plan_grid_device).
+struct PlanIn {
+  double cell;
+  int64_t max_cells;
+  PlanHint hint;
+};
+__device__ void write_plan(const unsigned long long* box, const PlanIn& in, GridPlan* __restrict__ plan);
+
 __global__ __launch_bounds__(256) void k_bbox_fold(const unsigned long long* __restrict__ part,
                                                    int nblk, unsigned long long* __restrict__ out,
-                                                   int32_t* __restrict__ zero_buf, int zero_n) {
+                                                   int32_t* __restrict__ zero_buf, int zero_n,
+                                                   PlanIn pin, GridPlan* __restrict__ plan) {
   __shared__ unsigned long long red[4][kBoxVals];
+  __shared__ unsigned long long fin[kBoxVals];
   for (int q = threadIdx.x; q < zero_n; q += 256) zero_buf[q] = 0;
   unsigned long long v[kBoxVals] = {~0ull, ~0ull, ~0ull, 0, 0, 0, ~0ull};
   for (int b = threadIdx.x; b < nblk; b += 256)
@@ -110,6 +120,11 @@ __global__ __launch_bounds__(256) void k_bbox_fold(const unsigned long long* __r
       r = is_min ? (o < r ? o : r) : (o > r ? o : r);
     }
     out[threadIdx.x] = r;
+    fin[threadIdx.x] = r;
+  }
+  if (plan) {  // kernel-uniform
+    __syncthreads();
+    if (threadIdx.x == 0) write_plan(fin, pin, plan);
   }
 }
 
@@ -346,7 +361,8 @@ int cloud_bbox(Ctx* c, const double* xyz, int64_t n, double mn[3], double mx[3],
   PQ_TRY(c->arena.get(kBoxVals, &d_box));
   PQ_TRY(c->arena.get(size_t(blocks) * kBoxVals, &d_part));
   hipLaunchKernelGGL(k_bbox, dim3(blocks), dim3(256), 0, c->stream, xyz, n, d_part);
-  hipLaunchKernelGGL(k_bbox_fold, dim3(1), dim3(256), 0, c->stream, d_part, blocks, d_box, zero_buf, zero_n);
+  hipLaunchKernelGGL(k_bbox_fold, dim3(1), dim3(256), 0, c->stream, d_part, blocks, d_box, zero_buf, zero_n, PlanIn{},
+                     static_cast<GridPlan*>(nullptr));
   PQ_HIP(hipGetLastError());
   unsigned long long h_box[kBoxVals];
   PQ_HIP(hipMemcpyAsync(h_box, d_box, sizeof(h_box), hipMemcpyDeviceToHost, c->stream));
@@ -709,9 +725,10 @@ __global__ __launch_bounds__(256) void k_order_big(const int32_t* __restrict__ b
                                                    double* __restrict__ sz, float4* __restrict__ p4,
                                                    int32_t* __restrict__ sub_cnt,
                                                    int32_t* __restrict__ sub_beg,
-                                                   int4* __restrict__ rec) {
+                                                   int4* __restrict__ rec, const GridPlan* __restrict__ plan) {
   __shared__ int tot[8], base[8], wcnt[4][8];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (!plan->ok) return;
   const int nbig = *big_cnt;  // usually 0: the launch is then a few idle blocks
   for (int bi = blockIdx.x; bi < nbig; bi += gridDim.x) {  // block-uniform
   const int c = big_list[bi];
@@ -816,8 +833,17 @@ template <int MODE>
 __global__ __launch_bounds__(256) void k_bk_hist(const double* __restrict__ xyz, int64_t n, GridParams g,
                                                  int rx, int ry, int rz, AxisMap am, int nbk, int bits,
                                                  int32_t* __restrict__ key_tmp,
-                                                 int32_t* __restrict__ tot) {
+                                                 int32_t* __restrict__ tot, const GridPlan* __restrict__ plan) {
   extern __shared__ __attribute__((aligned(16))) int32_t h[];
+  if (plan) {  // DBSCAN: the grid comes from the plan (the LDS was sized for at least its nbk)
+    if (!plan->ok) return;
+    g = GridParams{plan->mn[0], plan->mn[1], plan->mn[2], plan->inv_cell, plan->nx, plan->ny, plan->nz};
+    rx = plan->rx;
+    ry = plan->ry;
+    rz = plan->rz;
+    nbk = plan->nbk;
+    bits = plan->bits;
+  }
   for (int b = threadIdx.x; b < nbk; b += 256) h[b] = 0;
   __syncthreads();
   const int64_t base = int64_t(blockIdx.x) * kBkPts;
@@ -850,8 +876,12 @@ __global__ __launch_bounds__(256) void k_bk_hist(const double* __restrict__ xyz,
 // buckets; up to kBkFusedScan buckets every block of k_bk_scatter scans the totals itself instead.
 static constexpr int kBkFusedScan = 4096;
 __global__ __launch_bounds__(1024) void k_bk_scan(int nbk, const int32_t* __restrict__ tot,
-                                                  int32_t* __restrict__ bstart) {
+                                                  int32_t* __restrict__ bstart, const GridPlan* __restrict__ plan) {
   __shared__ int32_t wsum[16];
+  if (plan) {
+    if (!plan->ok) return;
+    nbk = plan->nbk;
+  }
   const int per = (nbk + 1023) / 1024;  // <= 16
   const int b0 = threadIdx.x * per;
   int32_t v[16], s = 0;
@@ -883,8 +913,14 @@ __global__ __launch_bounds__(256) void k_bk_scatter(const double* __restrict__ x
                                                     int32_t* __restrict__ cursor /*zeroed*/,
                                                     int32_t* __restrict__ bstart /*[nbk + 1]: written by block 0
                                                     (fused) or read (scanned by k_bk_scan)*/,
-                                                    int fused, PointRec* __restrict__ bucketed) {
+                                                    int fused, PointRec* __restrict__ bucketed,
+                                                    const GridPlan* __restrict__ plan) {
   extern __shared__ __attribute__((aligned(16))) int32_t h[];  // [nbk] ranks / shares (+ [nbk] bucket starts: fused)
+  if (plan) {
+    if (!plan->ok) return;
+    nbk = plan->nbk;
+    bits = plan->bits;
+  }
   int32_t* pre = h + nbk;
   __shared__ int32_t wsum[4];
   for (int b = threadIdx.x; b < nbk; b += 256) h[b] = 0;
@@ -971,10 +1007,13 @@ __global__ __launch_bounds__((1 << BITS) / 8) void k_bk_sort(
     int32_t* __restrict__ start, int32_t* __restrict__ order, int32_t* __restrict__ cell_of,
     int32_t* __restrict__ sub_of, double* __restrict__ sx, double* __restrict__ sy, double* __restrict__ sz,
     float4* __restrict__ p4 /*non-null: fp32 records instead of sx / sy / sz*/, int4* __restrict__ rec,
-    PointRec* __restrict__ keyed, int32_t* __restrict__ big_list, int32_t* __restrict__ big_cnt) {
+    PointRec* __restrict__ keyed, int32_t* __restrict__ big_list, int32_t* __restrict__ big_cnt,
+    const GridPlan* __restrict__ plan /*ncell1 and the number of buckets (the launch may have more blocks)*/) {
   constexpr int CELLS = 1 << BITS, T = CELLS / 8;
   __shared__ BkLds<BITS> L;
   const int bk = blockIdx.x, t = threadIdx.x;
+  if (!plan->ok || bk >= plan->nbk) return;
+  ncell1 = int64_t(plan->ncell) + 1;
   const int s = bstart[bk], e = bstart[bk + 1];
   const int64_t c0 = int64_t(bk) << BITS;  // first cell (directory entry) of the bucket
   if (s == e) {  // nothing in the bucket: its directory entries all say "the next point is s"
@@ -1267,10 +1306,12 @@ static int build_grid_bucketed(Ctx* c, const double* xyz, int64_t n, DevGrid* g)
   const size_t lds = size_t(nbk) * 4;
   const int fused = nbk <= kBkFusedScan;
   hipLaunchKernelGGL(k_bk_hist<2>, ga, blk, lds, c->stream, xyz, n, gp, 0, 0, 0, AxisMap{nullptr, nullptr, nullptr},
-                     int(nbk), bits, key_tmp, tot);
-  if (!fused) hipLaunchKernelGGL(k_bk_scan, dim3(1), dim3(1024), 0, c->stream, int(nbk), tot, bstart);
+                     int(nbk), bits, key_tmp, tot, static_cast<const GridPlan*>(nullptr));
+  if (!fused)
+    hipLaunchKernelGGL(k_bk_scan, dim3(1), dim3(1024), 0, c->stream, int(nbk), tot, bstart,
+                       static_cast<const GridPlan*>(nullptr));
   hipLaunchKernelGGL(k_bk_scatter, ga, blk, fused ? 2 * lds : lds, c->stream, xyz, n, int(nbk), bits, key_tmp, tot,
-                     cursor, bstart, fused, bucketed);
+                     cursor, bstart, fused, bucketed, static_cast<const GridPlan*>(nullptr));
   if (bits == 12)
     hipLaunchKernelGGL(k_bk_sort_plain<12>, dim3(unsigned(nbk)), dim3(512), 0, c->stream, g->ncell + 1, bstart,
                        bucketed, rank_tmp, g->start, g->order, g->cell_of, g->sx, g->sy, g->sz, g->p4, g->occ_part);
@@ -1281,25 +1322,193 @@ static int build_grid_bucketed(Ctx* c, const double* xyz, int64_t n, DevGrid* g)
   return 0;
 }
 
-int build_grid_octants(Ctx* c, const double* xyz, int64_t n, double min_cell, int64_t max_cells,
-                       DevGrid* g, SubCells* sub) {
+// ---- DBSCAN's grid plan ---------------------------------------------------------------------------
+
+__device__ __forceinline__ double ord_val_dev(unsigned long long k) {
+  const unsigned long long b = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
+  return __longlong_as_double(static_cast<long long>(b));
+}
+
+// bin_octants_host's first trial in the same fp64 operations (floor((mx - mn) / cell) + 1 interior
+// slabs, + 2 border slabs, the same bucket rounding), so that every point lands in the same cell
+__device__ void write_plan(const unsigned long long* box, const PlanIn& in, GridPlan* __restrict__ plan) {
+  GridPlan p;
+  bool ok = in.hint.valid != 0;
+  for (int a = 0; a < 3; ++a) {
+    p.mn[a] = ord_val_dev(box[a]);
+    p.mx[a] = ord_val_dev(box[3 + a]);
+    ok = ok && isfinite(p.mn[a]) && isfinite(p.mx[a]);
+  }
+  p.all_f32 = box[6] != 0 ? 1 : 0;
+  ok = ok && p.all_f32;
+  double tot = 1.0;
+  int raw[3];
+  for (int a = 0; a < 3; ++a) {
+    const double d = floor((p.mx[a] - p.mn[a]) / in.cell) + 1.0;
+    if (!(d < 2.0e9)) ok = false;
+    raw[a] = ok ? int(d) : 0;
+    tot *= d + 2.0;
+  }
+  ok = ok && tot <= double(in.max_cells);  // beyond: compressed axes or a doubled cell, which the host plans
+  p.inv_cell = 1.0 / in.cell;
+  p.rx = raw[0];
+  p.ry = raw[1];
+  p.rz = raw[2];
+  p.nx = raw[0] + 2;
+  p.ny = raw[1] + 2;
+  p.nz = raw[2] + 2;
+  const int64_t ncell = ok ? int64_t(p.nx) * p.ny * p.nz : 0;
+  const int64_t nbk = (ncell + 4096) >> 12;
+  ok = ok && ncell + 1 <= (int64_t(kBkMax) << 12) && ncell <= in.hint.ncell && nbk <= in.hint.nbk &&
+       (nbk <= kBkFusedScan) == (in.hint.fused != 0);
+  p.ncell = ok ? int(ncell) : 0;
+  p.nbk = ok ? int(nbk) : 0;
+  p.bits = 12;
+  p.ok = ok ? 1 : 0;
+  *plan = p;
+}
+
+int plan_grid_device(Ctx* c, const double* xyz, int64_t n, double cell, int64_t max_cells, const PlanHint& hint,
+                     GridPlan* d_plan, GridPlan* h_plan, hipEvent_t ev, int32_t* zero_buf, int zero_n) {
+  if (n <= 0) return fail(PYQSM_EINVAL, "bounding box of an empty cloud");
+  const int blocks = int(std::min<int64_t>(ceil_div(n, 256), int64_t(c->cu_count) * 4));
+  unsigned long long *d_box = nullptr, *d_part = nullptr;
+  PQ_TRY(c->arena.get(kBoxVals, &d_box));
+  PQ_TRY(c->arena.get(size_t(blocks) * kBoxVals, &d_part));
+  hipLaunchKernelGGL(k_bbox, dim3(blocks), dim3(256), 0, c->stream, xyz, n, d_part);
+  hipLaunchKernelGGL(k_bbox_fold, dim3(1), dim3(256), 0, c->stream, d_part, blocks, d_box, zero_buf, zero_n,
+                     PlanIn{cell, max_cells, hint}, d_plan);
+  PQ_HIP(hipGetLastError());
+  PQ_HIP(hipMemcpyAsync(h_plan, d_plan, sizeof(GridPlan), hipMemcpyDeviceToHost, c->stream));
+  PQ_HIP(hipEventRecord(ev, c->stream));
+  return 0;
+}
+
+// layout: [kBkMax totals | kBkMax reservation cursors | big-cell counter | four zeros for the caller
+// | kZeroedExtra more]
+int octant_zeroed_ints() { return 2 * kBkMax + 5 + kZeroedExtra; }
+
+// The output arrays of the octant binning and the two-level sort's launches, for a directory of at
+// most ncell cells in nbk buckets (the plan's exact numbers, or the hint's bounds); the kernels
+// read the grid itself from d_plan.
+static int enqueue_bucketed(Ctx* c, const double* xyz, int64_t n, const GridParams& gp, const int raw[3],
+                            AxisMap am, bool mapped, int64_t ncell, int64_t nbk, int bits, bool f32,
+                            int32_t* zeroed, const GridPlan* d_plan, DevGrid* g, SubCells* sub) {
+  int32_t *cell_tmp, *rank_tmp, *big_list, *bstart;
+  int32_t *tot = zeroed, *cursor = zeroed + kBkMax, *big_cnt = zeroed + 2 * kBkMax;
+  PointRec *keyed, *bucketed;
+  uint8_t* oct_rank;
+  g->p4 = nullptr;
+  g->sx = g->sy = g->sz = nullptr;
+  PQ_TRY(c->arena.get(size_t(ncell) + 1, &g->start));
+  PQ_TRY(c->arena.get(size_t(n), &g->order));
+  PQ_TRY(c->arena.get(size_t(n), &g->cell_of));
+  if (f32) {
+    PQ_TRY(c->arena.get(size_t(n), &g->p4));
+  } else {
+    PQ_TRY(c->arena.get(size_t(n), &g->sx));
+    PQ_TRY(c->arena.get(size_t(n), &g->sy));
+    PQ_TRY(c->arena.get(size_t(n), &g->sz));
+  }
+  PQ_TRY(c->arena.get(size_t(n), &cell_tmp));
+  PQ_TRY(c->arena.get(size_t(n), &rank_tmp));
+  PQ_TRY(c->arena.get(size_t(n), &keyed));
+  PQ_TRY(c->arena.get(size_t(n) * 8, &sub->sub_cnt));
+  PQ_TRY(c->arena.get(size_t(n) * 8, &sub->sub_beg));
+  PQ_TRY(c->arena.get(size_t(n), &sub->sub_of));
+  PQ_TRY(c->arena.get(size_t(n) * 8, &sub->rec));
+  PQ_TRY(c->arena.get(size_t(n) / kBigCell + 2, &big_list));
+  PQ_TRY(c->arena.get(size_t(nbk) + 1, &bstart));
+  PQ_TRY(c->arena.get(size_t(n), &oct_rank));
+  PQ_TRY(c->arena.get(size_t(n), &bucketed));
+  const dim3 ga(ceil_div(n, kBkPts)), blk(256);
+  const size_t lds = size_t(nbk) * 4;
+  if (mapped)
+    hipLaunchKernelGGL(k_bk_hist<1>, ga, blk, lds, c->stream, xyz, n, gp, raw[0], raw[1], raw[2], am, int(nbk), bits,
+                       cell_tmp, tot, d_plan);
+  else
+    hipLaunchKernelGGL(k_bk_hist<0>, ga, blk, lds, c->stream, xyz, n, gp, raw[0], raw[1], raw[2], am, int(nbk), bits,
+                       cell_tmp, tot, d_plan);
+  const int fused = nbk <= kBkFusedScan;
+  if (!fused) hipLaunchKernelGGL(k_bk_scan, dim3(1), dim3(1024), 0, c->stream, int(nbk), tot, bstart, d_plan);
+  hipLaunchKernelGGL(k_bk_scatter, ga, blk, fused ? 2 * lds : lds, c->stream, xyz, n, int(nbk), bits, cell_tmp, tot,
+                     cursor, bstart, fused, bucketed, d_plan);
+  if (bits == 12)
+    hipLaunchKernelGGL(k_bk_sort<12>, dim3(unsigned(nbk)), dim3(512), 0, c->stream, ncell + 1, bstart, bucketed,
+                       rank_tmp, oct_rank, g->start, g->order, g->cell_of, sub->sub_of, g->sx, g->sy, g->sz, g->p4,
+                       sub->rec, keyed, big_list, big_cnt, d_plan);
+  else
+    hipLaunchKernelGGL(k_bk_sort<13>, dim3(unsigned(nbk)), dim3(1024), 0, c->stream, ncell + 1, bstart, bucketed,
+                       rank_tmp, oct_rank, g->start, g->order, g->cell_of, sub->sub_of, g->sx, g->sy, g->sz, g->p4,
+                       sub->rec, keyed, big_list, big_cnt, d_plan);
+  PQ_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_order_big, dim3(unsigned(std::min<int64_t>(n / kBigCell + 1, 2048))), blk, 0, c->stream,
+                     big_list, big_cnt, g->start, keyed, g->order, g->cell_of, sub->sub_of, g->sx, g->sy, g->sz, g->p4,
+                     sub->sub_cnt, sub->sub_beg, sub->rec, d_plan);
+  PQ_HIP(hipGetLastError());
+  return 0;
+}
+
+int bin_octants_planned(Ctx* c, const double* xyz, int64_t n, double cell, const PlanHint& hint,
+                        const GridPlan* d_plan, int32_t* zeroed, DevGrid* g, SubCells* sub) {
+  // the host knows the edge (never doubled on this path) and the bounds of the directory, not its shape
+  g->minx = g->miny = g->minz = 0.0;
+  g->cell = cell;
+  g->inv_cell = 1.0 / cell;
+  g->nx = g->ny = g->nz = 0;
+  g->ncell = hint.ncell;
+  sub->zeroed4 = zeroed + 2 * kBkMax + 1;
+  const int raw[3] = {0, 0, 0};
+  return enqueue_bucketed(c, xyz, n, GridParams{}, raw, AxisMap{nullptr, nullptr, nullptr}, false, hint.ncell,
+                          hint.nbk, 12, true, zeroed, d_plan, g, sub);
+}
+
+static int upload_plan(Ctx* c, const GridPlan& p, GridPlan* h_up, GridPlan* d_plan) {
+  *h_up = p;  // the previous call's upload has run: the host waited on an event recorded after it
+  PQ_HIP(hipMemcpyAsync(d_plan, h_up, sizeof(GridPlan), hipMemcpyHostToDevice, c->stream));
+  return 0;
+}
+
+// Extents that would need more than `max_cells` cells of edge `min_cell` are first COMPRESSED
+// per axis: runs of empty slabs collapse to one empty slab, which keeps exactly the adjacencies
+// the 27-cell stencil and the sub-cell offsets use (two points in neighbouring slabs stay in
+// neighbouring slabs, all others end up at least one empty slab apart). Only if the compressed
+// grid is still too large is the edge doubled (g->cell > min_cell tells the caller).
+int bin_octants_host(Ctx* c, const double* xyz, int64_t n, double min_cell, int64_t max_cells, const GridPlan& box,
+                     int32_t* zeroed, GridPlan* h_up, GridPlan* d_plan, DevGrid* g, SubCells* sub,
+                     PlanHint* hint_out) {
+  *hint_out = PlanHint{};
   if (n <= 0) return fail(PYQSM_EINVAL, "build_grid_octants: empty cloud");
   if (n > (int64_t(1) << 27)) return fail(PYQSM_ERANGE, "octant sub-cells: more than 2^27 points");
   if (max_cells > (int64_t(1) << 28)) max_cells = int64_t(1) << 28;  // cell * 8 + octant in 31 bits
   if (!(min_cell > 0) || !std::isfinite(min_cell))
     return fail(PYQSM_EINVAL, "cell edge must be positive and finite");
   double mn[3], mx[3];
-  // the bucket totals and the big-cell counter of the two-level sort below: cleared by the
-  // bounding box's fold kernel on its way (two memset launches less)
-  // layout: [kBkMax totals | kBkMax reservation cursors | big-cell counter | four spare zeros for the caller]
-  int32_t* tot_big = nullptr;
-  PQ_TRY(c->arena.get(size_t(2 * kBkMax) + 5 + kZeroedExtra, &tot_big));
-  bool all_f32 = false;
-  PQ_TRY(cloud_bbox(c, xyz, n, mn, mx, &all_f32, tot_big, 2 * kBkMax + 5 + kZeroedExtra));
-  sub->zeroed4 = tot_big + 2 * kBkMax + 1;
+  for (int a = 0; a < 3; ++a) {
+    mn[a] = box.mn[a];
+    mx[a] = box.mx[a];
+    if (!std::isfinite(mn[a]) || !std::isfinite(mx[a])) return fail(PYQSM_EINVAL, "point coordinates must be finite");
+  }
+  bool all_f32 = box.all_f32 != 0;
+  sub->zeroed4 = zeroed + 2 * kBkMax + 1;
+  GridPlan hp{};
   {
     const char* f32_env = getenv("PYQSM_COORD_F32");  // "0": keep fp64 storage (A/B comparisons)
     if (f32_env && !strcmp(f32_env, "0")) all_f32 = false;
+  }
+  const char* bin_env = getenv("PYQSM_DBSCAN_BIN");
+  if (bin_env && !strcmp(bin_env, "2pass")) {  // the round-1 binning (A/B comparisons)
+    const double bbox[6] = {mn[0], mn[1], mn[2], mx[0], mx[1], mx[2]};
+    PQ_TRY(build_grid(c, xyz, n, min_cell, max_cells, g, bbox));
+    int32_t* zeroed4 = sub->zeroed4;
+    PQ_TRY(subsort_octants(c, g, n, sub));
+    sub->zeroed4 = zeroed4;
+    hp.nx = g->nx;
+    hp.ny = g->ny;
+    hp.nz = g->nz;
+    hp.ncell = int(g->ncell);
+    hp.ok = 1;
+    return upload_plan(c, hp, h_up, d_plan);
   }
   const dim3 grid(ceil_div(n, 256)), blk(256);
   double cell = min_cell;
@@ -1361,28 +1570,53 @@ int build_grid_octants(Ctx* c, const double* xyz, int64_t n, double min_cell, in
   g->ny = dims[1];
   g->nz = dims[2];
   g->ncell = int64_t(dims[0]) * dims[1] * dims[2];
-  int32_t *cell_tmp, *rank_tmp, *big_list, *big_cnt;
-  PointRec* keyed;
   // Two-level counting sort (k_bk_*): no scattered global atomics, the directory written once.
   // PYQSM_DBSCAN_BIN=atomic keeps round 2's one-atomic-per-point path (A/B comparisons); grids of
   // more than kBkMax buckets (2^27 cells) keep it too.
   const int bits = g->ncell + 1 <= (int64_t(kBkMax) << 12) ? 12 : 13;
   const int64_t nbk = (g->ncell + (int64_t(1) << bits)) >> bits;  // ceil((ncell + 1) / bucket)
-  const char* bin_env = getenv("PYQSM_DBSCAN_BIN");
   const bool bucketed_path = nbk <= kBkMax && !(bin_env && !strcmp(bin_env, "atomic"));
-  // fp32 records when the input allows it (round 2's path keeps fp64 arrays)
+  for (int a = 0; a < 3; ++a) {
+    hp.mn[a] = mn[a];
+    hp.mx[a] = mx[a];
+  }
+  hp.inv_cell = g->inv_cell;
+  hp.nx = dims[0];
+  hp.ny = dims[1];
+  hp.nz = dims[2];
+  hp.rx = raw[0];
+  hp.ry = raw[1];
+  hp.rz = raw[2];
+  hp.ncell = int(g->ncell);
+  hp.nbk = int(nbk);
+  hp.bits = bits;
+  hp.all_f32 = all_f32 && bucketed_path;  // fp32 records (round 2's path keeps fp64 arrays)
+  hp.ok = 1;
+  PQ_TRY(upload_plan(c, hp, h_up, d_plan));
+  GridParams gp{g->minx, g->miny, g->minz, g->inv_cell, g->nx, g->ny, g->nz};
+  if (bucketed_path) {
+    PQ_TRY(enqueue_bucketed(c, xyz, n, gp, raw, am, mapped, g->ncell, nbk, bits, hp.all_f32, zeroed, d_plan, g, sub));
+    // the kind of grid the bounding box's fold can plan: a hint with some headroom on the directory
+    // (the same bucket size and the same side of the fused-scan threshold)
+    if (!mapped && cell == min_cell && bits == 12 && hp.all_f32) {
+      int64_t ncell_h = std::min<int64_t>(g->ncell + g->ncell / 16, (int64_t(kBkMax) << 12) - 1);
+      if (nbk <= kBkFusedScan) ncell_h = std::min<int64_t>(ncell_h, (int64_t(kBkFusedScan) << 12) - 1);
+      hint_out->valid = 1;
+      hint_out->ncell = int(ncell_h);
+      hint_out->nbk = int((ncell_h + 4096) >> 12);
+      hint_out->fused = nbk <= kBkFusedScan;
+    }
+    return 0;
+  }
+  int32_t *cell_tmp, *rank_tmp, *big_list, *big_cnt = zeroed + 2 * kBkMax;
+  PointRec* keyed;
   g->p4 = nullptr;
-  g->sx = g->sy = g->sz = nullptr;
   PQ_TRY(c->arena.get(size_t(g->ncell) + 1, &g->start));
   PQ_TRY(c->arena.get(size_t(n), &g->order));
   PQ_TRY(c->arena.get(size_t(n), &g->cell_of));
-  if (all_f32 && bucketed_path) {
-    PQ_TRY(c->arena.get(size_t(n), &g->p4));
-  } else {
-    PQ_TRY(c->arena.get(size_t(n), &g->sx));
-    PQ_TRY(c->arena.get(size_t(n), &g->sy));
-    PQ_TRY(c->arena.get(size_t(n), &g->sz));
-  }
+  PQ_TRY(c->arena.get(size_t(n), &g->sx));
+  PQ_TRY(c->arena.get(size_t(n), &g->sy));
+  PQ_TRY(c->arena.get(size_t(n), &g->sz));
   PQ_TRY(c->arena.get(size_t(n), &cell_tmp));
   PQ_TRY(c->arena.get(size_t(n), &rank_tmp));
   PQ_TRY(c->arena.get(size_t(n), &keyed));
@@ -1391,42 +1625,6 @@ int build_grid_octants(Ctx* c, const double* xyz, int64_t n, double min_cell, in
   PQ_TRY(c->arena.get(size_t(n), &sub->sub_of));
   PQ_TRY(c->arena.get(size_t(n) * 8, &sub->rec));
   PQ_TRY(c->arena.get(size_t(n) / kBigCell + 2, &big_list));
-  big_cnt = tot_big + 2 * kBkMax;
-  GridParams gp{g->minx, g->miny, g->minz, g->inv_cell, g->nx, g->ny, g->nz};
-  if (bucketed_path) {
-    int32_t *tot = tot_big, *bstart, *cursor = tot_big + kBkMax;
-    uint8_t* oct_rank;
-    PointRec* bucketed;
-    PQ_TRY(c->arena.get(size_t(nbk) + 1, &bstart));
-    PQ_TRY(c->arena.get(size_t(n), &oct_rank));
-    PQ_TRY(c->arena.get(size_t(n), &bucketed));
-    const dim3 ga(ceil_div(n, kBkPts));
-    const size_t lds = size_t(nbk) * 4;
-    if (mapped)
-      hipLaunchKernelGGL(k_bk_hist<1>, ga, blk, lds, c->stream, xyz, n, gp, raw[0], raw[1], raw[2], am,
-                         int(nbk), bits, cell_tmp, tot);
-    else
-      hipLaunchKernelGGL(k_bk_hist<0>, ga, blk, lds, c->stream, xyz, n, gp, raw[0], raw[1], raw[2], am,
-                         int(nbk), bits, cell_tmp, tot);
-    const int fused = nbk <= kBkFusedScan;
-    if (!fused) hipLaunchKernelGGL(k_bk_scan, dim3(1), dim3(1024), 0, c->stream, int(nbk), tot, bstart);
-    hipLaunchKernelGGL(k_bk_scatter, ga, blk, fused ? 2 * lds : lds, c->stream, xyz, n, int(nbk), bits, cell_tmp, tot,
-                       cursor, bstart, fused, bucketed);
-    if (bits == 12)
-      hipLaunchKernelGGL(k_bk_sort<12>, dim3(unsigned(nbk)), dim3(512), 0, c->stream, g->ncell + 1, bstart,
-                         bucketed, rank_tmp, oct_rank, g->start, g->order, g->cell_of, sub->sub_of, g->sx, g->sy,
-                         g->sz, g->p4, sub->rec, keyed, big_list, big_cnt);
-    else
-      hipLaunchKernelGGL(k_bk_sort<13>, dim3(unsigned(nbk)), dim3(1024), 0, c->stream, g->ncell + 1, bstart,
-                         bucketed, rank_tmp, oct_rank, g->start, g->order, g->cell_of, sub->sub_of, g->sx, g->sy,
-                         g->sz, g->p4, sub->rec, keyed, big_list, big_cnt);
-    PQ_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_order_big, dim3(unsigned(std::min<int64_t>(n / kBigCell + 1, 2048))), blk, 0,
-                       c->stream, big_list, big_cnt, g->start, keyed, g->order, g->cell_of, sub->sub_of,
-                       g->sx, g->sy, g->sz, g->p4, sub->sub_cnt, sub->sub_beg, sub->rec);
-    PQ_HIP(hipGetLastError());
-    return 0;
-  }
   PQ_HIP(hipMemsetAsync(g->start, 0, (size_t(g->ncell) + 1) * 4, c->stream));
   if (mapped)
     hipLaunchKernelGGL(k_cell_count_oct<true>, grid, blk, 0, c->stream, xyz, n, gp, raw[0], raw[1], raw[2],
@@ -1445,7 +1643,7 @@ int build_grid_octants(Ctx* c, const double* xyz, int64_t n, double min_cell, in
   // grid reads their number on the device, so that no host round trip is needed
   hipLaunchKernelGGL(k_order_big, dim3(unsigned(std::min<int64_t>(n / kBigCell + 1, 2048))), blk, 0,
                      c->stream, big_list, big_cnt, g->start, keyed, g->order, g->cell_of, sub->sub_of,
-                     g->sx, g->sy, g->sz, g->p4, sub->sub_cnt, sub->sub_beg, sub->rec);
+                     g->sx, g->sy, g->sz, g->p4, sub->sub_cnt, sub->sub_beg, sub->rec, d_plan);
   PQ_HIP(hipGetLastError());
   return 0;
 }

@@ -201,8 +201,8 @@ struct SubCells {
   int32_t* sub_beg;  // [8 n]
   int32_t* sub_of;   // [n] sub-cell id of each sorted position
   int4* rec;         // [8 n] (sub_beg, sub_cnt, -1, 0) in one 16-byte record; .z is the caller's
-  // build_grid_octants only: four ints the binning's own kernels left zeroed, for the caller's
-  // counters (spares DBSCAN two memset launches per step); nullptr from subsort_octants
+  // bin_octants_*: four ints the bounding box's fold left zeroed, for the caller's counters
+  // (spares DBSCAN two memset launches per step); nullptr from subsort_octants
   // (+ kZeroedExtra more zeroed ints behind the four: DBSCAN's segmented list counters)
   int32_t* zeroed4 = nullptr;
 };
@@ -221,8 +221,46 @@ int subsort_octants(Ctx* c, DevGrid* g, int64_t n, SubCells* sub);
 // the 27-cell stencil and the sub-cell offsets use (two points in neighbouring slabs stay in
 // neighbouring slabs, all others end up at least one empty slab apart). Only if the compressed
 // grid is still too large is the edge doubled (g->cell > min_cell tells the caller).
-int build_grid_octants(Ctx* c, const double* xyz, int64_t n, double min_cell, int64_t max_cells,
-                       DevGrid* g, SubCells* sub);
+// DBSCAN builds it in two steps, declared below: plan_grid_device (bounding box and plan), then
+// bin_octants_planned (the plan read on the device) or bin_octants_host (planned on the host).
+
+// ---- DBSCAN's grid plan on the device --------------------------------------------------------
+// The grid DBSCAN bins with, as the kernels of its step read it (once per wave, scalar loads). The
+// bounding box's fold kernel writes it from the box with the host's own arithmetic; the host writes
+// it when it plans (axis-compressed or doubled grids, fp64 records, bits = 13, the atomic binning).
+// ok == 0: every kernel that reads the plan leaves at once and writes nothing.
+struct GridPlan {
+  double mn[3], mx[3];  // the bounding box (mn is the grid's origin)
+  double inv_cell;
+  int nx, ny, nz;  // including the border cells
+  int rx, ry, rz;  // interior slabs before axis compression (nx - 2 ... when there is none)
+  int ncell;       // nx * ny * nz
+  int nbk, bits;   // buckets of 2^bits cells of the two-level sort
+  int all_f32;     // every coordinate is exactly representable in fp32
+  int ok;
+};
+__device__ __forceinline__ Stencil plan_stencil(const GridPlan* p) { return Stencil{p->nx, p->nx * p->ny}; }
+// (PlanHint, the launch shapes a device-planned call is enqueued with, lives in common.hpp: the
+// context keeps the last one.)
+
+// k_bbox + the fold, which writes the plan of a grid of edge `cell` (at most `max_cells` cells)
+// into d_plan, clears zero_n ints of zero_buf, and an asynchronous copy of the plan into h_plan
+// (page-locked) followed by `ev`. Does not synchronise.
+int plan_grid_device(Ctx* c, const double* xyz, int64_t n, double cell, int64_t max_cells, const PlanHint& hint,
+                     GridPlan* d_plan, GridPlan* h_plan, hipEvent_t ev, int32_t* zero_buf, int zero_n);
+// Zeroed ints plan_grid_device must clear for the binning below (the bucket totals, reservation
+// cursors and the big-cell counter) plus kZeroedExtra + 4 for the caller.
+int octant_zeroed_ints();
+// The octant binning enqueued with the hint's shapes; every kernel reads the grid from d_plan.
+int bin_octants_planned(Ctx* c, const double* xyz, int64_t n, double cell, const PlanHint& hint,
+                        const GridPlan* d_plan, int32_t* zeroed, DevGrid* g, SubCells* sub);
+// The octant binning planned on the host from the box and fp32 flag of `box` (read back from
+// plan_grid_device; finite-checked here: PYQSM_EINVAL). Writes the exact plan to *h_exact, uploads
+// it through h_up (page-locked) to d_plan, and *hint_out = the hint it makes (valid = 0: the grid is
+// not of the device-plannable kind).
+int bin_octants_host(Ctx* c, const double* xyz, int64_t n, double min_cell, int64_t max_cells, const GridPlan& box,
+                     int32_t* zeroed, GridPlan* h_up, GridPlan* d_plan, DevGrid* g, SubCells* sub,
+                     PlanHint* hint_out);
 
 // A grid with cells `factor` times larger over the same points, derived from `fine`
 // by block sums and a deterministic scatter (no atomics, no second pass over xyz).
