@@ -463,6 +463,50 @@ int pyqsm_stat_outlier(const double* xyz, int64_t n, int32_t nb_neighbors, doubl
 int pyqsm_clean_cloud(const double* xyz, int64_t n, double voxel_size, double neighbors, double ratio,
                       int32_t iters, int64_t* m, double** out_xyz, int32_t device);
 
+/* ---- normals: estimation, consistent orientation, the stem stage ----------------------- */
+/*
+ * Open3D's PointCloud.estimate_normals and orient_normals_consistent_tangent_plane as get_stem_pcd
+ * applies them (pyQSM/qsm_generation.py:71-120; also fit.py:93, surf_recon.py:107,158,
+ * mesh_processing.py:201). Recollected from Open3D, parity unpinned; tests/normals_restatement.py
+ * defines the contract.
+ *
+ * pyqsm_estimate_normals: xyz f64 [n,3]. Neighbourhood of i: with radius > 0 and finite (hybrid),
+ *   the up to max_nn nearest points with d2 < radius^2, max_nn in [1, 256]; otherwise (KNN) the
+ *   min(max_nn, n) nearest, max_nn in [1, 192] (PYQSM_ERANGE outside). The point itself counts;
+ *   d2 = ((dx*dx) + dy*dy) + dz*dz in fp64; ties go to the lower index, so the neighbours are
+ *   ascending by (d2, index). Covariance on offsets o = p_j - p_i: m = (sum o) / N,
+ *   C = (sum (o - m)(o - m)^T) / N, each sum from 0.0 one add at a time in neighbour order. The
+ *   normal is the unit eigenvector of C's smallest eigenvalue (cyclic Jacobi, pca.hpp). Fewer
+ *   than 3 neighbours or C == 0: prev_normals[i] when given, else (0, 0, 1). Sign: flipped when
+ *   dot(n, prev_normals[i]) < 0, or without prev_normals (NULL) when n_z < 0.
+ *   normals f64 [n,3] out.
+ */
+int pyqsm_estimate_normals(const double* xyz, int64_t n, double radius, int32_t max_nn,
+                           const double* prev_normals, double* normals, int32_t device);
+/*
+ * pyqsm_orient_normals_tangent_plane: the min(k, n) nearest of every point (the point itself
+ *   counted, its self edge dropped), k in [1, 192], as undirected edges of weight
+ *   w = 1 - |(nx*mx + ny*my) + nz*mz| ordered by (w, min(i,j), max(i,j)): the unique minimum
+ *   spanning forest. A point's sign relative to its tree's root is the XOR along the tree path of
+ *   (dot(n_i, n_j) < 0) on the input normals. Each component is rooted at its highest point
+ *   (largest z, lowest index), whose normal is flipped when n_z < 0. No EMST edges: components of
+ *   the kNN graph are oriented independently. oriented f64 [n,3] out; *rounds (may be NULL) =
+ *   Boruvka rounds that merged components.
+ */
+int pyqsm_orient_normals_tangent_plane(const double* xyz, int64_t n, const double* normals, int32_t k,
+                                       double* oriented, int32_t* rounds, int32_t device);
+/*
+ * pyqsm_stem_cloud: get_stem_pcd's device part, one upload and one download: crop (keep
+ *   z > min z + crop_offset; no crop when that bound is exactly 0, as pyQSM's crop), normals
+ *   (radius, max_nn, prev_normals of all n points or NULL), orientation (orient_k), then
+ *   filter_by_norm's test -angle_cutoff < degrees(atan(nz / sqrt(nx^2 + ny^2))) < angle_cutoff
+ *   (angle 0 when nx = ny = 0). keep i64 [capacity n]: input indices of the kept points,
+ *   ascending; normals f64 [capacity n,3]: their oriented normals; *m = how many.
+ */
+int pyqsm_stem_cloud(const double* xyz, int64_t n, const double* prev_normals, double crop_offset,
+                     double radius, int32_t max_nn, int32_t orient_k, double angle_cutoff,
+                     int64_t* keep, double* normals, int64_t* m, int32_t device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -82,6 +82,10 @@ SIGNATURES = {
     "pyqsm_stat_outlier": (ctypes.c_int, [vp, i64, i32, dbl, vp, ctypes.POINTER(i64), vp, vp, i32]),
     "pyqsm_clean_cloud": (ctypes.c_int, [vp, i64, dbl, dbl, dbl, i32, ctypes.POINTER(i64),
                                          ctypes.POINTER(vp), i32]),
+    "pyqsm_estimate_normals": (ctypes.c_int, [vp, i64, dbl, i32, vp, vp, i32]),
+    "pyqsm_orient_normals_tangent_plane": (ctypes.c_int, [vp, i64, vp, i32, vp, ctypes.POINTER(i32), i32]),
+    "pyqsm_stem_cloud": (ctypes.c_int, [vp, i64, vp, dbl, dbl, i32, i32, dbl, vp, vp, ctypes.POINTER(i64),
+                                        i32]),
     "pyqsm_mean_f64": (ctypes.c_int, [vp, i64, ctypes.POINTER(dbl)]),
     "pyqsm_extreme_points": (ctypes.c_int, [vp, i64, vp, i32, vp, i32]),
     "pyqsm_outside_halfspaces": (ctypes.c_int, [vp, i64, vp, i32, dbl, vp, ctypes.POINTER(i64), i32]),

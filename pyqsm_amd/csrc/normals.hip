@@ -1,0 +1,727 @@
+// normals.hip — the stem stage of pyQSM's QSM route (pyQSM/qsm_generation.py:71-120 get_stem_pcd):
+// Open3D's PointCloud.estimate_normals and orient_normals_consistent_tangent_plane, the angle filter
+// of filter_by_norm, and the whole stage resident in HBM. Recollected from Open3D, parity unpinned;
+// tests/normals_restatement.py states the contract in NumPy/SciPy and the kernels are held to it bit
+// for bit.
+//
+// Normals. Hybrid search (radius > 0 and finite): the source cloud is binned into cells of the
+// radius; one wave per query (in the grid's sorted order) counts its candidates with d2 < r2 in the
+// 27 cells around it, collects them in LDS (or, when more than kNormCap lie inside, first finds the
+// max_nn-th smallest d2 exactly by bisection on its bit pattern, and collects those below it and
+// every tie at it), bitonic-sorts them by (d2, index) and keeps the first max_nn. KNN search: the
+// exact kNN (knn.hip, the point itself counted) already comes ascending by (d2, index). Either way
+// the wave gathers the offsets p_j - p_i into LDS, three lanes sum the mean and six lanes the
+// covariance entries, one add at a time in neighbour order; k_normal_finish then runs the Jacobi
+// solve (pca.hpp) and the sign rule on one lane per point.
+//
+// Orientation. Boruvka over the directed kNN edges with union-find labels that carry a parity bit
+// (label = root << 1 | parity of the point relative to its root). Every cross edge proposes itself
+// to both of its components with a two-phase 64-bit atomicMin (orderable weight bits, then the packed
+// (min, max) among equal weights): a total order, so the spanning forest is unique and a mutual pair
+// of components picks the same edge. Components hook along their edge (the lower id of a mutual
+// pair stays a root), the hook forest is compressed by pointer jumping in place and every label is
+// rewritten. A point's parity ends up the XOR of the flip bits along its tree path; the component's
+// highest point (lowest index on ties) fixes the sign. Only integer atomics, and every outcome is
+// independent of their arrival order.
+#include <algorithm>
+#include <cmath>
+
+#include "common.hpp"
+#include "grid.hpp"
+#include "pca.hpp"
+
+namespace pyqsm {
+
+int knn_device(Ctx* c, const double* xyz, int64_t n, int32_t k, int32_t exclude_self, int32_t* idx,
+               double* d2);                  // knn.hip
+static constexpr int kKnnMaxK = 192;          // knn.hip kMaxK: largest k of a KNN search and orientation
+static constexpr int kNormMaxNN = 256;        // largest max_nn of a hybrid search
+static constexpr int kNormCap = 512;          // (d2, index) pairs a wave sorts in LDS
+
+struct NGrid {
+  double minx, miny, minz, inv;
+  int nx, ny, nz;
+};
+
+// ---- neighbourhoods and covariance --------------------------------------------------------------
+// The runs of sorted positions of the 27 cells around the query's cell, clamped into the grid the
+// way the points were binned (grid.hip: cell_index): the grid may cover less than the cloud (it is
+// built over the box without its sparse tails), and clamping moves no two points further apart.
+struct Runs {
+  int qb[9], qe[9];
+};
+
+__device__ __forceinline__ void cell_runs(const NGrid& g, const int32_t* __restrict__ start, double x, double y,
+                                          double z, Runs* rr) {
+  const double fx = floor((x - g.minx) * g.inv), fy = floor((y - g.miny) * g.inv), fz = floor((z - g.minz) * g.inv);
+  const int cx = int(fmin(fmax(fx, 0.0), double(g.nx - 3))) + 1;
+  const int cy = int(fmin(fmax(fy, 0.0), double(g.ny - 3))) + 1;
+  const int cz = int(fmin(fmax(fz, 0.0), double(g.nz - 3))) + 1;
+  int w = 0;
+  for (int dz = -1; dz <= 1; ++dz)
+    for (int dy = -1; dy <= 1; ++dy, ++w) {
+      const int zz = cz + dz, yy = cy + dy;
+      rr->qb[w] = rr->qe[w] = 0;
+      if (zz < 0 || zz >= g.nz || yy < 0 || yy >= g.ny) continue;
+      const int x0 = cx - 1 < 0 ? 0 : cx - 1, x1 = cx + 1 >= g.nx ? g.nx - 1 : cx + 1;
+      const int row = (zz * g.ny + yy) * g.nx;
+      rr->qb[w] = start[row + x0];
+      rr->qe[w] = start[row + x1 + 1];
+    }
+}
+
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Covariance of the first cnt neighbours listed in nb (LDS, ascending (d2, index)) of point i:
+// o_j = p_j - p_i, m = (sum o) / cnt, C = (sum (o - m)(o - m)^T) / cnt, every sum from 0.0 one add
+// at a time in list order. o: LDS [3][kNormMaxNN], scratch: LDS, at least 3 doubles. Lane c < 6
+// writes entry c of (c00, c01, c02, c11, c12, c22) to cov[6 i + c]; lane 0 the count.
+__device__ void covariance_of_list(int lane, int i, int cnt, const int* nb, const double* __restrict__ xyz,
+                                   double (*o)[kNormMaxNN], double* scratch, double* __restrict__ cov,
+                                   int32_t* __restrict__ cnt_out) {
+  const double px = xyz[3 * size_t(i)], py = xyz[3 * size_t(i) + 1], pz = xyz[3 * size_t(i) + 2];
+  for (int t = lane; t < cnt; t += 64) {
+    const size_t j = size_t(nb[t]) * 3;
+    o[0][t] = xyz[j] - px;
+    o[1][t] = xyz[j + 1] - py;
+    o[2][t] = xyz[j + 2] - pz;
+  }
+  wave_sync();
+  const double dn = double(cnt);
+  if (lane < 3) {
+    double s = 0.0;
+    for (int t = 0; t < cnt; ++t) s = s + o[lane][t];
+    scratch[lane] = s / dn;
+  }
+  wave_sync();
+  if (lane < 6) {
+    const int a = lane < 3 ? 0 : (lane < 5 ? 1 : 2);
+    const int b = lane < 3 ? lane : (lane < 5 ? lane - 2 : 2);
+    const double ma = scratch[a], mb = scratch[b];
+    double s = 0.0;
+    for (int t = 0; t < cnt; ++t) s = s + (o[a][t] - ma) * (o[b][t] - mb);
+    cov[6 * size_t(i) + lane] = s / dn;
+  }
+  if (lane == 0) cnt_out[i] = cnt;
+}
+
+// Hybrid search, one wave per query: wave p serves the point at sorted position p (neighbouring
+// waves then read neighbouring cells). *overflow = 1 when more than kNormCap points tie at the
+// max_nn-th distance of some query (the result of that query is then not the contract's).
+template <class CO>
+__global__ __launch_bounds__(128) void k_normal_hybrid(int n, const double* __restrict__ xyz, NGrid g,
+                                                       const int32_t* __restrict__ start,
+                                                       const int32_t* __restrict__ order, CO co, double r2, int k,
+                                                       double* __restrict__ cov, int32_t* __restrict__ cnt_out,
+                                                       int32_t* __restrict__ overflow) {
+  __shared__ double sd[2][kNormCap];
+  __shared__ int si[2][kNormCap];
+  __shared__ double so[2][3][kNormMaxNN];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int p = blockIdx.x * 2 + w;
+  if (p >= n) return;  // whole wave
+  const int i = order[p];
+  const double x = xyz[3 * size_t(i)], y = xyz[3 * size_t(i) + 1], z = xyz[3 * size_t(i) + 2];
+  Runs rr;
+  cell_runs(g, start, x, y, z, &rr);
+  auto count_le = [&](double tau) {  // candidates with d2 < r2 and d2 <= tau
+    int cnt = 0;
+    for (int r = 0; r < 9; ++r)
+      for (int base = rr.qb[r]; base < rr.qe[r]; base += 64) {
+        const int q = base + lane;
+        bool in = false;
+        if (q < rr.qe[r]) {
+          const double d = co.d2(q, x, y, z);
+          in = d < r2 && d <= tau;
+        }
+        cnt += __popcll(__ballot(in));
+      }
+    return cnt;
+  };
+  const int total = count_le(__builtin_inf());
+  double tau = __builtin_inf();  // collect d2 < tau, and d2 == tau
+  if (total > kNormCap) {
+    unsigned long long lo = 0, hi = (unsigned long long)__double_as_longlong(r2);
+    while (lo < hi) {  // smallest t with #{d2 <= t} >= k (k < total; d2 >= 0 orders as its bits)
+      const unsigned long long mid = lo + ((hi - lo) >> 1);
+      if (count_le(__longlong_as_double((long long)mid)) >= k) hi = mid;
+      else lo = mid + 1;
+    }
+    tau = __longlong_as_double((long long)lo);
+  }
+  int have = 0;
+  for (int r = 0; r < 9; ++r)
+    for (int base = rr.qb[r]; base < rr.qe[r]; base += 64) {
+      const int q = base + lane;
+      double d = 0.0;
+      bool take = false;
+      if (q < rr.qe[r]) {
+        d = co.d2(q, x, y, z);
+        take = d < r2 && d <= tau;
+      }
+      const unsigned long long kb = __ballot(take);
+      const int slot = have + __popcll(kb & ((1ull << lane) - 1ull));
+      if (take && slot < kNormCap) {
+        sd[w][slot] = d;
+        si[w][slot] = order[q];
+      }
+      have += __popcll(kb);
+    }
+  if (have > kNormCap) {
+    if (lane == 0) *overflow = 1;
+    have = kNormCap;
+  }
+  int np2 = 1;
+  while (np2 < have) np2 <<= 1;
+  for (int t = have + lane; t < np2; t += 64) {
+    sd[w][t] = __builtin_inf();
+    si[w][t] = 0x7FFFFFFF;
+  }
+  wave_sync();
+  for (int k2 = 2; k2 <= np2; k2 <<= 1)
+    for (int j = k2 >> 1; j > 0; j >>= 1) {
+      for (int t = lane; t < np2; t += 64) {
+        const int u = t ^ j;
+        if (u > t) {
+          const double da = sd[w][t], db = sd[w][u];
+          const int ia = si[w][t], ib = si[w][u];
+          const bool a_gt_b = da > db || (da == db && ia > ib);
+          if (a_gt_b == ((t & k2) == 0)) {
+            sd[w][t] = db;
+            si[w][t] = ib;
+            sd[w][u] = da;
+            si[w][u] = ia;
+          }
+        }
+      }
+      wave_sync();
+    }
+  covariance_of_list(lane, i, min(have, k), si[w], xyz, so[w], sd[w], cov, cnt_out);
+}
+
+// KNN search: the k nearest (knn_device, ascending by (d2, index)), one wave per point.
+__global__ __launch_bounds__(128) void k_normal_knn(int n, const double* __restrict__ xyz,
+                                                    const int32_t* __restrict__ idx, int k,
+                                                    double* __restrict__ cov, int32_t* __restrict__ cnt_out) {
+  __shared__ int si[2][kKnnMaxK];
+  __shared__ double so[2][3][kNormMaxNN];
+  __shared__ double sm[2][4];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int i = blockIdx.x * 2 + w;
+  if (i >= n) return;
+  for (int t = lane; t < k; t += 64) si[w][t] = idx[size_t(i) * k + t];
+  wave_sync();
+  covariance_of_list(lane, i, k, si[w], xyz, so[w], sm[w], cov, cnt_out);
+}
+
+// One lane per point: fewer than 3 neighbours or an all-zero covariance keep the previous normal,
+// or give (0, 0, 1) without one; otherwise the smallest eigenvector, flipped when it points away
+// from the previous normal (dot < 0) or, without one, when n_z < 0.
+__global__ __launch_bounds__(256) void k_normal_finish(int n, const double* __restrict__ cov,
+                                                       const int32_t* __restrict__ cnt,
+                                                       const double* __restrict__ prev, double* __restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double* c = cov + 6 * size_t(i);
+  const Sym3 A = {c[0], c[1], c[2], c[3], c[4], c[5]};
+  double* o = out + 3 * size_t(i);
+  const bool zero = A.a00 == 0.0 && A.a01 == 0.0 && A.a02 == 0.0 && A.a11 == 0.0 && A.a12 == 0.0 && A.a22 == 0.0;
+  if (cnt[i] < 3 || zero) {
+    o[0] = prev ? prev[3 * size_t(i)] : 0.0;
+    o[1] = prev ? prev[3 * size_t(i) + 1] : 0.0;
+    o[2] = prev ? prev[3 * size_t(i) + 2] : 1.0;
+    return;
+  }
+  double v[3];
+  smallest_eigvec(A, v);
+  bool flip;
+  if (prev) {
+    const double* q = prev + 3 * size_t(i);
+    flip = (v[0] * q[0] + v[1] * q[1]) + v[2] * q[2] < 0.0;
+  } else {
+    flip = v[2] < 0.0;
+  }
+  o[0] = flip ? -v[0] : v[0];
+  o[1] = flip ? -v[1] : v[1];
+  o[2] = flip ? -v[2] : v[2];
+}
+
+// ---- orientation: Boruvka with parity ----------------------------------------------------------
+// A double's bits mapped so that unsigned order is numeric order (negative values included).
+__device__ __forceinline__ unsigned long long ord_bits(double v) {
+  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+
+__device__ __forceinline__ double dot3(const double* __restrict__ nrm, int a, int b) {
+  const double* p = nrm + 3 * size_t(a);
+  const double* q = nrm + 3 * size_t(b);
+  return (p[0] * q[0] + p[1] * q[1]) + p[2] * q[2];
+}
+
+__global__ __launch_bounds__(256) void k_label_init(int n, uint32_t* __restrict__ lab) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) lab[i] = uint32_t(i) << 1;
+}
+
+// Phase 1: the smallest orderable weight 1 - |dot| of the cross edges of every component.
+__global__ __launch_bounds__(256) void k_min_w(int64_t ne, int k, const int32_t* __restrict__ idx,
+                                               const double* __restrict__ nrm, const uint32_t* __restrict__ lab,
+                                               unsigned long long* __restrict__ bw) {
+  const int64_t e = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (e >= ne) return;
+  const int i = int(e / k), j = idx[e];
+  if (j == i) return;
+  const uint32_t ci = lab[i] >> 1, cj = lab[j] >> 1;
+  if (ci == cj) return;
+  const unsigned long long key = ord_bits(1.0 - fabs(dot3(nrm, i, j)));
+  // the minima only fall: an edge no lighter than what is already there (a stale read is no lower
+  // than the true value) cannot change them, and skipping it spares the atomic
+  if (key < bw[ci]) atomicMin(&bw[ci], key);
+  if (key < bw[cj]) atomicMin(&bw[cj], key);
+}
+
+// Phase 2: among the edges of that weight, the smallest packed (min, max).
+__global__ __launch_bounds__(256) void k_min_e(int64_t ne, int k, const int32_t* __restrict__ idx,
+                                               const double* __restrict__ nrm, const uint32_t* __restrict__ lab,
+                                               const unsigned long long* __restrict__ bw,
+                                               unsigned long long* __restrict__ be) {
+  const int64_t e = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (e >= ne) return;
+  const int i = int(e / k), j = idx[e];
+  if (j == i) return;
+  const uint32_t ci = lab[i] >> 1, cj = lab[j] >> 1;
+  if (ci == cj) return;
+  const unsigned long long key = ord_bits(1.0 - fabs(dot3(nrm, i, j)));
+  const unsigned long long pk = (i < j) ? ((unsigned long long)i << 32 | uint32_t(j))
+                                        : ((unsigned long long)j << 32 | uint32_t(i));
+  if (key == bw[ci]) atomicMin(&be[ci], pk);
+  if (key == bw[cj]) atomicMin(&be[cj], pk);
+}
+
+// Every root with an edge hooks to the component across it: hk[c] = other << 1 | parity of c
+// relative to other. A mutual pair has chosen the same edge; its lower id stays a root.
+__global__ __launch_bounds__(256) void k_hook(int n, const double* __restrict__ nrm, const uint32_t* __restrict__ lab,
+                                              const unsigned long long* __restrict__ be, uint32_t* __restrict__ hk,
+                                              int32_t* __restrict__ hooks) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= n) return;
+  if ((lab[c] >> 1) != uint32_t(c)) return;
+  const unsigned long long pk = be[c];
+  hk[c] = uint32_t(c) << 1;
+  if (pk == ~0ull) return;
+  const int a = int(pk >> 32), b = int(pk & 0xFFFFFFFFu);
+  const uint32_t la = lab[a], lb = lab[b];
+  const uint32_t ca = la >> 1, cb = lb >> 1;
+  const uint32_t other = ca == uint32_t(c) ? cb : ca;
+  if (be[other] == pk && uint32_t(c) < other) return;
+  const uint32_t f = dot3(nrm, a, b) < 0.0 ? 1u : 0u;
+  hk[c] = (other << 1) | ((la ^ lb ^ f) & 1u);
+  atomicAdd(hooks, 1);
+}
+
+// Pointer jumping on the hook forest, in place: an entry always names an ancestor with the parity
+// relative to it, so concurrent jumps by other roots only shorten the walk.
+__global__ __launch_bounds__(256) void k_compress(int n, const uint32_t* __restrict__ lab, uint32_t* hk) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= n) return;
+  if ((lab[c] >> 1) != uint32_t(c)) return;
+  for (;;) {
+    const uint32_t h = __hip_atomic_load(&hk[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t p = h >> 1;
+    if (p == uint32_t(c)) break;
+    const uint32_t hp = __hip_atomic_load(&hk[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if ((hp >> 1) == p) break;
+    __hip_atomic_store(&hk[c], (hp & ~1u) | ((h ^ hp) & 1u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_relabel(int n, uint32_t* __restrict__ lab, const uint32_t* __restrict__ hk) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t l = lab[i];
+  const uint32_t h = hk[l >> 1];
+  lab[i] = (h & ~1u) | ((l ^ h) & 1u);
+}
+
+// The highest point of every component, lowest index on ties: orderable z first, then the index.
+__global__ __launch_bounds__(256) void k_top_z(int n, const double* __restrict__ xyz, const uint32_t* __restrict__ lab,
+                                               unsigned long long* __restrict__ tz) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t r = lab[i] >> 1;
+  const unsigned long long z = ord_bits(xyz[3 * size_t(i) + 2]);
+  if (z > tz[r]) atomicMax(&tz[r], z);  // the maxima only rise: see k_min_w
+}
+
+__global__ __launch_bounds__(256) void k_top_i(int n, const double* __restrict__ xyz, const uint32_t* __restrict__ lab,
+                                               const unsigned long long* __restrict__ tz, uint32_t* __restrict__ ti) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t r = lab[i] >> 1;
+  if (ord_bits(xyz[3 * size_t(i) + 2]) == tz[r]) atomicMin(&ti[r], uint32_t(i));
+}
+
+// Sign of i = parity of i relative to the highest point, XOR (that point's n_z < 0).
+__global__ __launch_bounds__(256) void k_orient_final(int n, const double* __restrict__ nrm,
+                                                      const uint32_t* __restrict__ lab,
+                                                      const uint32_t* __restrict__ ti, double* __restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t l = lab[i];
+  const uint32_t top = ti[l >> 1];
+  const uint32_t s = ((l ^ lab[top]) & 1u) ^ (nrm[3 * size_t(top) + 2] < 0.0 ? 1u : 0u);
+  const double* v = nrm + 3 * size_t(i);
+  double* o = out + 3 * size_t(i);
+  o[0] = s ? -v[0] : v[0];
+  o[1] = s ? -v[1] : v[1];
+  o[2] = s ? -v[2] : v[2];
+}
+
+// ---- stem stage: crop and angle filter -----------------------------------------------------------
+// keep[i] = z > bound (pyQSM's crop removes z <= min z + offset); entry n = 0 for the scan
+__global__ __launch_bounds__(256) void k_crop_mask(int n, const double* __restrict__ xyz, double bound,
+                                                   int32_t* __restrict__ keep) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i > n) return;
+  keep[i] = i < n && xyz[3 * size_t(i) + 2] > bound ? 1 : 0;
+}
+
+// gathers the kept rows (pos = scanned mask) of xyz and, when given, of the normals, and their indices
+__global__ __launch_bounds__(256) void k_gather_kept(int n, const int32_t* __restrict__ pos,
+                                                     const double* __restrict__ a, const double* __restrict__ b,
+                                                     const int64_t* __restrict__ src_idx, double* __restrict__ oa,
+                                                     double* __restrict__ ob, int64_t* __restrict__ oidx) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int p = pos[i];
+  if (pos[i + 1] == p) return;
+  for (int c = 0; c < 3; ++c) {
+    if (oa) oa[3 * size_t(p) + c] = a[3 * size_t(i) + c];
+    if (ob) ob[3 * size_t(p) + c] = b[3 * size_t(i) + c];
+  }
+  if (oidx) oidx[p] = src_idx ? src_idx[i] : int64_t(i);
+}
+
+// filter_by_norm: angle = degrees(atan(n_z / sqrt(n_x^2 + n_y^2))), 0 when n_x = n_y = 0; keep
+// -t < angle < t (rev: angle < -t or angle > t)
+__global__ __launch_bounds__(256) void k_angle_mask(int n, const double* __restrict__ nrm, double t, int rev,
+                                                    int32_t* __restrict__ keep) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i > n) return;
+  if (i == n) {
+    keep[n] = 0;
+    return;
+  }
+  const double* v = nrm + 3 * size_t(i);
+  const double den = sqrt(v[0] * v[0] + v[1] * v[1]);
+  const double ang = den != 0.0 ? atan(v[2] / den) * (180.0 / M_PI) : 0.0;
+  const bool in = ang > -t && ang < t;
+  keep[i] = (rev ? (ang < -t || ang > t) : in) ? 1 : 0;
+}
+
+// ---- device-resident steps ---------------------------------------------------------------------
+static bool hybrid_search(double radius) { return radius > 0 && std::isfinite(radius); }
+
+static int check_max_nn(double radius, int32_t max_nn) {
+  const int top = hybrid_search(radius) ? kNormMaxNN : kKnnMaxK;
+  if (max_nn < 1 || max_nn > top)
+    return fail(PYQSM_ERANGE, "max_nn must be in [1, %d] for a %s search", top, hybrid_search(radius) ? "hybrid" : "KNN");
+  return 0;
+}
+
+// Normals of the n points at d_xyz into d_out (both device); d_prev (device, may be null) the
+// previous normals.
+static int normals_device(Ctx* c, const double* d_xyz, int64_t n, double radius, int32_t max_nn,
+                          const double* d_prev, double* d_out) {
+  if (n == 0) return 0;
+  const int N = int(n);
+  double* cov;
+  int32_t* cnt;
+  PQ_TRY(c->arena.get(size_t(n) * 6, &cov));
+  PQ_TRY(c->arena.get(size_t(n), &cnt));
+  int32_t* overflow = nullptr;
+  if (hybrid_search(radius)) {
+    PQ_TRY(c->arena.get(1, &overflow));
+    PQ_HIP(hipMemsetAsync(overflow, 0, 4, c->stream));
+    DevGrid g;
+    {
+      ProfScope ps(c, "normals_grid");
+      double box[6];
+      bool all_f32 = false;
+      PQ_TRY(cloud_bbox(c, d_xyz, n, box, box + 3, &all_f32));
+      int64_t outside = 0;
+      PQ_TRY(robust_box(c, d_xyz, n, int(std::min<int64_t>(8192, std::max<int64_t>(256, n / 256))), box, &outside));
+      PQ_TRY(build_grid(c, d_xyz, n, radius * (1.0 + 1.0 / 1048576.0), int64_t(1) << 28, &g, box, all_f32));
+    }
+    const NGrid ng{g.minx, g.miny, g.minz, g.inv_cell, g.nx, g.ny, g.nz};
+    ProfScope ps(c, "normals_cov");
+    on_coords(g, [&](auto co) {
+      hipLaunchKernelGGL(k_normal_hybrid<decltype(co)>, dim3(ceil_div(n, 2)), dim3(128), 0, c->stream, N, d_xyz, ng,
+                         g.start, g.order, co, radius * radius, int(max_nn), cov, cnt, overflow);
+    });
+    PQ_HIP(hipGetLastError());
+  } else {
+    const int k = int(std::min<int64_t>(max_nn, n));
+    int32_t* idx;
+    double* d2;
+    PQ_TRY(c->arena.get(size_t(n) * k, &idx));
+    PQ_TRY(c->arena.get(size_t(n) * k, &d2));
+    {
+      ProfScope ps(c, "normals_knn");
+      PQ_TRY(knn_device(c, d_xyz, n, k, 0, idx, d2));
+    }
+    ProfScope ps(c, "normals_cov");
+    hipLaunchKernelGGL(k_normal_knn, dim3(ceil_div(n, 2)), dim3(128), 0, c->stream, N, d_xyz,
+                       static_cast<const int32_t*>(idx), k, cov, cnt);
+    PQ_HIP(hipGetLastError());
+  }
+  {
+    ProfScope ps(c, "normals_eig");
+    hipLaunchKernelGGL(k_normal_finish, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, N,
+                       static_cast<const double*>(cov), static_cast<const int32_t*>(cnt), d_prev, d_out);
+    PQ_HIP(hipGetLastError());
+  }
+  if (overflow) {
+    int32_t of = 0;
+    PQ_HIP(hipMemcpyAsync(&of, overflow, 4, hipMemcpyDeviceToHost, c->stream));
+    PQ_HIP(hipStreamSynchronize(c->stream));
+    if (of) return fail(PYQSM_ERANGE, "more than %d points tie at the max_nn-th distance of a query", kNormCap);
+  }
+  return 0;
+}
+
+// Orients the normals d_nrm of the n points d_xyz into d_out (all device). *rounds: Boruvka rounds
+// that hooked at least one component.
+static int orient_device(Ctx* c, const double* d_xyz, int64_t n, int32_t k, const double* d_nrm, double* d_out,
+                         int32_t* rounds) {
+  *rounds = 0;
+  if (n == 0) return 0;
+  const int N = int(n);
+  const int kk = int(std::min<int64_t>(k, n));
+  const int64_t ne = int64_t(n) * kk;
+  int32_t *idx, *hooks;
+  double* d2;
+  uint32_t *lab, *hk, *ti;
+  unsigned long long *bw, *be, *tz;
+  PQ_TRY(c->arena.get(size_t(ne), &idx));
+  PQ_TRY(c->arena.get(size_t(ne), &d2));
+  PQ_TRY(c->arena.get(size_t(n), &lab));
+  PQ_TRY(c->arena.get(size_t(n), &hk));
+  PQ_TRY(c->arena.get(size_t(n), &ti));
+  PQ_TRY(c->arena.get(size_t(n), &bw));
+  PQ_TRY(c->arena.get(size_t(n), &be));
+  PQ_TRY(c->arena.get(size_t(n), &tz));
+  PQ_TRY(c->arena.get(1, &hooks));
+  {
+    ProfScope ps(c, "orient_knn");
+    PQ_TRY(knn_device(c, d_xyz, n, kk, 0, idx, d2));
+  }
+  hipLaunchKernelGGL(k_label_init, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, N, lab);
+  PQ_HIP(hipGetLastError());
+  const int eb = ceil_div(ne, 256), pb = ceil_div(n, 256);
+  for (;;) {
+    {
+      ProfScope ps(c, "orient_min_edge");
+      PQ_HIP(hipMemsetAsync(bw, 0xFF, size_t(n) * 8, c->stream));
+      PQ_HIP(hipMemsetAsync(be, 0xFF, size_t(n) * 8, c->stream));
+      PQ_HIP(hipMemsetAsync(hooks, 0, 4, c->stream));
+      hipLaunchKernelGGL(k_min_w, dim3(eb), dim3(256), 0, c->stream, ne, kk, static_cast<const int32_t*>(idx), d_nrm,
+                         static_cast<const uint32_t*>(lab), bw);
+      hipLaunchKernelGGL(k_min_e, dim3(eb), dim3(256), 0, c->stream, ne, kk, static_cast<const int32_t*>(idx), d_nrm,
+                         static_cast<const uint32_t*>(lab), static_cast<const unsigned long long*>(bw), be);
+      PQ_HIP(hipGetLastError());
+    }
+    int32_t h = 0;
+    {
+      ProfScope ps(c, "orient_hook");
+      hipLaunchKernelGGL(k_hook, dim3(pb), dim3(256), 0, c->stream, N, d_nrm, static_cast<const uint32_t*>(lab),
+                         static_cast<const unsigned long long*>(be), hk, hooks);
+      PQ_HIP(hipGetLastError());
+      PQ_HIP(hipMemcpyAsync(&h, hooks, 4, hipMemcpyDeviceToHost, c->stream));
+      PQ_HIP(hipStreamSynchronize(c->stream));
+    }
+    if (h == 0) break;
+    ++*rounds;
+    ProfScope ps(c, "orient_jump");
+    hipLaunchKernelGGL(k_compress, dim3(pb), dim3(256), 0, c->stream, N, static_cast<const uint32_t*>(lab), hk);
+    hipLaunchKernelGGL(k_relabel, dim3(pb), dim3(256), 0, c->stream, N, lab, static_cast<const uint32_t*>(hk));
+    PQ_HIP(hipGetLastError());
+  }
+  ProfScope ps(c, "orient_sign");
+  PQ_HIP(hipMemsetAsync(tz, 0, size_t(n) * 8, c->stream));
+  PQ_HIP(hipMemsetAsync(ti, 0xFF, size_t(n) * 4, c->stream));
+  hipLaunchKernelGGL(k_top_z, dim3(pb), dim3(256), 0, c->stream, N, d_xyz, static_cast<const uint32_t*>(lab), tz);
+  hipLaunchKernelGGL(k_top_i, dim3(pb), dim3(256), 0, c->stream, N, d_xyz, static_cast<const uint32_t*>(lab),
+                     static_cast<const unsigned long long*>(tz), ti);
+  hipLaunchKernelGGL(k_orient_final, dim3(pb), dim3(256), 0, c->stream, N, d_nrm, static_cast<const uint32_t*>(lab),
+                     static_cast<const uint32_t*>(ti), d_out);
+  PQ_HIP(hipGetLastError());
+  return 0;
+}
+
+static int check_n(int64_t n) {
+  if (n < 0) return fail(PYQSM_EINVAL, "negative size");
+  if (n > 0x7FFFFF00LL) return fail(PYQSM_ERANGE, "more than 2^31 points per call");
+  return 0;
+}
+
+static int check_orient_k(int32_t k) {
+  if (k < 1 || k > kKnnMaxK) return fail(PYQSM_ERANGE, "k must be in [1, %d]", kKnnMaxK);
+  return 0;
+}
+
+}  // namespace pyqsm
+
+using namespace pyqsm;
+
+extern "C" {
+
+int pyqsm_estimate_normals(const double* xyz, int64_t n, double radius, int32_t max_nn, const double* prev_normals,
+                           double* normals, int32_t device) {
+  PQ_API_RANGE("pyqsm_estimate_normals");
+  PQ_TRY(check_n(n));
+  PQ_TRY(check_max_nn(radius, max_nn));
+  if (n > 0 && (!xyz || !normals)) return fail(PYQSM_EINVAL, "pyqsm_estimate_normals: NULL pointer");
+  if (n == 0) return 0;
+  Ctx* c = ctx_for(device);
+  if (!c) return PYQSM_ENODEV;
+  std::lock_guard<std::mutex> lk(c->mu);
+  c->arena.reset();
+  double *d_xyz, *d_prev = nullptr, *d_out;
+  PQ_TRY(c->arena.get(size_t(n) * 3, &d_xyz));
+  PQ_TRY(c->arena.get(size_t(n) * 3, &d_out));
+  PQ_HIP(hipMemcpyAsync(d_xyz, xyz, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+  if (prev_normals) {
+    PQ_TRY(c->arena.get(size_t(n) * 3, &d_prev));
+    PQ_HIP(hipMemcpyAsync(d_prev, prev_normals, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+  }
+  PQ_TRY(normals_device(c, d_xyz, n, radius, max_nn, d_prev, d_out));
+  PQ_HIP(hipMemcpyAsync(normals, d_out, size_t(n) * 24, hipMemcpyDeviceToHost, c->stream));
+  PQ_HIP(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int pyqsm_orient_normals_tangent_plane(const double* xyz, int64_t n, const double* normals, int32_t k,
+                                       double* oriented, int32_t* rounds, int32_t device) {
+  PQ_API_RANGE("pyqsm_orient_normals_tangent_plane");
+  PQ_TRY(check_n(n));
+  PQ_TRY(check_orient_k(k));
+  if (n > 0 && (!xyz || !normals || !oriented)) return fail(PYQSM_EINVAL, "pyqsm_orient_normals_tangent_plane: NULL pointer");
+  if (rounds) *rounds = 0;
+  if (n == 0) return 0;
+  Ctx* c = ctx_for(device);
+  if (!c) return PYQSM_ENODEV;
+  std::lock_guard<std::mutex> lk(c->mu);
+  c->arena.reset();
+  double *d_xyz, *d_nrm, *d_out;
+  PQ_TRY(c->arena.get(size_t(n) * 3, &d_xyz));
+  PQ_TRY(c->arena.get(size_t(n) * 3, &d_nrm));
+  PQ_TRY(c->arena.get(size_t(n) * 3, &d_out));
+  PQ_HIP(hipMemcpyAsync(d_xyz, xyz, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+  PQ_HIP(hipMemcpyAsync(d_nrm, normals, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+  int32_t r = 0;
+  PQ_TRY(orient_device(c, d_xyz, n, k, d_nrm, d_out, &r));
+  PQ_HIP(hipMemcpyAsync(oriented, d_out, size_t(n) * 24, hipMemcpyDeviceToHost, c->stream));
+  PQ_HIP(hipStreamSynchronize(c->stream));
+  if (rounds) *rounds = r;
+  return 0;
+}
+
+int pyqsm_stem_cloud(const double* xyz, int64_t n, const double* prev_normals, double crop_offset, double radius,
+                     int32_t max_nn, int32_t orient_k, double angle_cutoff, int64_t* keep, double* normals,
+                     int64_t* m_out, int32_t device) {
+  PQ_API_RANGE("pyqsm_stem_cloud");
+  PQ_TRY(check_n(n));
+  if (!m_out) return fail(PYQSM_EINVAL, "pyqsm_stem_cloud: NULL out-parameter");
+  *m_out = 0;
+  PQ_TRY(check_max_nn(radius, max_nn));
+  PQ_TRY(check_orient_k(orient_k));
+  if (!std::isfinite(crop_offset)) return fail(PYQSM_EINVAL, "crop_offset must be finite");
+  if (std::isnan(angle_cutoff)) return fail(PYQSM_EINVAL, "angle_cutoff must not be NaN");
+  if (n > 0 && (!xyz || !keep || !normals)) return fail(PYQSM_EINVAL, "pyqsm_stem_cloud: NULL pointer");
+  if (n == 0) return 0;
+  Ctx* c = ctx_for(device);
+  if (!c) return PYQSM_ENODEV;
+  std::lock_guard<std::mutex> lk(c->mu);
+  c->arena.reset();
+  const int N = int(n);
+  double *d_xyz, *d_prev = nullptr;
+  PQ_TRY(c->arena.get(size_t(n) * 3, &d_xyz));
+  PQ_HIP(hipMemcpyAsync(d_xyz, xyz, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+  if (prev_normals) {
+    PQ_TRY(c->arena.get(size_t(n) * 3, &d_prev));
+    PQ_HIP(hipMemcpyAsync(d_prev, prev_normals, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+  }
+  // crop: pyQSM removes z <= min z + offset, and skips the crop when that bound is exactly 0
+  double mn[3], mx[3];
+  PQ_TRY(cloud_bbox(c, d_xyz, n, mn, mx));
+  const double bound = mn[2] + crop_offset;
+  const double* cxyz = d_xyz;
+  const double* cprev = d_prev;
+  int64_t* c_idx = nullptr;
+  int64_t m = n;
+  if (bound != 0.0) {
+    ProfScope ps(c, "stem_crop");
+    int32_t* pos;
+    PQ_TRY(c->arena.get(size_t(n) + 1, &pos));
+    hipLaunchKernelGGL(k_crop_mask, dim3(ceil_div(n + 1, 256)), dim3(256), 0, c->stream, N, d_xyz, bound, pos);
+    PQ_HIP(hipGetLastError());
+    PQ_TRY(exclusive_scan_i32(c, pos, n + 1));
+    int32_t cnt = 0;
+    PQ_HIP(hipMemcpyAsync(&cnt, pos + n, 4, hipMemcpyDeviceToHost, c->stream));
+    PQ_HIP(hipStreamSynchronize(c->stream));
+    m = cnt;
+    if (m == 0) return 0;
+    double *nx, *np = nullptr;
+    PQ_TRY(c->arena.get(size_t(m) * 3, &nx));
+    if (d_prev) PQ_TRY(c->arena.get(size_t(m) * 3, &np));
+    PQ_TRY(c->arena.get(size_t(m), &c_idx));
+    hipLaunchKernelGGL(k_gather_kept, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, N,
+                       static_cast<const int32_t*>(pos), static_cast<const double*>(d_xyz),
+                       static_cast<const double*>(d_prev), static_cast<const int64_t*>(nullptr), nx, np, c_idx);
+    PQ_HIP(hipGetLastError());
+    cxyz = nx;
+    cprev = np;
+  }
+  double *nrm, *ori;
+  PQ_TRY(c->arena.get(size_t(m) * 3, &nrm));
+  PQ_TRY(c->arena.get(size_t(m) * 3, &ori));
+  PQ_TRY(normals_device(c, cxyz, m, radius, max_nn, cprev, nrm));
+  int32_t rounds = 0;
+  PQ_TRY(orient_device(c, cxyz, m, orient_k, nrm, ori, &rounds));
+  int32_t* pos;
+  double* k_nrm;
+  int64_t* k_idx;
+  PQ_TRY(c->arena.get(size_t(m) + 1, &pos));
+  PQ_TRY(c->arena.get(size_t(m) * 3, &k_nrm));
+  PQ_TRY(c->arena.get(size_t(m), &k_idx));
+  {
+    ProfScope ps(c, "stem_filter");
+    hipLaunchKernelGGL(k_angle_mask, dim3(ceil_div(m + 1, 256)), dim3(256), 0, c->stream, int(m),
+                       static_cast<const double*>(ori), angle_cutoff, 0, pos);
+    PQ_HIP(hipGetLastError());
+    PQ_TRY(exclusive_scan_i32(c, pos, m + 1));
+    hipLaunchKernelGGL(k_gather_kept, dim3(ceil_div(m, 256)), dim3(256), 0, c->stream, int(m),
+                       static_cast<const int32_t*>(pos), static_cast<const double*>(ori),
+                       static_cast<const double*>(nullptr), static_cast<const int64_t*>(c_idx), k_nrm,
+                       static_cast<double*>(nullptr), k_idx);
+    PQ_HIP(hipGetLastError());
+  }
+  int32_t cnt = 0;
+  PQ_HIP(hipMemcpyAsync(&cnt, pos + m, 4, hipMemcpyDeviceToHost, c->stream));
+  PQ_HIP(hipStreamSynchronize(c->stream));
+  if (cnt > 0) {
+    PQ_HIP(hipMemcpyAsync(keep, k_idx, size_t(cnt) * 8, hipMemcpyDeviceToHost, c->stream));
+    PQ_HIP(hipMemcpyAsync(normals, k_nrm, size_t(cnt) * 24, hipMemcpyDeviceToHost, c->stream));
+    PQ_HIP(hipStreamSynchronize(c->stream));
+  }
+  *m_out = cnt;
+  return 0;
+}
+
+}  // extern "C"

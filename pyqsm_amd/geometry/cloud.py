@@ -33,10 +33,48 @@ def as_points(obj) -> np.ndarray:
     return pts
 
 
+class KDTreeSearchParamHybrid:
+    """Open3D's ``KDTreeSearchParamHybrid``: up to ``max_nn`` nearest within ``radius``."""
+
+    def __init__(self, radius, max_nn):
+        self.radius = float(radius)
+        self.max_nn = int(max_nn)
+
+
+class KDTreeSearchParamKNN:
+    """Open3D's ``KDTreeSearchParamKNN``: the ``knn`` nearest."""
+
+    def __init__(self, knn=30):
+        self.knn = int(knn)
+
+
+def _search_param(param):
+    """(radius or None, max_nn) of a search parameter object, read by duck typing so that Open3D's
+    own classes work too: ``.radius`` and ``.max_nn`` (hybrid), or ``.knn``."""
+    if param is None:
+        return None, 30
+    if hasattr(param, "radius") and hasattr(param, "max_nn"):
+        return float(param.radius), int(param.max_nn)
+    if hasattr(param, "knn"):
+        return None, int(param.knn)
+    raise TypeError(f"unsupported search parameter {param!r}: expected .radius/.max_nn or .knn")
+
+
+def _normalized(v):
+    """Rows divided by their length; zero rows stay zero (Eigen's normalize)."""
+    v = np.asarray(v, dtype=np.float64)
+    ln = np.linalg.norm(v, axis=1)
+    out = v.copy()
+    nz = ln > 0
+    out[nz] = v[nz] / ln[nz, None]
+    return out
+
+
 class PointCloud:
-    def __init__(self, points=None, colors=None):
+    def __init__(self, points=None, colors=None, normals=None):
         self.points = np.zeros((0, 3)) if points is None else np.asarray(points, dtype=np.float64)
         self.colors = colors
+        self.normals = None if normals is None else np.asarray(normals, dtype=np.float64)
 
     def __len__(self):
         return len(self.points)
@@ -46,11 +84,49 @@ class PointCloud:
 
     def select_by_index(self, idx, invert: bool = False) -> "PointCloud":
         idx = np.asarray(idx, dtype=np.int64)
+        nrm = self.normals if self.has_normals() else None
         if invert:
             mask = np.ones(len(self.points), dtype=bool)
             mask[idx] = False
-            return PointCloud(self.points[mask])
-        return PointCloud(self.points[idx])
+            return PointCloud(self.points[mask], normals=None if nrm is None else nrm[mask])
+        return PointCloud(self.points[idx], normals=None if nrm is None else nrm[idx])
+
+    def has_normals(self) -> bool:
+        return self.normals is not None and len(self.normals) == len(self.points) and len(self.points) > 0
+
+    def estimate_normals(self, search_param=None, fast_normal_computation: bool = True, device: int = 0):
+        """Open3D's ``estimate_normals`` on the GPU (``hip.estimate_normals``). ``search_param``:
+        anything with ``.radius`` and ``.max_nn`` (hybrid) or ``.knn`` (KNN), Open3D's own classes
+        included; the default is the 30 nearest. Existing normals set the sign and are kept where a
+        neighbourhood is degenerate; without them the sign makes n_z >= 0. Recollected from Open3D,
+        parity unpinned. ``fast_normal_computation`` is accepted: there is one solver."""
+        radius, max_nn = _search_param(search_param)
+        prev = self.normals if self.has_normals() else None
+        self.normals = _hip().estimate_normals(self.points, radius, max_nn, normals=prev, device=device)
+        return True
+
+    def orient_normals_consistent_tangent_plane(self, k, *args, device: int = 0, **kwargs):
+        """Open3D's ``orient_normals_consistent_tangent_plane(k)`` on the GPU: signs made consistent
+        along the minimum spanning forest of the kNN graph, every component rooted at its highest
+        point with n_z >= 0 there (no Delaunay EMST edges: components are oriented apart). Open3D's
+        newer ``lambda`` and ``cos_alpha_tol`` are accepted at their defaults (0, 1) only."""
+        extra = dict(zip(("lambda", "cos_alpha_tol"), args))
+        extra.update(kwargs)
+        unknown = set(extra) - {"lambda", "lambda_", "cos_alpha_tol"}
+        if unknown:
+            raise TypeError(f"unexpected arguments {sorted(unknown)}")
+        lam = extra.get("lambda", extra.get("lambda_", 0.0))
+        tol = extra.get("cos_alpha_tol", 1.0)
+        if float(lam) != 0.0 or float(tol) != 1.0:
+            raise ValueError("only lambda = 0 and cos_alpha_tol = 1 are supported")
+        if not self.has_normals():
+            raise RuntimeError("the cloud has no normals: call estimate_normals first")
+        self.normals = _hip().orient_normals_tangent_plane(self.points, self.normals, k, device=device)
+
+    def normalize_normals(self) -> "PointCloud":
+        if self.has_normals():
+            self.normals = _normalized(self.normals)
+        return self
 
     def paint_uniform_color(self, rgb):
         self.colors = np.tile(np.asarray(rgb, dtype=np.float64), (len(self.points), 1))
@@ -61,14 +137,19 @@ class PointCloud:
 
     def voxel_down_sample(self, voxel_size, device: int = 0) -> "PointCloud":
         """Open3D's ``voxel_down_sample`` on the GPU (``hip.voxel_down_sample``): the mean of every
-        occupied voxel, colours averaged the same way when present. Recollected from Open3D,
+        occupied voxel, colours and normals averaged the same way when present (normals then
+        normalised). Recollected from Open3D,
         parity unpinned. Unlike Open3D (whose order comes from a hash map) the voxels are ordered
         by the smallest input index they hold."""
         col = None
         if self.colors is not None and len(np.asarray(self.colors)) == len(self.points):
             col = self.colors
         xyz, rgb = _hip().voxel_down_sample(self.points, voxel_size, colors=col, device=device)
-        return PointCloud(xyz, rgb)
+        nrm = None
+        if self.has_normals():  # the same per-voxel means, normalised (a zero mean stays zero)
+            nrm = _normalized(_hip().voxel_down_sample(self.points, voxel_size, colors=self.normals,
+                                                       device=device)[1])
+        return PointCloud(xyz, rgb, nrm)
 
     def remove_statistical_outlier(self, nb_neighbors, std_ratio, print_progress: bool = False,
                                    device: int = 0):

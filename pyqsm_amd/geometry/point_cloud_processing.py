@@ -1,5 +1,6 @@
 """The DBSCAN entry points of pyQSM/geometry/point_cloud_processing.py
-(cluster_plus :169-203, cluster_and_get_largest :205-218) on the HIP kernels.
+(cluster_plus :169-203, cluster_and_get_largest :205-218) on the HIP kernels, and its
+filter_by_norm (:246-256) on the normals they leave.
 
 The reference calls Open3D's ``PointCloud.cluster_dbscan``; its result (noise -1,
 clusters numbered in index order of their first core point, border points given
@@ -71,3 +72,30 @@ def cluster_and_get_largest(pcd, eps=config["trunk"]["cluster_eps"],
     unique_vals, counts = np.unique(labels, return_counts=True)
     largest = unique_vals[np.argmax(counts)]
     return _select(pcd, pts, np.where(labels == largest)[0])
+
+
+def _angles_deg(normals):
+    """pyQSM's np.degrees(get_angles(n)) for every row: get_angles returns arctan(nz / sqrt(nx^2 +
+    ny^2)) in radians whenever that is non-zero (its ``radians`` flag is overwritten), 0 when it is
+    zero or nx = ny = 0; filter_by_norm then converts to degrees."""
+    n = np.asarray(normals, dtype=np.float64).reshape(-1, 3)
+    a, b, c = n[:, 0], n[:, 1], n[:, 2]
+    denom = np.sqrt(a**2 + b**2)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rad = np.arctan(c / np.sqrt(a**2 + b**2))
+    rad = np.where(denom != 0, rad, 0.0)
+    return np.degrees(rad)
+
+
+def filter_by_norm(pcd, angle_thresh=10, rev=False):
+    """point_cloud_processing.py:246-256: the sub-cloud of the points whose normal makes an angle
+    strictly inside (-angle_thresh, angle_thresh) degrees with the XY plane (the complement with
+    ``rev``). A normal with nx = ny = 0 has angle 0 and is kept. Needs ``pcd.normals``."""
+    norms = np.asarray(pcd.normals)
+    angles = _angles_deg(norms)
+    log.info(f"{angle_thresh=}")
+    if rev:
+        stem_idxs = np.where((angles < -angle_thresh) | (angles > angle_thresh))[0]
+    else:
+        stem_idxs = np.where((angles > -angle_thresh) & (angles < angle_thresh))[0]
+    return pcd.select_by_index(stem_idxs)

@@ -639,3 +639,82 @@ def clean_cloud(points, voxel_size: float, neighbors, ratio: float, iters: int, 
                                 ctypes.byref(px), int(device)))
     M = m.value
     return _adopt(lib, px, ctypes.c_double, max(3 * M, 1), np.float64)[:3 * M].reshape(M, 3)
+
+
+# ---- normals --------------------------------------------------------------------------------
+def _search_args(radius, max_nn):
+    """(radius, max_nn) of a normal search; radius <= 0, inf or None: KNN search."""
+    r = 0.0 if radius is None else float(radius)
+    if np.isnan(r):
+        raise ValueError("radius must not be NaN")
+    hybrid = r > 0 and np.isfinite(r)
+    nn = int(max_nn)
+    top = 256 if hybrid else 192
+    if not 1 <= nn <= top:
+        raise ValueError(f"max_nn must be in [1, {top}] for a {'hybrid' if hybrid else 'KNN'} search, got {max_nn!r}")
+    return (r if hybrid else 0.0), nn
+
+
+def _normals_like(normals, n):
+    if normals is None:
+        return None
+    nrm = np.ascontiguousarray(np.asarray(normals), dtype=np.float64)
+    if nrm.shape != (n, 3):
+        raise ValueError(f"normals must have shape {(n, 3)}, got {nrm.shape}")
+    return nrm
+
+
+def _orient_k(k):
+    kk = int(k)
+    if not 1 <= kk <= 192:
+        raise ValueError(f"k must be in [1, 192], got {k!r}")
+    return kk
+
+
+def estimate_normals(points, radius, max_nn: int, normals=None, device: int = 0):
+    """``pyqsm_estimate_normals``: float64 [n,3] unit normals. ``radius`` > 0 and finite: hybrid
+    search (up to ``max_nn`` nearest with d2 < radius^2); otherwise the ``max_nn`` nearest.
+    ``normals`` (the cloud's previous normals) set the sign and are kept where a neighbourhood
+    is degenerate; without them the sign makes n_z >= 0 and the fallback is (0, 0, 1)."""
+    pts = _points(points)
+    r, nn = _search_args(radius, max_nn)
+    n = pts.shape[0]
+    prev = _normals_like(normals, n)
+    out = np.empty((n, 3), dtype=np.float64)
+    check(_lib.load().pyqsm_estimate_normals(_p(pts), n, r, nn, _p(prev), _p(out), int(device)))
+    return out
+
+
+def orient_normals_tangent_plane(points, normals, k: int, return_rounds: bool = False, device: int = 0):
+    """``pyqsm_orient_normals_tangent_plane``: the normals with their signs made consistent along
+    the minimum spanning forest of the kNN graph (weights 1 - |dot|), each component rooted at
+    its highest point with n_z >= 0 there. With ``return_rounds`` also the Boruvka round count."""
+    pts = _points(points)
+    n = pts.shape[0]
+    nrm = _normals_like(normals, n)
+    kk = _orient_k(k)
+    out = np.empty((n, 3), dtype=np.float64)
+    rounds = i32(0)
+    check(_lib.load().pyqsm_orient_normals_tangent_plane(_p(pts), n, _p(nrm), kk, _p(out),
+                                                         ctypes.byref(rounds), int(device)))
+    return (out, rounds.value) if return_rounds else out
+
+
+def stem_cloud(points, radius, max_nn: int, orient_k: int, angle_cutoff: float, crop_offset: float = 0.5,
+               normals=None, device: int = 0):
+    """``pyqsm_stem_cloud``: crop, normals, orientation and the angle filter in HBM. Returns
+    (kept input indices int64 ascending, their oriented normals float64 [m,3])."""
+    pts = _points(points)
+    r, nn = _search_args(radius, max_nn)
+    n = pts.shape[0]
+    prev = _normals_like(normals, n)
+    kk = _orient_k(orient_k)
+    t = float(angle_cutoff)
+    if np.isnan(t):
+        raise ValueError("angle_cutoff must not be NaN")
+    keep = np.empty(n, dtype=np.int64)
+    nrm = np.empty((n, 3), dtype=np.float64)
+    m = i64(0)
+    check(_lib.load().pyqsm_stem_cloud(_p(pts), n, _p(prev), float(crop_offset), r, nn, kk, t, _p(keep),
+                                       _p(nrm), ctypes.byref(m), int(device)))
+    return keep[:m.value].copy(), nrm[:m.value].copy()

@@ -1,8 +1,9 @@
-"""The RANSAC caller of ``pyQSM/qsm_generation.py``.
+"""The RANSAC caller and the stem stage of ``pyQSM/qsm_generation.py``.
 
-Only ``fit_cyl_to_cluster`` (``qsm_generation.py:138-179``) lives here: the function through
-which the sphere-stepping QSM builder reaches ``fit_shape_RANSAC``. The stepping driver itself
-(``sphere_step``, file IO, drawing) is outside the hot-path scope.
+``fit_cyl_to_cluster`` (``qsm_generation.py:138-179``) is the function through which the
+sphere-stepping QSM builder reaches ``fit_shape_RANSAC``; ``get_stem_pcd`` (``:71-120``) keeps the
+points whose oriented normal is close to horizontal, on one device-resident call. The stepping
+driver itself (``sphere_step``, file IO, drawing) is outside the hot-path scope.
 """
 from __future__ import annotations
 
@@ -12,6 +13,8 @@ import numpy as np
 
 try:  # flat import style of the reference (pyqsm_amd on sys.path) or package import
     from ._shadow import fall_through
+    from . import hip
+    from .geometry.cloud import PointCloud, as_points
     from .math_utils.fit import fit_shape_RANSAC
     from .math_utils.general import get_center
     from .set_config import config
@@ -20,6 +23,8 @@ except ImportError:  # pragma: no cover
     import sys
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from pyqsm_amd._shadow import fall_through
+    from pyqsm_amd import hip
+    from pyqsm_amd.geometry.cloud import PointCloud, as_points
     from pyqsm_amd.math_utils.fit import fit_shape_RANSAC
     from pyqsm_amd.math_utils.general import get_center
     from pyqsm_amd.set_config import config
@@ -59,3 +64,46 @@ def fit_cyl_to_cluster(main_pcd, curr_pts, last_radius, cluster_idxs, cyls=[], c
         cyl_details.append({"center": get_center(curr_pts), "axis": axis,
                             "height": prev_neighbor_height, "radius": fit_radius})
     return good_fit_found
+
+
+_stem = config.get("stem", {})
+
+
+def get_stem_pcd(pcd=None, source_file=None,
+                 normals_radius=_stem.get("normals_radius", 0.1),
+                 normals_nn=_stem.get("normals_nn", 30),
+                 nb_neighbors=_stem.get("stem_neighbors", 10),
+                 std_ratio=_stem.get("stem_ratio", 2),
+                 angle_cutoff=_stem.get("angle_cutoff", 10),
+                 voxel_size=_stem.get("stem_voxel_size", ""),
+                 post_id_stat_down=_stem.get("post_id_stat_down", False),
+                 orient_k: int = 100, device: int = 0):
+    """qsm_generation.py:71-120 on ``hip.stem_cloud``: crop away z <= min z + 0.5 (skipped when that
+    bound is exactly 0, as pyQSM's ``crop`` does), estimate normals with a hybrid search
+    (``normals_radius``, ``normals_nn``), orient them over the ``orient_k`` = 100 nearest and keep
+    the points ``filter_by_norm(angle_cutoff)`` keeps; all in HBM. Then, if ``voxel_size`` is
+    truthy, ``voxel_down_sample``; if ``post_id_stat_down``, ``remove_statistical_outlier``
+    (``nb_neighbors``, ``std_ratio``) on the stem cloud (the reference names an undefined
+    ``test`` there; its evident intent). The reference's drawing and debugger block is dropped.
+    Returns a ``PointCloud`` with the kept points and their oriented normals. Previous normals of
+    ``pcd`` set the normals' sign, as Open3D's estimate_normals does."""
+    if source_file:
+        raise NotImplementedError("reading point cloud files is not part of this package: pass pcd")
+    if pcd is None:
+        raise ValueError("get_stem_pcd needs a cloud (pcd)")
+    pts = as_points(pcd)
+    prev = getattr(pcd, "normals", None)
+    if prev is not None and (not hasattr(pcd, "has_normals") or not pcd.has_normals()):
+        prev = None
+    log.info("Estimating and orienting normals")
+    idx, nrm = hip.stem_cloud(pts, normals_radius, normals_nn, orient_k, angle_cutoff,
+                              crop_offset=0.5, normals=prev, device=device)
+    stem_cloud = PointCloud(pts[idx], normals=nrm)
+    log.info("cleaning result (if requested)")
+    if voxel_size:
+        stem_cloud = stem_cloud.voxel_down_sample(voxel_size=voxel_size, device=device)
+    if post_id_stat_down:
+        _, ind = stem_cloud.remove_statistical_outlier(nb_neighbors=nb_neighbors, std_ratio=std_ratio,
+                                                       device=device)
+        stem_cloud = stem_cloud.select_by_index(ind)
+    return stem_cloud
