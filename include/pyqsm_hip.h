@@ -507,6 +507,67 @@ int pyqsm_stem_cloud(const double* xyz, int64_t n, const double* prev_normals, d
                      double radius, int32_t max_nn, int32_t orient_k, double angle_cutoff,
                      int64_t* keep, double* normals, int64_t* m, int32_t device);
 
+/* ---- branch tracing: k-means, silhouette, the ball step with exclusion ------------------- */
+/*
+ * pyQSM's sphere_step (qsm_generation.py:182-316) and the kmeans it reaches through
+ * choose_and_cluster (math_utils/fit.py:58-85, 168-214). tests/sphere_restatement.py states the
+ * contract; DESIGN.md section 10.
+ *
+ * Chunk sum (the reduction of the centroid sums and of the mean silhouette): 256 consecutive values
+ * per chunk (zeros past the end), each group of four summed ((v0 + v1) + v2) + v3, the 64 group sums
+ * added pairwise (neighbours first, six levels); the chunk totals added one at a time from 0.0.
+ *
+ * pyqsm_kmeans: scipy.cluster.vq.kmeans2(xy, init, iters, minit='matrix') on the x, y of the m
+ *   points xyz f64 [m,3], k in [1, PYQSM_KMEANS_MAX_K]. vq: label = argmin over c of
+ *   (dx*dx) + dy*dy with d = p - centroid, ties to the lowest c. Update: the chunk sums of each
+ *   centroid's members' x and y over their count; a centroid without members keeps its position.
+ *   init f64 [k,2]; centroids f64 [k,2] after the last update; labels i32 [m] of the last
+ *   assignment (which precedes the last update), as kmeans2 returns them.
+ */
+#define PYQSM_KMEANS_MAX_K 8
+#define PYQSM_KMEANS_MAX_Q 4
+#define PYQSM_SILHOUETTE_MAX_K 65536
+int pyqsm_kmeans(const double* xyz, int64_t m, int32_t k, int32_t iters, const double* init,
+                 double* centroids, int32_t* labels, int32_t device);
+/*
+ * pyqsm_silhouette: sklearn.metrics.silhouette_score of xyz f64 [m,3] under labels i32 [m] in
+ *   [0, k), k <= PYQSM_SILHOUETTE_MAX_K. d(i,j) = sqrt(((dx*dx) + dy*dy) + dz*dz), dx = x_i - x_j,
+ *   correctly rounded. For every point and every label c the sum of d(i,j) over the members j of c,
+ *   one add at a time from 0.0 in ascending j. a = own sum / (n_own - 1); b = the smallest
+ *   sum / n_c over the other labels with members; s_i = (b - a) / max(a, b), 0 for a singleton and
+ *   for 0/0. *score = chunk sum of s over m. *n_present = labels with members; the labelling is
+ *   valid iff 2 <= *n_present <= m - 1 (sklearn raises otherwise; here every s_i and *score are
+ *   0). samples f64 [m] (may be NULL) = s_i.
+ */
+int pyqsm_silhouette(const double* xyz, int64_t m, const int32_t* labels, int32_t k, double* score,
+                     int32_t* n_present, double* samples, int32_t device);
+/*
+ * pyqsm_kmeans_select: the candidates of pyQSM's kmeans in one pass: for q < nk, k = k0 + q
+ *   (1 <= k0, k0 + nk - 1 <= PYQSM_KMEANS_MAX_K, nk <= PYQSM_KMEANS_MAX_Q) pyqsm_kmeans with
+ *   `iters` iterations from init (f64, the nk initial centroid sets packed: [k0 + (k0+1) + ...][2]),
+ *   then pyqsm_silhouette of the 3-D points under its labels. labels i32 [nk,m], scores f64 [nk],
+ *   present i32 [nk] come back in one copy. The _dev form takes device-resident xyz.
+ */
+int pyqsm_kmeans_select(const double* xyz, int64_t m, int32_t k0, int32_t nk, int32_t iters,
+                        const double* init, int32_t* labels, double* scores, int32_t* present,
+                        int32_t device);
+int pyqsm_kmeans_select_dev(const double* xyz_dev, int64_t m, int32_t k0, int32_t nk, int32_t iters,
+                            const double* init, int32_t* labels, double* scores, int32_t* present,
+                            int32_t device);
+/*
+ * pyqsm_ball_excl_dev: the points i of the device cloud xyz_dev f64 [n,3] with
+ *   ((dx*dx) + dy*dy) + dz*dz <= radius^2 (pyqsm_ball_query's inclusive bound) and found_dev[i] == 0
+ *   (u8 [n]), compacted by scan: idx_dev i64 [capacity n] ascending, out_xyz_dev f64 [capacity n,3]
+ *   their coordinates (contiguous: the input of pyqsm_dbscan_dev_ex and pyqsm_kmeans_select_dev).
+ *   *count (host) = how many; reading it synchronises.
+ * pyqsm_mark_found_dev: found_dev[idx[j]] = 1 for the cnt host indices idx (those outside [0, n)
+ *   are skipped). Synchronises.
+ */
+int pyqsm_ball_excl_dev(const double* xyz_dev, int64_t n, const uint8_t* found_dev, const double center[3],
+                        double radius, int64_t* idx_dev, double* out_xyz_dev, int64_t* count,
+                        int32_t device);
+int pyqsm_mark_found_dev(uint8_t* found_dev, int64_t n, const int64_t* idx, int64_t cnt, int32_t device);
+
 #ifdef __cplusplus
 }
 #endif

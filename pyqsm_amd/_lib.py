@@ -89,6 +89,12 @@ SIGNATURES = {
     "pyqsm_mean_f64": (ctypes.c_int, [vp, i64, ctypes.POINTER(dbl)]),
     "pyqsm_extreme_points": (ctypes.c_int, [vp, i64, vp, i32, vp, i32]),
     "pyqsm_outside_halfspaces": (ctypes.c_int, [vp, i64, vp, i32, dbl, vp, ctypes.POINTER(i64), i32]),
+    "pyqsm_kmeans": (ctypes.c_int, [vp, i64, i32, i32, vp, vp, vp, i32]),
+    "pyqsm_silhouette": (ctypes.c_int, [vp, i64, vp, i32, ctypes.POINTER(dbl), ctypes.POINTER(i32), vp, i32]),
+    "pyqsm_kmeans_select": (ctypes.c_int, [vp, i64, i32, i32, i32, vp, vp, vp, vp, i32]),
+    "pyqsm_kmeans_select_dev": (ctypes.c_int, [vp, i64, i32, i32, i32, vp, vp, vp, vp, i32]),
+    "pyqsm_ball_excl_dev": (ctypes.c_int, [vp, i64, vp, vp, dbl, vp, vp, ctypes.POINTER(i64), i32]),
+    "pyqsm_mark_found_dev": (ctypes.c_int, [vp, i64, vp, i64, i32]),
 }
 
 _lib = None

@@ -718,3 +718,97 @@ def stem_cloud(points, radius, max_nn: int, orient_k: int, angle_cutoff: float, 
     check(_lib.load().pyqsm_stem_cloud(_p(pts), n, _p(prev), float(crop_offset), r, nn, kk, t, _p(keep),
                                        _p(nrm), ctypes.byref(m), int(device)))
     return keep[:m.value].copy(), nrm[:m.value].copy()
+
+
+# ---------------------------------------------------------------- k-means, silhouette, ball step
+
+KMEANS_MAX_K = 8        # PYQSM_KMEANS_MAX_K
+KMEANS_MAX_Q = 4        # PYQSM_KMEANS_MAX_Q
+SILHOUETTE_MAX_K = 65536
+
+
+def _xyz_for_xy(data) -> np.ndarray:
+    """[m,2] (or [m,3]) as the [m,3] rows the k-means kernels read (z unused)."""
+    d = np.asarray(data, dtype=np.float64)
+    if d.ndim != 2 or d.shape[1] not in (2, 3):
+        raise ValueError(f"expected points of shape [m,2] or [m,3], got {d.shape}")
+    if d.shape[1] == 3:
+        return np.ascontiguousarray(d)
+    out = np.zeros((d.shape[0], 3))
+    out[:, :2] = d
+    return out
+
+
+def kmeans(data, init, iters: int = 10, device: int = 0):
+    """``pyqsm_kmeans``: Lloyd on the x, y of ``data`` ([m,2] or [m,3]) from the centroids ``init``
+    [k,2]. Returns ``(centroids f64 [k,2], labels int32 [m])`` as kmeans2(minit='matrix')."""
+    xyz = _xyz_for_xy(data)
+    c0 = np.ascontiguousarray(init, dtype=np.float64).reshape(-1, 2)
+    k = c0.shape[0]
+    cent = np.empty((k, 2))
+    labels = np.empty(xyz.shape[0], dtype=np.int32)
+    check(_lib.load().pyqsm_kmeans(_p(xyz), xyz.shape[0], k, int(iters), _p(c0), _p(cent), _p(labels),
+                                   int(device)))
+    return cent, labels
+
+
+def silhouette(points, labels, k: int | None = None, return_samples: bool = False, device: int = 0):
+    """``pyqsm_silhouette``: ``(score, labels present)`` (and the per-point values when
+    ``return_samples``) of ``points`` [m,3] under ``labels`` in [0, k)."""
+    pts = _points(points)
+    lab = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+    if lab.shape[0] != pts.shape[0]:
+        raise ValueError("one label per point")
+    k = int(lab.max()) + 1 if k is None and len(lab) else int(k or 1)
+    score, present = dbl(0.0), i32(0)
+    samples = np.empty(pts.shape[0]) if return_samples else None
+    check(_lib.load().pyqsm_silhouette(_p(pts), pts.shape[0], _p(lab), k, ctypes.byref(score),
+                                       ctypes.byref(present), _p(samples), int(device)))
+    if return_samples:
+        return score.value, int(present.value), samples
+    return score.value, int(present.value)
+
+
+def _select_args(m, k0, inits):
+    nk = len(inits)
+    init = np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.float64).reshape(-1, 2)
+                                                for c in inits]))
+    if init.shape[0] != sum(k0 + q for q in range(nk)):
+        raise ValueError("inits[q] must hold k0 + q centroids")
+    return nk, init, np.empty((nk, m), dtype=np.int32), np.empty(nk), np.empty(nk, dtype=np.int32)
+
+
+def kmeans_select(points, k0: int, inits, iters: int = 10, device: int = 0):
+    """``pyqsm_kmeans_select``: for q < len(inits), k = k0 + q, Lloyd on the xy of ``points`` [m,3]
+    from ``inits[q]`` [k,2], then the silhouette of the 3-D points under those labels. Returns
+    ``(labels int32 [nk,m], scores f64 [nk], present int32 [nk])``."""
+    pts = _points(points)
+    nk, init, labels, scores, present = _select_args(pts.shape[0], k0, inits)
+    check(_lib.load().pyqsm_kmeans_select(_p(pts), pts.shape[0], int(k0), nk, int(iters), _p(init),
+                                          _p(labels), _p(scores), _p(present), int(device)))
+    return labels, scores, present
+
+
+def kmeans_select_dev(xyz_ptr: int, m: int, k0: int, inits, iters: int = 10, device: int = 0):
+    """:func:`kmeans_select` on ``m`` device-resident points (a ball step's gathered buffer)."""
+    nk, init, labels, scores, present = _select_args(int(m), k0, inits)
+    check(_lib.load().pyqsm_kmeans_select_dev(xyz_ptr, int(m), int(k0), nk, int(iters), _p(init),
+                                              _p(labels), _p(scores), _p(present), int(device)))
+    return labels, scores, present
+
+
+def ball_excl_dev(xyz_ptr: int, n: int, found_ptr: int, center, radius: float, idx_ptr: int,
+                  out_xyz_ptr: int, device: int = 0) -> int:
+    """``pyqsm_ball_excl_dev``: the unfound points within ``radius`` of ``center`` compacted into
+    ``idx_ptr`` (int64, ascending) and ``out_xyz_ptr`` (f64 [.,3]); returns how many."""
+    c = np.ascontiguousarray(center, dtype=np.float64).reshape(3)
+    cnt = i64(0)
+    check(_lib.load().pyqsm_ball_excl_dev(xyz_ptr, int(n), found_ptr, _p(c), float(radius), idx_ptr,
+                                          out_xyz_ptr, ctypes.byref(cnt), int(device)))
+    return int(cnt.value)
+
+
+def mark_found_dev(found_ptr: int, n: int, idx, device: int = 0) -> None:
+    """``pyqsm_mark_found_dev``: set the device mask at the host indices ``idx``."""
+    ix = np.ascontiguousarray(idx, dtype=np.int64).reshape(-1)
+    check(_lib.load().pyqsm_mark_found_dev(found_ptr, int(n), _p(ix), ix.shape[0], int(device)))

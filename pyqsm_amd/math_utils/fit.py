@@ -3,7 +3,7 @@ signatures (pyQSM/math_utils/fit.py), computed by the HIP kernels.
 
     cluster_DBSCAN(pts_idxs, points, eps, min_pts)         fit.py:217-250
     fit_shape_RANSAC(pcd, pts, threshold, lower_bound, ...) fit.py:253-339
-    choose_and_cluster(new_neighbors, main_pts, ...)        fit.py:58-85 (DBSCAN branch)
+    choose_and_cluster(new_neighbors, main_pts, ...)        fit.py:58-85
     z_align_and_fit(pcd, axis_guess, **kwargs)              fit.py:23-45
 
 plus the aliases BASELINE.json's north_star names: ``dbscan`` and ``fit_cylinder``.
@@ -23,6 +23,7 @@ try:
     from ..geometry.cloud import Cylinder, PointCloud, as_points
     from ..set_config import config, log
     from .general import get_radius, rotation_matrix_from_arr, unit_vector
+    from . import clustering as _clustering
 except ImportError:  # imported flat, with pyqsm_amd/ itself on sys.path (pyQSM's layout)
     import os
     import sys
@@ -32,6 +33,7 @@ except ImportError:  # imported flat, with pyqsm_amd/ itself on sys.path (pyQSM'
     from pyqsm_amd.geometry.cloud import Cylinder, PointCloud, as_points
     from pyqsm_amd.set_config import config, log
     from pyqsm_amd.math_utils.general import get_radius, rotation_matrix_from_arr, unit_vector
+    from pyqsm_amd.math_utils import clustering as _clustering
 
 # names pyQSM's module of the same name defines and this one does not (pyqsm_amd/_shadow.py)
 __getattr__ = fall_through(__name__)
@@ -97,18 +99,25 @@ def cluster_DBSCAN(pts_idxs, points, eps, min_pts, device: int = 0):
     return unique_labels, idxs, noise
 
 
-def choose_and_cluster(new_neighbors, main_pts, cluster_type="DBSCAN", debug=False):
-    """fit.py:58-85. Only the DBSCAN branch is on the hot path; ``"kmeans"`` (a
-    SciPy kmeans2 + silhouette heuristic with plotting, fit.py:168-214) is outside
-    the scope of this package and raises."""
-    if cluster_type == "kmeans":
-        raise NotImplementedError("the k-means branch of choose_and_cluster is not part of the "
-                                  "HIP hot path (SURVEY.md §2); pass cluster_type='DBSCAN'")
+def choose_and_cluster(new_neighbors, main_pts, cluster_type="DBSCAN", debug=False, seed=None,
+                       device: int = 0):
+    """fit.py:58-85. ``"kmeans"``: ``clustering.kmeans(nn_points, 1)`` (initial centroids drawn
+    from ``seed``); its local indices are mapped through ``new_neighbors``, so the clusters hold
+    indices of ``main_pts`` like the DBSCAN branch's (the reference hands the local indices on).
+    Fewer than two clusters fall back to DBSCAN, as in the reference. ``debug`` plotted there; it
+    is accepted and ignored."""
+    new_neighbors = np.asarray(new_neighbors)
     nn_points = np.asarray(main_pts)[new_neighbors]
-    log.info("clustering via DBSCAN")
-    labels, returned_clusters, _noise = cluster_DBSCAN(
-        new_neighbors, nn_points, eps=config["dbscan"]["epsilon"],
-        min_pts=config["dbscan"]["min_neighbors"])
+    returned_clusters = []
+    if cluster_type == "kmeans":
+        log.info("clustering via kmeans")
+        labels, local = _clustering.kmeans(nn_points, 1, seed=seed, device=device)
+        returned_clusters = [new_neighbors[c] for c in local]
+    if cluster_type != "kmeans" or len(returned_clusters) < 2:
+        log.info("clustering via DBSCAN")
+        labels, returned_clusters, _noise = cluster_DBSCAN(
+            new_neighbors, nn_points, eps=config["dbscan"]["epsilon"],
+            min_pts=config["dbscan"]["min_neighbors"], device=device)
     return labels, returned_clusters
 
 
