@@ -317,8 +317,17 @@ __device__ __forceinline__ void unite(int* parent, int a, int b) {
 // neighbours (1.15 ms per million points, 91 % memory waits); this one looks at
 // 62 neighbour sub-cells per sub-cell, most of them empty or already joined.
 
-// The first point of every sub-cell run finds the run's first core point (the sub-cell's
-// representative), hangs the other core points of the run under it and lists it.
+// A thread per sorted point, a wave per 64 consecutive points: sub-cell runs are contiguous, so "which core
+// point of my run comes first" is a ballot over the wave's core flags. The representative (the run's first
+// core point) takes the run's minimum of original indices, a segmented min over the wave's lanes plus, for the
+// one run that goes on past the wave, the rest of it 64 points per step; it fills in the record and lists the
+// sub-cell. Core points hang themselves under it. A run that began in an earlier wave is looked up from its
+// start, 64 core flags per load. Everything a wave needs besides the run records, the 64 points before and
+// after it included, is loaded up front side by side, so that only runs longer than that loop. (The first
+// version let each run's first thread walk the run alone with byte loads: 24 us per million points, the
+// longest run of a wave setting the wave's time; this one 18.6 us. Neither the loads one after the other
+// (18.9) nor four rounds of 1024 points per block with one append (17.5; k_labels the same way 18.3 -> 20.5)
+// moved it much: it is not bound by one wave's chain of loads nor by the list's atomic.)
 __global__ __launch_bounds__(1024) void k_sub_rep(int n, const int32_t* __restrict__ sub_of,
                                                  const uint8_t* __restrict__ core,
                                                  const int32_t* __restrict__ order,
@@ -331,41 +340,94 @@ __global__ __launch_bounds__(1024) void k_sub_rep(int n, const int32_t* __restri
                                                  int4* __restrict__ list_xyz) {
   if (!plan->ok) return;
   const int nx = plan->nx, ny = plan->ny;
-  int p = blockIdx.x * 1024 + threadIdx.x;
-  int rep = -1, sid = 0, e = 0;
-  if (p < n) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int base = blockIdx.x * 1024 + w * 64;  // the wave's first position
+  const int p = base + lane;
+  const bool live = p < n;
+  int sid = 0, s = n, e = n, ord = 0x7FFFFFFF, cell = 0;  // sub-cell, run [s, e), original index, cell
+  bool c = false;
+  // the wave before and the wave after: their core flags, and the next one's original indices
+  const bool c_prev = base >= 64 && p - 64 < n && core[p - 64];
+  const bool c_next = p + 64 < n && core[p + 64];
+  const int o_next = c_next ? order[p + 64] : 0x7FFFFFFF;
+  if (live) {
     sid = sub_of[p];
-    const int4 run = rec[sid];  // (first position, points, -, -) of the sub-cell
-    if (run.x == p) {
-      e = p + run.y;
-      int mn = 0x7FFFFFFF;
-      for (int q = p; q < e; ++q)
-        if (core[q]) {
-          if (rep < 0) rep = q;
-          parent[q] = rep;
-          mn = min(mn, order[q]);
-        }
-      if (rep >= 0) {
-        rec[sid].z = rep;
-        run_min[rep] = mn;  // smallest original index among the run's core points
+    c = core[p];
+    if (c) ord = order[p];
+    cell = cell_of[p];
+    const int2 run = *reinterpret_cast<const int2*>(rec + sid);  // (first position, points)
+    s = run.x;
+    e = run.x + run.y;
+  }
+  const unsigned long long cb = __ballot(c);
+  // the run of lane 0 may have begun in an earlier wave: its first core point there, if any (wave-uniform)
+  int lead = -1;
+  const int s0 = __shfl(s, 0, 64);
+  if (s0 < base && s0 >= base - 64) {  // within the wave before
+    const unsigned long long f = __ballot(c_prev && base - 64 + lane >= s0);
+    if (f) lead = base - 64 + __ffsll(f) - 1;
+  } else {
+    for (int q0 = s0; q0 < base; q0 += 64) {
+      const int q = q0 + lane;
+      const unsigned long long f = __ballot(q < base && core[q]);
+      if (f) {
+        lead = q0 + __ffsll(f) - 1;
+        break;
       }
     }
+  }
+  int rep = -1;
+  if (c) {
+    if (s < base && lead >= 0) {
+      rep = lead;
+    } else {  // the first core lane of my run in this wave (lane itself at the latest)
+      const int lo = s > base ? s - base : 0;
+      rep = base + __ffsll(cb & (~0ull << lo)) - 1;
+    }
+    parent[p] = rep;
+  }
+  const bool is_rep = c && rep == p;
+  // smallest original index of the core points from each lane to its run's end within the wave
+  int mn = ord;
+  const int seg_end = e - base < 64 ? e - base : 64;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int o = __shfl_down(mn, off, 64);
+    if (lane + off < seg_end) mn = o < mn ? o : mn;
+  }
+  // ... and beyond it, for the representative whose run goes on past the wave (at most one)
+  const unsigned long long tail = __ballot(is_rep && e > base + 64);
+  if (tail) {
+    const int t = __ffsll(tail) - 1;
+    const int et = __shfl(e, t, 64);
+    int m2 = base + 64 + lane < et ? o_next : 0x7FFFFFFF;
+    for (int q = base + 128 + lane; q < et; q += 64)
+      if (core[q]) m2 = min(m2, order[q]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const int o = __shfl_xor(m2, off, 64);
+      m2 = o < m2 ? o : m2;
+    }
+    if (lane == t) mn = min(mn, m2);
+  }
+  if (is_rep) {
+    rec[sid].z = rep;
+    run_min[rep] = mn;  // smallest original index among the run's core points
   }
   // block-aggregated append of the representatives: one atomic per block of 1024 threads
   // (atomics on a single address are served one at a time: one per wave cost 0.16 ms per
   // million points, one per 256 threads still 0.04 ms)
   __shared__ int wcount[16], wbase[16];
-  const unsigned long long b = __ballot(rep >= 0);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const unsigned long long b = __ballot(is_rep);
   if (lane == 0) wcount[w] = __popcll(b);
   __syncthreads();
   if (threadIdx.x == 0) {
     int tot = 0;
     for (int k = 0; k < 16; ++k) tot += wcount[k];
-    int base = tot ? atomicAdd(list_cnt, tot) : 0;
+    int base2 = tot ? atomicAdd(list_cnt, tot) : 0;
     for (int k = 0; k < 16; ++k) {
-      wbase[k] = base;
-      base += wcount[k];
+      wbase[k] = base2;
+      base2 += wcount[k];
     }
   }
   __syncthreads();
@@ -373,9 +435,9 @@ __global__ __launch_bounds__(1024) void k_sub_rep(int n, const int32_t* __restri
   // ... and, for k_hook_sub, its cell's grid coordinates and its octant: the two integer divisions by the
   // grid's dimensions happen HERE, once per sub-cell — in the hook pass every wave did twelve of them per
   // four sub-cells (~40 instructions each; the pass's look-ups were 48 us of its 81, a third of that this)
-  if (rep >= 0) {
+  if (is_rep) {
     const int slot = wbase[w] + __popcll(b & ((1ull << lane) - 1ull));
-    const int c1 = cell_of[rep];
+    const int c1 = cell;
     list[slot] = make_int4(rep, c1, sid, e - rep);
     list_xyz[slot] = make_int4(c1 % nx, (c1 / nx) % ny, c1 / (nx * ny), sid & 7);
   }
@@ -636,13 +698,52 @@ __global__ __launch_bounds__(256) void k_union_points(int n, Stencil st,
   })
 }
 
+// parent[p] = root for every core point (the per-point union-find's trees)
+__global__ __launch_bounds__(256) void k_flatten(int n, const uint8_t* __restrict__ core,
+                                                 int* __restrict__ parent, const GridPlan* __restrict__ plan) {
+  int p = blockIdx.x * 256 + threadIdx.x;
+  if (!plan->ok || p >= n || !core[p]) return;
+  int r = p;
+  for (int nx = parent[r]; nx != r; nx = parent[r]) r = nx;
+  parent[p] = r;  // benign: r is still an ancestor for concurrent readers
+}
+
+// Block-aggregated append of the flagged threads' values to list[*cnt]: one atomic per block (atomics on one
+// address are served one at a time). Every thread of the block calls it.
+template <int kThreads>
+__device__ __forceinline__ void block_append(bool take, int value, int32_t* __restrict__ list,
+                                             int32_t* __restrict__ cnt) {
+  constexpr int kWaves = kThreads / 64;
+  __shared__ int wcount[kWaves], wbase[kWaves];
+  const unsigned long long b = __ballot(take);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (lane == 0) wcount[w] = __popcll(b);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int tot = 0;
+    for (int k = 0; k < kWaves; ++k) tot += wcount[k];
+    int base = tot ? atomicAdd(cnt, tot) : 0;
+    for (int k = 0; k < kWaves; ++k) {
+      wbase[k] = base;
+      base += wcount[k];
+    }
+  }
+  __syncthreads();
+  if (take) list[wbase[w] + __popcll(b & ((1ull << lane) - 1ull))] = value;
+}
+
+// k_flatten ran: parent[p] is the root. Folds the components' smallest original indices and lists the roots.
 __global__ __launch_bounds__(256) void k_point_min(int n, const uint8_t* __restrict__ core,
                                                    const int* __restrict__ parent,
                                                    const int32_t* __restrict__ order,
-                                                   int* __restrict__ min_orig) {
+                                                   int* __restrict__ min_orig,
+                                                   int32_t* __restrict__ roots,
+                                                   int32_t* __restrict__ roots_cnt,
+                                                   const GridPlan* __restrict__ plan) {
   int p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= n || !core[p]) return;
-  atomicMin(min_orig + parent[p], order[p]);  // k_flatten ran: parent[p] is the root
+  const bool is_c = plan->ok && p < n && core[p];
+  if (is_c) atomicMin(min_orig + parent[p], order[p]);
+  block_append<256>(is_c && parent[p] == p, p, roots, roots_cnt);
 }
 
 // Smallest original core index of every component, folded from the per-run minima of
@@ -650,21 +751,27 @@ __global__ __launch_bounds__(256) void k_point_min(int n, const uint8_t* __restr
 // wave's representatives share a root (the common case), and an atomic only if it can
 // still lower the stored minimum. (Folding all core points this way cost 0.23 ms per
 // million points: atomics and coherent loads on a handful of hot addresses.)
-__global__ __launch_bounds__(256) void k_rep_min(const int4* __restrict__ list,
-                                                 const int32_t* __restrict__ m_ptr,
-                                                 const int* __restrict__ parent,
-                                                 const int* __restrict__ run_min,
-                                                 int* __restrict__ min_orig) {
+// Each representative also points straight at its root, and the roots are listed: the unions only ever
+// rewrote representatives' pointers, so every core point now reaches its root in two hops
+// (point -> representative -> root) and no pass over all points is needed to flatten them.
+__global__ __launch_bounds__(256) void k_rep_root(const int4* __restrict__ list,
+                                                  const int32_t* __restrict__ m_ptr,
+                                                  int* __restrict__ parent,
+                                                  const int* __restrict__ run_min,
+                                                  int* __restrict__ min_orig,
+                                                  int32_t* __restrict__ roots,
+                                                  int32_t* __restrict__ roots_cnt) {
   const int m = *m_ptr;
   int s = blockIdx.x * 256 + threadIdx.x;
   const bool active = s < m;
-  int r = -1, v = 0x7FFFFFFF;
+  int p = -1, r = -1, v = 0x7FFFFFFF;
   if (active) {
-    const int p = list[s].x;
+    p = list[s].x;
     // the root: after the compression that preceded k_union_sub and its few unions the chain is
     // one to three links long (a second compression pass over the list cost 20 us for this)
     r = p;
     for (int nx = parent[r]; nx != r; nx = parent[r]) r = nx;
+    if (r != p) parent[p] = r;  // benign: r is still an ancestor for concurrent readers
     v = run_min[p];
   }
   const volatile int* vmin = min_orig;  // plain pre-check: a stale value only costs an atomic
@@ -685,31 +792,117 @@ __global__ __launch_bounds__(256) void k_rep_min(const int4* __restrict__ list,
     if (lane == lead && mn < vmin[r0]) atomicMin(min_orig + r0, mn);
     rem &= ~__ballot(mine);
   }
+  block_append<256>(active && r == p, p, roots, roots_cnt);
 }
 
-// parent[p] = root for every core point (point -> representative -> root). With `flag` given
-// (the components' smallest indices are final by then) the roots also mark their cluster's
-// slot, which spares k_mark_roots.
-__global__ __launch_bounds__(256) void k_flatten(int n, const uint8_t* __restrict__ core,
-                                                 int* __restrict__ parent,
-                                                 const int* __restrict__ min_orig /*may be null*/,
-                                                 int32_t* __restrict__ flag /*may be null*/,
-                                                 const GridPlan* __restrict__ plan) {
-  int p = blockIdx.x * 256 + threadIdx.x;
-  if (!plan->ok || p >= n || !core[p]) return;
-  int r = p;
-  for (int nx = parent[r]; nx != r; nx = parent[r]) r = nx;
-  parent[p] = r;  // benign: r is still an ancestor for concurrent readers
-  if (flag && r == p) flag[min_orig[p]] = 1;
+// Cluster number = rank of the component's smallest original index among all components'. Up to kRankCap
+// components (the forest has 20) one workgroup sorts the roots by that index in LDS and overwrites each
+// root's min_orig with its number. Beyond it the numbering must not depend on the count of components: every
+// block marks its share of the smallest indices in a bitmap of n bits, and the last block to finish writes
+// the exclusive prefix of the bitmap's word popcounts; a number is then that prefix plus a popcount within the
+// word (cluster_number). Which of the two is decided here on the device, from the root count, and the label
+// passes read the same count. (It replaces a flag per point and a three-launch scan over n + 1 words.)
+static constexpr int kRankCap = 4096;
+static constexpr int kNumberThreads = 1024;
+
+__global__ __launch_bounds__(kNumberThreads) void k_number(int n, const int32_t* __restrict__ roots,
+                                                           const int32_t* __restrict__ roots_cnt,
+                                                           int* __restrict__ min_orig,
+                                                           uint32_t* __restrict__ bits /*zeroed, n / 32 + 1*/,
+                                                           int32_t* __restrict__ wpre /*n / 32 + 1*/,
+                                                           int32_t* __restrict__ done /*zeroed*/,
+                                                           const GridPlan* __restrict__ plan) {
+  if (!plan->ok) return;
+  const int R = *roots_cnt;
+  const int t = threadIdx.x;
+  if (R <= kRankCap) {
+    if (blockIdx.x != 0) return;
+    __shared__ unsigned long long key[kRankCap];
+    int P = 2;
+    while (P < R) P <<= 1;
+    for (int i = t; i < P; i += kNumberThreads) {
+      unsigned long long k = ~0ull;
+      if (i < R) {
+        const int r = roots[i];
+        k = (static_cast<unsigned long long>(min_orig[r]) << 32) | static_cast<uint32_t>(r);
+      }
+      key[i] = k;
+    }
+    __syncthreads();
+    // bitonic sort of P keys (the smallest indices are distinct: so are the keys)
+    for (int k = 2; k <= P; k <<= 1)
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        for (int i = t; i < P; i += kNumberThreads) {
+          const int l = i ^ j;
+          if (l > i) {
+            const unsigned long long a = key[i], b = key[l];
+            if ((a > b) == ((i & k) == 0)) {
+              key[i] = b;
+              key[l] = a;
+            }
+          }
+        }
+        __syncthreads();
+      }
+    for (int i = t; i < R; i += kNumberThreads) min_orig[static_cast<uint32_t>(key[i])] = i;
+    return;
+  }
+  for (int i = blockIdx.x * kNumberThreads + t; i < R; i += gridDim.x * kNumberThreads) {
+    const int v = min_orig[roots[i]];
+    __hip_atomic_fetch_or(bits + (v >> 5), 1u << (v & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  // the last block to get here sees every mark
+  __shared__ int last;
+  __threadfence();
+  __syncthreads();
+  if (t == 0) last = atomicAdd(done, 1) == int(gridDim.x) - 1;
+  __syncthreads();
+  if (!last) return;
+  __threadfence();
+  // exclusive prefix of the words' popcounts, 16 consecutive words per thread and round
+  __shared__ int wsum[kNumberThreads / 64];
+  const int lane = t & 63, wv = t >> 6;
+  const int nw = n / 32 + 1;
+  int carry = 0;
+  for (int w0 = 0; w0 < nw; w0 += 16 * kNumberThreads) {
+    const int i0 = w0 + 16 * t;
+    int cnt[16], sum = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      cnt[k] = i0 + k < nw ? __popc(__hip_atomic_load(bits + i0 + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) : 0;
+      sum += cnt[k];
+    }
+    int incl = sum;  // inclusive scan over the wave
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int o = __shfl_up(incl, off, 64);
+      if (lane >= off) incl += o;
+    }
+    if (lane == 63) wsum[wv] = incl;
+    __syncthreads();
+    int before = carry, total = 0;
+    for (int k = 0; k < kNumberThreads / 64; ++k) {
+      before += k < wv ? wsum[k] : 0;
+      total += wsum[k];
+    }
+    int run = before + incl - sum;
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+      if (i0 + k < nw) {
+        wpre[i0 + k] = run;
+        run += cnt[k];
+      }
+    carry += total;
+    __syncthreads();  // wsum is rewritten next round
+  }
 }
 
-__global__ __launch_bounds__(256) void k_mark_roots(int n, const uint8_t* __restrict__ core,
-                                                    const int* __restrict__ parent,
-                                                    const int* __restrict__ min_orig,
-                                                    int32_t* __restrict__ flag) {
-  int p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= n || !core[p]) return;
-  if (parent[p] == p) flag[min_orig[p]] = 1;
+// The cluster number of a component from what k_number left in min_orig[root] (or the smallest index of the
+// component's points among its neighbours, for the border pass: the numbering keeps the order of the indices).
+__device__ __forceinline__ int cluster_number(int v, int n_roots, const uint32_t* __restrict__ bits,
+                                              const int32_t* __restrict__ wpre) {
+  if (n_roots <= kRankCap) return v;  // already the number
+  return wpre[v >> 5] + __popc(bits[v >> 5] & ((1u << (v & 31)) - 1u));
 }
 
 // Labels of the core points; the others (noise and border candidates, a few percent) are
@@ -718,7 +911,9 @@ __global__ __launch_bounds__(256) void k_mark_roots(int n, const uint8_t* __rest
 __global__ __launch_bounds__(1024) void k_labels(int n, const uint8_t* __restrict__ core,
                                                  const int* __restrict__ parent,
                                                  const int* __restrict__ min_orig,
-                                                 const int32_t* __restrict__ rank,
+                                                 const int32_t* __restrict__ roots_cnt,
+                                                 const uint32_t* __restrict__ bits,
+                                                 const int32_t* __restrict__ wpre,
                                                  const int32_t* __restrict__ order,
                                                  int64_t* __restrict__ labels,
                                                  uint8_t* __restrict__ is_core,
@@ -728,25 +923,12 @@ __global__ __launch_bounds__(1024) void k_labels(int n, const uint8_t* __restric
   int p = blockIdx.x * 1024 + threadIdx.x;
   const bool live = p < n;
   const bool is_c = live && core[p];
-  if (is_c) labels[order[p]] = int64_t(rank[min_orig[parent[p]]]);
-  if (live && is_core) is_core[order[p]] = is_c;
-  // block-aggregated append: one atomic per 1024 threads (atomics on one address are served one at a time)
-  __shared__ int wcount[16], wbase[16];
-  const unsigned long long nb = __ballot(live && !is_c);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) wcount[w] = __popcll(nb);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int tot = 0;
-    for (int k = 0; k < 16; ++k) tot += wcount[k];
-    int base = tot ? atomicAdd(rest_cnt, tot) : 0;
-    for (int k = 0; k < 16; ++k) {
-      wbase[k] = base;
-      base += wcount[k];
-    }
+  if (is_c) {
+    const int v = min_orig[parent[parent[p]]];  // point -> representative -> root
+    labels[order[p]] = int64_t(cluster_number(v, *roots_cnt, bits, wpre));
   }
-  __syncthreads();
-  if (live && !is_c) rest[wbase[w] + __popcll(nb & ((1ull << lane) - 1ull))] = p;
+  if (live && is_core) is_core[order[p]] = is_c;
+  block_append<1024>(live && !is_c, p, rest, rest_cnt);
 }
 
 // One WAVE per non-core point: smallest cluster number among its core neighbours, or -1.
@@ -759,12 +941,15 @@ __global__ __launch_bounds__(256) void k_labels_border(const int32_t* __restrict
                                                        const uint8_t* __restrict__ core,
                                                        const int* __restrict__ parent,
                                                        const int* __restrict__ min_orig,
-                                                       const int32_t* __restrict__ rank,
+                                                       const int32_t* __restrict__ roots_cnt,
+                                                       const uint32_t* __restrict__ bits,
+                                                       const int32_t* __restrict__ wpre,
                                                        const int32_t* __restrict__ order,
                                                        int64_t* __restrict__ labels) {
   if (!plan->ok) return;
   const Stencil st = plan_stencil(plan);
   const int m = *rest_cnt;
+  const int n_roots = *roots_cnt;
   const int lane = threadIdx.x & 63;
   for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < m; i += gridDim.x * 4) {  // wave-uniform
     const int p = rest[i];
@@ -778,7 +963,7 @@ __global__ __launch_bounds__(256) void k_labels_border(const int32_t* __restrict
       if (g < t.pre[9]) {
         const int q = t.at(g);
         if (core[q] && co.d2(q, x, y, z) <= r2) {
-          const int mo = min_orig[parent[q]];
+          const int mo = min_orig[parent[parent[q]]];
           best = mo < best ? mo : best;
         }
       }
@@ -788,15 +973,16 @@ __global__ __launch_bounds__(256) void k_labels_border(const int32_t* __restrict
       const int o = __shfl_xor(best, off, 64);
       best = o < best ? o : best;
     }
-    if (lane == 0) labels[order[p]] = best == kNoRoot ? int64_t(-1) : int64_t(rank[best]);
+    if (lane == 0)
+      labels[order[p]] = best == kNoRoot ? int64_t(-1) : int64_t(cluster_number(best, n_roots, bits, wpre));
   }
 }
 
 // Core flags, union-find and labels over a binned cloud. The kernels read the grid from d_plan.
-// *flag_out: the cluster numbering (flag[n] = the number of clusters once the step has run).
+// *count_out: where the number of clusters lies on the device once the step has run.
 static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool radius_inclusive, const DevGrid& g,
                           const SubCells& sub, const GridPlan* d_plan, int64_t* labels, uint8_t* is_core,
-                          int32_t** flag_out) {
+                          const int32_t** count_out) {
   // the sub-cell shortcuts need cells of edge eps (not doubled to fit the dense grid)
   const bool fine = g.cell <= eps * (1.0 + 1.0 / 524288.0);
   const int N = int(n);
@@ -809,11 +995,15 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
   const double r2 = radius_inclusive ? eps * eps : nextafter(eps * eps, 0.0);
   uint8_t* core;
   int *parent, *min_orig;
-  int32_t* flag;
+  int32_t* flag;  // [n + 1], zeroed by k_core_tiled: the bitmap of k_number's large-count numbering
   PQ_TRY(c->arena.get(size_t(n), &core));
   PQ_TRY(c->arena.get(size_t(n), &parent));
   PQ_TRY(c->arena.get(size_t(n), &min_orig));
   PQ_TRY(c->arena.get(size_t(n) + 1, &flag));
+  uint32_t* const bits = reinterpret_cast<uint32_t*>(flag);
+  int32_t *roots, *wpre;  // the components' roots; k_number's word prefix (n / 32 + 1)
+  PQ_TRY(c->arena.get(size_t(n), &roots));
+  PQ_TRY(c->arena.get(size_t(n / 32) + 1, &wpre));
   int4* list;
   int32_t* list_cnt;
   int* run_min;
@@ -821,9 +1011,10 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
   PQ_TRY(c->arena.get(size_t(n), &list));
   int4* list_xyz;  // [n] grid coordinates and octant of every listed sub-cell
   PQ_TRY(c->arena.get(size_t(n), &list_xyz));
-  // [0] listed sub-cells, [1] stragglers of the core pass, [2] scratch of the union phase, [3] non-core
+  // [0] listed sub-cells, [1] roots (= clusters), [2] blocks k_number has seen finish, [3] non-core
   // points of the label pass. The binning leaves four zeroed ints behind for this (no memset launches).
   list_cnt = sub.zeroed4;
+  int32_t* const roots_cnt = list_cnt + 1;
   int32_t* rest;
   // (the core pass's stragglers come in kRestSegs segments of seg_cap entries; the label pass reuses the
   // array as one list of at most n)
@@ -865,8 +1056,8 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
   }
   {
     ProfScope ps(c, "dbscan_union");
-    // (parent / min_orig / flag were initialised by k_core_tiled; list_cnt[0] and [2] are still the zeros
-    // the binning left)
+    // (parent / min_orig / flag were initialised by k_core_tiled; list_cnt[0..2] are still the zeros the
+    // binning left)
     if (fine) {
       hipLaunchKernelGGL(k_sub_rep, dim3(ceil_div(n, 1024)), dim3(1024), 0, c->stream, N, sub.sub_of, core,
                          g.order, parent, g.cell_of, sub.rec, run_min, list, list_cnt, d_plan, list_xyz);
@@ -946,35 +1137,37 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
                                   pk.stop, 0, list, list_cnt, nbr, sub.sub_of, sub.rec, co, r2, core, parent);
           });
         }
-        hipLaunchKernelGGL(k_rep_min, gl, block, 0, c->stream, list, list_cnt, parent, run_min, min_orig);
+        hipLaunchKernelGGL(k_rep_root, gl, block, 0, c->stream, list, list_cnt, parent, run_min, min_orig, roots,
+                           roots_cnt);
       }
       PQ_HIP(hipGetLastError());
-      hipLaunchKernelGGL(k_flatten, grid, block, 0, c->stream, N, core, parent, min_orig, flag, d_plan);
     } else {
       on_coords(g, [&](auto co) {
         hipLaunchKernelGGL(k_union_points<decltype(co)>, grid, block, 0, c->stream, N, st, g.start, g.cell_of, co,
                            r2, core, parent);
       });
-      hipLaunchKernelGGL(k_flatten, grid, block, 0, c->stream, N, core, parent, static_cast<const int*>(nullptr),
-                         static_cast<int32_t*>(nullptr), d_plan);
-      hipLaunchKernelGGL(k_point_min, grid, block, 0, c->stream, N, core, parent, g.order, min_orig);
-      hipLaunchKernelGGL(k_mark_roots, grid, block, 0, c->stream, N, core, parent, min_orig, flag);
+      hipLaunchKernelGGL(k_flatten, grid, block, 0, c->stream, N, core, parent, d_plan);
+      hipLaunchKernelGGL(k_point_min, grid, block, 0, c->stream, N, core, parent, g.order, min_orig, roots,
+                         roots_cnt, d_plan);
     }
+    // one workgroup numbers up to kRankCap clusters; more take the bitmap, a block per CU at most
+    hipLaunchKernelGGL(k_number, dim3(std::min<int64_t>(ceil_div(n, kNumberThreads), c->cu_count)),
+                       dim3(kNumberThreads), 0, c->stream, N, roots, roots_cnt, min_orig, bits, wpre, list_cnt + 2,
+                       d_plan);
     PQ_HIP(hipGetLastError());
-    PQ_TRY(exclusive_scan_i32(c, flag, n + 1));
   }
   {
     ProfScope ps(c, "dbscan_label");
-    hipLaunchKernelGGL(k_labels, dim3(ceil_div(n, 1024)), dim3(1024), 0, c->stream, N, core, parent, min_orig, flag, g.order,
-                       labels, is_core, rest, list_cnt + 3, d_plan);
+    hipLaunchKernelGGL(k_labels, dim3(ceil_div(n, 1024)), dim3(1024), 0, c->stream, N, core, parent, min_orig,
+                       roots_cnt, bits, wpre, g.order, labels, is_core, rest, list_cnt + 3, d_plan);
     on_coords(g, [&](auto co) {
       hipLaunchKernelGGL(k_labels_border<decltype(co)>, dim3(std::min<int64_t>(8192, ceil_div(n, 64))), block, 0,
                          c->stream, rest, list_cnt + 3, d_plan, g.start, g.cell_of, co, r2, core, parent, min_orig,
-                         flag, g.order, labels);
+                         roots_cnt, bits, wpre, g.order, labels);
     });
     PQ_HIP(hipGetLastError());
   }
-  *flag_out = flag;
+  *count_out = roots_cnt;
   return 0;
 }
 
@@ -1016,14 +1209,14 @@ static int dbscan_device(Ctx* c, const double* xyz, int64_t n, double eps, int32
   const PlanHint hint = speculate ? c->plan_hint : PlanHint{};
   DevGrid g;
   SubCells sub;
-  int32_t* flag = nullptr;
+  const int32_t* count = nullptr;
   std::optional<ProfScope> bin_scope(std::in_place, c, "dbscan_bin");
   PQ_TRY(plan_grid_device(c, xyz, n, cell, max_cells, hint, d_plan, h_plan, c->plan_ev, zeroed, octant_zeroed_ints()));
   const Arena::Mark mark = c->arena.mark();
   if (speculate) {
     PQ_TRY(bin_octants_planned(c, xyz, n, cell, hint, d_plan, zeroed, &g, &sub));
     bin_scope.reset();
-    PQ_TRY(cluster_binned(c, n, eps, min_pts, radius_inclusive, g, sub, d_plan, labels, is_core, &flag));
+    PQ_TRY(cluster_binned(c, n, eps, min_pts, radius_inclusive, g, sub, d_plan, labels, is_core, &count));
   }
   PQ_HIP(hipEventSynchronize(c->plan_ev));
   const bool hit = speculate && h_plan[0].ok;
@@ -1036,7 +1229,7 @@ static int dbscan_device(Ctx* c, const double* xyz, int64_t n, double eps, int32
     PQ_TRY(bin_octants_host(c, xyz, n, cell, max_cells, h_plan[0], zeroed, &h_plan[1], d_plan + 1, &g, &sub, &next));
     bin_scope.reset();
     if (next.valid) c->plan_hint = next;  // (a grid of another kind keeps the hint there is)
-    PQ_TRY(cluster_binned(c, n, eps, min_pts, radius_inclusive, g, sub, d_plan + 1, labels, is_core, &flag));
+    PQ_TRY(cluster_binned(c, n, eps, min_pts, radius_inclusive, g, sub, d_plan + 1, labels, is_core, &count));
   }
   if (c->prof >= 1) {
     c->timers["dbscan_f32_records"].launches += g.p4 ? 1 : 0;  // which storage form ran
@@ -1044,7 +1237,7 @@ static int dbscan_device(Ctx* c, const double* xyz, int64_t n, double eps, int32
   }
   if (n_clusters) {
     int32_t h = 0;
-    PQ_HIP(hipMemcpyAsync(&h, flag + n, 4, hipMemcpyDeviceToHost, c->stream));
+    PQ_HIP(hipMemcpyAsync(&h, count, 4, hipMemcpyDeviceToHost, c->stream));
     PQ_HIP(hipStreamSynchronize(c->stream));
     *n_clusters = h;
   }
