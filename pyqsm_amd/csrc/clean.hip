@@ -302,22 +302,6 @@ __global__ __launch_bounds__(256) void k_stat_mask(const double* __restrict__ av
   keep[i] = (a > 0 && a < thr) ? 1 : 0;
 }
 
-// pos = scanned mask: kept indices ascending (idx, may be null) and the kept points gathered
-// into a fresh contiguous array (out_xyz, may be null)
-__global__ __launch_bounds__(256) void k_stat_compact(const int32_t* __restrict__ pos, int n, const double* __restrict__ xyz,
-                                                      int64_t* __restrict__ idx, double* __restrict__ out_xyz) {
-  const int i = int(blockIdx.x) * 256 + int(threadIdx.x);
-  if (i >= n) return;
-  const int p = pos[i];
-  if (pos[i + 1] == p) return;
-  if (idx) idx[p] = i;
-  if (out_xyz) {
-    out_xyz[size_t(p) * 3] = xyz[size_t(i) * 3];
-    out_xyz[size_t(p) * 3 + 1] = xyz[size_t(i) * 3 + 1];
-    out_xyz[size_t(p) * 3 + 2] = xyz[size_t(i) * 3 + 2];
-  }
-}
-
 // ---- device-resident steps -------------------------------------------------------------------
 struct VoxelDev {
   int64_t m = 0;                    // voxels (host)
@@ -420,9 +404,10 @@ static int voxel_means(Ctx* c, const double* xyz, const double* rgb, int64_t n, 
 }
 
 // Statistical outlier removal of the n points at xyz (device). Writes avg [n] (arena when null),
-// stats [3] = (mean, std, thr) and the scanned keep mask pos [n+1] (pos[n] = kept count).
+// stats [3] = (mean, std, thr), the kept indices ascending (keep, may be null), the kept points
+// (out_xyz, may be null) and the scanned keep mask pos [n+1] (pos[n] = kept count).
 static int stat_device(Ctx* c, const double* xyz, int64_t n, int32_t nb, double ratio, double* avg, double* stats,
-                       int32_t** pos_out) {
+                       int64_t* keep, double* out_xyz, int32_t** pos_out) {
   const int N = int(n);
   const int k = int(std::min<int64_t>(nb, n));
   if (k > kKnnMaxK) return fail(PYQSM_ERANGE, "nb_neighbors must be at most %d", kKnnMaxK);
@@ -453,7 +438,7 @@ static int stat_device(Ctx* c, const double* xyz, int64_t n, int32_t nb, double 
     ProfScope ps(c, "clean_compact");
     hipLaunchKernelGGL(k_stat_mask, dim3(ceil_div(n + 1, 256)), dim3(256), 0, c->stream, avg, N, stats, pos);
     PQ_HIP(hipGetLastError());
-    PQ_TRY(exclusive_scan_i32(c, pos, n + 1));
+    PQ_TRY(compact_flagged(c, pos, n, keep, nullptr, xyz, out_xyz));
   }
   *pos_out = pos;
   return 0;
@@ -574,10 +559,7 @@ int pyqsm_stat_outlier(const double* xyz, int64_t n, int32_t nb_neighbors, doubl
   if (avg) PQ_TRY(c->arena.get(size_t(n), &d_avg));
   PQ_HIP(hipMemcpyAsync(d_xyz, xyz, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
   int32_t* pos;
-  PQ_TRY(stat_device(c, d_xyz, n, nb_neighbors, std_ratio, d_avg, d_stats, &pos));
-  hipLaunchKernelGGL(k_stat_compact, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, pos, int(n),
-                     static_cast<const double*>(d_xyz), d_keep, static_cast<double*>(nullptr));
-  PQ_HIP(hipGetLastError());
+  PQ_TRY(stat_device(c, d_xyz, n, nb_neighbors, std_ratio, d_avg, d_stats, d_keep, nullptr, &pos));
   int32_t cnt = 0;
   PQ_HIP(hipMemcpyAsync(&cnt, pos + n, 4, hipMemcpyDeviceToHost, c->stream));
   if (avg) PQ_HIP(hipMemcpyAsync(avg, d_avg, size_t(n) * 8, hipMemcpyDeviceToHost, c->stream));
@@ -629,13 +611,7 @@ int pyqsm_clean_cloud(const double* xyz, int64_t n, double voxel_size, double ne
       PQ_TRY(c->arena.get(4, &stats));
       const Arena::Mark mk = c->arena.mark();
       int32_t* pos;
-      PQ_TRY(stat_device(c, cur, m, int32_t(nb), r, nullptr, stats, &pos));
-      {
-        ProfScope ps(c, "clean_compact");
-        hipLaunchKernelGGL(k_stat_compact, dim3(ceil_div(m, 256)), dim3(256), 0, c->stream, pos, int(m), cur,
-                           static_cast<int64_t*>(nullptr), next);
-        PQ_HIP(hipGetLastError());
-      }
+      PQ_TRY(stat_device(c, cur, m, int32_t(nb), r, nullptr, stats, nullptr, next, &pos));
       int32_t cnt = 0;
       PQ_HIP(hipMemcpyAsync(&cnt, pos + m, 4, hipMemcpyDeviceToHost, c->stream));
       PQ_HIP(hipStreamSynchronize(c->stream));

@@ -163,6 +163,15 @@ int laplacian_device(Ctx* c, const double* d_xyz, int64_t n, const int64_t* seg_
 // Exclusive prefix sum of n int32 values, in place, on the stream (scan.hip).
 int exclusive_scan_i32(Ctx* c, int32_t* data, int64_t n);
 
+// Selects the flagged rows (scan.hip). flags [n + 1], written by the caller's predicate kernel,
+// flags[n] == 0: scanned in place, so the count is left in flags[n] (on the device). For every
+// flagged i, in ascending order, writes idx[p] = src_idx ? src_idx[i] : i and copies row i of
+// a / b ([n,3] f64) to row p of out_a / out_b. idx, a / out_a and b / out_b may be null.
+// Enqueues only: no read-back, no synchronisation.
+int compact_flagged(Ctx* c, int32_t* flags, int64_t n, int64_t* idx, const int64_t* src_idx = nullptr,
+                    const double* a = nullptr, double* out_a = nullptr, const double* b = nullptr,
+                    double* out_b = nullptr);
+
 // Stable sort of n (key, value) pairs by the low `bits` bits of the key (scan.hip: radix passes
 // without global atomics, so the order is reproducible). *keys / *vals are the inputs and, on
 // return, point at the sorted arrays (the inputs themselves or arena buffers of the same size).

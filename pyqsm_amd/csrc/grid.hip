@@ -128,23 +128,6 @@ __global__ __launch_bounds__(256) void k_bbox_fold(const unsigned long long* __r
   }
 }
 
-struct GridParams {
-  double minx, miny, minz, inv_cell;
-  int nx, ny, nz;
-};
-
-__device__ __forceinline__ int cell_index(const GridParams& g, double x, double y, double z) {
-  // interior cells are 1 .. n-2; the clamp guards the max-boundary point and puts points outside
-  // the grid's box into its outermost cells — clamped in double, so that a point a light year
-  // away does not overflow the int
-  const double fx = floor((x - g.minx) * g.inv_cell), fy = floor((y - g.miny) * g.inv_cell),
-               fz = floor((z - g.minz) * g.inv_cell);
-  const int cx = int(fmin(fmax(fx, 0.0), double(g.nx - 3))) + 1;
-  const int cy = int(fmin(fmax(fy, 0.0), double(g.ny - 3))) + 1;
-  const int cz = int(fmin(fmax(fz, 0.0), double(g.nz - 3))) + 1;
-  return (cz * g.ny + cy) * g.nx + cx;
-}
-
 __global__ __launch_bounds__(256) void k_cell_count(const double* __restrict__ xyz, int64_t n,
                                                     GridParams g, int32_t* __restrict__ counts,
                                                     int32_t* __restrict__ cell_tmp,
@@ -443,7 +426,7 @@ int build_grid(Ctx* c, const double* xyz, int64_t n, double min_cell, int64_t ma
   PQ_TRY(c->arena.get(size_t(n), &cell_tmp));
   PQ_TRY(c->arena.get(size_t(n), &rank_tmp));
   PQ_HIP(hipMemsetAsync(g->start, 0, (size_t(g->ncell) + 1) * 4, c->stream));
-  GridParams gp{g->minx, g->miny, g->minz, g->inv_cell, g->nx, g->ny, g->nz};
+  const GridParams gp = grid_params(*g);
   const dim3 grid(ceil_div(n, 256));
   g->occ_blocks = int(grid.x);
   PQ_TRY(c->arena.get(size_t(g->occ_blocks), &g->occ_part));
@@ -542,7 +525,7 @@ int subsort_octants(Ctx* c, DevGrid* g, int64_t n, SubCells* sub) {
   PQ_TRY(c->arena.get(size_t(n), &sy2));
   PQ_TRY(c->arena.get(size_t(n), &sz2));
   PQ_HIP(hipMemsetAsync(sub->sub_cnt, 0, size_t(n) * 32, c->stream));
-  GridParams gp{g->minx, g->miny, g->minz, g->inv_cell, g->nx, g->ny, g->nz};
+  const GridParams gp = grid_params(*g);
   const dim3 grid(ceil_div(n, 256)), blk(256);
   hipLaunchKernelGGL(k_sub_count, grid, blk, 0, c->stream, int(n), gp, g->start, g->cell_of, g->sx,
                      g->sy, g->sz, sub->sub_cnt, oct_rank);
@@ -1301,7 +1284,7 @@ static int build_grid_bucketed(Ctx* c, const double* xyz, int64_t n, DevGrid* g)
   g->occ_blocks = int(nbk);
   PQ_TRY(c->arena.get(size_t(nbk), &g->occ_part));
   PQ_HIP(hipMemsetAsync(tot, 0, size_t(nbk) * 8, c->stream));
-  GridParams gp{g->minx, g->miny, g->minz, g->inv_cell, g->nx, g->ny, g->nz};
+  const GridParams gp = grid_params(*g);
   const dim3 ga(ceil_div(n, kBkPts)), blk(256);
   const size_t lds = size_t(nbk) * 4;
   const int fused = nbk <= kBkFusedScan;
@@ -1593,7 +1576,7 @@ int bin_octants_host(Ctx* c, const double* xyz, int64_t n, double min_cell, int6
   hp.all_f32 = all_f32 && bucketed_path;  // fp32 records (round 2's path keeps fp64 arrays)
   hp.ok = 1;
   PQ_TRY(upload_plan(c, hp, h_up, d_plan));
-  GridParams gp{g->minx, g->miny, g->minz, g->inv_cell, g->nx, g->ny, g->nz};
+  const GridParams gp = grid_params(*g);
   if (bucketed_path) {
     PQ_TRY(enqueue_bucketed(c, xyz, n, gp, raw, am, mapped, g->ncell, nbk, bits, hp.all_f32, zeroed, d_plan, g, sub));
     // the kind of grid the bounding box's fold can plan: a hint with some headroom on the directory

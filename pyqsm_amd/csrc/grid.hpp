@@ -33,6 +33,56 @@ struct DevGrid {
   int occ_blocks = 0;
 };
 
+// ---- the grid's geometry, as kernels take it by value -----------------------------------------
+struct GridParams {
+  double minx, miny, minz, inv_cell;
+  int nx, ny, nz;
+};
+inline GridParams grid_params(const DevGrid& g) { return GridParams{g.minx, g.miny, g.minz, g.inv_cell, g.nx, g.ny, g.nz}; }
+
+// The cell a point is binned into, and the cell every lookup of it must use: interior cells are
+// 1 .. n-2; the clamp guards the max-boundary point and puts points outside the grid's box into its
+// outermost cells — clamped in double, so that a point a light year away does not overflow the int.
+// A clamp moves no two points further apart, so whatever lies within a cell edge of a point outside
+// the box still sits in the 27 cells around its clamped cell.
+__device__ __forceinline__ void clamped_cell(const GridParams& g, double x, double y, double z, int* cx, int* cy,
+                                             int* cz) {
+  const double fx = floor((x - g.minx) * g.inv_cell), fy = floor((y - g.miny) * g.inv_cell),
+               fz = floor((z - g.minz) * g.inv_cell);
+  *cx = int(fmin(fmax(fx, 0.0), double(g.nx - 3))) + 1;
+  *cy = int(fmin(fmax(fy, 0.0), double(g.ny - 3))) + 1;
+  *cz = int(fmin(fmax(fz, 0.0), double(g.nz - 3))) + 1;
+}
+
+__device__ __forceinline__ int cell_index(const GridParams& g, double x, double y, double z) {
+  int cx, cy, cz;
+  clamped_cell(g, x, y, z, &cx, &cy, &cz);
+  return (cz * g.ny + cy) * g.nx + cx;
+}
+
+// The 27-cell stencil of a point as nine runs [qb[w], qe[w]) of sorted positions, one per (y,z) row
+// (empty for rows outside the grid).
+struct StencilRuns {
+  int qb[9], qe[9];
+};
+
+__device__ __forceinline__ void point_stencil_runs(const GridParams& g, const int32_t* __restrict__ start, double x,
+                                                   double y, double z, StencilRuns* rr) {
+  int cx, cy, cz;
+  clamped_cell(g, x, y, z, &cx, &cy, &cz);
+  int w = 0;
+  for (int dz = -1; dz <= 1; ++dz)
+    for (int dy = -1; dy <= 1; ++dy, ++w) {
+      const int zz = cz + dz, yy = cy + dy;
+      rr->qb[w] = rr->qe[w] = 0;
+      if (zz < 0 || zz >= g.nz || yy < 0 || yy >= g.ny) continue;
+      const int x0 = cx - 1 < 0 ? 0 : cx - 1, x1 = cx + 1 >= g.nx ? g.nx - 1 : cx + 1;
+      const int row = (zz * g.ny + yy) * g.nx;
+      rr->qb[w] = start[row + x0];
+      rr->qe[w] = start[row + x1 + 1];
+    }
+}
+
 // Builds the grid for n points (f64 [n,3], device) with cells of at least
 // `min_cell` edge (the edge is doubled until the dense grid has at most
 // `max_cells` cells). All arrays come from the context arena. Synchronises the

@@ -72,12 +72,6 @@ __global__ __launch_bounds__(256) void k_outside(const double* __restrict__ xyz,
   flags[i] = out ? 1 : 0;
 }
 
-__global__ __launch_bounds__(256) void k_outside_list(int64_t n, const int32_t* __restrict__ pos,
-                                                      int64_t* __restrict__ idx) {
-  const int64_t i = blockIdx.x * 256ll + threadIdx.x;
-  if (i < n && pos[i + 1] != pos[i]) idx[pos[i]] = i;
-}
-
 }  // namespace pyqsm
 
 using namespace pyqsm;
@@ -144,12 +138,9 @@ int pyqsm_outside_halfspaces(const double* xyz, int64_t n, const double* eq, int
     for (int a = 0; a < 4; ++a) hp.eq[f][a] = eq[4 * f + a];
   PQ_HIP(hipMemcpyAsync(d_xyz, xyz, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
   PQ_HIP(hipMemcpyAsync(d_pl, &hp, sizeof(Planes), hipMemcpyHostToDevice, c->stream));
-  const dim3 g(ceil_div(n + 1, 256)), blk(256);
-  hipLaunchKernelGGL(k_outside, g, blk, 0, c->stream, d_xyz, n, d_pl, margin, d_flags);
+  hipLaunchKernelGGL(k_outside, dim3(ceil_div(n + 1, 256)), dim3(256), 0, c->stream, d_xyz, n, d_pl, margin, d_flags);
   PQ_HIP(hipGetLastError());
-  PQ_TRY(exclusive_scan_i32(c, d_flags, n + 1));
-  hipLaunchKernelGGL(k_outside_list, g, blk, 0, c->stream, n, d_flags, d_idx);
-  PQ_HIP(hipGetLastError());
+  PQ_TRY(compact_flagged(c, d_flags, n, d_idx));
   int32_t m = 0;
   PQ_HIP(hipMemcpyAsync(&m, d_flags + n, 4, hipMemcpyDeviceToHost, c->stream));
   PQ_HIP(hipStreamSynchronize(c->stream));  // hp may go

@@ -20,7 +20,7 @@
 // silhouette: 256 consecutive values per chunk, lane l of a wave holding values 4l..4l+3 summed
 // as ((v0 + v1) + v2) + v3, then an xor butterfly over the 64 lanes (pairs of neighbours first);
 // the chunk totals are added one at a time from 0.0 in chunk order.
-#include "common.hpp"
+#include "grid.hpp"  // sqdist3
 
 #include <cmath>
 
@@ -297,26 +297,9 @@ __global__ __launch_bounds__(256) void k_ball_excl_flags(int64_t n, const double
   if (i > n) return;
   int32_t f = 0;
   if (i < n && !found[i]) {
-    const double t0 = xyz[3 * i] - cx, t1 = xyz[3 * i + 1] - cy, t2 = xyz[3 * i + 2] - cz;
-    double d = t0 * t0;
-    d = d + t1 * t1;
-    d = d + t2 * t2;
-    f = d <= r2;
+    f = sqdist3(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], cx, cy, cz) <= r2;
   }
   flags[i] = f;
-}
-
-__global__ __launch_bounds__(256) void k_ball_excl_compact(int64_t n, const double* __restrict__ xyz,
-                                                           const int32_t* __restrict__ pos,
-                                                           int64_t* __restrict__ idx,
-                                                           double* __restrict__ out_xyz) {
-  const int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
-  if (i >= n || pos[i + 1] == pos[i]) return;
-  const int64_t p = pos[i];
-  idx[p] = i;
-  out_xyz[3 * p] = xyz[3 * i];
-  out_xyz[3 * p + 1] = xyz[3 * i + 1];
-  out_xyz[3 * p + 2] = xyz[3 * i + 2];
 }
 
 __global__ __launch_bounds__(256) void k_mark_found(uint8_t* __restrict__ found, int64_t n,
@@ -558,10 +541,7 @@ int pyqsm_ball_excl_dev(const double* xyz_dev, int64_t n, const uint8_t* found_d
     ProfScope ps(c, "ball_excl");
     hipLaunchKernelGGL(k_ball_excl_flags, dim3(ceil_div(n + 1, 256)), dim3(256), 0, c->stream, n, xyz_dev,
                        found_dev, center[0], center[1], center[2], radius * radius, d_flags);
-    PQ_TRY(exclusive_scan_i32(c, d_flags, n + 1));
-    hipLaunchKernelGGL(k_ball_excl_compact, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, n, xyz_dev,
-                       d_flags, idx_dev, out_xyz_dev);
-    PQ_HIP(hipGetLastError());
+    PQ_TRY(compact_flagged(c, d_flags, n, idx_dev, nullptr, xyz_dev, out_xyz_dev));
   }
   int32_t total = 0;
   PQ_HIP(hipMemcpyAsync(&total, d_flags + n, 4, hipMemcpyDeviceToHost, c->stream));

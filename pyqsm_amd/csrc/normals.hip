@@ -38,38 +38,7 @@ static constexpr int kKnnMaxK = 192;          // knn.hip kMaxK: largest k of a K
 static constexpr int kNormMaxNN = 256;        // largest max_nn of a hybrid search
 static constexpr int kNormCap = 512;          // (d2, index) pairs a wave sorts in LDS
 
-struct NGrid {
-  double minx, miny, minz, inv;
-  int nx, ny, nz;
-};
-
 // ---- neighbourhoods and covariance --------------------------------------------------------------
-// The runs of sorted positions of the 27 cells around the query's cell, clamped into the grid the
-// way the points were binned (grid.hip: cell_index): the grid may cover less than the cloud (it is
-// built over the box without its sparse tails), and clamping moves no two points further apart.
-struct Runs {
-  int qb[9], qe[9];
-};
-
-__device__ __forceinline__ void cell_runs(const NGrid& g, const int32_t* __restrict__ start, double x, double y,
-                                          double z, Runs* rr) {
-  const double fx = floor((x - g.minx) * g.inv), fy = floor((y - g.miny) * g.inv), fz = floor((z - g.minz) * g.inv);
-  const int cx = int(fmin(fmax(fx, 0.0), double(g.nx - 3))) + 1;
-  const int cy = int(fmin(fmax(fy, 0.0), double(g.ny - 3))) + 1;
-  const int cz = int(fmin(fmax(fz, 0.0), double(g.nz - 3))) + 1;
-  int w = 0;
-  for (int dz = -1; dz <= 1; ++dz)
-    for (int dy = -1; dy <= 1; ++dy, ++w) {
-      const int zz = cz + dz, yy = cy + dy;
-      rr->qb[w] = rr->qe[w] = 0;
-      if (zz < 0 || zz >= g.nz || yy < 0 || yy >= g.ny) continue;
-      const int x0 = cx - 1 < 0 ? 0 : cx - 1, x1 = cx + 1 >= g.nx ? g.nx - 1 : cx + 1;
-      const int row = (zz * g.ny + yy) * g.nx;
-      rr->qb[w] = start[row + x0];
-      rr->qe[w] = start[row + x1 + 1];
-    }
-}
-
 __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -113,7 +82,7 @@ __device__ void covariance_of_list(int lane, int i, int cnt, const int* nb, cons
 // waves then read neighbouring cells). *overflow = 1 when more than kNormCap points tie at the
 // max_nn-th distance of some query (the result of that query is then not the contract's).
 template <class CO>
-__global__ __launch_bounds__(128) void k_normal_hybrid(int n, const double* __restrict__ xyz, NGrid g,
+__global__ __launch_bounds__(128) void k_normal_hybrid(int n, const double* __restrict__ xyz, GridParams g,
                                                        const int32_t* __restrict__ start,
                                                        const int32_t* __restrict__ order, CO co, double r2, int k,
                                                        double* __restrict__ cov, int32_t* __restrict__ cnt_out,
@@ -126,8 +95,8 @@ __global__ __launch_bounds__(128) void k_normal_hybrid(int n, const double* __re
   if (p >= n) return;  // whole wave
   const int i = order[p];
   const double x = xyz[3 * size_t(i)], y = xyz[3 * size_t(i) + 1], z = xyz[3 * size_t(i) + 2];
-  Runs rr;
-  cell_runs(g, start, x, y, z, &rr);
+  StencilRuns rr;  // clamped like the points were binned: the grid may cover less than the cloud
+  point_stencil_runs(g, start, x, y, z, &rr);
   auto count_le = [&](double tau) {  // candidates with d2 < r2 and d2 <= tau
     int cnt = 0;
     for (int r = 0; r < 9; ++r)
@@ -391,22 +360,6 @@ __global__ __launch_bounds__(256) void k_crop_mask(int n, const double* __restri
   keep[i] = i < n && xyz[3 * size_t(i) + 2] > bound ? 1 : 0;
 }
 
-// gathers the kept rows (pos = scanned mask) of xyz and, when given, of the normals, and their indices
-__global__ __launch_bounds__(256) void k_gather_kept(int n, const int32_t* __restrict__ pos,
-                                                     const double* __restrict__ a, const double* __restrict__ b,
-                                                     const int64_t* __restrict__ src_idx, double* __restrict__ oa,
-                                                     double* __restrict__ ob, int64_t* __restrict__ oidx) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const int p = pos[i];
-  if (pos[i + 1] == p) return;
-  for (int c = 0; c < 3; ++c) {
-    if (oa) oa[3 * size_t(p) + c] = a[3 * size_t(i) + c];
-    if (ob) ob[3 * size_t(p) + c] = b[3 * size_t(i) + c];
-  }
-  if (oidx) oidx[p] = src_idx ? src_idx[i] : int64_t(i);
-}
-
 // filter_by_norm: angle = degrees(atan(n_z / sqrt(n_x^2 + n_y^2))), 0 when n_x = n_y = 0; keep
 // -t < angle < t (rev: angle < -t or angle > t)
 __global__ __launch_bounds__(256) void k_angle_mask(int n, const double* __restrict__ nrm, double t, int rev,
@@ -458,11 +411,10 @@ static int normals_device(Ctx* c, const double* d_xyz, int64_t n, double radius,
       PQ_TRY(robust_box(c, d_xyz, n, int(std::min<int64_t>(8192, std::max<int64_t>(256, n / 256))), box, &outside));
       PQ_TRY(build_grid(c, d_xyz, n, radius * (1.0 + 1.0 / 1048576.0), int64_t(1) << 28, &g, box, all_f32));
     }
-    const NGrid ng{g.minx, g.miny, g.minz, g.inv_cell, g.nx, g.ny, g.nz};
     ProfScope ps(c, "normals_cov");
     on_coords(g, [&](auto co) {
-      hipLaunchKernelGGL(k_normal_hybrid<decltype(co)>, dim3(ceil_div(n, 2)), dim3(128), 0, c->stream, N, d_xyz, ng,
-                         g.start, g.order, co, radius * radius, int(max_nn), cov, cnt, overflow);
+      hipLaunchKernelGGL(k_normal_hybrid<decltype(co)>, dim3(ceil_div(n, 2)), dim3(128), 0, c->stream, N, d_xyz,
+                         grid_params(g), g.start, g.order, co, radius * radius, int(max_nn), cov, cnt, overflow);
     });
     PQ_HIP(hipGetLastError());
   } else {
@@ -668,23 +620,19 @@ int pyqsm_stem_cloud(const double* xyz, int64_t n, const double* prev_normals, d
   if (bound != 0.0) {
     ProfScope ps(c, "stem_crop");
     int32_t* pos;
+    double *nx, *np = nullptr;
     PQ_TRY(c->arena.get(size_t(n) + 1, &pos));
+    PQ_TRY(c->arena.get(size_t(n) * 3, &nx));
+    if (d_prev) PQ_TRY(c->arena.get(size_t(n) * 3, &np));
+    PQ_TRY(c->arena.get(size_t(n), &c_idx));
     hipLaunchKernelGGL(k_crop_mask, dim3(ceil_div(n + 1, 256)), dim3(256), 0, c->stream, N, d_xyz, bound, pos);
     PQ_HIP(hipGetLastError());
-    PQ_TRY(exclusive_scan_i32(c, pos, n + 1));
+    PQ_TRY(compact_flagged(c, pos, n, c_idx, nullptr, d_xyz, nx, d_prev, np));
     int32_t cnt = 0;
     PQ_HIP(hipMemcpyAsync(&cnt, pos + n, 4, hipMemcpyDeviceToHost, c->stream));
     PQ_HIP(hipStreamSynchronize(c->stream));
     m = cnt;
     if (m == 0) return 0;
-    double *nx, *np = nullptr;
-    PQ_TRY(c->arena.get(size_t(m) * 3, &nx));
-    if (d_prev) PQ_TRY(c->arena.get(size_t(m) * 3, &np));
-    PQ_TRY(c->arena.get(size_t(m), &c_idx));
-    hipLaunchKernelGGL(k_gather_kept, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, N,
-                       static_cast<const int32_t*>(pos), static_cast<const double*>(d_xyz),
-                       static_cast<const double*>(d_prev), static_cast<const int64_t*>(nullptr), nx, np, c_idx);
-    PQ_HIP(hipGetLastError());
     cxyz = nx;
     cprev = np;
   }
@@ -705,12 +653,7 @@ int pyqsm_stem_cloud(const double* xyz, int64_t n, const double* prev_normals, d
     hipLaunchKernelGGL(k_angle_mask, dim3(ceil_div(m + 1, 256)), dim3(256), 0, c->stream, int(m),
                        static_cast<const double*>(ori), angle_cutoff, 0, pos);
     PQ_HIP(hipGetLastError());
-    PQ_TRY(exclusive_scan_i32(c, pos, m + 1));
-    hipLaunchKernelGGL(k_gather_kept, dim3(ceil_div(m, 256)), dim3(256), 0, c->stream, int(m),
-                       static_cast<const int32_t*>(pos), static_cast<const double*>(ori),
-                       static_cast<const double*>(nullptr), static_cast<const int64_t*>(c_idx), k_nrm,
-                       static_cast<double*>(nullptr), k_idx);
-    PQ_HIP(hipGetLastError());
+    PQ_TRY(compact_flagged(c, pos, m, k_idx, c_idx, ori, k_nrm));
   }
   int32_t cnt = 0;
   PQ_HIP(hipMemcpyAsync(&cnt, pos + m, 4, hipMemcpyDeviceToHost, c->stream));

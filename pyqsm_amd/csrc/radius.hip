@@ -22,41 +22,12 @@
 
 namespace pyqsm {
 
-__device__ __forceinline__ double sqd(double ax, double ay, double az, double bx, double by,
-                                      double bz) {
-  double t0 = ax - bx, t1 = ay - by, t2 = az - bz;
-  double d = t0 * t0;
-  d = d + t1 * t1;
-  d = d + t2 * t2;
-  return d;
-}
-
 __global__ __launch_bounds__(256) void k_ball_flags(int64_t n, const double* __restrict__ xyz,
                                                     double cx, double cy, double cz, double r2,
                                                     int32_t* __restrict__ flags) {
   int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
   if (i > n) return;
-  flags[i] = i < n && sqd(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], cx, cy, cz) <= r2;
-}
-
-__global__ __launch_bounds__(256) void k_ball_compact(int64_t n, const int32_t* __restrict__ pos,
-                                                      int64_t* __restrict__ out) {
-  int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
-  if (i >= n) return;
-  if (pos[i + 1] != pos[i]) out[pos[i]] = i;
-}
-
-struct RGrid {
-  double minx, miny, minz, inv;
-  int nx, ny, nz;
-};
-
-__device__ __forceinline__ void clamped_cell(const RGrid& g, double x, double y, double z, int* cx, int* cy,
-                                             int* cz) {
-  const double fx = floor((x - g.minx) * g.inv), fy = floor((y - g.miny) * g.inv), fz = floor((z - g.minz) * g.inv);
-  *cx = int(fmin(fmax(fx, 0.0), double(g.nx - 3))) + 1;
-  *cy = int(fmin(fmax(fy, 0.0), double(g.ny - 3))) + 1;
-  *cz = int(fmin(fmax(fz, 0.0), double(g.nz - 3))) + 1;
+  flags[i] = i < n && sqdist3(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], cx, cy, cz) <= r2;
 }
 
 // MODE 0: count of source points with d2 < r2.  MODE 1: count with d2 <= tau.
@@ -64,13 +35,13 @@ __device__ __forceinline__ void clamped_cell(const RGrid& g, double x, double y,
 // MODE 3: as MODE 1, and *below = the largest d2 <= tau, *above = the smallest d2 > tau (both among
 //         the candidates with d2 < r2; -1 / +inf when there is none).
 template <int MODE, class CO>
-__device__ __forceinline__ int walk(const RGrid& g, const int32_t* __restrict__ start,
+__device__ __forceinline__ int walk(const GridParams& g, const int32_t* __restrict__ start,
                                     const int32_t* __restrict__ order,
                                     CO co, double x, double y, double z,
                                     double r2, double tau, int budget, uint8_t* __restrict__ mark,
                                     int32_t* __restrict__ lab_out = nullptr, int lab = 0,
                                     double* below = nullptr, double* above = nullptr) {
-  // The query's cell, clamped into the grid the way the sources were binned (grid.hip: cell_index):
+  // The query's cell, clamped into the grid the way the sources were binned (grid.hpp: clamped_cell):
   // the grid may cover less than the cloud (source_grid below), and a clamp moves no two points
   // further apart, so whatever is within the radius of a query outside still sits in the 27 cells
   // around its clamped cell; the distance test is on the true coordinates.
@@ -121,7 +92,7 @@ __device__ __forceinline__ int walk(const RGrid& g, const int32_t* __restrict__ 
 
 template <class CO>
 __global__ __launch_bounds__(256) void k_radius_mark(int m, const double* __restrict__ qry,
-                                                     RGrid g, const int32_t* __restrict__ start,
+                                                     GridParams g, const int32_t* __restrict__ start,
                                                      const int32_t* __restrict__ order,
                                                      CO co, double r2,
                                                      int k, uint8_t* __restrict__ mark,
@@ -183,7 +154,7 @@ __global__ __launch_bounds__(256) void k_radius_mark(int m, const double* __rest
 // In cell order the lanes of a wave walk the same few runs and their loads fall on shared lines
 // (100 k queries against 1 M sources: 4.8 -> 4.0 ms). Marks, labels (atomicMin) and the per-query
 // counts do not depend on the order in which the queries are served.
-__global__ __launch_bounds__(256) void k_query_keys(int m, const double* __restrict__ qry, RGrid g,
+__global__ __launch_bounds__(256) void k_query_keys(int m, const double* __restrict__ qry, GridParams g,
                                                     uint32_t* __restrict__ key, int32_t* __restrict__ ident) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= m) return;
@@ -193,7 +164,7 @@ __global__ __launch_bounds__(256) void k_query_keys(int m, const double* __restr
   ident[i] = i;
 }
 
-static int query_order(Ctx* c, const double* d_qry, int64_t m, const RGrid& rg, int64_t ncell, int32_t** perm) {
+static int query_order(Ctx* c, const double* d_qry, int64_t m, const GridParams& rg, int64_t ncell, int32_t** perm) {
   *perm = nullptr;
   const char* e = getenv("PYQSM_RADIUS_SORT");  // "0": serve the queries in the caller's order
   if (m < 1024 || (e && e[0] == '0')) return 0;
@@ -217,30 +188,8 @@ static int query_order(Ctx* c, const double* d_qry, int64_t m, const RGrid& rg, 
 // LDS, bitonic-sort them by (d2, index) and write k entries, padded with (inf, n).
 static constexpr int kKnnCap = 2048;  // largest k (LDS: 24 KB per wave)
 
-struct RowRuns {
-  int qb[9], qe[9];
-};
-
-__device__ __forceinline__ bool query_runs(const RGrid& g, const int32_t* __restrict__ start,
-                                           double x, double y, double z, RowRuns* rr) {
-  int cx, cy, cz;
-  clamped_cell(g, x, y, z, &cx, &cy, &cz);
-  int w = 0;
-  for (int dz = -1; dz <= 1; ++dz)
-    for (int dy = -1; dy <= 1; ++dy, ++w) {
-      const int zz = cz + dz, yy = cy + dy;
-      rr->qb[w] = rr->qe[w] = 0;
-      if (zz < 0 || zz >= g.nz || yy < 0 || yy >= g.ny) continue;
-      const int x0 = cx - 1 < 0 ? 0 : cx - 1, x1 = cx + 1 >= g.nx ? g.nx - 1 : cx + 1;
-      const int row = (zz * g.ny + yy) * g.nx;
-      rr->qb[w] = start[row + x0];
-      rr->qe[w] = start[row + x1 + 1];
-    }
-  return true;
-}
-
 template <class CO>
-__global__ __launch_bounds__(128) void k_radius_knn(int m, const double* __restrict__ qry, RGrid g,
+__global__ __launch_bounds__(128) void k_radius_knn(int m, const double* __restrict__ qry, GridParams g,
                                                     const int32_t* __restrict__ start,
                                                     const int32_t* __restrict__ order,
                                                     CO co, double r2, int k,
@@ -252,8 +201,8 @@ __global__ __launch_bounds__(128) void k_radius_knn(int m, const double* __restr
   const int i = blockIdx.x * 2 + w;
   if (i >= m) return;  // whole wave
   const double x = qry[3 * i], y = qry[3 * i + 1], z = qry[3 * i + 2];
-  RowRuns rr;
-  const bool inside = query_runs(g, start, x, y, z, &rr);
+  StencilRuns rr;
+  point_stencil_runs(g, start, x, y, z, &rr);
   // count of candidates with d2 < r2 and d2 <= tau
   auto count_le = [&](double tau) {
     int cnt = 0;
@@ -269,7 +218,7 @@ __global__ __launch_bounds__(128) void k_radius_knn(int m, const double* __restr
       }
     return cnt;
   };
-  int total = inside ? count_le(__builtin_inf()) : 0;
+  int total = count_le(__builtin_inf());
   double tau = __builtin_inf();
   int budget = 0;  // ties at tau that still fit
   if (total > k) {
@@ -388,10 +337,7 @@ int pyqsm_ball_query(const double* xyz, int64_t n, const double center[3], doubl
     ProfScope ps(c, "ball_query");
     hipLaunchKernelGGL(k_ball_flags, dim3(ceil_div(n + 1, 256)), dim3(256), 0, c->stream, n, d_xyz,
                        center[0], center[1], center[2], radius * radius, d_flags);
-    PQ_TRY(exclusive_scan_i32(c, d_flags, n + 1));
-    hipLaunchKernelGGL(k_ball_compact, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, n, d_flags,
-                       d_out);
-    PQ_HIP(hipGetLastError());
+    PQ_TRY(compact_flagged(c, d_flags, n, d_out));
   }
   int32_t total = 0;
   PQ_HIP(hipMemcpyAsync(&total, d_flags + n, 4, hipMemcpyDeviceToHost, c->stream));
@@ -431,7 +377,7 @@ int pyqsm_radius_mark(const double* src, int64_t n, const double* qry, int64_t m
   PQ_HIP(hipMemsetAsync(d_mark, 0, size_t(n), c->stream));
   DevGrid g;
   PQ_TRY(source_grid(c, d_src, n, radius, &g));
-  RGrid rg{g.minx, g.miny, g.minz, g.inv_cell, g.nx, g.ny, g.nz};
+  const GridParams rg = grid_params(g);
   {
     ProfScope ps(c, "radius_mark");
     int32_t* perm = nullptr;
@@ -481,7 +427,7 @@ int pyqsm_radius_knn(const double* src, int64_t n, const double* qry, int64_t m,
   PQ_HIP(hipMemcpyAsync(d_qry, qry, size_t(m) * 24, hipMemcpyHostToDevice, c->stream));
   DevGrid g;
   PQ_TRY(source_grid(c, d_src, n, radius, &g));
-  RGrid rg{g.minx, g.miny, g.minz, g.inv_cell, g.nx, g.ny, g.nz};
+  const GridParams rg = grid_params(g);
   {
     ProfScope ps(c, "radius_knn");
     on_coords(g, [&](auto co) {
@@ -531,7 +477,7 @@ int pyqsm_radius_label(const double* src, int64_t n, const double* qry, int64_t 
   PQ_HIP(hipMemsetAsync(d_lab, 0x7F, size_t(n) * 4, c->stream));  // 0x7F7F7F7F > any label
   DevGrid g;
   PQ_TRY(source_grid(c, d_src, n, radius, &g));
-  RGrid rg{g.minx, g.miny, g.minz, g.inv_cell, g.nx, g.ny, g.nz};
+  const GridParams rg = grid_params(g);
   {
     ProfScope ps(c, "radius_label");
     int32_t* perm = nullptr;

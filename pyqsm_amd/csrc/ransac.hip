@@ -169,16 +169,6 @@ __global__ __launch_bounds__(256) void k_flags(const double* __restrict__ pts, i
   flags[i] = model_dist<SHAPE>(m, pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]) <= thresh;
 }
 
-__global__ __launch_bounds__(256) void k_compact(int64_t n, const double* __restrict__ pts,
-                                                 const Model* __restrict__ models, int64_t best,
-                                                 double thresh, int shape,
-                                                 const int32_t* __restrict__ pos,
-                                                 int64_t* __restrict__ out) {
-  int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
-  if (i >= n) return;
-  if (pos[i + 1] != pos[i]) out[pos[i]] = i;
-}
-
 // ---- many independent fits in one call (pyqsm_ransac_batch) ---------------------------------
 
 // blockIdx.y = a tile of kTile points of one set (tile_set / tile_base list the tiles of all sets)
@@ -424,10 +414,7 @@ int pyqsm_ransac(const double* pts, int64_t n, const int64_t* triples, int64_t H
       hipLaunchKernelGGL(k_flags<1>, grid, dim3(256), 0, c->stream, d_pts, n, d_models, best,
                          thresh, d_flags);
     PQ_HIP(hipGetLastError());
-    PQ_TRY(exclusive_scan_i32(c, d_flags, n + 1));
-    hipLaunchKernelGGL(k_compact, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, n, d_pts,
-                       d_models, best, thresh, shape, d_flags, d_out);
-    PQ_HIP(hipGetLastError());
+    PQ_TRY(compact_flagged(c, d_flags, n, d_out));
   }
   Model m;
   PQ_HIP(hipMemcpyAsync(&m, d_models + best, sizeof(Model), hipMemcpyDeviceToHost, c->stream));

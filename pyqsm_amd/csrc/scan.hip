@@ -147,6 +147,39 @@ int exclusive_scan_i32(Ctx* c, int32_t* data, int64_t n) {
   return 0;
 }
 
+__device__ __forceinline__ void copy_row(const double* __restrict__ src, int64_t i, double* __restrict__ dst,
+                                         int64_t p) {
+  const double x = src[3 * i], y = src[3 * i + 1], z = src[3 * i + 2];  // three loads in flight
+  dst[3 * p] = x;
+  dst[3 * p + 1] = y;
+  dst[3 * p + 2] = z;
+}
+
+// the scatter of compact_flagged (pos = the scanned flags)
+__global__ __launch_bounds__(256) void k_compact_flagged(int64_t n, const int32_t* __restrict__ pos,
+                                                         int64_t* __restrict__ idx,
+                                                         const int64_t* __restrict__ src_idx,
+                                                         const double* __restrict__ a, double* __restrict__ out_a,
+                                                         const double* __restrict__ b, double* __restrict__ out_b) {
+  const int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
+  if (i >= n) return;
+  const int64_t p = pos[i];
+  if (pos[i + 1] == p) return;
+  if (idx) idx[p] = src_idx ? src_idx[i] : i;
+  if (out_a) copy_row(a, i, out_a, p);
+  if (out_b) copy_row(b, i, out_b, p);
+}
+
+int compact_flagged(Ctx* c, int32_t* flags, int64_t n, int64_t* idx, const int64_t* src_idx, const double* a,
+                    double* out_a, const double* b, double* out_b) {
+  PQ_TRY(exclusive_scan_i32(c, flags, n + 1));
+  if (n > 0)
+    hipLaunchKernelGGL(k_compact_flagged, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, n,
+                       static_cast<const int32_t*>(flags), idx, src_idx, a, out_a, b, out_b);
+  PQ_HIP(hipGetLastError());
+  return 0;
+}
+
 // ---- stable radix sort of (key, value) pairs ----------------------------------------------------
 // Least-significant-digit passes of 8 bits; each pass is a per-tile digit histogram, the scan
 // above over [digit][tile], and a scatter in which a pair's place among the equal digits of its
