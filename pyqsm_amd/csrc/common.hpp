@@ -73,11 +73,25 @@ class Arena {
   size_t cur_ = 0;  // chunk allocations currently come from
 };
 
+// A stamped interval: from the earliest block start of launch `first` to the latest block end of
+// launch `last` (indices into Ctx::stamp_launches); first < 0: a scope without a stamped launch.
+struct StampRec {
+  int first, last;
+};
+
 struct Timer {
   double ms = 0.0;
   int64_t launches = 0;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
   std::vector<int> weights;  // launches represented by each pending pair
+  std::vector<StampRec> stamped;  // one launch each
+};
+
+// Where a stamped launch's slots lie: chunk of Ctx::stamp_chunks, first slot, blocks.
+struct StampLaunch {
+  int chunk;
+  size_t off;
+  int nblk;
 };
 
 // The launch shapes a device-planned DBSCAN call is enqueued with (grid.hpp GridPlan): the exact plan
@@ -102,8 +116,17 @@ struct Ctx {
   // DBSCAN's grid plan: page-locked [read-back, upload] slots, the timing-disabled event the host
   // waits on for the read-back, and the hint of the last host-planned call (dbscan.hip)
   void* plan_pinned = nullptr;
-  hipEvent_t plan_ev = nullptr;
+  unsigned plan_seq = 0;  // the sequence number of the last plan the fold was asked to write
   PlanHint plan_hint;
+  // device-clock stamps of the profiled launches since the last drain (stamp_slots): grow-only
+  // chunks of device memory, two u64 slots per block
+  struct StampChunk {
+    unsigned long long* base;
+    size_t size, used;  // in slots
+  };
+  std::vector<StampChunk> stamp_chunks;
+  std::vector<StampLaunch> stamp_launches;
+  int stamp_khz = 100000;  // the constant clock's rate
 };
 
 // Returns the context for `device`, creating it on first use. nullptr + error
@@ -131,6 +154,55 @@ class ProfKernel {
   ProfKernel(Ctx* c, const char* name);
   hipEvent_t start = nullptr, stop = nullptr;
 };
+
+// Device-clock timing of a profiled step without events between its kernels (DBSCAN). A stamped
+// kernel takes the pointer stamp_slots() returns (null when profiling is off) and runs its body
+// through stamped(): every block writes its start and the end of its last wave to its own two
+// slots, on the 100 MHz constant clock. drain_timers reduces them on the host. The stamps time
+// the blocks' work only: the dispatch gaps between kernels are not in them.
+// Slots for one launch of `nblk` blocks, registered as the context's next stamped launch; nullptr
+// when profiling is below `level` or the slots cannot be allocated.
+unsigned long long* stamp_slots(Ctx* c, int64_t nblk, int level = 1);
+// A single-block kernel that only stamps: the start or the end of a scope whose first or last
+// kernel is not stamped (rare paths). Does nothing when profiling is off.
+int stamp_mark(Ctx* c);
+
+// The scope of a phase: from the first stamped launch enqueued while it is open to the last one.
+class StampScope {
+ public:
+  StampScope(Ctx* c, const char* name, int level = 1);
+  ~StampScope();
+
+ private:
+  Ctx* c_;
+  Timer* t_ = nullptr;
+  int first_ = 0;
+};
+
+// The slots of one stamped kernel launch of `nblk` blocks, timed under `name` on its own.
+class StampKernel {
+ public:
+  StampKernel(Ctx* c, const char* name, int64_t nblk);
+  unsigned long long* slots = nullptr;
+};
+
+// Runs `body` (the kernel's code; a `return` in it leaves the body) between the block's stamps.
+// One barrier before the body and one LDS atomic per wave after it, only when st != nullptr.
+template <typename F>
+__device__ __forceinline__ void stamped(unsigned long long* __restrict__ st, F&& body) {
+  __shared__ int done;
+  if (st) {  // kernel-uniform
+    if (threadIdx.x == 0) {
+      done = 0;
+      st[2 * size_t(blockIdx.x)] = wall_clock64();
+    }
+    __syncthreads();
+  }
+  body();
+  if (st && (threadIdx.x & 63) == 0) {  // every wave, all of its lanes back
+    if (atomicAdd(&done, 1) == int((blockDim.x + 63) / 64) - 1) st[2 * size_t(blockIdx.x) + 1] = wall_clock64();
+  }
+}
 
 // roctx range around a C-ABI entry point (tracing): shows up in
 // `rocprofv3 --marker-trace`. librocprofiler-sdk-roctx is looked up once at run time;

@@ -3,6 +3,8 @@
 
 #include <dlfcn.h>
 
+#include <algorithm>
+
 namespace pyqsm {
 
 // ---- roctx ranges --------------------------------------------------------
@@ -261,6 +263,9 @@ Ctx* ctx_for(int device) {
   }
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->cu_count = prop.multiProcessorCount;
+  int khz = 0;
+  if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) == hipSuccess && khz > 0)
+    c->stamp_khz = khz;
   pool.all.push_back(c);
   t_held.ctx[device] = c;
   return c;
@@ -302,6 +307,74 @@ ProfKernel::ProfKernel(Ctx* c, const char* name) {
   stop = b;
 }
 
+// ---- device-clock stamps ------------------------------------------------------------------
+
+__global__ __launch_bounds__(64) void k_stamp(unsigned long long* __restrict__ st) {
+  if (threadIdx.x == 0) {
+    const unsigned long long t = wall_clock64();
+    st[0] = t;
+    st[1] = t;
+  }
+}
+
+// A chunk of at least `slots` slots: the first one (allocated when profiling is switched on) holds
+// every launch of many steps, so that a timed loop allocates nothing; when one runs out, another of
+// the size of all before it is added, and drain_timers folds them into one.
+static constexpr size_t kStampChunkMin = size_t(1) << 21;  // 16 MB
+static bool stamp_chunk_add(Ctx* c, size_t slots) {
+  size_t want = kStampChunkMin;
+  for (auto& ch : c->stamp_chunks) want += ch.size;
+  if (c->stamp_chunks.empty()) want = kStampChunkMin;
+  want = std::max(want, slots);
+  void* p = nullptr;
+  if (hipMalloc(&p, want * 8) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  c->stamp_chunks.push_back({static_cast<unsigned long long*>(p), want, 0});
+  return true;
+}
+
+unsigned long long* stamp_slots(Ctx* c, int64_t nblk, int level) {
+  if (c->prof < level || nblk <= 0) return nullptr;
+  const size_t need = size_t(nblk) * 2;
+  if (c->stamp_chunks.empty() || c->stamp_chunks.back().used + need > c->stamp_chunks.back().size)
+    if (!stamp_chunk_add(c, need)) return nullptr;
+  Ctx::StampChunk& ch = c->stamp_chunks.back();
+  c->stamp_launches.push_back({int(c->stamp_chunks.size()) - 1, ch.used, int(nblk)});
+  unsigned long long* p = ch.base + ch.used;
+  ch.used += need;
+  return p;
+}
+
+int stamp_mark(Ctx* c) {
+  unsigned long long* st = stamp_slots(c, 1);
+  if (!st) return 0;
+  hipLaunchKernelGGL(k_stamp, dim3(1), dim3(64), 0, c->stream, st);
+  PQ_HIP(hipGetLastError());
+  return 0;
+}
+
+StampScope::StampScope(Ctx* c, const char* name, int level) : c_(c) {
+  if (c->prof < level) return;
+  t_ = &c->timers[name];
+  first_ = int(c->stamp_launches.size());
+}
+
+StampScope::~StampScope() {
+  if (!t_) return;
+  const int last = int(c_->stamp_launches.size()) - 1;
+  t_->stamped.push_back(last >= first_ ? StampRec{first_, last} : StampRec{-1, -1});
+}
+
+StampKernel::StampKernel(Ctx* c, const char* name, int64_t nblk) {
+  slots = stamp_slots(c, nblk);
+  if (slots) {
+    const int i = int(c->stamp_launches.size()) - 1;
+    c->timers[name].stamped.push_back({i, i});
+  }
+}
+
 static void drain_timers(Ctx* c) {
   (void)hipStreamSynchronize(c->stream);
   for (auto& kv : c->timers) {
@@ -319,6 +392,49 @@ static void drain_timers(Ctx* c) {
     t.pending.clear();
     t.weights.clear();
   }
+  // the stamps: one read-back per chunk, then per launch the earliest start and the latest end
+  std::vector<std::vector<unsigned long long>> host(c->stamp_chunks.size());
+  bool read = true;
+  for (size_t k = 0; k < c->stamp_chunks.size(); ++k) {
+    const Ctx::StampChunk& ch = c->stamp_chunks[k];
+    host[k].resize(ch.used);
+    if (ch.used && hipMemcpy(host[k].data(), ch.base, ch.used * 8, hipMemcpyDeviceToHost) != hipSuccess) read = false;
+  }
+  std::vector<std::pair<unsigned long long, unsigned long long>> span(c->stamp_launches.size());
+  for (size_t i = 0; i < span.size(); ++i) {
+    const StampLaunch& l = c->stamp_launches[i];
+    unsigned long long lo = ~0ull, hi = 0;
+    if (read) {
+      const unsigned long long* s = host[size_t(l.chunk)].data() + l.off;
+      for (int b = 0; b < l.nblk; ++b) {
+        lo = std::min(lo, s[2 * b]);
+        hi = std::max(hi, s[2 * b + 1]);
+      }
+    }
+    span[i] = {lo, hi};
+  }
+  for (auto& kv : c->timers) {
+    Timer& t = kv.second;
+    for (const StampRec& r : t.stamped) {
+      if (r.first >= 0 && read) {
+        const unsigned long long a = span[size_t(r.first)].first, b = span[size_t(r.last)].second;
+        if (b > a) t.ms += double(b - a) / c->stamp_khz;
+      }
+      t.launches += 1;
+    }
+    t.stamped.clear();
+  }
+  c->stamp_launches.clear();
+  if (c->stamp_chunks.size() > 1) {  // fold: the next steps of this size allocate nothing
+    size_t total = 0;
+    for (auto& ch : c->stamp_chunks) {
+      total += ch.size;
+      (void)hipFree(ch.base);
+    }
+    c->stamp_chunks.clear();
+    (void)stamp_chunk_add(c, total);
+  }
+  for (auto& ch : c->stamp_chunks) ch.used = 0;
 }
 
 }  // namespace pyqsm
@@ -350,7 +466,8 @@ int pyqsm_shutdown(void) {
         drain_timers(c);
         c->arena.destroy();
         if (c->plan_pinned) (void)hipHostFree(c->plan_pinned);
-        if (c->plan_ev) (void)hipEventDestroy(c->plan_ev);
+        for (auto& ch : c->stamp_chunks) (void)hipFree(ch.base);
+        c->stamp_chunks.clear();
         (void)hipStreamDestroy(c->stream);
       }
       delete c;
@@ -427,6 +544,7 @@ int pyqsm_prof_enable(int device, int on) {
   if (!c) return PYQSM_ENODEV;
   std::lock_guard<std::mutex> lk(c->mu);
   c->prof = on < 0 ? 0 : on;
+  if (c->prof && c->stamp_chunks.empty()) (void)stamp_chunk_add(c, 0);  // not inside a timed loop
   return 0;
 }
 

@@ -18,6 +18,9 @@
 // d2 = ((dx*dx) + dy*dy) + dz*dz with separately rounded products, compared
 // with fl(eps*eps). The library is compiled with -ffp-contract=off.
 #include "grid.hpp"
+
+#include <atomic>
+#include <chrono>
 #include <optional>
 #include <vector>
 
@@ -83,8 +86,10 @@ __global__ __launch_bounds__(256) void k_core_tiled(int n, const GridPlan* __res
                                                     int32_t* __restrict__ flag /*[n + 1]*/, int max_chunks,
                                                     unsigned long long* __restrict__ tests /*may be null:
                                                     [256] slots, candidates staged per wave (x 64 lanes
-                                                    = lane-tests executed)*/) {
+                                                    = lane-tests executed)*/,
+    unsigned long long* __restrict__ st /*stamps or null*/) {
   __shared__ TileLds L;
+  stamped(st, [&] {
   // wave-uniform quantities are forced into SGPRs so that the loops below are scalar
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int p0 = (blockIdx.x * 4 + w) * 64;
@@ -183,6 +188,7 @@ __global__ __launch_bounds__(256) void k_core_tiled(int n, const GridPlan* __res
     if (p == n - 1) flag[n] = 0;
   }
   if (tests && lane == 0) atomicAdd(tests + (blockIdx.x & 255), static_cast<unsigned long long>(staged));
+  });
 }
 
 // The 27-cell stencil of one point as ONE sequence of candidates: the nine runs' bounds are loaded side
@@ -225,7 +231,9 @@ __global__ __launch_bounds__(256) void k_core_rest(const int32_t* __restrict__ r
                                                    int seg_cap, const GridPlan* __restrict__ plan,
                                                    const int32_t* __restrict__ start,
                                                    const int32_t* __restrict__ cell_of, CO co, double r2,
-                                                   int min_pts, uint8_t* __restrict__ core) {
+                                                   int min_pts, uint8_t* __restrict__ core,
+    unsigned long long* __restrict__ st /*stamps or null*/) {
+  stamped(st, [&] {
   if (!plan->ok) return;
   const Stencil st = plan_stencil(plan);
   const int lane = threadIdx.x & 63;
@@ -257,6 +265,7 @@ __global__ __launch_bounds__(256) void k_core_rest(const int32_t* __restrict__ r
       co.mark_core(p, cnt >= min_pts);
     }
   }
+  });
 }
 
 // ---- union-find --------------------------------------------------------------
@@ -337,7 +346,9 @@ __global__ __launch_bounds__(1024) void k_sub_rep(int n, const int32_t* __restri
                                                  int* __restrict__ run_min,
                                                  int4* __restrict__ list,
                                                  int32_t* __restrict__ list_cnt, const GridPlan* __restrict__ plan,
-                                                 int4* __restrict__ list_xyz) {
+                                                 int4* __restrict__ list_xyz,
+    unsigned long long* __restrict__ st /*stamps or null*/) {
+  stamped(st, [&] {
   if (!plan->ok) return;
   const int nx = plan->nx, ny = plan->ny;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -441,6 +452,7 @@ __global__ __launch_bounds__(1024) void k_sub_rep(int n, const int32_t* __restri
     list[slot] = make_int4(rep, c1, sid, e - rep);
     list_xyz[slot] = make_int4(c1 % nx, (c1 / nx) % ny, c1 / (nx * ny), sid & 7);
   }
+  });
 }
 
 // The 62 lexicographically positive (dz, dy, dx) offsets in [-2,2]^3 as (dx, dy, dz): the 13
@@ -484,7 +496,9 @@ __global__ __launch_bounds__(256) void k_hook_sub(const int4* __restrict__ list,
                                                   const int4* __restrict__ rec, CO co, double r2,
                                                   const uint8_t* __restrict__ core,
                                                   int* __restrict__ parent,
-                                                  int32_t* __restrict__ nbr) {
+                                                  int32_t* __restrict__ nbr,
+    unsigned long long* __restrict__ st /*stamps or null*/) {
+  stamped(st, [&] {
   if (!plan->ok) return;
   const int nx = plan->nx, ny = plan->ny;
   const int m = *m_ptr;
@@ -577,6 +591,7 @@ __global__ __launch_bounds__(256) void k_hook_sub(const int4* __restrict__ list,
   // above are 48 of those 81 us and live on occupancy (half the resident waves: 118 us); the rounds'
   // record arrays cost the registers that occupancy needs.)
   }
+  });
 }
 
 // Pass 2: a WAVE per kSubPerWave sub-cells with core points, over the same pairs (sub-cell, neighbour at
@@ -593,7 +608,9 @@ __global__ __launch_bounds__(256) void k_union_sub(const int4* __restrict__ list
                                                    const int32_t* __restrict__ nbr,
                                                    const int32_t* __restrict__ sub_of,
                                                    const int4* __restrict__ rec, CO co, double r2,
-                                                   const uint8_t* __restrict__ core, int* parent) {
+                                                   const uint8_t* __restrict__ core, int* parent,
+    unsigned long long* __restrict__ st /*stamps or null*/) {
+  stamped(st, [&] {
   const int m = *m_ptr;
   const int k = threadIdx.x & 63;
   for (int s0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * kSubPerWave; s0 < m; s0 += gridDim.x * 4 * kSubPerWave) {
@@ -669,6 +686,7 @@ __global__ __launch_bounds__(256) void k_union_sub(const int4* __restrict__ list
     }
   }
   }
+  });
 }
 
 // ---- fallback for coarsened grids ----------------------------------------------------
@@ -811,7 +829,9 @@ __global__ __launch_bounds__(kNumberThreads) void k_number(int n, const int32_t*
                                                            uint32_t* __restrict__ bits /*zeroed, n / 32 + 1*/,
                                                            int32_t* __restrict__ wpre /*n / 32 + 1*/,
                                                            int32_t* __restrict__ done /*zeroed*/,
-                                                           const GridPlan* __restrict__ plan) {
+                                                           const GridPlan* __restrict__ plan,
+    unsigned long long* __restrict__ st /*stamps or null*/) {
+  stamped(st, [&] {
   if (!plan->ok) return;
   const int R = *roots_cnt;
   const int t = threadIdx.x;
@@ -895,6 +915,7 @@ __global__ __launch_bounds__(kNumberThreads) void k_number(int n, const int32_t*
     carry += total;
     __syncthreads();  // wsum is rewritten next round
   }
+  });
 }
 
 // The cluster number of a component from what k_number left in min_orig[root] (or the smallest index of the
@@ -918,7 +939,9 @@ __global__ __launch_bounds__(1024) void k_labels(int n, const uint8_t* __restric
                                                  int64_t* __restrict__ labels,
                                                  uint8_t* __restrict__ is_core,
                                                  int32_t* __restrict__ rest,
-                                                 int32_t* __restrict__ rest_cnt, const GridPlan* __restrict__ plan) {
+                                                 int32_t* __restrict__ rest_cnt, const GridPlan* __restrict__ plan,
+    unsigned long long* __restrict__ st /*stamps or null*/) {
+  stamped(st, [&] {
   if (!plan->ok) return;  // block-uniform
   int p = blockIdx.x * 1024 + threadIdx.x;
   const bool live = p < n;
@@ -929,6 +952,7 @@ __global__ __launch_bounds__(1024) void k_labels(int n, const uint8_t* __restric
   }
   if (live && is_core) is_core[order[p]] = is_c;
   block_append<1024>(live && !is_c, p, rest, rest_cnt);
+  });
 }
 
 // One WAVE per non-core point: smallest cluster number among its core neighbours, or -1.
@@ -945,7 +969,9 @@ __global__ __launch_bounds__(256) void k_labels_border(const int32_t* __restrict
                                                        const uint32_t* __restrict__ bits,
                                                        const int32_t* __restrict__ wpre,
                                                        const int32_t* __restrict__ order,
-                                                       int64_t* __restrict__ labels) {
+                                                       int64_t* __restrict__ labels,
+    unsigned long long* __restrict__ st /*stamps or null*/) {
+  stamped(st, [&] {
   if (!plan->ok) return;
   const Stencil st = plan_stencil(plan);
   const int m = *rest_cnt;
@@ -976,6 +1002,7 @@ __global__ __launch_bounds__(256) void k_labels_border(const int32_t* __restrict
     if (lane == 0)
       labels[order[p]] = best == kNoRoot ? int64_t(-1) : int64_t(cluster_number(best, n_roots, bits, wpre));
   }
+  });
 }
 
 // Core flags, union-find and labels over a binned cloud. The kernels read the grid from d_plan.
@@ -1023,7 +1050,7 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
   PQ_TRY(c->arena.get(std::max<size_t>(size_t(n), size_t(seg_cap) * kRestSegs), &rest));
   int32_t* const rest_segs = list_cnt + 4;  // kRestSegs zeroed counters
   {
-    ProfScope ps(c, "dbscan_core");
+    StampScope ps(c, "dbscan_core");
     unsigned long long* d_tests = nullptr;
     if (c->prof >= 2) {
       PQ_TRY(c->arena.get(256, &d_tests));
@@ -1033,11 +1060,11 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
     // serve min_pts = 10, and in proportion beyond
     const int max_chunks = std::min(32, std::max(kMaxChunks, (kMaxChunks * min_pts + 9) / 10));
     {
-      const ProfKernel pk(c, "k_core_tiled");
+      const StampKernel pk(c, "k_core_tiled", grid.x);
       on_coords(g, [&](auto co) {
-        hipExtLaunchKernelGGL(k_core_tiled<decltype(co)>, grid, block, 0, c->stream, pk.start, pk.stop, 0, N, d_plan,
-                              g.start, g.cell_of, co, r2, min_pts, core, rest, rest_segs, seg_cap, parent, min_orig,
-                              flag, max_chunks, d_tests);
+        hipLaunchKernelGGL(k_core_tiled<decltype(co)>, grid, block, 0, c->stream, N, d_plan, g.start, g.cell_of, co, r2,
+                           min_pts, core, rest, rest_segs, seg_cap, parent, min_orig, flag, max_chunks, d_tests,
+                           pk.slots);
       });
     }
     if (d_tests) {  // profiling level 2 only: read the counter back (synchronises)
@@ -1048,19 +1075,22 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
       for (unsigned long long v : h) tot += v;
       c->timers["core_pair_tests"].launches += int64_t(tot) * 64;  // lane-tests executed
     }
+    const dim3 gr(std::min<int64_t>(8192, ceil_div(n, 64)));
+    unsigned long long* const st_rest = stamp_slots(c, gr.x);
     on_coords(g, [&](auto co) {
-      hipLaunchKernelGGL(k_core_rest<decltype(co)>, dim3(std::min<int64_t>(8192, ceil_div(n, 64))), block, 0,
-                         c->stream, rest, rest_segs, seg_cap, d_plan, g.start, g.cell_of, co, r2, min_pts, core);
+      hipLaunchKernelGGL(k_core_rest<decltype(co)>, gr, block, 0, c->stream, rest, rest_segs, seg_cap, d_plan, g.start,
+                         g.cell_of, co, r2, min_pts, core, st_rest);
     });
     PQ_HIP(hipGetLastError());
   }
   {
-    ProfScope ps(c, "dbscan_union");
+    StampScope ps(c, "dbscan_union");
     // (parent / min_orig / flag were initialised by k_core_tiled; list_cnt[0..2] are still the zeros the
     // binning left)
     if (fine) {
       hipLaunchKernelGGL(k_sub_rep, dim3(ceil_div(n, 1024)), dim3(1024), 0, c->stream, N, sub.sub_of, core,
-                         g.order, parent, g.cell_of, sub.rec, run_min, list, list_cnt, d_plan, list_xyz);
+                         g.order, parent, g.cell_of, sub.rec, run_min, list, list_cnt, d_plan, list_xyz,
+                         stamp_slots(c, ceil_div(n, 1024)));
       // The number m of listed sub-cells stays on the device: the passes below are launched for the
       // upper bound (a sub-cell holds at least one point, in practice ~5) and read m themselves —
       // waves beyond it leave at once — which spares the host round trip in the middle of the step
@@ -1091,11 +1121,10 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
         int32_t* nbr;  // [m][64] representatives of the neighbour sub-cells pass 1 resolved
         PQ_TRY(c->arena.get(size_t(rows) * 64, &nbr));
         {
-          const ProfKernel pk(c, "k_hook_sub");
+          const StampKernel pk(c, "k_hook_sub", gh.x);
           on_coords(g, [&](auto co) {
-            hipExtLaunchKernelGGL((k_hook_sub<kSubPerWaveDefault, decltype(co)>), gh, block, 0, c->stream, pk.start,
-                                  pk.stop, 0, list, list_xyz, list_cnt, d_plan, g.start, sub.rec, co, r2, core, parent,
-                                  nbr);
+            hipLaunchKernelGGL((k_hook_sub<kSubPerWaveDefault, decltype(co)>), gh, block, 0, c->stream, list, list_xyz,
+                               list_cnt, d_plan, g.start, sub.rec, co, r2, core, parent, nbr, pk.slots);
           });
         }
         if (getenv("PYQSM_DBSCAN_TRACE")) {  // how deep are the chains the hook pass leaves?
@@ -1131,10 +1160,10 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
         // what is left: joining the few trees per cluster. Almost every pair of neighbours
         // now shows the same root through two plain loads.
         {
-          const ProfKernel pk(c, "k_union_sub");
+          const StampKernel pk(c, "k_union_sub", gu.x);
           on_coords(g, [&](auto co) {
-            hipExtLaunchKernelGGL((k_union_sub<kSubPerWaveDefault, decltype(co)>), gu, block, 0, c->stream, pk.start,
-                                  pk.stop, 0, list, list_cnt, nbr, sub.sub_of, sub.rec, co, r2, core, parent);
+            hipLaunchKernelGGL((k_union_sub<kSubPerWaveDefault, decltype(co)>), gu, block, 0, c->stream, list, list_cnt,
+                               nbr, sub.sub_of, sub.rec, co, r2, core, parent, pk.slots);
           });
         }
         hipLaunchKernelGGL(k_rep_root, gl, block, 0, c->stream, list, list_cnt, parent, run_min, min_orig, roots,
@@ -1142,6 +1171,7 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
       }
       PQ_HIP(hipGetLastError());
     } else {
+      PQ_TRY(stamp_mark(c));  // (the per-point union-find is not stamped itself)
       on_coords(g, [&](auto co) {
         hipLaunchKernelGGL(k_union_points<decltype(co)>, grid, block, 0, c->stream, N, st, g.start, g.cell_of, co,
                            r2, core, parent);
@@ -1151,19 +1181,21 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
                          roots_cnt, d_plan);
     }
     // one workgroup numbers up to kRankCap clusters; more take the bitmap, a block per CU at most
-    hipLaunchKernelGGL(k_number, dim3(std::min<int64_t>(ceil_div(n, kNumberThreads), c->cu_count)),
-                       dim3(kNumberThreads), 0, c->stream, N, roots, roots_cnt, min_orig, bits, wpre, list_cnt + 2,
-                       d_plan);
+    const dim3 gn(std::min<int64_t>(ceil_div(n, kNumberThreads), c->cu_count));
+    hipLaunchKernelGGL(k_number, gn, dim3(kNumberThreads), 0, c->stream, N, roots, roots_cnt, min_orig, bits, wpre,
+                       list_cnt + 2, d_plan, stamp_slots(c, gn.x));
     PQ_HIP(hipGetLastError());
   }
   {
-    ProfScope ps(c, "dbscan_label");
+    StampScope ps(c, "dbscan_label");
     hipLaunchKernelGGL(k_labels, dim3(ceil_div(n, 1024)), dim3(1024), 0, c->stream, N, core, parent, min_orig,
-                       roots_cnt, bits, wpre, g.order, labels, is_core, rest, list_cnt + 3, d_plan);
+                       roots_cnt, bits, wpre, g.order, labels, is_core, rest, list_cnt + 3, d_plan,
+                       stamp_slots(c, ceil_div(n, 1024)));
+    const dim3 gb(std::min<int64_t>(8192, ceil_div(n, 64)));
+    unsigned long long* const st_border = stamp_slots(c, gb.x);
     on_coords(g, [&](auto co) {
-      hipLaunchKernelGGL(k_labels_border<decltype(co)>, dim3(std::min<int64_t>(8192, ceil_div(n, 64))), block, 0,
-                         c->stream, rest, list_cnt + 3, d_plan, g.start, g.cell_of, co, r2, core, parent, min_orig,
-                         roots_cnt, bits, wpre, g.order, labels);
+      hipLaunchKernelGGL(k_labels_border<decltype(co)>, gb, block, 0, c->stream, rest, list_cnt + 3, d_plan, g.start,
+                         g.cell_of, co, r2, core, parent, min_orig, roots_cnt, bits, wpre, g.order, labels, st_border);
     });
     PQ_HIP(hipGetLastError());
   }
@@ -1171,6 +1203,24 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
   return 0;
 }
 
+
+// The fold's plan in the host-mapped slot: a bounded poll of its sequence number (the fold runs within
+// microseconds of the call unless the stream holds earlier work), then, when the bound runs out, the
+// stream's synchronisation (which waits for the speculative step too).
+static constexpr double kPlanPollMs = 20.0;
+static int wait_plan(Ctx* c, const GridPlan* h_plan, unsigned seq) {
+  const volatile unsigned* const s = &h_plan->seq;
+  const auto t0 = std::chrono::steady_clock::now();
+  while (*s != seq) {
+    if (std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() > kPlanPollMs) {
+      PQ_HIP(hipStreamSynchronize(c->stream));
+      if (*s != seq) return fail(PYQSM_EHIP, "DBSCAN: the grid plan was not written (sequence %u)", seq);
+      break;
+    }
+  }
+  std::atomic_thread_fence(std::memory_order_acquire);
+  return 0;
+}
 
 // The bounding box's fold plans the grid on the device. With a shape hint (the last host-planned call
 // of this context) the whole step is enqueued at once behind it, and the host waits only for the
@@ -1192,10 +1242,14 @@ static int dbscan_device(Ctx* c, const double* xyz, int64_t n, double eps, int32
   const double cell = eps * (1.0 + 1.0 / 1048576.0);
   const int64_t max_cells = int64_t(1) << 28;
   if (!c->plan_pinned) {
-    PQ_HIP(hipHostMalloc(&c->plan_pinned, 2 * sizeof(GridPlan), hipHostMallocDefault));
-    PQ_HIP(hipEventCreateWithFlags(&c->plan_ev, hipEventDisableTiming));
+    PQ_HIP(hipHostMalloc(&c->plan_pinned, 2 * sizeof(GridPlan), hipHostMallocMapped | hipHostMallocCoherent));
+    memset(c->plan_pinned, 0, 2 * sizeof(GridPlan));
   }
   GridPlan* const h_plan = static_cast<GridPlan*>(c->plan_pinned);  // [0] read-back, [1] upload
+  GridPlan* h_plan_dev;  // the read-back slot as the fold writes it
+  PQ_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h_plan_dev), c->plan_pinned, 0));
+  if (++c->plan_seq == 0) c->plan_seq = 1;  // 0: the slot's value while the fold writes it
+  const unsigned seq = c->plan_seq;
   GridPlan* d_plan;  // [0] the fold's, [1] the host's
   int32_t* zeroed;
   PQ_TRY(c->arena.get(2, &d_plan));
@@ -1210,15 +1264,15 @@ static int dbscan_device(Ctx* c, const double* xyz, int64_t n, double eps, int32
   DevGrid g;
   SubCells sub;
   const int32_t* count = nullptr;
-  std::optional<ProfScope> bin_scope(std::in_place, c, "dbscan_bin");
-  PQ_TRY(plan_grid_device(c, xyz, n, cell, max_cells, hint, d_plan, h_plan, c->plan_ev, zeroed, octant_zeroed_ints()));
+  std::optional<StampScope> bin_scope(std::in_place, c, "dbscan_bin");
+  PQ_TRY(plan_grid_device(c, xyz, n, cell, max_cells, hint, d_plan, h_plan_dev, seq, zeroed, octant_zeroed_ints()));
   const Arena::Mark mark = c->arena.mark();
   if (speculate) {
     PQ_TRY(bin_octants_planned(c, xyz, n, cell, hint, d_plan, zeroed, &g, &sub));
     bin_scope.reset();
     PQ_TRY(cluster_binned(c, n, eps, min_pts, radius_inclusive, g, sub, d_plan, labels, is_core, &count));
   }
-  PQ_HIP(hipEventSynchronize(c->plan_ev));
+  PQ_TRY(wait_plan(c, h_plan, seq));
   const bool hit = speculate && h_plan[0].ok;
   if (!hit) {
     // planned on the host; the kernels enqueued above (if any) left without a write, so their
@@ -1226,7 +1280,9 @@ static int dbscan_device(Ctx* c, const double* xyz, int64_t n, double eps, int32
     c->arena.rewind(mark);
     PlanHint next;
     if (!bin_scope) bin_scope.emplace(c, "dbscan_bin");
+    PQ_TRY(stamp_mark(c));  // (the host-planned binning's first and last kernels vary with the grid)
     PQ_TRY(bin_octants_host(c, xyz, n, cell, max_cells, h_plan[0], zeroed, &h_plan[1], d_plan + 1, &g, &sub, &next));
+    PQ_TRY(stamp_mark(c));
     bin_scope.reset();
     if (next.valid) c->plan_hint = next;  // (a grid of another kind keeps the hint there is)
     PQ_TRY(cluster_binned(c, n, eps, min_pts, radius_inclusive, g, sub, d_plan + 1, labels, is_core, &count));
@@ -1260,7 +1316,7 @@ int pyqsm_dbscan_dev_ex(const double* xyz_dev, int64_t n, double eps, int32_t mi
   if (!c) return PYQSM_ENODEV;
   std::lock_guard<std::mutex> lk(c->mu);
   c->arena.reset();
-  ProfScope ps(c, "dbscan_total");
+  StampScope ps(c, "dbscan_total");
   return dbscan_device(c, xyz_dev, n, eps, min_pts, radius_inclusive != 0, labels_dev, is_core_dev,
                        n_clusters);
 }

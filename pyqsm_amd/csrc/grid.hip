@@ -25,9 +25,11 @@ static double ord_val(unsigned long long k) {
 // representable in fp32 (double(float(v)) == v: true for PCD / LAS derived clouds), else 0
 static constexpr int kBoxVals = 7;
 __global__ __launch_bounds__(256) void k_bbox(const double* __restrict__ xyz, int64_t n,
-                                              unsigned long long* __restrict__ part /*[grid][7]*/) {
+                                              unsigned long long* __restrict__ part /*[grid][7]*/,
+    unsigned long long* __restrict__ st /*stamps or null*/) {
   __shared__ unsigned long long red[4][6];
   __shared__ int red_f32[4];
+  stamped(st, [&] {
   unsigned long long mn[3] = {~0ull, ~0ull, ~0ull}, mx[3] = {0, 0, 0};
   bool f32ok = true;
   for (int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; i < n;
@@ -71,6 +73,7 @@ __global__ __launch_bounds__(256) void k_bbox(const double* __restrict__ xyz, in
   }
   if (threadIdx.x == 6)
     part[size_t(blockIdx.x) * kBoxVals + 6] = (red_f32[0] && red_f32[1] && red_f32[2] && red_f32[3]) ? 1ull : 0ull;
+  });
 }
 
 // (Folding in k_bbox itself — the block that counts itself last reads everybody's records — was tried
@@ -79,11 +82,14 @@ __global__ __launch_bounds__(256) void k_bbox(const double* __restrict__ xyz, in
 // One block folds the per-block records (the fp32 flag as a minimum: 0 wins) and, while it is
 // there, clears `zero_n` ints for the caller (the bucket counters of the binning that follows:
 // two memset launches less on the critical path).
-// With `plan` (DBSCAN), the fold also writes the grid plan of edge `cell` (see plan_grid_device).
+// With `plan` (DBSCAN), the fold also writes the grid plan of edge `cell` (see plan_grid_device), and
+// the same plan to `host` (host-mapped, coherent) with the sequence number `seq` stored last.
 struct PlanIn {
   double cell;
   int64_t max_cells;
   PlanHint hint;
+  GridPlan* host;
+  unsigned seq;
 };
 __device__ void write_plan(const unsigned long long* box, const PlanIn& in, GridPlan* __restrict__ plan);
 
@@ -343,7 +349,8 @@ int cloud_bbox(Ctx* c, const double* xyz, int64_t n, double mn[3], double mx[3],
   unsigned long long *d_box = nullptr, *d_part = nullptr;
   PQ_TRY(c->arena.get(kBoxVals, &d_box));
   PQ_TRY(c->arena.get(size_t(blocks) * kBoxVals, &d_part));
-  hipLaunchKernelGGL(k_bbox, dim3(blocks), dim3(256), 0, c->stream, xyz, n, d_part);
+  hipLaunchKernelGGL(k_bbox, dim3(blocks), dim3(256), 0, c->stream, xyz, n, d_part,
+                     static_cast<unsigned long long*>(nullptr));
   hipLaunchKernelGGL(k_bbox_fold, dim3(1), dim3(256), 0, c->stream, d_part, blocks, d_box, zero_buf, zero_n, PlanIn{},
                      static_cast<GridPlan*>(nullptr));
   PQ_HIP(hipGetLastError());
@@ -802,12 +809,12 @@ __global__ __launch_bounds__(256) void k_order_big(const int32_t* __restrict__ b
 //                     scan of the bucket's cell counts -> the bucket's directory entries,
 //                     written once and coalesced; every point then goes straight to its final,
 //                     octant-ordered place. Cells with more than 255 points (a packed count could
-//                     overflow) are listed for k_order_big exactly as before.
+//                     overflow) are ordered by the same block afterwards, as k_order_big does.
 // Same arrays as build_grid_octants leaves (the order inside a sub-cell is the arrival order of
 // atomics in both versions, and nothing downstream depends on it).
 static constexpr int kBkMax = 16384;            // buckets (LDS histogram of the A passes: <= 64 KB)
 static constexpr int kBkPts = 2048;             // points per block of the A passes
-static constexpr int kBkBig = 255;              // cells above this go through k_order_big
+static constexpr int kBkBig = 255;              // cells above this are ordered after k_bk_sort's sweep
 static constexpr int kBkPer = 4;                // records a thread of k_bk_sort keeps in registers
 
 // MODE 0: cell and octant on the raw grid; 1: the same through the axis-compression maps;
@@ -976,6 +983,9 @@ struct BkLds {
   int32_t cnt[1 << BITS];             // points per cell, then (in place) the cell's offset in the bucket
   uint32_t big[(1 << BITS) / 32];     // cells with more than kBkBig points
   int32_t wsum[16];
+  int32_t any_big;                    // some cell of the bucket is in `big`
+  int32_t btot[8], bbase[8];          // a big cell's octant totals and running bases
+  int32_t bw[(1 << BITS) / 512][8];   // per wave: points of each octant in the current chunk
 };
 
 // One block per bucket of 2^BITS cells, a thread per eight cells (BITS = 12: 512 threads and 49 KB of
@@ -990,10 +1000,12 @@ __global__ __launch_bounds__((1 << BITS) / 8) void k_bk_sort(
     int32_t* __restrict__ start, int32_t* __restrict__ order, int32_t* __restrict__ cell_of,
     int32_t* __restrict__ sub_of, double* __restrict__ sx, double* __restrict__ sy, double* __restrict__ sz,
     float4* __restrict__ p4 /*non-null: fp32 records instead of sx / sy / sz*/, int4* __restrict__ rec,
-    PointRec* __restrict__ keyed, int32_t* __restrict__ big_list, int32_t* __restrict__ big_cnt,
-    const GridPlan* __restrict__ plan /*ncell1 and the number of buckets (the launch may have more blocks)*/) {
+    PointRec* __restrict__ keyed /*big cells' runs in arrival order*/,
+    const GridPlan* __restrict__ plan /*ncell1 and the number of buckets (the launch may have more blocks)*/,
+    unsigned long long* __restrict__ st /*stamps or null*/) {
   constexpr int CELLS = 1 << BITS, T = CELLS / 8;
   __shared__ BkLds<BITS> L;
+  stamped(st, [&] {
   const int bk = blockIdx.x, t = threadIdx.x;
   if (!plan->ok || bk >= plan->nbk) return;
   ncell1 = int64_t(plan->ncell) + 1;
@@ -1029,6 +1041,7 @@ __global__ __launch_bounds__((1 << BITS) / 8) void k_bk_sort(
     L.cnt[k * T + t] = 0;
   }
   if (t < CELLS / 32) L.big[t] = 0u;
+  if (t == 0) L.any_big = 0;
   __syncthreads();
   // sweep 1: arrival rank in the cell and in the octant
   if (inreg) {
@@ -1093,9 +1106,9 @@ __global__ __launch_bounds__((1 << BITS) / 8) void k_bk_sort(
     L.cnt[cl] = pre[k];
     if (v[k] == 0) continue;
     const int b = s + pre[k];  // the cell's first sorted position: identifies its sub-cells
-    if (v[k] > kBkBig) {
+    if (v[k] > kBkBig) {  // rare: the block orders the cell after sweep 2
       atomicOr(&L.big[cl >> 5], 1u << (cl & 31));
-      big_list[atomicAdd(big_cnt, 1)] = int(c0) + cl;  // rare; k_order_big writes the cell's records
+      L.any_big = 1;
       continue;
     }
     const unsigned long long c64 = L.oct[cl];
@@ -1135,6 +1148,80 @@ __global__ __launch_bounds__((1 << BITS) / 8) void k_bk_sort(
   } else {
     for (int j = s + t; j < e; j += T) place(bucketed[j], rank_tmp[j], int(oct_rank[j]));
   }
+  // Cells above kBkBig points (none on a scan at eps ~ 10 x the point spacing): the whole block sorts each
+  // one's run of `keyed` by octant, stable in arrival order, as k_order_big does for the atomic binning (two
+  // sweeps, ranks inside a chunk by ballots). Without such a cell nothing more runs, and no kernel is
+  // launched for them.
+  __syncthreads();  // the big cells' runs of `keyed` are written, L.any_big is final
+  if (!L.any_big) return;  // block-uniform
+  for (int wd = 0; wd < CELLS / 32; ++wd) {
+    for (uint32_t bm = L.big[wd]; bm; bm &= bm - 1u) {  // block-uniform
+      const int cl = wd * 32 + __ffs(bm) - 1;
+      const int b = s + L.cnt[cl], e2 = s + (cl + 1 < CELLS ? L.cnt[cl + 1] : e - s);
+      int loc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      for (int q = b + t; q < e2; q += T) {
+        const int oq = keyed[q].key & 7;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) loc[k] += oq == k;
+      }
+      if (t < 8) L.btot[t] = 0;
+      __syncthreads();
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        int cnt = loc[k];
+        for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
+        if (lane == 0 && cnt) atomicAdd(&L.btot[k], cnt);  // LDS
+      }
+      __syncthreads();
+      if (t == 0) {
+        int r2 = b;
+        for (int k = 0; k < 8; ++k) {
+          L.bbase[k] = r2;
+          rec[size_t(b) * 8 + k] = make_int4(r2, L.btot[k], -1, 0);
+          r2 += L.btot[k];
+        }
+      }
+      __syncthreads();
+      for (int q0 = b; q0 < e2; q0 += T) {
+        const int q = q0 + t;
+        const bool live = q < e2;
+        PointRec pr;
+        pr.key = 0;
+        if (live) pr = keyed[q];
+        const int o = pr.key & 7;
+        int before = 0;  // same octant, earlier lane of this wave
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const unsigned long long m = __ballot(live && o == k);
+          if (lane == 0) L.bw[w][k] = __popcll(m);
+          if (o == k) before = __popcll(m & ((1ull << lane) - 1ull));
+        }
+        __syncthreads();
+        if (live) {
+          int f = L.bbase[o] + before;
+          for (int ww = 0; ww < w; ++ww) f += L.bw[ww][o];
+          order[f] = pr.idx;
+          cell_of[f] = pr.key >> 3;
+          sub_of[f] = b * 8 + o;
+          if (p4) {
+            p4[f] = make_float4(float(pr.x), float(pr.y), float(pr.z), 0.f);
+          } else {
+            sx[f] = pr.x;
+            sy[f] = pr.y;
+            sz[f] = pr.z;
+          }
+        }
+        __syncthreads();
+        if (t < 8) {
+          int add = 0;
+          for (int ww = 0; ww < T / 64; ++ww) add += L.bw[ww][t];
+          L.bbase[t] += add;
+        }
+        __syncthreads();
+      }
+    }
+  }
+  });
 }
 
 // The same second level without octants (build_grid): a count per cell is all there is, so a bucket
@@ -1348,22 +1435,29 @@ __device__ void write_plan(const unsigned long long* box, const PlanIn& in, Grid
   p.nbk = ok ? int(nbk) : 0;
   p.bits = 12;
   p.ok = ok ? 1 : 0;
+  p.seq = in.seq;
   *plan = p;
+  if (in.host) {
+    // the host polls the sequence number: everything else first, visible to the host before it
+    // (one system-scope release, by one thread of the one folding block)
+    p.seq = 0;
+    *in.host = p;
+    __threadfence_system();
+    *reinterpret_cast<volatile unsigned*>(&in.host->seq) = in.seq;
+  }
 }
 
 int plan_grid_device(Ctx* c, const double* xyz, int64_t n, double cell, int64_t max_cells, const PlanHint& hint,
-                     GridPlan* d_plan, GridPlan* h_plan, hipEvent_t ev, int32_t* zero_buf, int zero_n) {
+                     GridPlan* d_plan, GridPlan* h_plan, unsigned seq, int32_t* zero_buf, int zero_n) {
   if (n <= 0) return fail(PYQSM_EINVAL, "bounding box of an empty cloud");
   const int blocks = int(std::min<int64_t>(ceil_div(n, 256), int64_t(c->cu_count) * 4));
   unsigned long long *d_box = nullptr, *d_part = nullptr;
   PQ_TRY(c->arena.get(kBoxVals, &d_box));
   PQ_TRY(c->arena.get(size_t(blocks) * kBoxVals, &d_part));
-  hipLaunchKernelGGL(k_bbox, dim3(blocks), dim3(256), 0, c->stream, xyz, n, d_part);
+  hipLaunchKernelGGL(k_bbox, dim3(blocks), dim3(256), 0, c->stream, xyz, n, d_part, stamp_slots(c, blocks));
   hipLaunchKernelGGL(k_bbox_fold, dim3(1), dim3(256), 0, c->stream, d_part, blocks, d_box, zero_buf, zero_n,
-                     PlanIn{cell, max_cells, hint}, d_plan);
+                     PlanIn{cell, max_cells, hint, h_plan, seq}, d_plan);
   PQ_HIP(hipGetLastError());
-  PQ_HIP(hipMemcpyAsync(h_plan, d_plan, sizeof(GridPlan), hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipEventRecord(ev, c->stream));
   return 0;
 }
 
@@ -1377,8 +1471,8 @@ int octant_zeroed_ints() { return 2 * kBkMax + 5 + kZeroedExtra; }
 static int enqueue_bucketed(Ctx* c, const double* xyz, int64_t n, const GridParams& gp, const int raw[3],
                             AxisMap am, bool mapped, int64_t ncell, int64_t nbk, int bits, bool f32,
                             int32_t* zeroed, const GridPlan* d_plan, DevGrid* g, SubCells* sub) {
-  int32_t *cell_tmp, *rank_tmp, *big_list, *bstart;
-  int32_t *tot = zeroed, *cursor = zeroed + kBkMax, *big_cnt = zeroed + 2 * kBkMax;
+  int32_t *cell_tmp, *rank_tmp, *bstart;
+  int32_t *tot = zeroed, *cursor = zeroed + kBkMax;
   PointRec *keyed, *bucketed;
   uint8_t* oct_rank;
   g->p4 = nullptr;
@@ -1400,7 +1494,6 @@ static int enqueue_bucketed(Ctx* c, const double* xyz, int64_t n, const GridPara
   PQ_TRY(c->arena.get(size_t(n) * 8, &sub->sub_beg));
   PQ_TRY(c->arena.get(size_t(n), &sub->sub_of));
   PQ_TRY(c->arena.get(size_t(n) * 8, &sub->rec));
-  PQ_TRY(c->arena.get(size_t(n) / kBigCell + 2, &big_list));
   PQ_TRY(c->arena.get(size_t(nbk) + 1, &bstart));
   PQ_TRY(c->arena.get(size_t(n), &oct_rank));
   PQ_TRY(c->arena.get(size_t(n), &bucketed));
@@ -1416,18 +1509,15 @@ static int enqueue_bucketed(Ctx* c, const double* xyz, int64_t n, const GridPara
   if (!fused) hipLaunchKernelGGL(k_bk_scan, dim3(1), dim3(1024), 0, c->stream, int(nbk), tot, bstart, d_plan);
   hipLaunchKernelGGL(k_bk_scatter, ga, blk, fused ? 2 * lds : lds, c->stream, xyz, n, int(nbk), bits, cell_tmp, tot,
                      cursor, bstart, fused, bucketed, d_plan);
+  unsigned long long* const st_sort = stamp_slots(c, nbk);  // the binning's last kernel
   if (bits == 12)
     hipLaunchKernelGGL(k_bk_sort<12>, dim3(unsigned(nbk)), dim3(512), 0, c->stream, ncell + 1, bstart, bucketed,
                        rank_tmp, oct_rank, g->start, g->order, g->cell_of, sub->sub_of, g->sx, g->sy, g->sz, g->p4,
-                       sub->rec, keyed, big_list, big_cnt, d_plan);
+                       sub->rec, keyed, d_plan, st_sort);
   else
     hipLaunchKernelGGL(k_bk_sort<13>, dim3(unsigned(nbk)), dim3(1024), 0, c->stream, ncell + 1, bstart, bucketed,
                        rank_tmp, oct_rank, g->start, g->order, g->cell_of, sub->sub_of, g->sx, g->sy, g->sz, g->p4,
-                       sub->rec, keyed, big_list, big_cnt, d_plan);
-  PQ_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_order_big, dim3(unsigned(std::min<int64_t>(n / kBigCell + 1, 2048))), blk, 0, c->stream,
-                     big_list, big_cnt, g->start, keyed, g->order, g->cell_of, sub->sub_of, g->sx, g->sy, g->sz, g->p4,
-                     sub->sub_cnt, sub->sub_beg, sub->rec, d_plan);
+                       sub->rec, keyed, d_plan, st_sort);
   PQ_HIP(hipGetLastError());
   return 0;
 }

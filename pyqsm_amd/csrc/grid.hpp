@@ -288,16 +288,17 @@ struct GridPlan {
   int nbk, bits;   // buckets of 2^bits cells of the two-level sort
   int all_f32;     // every coordinate is exactly representable in fp32
   int ok;
+  unsigned seq;    // the call's sequence number (the host's read-back slot: stored last)
 };
 __device__ __forceinline__ Stencil plan_stencil(const GridPlan* p) { return Stencil{p->nx, p->nx * p->ny}; }
 // (PlanHint, the launch shapes a device-planned call is enqueued with, lives in common.hpp: the
 // context keeps the last one.)
 
 // k_bbox + the fold, which writes the plan of a grid of edge `cell` (at most `max_cells` cells)
-// into d_plan, clears zero_n ints of zero_buf, and an asynchronous copy of the plan into h_plan
-// (page-locked) followed by `ev`. Does not synchronise.
+// into d_plan and into h_plan (host-mapped, coherent: no copy, no event; h_plan->seq = seq once the
+// rest of it is visible to the host) and clears zero_n ints of zero_buf. Does not synchronise.
 int plan_grid_device(Ctx* c, const double* xyz, int64_t n, double cell, int64_t max_cells, const PlanHint& hint,
-                     GridPlan* d_plan, GridPlan* h_plan, hipEvent_t ev, int32_t* zero_buf, int zero_n);
+                     GridPlan* d_plan, GridPlan* h_plan, unsigned seq, int32_t* zero_buf, int zero_n);
 // Zeroed ints plan_grid_device must clear for the binning below (the bucket totals, reservation
 // cursors and the big-cell counter) plus kZeroedExtra + 4 for the caller.
 int octant_zeroed_ints();
