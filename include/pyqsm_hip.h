@@ -568,6 +568,42 @@ int pyqsm_ball_excl_dev(const double* xyz_dev, int64_t n, const uint8_t* found_d
                         int32_t device);
 int pyqsm_mark_found_dev(uint8_t* found_dev, int64_t n, const int64_t* idx, int64_t cnt, int32_t device);
 
+/* ---- geometric features and neighbour smoothing ------------------------------------------ */
+/*
+ * jakteristics' compute_features and pyQSM's smooth_feature (pyQSM/exploration.py:62-90,
+ * utils/algo.py:8-22). Recollected from jakteristics (Hackel et al. 2016), parity unpinned;
+ * tests/features_restatement.py defines the contract; DESIGN.md section 11.
+ *
+ * pyqsm_geometric_features: xyz f64 [n,3]. Neighbourhood of i: every j (i included) with
+ *   ((dx*dx) + dy*dy) + dz*dz <= radius^2 in fp64 (metric 2), or (|dx| + |dy|) + |dz| <= radius
+ *   (metric 1); when more than max_k qualify, the max_k first by (distance, index). Covariance on
+ *   the offsets o = p_j - p_i: C = (sum o o^T - (sum o)(sum o)^T / N) / (N - 1), the sums exact in
+ *   128-bit fixed point (every term rounded to 2^-61 of the largest possible offset), so the
+ *   result is reproducible bit for bit and independent of the input order. lambda1 >= lambda2 >=
+ *   lambda3 (clamped to >= 0), e3 the unit eigenvector of lambda3 with e3_z >= 0. feature_ids
+ *   [n_features] (1 to 32 columns) in jakteristics' FEATURE_NAMES numbering: 0 eigenvalue_sum,
+ *   1 omnivariance, 2 eigenentropy, 3 anisotropy, 4 planarity, 5 linearity, 6 PCA1, 7 PCA2,
+ *   8 surface_variation, 9 sphericity, 10 verticality, 11 nx, 12 ny, 13 nz. N < 3 or
+ *   lambda1 == 0: NaN. out f64 [n, n_features]; counts i32 [n] (may be NULL): N before the cap.
+ *   radius <= 0 or not finite, a bad metric or feature id: PYQSM_EINVAL; max_k < 1 or
+ *   n_features outside [1, 32]: PYQSM_ERANGE.
+ */
+int pyqsm_geometric_features(const double* xyz, int64_t n, double radius, int32_t max_k, int32_t metric,
+                             const int32_t* feature_ids, int32_t n_features, double* out, int32_t* counts,
+                             int32_t device);
+/*
+ * pyqsm_smooth_values: the k nearest of each query among the n points xyz f64 [n,3], ascending by
+ *   (d2, index) with d2 = ((dx*dx) + dy*dy) + dz*dz; qry f64 [m,3], or NULL for the points
+ *   themselves (m == n; each point then counts itself). k in [1, 192] (PYQSM_ERANGE), k > n:
+ *   PYQSM_EINVAL. values f64 [n, F] reduced over each query's neighbours into out f64 [m, F]:
+ *   reducer 0 mean (fp64 sum in neighbour order, divided by k), 1 median (np.median: the mean of
+ *   the two middle values for even k), 2 min, 3 max; NaN propagates as in NumPy. reducer -1: no
+ *   reduction (values and out may be NULL). idx i32 [m, k] (may be NULL unless reducer is -1):
+ *   the neighbour table.
+ */
+int pyqsm_smooth_values(const double* xyz, int64_t n, const double* qry, int64_t m, const double* values,
+                        int32_t F, int32_t k, int32_t reducer, double* out, int32_t* idx, int32_t device);
+
 #ifdef __cplusplus
 }
 #endif

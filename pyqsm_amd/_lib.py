@@ -95,6 +95,8 @@ SIGNATURES = {
     "pyqsm_kmeans_select_dev": (ctypes.c_int, [vp, i64, i32, i32, i32, vp, vp, vp, vp, i32]),
     "pyqsm_ball_excl_dev": (ctypes.c_int, [vp, i64, vp, vp, dbl, vp, vp, ctypes.POINTER(i64), i32]),
     "pyqsm_mark_found_dev": (ctypes.c_int, [vp, i64, vp, i64, i32]),
+    "pyqsm_geometric_features": (ctypes.c_int, [vp, i64, dbl, i32, i32, vp, i32, vp, vp, i32]),
+    "pyqsm_smooth_values": (ctypes.c_int, [vp, i64, vp, i64, vp, i32, i32, i32, vp, vp, i32]),
 }
 
 _lib = None

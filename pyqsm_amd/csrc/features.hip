@@ -1,0 +1,664 @@
+// features.hip — the per-point neighbourhood features pyQSM labels wood, leaf and epiphyte points
+// with (pyQSM/exploration.py:62-90, utils/algo.py:8-22): jakteristics' compute_features (the
+// covariance of every point within a radius, its eigen-decomposition and up to 14 eigenvalue
+// features, after Hackel et al. 2016) and smooth_feature (a reducer over each query's k nearest
+// points). Recollected from jakteristics, parity unpinned; tests/features_restatement.py states the
+// contract in NumPy/SciPy.
+//
+// Features. The cloud is binned into cells of the radius; one wave per point, in the grid's sorted
+// order, walks the nine stencil runs 64 candidates at a time. Candidates inside the ball (d2 <= r2,
+// or the L1 distance <= r) have their offsets o = p_j - p_i staged in LDS; every 64 staged offsets
+// each lane adds one neighbour's first and second moments. The moments are fixed point: every
+// term o_a (and the fp64 product o_a * o_b) is scaled by a power of two that maps the largest
+// possible offset to 2^61 and rounded to an integer, and summed in 128 bits, lane partials folded
+// by a butterfly. The sum is then exact, so the result does not depend on the order in which the
+// grid's binning left the points of a cell, nor on the order of the input (integer additions only,
+// no atomics). A point with more than max_k points in its ball keeps the max_k first by (distance,
+// index): the threshold distance by bisection on its bit pattern, then the index bound among the
+// ties at it by bisection on the index. k_feat_finish turns the moments' covariance into the
+// eigenvalues and e3 (pca.hpp sym3_eigh_desc) and writes the requested features in fp64.
+//
+// Smoothing. The k nearest of every query, ascending by (d2, index): the exact kNN (knn.hip) when
+// the queries are the points themselves; otherwise k_query_knn, one wave per query over a grid of
+// cells of R: with at least k points within R the k first by (d2, index) are exact, the others are
+// served again with R doubled. The neighbour table stays in the arena; k_smooth_reduce gathers each
+// row's values into LDS and reduces them (mean: fp64 sum in neighbour order over k; median: ranks by
+// (value, position), the mean of the two middle values for even k; min, max), NaN propagating as in
+// NumPy.
+#include <algorithm>
+#include <cmath>
+
+#include "common.hpp"
+#include "grid.hpp"
+#include "pca.hpp"
+
+namespace pyqsm {
+
+int knn_device(Ctx* c, const double* xyz, int64_t n, int32_t k, int32_t exclude_self, int32_t* idx,
+               double* d2);                // knn.hip
+static constexpr int kSmoothMaxK = 192;    // knn.hip kMaxK: largest k of a smoothing
+static constexpr int kFeatCount = 14;      // jakteristics' FEATURE_NAMES
+static constexpr int kFeatMaxCols = 32;    // columns one call may ask for
+static constexpr int kFeatWaves = 4;       // waves per block of k_feat_moments
+static constexpr int kQueryCap = 512;      // (d2, index) pairs k_query_knn sorts without bisection
+
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// ---- fixed-point moments -------------------------------------------------------------------------
+// A signed 128-bit integer as (low word, high word).
+struct I128 {
+  unsigned long long lo;
+  long long hi;
+};
+
+// a += x, x an integral double with |x| <= 2^62
+__device__ __forceinline__ void acc128(I128& a, double x) {
+  const long long v = (long long)x;
+  const unsigned long long lo = a.lo + (unsigned long long)v;
+  a.hi += (v < 0 ? -1LL : 0LL) + (lo < a.lo ? 1LL : 0LL);
+  a.lo = lo;
+}
+
+// a += the value lane ^ off holds
+__device__ __forceinline__ void fold128(I128& a, int off) {
+  const unsigned long long blo = __shfl_xor(a.lo, off, 64);
+  const long long bhi = __shfl_xor(a.hi, off, 64);
+  const unsigned long long lo = a.lo + blo;
+  a.hi = a.hi + bhi + (lo < a.lo ? 1LL : 0LL);
+  a.lo = lo;
+}
+
+// the magnitude as hi * 2^64 + lo, the sign applied after: small negative sums stay exact
+__device__ __forceinline__ double to_double(I128 a) {
+  const bool neg = a.hi < 0;
+  if (neg) {
+    a.lo = ~a.lo + 1ull;
+    a.hi = ~a.hi + (a.lo == 0ull ? 1LL : 0LL);
+  }
+  const double v = double((unsigned long long)a.hi) * 18446744073709551616.0 + double(a.lo);
+  return neg ? -v : v;
+}
+
+// Powers of two per axis: s1[a] maps the largest offset along a to at most 2^61, s2 the products
+// of the pairs (00, 01, 02, 11, 12, 22); u1, u2 their inverses.
+struct FeatScale {
+  double s1[3], s2[6], u1[3], u2[6];
+};
+
+__device__ __forceinline__ void add_moments(I128* M, const FeatScale& sc, double ox, double oy, double oz) {
+  acc128(M[0], rint(ox * sc.s1[0]));
+  acc128(M[1], rint(oy * sc.s1[1]));
+  acc128(M[2], rint(oz * sc.s1[2]));
+  acc128(M[3], rint((ox * ox) * sc.s2[0]));
+  acc128(M[4], rint((ox * oy) * sc.s2[1]));
+  acc128(M[5], rint((ox * oz) * sc.s2[2]));
+  acc128(M[6], rint((oy * oy) * sc.s2[3]));
+  acc128(M[7], rint((oy * oz) * sc.s2[4]));
+  acc128(M[8], rint((oz * oz) * sc.s2[5]));
+}
+
+// The distance the ball is tested with: d2 = ((dx*dx) + dy*dy) + dz*dz, or (|dx| + |dy|) + |dz|.
+template <class CO, bool L1>
+__device__ __forceinline__ double feat_dist(const CO& co, int q, double x, double y, double z, double& a, double& b,
+                                            double& c) {
+  co.get(q, a, b, c);
+  if (L1) return (fabs(a - x) + fabs(b - y)) + fabs(c - z);
+  return sqdist3(x, y, z, a, b, c);
+}
+
+// One wave per point at sorted position p. lim: r^2 (L2) or r (L1), inclusive. Writes the
+// covariance entries (c00, c01, c02, c11, c12, c22) of the neighbours kept (np.cov's N - 1 divisor;
+// zeros below two), their number used[i] and the ball's count cnt_out[i] before the cap.
+template <class CO, bool L1>
+__global__ __launch_bounds__(64 * kFeatWaves) void k_feat_moments(
+    int n, const double* __restrict__ xyz, GridParams g, const int32_t* __restrict__ start,
+    const int32_t* __restrict__ order, CO co, double lim, int max_k, FeatScale sc, double* __restrict__ cov,
+    int32_t* __restrict__ used, int32_t* __restrict__ cnt_out) {
+  __shared__ double sb[kFeatWaves][3][128];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int p = blockIdx.x * kFeatWaves + w;
+  if (p >= n) return;  // whole wave
+  const int i = order[p];
+  const double x = xyz[3 * size_t(i)], y = xyz[3 * size_t(i) + 1], z = xyz[3 * size_t(i) + 2];
+  StencilRuns rr;  // clamped like the points were binned
+  point_stencil_runs(g, start, x, y, z, &rr);
+  // in the ball and (d < tau, or d == tau and index <= ilim)
+  auto count = [&](double tau, int ilim) {
+    int cnt = 0;
+    for (int r = 0; r < 9; ++r)
+      for (int base = rr.qb[r]; base < rr.qe[r]; base += 64) {
+        const int q = base + lane;
+        bool in = false;
+        if (q < rr.qe[r]) {
+          double a, b, c;
+          const double d = feat_dist<CO, L1>(co, q, x, y, z, a, b, c);
+          in = d <= lim && (d < tau || (d == tau && order[q] <= ilim));
+        }
+        cnt += __popcll(__ballot(in));
+      }
+    return cnt;
+  };
+  const int total = count(__builtin_inf(), 0x7FFFFFFF);
+  double tau = __builtin_inf();
+  int ilim = 0x7FFFFFFF;
+  if (total > max_k) {
+    unsigned long long lo = 0, hi = (unsigned long long)__double_as_longlong(lim);
+    while (lo < hi) {  // smallest t with #{d <= t} >= max_k (d >= 0 orders as its bits)
+      const unsigned long long mid = lo + ((hi - lo) >> 1);
+      if (count(__longlong_as_double((long long)mid), 0x7FFFFFFF) >= max_k) hi = mid;
+      else lo = mid + 1;
+    }
+    tau = __longlong_as_double((long long)lo);
+    int ia = 0, ib = n - 1;  // smallest index bound that completes max_k among the ties at tau
+    while (ia < ib) {
+      const int mid = ia + ((ib - ia) >> 1);
+      if (count(tau, mid) >= max_k) ib = mid;
+      else ia = mid + 1;
+    }
+    ilim = ia;
+  }
+  I128 M[9];
+  for (int t = 0; t < 9; ++t) M[t] = I128{0ull, 0LL};
+  int have = 0, N = 0;
+  for (int r = 0; r < 9; ++r)
+    for (int base = rr.qb[r]; base < rr.qe[r]; base += 64) {
+      const int q = base + lane;
+      bool take = false;
+      double a = 0.0, b = 0.0, c = 0.0;
+      if (q < rr.qe[r]) {
+        const double d = feat_dist<CO, L1>(co, q, x, y, z, a, b, c);
+        take = d <= lim && (d < tau || (d == tau && order[q] <= ilim));
+      }
+      const unsigned long long kb = __ballot(take);
+      if (take) {  // have < 64 here, so slot < 128
+        const int slot = have + __popcll(kb & ((1ull << lane) - 1ull));
+        sb[w][0][slot] = a - x;
+        sb[w][1][slot] = b - y;
+        sb[w][2][slot] = c - z;
+      }
+      have += __popcll(kb);
+      if (have >= 64) {
+        wave_sync();
+        add_moments(M, sc, sb[w][0][lane], sb[w][1][lane], sb[w][2][lane]);
+        wave_sync();
+        if (lane < have - 64) {
+          sb[w][0][lane] = sb[w][0][lane + 64];
+          sb[w][1][lane] = sb[w][1][lane + 64];
+          sb[w][2][lane] = sb[w][2][lane + 64];
+        }
+        wave_sync();
+        have -= 64;
+        N += 64;
+      }
+    }
+  wave_sync();
+  if (lane < have) add_moments(M, sc, sb[w][0][lane], sb[w][1][lane], sb[w][2][lane]);
+  N += have;
+  for (int off = 32; off > 0; off >>= 1)
+    for (int t = 0; t < 9; ++t) fold128(M[t], off);
+  if (lane == 0) {
+    double* o = cov + 6 * size_t(i);
+    if (N >= 2) {
+      const double dn = double(N);
+      double s1[3];
+      for (int a = 0; a < 3; ++a) s1[a] = to_double(M[a]) * sc.u1[a];
+      const int A[6] = {0, 0, 0, 1, 1, 2}, B[6] = {0, 1, 2, 1, 2, 2};
+      for (int e = 0; e < 6; ++e) {
+        const double s2 = to_double(M[3 + e]) * sc.u2[e];
+        o[e] = (s2 - s1[A[e]] * (s1[B[e]] / dn)) / (dn - 1.0);
+      }
+    } else {
+      for (int e = 0; e < 6; ++e) o[e] = 0.0;
+    }
+    used[i] = N;
+    cnt_out[i] = total;
+  }
+}
+
+struct FeatList {
+  int n;
+  int id[kFeatMaxCols];
+};
+
+// One lane per point: the eigenvalues (clamped to >= 0) and e3 (e3_z >= 0), then the requested
+// features in jakteristics' FEATURE_NAMES numbering; all NaN when fewer than 3 neighbours were kept
+// or lambda1 == 0.
+__global__ __launch_bounds__(256) void k_feat_finish(int n, const double* __restrict__ cov,
+                                                     const int32_t* __restrict__ used, FeatList fl,
+                                                     double* __restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double* cv = cov + 6 * size_t(i);
+  double l[3] = {0.0, 0.0, 0.0}, e[3] = {0.0, 0.0, 0.0};
+  bool nan = used[i] < 3;
+  if (!nan) {
+    sym3_eigh_desc(Sym3{cv[0], cv[1], cv[2], cv[3], cv[4], cv[5]}, l, e);
+    for (int s = 0; s < 3; ++s) l[s] = l[s] > 0.0 ? l[s] : 0.0;
+    nan = !(l[0] > 0.0);
+    if (e[2] < 0.0) {
+      e[0] = -e[0];
+      e[1] = -e[1];
+      e[2] = -e[2];
+    }
+  }
+  const double S = (l[0] + l[1]) + l[2];
+  double* o = out + size_t(i) * fl.n;
+  for (int f = 0; f < fl.n; ++f) {
+    double v = __builtin_nan("");
+    if (!nan) switch (fl.id[f]) {
+        case 0: v = S; break;
+        case 1: v = cbrt((l[0] * l[1]) * l[2]); break;
+        case 2: {
+          double h = 0.0;
+          for (int s = 0; s < 3; ++s)
+            if (l[s] > 0.0) h = h + l[s] * log(l[s]);
+          v = -h;
+          break;
+        }
+        case 3: v = (l[0] - l[2]) / l[0]; break;
+        case 4: v = (l[1] - l[2]) / l[0]; break;
+        case 5: v = (l[0] - l[1]) / l[0]; break;
+        case 6: v = l[0] / S; break;
+        case 7: v = l[1] / S; break;
+        case 8: v = l[2] / S; break;
+        case 9: v = l[2] / l[0]; break;
+        case 10: v = 1.0 - fabs(e[2]); break;
+        case 11: v = e[0]; break;
+        case 12: v = e[1]; break;
+        default: v = e[2]; break;
+      }
+    o[f] = v;
+  }
+}
+
+// ---- smoothing: the k nearest of separate queries ------------------------------------------------
+__global__ __launch_bounds__(256) void k_iota(int m, int32_t* __restrict__ list) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < m) list[i] = i;
+}
+
+// One wave per listed query: the points with d2 <= R2 (the grid's cells are at least R). Fewer than
+// k: the query goes on the next list (integer atomic; a query's result does not depend on the
+// round or the slot it is served in). Otherwise the k first by (d2, index) — all of them are
+// within R — into idx[q * k ...].
+template <class CO>
+__global__ __launch_bounds__(128) void k_query_knn(int m_list, const int32_t* __restrict__ list,
+                                                   const double* __restrict__ qry, GridParams g,
+                                                   const int32_t* __restrict__ start,
+                                                   const int32_t* __restrict__ order, CO co, double R2, int k,
+                                                   int n_src, int32_t* __restrict__ idx,
+                                                   int32_t* __restrict__ next, int32_t* __restrict__ n_next) {
+  __shared__ double sd[2][kQueryCap];
+  __shared__ int si[2][kQueryCap];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int t = blockIdx.x * 2 + w;
+  if (t >= m_list) return;  // whole wave
+  const int qi = list[t];
+  const double x = qry[3 * size_t(qi)], y = qry[3 * size_t(qi) + 1], z = qry[3 * size_t(qi) + 2];
+  StencilRuns rr;
+  point_stencil_runs(g, start, x, y, z, &rr);
+  auto count = [&](double tau, int ilim) {  // d2 <= R2 and (d2 < tau, or d2 == tau and index <= ilim)
+    int cnt = 0;
+    for (int r = 0; r < 9; ++r)
+      for (int base = rr.qb[r]; base < rr.qe[r]; base += 64) {
+        const int q = base + lane;
+        bool in = false;
+        if (q < rr.qe[r]) {
+          const double d = co.d2(q, x, y, z);
+          in = d <= R2 && (d < tau || (d == tau && order[q] <= ilim));
+        }
+        cnt += __popcll(__ballot(in));
+      }
+    return cnt;
+  };
+  const int total = count(__builtin_inf(), 0x7FFFFFFF);
+  if (total < k) {
+    if (lane == 0) next[atomicAdd(n_next, 1)] = qi;
+    return;
+  }
+  double tau = __builtin_inf();
+  int ilim = 0x7FFFFFFF;
+  if (total > kQueryCap) {  // exactly k survive: the k-th d2, then the index bound among its ties
+    unsigned long long lo = 0, hi = (unsigned long long)__double_as_longlong(R2);
+    while (lo < hi) {
+      const unsigned long long mid = lo + ((hi - lo) >> 1);
+      if (count(__longlong_as_double((long long)mid), 0x7FFFFFFF) >= k) hi = mid;
+      else lo = mid + 1;
+    }
+    tau = __longlong_as_double((long long)lo);
+    int ia = 0, ib = n_src - 1;
+    while (ia < ib) {
+      const int mid = ia + ((ib - ia) >> 1);
+      if (count(tau, mid) >= k) ib = mid;
+      else ia = mid + 1;
+    }
+    ilim = ia;
+  }
+  int have = 0;  // at most kQueryCap (all of them) or exactly k (after the bisections)
+  for (int r = 0; r < 9; ++r)
+    for (int base = rr.qb[r]; base < rr.qe[r]; base += 64) {
+      const int q = base + lane;
+      double d = 0.0;
+      bool take = false;
+      int id = 0;
+      if (q < rr.qe[r]) {
+        d = co.d2(q, x, y, z);
+        id = order[q];
+        take = d <= R2 && (d < tau || (d == tau && id <= ilim));
+      }
+      const unsigned long long kb = __ballot(take);
+      const int slot = have + __popcll(kb & ((1ull << lane) - 1ull));
+      if (take && slot < kQueryCap) {
+        sd[w][slot] = d;
+        si[w][slot] = id;
+      }
+      have += __popcll(kb);
+    }
+  have = have < kQueryCap ? have : kQueryCap;
+  int np2 = 1;
+  while (np2 < have) np2 <<= 1;
+  for (int u = have + lane; u < np2; u += 64) {
+    sd[w][u] = __builtin_inf();
+    si[w][u] = 0x7FFFFFFF;
+  }
+  wave_sync();
+  for (int k2 = 2; k2 <= np2; k2 <<= 1)
+    for (int j = k2 >> 1; j > 0; j >>= 1) {
+      for (int a = lane; a < np2; a += 64) {
+        const int b = a ^ j;
+        if (b > a) {
+          const double da = sd[w][a], db = sd[w][b];
+          const int ia = si[w][a], ib = si[w][b];
+          const bool a_gt_b = da > db || (da == db && ia > ib);
+          if (a_gt_b == ((a & k2) == 0)) {
+            sd[w][a] = db;
+            si[w][a] = ib;
+            sd[w][b] = da;
+            si[w][b] = ia;
+          }
+        }
+      }
+      wave_sync();
+    }
+  for (int u = lane; u < k; u += 64) idx[size_t(qi) * k + u] = si[w][u];
+}
+
+// ---- smoothing: the reduction over each row of the neighbour table -------------------------------
+// One wave per query row; per column the k values go through LDS. reducer 0 mean, 1 median, 2 min,
+// 3 max.
+__global__ __launch_bounds__(128) void k_smooth_reduce(int m, const int32_t* __restrict__ idx, int k,
+                                                       const double* __restrict__ vals, int F, int reducer,
+                                                       double* __restrict__ out) {
+  __shared__ double sv[2][kSmoothMaxK];
+  __shared__ double ss[2][kSmoothMaxK];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int q = blockIdx.x * 2 + w;
+  if (q >= m) return;  // whole wave
+  const int32_t* row = idx + size_t(q) * k;
+  for (int f = 0; f < F; ++f) {
+    bool nan_here = false;
+    for (int t = lane; t < k; t += 64) {
+      const double v = vals[size_t(row[t]) * F + f];
+      sv[w][t] = v;
+      nan_here = nan_here || v != v;
+    }
+    const bool any_nan = __ballot(nan_here) != 0ull;
+    wave_sync();
+    double res = 0.0;
+    if (reducer == 1) {
+      if (!any_nan) {  // rank by (value, position): a permutation, so ss is the sorted row
+        for (int t = lane; t < k; t += 64) {
+          const double v = sv[w][t];
+          int rank = 0;
+          for (int u = 0; u < k; ++u) {
+            const double o = sv[w][u];
+            rank += (o < v || (o == v && u < t)) ? 1 : 0;
+          }
+          ss[w][rank] = v;
+        }
+        wave_sync();
+        res = (k & 1) ? ss[w][k >> 1] : (ss[w][(k >> 1) - 1] + ss[w][k >> 1]) / 2.0;
+      } else {
+        res = __builtin_nan("");
+      }
+    } else if (lane == 0) {
+      if (reducer == 0) {
+        double s = 0.0;
+        for (int t = 0; t < k; ++t) s = s + sv[w][t];
+        res = s / double(k);
+      } else {
+        res = sv[w][0];
+        for (int t = 1; t < k; ++t) {
+          const double v = sv[w][t];
+          if (res != res) break;  // NaN stays
+          if (v != v || (reducer == 2 ? v < res : v > res)) res = v;
+        }
+      }
+    }
+    if (lane == 0) out[size_t(q) * F + f] = res;
+    wave_sync();  // the next column overwrites sv and ss
+  }
+}
+
+// ---- host side -----------------------------------------------------------------------------------
+static int check_count(int64_t n) {
+  if (n < 0) return fail(PYQSM_EINVAL, "negative size");
+  if (n > 0x7FFFFF00LL) return fail(PYQSM_ERANGE, "more than 2^31 points per call");
+  return 0;
+}
+
+// The scales for offsets bounded by bound[a] along each axis (zero extents: any scale).
+static FeatScale feat_scale(const double bound[3]) {
+  FeatScale sc;
+  int sh[3];
+  for (int a = 0; a < 3; ++a) {
+    const double b = std::max(bound[a], std::ldexp(1.0, -400));
+    int e = 0;
+    std::frexp(b, &e);  // b < 2^e
+    sh[a] = 61 - e;
+    sc.s1[a] = std::ldexp(1.0, sh[a]);
+    sc.u1[a] = std::ldexp(1.0, -sh[a]);
+  }
+  const int A[6] = {0, 0, 0, 1, 1, 2}, B[6] = {0, 1, 2, 1, 2, 2};
+  for (int e = 0; e < 6; ++e) {
+    sc.s2[e] = std::ldexp(1.0, sh[A[e]] + sh[B[e]] - 61);
+    sc.u2[e] = std::ldexp(1.0, 61 - sh[A[e]] - sh[B[e]]);
+  }
+  return sc;
+}
+
+// The grid the neighbourhood kernels walk: cells of at least `cell`, over the cloud without its
+// sparse tails (they clamp into the outermost cells), as normals.hip builds it.
+static int feature_grid(Ctx* c, const double* d_xyz, int64_t n, double cell, DevGrid* g, double box[6],
+                        bool* all_f32) {
+  PQ_TRY(cloud_bbox(c, d_xyz, n, box, box + 3, all_f32));
+  double rb[6];
+  std::copy(box, box + 6, rb);
+  int64_t outside = 0;
+  PQ_TRY(robust_box(c, d_xyz, n, int(std::min<int64_t>(8192, std::max<int64_t>(256, n / 256))), rb, &outside));
+  return build_grid(c, d_xyz, n, cell, int64_t(1) << 28, g, rb, *all_f32);
+}
+
+// The k nearest of the m queries d_qry among the n points d_src into d_idx [m, k] (k <= n).
+static int query_knn_device(Ctx* c, const double* d_src, int64_t n, const double* d_qry, int64_t m, int k,
+                            int32_t* d_idx) {
+  int32_t *list, *next, *n_next;
+  PQ_TRY(c->arena.get(size_t(m), &list));
+  PQ_TRY(c->arena.get(size_t(m), &next));
+  PQ_TRY(c->arena.get(1, &n_next));
+  hipLaunchKernelGGL(k_iota, dim3(ceil_div(m, 256)), dim3(256), 0, c->stream, int(m), list);
+  PQ_HIP(hipGetLastError());
+  double box[6];
+  bool all_f32 = false;
+  PQ_TRY(cloud_bbox(c, d_src, n, box, box + 3, &all_f32));
+  const double ext = std::max({box[3] - box[0], box[4] - box[1], box[5] - box[2]});
+  // a first radius that holds about k points on a surface-like cloud; doubled for the queries
+  // that find fewer
+  double R = 0.5 * ext * std::sqrt(double(k) / double(n));
+  if (!(R > 0) || !std::isfinite(R)) R = 1.0;
+  int64_t left = m;
+  while (left > 0) {
+    if (!std::isfinite(R * R)) return fail(PYQSM_ERANGE, "query kNN: no radius holds k points");
+    const Arena::Mark mk = c->arena.mark();
+    DevGrid g;
+    double gb[6];
+    bool f32 = false;
+    PQ_TRY(feature_grid(c, d_src, n, R * (1.0 + 1.0 / 1048576.0), &g, gb, &f32));
+    PQ_HIP(hipMemsetAsync(n_next, 0, 4, c->stream));
+    on_coords(g, [&](auto co) {
+      hipLaunchKernelGGL(k_query_knn<decltype(co)>, dim3(ceil_div(left, 2)), dim3(128), 0, c->stream, int(left),
+                         static_cast<const int32_t*>(list), d_qry, grid_params(g), g.start, g.order, co, R * R, k,
+                         int(n), d_idx, next, n_next);
+    });
+    PQ_HIP(hipGetLastError());
+    int32_t nn = 0;
+    PQ_HIP(hipMemcpyAsync(&nn, n_next, 4, hipMemcpyDeviceToHost, c->stream));
+    PQ_HIP(hipStreamSynchronize(c->stream));
+    c->arena.rewind(mk);
+    std::swap(list, next);
+    left = nn;
+    R *= 2.0;
+  }
+  return 0;
+}
+
+}  // namespace pyqsm
+
+using namespace pyqsm;
+
+extern "C" {
+
+int pyqsm_geometric_features(const double* xyz, int64_t n, double radius, int32_t max_k, int32_t metric,
+                             const int32_t* feature_ids, int32_t n_features, double* out, int32_t* counts,
+                             int32_t device) {
+  PQ_API_RANGE("pyqsm_geometric_features");
+  PQ_TRY(check_count(n));
+  if (!(radius > 0) || !std::isfinite(radius)) return fail(PYQSM_EINVAL, "radius must be positive and finite");
+  if (max_k < 1) return fail(PYQSM_ERANGE, "max_k must be at least 1");
+  if (metric != 1 && metric != 2) return fail(PYQSM_EINVAL, "metric must be 2 (L2) or 1 (L1)");
+  if (n_features < 1 || n_features > kFeatMaxCols)
+    return fail(PYQSM_ERANGE, "n_features must be in [1, %d]", kFeatMaxCols);
+  if (!feature_ids) return fail(PYQSM_EINVAL, "pyqsm_geometric_features: NULL pointer");
+  FeatList fl;
+  fl.n = n_features;
+  for (int f = 0; f < kFeatMaxCols; ++f) fl.id[f] = 0;
+  for (int f = 0; f < n_features; ++f) {
+    if (feature_ids[f] < 0 || feature_ids[f] >= kFeatCount)
+      return fail(PYQSM_EINVAL, "feature id %d is not in [0, %d)", int(feature_ids[f]), kFeatCount);
+    fl.id[f] = feature_ids[f];
+  }
+  if (n > 0 && (!xyz || !out)) return fail(PYQSM_EINVAL, "pyqsm_geometric_features: NULL pointer");
+  if (n == 0) return 0;
+  Ctx* c = ctx_for(device);
+  if (!c) return PYQSM_ENODEV;
+  std::lock_guard<std::mutex> lk(c->mu);
+  c->arena.reset();
+  const int N = int(n);
+  double *d_xyz, *cov, *d_out;
+  int32_t *used, *cnt;
+  PQ_TRY(c->arena.get(size_t(n) * 3, &d_xyz));
+  PQ_TRY(c->arena.get(size_t(n) * 6, &cov));
+  PQ_TRY(c->arena.get(size_t(n) * n_features, &d_out));
+  PQ_TRY(c->arena.get(size_t(n), &used));
+  PQ_TRY(c->arena.get(size_t(n), &cnt));
+  PQ_HIP(hipMemcpyAsync(d_xyz, xyz, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+  DevGrid g;
+  double box[6];
+  {
+    ProfScope ps(c, "features_grid");
+    bool all_f32 = false;
+    PQ_TRY(feature_grid(c, d_xyz, n, radius * (1.0 + 1.0 / 1048576.0), &g, box, &all_f32));
+  }
+  // an offset inside the ball is at most the radius (one rounding more) and at most the extent
+  double bound[3];
+  for (int a = 0; a < 3; ++a) bound[a] = std::min(radius * (1.0 + 1.0 / 1048576.0), box[3 + a] - box[a]);
+  const FeatScale sc = feat_scale(bound);
+  {
+    ProfScope ps(c, "features_moments");
+    const double lim = metric == 2 ? radius * radius : radius;
+    on_coords(g, [&](auto co) {
+      if (metric == 2)
+        hipLaunchKernelGGL((k_feat_moments<decltype(co), false>), dim3(ceil_div(n, kFeatWaves)),
+                           dim3(64 * kFeatWaves), 0, c->stream, N, static_cast<const double*>(d_xyz), grid_params(g),
+                           static_cast<const int32_t*>(g.start), static_cast<const int32_t*>(g.order), co, lim,
+                           int(max_k), sc, cov, used, cnt);
+      else
+        hipLaunchKernelGGL((k_feat_moments<decltype(co), true>), dim3(ceil_div(n, kFeatWaves)),
+                           dim3(64 * kFeatWaves), 0, c->stream, N, static_cast<const double*>(d_xyz), grid_params(g),
+                           static_cast<const int32_t*>(g.start), static_cast<const int32_t*>(g.order), co, lim,
+                           int(max_k), sc, cov, used, cnt);
+    });
+    PQ_HIP(hipGetLastError());
+  }
+  {
+    ProfScope ps(c, "features_finish");
+    hipLaunchKernelGGL(k_feat_finish, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, N,
+                       static_cast<const double*>(cov), static_cast<const int32_t*>(used), fl, d_out);
+    PQ_HIP(hipGetLastError());
+  }
+  PQ_HIP(hipMemcpyAsync(out, d_out, size_t(n) * n_features * 8, hipMemcpyDeviceToHost, c->stream));
+  if (counts) PQ_HIP(hipMemcpyAsync(counts, cnt, size_t(n) * 4, hipMemcpyDeviceToHost, c->stream));
+  PQ_HIP(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int pyqsm_smooth_values(const double* xyz, int64_t n, const double* qry, int64_t m, const double* values, int32_t F,
+                        int32_t k, int32_t reducer, double* out, int32_t* idx, int32_t device) {
+  PQ_API_RANGE("pyqsm_smooth_values");
+  PQ_TRY(check_count(n));
+  PQ_TRY(check_count(m));
+  if (!qry && m != n) return fail(PYQSM_EINVAL, "without queries m must equal n");
+  if (k < 1 || k > kSmoothMaxK) return fail(PYQSM_ERANGE, "k must be in [1, %d]", kSmoothMaxK);
+  if (k > n) return fail(PYQSM_EINVAL, "k = %d is larger than the %lld points", int(k), (long long)n);
+  if (reducer < -1 || reducer > 3) return fail(PYQSM_EINVAL, "reducer must be in [-1, 3]");
+  if (reducer >= 0 && (F < 1 || !values || !out)) return fail(PYQSM_EINVAL, "pyqsm_smooth_values: values and out needed");
+  if (reducer < 0 && !idx) return fail(PYQSM_EINVAL, "pyqsm_smooth_values: reducer -1 needs idx");
+  if (!xyz) return fail(PYQSM_EINVAL, "pyqsm_smooth_values: NULL pointer");
+  if (reducer >= 0 && int64_t(F) * std::max<int64_t>(n, m) > (int64_t(1) << 40))
+    return fail(PYQSM_ERANGE, "values too large");
+  if (qry)
+    for (int64_t t = 0; t < 3 * m; ++t)
+      if (!std::isfinite(qry[t])) return fail(PYQSM_EINVAL, "query coordinates must be finite");
+  if (m == 0) return 0;
+  Ctx* c = ctx_for(device);
+  if (!c) return PYQSM_ENODEV;
+  std::lock_guard<std::mutex> lk(c->mu);
+  c->arena.reset();
+  double *d_xyz, *d_qry = nullptr, *d_d2 = nullptr;
+  int32_t* d_idx;
+  PQ_TRY(c->arena.get(size_t(n) * 3, &d_xyz));
+  PQ_TRY(c->arena.get(size_t(m) * k, &d_idx));
+  PQ_HIP(hipMemcpyAsync(d_xyz, xyz, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+  {
+    ProfScope ps(c, "smooth_knn");
+    if (!qry) {
+      PQ_TRY(c->arena.get(size_t(n) * k, &d_d2));
+      PQ_TRY(knn_device(c, d_xyz, n, k, 0, d_idx, d_d2));
+    } else {
+      PQ_TRY(c->arena.get(size_t(m) * 3, &d_qry));
+      PQ_HIP(hipMemcpyAsync(d_qry, qry, size_t(m) * 24, hipMemcpyHostToDevice, c->stream));
+      PQ_TRY(query_knn_device(c, d_xyz, n, d_qry, m, k, d_idx));
+    }
+  }
+  if (reducer >= 0) {
+    double *d_vals, *d_out;
+    PQ_TRY(c->arena.get(size_t(n) * F, &d_vals));
+    PQ_TRY(c->arena.get(size_t(m) * F, &d_out));
+    PQ_HIP(hipMemcpyAsync(d_vals, values, size_t(n) * F * 8, hipMemcpyHostToDevice, c->stream));
+    ProfScope ps(c, "smooth_reduce");
+    hipLaunchKernelGGL(k_smooth_reduce, dim3(ceil_div(m, 2)), dim3(128), 0, c->stream, int(m),
+                       static_cast<const int32_t*>(d_idx), int(k), static_cast<const double*>(d_vals), int(F),
+                       int(reducer), d_out);
+    PQ_HIP(hipGetLastError());
+    PQ_HIP(hipMemcpyAsync(out, d_out, size_t(m) * F * 8, hipMemcpyDeviceToHost, c->stream));
+  }
+  if (idx) PQ_HIP(hipMemcpyAsync(idx, d_idx, size_t(m) * k * 4, hipMemcpyDeviceToHost, c->stream));
+  PQ_HIP(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+}  // extern "C"

@@ -812,3 +812,122 @@ def mark_found_dev(found_ptr: int, n: int, idx, device: int = 0) -> None:
     """``pyqsm_mark_found_dev``: set the device mask at the host indices ``idx``."""
     ix = np.ascontiguousarray(idx, dtype=np.int64).reshape(-1)
     check(_lib.load().pyqsm_mark_found_dev(found_ptr, int(n), _p(ix), ix.shape[0], int(device)))
+
+
+# ---------------------------------------------------------------- geometric features, smoothing
+
+# jakteristics' FEATURE_NAMES, in its order (the ids pyqsm_geometric_features takes)
+FEATURE_NAMES = ("eigenvalue_sum", "omnivariance", "eigenentropy", "anisotropy", "planarity", "linearity",
+                 "PCA1", "PCA2", "surface_variation", "sphericity", "verticality", "nx", "ny", "nz")
+SMOOTH_MAX_K = 192
+SMOOTH_REDUCERS = {"mean": 0, "median": 1, "min": 2, "amin": 2, "max": 3, "amax": 3}
+
+
+def feature_ids(feature_names) -> np.ndarray:
+    """The FEATURE_NAMES ids of ``feature_names`` (a name or a sequence of names), in that order;
+    ValueError naming the valid ones for anything else."""
+    names = [feature_names] if isinstance(feature_names, str) else list(feature_names)
+    if not 1 <= len(names) <= 32:
+        raise ValueError(f"between 1 and 32 feature names are needed, got {len(names)}")
+    bad = [f for f in names if f not in FEATURE_NAMES]
+    if bad:
+        raise ValueError(f"unknown feature name(s) {bad}; valid names: {', '.join(FEATURE_NAMES)}")
+    return np.array([FEATURE_NAMES.index(f) for f in names], dtype=np.int32)
+
+
+def _feature_args(radius, max_k, metric):
+    r = float(radius)
+    if not (r > 0 and np.isfinite(r)):
+        raise ValueError(f"radius must be positive and finite, got {radius!r}")
+    mk = int(max_k)
+    if not 1 <= mk <= 0x7FFFFFFF:
+        raise ValueError(f"max_k must be in [1, 2^31 - 1], got {max_k!r}")
+    codes = {"euclidean": 2, "l2": 2, "manhattan": 1, "l1": 1, "cityblock": 1}
+    if metric not in codes:
+        raise ValueError(f"metric must be one of {sorted(codes)}, got {metric!r}")
+    return r, mk, codes[metric]
+
+
+def geometric_features(points, radius, feature_names=None, max_k: int = 50000, metric: str = "euclidean",
+                       return_counts: bool = False, device: int = 0):
+    """``pyqsm_geometric_features``: float64 [n, F] eigenvalue features of every point's ball
+    (jakteristics' formulas, columns in the order of ``feature_names``, all 14 when None); NaN
+    where fewer than 3 points were kept or lambda1 == 0. ``metric`` "euclidean" or "manhattan".
+    With ``return_counts`` also the int32 [n] ball counts before the ``max_k`` cap."""
+    ids = feature_ids(FEATURE_NAMES if feature_names is None else feature_names)
+    r, mk, code = _feature_args(radius, max_k, metric)
+    pts = _points(points)
+    n = pts.shape[0]
+    out = np.empty((n, len(ids)), dtype=np.float64)
+    cnt = np.empty(n, dtype=np.int32)
+    check(_lib.load().pyqsm_geometric_features(_p(pts), n, r, mk, code, _p(ids), len(ids), _p(out), _p(cnt),
+                                               int(device)))
+    return (out, cnt) if return_counts else out
+
+
+def smooth_reducer(reducer):
+    """The device code of a reducer (np.mean, np.median, np.min / np.amin, np.max / np.amax or
+    those names), or None for any other callable (reduced on the host)."""
+    if isinstance(reducer, str):
+        if reducer not in SMOOTH_REDUCERS:
+            raise ValueError(f"reducer must be one of {sorted(SMOOTH_REDUCERS)} or a callable, got {reducer!r}")
+        return SMOOTH_REDUCERS[reducer]
+    for name, code in SMOOTH_REDUCERS.items():
+        if reducer is getattr(np, name, None):
+            return code
+    if not callable(reducer):
+        raise ValueError(f"reducer must be a name or a callable, got {reducer!r}")
+    return None
+
+
+def _smooth_k(k, n):
+    kk = int(k)
+    if not 1 <= kk <= SMOOTH_MAX_K:
+        raise ValueError(f"k must be in [1, {SMOOTH_MAX_K}], got {k!r}")
+    if kk > n:
+        raise ValueError(f"Expected n_neighbors <= n_samples, but n_samples = {n}, n_neighbors = {kk}")
+    return kk
+
+
+def smooth_values(points, values, k: int, reducer="mean", queries=None, return_indices: bool = False,
+                  device: int = 0):
+    """``pyqsm_smooth_values``: ``reducer`` over the values of each query's ``k`` nearest points
+    (ascending by (d2, index); the queries are the points themselves when ``queries`` is None).
+    ``values`` [n] or [n, F] gives [m] or [m, F]. np.mean / np.median / np.min / np.max (or their
+    names) reduce on the device; any other callable gets ``values[idx]`` ([m, k, ...]) with
+    ``axis=1`` on the host. The result has the dtype NumPy's reducer would give. With
+    ``return_indices`` also the int64 [m, k] neighbour table."""
+    pts = _points(points)
+    n = pts.shape[0]
+    vals = np.asarray(values)
+    if vals.ndim not in (1, 2) or vals.shape[0] != n:
+        raise ValueError(f"values must have shape [{n}] or [{n}, F], got {vals.shape}")
+    kk = _smooth_k(k, n)
+    code = smooth_reducer(reducer)
+    qry = None if queries is None else _points(queries)
+    if qry is not None and not np.isfinite(qry).all():
+        raise ValueError("query coordinates must be finite")
+    m = n if qry is None else qry.shape[0]
+    is_int = vals.dtype.kind in "iub"
+    big_int = is_int and vals.size and np.abs(vals.astype(np.float64)).max() >= 2.0 ** 53
+    if vals.dtype.kind not in "iubf" or (big_int and code in (2, 3)):
+        code = None                                # exact on the host, from the GPU's table
+    host = code is None
+    want_idx = host or return_indices
+    idx = np.empty((m, kk), dtype=np.int32) if want_idx else None
+    F = 1 if vals.ndim == 1 else vals.shape[1]
+    if host:
+        check(_lib.load().pyqsm_smooth_values(_p(pts), n, _p(qry), m, None, F, kk, -1, None, _p(idx), int(device)))
+        red = getattr(np, reducer) if isinstance(reducer, str) else reducer
+        res = red(vals[idx], axis=1)
+    else:
+        v64 = np.ascontiguousarray(vals.reshape(n, F), dtype=np.float64)
+        out = np.empty((m, F), dtype=np.float64)
+        check(_lib.load().pyqsm_smooth_values(_p(pts), n, _p(qry), m, _p(v64), F, kk, code, _p(out), _p(idx),
+                                              int(device)))
+        res = out if vals.ndim == 2 else out[:, 0]
+        if vals.dtype.kind == "f" or code in (2, 3):   # integers: float64 for mean and median
+            res = res.astype(vals.dtype)
+    if return_indices:
+        return res, idx.astype(np.int64)
+    return res
