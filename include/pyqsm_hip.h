@@ -604,6 +604,56 @@ int pyqsm_geometric_features(const double* xyz, int64_t n, double radius, int32_
 int pyqsm_smooth_values(const double* xyz, int64_t n, const double* qry, int64_t m, const double* values,
                         int32_t F, int32_t k, int32_t reducer, double* out, int32_t* idx, int32_t device);
 
+/* ---- tree-ensemble inference -------------------------------------------------------------- */
+/*
+ * Inference of a fitted scikit-learn tree ensemble (pyQSM/exploration.py:460-538: the
+ * RandomForestClassifier that labels points wood / leaf / epiphyte). Training stays on the host.
+ * The contract is scikit-learn's own arithmetic (tree/_tree.pyx _apply_dense,
+ * ForestClassifier.predict_proba with n_jobs=1) and is matched bit for bit;
+ * tests/forest_restatement.py restates it in NumPy; DESIGN.md section 12.
+ *
+ *   row x (float32 [F]; NaN allowed, +-inf is the caller's to reject), per tree from the root: at
+ *   an internal node (feature f, threshold t f64, missing_go_to_left): x[f] NaN goes left when
+ *   the flag is set, else right; otherwise left iff (double)x[f] <= t. A leaf has left == -1.
+ *   leaves[i, k] = the leaf's node number within tree k. acc = 0 (f64 [C]); for k = 0 .. T-1 in
+ *   that order acc += value[leaf_k, :]; proba = acc / T (one division per entry); label = the
+ *   first maximum of proba. No floating-point atomics, no re-associated partial sums: every run
+ *   gives the same bits.
+ *
+ * Limits of the device layout (an 8-byte node record: float32 threshold; missing flag, 8-bit
+ * feature and 22-bit child slot packed; one f64 accumulator per class and lane; a block's rows in
+ * LDS). The float32 threshold is the largest float32 not above t, which decides every float32 x
+ * exactly as (double)x <= t does.
+ */
+#define PYQSM_FOREST_MAX_FEATURES 64
+#define PYQSM_FOREST_MAX_CLASSES 32
+#define PYQSM_FOREST_MAX_TREE_NODES 4194304u /* per tree; 2^31 - 1 in the whole forest */
+/*
+ * pyqsm_forest_create: the T trees' nodes concatenated, tree k in [tree_offsets[k],
+ *   tree_offsets[k+1]) (tree_offsets i64 [T+1], [0] == 0), children as node numbers within their
+ *   tree (left == right == -1: leaf), value f64 [nodes, C]. The topology is validated on the host
+ *   before anything is uploaded: children in range and reached once (so every path ends in a
+ *   leaf), 0 <= feature < F, thresholds not NaN, leaf values finite: PYQSM_EINVAL otherwise;
+ *   beyond the limits above: PYQSM_ERANGE. Nodes no path reaches are ignored. The forest is
+ *   re-laid out, uploaded once to `device` and stays there until pyqsm_forest_free (NULL: no-op).
+ * pyqsm_forest_info: info[0..7] = T, C, F, node records on the device, leaves, depth of the
+ *   deepest leaf (root = 0), device bytes, nodes of each tree staged in LDS.
+ * pyqsm_forest_stage: how many of each tree's first (breadth-first) nodes the kernel reads from
+ *   LDS: 0, 512, 1024 or 2048 (default: 1024 up to 16 features and 8 classes, where a lane walks
+ *   two rows at a time, else 512). Changes speed only, never a result.
+ * pyqsm_forest_predict: X f32 [n, F] on the host; proba f64 [n, C], label i32 [n] (class index)
+ *   and leaves i32 [n, T] on the host, each may be NULL. Rows go through the device in chunks that
+ *   fit the arena; offsets are 64-bit (n * T may exceed 2^31).
+ */
+int pyqsm_forest_create(const int64_t* tree_offsets, const int32_t* left, const int32_t* right,
+                        const int32_t* feature, const double* threshold, const uint8_t* missing_left,
+                        const double* value, int32_t T, int32_t C, int32_t F, int32_t device, void** forest);
+int pyqsm_forest_free(void* forest);
+int pyqsm_forest_info(const void* forest, int64_t info[8]);
+int pyqsm_forest_stage(void* forest, int32_t staged_nodes);
+int pyqsm_forest_predict(const void* forest, const float* X, int64_t n, double* proba, int32_t* label,
+                         int32_t* leaves);
+
 #ifdef __cplusplus
 }
 #endif

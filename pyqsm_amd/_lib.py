@@ -97,6 +97,11 @@ SIGNATURES = {
     "pyqsm_mark_found_dev": (ctypes.c_int, [vp, i64, vp, i64, i32]),
     "pyqsm_geometric_features": (ctypes.c_int, [vp, i64, dbl, i32, i32, vp, i32, vp, vp, i32]),
     "pyqsm_smooth_values": (ctypes.c_int, [vp, i64, vp, i64, vp, i32, i32, i32, vp, vp, i32]),
+    "pyqsm_forest_create": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, ctypes.POINTER(vp)]),
+    "pyqsm_forest_free": (ctypes.c_int, [vp]),
+    "pyqsm_forest_info": (ctypes.c_int, [vp, vp]),
+    "pyqsm_forest_stage": (ctypes.c_int, [vp, i32]),
+    "pyqsm_forest_predict": (ctypes.c_int, [vp, vp, i64, vp, vp, vp]),
 }
 
 _lib = None

@@ -92,7 +92,7 @@ HOT_FUNCTIONS = {
     "utils.lib_integration": ("find_neighbors_in_ball", "get_neighbors_in_tree"),
     "tree_isolation": ("extend_seed_clusters",),
     "qsm_generation": ("fit_cyl_to_cluster",),
-    "exploration": ("compute_features", "smooth_feature"),
+    "exploration": ("compute_features", "smooth_feature", "random_forest_classification"),
     "utils.algo": ("smooth_feature",),
 }
 

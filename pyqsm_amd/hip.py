@@ -931,3 +931,123 @@ def smooth_values(points, values, k: int, reducer="mean", queries=None, return_i
     if return_indices:
         return res, idx.astype(np.int64)
     return res
+
+
+# ---------------------------------------------------------------- tree-ensemble inference
+
+FOREST_MAX_FEATURES = 64
+FOREST_MAX_CLASSES = 32
+FOREST_MAX_TREE_NODES = 1 << 22
+FOREST_STAGED = (0, 512, 1024, 2048)
+
+
+def forest_rows(X, n_features: int) -> np.ndarray:
+    """``X`` as C-contiguous float32 [n, n_features], checked as scikit-learn checks it for a tree:
+    NaN passes, ±inf or a finite value beyond float32's range raises ValueError."""
+    a = np.asarray(X)
+    if a.dtype.kind not in "iubf":
+        raise ValueError(f"X must be numeric, got dtype {a.dtype}")
+    if a.ndim != 2:
+        raise ValueError(f"Expected 2D array, got {a.ndim}D array instead")
+    if a.shape[1] != n_features:
+        raise ValueError(f"X has {a.shape[1]} features, but the forest is expecting {n_features} features as input.")
+    with np.errstate(over="ignore"):
+        x = np.ascontiguousarray(a, dtype=np.float32)
+    if np.isinf(x).any():
+        raise ValueError("Input X contains infinity or a value too large for dtype('float32').")
+    return x
+
+
+class DeviceForest:
+    """A fitted tree ensemble resident in HBM (``pyqsm_forest_create``): the trees' nodes
+    concatenated, tree k in ``tree_offsets[k]:tree_offsets[k+1]``, children as node numbers within
+    their tree (-1: leaf), ``value`` [nodes, C]. Context manager like :class:`DeviceMesh`."""
+
+    def __init__(self, tree_offsets, left, right, feature, threshold, missing_left, value, n_features: int,
+                 device: int = 0):
+        off = np.ascontiguousarray(tree_offsets, dtype=np.int64)
+        if off.ndim != 1 or off.size < 2 or off[0] != 0 or (np.diff(off) < 1).any():
+            raise ValueError("tree_offsets must be [T+1], start at 0 and ascend by at least one node per tree")
+        nodes = int(off[-1])
+        lt = np.ascontiguousarray(left, dtype=np.int32)
+        rt = np.ascontiguousarray(right, dtype=np.int32)
+        ft = np.ascontiguousarray(feature, dtype=np.int32)
+        th = np.ascontiguousarray(threshold, dtype=np.float64)
+        ml = np.ascontiguousarray(missing_left, dtype=np.uint8)
+        val = np.ascontiguousarray(value, dtype=np.float64)
+        for name, a in (("left", lt), ("right", rt), ("feature", ft), ("threshold", th), ("missing_left", ml)):
+            if a.shape != (nodes,):
+                raise ValueError(f"{name} must have shape [{nodes}], got {a.shape}")
+        if val.ndim != 2 or val.shape[0] != nodes or val.shape[1] < 1:
+            raise ValueError(f"value must have shape [{nodes}, C], got {val.shape}")
+        self.n_trees, self.n_classes, self.n_features = off.size - 1, int(val.shape[1]), int(n_features)
+        if not 1 <= self.n_features <= FOREST_MAX_FEATURES:
+            raise ValueError(f"n_features must be in [1, {FOREST_MAX_FEATURES}], got {n_features!r}")
+        if self.n_classes > FOREST_MAX_CLASSES:
+            raise ValueError(f"at most {FOREST_MAX_CLASSES} classes, got {self.n_classes}")
+        if int(np.diff(off).max()) > FOREST_MAX_TREE_NODES:
+            raise ValueError(f"at most {FOREST_MAX_TREE_NODES} nodes per tree, got {int(np.diff(off).max())}")
+        self.device = int(device)
+        self._h = None
+        h = vp()
+        check(_lib.load().pyqsm_forest_create(_p(off), _p(lt), _p(rt), _p(ft), _p(th), _p(ml), _p(val),
+                                              self.n_trees, self.n_classes, self.n_features, self.device,
+                                              ctypes.byref(h)))
+        self._h = h.value
+
+    def _handle(self):
+        if not self._h:
+            raise ValueError("the forest has been freed")
+        return self._h
+
+    def info(self) -> dict:
+        """T, C, F, the node records and leaves on the device, the deepest leaf, device bytes and
+        the nodes of each tree the kernel reads from LDS (``pyqsm_forest_info``)."""
+        out = np.zeros(8, dtype=np.int64)
+        check(_lib.load().pyqsm_forest_info(self._handle(), _p(out)))
+        keys = ("n_trees", "n_classes", "n_features", "nodes", "leaves", "max_depth", "device_bytes", "staged_nodes")
+        return dict(zip(keys, (int(v) for v in out)))
+
+    def stage(self, staged_nodes: int) -> None:
+        """How many of each tree's first nodes are read from LDS (speed only; 0, 512, 1024, 2048)."""
+        if staged_nodes not in FOREST_STAGED:
+            raise ValueError(f"staged_nodes must be one of {FOREST_STAGED}, got {staged_nodes!r}")
+        check(_lib.load().pyqsm_forest_stage(self._handle(), int(staged_nodes)))
+
+    def predict(self, X, proba: bool = True, label: bool = True, leaves: bool = False):
+        """One pass over the rows (``pyqsm_forest_predict``): (proba f64 [n, C], label i32 [n] class
+        index, leaves i32 [n, T]), None for what was not asked for."""
+        h = self._handle()
+        x = forest_rows(X, self.n_features)
+        n = x.shape[0]
+        p = np.empty((n, self.n_classes), dtype=np.float64) if proba else None
+        lab = np.empty(n, dtype=np.int32) if label else None
+        lv = np.empty((n, self.n_trees), dtype=np.int32) if leaves else None
+        check(_lib.load().pyqsm_forest_predict(h, _p(x), n, _p(p), _p(lab), _p(lv)))
+        return p, lab, lv
+
+    def predict_proba(self, X) -> np.ndarray:
+        return self.predict(X, True, False, False)[0]
+
+    def predict_index(self, X) -> np.ndarray:
+        return self.predict(X, False, True, False)[1]
+
+    def apply(self, X) -> np.ndarray:
+        return self.predict(X, False, False, True)[2]
+
+    def free(self) -> None:
+        if self._h:
+            _lib.load().pyqsm_forest_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
