@@ -3,6 +3,7 @@
 
 #include <atomic>
 #include <cmath>
+#include <type_traits>
 
 namespace pyqsm {
 
@@ -803,19 +804,44 @@ __global__ __launch_bounds__(256) void k_order_big(const int32_t* __restrict__ b
 //   A2  k_bk_scatter  every block scans the <= 16384 bucket totals itself (no one-block kernel between the
 //                     passes); the same LDS histogram again, this time returning the rank inside the block;
 //                     a block reserves its share of every bucket with one returning atomic
-//                     (same shape) and writes the 32-byte records bucket by bucket
+//                     (same shape) and writes the records bucket by bucket: 16 bytes (fp32-representable
+//                     clouds) or 32, and the 4-byte key in an array of its own
 //   B   k_bk_sort     one block per bucket, everything in LDS: a count per cell (arrival rank) and
 //                     eight 8-bit counts per cell packed in a u64 (rank inside the octant), a block
 //                     scan of the bucket's cell counts -> the bucket's directory entries,
 //                     written once and coalesced; every point then goes straight to its final,
 //                     octant-ordered place. Cells with more than 255 points (a packed count could
-//                     overflow) are ordered by the same block afterwards, as k_order_big does.
+//                     overflow) are ordered by the same block afterwards, as k_order_big does. A
+//                     bucket of at most 64 points skips the counters: one wave ranks its points.
 // Same arrays as build_grid_octants leaves (the order inside a sub-cell is the arrival order of
 // atomics in both versions, and nothing downstream depends on it).
 static constexpr int kBkMax = 16384;            // buckets (LDS histogram of the A passes: <= 64 KB)
-static constexpr int kBkPts = 2048;             // points per block of the A passes
 static constexpr int kBkBig = 255;              // cells above this are ordered after k_bk_sort's sweep
-static constexpr int kBkPer = 4;                // records a thread of k_bk_sort keeps in registers
+static constexpr int kBkPer = 12;               // points of a bucket whose key and ranks a thread of k_bk_sort keeps
+                                                // in registers, one word each: a bucket of up to 512 * 12 = 6144
+                                                // points (8192-cell buckets: 12288) is sorted without a rank
+                                                // leaving the registers
+
+// Points per 256-thread block of the A passes. 1024 and 512 (two and four times the blocks) were measured
+// against it on the forest: the step 0.366 and 0.389 ms against 0.360 at 1 M points, 1.63 and 1.71 ms
+// against 1.60 at 5 M. What a block pays before its first point (LDS clear, the scan of the bucket
+// totals, one reservation per bucket it touches) does not shrink with its share of the points.
+static constexpr int kBkPts = 2048;
+
+// The bucketed record of a point. Clouds whose coordinates are all fp32-representable (F32: the grid
+// keeps float4 records) move 16 bytes, (x, y, z, index bits); the others three doubles, the index and
+// the key. Both forms leave the key (cell * 8 + octant) in an array of its own as well, which is all
+// that the sort's first sweep reads.
+template <bool F32>
+struct BkRec;
+template <>
+struct BkRec<true> {
+  using type = float4;
+};
+template <>
+struct BkRec<false> {
+  using type = PointRec;
+};
 
 // MODE 0: cell and octant on the raw grid; 1: the same through the axis-compression maps;
 // 2: cell only, clamped into the grid's box (build_grid: what kNN and the radius queries bin with)
@@ -897,15 +923,35 @@ __global__ __launch_bounds__(1024) void k_bk_scan(int nbk, const int32_t* __rest
   if (threadIdx.x == 1023) bstart[nbk] = run;
 }
 
+template <bool F32>
 __global__ __launch_bounds__(256) void k_bk_scatter(const double* __restrict__ xyz, int64_t n, int nbk,
                                                     int bits, const int32_t* __restrict__ key_tmp,
                                                     const int32_t* __restrict__ tot,
                                                     int32_t* __restrict__ cursor /*zeroed*/,
                                                     int32_t* __restrict__ bstart /*[nbk + 1]: written by block 0
                                                     (fused) or read (scanned by k_bk_scan)*/,
-                                                    int fused, PointRec* __restrict__ bucketed,
+                                                    int fused,
+                                                    typename BkRec<F32>::type* __restrict__ bucketed,
+                                                    int32_t* __restrict__ keyb /*the keys in bucket order*/,
                                                     const GridPlan* __restrict__ plan) {
   extern __shared__ __attribute__((aligned(16))) int32_t h[];  // [nbk] ranks / shares (+ [nbk] bucket starts: fused)
+  // the block's keys and coordinates first: their loads are in flight during the scan of the totals
+  const int64_t base = int64_t(blockIdx.x) * kBkPts;
+  using Coord = typename std::conditional<F32, float, double>::type;  // what the record keeps
+  int key[kBkPts / 256], lr[kBkPts / 256];
+  Coord px[kBkPts / 256], py[kBkPts / 256], pz[kBkPts / 256];
+#pragma unroll
+  for (int k = 0; k < kBkPts / 256; ++k) {
+    const int64_t i = base + k * 256 + threadIdx.x;
+    key[k] = -1;
+    px[k] = py[k] = pz[k] = Coord(0);
+    if (i < n) {
+      key[k] = key_tmp[i];
+      px[k] = Coord(xyz[3 * i]);
+      py[k] = Coord(xyz[3 * i + 1]);
+      pz[k] = Coord(xyz[3 * i + 2]);
+    }
+  }
   if (plan) {
     if (!plan->ok) return;
     nbk = plan->nbk;
@@ -915,11 +961,18 @@ __global__ __launch_bounds__(256) void k_bk_scatter(const double* __restrict__ x
   __shared__ int32_t wsum[4];
   for (int b = threadIdx.x; b < nbk; b += 256) h[b] = 0;
   // fused: every block scans the bucket totals itself (<= 16 KB out of L2: cheaper than a one-block
-  // kernel of its own between the two passes): thread t owns `per` consecutive buckets
+  // kernel of its own between the two passes): thread t owns kPer consecutive buckets, whose totals it
+  // loads together and keeps in registers (as a loop of `nbk / 256` loads, each waited for, and run twice,
+  // it was most of the 13 us that a launch of one block with 64 points took on the forest's 3 687 buckets)
   if (fused) {
-    const int per = (nbk + 255) / 256, b0 = threadIdx.x * per;
-    int32_t s = 0;
-    for (int k = 0; k < per; ++k) s += b0 + k < nbk ? tot[b0 + k] : 0;
+    constexpr int kPer = kBkFusedScan / 256;
+    const int b0 = threadIdx.x * kPer;
+    int32_t v[kPer], s = 0;
+#pragma unroll
+    for (int k = 0; k < kPer; ++k) {
+      v[k] = b0 + k < nbk ? tot[b0 + k] : 0;
+      s += v[k];
+    }
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     int32_t incl = s;
 #pragma unroll
@@ -931,41 +984,60 @@ __global__ __launch_bounds__(256) void k_bk_scatter(const double* __restrict__ x
     __syncthreads();
     int32_t run = incl - s;
     for (int q = 0; q < w; ++q) run += wsum[q];
-    for (int k = 0; k < per; ++k) {
+#pragma unroll
+    for (int k = 0; k < kPer; ++k) {
       if (b0 + k < nbk) {
         pre[b0 + k] = run;
         if (blockIdx.x == 0) bstart[b0 + k] = run;
-        run += tot[b0 + k];
       }
+      run += v[k];
     }
-    if (blockIdx.x == 0 && threadIdx.x == 255) bstart[nbk] = run;
+    if (blockIdx.x == 0 && threadIdx.x == 255) bstart[nbk] = run;  // buckets past nbk count as empty
   }
   __syncthreads();
-  const int64_t base = int64_t(blockIdx.x) * kBkPts;
-  int key[kBkPts / 256], lr[kBkPts / 256];
 #pragma unroll
   for (int k = 0; k < kBkPts / 256; ++k) {
-    const int64_t i = base + k * 256 + threadIdx.x;
-    key[k] = i < n ? key_tmp[i] : -1;
     lr[k] = key[k] >= 0 ? atomicAdd(&h[key[k] >> (3 + bits)], 1) : 0;  // rank inside this block's share
   }
   __syncthreads();
-  for (int b = threadIdx.x; b < nbk; b += 256) {
-    const int v = h[b];
-    if (v) h[b] = (fused ? pre[b] : bstart[b]) + atomicAdd(&cursor[b], v);  // this block's share of the bucket
+  // this block's share of every bucket it has points in: the reservations of sixteen buckets per thread
+  // are issued before the first of them is waited for
+  for (int bb = 0; bb < nbk; bb += 16 * 256) {
+    int32_t v[16], a[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const int b = bb + k * 256 + threadIdx.x;
+      v[k] = b < nbk ? h[b] : 0;
+    }
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      a[k] = 0;
+      if (v[k]) a[k] = atomicAdd(&cursor[bb + k * 256 + threadIdx.x], v[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const int b = bb + k * 256 + threadIdx.x;
+      if (v[k]) h[b] = (fused ? pre[b] : bstart[b]) + a[k];
+    }
   }
   __syncthreads();
 #pragma unroll
   for (int k = 0; k < kBkPts / 256; ++k) {
     if (key[k] < 0) continue;
     const int64_t i = base + k * 256 + threadIdx.x;
-    PointRec r;
-    r.x = xyz[3 * i];
-    r.y = xyz[3 * i + 1];
-    r.z = xyz[3 * i + 2];
-    r.idx = int(i);
-    r.key = key[k];
-    bucketed[h[key[k] >> (3 + bits)] + lr[k]] = r;
+    const int pos = h[key[k] >> (3 + bits)] + lr[k];
+    keyb[pos] = key[k];
+    if constexpr (F32) {
+      bucketed[pos] = make_float4(px[k], py[k], pz[k], __int_as_float(int(i)));
+    } else {
+      PointRec r;
+      r.x = px[k];
+      r.y = py[k];
+      r.z = pz[k];
+      r.idx = int(i);
+      r.key = key[k];
+      bucketed[pos] = r;
+    }
   }
 }
 
@@ -988,22 +1060,43 @@ struct BkLds {
   int32_t bw[(1 << BITS) / 512][8];   // per wave: points of each octant in the current chunk
 };
 
+// What sweep 1 leaves of a point, in one word: the key inside the bucket (cell * 8 + octant, BITS + 3
+// <= 16 bits), the arrival rank in the cell saturated at 255 and the arrival rank in the octant. A
+// cell of at most kBkBig points has ranks below 255; a saturated rank belongs to a cell that the
+// block orders afterwards, and its exact value goes through rank_tmp (the octant's rank is not read
+// there).
+__device__ __forceinline__ uint32_t bk_word(int lk, int rr, int r8) {
+  return (uint32_t(lk) << 16) | (uint32_t(rr < 255 ? rr : 255) << 8) | uint32_t(r8);
+}
+
+// records of a bucket that a thread of sweep 2 fetches together, one group ahead of the one it places:
+// two of 16 bytes or one of 32 (more cost over 90 VGPRs, or scratch under the cap of 80 that keeps
+// three blocks on a CU)
+template <bool F32>
+static constexpr int kBkGrp = F32 ? 2 : 1;
+
 // One block per bucket of 2^BITS cells, a thread per eight cells (BITS = 12: 512 threads and 49 KB of
-// LDS, three blocks per CU; BITS = 13 for directories beyond 2^26 cells). A bucket of at most
-// kBkPer points per thread — every bucket of a scan — keeps its records and ranks in registers
-// between the two sweeps: the block's chain of dependent memory round trips is then bstart ->
-// records -> stores. Larger buckets go through rank_tmp / oct_rank in global memory.
-template <int BITS>
-__global__ __launch_bounds__((1 << BITS) / 8) void k_bk_sort(
+// LDS, three blocks per CU; BITS = 13 for directories beyond 2^26 cells). Sweep 1 reads only the
+// 4-byte keys; the keys and ranks of the bucket's first T * kBkPer points stay in registers between
+// the sweeps (on the 1 M-point forest of the benchmark the largest of the 3 687 buckets holds 4 891
+// points: every bucket), and sweep 2 fetches the records in unrolled groups, the next group's loads
+// issued before the current one is placed. The block's chain of dependent memory round trips is
+// bstart -> keys (and the first group of records) -> records -> stores. A bucket beyond the capacity
+// takes further rounds of the same register tile, whose words alone go through word_tmp.
+template <int BITS, bool F32>
+__global__ __launch_bounds__((1 << BITS) / 8, BITS == 12 ? 6 : 4) void k_bk_sort(
     int64_t ncell1 /*directory entries: ncell + 1*/, const int32_t* __restrict__ bstart,
-    const PointRec* __restrict__ bucketed, int32_t* __restrict__ rank_tmp, uint8_t* __restrict__ oct_rank,
-    int32_t* __restrict__ start, int32_t* __restrict__ order, int32_t* __restrict__ cell_of,
-    int32_t* __restrict__ sub_of, double* __restrict__ sx, double* __restrict__ sy, double* __restrict__ sz,
+    const typename BkRec<F32>::type* __restrict__ bucketed, const int32_t* __restrict__ keyb,
+    uint32_t* __restrict__ word_tmp, int32_t* __restrict__ rank_tmp, int32_t* __restrict__ start,
+    int32_t* __restrict__ order, int32_t* __restrict__ cell_of, int32_t* __restrict__ sub_of,
+    double* __restrict__ sx, double* __restrict__ sy, double* __restrict__ sz,
     float4* __restrict__ p4 /*non-null: fp32 records instead of sx / sy / sz*/, int4* __restrict__ rec,
     PointRec* __restrict__ keyed /*big cells' runs in arrival order*/,
     const GridPlan* __restrict__ plan /*ncell1 and the number of buckets (the launch may have more blocks)*/,
     unsigned long long* __restrict__ st /*stamps or null*/) {
-  constexpr int CELLS = 1 << BITS, T = CELLS / 8;
+  constexpr int CELLS = 1 << BITS, T = CELLS / 8, CAP = T * kBkPer, G = kBkGrp<F32>;
+  using Rec = typename BkRec<F32>::type;
+  static_assert(kBkPer % G == 0, "whole groups");
   __shared__ BkLds<BITS> L;
   stamped(st, [&] {
   const int bk = blockIdx.x, t = threadIdx.x;
@@ -1024,16 +1117,83 @@ __global__ __launch_bounds__((1 << BITS) / 8) void k_bk_sort(
     }
     return;
   }
-  const bool inreg = e - s <= T * kBkPer;  // block-uniform
-  PointRec me[kBkPer];
-  int rr[kBkPer], r8[kBkPer];
-  if (inreg) {  // issue the loads before the LDS is cleared
+  if (e - s <= 64) {
+    // A wave's worth of points (two buckets in three on a forest: the grid's box is mostly air): no
+    // counters, no scan. Wave 0 ranks the points against each other, key by key, and places them; every
+    // thread then counts the points in the cells below each of its eight. (3 642 buckets of the 1 M-point
+    // forest's grid took 13.5 us when all were empty, 28.6 us with eleven points each through the
+    // counters: what a block pays for the counters, not the bytes, was the cost of these buckets.)
+    int32_t* const cells = L.cnt;  // [64] the points' cells
+    const int m = e - s;
+    if (t < 64) {
+      const bool live = t < m;
+      const int lk = live ? keyb[s + t] & (8 * CELLS - 1) : 0;
+      Rec p = {};
+      if (live) p = bucketed[s + t];
+      int below_key = 0, below_cell = 0;
+      unsigned long long oc = 0ull;  // the octant counts of this point's cell
+      for (int q = 0; q < m; ++q) {  // wave-uniform
+        const int kq = __builtin_amdgcn_readlane(lk, q);
+        below_key += (kq < lk || (kq == lk && q < t)) ? 1 : 0;
+        below_cell += (kq >> 3) < (lk >> 3) ? 1 : 0;
+        if ((kq >> 3) == (lk >> 3)) oc += 1ull << (8 * (kq & 7));
+      }
+      if (live) {
+        const int cl = lk >> 3, o = lk & 7, b = s + below_cell, f = s + below_key;
+        cells[t] = cl;
+        cell_of[f] = int(c0) + cl;
+        sub_of[f] = b * 8 + o;
+        if constexpr (F32) {
+          order[f] = __float_as_int(p.w);
+          p4[f] = make_float4(p.x, p.y, p.z, 0.f);
+        } else {
+          order[f] = p.idx;
+          sx[f] = p.x;
+          sy[f] = p.y;
+          sz[f] = p.z;
+        }
+        if (below_key == below_cell) {  // the first point of its cell: the cell's sub-cell records
+          int r2 = b;
 #pragma unroll
-    for (int k = 0; k < kBkPer; ++k) {
-      const int j = s + k * T + t;
-      me[k].key = -1;
-      if (j < e) me[k] = bucketed[j];
+          for (int o2 = 0; o2 < 8; ++o2) {
+            const int cnt = int((oc >> (8 * o2)) & 255ull);
+            rec[size_t(b) * 8 + o2] = make_int4(r2, cnt, -1, 0);
+            r2 += cnt;
+          }
+        }
+      }
     }
+    __syncthreads();
+    int32_t pre[8] = {s, s, s, s, s, s, s, s};
+    for (int q = 0; q < m; ++q) {
+      const int d = cells[q] - 8 * t;  // the same address in every lane
+#pragma unroll
+      for (int k = 0; k < 8; ++k) pre[k] += d < k ? 1 : 0;
+    }
+    const int64_t cidx = c0 + 8 * t;
+    if (cidx + 7 < ncell1) {
+      *reinterpret_cast<int4*>(start + cidx) = make_int4(pre[0], pre[1], pre[2], pre[3]);
+      *reinterpret_cast<int4*>(start + cidx + 4) = make_int4(pre[4], pre[5], pre[6], pre[7]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (cidx + k < ncell1) start[cidx + k] = pre[k];
+    }
+    return;
+  }
+  // the loads are issued before the LDS is cleared: the keys of the register tile (point k * T + t of
+  // the bucket is thread t's k-th) and the first group of records
+  uint32_t wd[kBkPer];
+#pragma unroll
+  for (int k = 0; k < kBkPer; ++k) {
+    const int j = s + k * T + t;
+    wd[k] = j < e ? uint32_t(keyb[j]) : 0u;
+  }
+  Rec cur[G] = {};
+#pragma unroll
+  for (int k = 0; k < G; ++k) {
+    const int j = s + k * T + t;
+    if (j < e) cur[k] = bucketed[j];
   }
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
@@ -1044,21 +1204,29 @@ __global__ __launch_bounds__((1 << BITS) / 8) void k_bk_sort(
   if (t == 0) L.any_big = 0;
   __syncthreads();
   // sweep 1: arrival rank in the cell and in the octant
-  if (inreg) {
+  auto rank_of = [&](uint32_t ky, int j) {
+    const int lk = int(ky) & (8 * CELLS - 1), cl = lk >> 3, o = lk & 7;
+    const int rr = atomicAdd(&L.cnt[cl], 1);
+    const int r8 = int((atomicAdd(&L.oct[cl], 1ull << (8 * o)) >> (8 * o)) & 255ull);
+    if (rr >= 255) rank_tmp[j] = rr;
+    return bk_word(lk, rr, r8);
+  };
+#pragma unroll
+  for (int k = 0; k < kBkPer; ++k) {
+    const int j = s + k * T + t;
+    if (j < e) wd[k] = rank_of(wd[k], j);
+  }
+  for (int base = s + CAP; base < e; base += CAP) {  // block-uniform: further rounds of the tile
+    uint32_t kk[kBkPer];
 #pragma unroll
     for (int k = 0; k < kBkPer; ++k) {
-      if (me[k].key < 0) continue;
-      const int cl = (me[k].key >> 3) & (CELLS - 1), o = me[k].key & 7;
-      rr[k] = atomicAdd(&L.cnt[cl], 1);
-      r8[k] = int((atomicAdd(&L.oct[cl], 1ull << (8 * o)) >> (8 * o)) & 255ull);
+      const int j = base + k * T + t;
+      kk[k] = j < e ? uint32_t(keyb[j]) : 0u;
     }
-  } else {
-    for (int j = s + t; j < e; j += T) {
-      const int key = bucketed[j].key;
-      const int cl = (key >> 3) & (CELLS - 1), o = key & 7;
-      rank_tmp[j] = atomicAdd(&L.cnt[cl], 1);
-      const unsigned long long old = atomicAdd(&L.oct[cl], 1ull << (8 * o));
-      oct_rank[j] = uint8_t(old >> (8 * o));  // meaningful only in cells of at most kBkBig points
+#pragma unroll
+    for (int k = 0; k < kBkPer; ++k) {
+      const int j = base + k * T + t;
+      if (j < e) word_tmp[j] = rank_of(kk[k], j);
     }
   }
   __syncthreads();
@@ -1122,31 +1290,75 @@ __global__ __launch_bounds__((1 << BITS) / 8) void k_bk_sort(
   }
   __syncthreads();
   // sweep 2: every point to its final place (big cells: to the cell's run of `keyed`, in arrival order)
-  auto place = [&](const PointRec& p, int arrival, int in_oct) {
-    const int cl = (p.key >> 3) & (CELLS - 1), o = p.key & 7;
+  auto place = [&](const Rec& p, uint32_t w, int j) {
+    const int lk = int(w >> 16), cl = lk >> 3, o = lk & 7, arr = int((w >> 8) & 255u);
     const int b = s + L.cnt[cl];
     if ((L.big[cl >> 5] >> (cl & 31)) & 1u) {
-      keyed[b + arrival] = p;
+      PointRec q;
+      q.x = p.x;
+      q.y = p.y;
+      q.z = p.z;
+      q.key = int(c0 << 3) + lk;
+      if constexpr (F32)
+        q.idx = __float_as_int(p.w);
+      else
+        q.idx = p.idx;
+      keyed[b + (arr < 255 ? arr : rank_tmp[j])] = q;
       return;
     }
-    const int f = b + bytes_below(L.oct[cl], o) + in_oct;
-    order[f] = p.idx;
-    cell_of[f] = p.key >> 3;
+    const int f = b + bytes_below(L.oct[cl], o) + int(w & 255u);
+    cell_of[f] = int(c0) + cl;
     sub_of[f] = b * 8 + o;
-    if (p4) {
-      p4[f] = make_float4(float(p.x), float(p.y), float(p.z), 0.f);
+    if constexpr (F32) {
+      order[f] = __float_as_int(p.w);
+      p4[f] = make_float4(p.x, p.y, p.z, 0.f);
     } else {
+      order[f] = p.idx;
       sx[f] = p.x;
       sy[f] = p.y;
       sz[f] = p.z;
     }
   };
-  if (inreg) {
 #pragma unroll
-    for (int k = 0; k < kBkPer; ++k)
-      if (me[k].key >= 0) place(me[k], rr[k], r8[k]);
-  } else {
-    for (int j = s + t; j < e; j += T) place(bucketed[j], rank_tmp[j], int(oct_rank[j]));
+  for (int g = 0; g < kBkPer / G; ++g) {
+    if (s + g * G * T >= e) break;  // block-uniform
+    Rec nxt[G] = {};
+    if (g + 1 < kBkPer / G) {
+#pragma unroll
+      for (int k = 0; k < G; ++k) {
+        const int j = s + ((g + 1) * G + k) * T + t;
+        if (j < e) nxt[k] = bucketed[j];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < G; ++k) {
+      const int j = s + (g * G + k) * T + t;
+      if (j < e) place(cur[k], wd[g * G + k], j);
+    }
+#pragma unroll
+    for (int k = 0; k < G; ++k) cur[k] = nxt[k];
+  }
+  for (int base = s + CAP; base < e; base += CAP) {  // block-uniform
+#pragma unroll
+    for (int g = 0; g < kBkPer / G; ++g) {
+      if (base + g * G * T >= e) break;
+      Rec r[G] = {};
+      uint32_t w[G];
+#pragma unroll
+      for (int k = 0; k < G; ++k) {
+        const int j = base + (g * G + k) * T + t;
+        w[k] = 0u;
+        if (j < e) {
+          r[k] = bucketed[j];
+          w[k] = word_tmp[j];
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < G; ++k) {
+        const int j = base + (g * G + k) * T + t;
+        if (j < e) place(r[k], w[k], j);
+      }
+    }
   }
   // Cells above kBkBig points (none on a scan at eps ~ 10 x the point spacing): the whole block sorts each
   // one's run of `keyed` by octant, stable in arrival order, as k_order_big does for the atomic binning (two
@@ -1227,13 +1439,15 @@ __global__ __launch_bounds__((1 << BITS) / 8) void k_bk_sort(
 // The same second level without octants (build_grid): a count per cell is all there is, so a bucket
 // of 2^BITS cells needs 4 bytes of LDS per cell, the arrival rank IS the place inside the cell, and
 // no cell is too big. occ[bucket] = occupied cells of the bucket (count_occupied adds them up).
-template <int BITS>
-__global__ __launch_bounds__((1 << BITS) / 8) void k_bk_sort_plain(
-    int64_t ncell1, const int32_t* __restrict__ bstart, const PointRec* __restrict__ bucketed,
-    int32_t* __restrict__ rank_tmp, int32_t* __restrict__ start, int32_t* __restrict__ order,
+template <int BITS, bool F32>
+__global__ __launch_bounds__((1 << BITS) / 8, BITS == 12 ? 6 : 4) void k_bk_sort_plain(
+    int64_t ncell1, const int32_t* __restrict__ bstart, const typename BkRec<F32>::type* __restrict__ bucketed,
+    const int32_t* __restrict__ keyb, uint32_t* __restrict__ word_tmp, int32_t* __restrict__ rank_tmp,
+    int32_t* __restrict__ start, int32_t* __restrict__ order,
     int32_t* __restrict__ cell_of, double* __restrict__ sx, double* __restrict__ sy, double* __restrict__ sz,
     float4* __restrict__ p4 /*non-null: fp32 records instead of sx / sy / sz*/, int32_t* __restrict__ occ) {
-  constexpr int CELLS = 1 << BITS, T = CELLS / 8;
+  constexpr int CELLS = 1 << BITS, T = CELLS / 8, CAP = T * kBkPer, G = kBkGrp<F32>;
+  using Rec = typename BkRec<F32>::type;
   __shared__ int32_t cnt[CELLS];
   __shared__ int32_t wsum[16], wocc[16];
   const int bk = blockIdx.x, t = threadIdx.x;
@@ -1253,26 +1467,50 @@ __global__ __launch_bounds__((1 << BITS) / 8) void k_bk_sort_plain(
     if (t == 0) occ[bk] = 0;
     return;
   }
-  const bool inreg = e - s <= T * kBkPer;
-  PointRec me[kBkPer];
-  int rr[kBkPer];
-  if (inreg) {
+  // as k_bk_sort: a word per point of the first CAP points in registers (the cell inside the bucket in
+  // the top BITS bits, below it the arrival rank, saturated: the exact value of a rank that does not fit
+  // goes through rank_tmp), the records fetched in groups by the second sweep, further rounds of the
+  // tile for a bucket beyond CAP
+  constexpr int RB = 32 - BITS;
+  constexpr int RMAX = (1 << RB) - 1;
+  uint32_t wd[kBkPer];
 #pragma unroll
-    for (int k = 0; k < kBkPer; ++k) {
-      const int j = s + k * T + t;
-      me[k].key = -1;
-      if (j < e) me[k] = bucketed[j];
-    }
+  for (int k = 0; k < kBkPer; ++k) {
+    const int j = s + k * T + t;
+    wd[k] = j < e ? uint32_t(keyb[j]) : 0u;
+  }
+  Rec cur[G] = {};
+#pragma unroll
+  for (int k = 0; k < G; ++k) {
+    const int j = s + k * T + t;
+    if (j < e) cur[k] = bucketed[j];
   }
 #pragma unroll
   for (int k = 0; k < 8; ++k) cnt[k * T + t] = 0;
   __syncthreads();
-  if (inreg) {
+  auto rank_of = [&](uint32_t ky, int j) {
+    const int cl = int(ky >> 3) & (CELLS - 1);
+    const int rr = atomicAdd(&cnt[cl], 1);
+    if (rr >= RMAX) rank_tmp[j] = rr;
+    return (uint32_t(cl) << RB) | uint32_t(rr < RMAX ? rr : RMAX);
+  };
 #pragma unroll
-    for (int k = 0; k < kBkPer; ++k)
-      if (me[k].key >= 0) rr[k] = atomicAdd(&cnt[(me[k].key >> 3) & (CELLS - 1)], 1);
-  } else {
-    for (int j = s + t; j < e; j += T) rank_tmp[j] = atomicAdd(&cnt[(bucketed[j].key >> 3) & (CELLS - 1)], 1);
+  for (int k = 0; k < kBkPer; ++k) {
+    const int j = s + k * T + t;
+    if (j < e) wd[k] = rank_of(wd[k], j);
+  }
+  for (int base = s + CAP; base < e; base += CAP) {  // block-uniform
+    uint32_t kk[kBkPer];
+#pragma unroll
+    for (int k = 0; k < kBkPer; ++k) {
+      const int j = base + k * T + t;
+      kk[k] = j < e ? uint32_t(keyb[j]) : 0u;
+    }
+#pragma unroll
+    for (int k = 0; k < kBkPer; ++k) {
+      const int j = base + k * T + t;
+      if (j < e) word_tmp[j] = rank_of(kk[k], j);
+    }
   }
   __syncthreads();
   int32_t v[8], tot = 0, nocc = 0;
@@ -1326,24 +1564,60 @@ __global__ __launch_bounds__((1 << BITS) / 8) void k_bk_sort_plain(
 #pragma unroll
   for (int k = 0; k < 8; ++k) cnt[8 * t + k] = pre[k];
   __syncthreads();
-  auto place = [&](const PointRec& p, int arrival) {
-    const int f = s + cnt[(p.key >> 3) & (CELLS - 1)] + arrival;
-    order[f] = p.idx;
-    cell_of[f] = p.key >> 3;
-    if (p4) {
-      p4[f] = make_float4(float(p.x), float(p.y), float(p.z), 0.f);
+  auto place = [&](const Rec& p, uint32_t w, int j) {
+    const int cl = int(w >> RB), arr = int(w & uint32_t(RMAX));
+    const int f = s + cnt[cl] + (arr < RMAX ? arr : rank_tmp[j]);
+    cell_of[f] = int(c0) + cl;
+    if constexpr (F32) {
+      order[f] = __float_as_int(p.w);
+      p4[f] = make_float4(p.x, p.y, p.z, 0.f);
     } else {
+      order[f] = p.idx;
       sx[f] = p.x;
       sy[f] = p.y;
       sz[f] = p.z;
     }
   };
-  if (inreg) {
 #pragma unroll
-    for (int k = 0; k < kBkPer; ++k)
-      if (me[k].key >= 0) place(me[k], rr[k]);
-  } else {
-    for (int j = s + t; j < e; j += T) place(bucketed[j], rank_tmp[j]);
+  for (int g = 0; g < kBkPer / G; ++g) {
+    if (s + g * G * T >= e) break;  // block-uniform
+    Rec nxt[G] = {};
+    if (g + 1 < kBkPer / G) {
+#pragma unroll
+      for (int k = 0; k < G; ++k) {
+        const int j = s + ((g + 1) * G + k) * T + t;
+        if (j < e) nxt[k] = bucketed[j];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < G; ++k) {
+      const int j = s + (g * G + k) * T + t;
+      if (j < e) place(cur[k], wd[g * G + k], j);
+    }
+#pragma unroll
+    for (int k = 0; k < G; ++k) cur[k] = nxt[k];
+  }
+  for (int base = s + CAP; base < e; base += CAP) {  // block-uniform
+#pragma unroll
+    for (int g = 0; g < kBkPer / G; ++g) {
+      if (base + g * G * T >= e) break;
+      Rec r[G] = {};
+      uint32_t w[G];
+#pragma unroll
+      for (int k = 0; k < G; ++k) {
+        const int j = base + (g * G + k) * T + t;
+        w[k] = 0u;
+        if (j < e) {
+          r[k] = bucketed[j];
+          w[k] = word_tmp[j];
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < G; ++k) {
+        const int j = base + (g * G + k) * T + t;
+        if (j < e) place(r[k], w[k], j);
+      }
+    }
   }
 }
 
@@ -1357,37 +1631,80 @@ static bool bucketed_fits(const DevGrid& g) {
   return nbk <= kBkMax && !(env && !strcmp(env, "atomic"));
 }
 
+// the A passes; `bucketed` holds float4 (f32) or PointRec records
+static void enqueue_bk_a(Ctx* c, int mode, bool f32, const double* xyz, int64_t n, const GridParams& gp,
+                         const int raw[3], AxisMap am, int64_t nbk, int bits, int32_t* key_tmp, int32_t* tot,
+                         int32_t* cursor, int32_t* bstart, void* bucketed, int32_t* keyb, const GridPlan* d_plan) {
+  const dim3 ga(ceil_div(n, kBkPts)), blk(256);
+  const size_t lds = size_t(nbk) * 4;
+  const int fused = nbk <= kBkFusedScan;
+#define PQ_BK_HIST(MODE)                                                                                         \
+  hipLaunchKernelGGL(k_bk_hist<MODE>, ga, blk, lds, c->stream, xyz, n, gp, raw[0], raw[1], raw[2], am, int(nbk), \
+                     bits, key_tmp, tot, d_plan)
+  if (mode == 0)
+    PQ_BK_HIST(0);
+  else if (mode == 1)
+    PQ_BK_HIST(1);
+  else
+    PQ_BK_HIST(2);
+#undef PQ_BK_HIST
+  if (!fused) hipLaunchKernelGGL(k_bk_scan, dim3(1), dim3(1024), 0, c->stream, int(nbk), tot, bstart, d_plan);
+  if (f32)
+    hipLaunchKernelGGL(k_bk_scatter<true>, ga, blk, fused ? 2 * lds : lds, c->stream, xyz, n, int(nbk), bits,
+                       key_tmp, tot, cursor, bstart, fused, static_cast<float4*>(bucketed), keyb, d_plan);
+  else
+    hipLaunchKernelGGL(k_bk_scatter<false>, ga, blk, fused ? 2 * lds : lds, c->stream, xyz, n, int(nbk), bits,
+                       key_tmp, tot, cursor, bstart, fused, static_cast<PointRec*>(bucketed), keyb, d_plan);
+}
+
+template <int BITS, bool F32>
+static void launch_bk_sort_plain(Ctx* c, int64_t nbk, const int32_t* bstart, const void* bucketed, const int32_t* keyb,
+                                 uint32_t* word_tmp, int32_t* rank_tmp, DevGrid* g) {
+  hipLaunchKernelGGL((k_bk_sort_plain<BITS, F32>), dim3(unsigned(nbk)), dim3((1 << BITS) / 8), 0, c->stream,
+                     g->ncell + 1, bstart, static_cast<const typename BkRec<F32>::type*>(bucketed), keyb, word_tmp,
+                     rank_tmp, g->start, g->order, g->cell_of, g->sx, g->sy, g->sz, g->p4, g->occ_part);
+}
+
 static int build_grid_bucketed(Ctx* c, const double* xyz, int64_t n, DevGrid* g) {
   const int bits = g->ncell + 1 <= (int64_t(kBkMax) << 12) ? 12 : 13;
   const int64_t nbk = (g->ncell + (int64_t(1) << bits)) >> bits;
-  int32_t *tot, *bstart, *cursor, *key_tmp, *rank_tmp;
-  PointRec* bucketed;
+  const bool f32 = g->p4 != nullptr;  // float4 records in, float4 records out
+  int32_t *tot, *bstart, *cursor, *key_tmp, *keyb, *rank_tmp;
+  uint32_t* word_tmp;
+  void* bucketed;
   PQ_TRY(c->arena.get(size_t(nbk) * 2, &tot));  // totals, then the reservation cursors: one memset
   cursor = tot + nbk;
   PQ_TRY(c->arena.get(size_t(nbk) + 1, &bstart));
   PQ_TRY(c->arena.get(size_t(n), &key_tmp));
+  PQ_TRY(c->arena.get(size_t(n), &keyb));
+  PQ_TRY(c->arena.get(size_t(n), &word_tmp));
   PQ_TRY(c->arena.get(size_t(n), &rank_tmp));
-  PQ_TRY(c->arena.get(size_t(n), &bucketed));
+  if (f32) {
+    float4* b4;
+    PQ_TRY(c->arena.get(size_t(n), &b4));
+    bucketed = b4;
+  } else {
+    PointRec* b8;
+    PQ_TRY(c->arena.get(size_t(n), &b8));
+    bucketed = b8;
+  }
   g->occ_blocks = int(nbk);
   PQ_TRY(c->arena.get(size_t(nbk), &g->occ_part));
   PQ_HIP(hipMemsetAsync(tot, 0, size_t(nbk) * 8, c->stream));
-  const GridParams gp = grid_params(*g);
-  const dim3 ga(ceil_div(n, kBkPts)), blk(256);
-  const size_t lds = size_t(nbk) * 4;
-  const int fused = nbk <= kBkFusedScan;
-  hipLaunchKernelGGL(k_bk_hist<2>, ga, blk, lds, c->stream, xyz, n, gp, 0, 0, 0, AxisMap{nullptr, nullptr, nullptr},
-                     int(nbk), bits, key_tmp, tot, static_cast<const GridPlan*>(nullptr));
-  if (!fused)
-    hipLaunchKernelGGL(k_bk_scan, dim3(1), dim3(1024), 0, c->stream, int(nbk), tot, bstart,
-                       static_cast<const GridPlan*>(nullptr));
-  hipLaunchKernelGGL(k_bk_scatter, ga, blk, fused ? 2 * lds : lds, c->stream, xyz, n, int(nbk), bits, key_tmp, tot,
-                     cursor, bstart, fused, bucketed, static_cast<const GridPlan*>(nullptr));
-  if (bits == 12)
-    hipLaunchKernelGGL(k_bk_sort_plain<12>, dim3(unsigned(nbk)), dim3(512), 0, c->stream, g->ncell + 1, bstart,
-                       bucketed, rank_tmp, g->start, g->order, g->cell_of, g->sx, g->sy, g->sz, g->p4, g->occ_part);
-  else
-    hipLaunchKernelGGL(k_bk_sort_plain<13>, dim3(unsigned(nbk)), dim3(1024), 0, c->stream, g->ncell + 1, bstart,
-                       bucketed, rank_tmp, g->start, g->order, g->cell_of, g->sx, g->sy, g->sz, g->p4, g->occ_part);
+  const int raw[3] = {0, 0, 0};
+  enqueue_bk_a(c, 2, f32, xyz, n, grid_params(*g), raw, AxisMap{nullptr, nullptr, nullptr}, nbk, bits, key_tmp, tot,
+               cursor, bstart, bucketed, keyb, nullptr);
+  if (bits == 12) {
+    if (f32)
+      launch_bk_sort_plain<12, true>(c, nbk, bstart, bucketed, keyb, word_tmp, rank_tmp, g);
+    else
+      launch_bk_sort_plain<12, false>(c, nbk, bstart, bucketed, keyb, word_tmp, rank_tmp, g);
+  } else {
+    if (f32)
+      launch_bk_sort_plain<13, true>(c, nbk, bstart, bucketed, keyb, word_tmp, rank_tmp, g);
+    else
+      launch_bk_sort_plain<13, false>(c, nbk, bstart, bucketed, keyb, word_tmp, rank_tmp, g);
+  }
   PQ_HIP(hipGetLastError());
   return 0;
 }
@@ -1468,56 +1785,64 @@ int octant_zeroed_ints() { return 2 * kBkMax + 5 + kZeroedExtra; }
 // The output arrays of the octant binning and the two-level sort's launches, for a directory of at
 // most ncell cells in nbk buckets (the plan's exact numbers, or the hint's bounds); the kernels
 // read the grid itself from d_plan.
+template <int BITS, bool F32>
+static void launch_bk_sort(Ctx* c, int64_t ncell, int64_t nbk, const int32_t* bstart, const void* bucketed,
+                           const int32_t* keyb, uint32_t* word_tmp, int32_t* rank_tmp, PointRec* keyed,
+                           const GridPlan* d_plan, DevGrid* g, SubCells* sub) {
+  unsigned long long* const st_sort = stamp_slots(c, nbk);  // the binning's last kernel
+  hipLaunchKernelGGL((k_bk_sort<BITS, F32>), dim3(unsigned(nbk)), dim3((1 << BITS) / 8), 0, c->stream, ncell + 1, bstart,
+                     static_cast<const typename BkRec<F32>::type*>(bucketed), keyb, word_tmp, rank_tmp, g->start, g->order,
+                     g->cell_of, sub->sub_of, g->sx, g->sy, g->sz, g->p4, sub->rec, keyed, d_plan, st_sort);
+}
+
 static int enqueue_bucketed(Ctx* c, const double* xyz, int64_t n, const GridParams& gp, const int raw[3],
                             AxisMap am, bool mapped, int64_t ncell, int64_t nbk, int bits, bool f32,
                             int32_t* zeroed, const GridPlan* d_plan, DevGrid* g, SubCells* sub) {
-  int32_t *cell_tmp, *rank_tmp, *bstart;
+  int32_t *cell_tmp, *keyb, *rank_tmp, *bstart;
+  uint32_t* word_tmp;
   int32_t *tot = zeroed, *cursor = zeroed + kBkMax;
-  PointRec *keyed, *bucketed;
-  uint8_t* oct_rank;
+  PointRec* keyed;
+  void* bucketed;
   g->p4 = nullptr;
   g->sx = g->sy = g->sz = nullptr;
+  sub->sub_cnt = sub->sub_beg = nullptr;  // nothing reads them on this path: `rec` holds both
   PQ_TRY(c->arena.get(size_t(ncell) + 1, &g->start));
   PQ_TRY(c->arena.get(size_t(n), &g->order));
   PQ_TRY(c->arena.get(size_t(n), &g->cell_of));
   if (f32) {
+    float4* b4;
     PQ_TRY(c->arena.get(size_t(n), &g->p4));
+    PQ_TRY(c->arena.get(size_t(n), &b4));
+    bucketed = b4;
   } else {
+    PointRec* b8;
     PQ_TRY(c->arena.get(size_t(n), &g->sx));
     PQ_TRY(c->arena.get(size_t(n), &g->sy));
     PQ_TRY(c->arena.get(size_t(n), &g->sz));
+    PQ_TRY(c->arena.get(size_t(n), &b8));
+    bucketed = b8;
   }
   PQ_TRY(c->arena.get(size_t(n), &cell_tmp));
+  PQ_TRY(c->arena.get(size_t(n), &keyb));
+  PQ_TRY(c->arena.get(size_t(n), &word_tmp));
   PQ_TRY(c->arena.get(size_t(n), &rank_tmp));
   PQ_TRY(c->arena.get(size_t(n), &keyed));
-  PQ_TRY(c->arena.get(size_t(n) * 8, &sub->sub_cnt));
-  PQ_TRY(c->arena.get(size_t(n) * 8, &sub->sub_beg));
   PQ_TRY(c->arena.get(size_t(n), &sub->sub_of));
   PQ_TRY(c->arena.get(size_t(n) * 8, &sub->rec));
   PQ_TRY(c->arena.get(size_t(nbk) + 1, &bstart));
-  PQ_TRY(c->arena.get(size_t(n), &oct_rank));
-  PQ_TRY(c->arena.get(size_t(n), &bucketed));
-  const dim3 ga(ceil_div(n, kBkPts)), blk(256);
-  const size_t lds = size_t(nbk) * 4;
-  if (mapped)
-    hipLaunchKernelGGL(k_bk_hist<1>, ga, blk, lds, c->stream, xyz, n, gp, raw[0], raw[1], raw[2], am, int(nbk), bits,
-                       cell_tmp, tot, d_plan);
-  else
-    hipLaunchKernelGGL(k_bk_hist<0>, ga, blk, lds, c->stream, xyz, n, gp, raw[0], raw[1], raw[2], am, int(nbk), bits,
-                       cell_tmp, tot, d_plan);
-  const int fused = nbk <= kBkFusedScan;
-  if (!fused) hipLaunchKernelGGL(k_bk_scan, dim3(1), dim3(1024), 0, c->stream, int(nbk), tot, bstart, d_plan);
-  hipLaunchKernelGGL(k_bk_scatter, ga, blk, fused ? 2 * lds : lds, c->stream, xyz, n, int(nbk), bits, cell_tmp, tot,
-                     cursor, bstart, fused, bucketed, d_plan);
-  unsigned long long* const st_sort = stamp_slots(c, nbk);  // the binning's last kernel
-  if (bits == 12)
-    hipLaunchKernelGGL(k_bk_sort<12>, dim3(unsigned(nbk)), dim3(512), 0, c->stream, ncell + 1, bstart, bucketed,
-                       rank_tmp, oct_rank, g->start, g->order, g->cell_of, sub->sub_of, g->sx, g->sy, g->sz, g->p4,
-                       sub->rec, keyed, d_plan, st_sort);
-  else
-    hipLaunchKernelGGL(k_bk_sort<13>, dim3(unsigned(nbk)), dim3(1024), 0, c->stream, ncell + 1, bstart, bucketed,
-                       rank_tmp, oct_rank, g->start, g->order, g->cell_of, sub->sub_of, g->sx, g->sy, g->sz, g->p4,
-                       sub->rec, keyed, d_plan, st_sort);
+  enqueue_bk_a(c, mapped ? 1 : 0, f32, xyz, n, gp, raw, am, nbk, bits, cell_tmp, tot, cursor, bstart, bucketed, keyb,
+               d_plan);
+  if (bits == 12) {
+    if (f32)
+      launch_bk_sort<12, true>(c, ncell, nbk, bstart, bucketed, keyb, word_tmp, rank_tmp, keyed, d_plan, g, sub);
+    else
+      launch_bk_sort<12, false>(c, ncell, nbk, bstart, bucketed, keyb, word_tmp, rank_tmp, keyed, d_plan, g, sub);
+  } else {
+    if (f32)
+      launch_bk_sort<13, true>(c, ncell, nbk, bstart, bucketed, keyb, word_tmp, rank_tmp, keyed, d_plan, g, sub);
+    else
+      launch_bk_sort<13, false>(c, ncell, nbk, bstart, bucketed, keyb, word_tmp, rank_tmp, keyed, d_plan, g, sub);
+  }
   PQ_HIP(hipGetLastError());
   return 0;
 }

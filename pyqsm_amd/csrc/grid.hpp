@@ -247,8 +247,8 @@ inline void on_coords(const DevGrid& g, F&& fn) {
 // [sub_beg[id], sub_beg[id] + sub_cnt[id]). sub_cnt is zero for empty octants of an
 // occupied cell; entries of unoccupied ids are never written and must not be read.
 struct SubCells {
-  int32_t* sub_cnt;  // [8 n]
-  int32_t* sub_beg;  // [8 n]
+  int32_t* sub_cnt;  // [8 n]; null from the two-level sort (k_bk_sort), which writes `rec` alone
+  int32_t* sub_beg;  // [8 n]; likewise
   int32_t* sub_of;   // [n] sub-cell id of each sorted position
   int4* rec;         // [8 n] (sub_beg, sub_cnt, -1, 0) in one 16-byte record; .z is the caller's
   // bin_octants_*: four ints the bounding box's fold left zeroed, for the caller's counters
