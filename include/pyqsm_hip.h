@@ -325,6 +325,39 @@ int pyqsm_radius_label(const double* src, int64_t n, const double* qry, int64_t 
                        const int32_t* qry_label, double radius, int32_t k_cap, int32_t* label,
                        int32_t* counts, int32_t device);
 
+/* ---- cluster adjacency ------------------------------------------------------ */
+/*
+ * Which clusters of a labelled cloud touch which clusters of another, how closely and at how many
+ * point pairs: the graph pyQSM/cluster_joining.py:126-164 (determine_adjacency) builds from one
+ * cKDTree.sparse_distance_matrix(tree_j, threshold) per cluster pair, in one grid pass.
+ *   src f64 [n,3] with src_label i32 [n] in [0, n_src_labels); tgt f64 [m,3] with tgt_label i32 [m]
+ *   in [0, n_tgt_labels). A negative label means "ignore this point". A point pair counts when
+ *   d2 = ((dx*dx) + dy*dy) + dz*dz <= threshold * threshold, both in fp64 (inclusive; zero counts).
+ *   One row per cluster pair (a, b) with at least one such point pair, ascending by (a, b):
+ *   a, b i32; min_d2 f64 (the minimum SQUARED distance; sqrt of it is cKDTree's value); pairs i64
+ *   (point pairs within the threshold). Each array holds `capacity` rows: at most that many are
+ *   written, *count is the number found, and a caller who gets count > capacity calls again.
+ * flags: PYQSM_ADJ_SAME_CLOUD  source and target are one cloud (tgt, tgt_label, m, n_tgt_labels are
+ *          ignored): only rows with a < b, every unordered point pair counted once, pairs of equal
+ *          label skipped;
+ *        PYQSM_ADJ_WITNESS     also src_idx, tgt_idx i64 [capacity]: the closest point pair, on ties
+ *          the smallest source index, then the smallest target index (both NULL otherwise);
+ *        PYQSM_ADJ_NO_CACHE    every point pair goes to the table with atomics of its own (same
+ *          result; for measuring what the per-lane accumulation saves).
+ * stats i64 [2] or NULL: distance tests evaluated, pairs of table atomics issued.
+ * Nothing labelled on either side: *count = 0 and no device is touched. Non-finite coordinates,
+ * threshold <= 0 or not finite, a label >= its bound: PYQSM_EINVAL. n_src_labels * n_tgt_labels
+ * above 2^26: PYQSM_ERANGE (split the sources by label range; rows stay sorted).
+ */
+#define PYQSM_ADJ_SAME_CLOUD 1
+#define PYQSM_ADJ_WITNESS 2
+#define PYQSM_ADJ_NO_CACHE 4
+int pyqsm_cluster_adjacency(const double* src, const int32_t* src_label, int64_t n, int32_t n_src_labels,
+                            const double* tgt, const int32_t* tgt_label, int64_t m, int32_t n_tgt_labels,
+                            double threshold, int32_t flags, int64_t capacity, int32_t* a, int32_t* b,
+                            double* min_d2, int64_t* pairs, int64_t* src_idx, int64_t* tgt_idx, int64_t* count,
+                            int64_t* stats, int32_t device);
+
 /* ---- farthest-point down-sampling ---------------------------------------- */
 /*
  * Stands in for open3d PointCloud.farthest_point_down_sample(num_samples) as

@@ -91,6 +91,7 @@ HOT_FUNCTIONS = {
                         "project_to_image", "raycast_to_pcd", "mri"),
     "utils.lib_integration": ("find_neighbors_in_ball", "get_neighbors_in_tree"),
     "tree_isolation": ("extend_seed_clusters",),
+    "cluster_joining": ("determine_adjacency", "create_kdtrees"),
     "qsm_generation": ("fit_cyl_to_cluster",),
     "exploration": ("compute_features", "smooth_feature", "random_forest_classification"),
     "utils.algo": ("smooth_feature",),

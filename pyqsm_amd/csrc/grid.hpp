@@ -317,6 +317,16 @@ int bin_octants_host(Ctx* c, const double* xyz, int64_t n, double min_cell, int6
 // by block sums and a deterministic scatter (no atomics, no second pass over xyz).
 int coarsen_grid(Ctx* c, const DevGrid& fine, int64_t n, int factor, DevGrid* coarse);
 
+// ---- what the fixed-radius kernels share (radius.hip, adjacency.hip) --------------------------
+// The grid a fixed-radius query walks: `d_src` binned into cells of edge `radius` (a hair more, so
+// that an inclusive bound stays inside the 27 cells), over the cloud without its sparse tails
+// (cloud_bbox -> robust_box -> build_grid); fp32 records when every coordinate allows. Points the
+// box gave up sit in its outermost cells, and queries find them through clamped_cell.
+int radius_grid(Ctx* c, const double* d_src, int64_t n, double radius, DevGrid* g);
+// *perm = the m query points (f64 [m,3], device) in the order of the grid's cells, or nullptr for
+// fewer than 1024 queries (or PYQSM_RADIUS_SORT=0): serve them in the caller's order.
+int query_order(Ctx* c, const double* d_qry, int64_t m, const GridParams& rg, int64_t ncell, int32_t** perm);
+
 // Number of occupied cells (reads back one int; synchronises).
 int count_occupied(Ctx* c, const DevGrid& g, int64_t* occupied);
 

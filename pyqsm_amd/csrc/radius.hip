@@ -42,7 +42,7 @@ __device__ __forceinline__ int walk(const GridParams& g, const int32_t* __restri
                                     int32_t* __restrict__ lab_out = nullptr, int lab = 0,
                                     double* below = nullptr, double* above = nullptr) {
   // The query's cell, clamped into the grid the way the sources were binned (grid.hpp: clamped_cell):
-  // the grid may cover less than the cloud (source_grid below), and a clamp moves no two points
+  // the grid may cover less than the cloud (grid.hpp: radius_grid), and a clamp moves no two points
   // further apart, so whatever is within the radius of a query outside still sits in the 27 cells
   // around its clamped cell; the distance test is on the true coordinates.
   int cx, cy, cz;
@@ -148,38 +148,6 @@ __global__ __launch_bounds__(256) void k_radius_mark(int m, const double* __rest
   (void)walk<2>(g, start, order, co, x, y, z, r2, tau, budget, mark, lo_, lab);
 }
 
-
-// The queries in the order of the source grid's cells (round 3): a lane per query walks ~850 candidates of
-// 27 cells, and 64 unrelated queries per wave are 64 unrelated walks — every load a gather of 64 lines.
-// In cell order the lanes of a wave walk the same few runs and their loads fall on shared lines
-// (100 k queries against 1 M sources: 4.8 -> 4.0 ms). Marks, labels (atomicMin) and the per-query
-// counts do not depend on the order in which the queries are served.
-__global__ __launch_bounds__(256) void k_query_keys(int m, const double* __restrict__ qry, GridParams g,
-                                                    uint32_t* __restrict__ key, int32_t* __restrict__ ident) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= m) return;
-  int cx, cy, cz;
-  clamped_cell(g, qry[3 * i], qry[3 * i + 1], qry[3 * i + 2], &cx, &cy, &cz);
-  key[i] = uint32_t((cz * g.ny + cy) * g.nx + cx);
-  ident[i] = i;
-}
-
-static int query_order(Ctx* c, const double* d_qry, int64_t m, const GridParams& rg, int64_t ncell, int32_t** perm) {
-  *perm = nullptr;
-  const char* e = getenv("PYQSM_RADIUS_SORT");  // "0": serve the queries in the caller's order
-  if (m < 1024 || (e && e[0] == '0')) return 0;
-  uint32_t* key;
-  int32_t* ident;
-  PQ_TRY(c->arena.get(size_t(m), &key));
-  PQ_TRY(c->arena.get(size_t(m), &ident));
-  hipLaunchKernelGGL(k_query_keys, dim3(ceil_div(m, 256)), dim3(256), 0, c->stream, int(m), d_qry, rg, key, ident);
-  PQ_HIP(hipGetLastError());
-  int bits = 1;
-  while (bits < 32 && (int64_t(1) << bits) < ncell) ++bits;
-  PQ_TRY(stable_sort_pairs_u32(c, &key, &ident, m, bits));
-  *perm = ident;
-  return 0;
-}
 
 // ---- k nearest within a bound, as sorted padded tables (cKDTree.query semantics) --------
 // One wave per query. Count the source points inside the bound (64 candidates per step);
@@ -294,18 +262,6 @@ __global__ __launch_bounds__(128) void k_radius_knn(int m, const double* __restr
   }
 }
 
-// The grid of the source points: cells of the radius, over the cloud without its sparse tails (a few
-// stray returns far outside would otherwise inflate the box until the dense grid cannot have cells
-// of the radius any more — every doubling of the edge is 8x the points per cell).
-static int source_grid(Ctx* c, const double* d_src, int64_t n, double radius, DevGrid* g) {
-  double box[6];
-  bool all_f32 = false;  // every source coordinate fp32-representable: 16-byte fp32 records (grid.hpp: on_coords)
-  PQ_TRY(cloud_bbox(c, d_src, n, box, box + 3, &all_f32));
-  int64_t outside = 0;
-  PQ_TRY(robust_box(c, d_src, n, int(std::min<int64_t>(8192, std::max<int64_t>(256, n / 256))), box, &outside));
-  return build_grid(c, d_src, n, radius * (1.0 + 1.0 / 1048576.0), int64_t(1) << 28, g, box, all_f32);
-}
-
 }  // namespace pyqsm
 
 using namespace pyqsm;
@@ -376,7 +332,7 @@ int pyqsm_radius_mark(const double* src, int64_t n, const double* qry, int64_t m
   PQ_HIP(hipMemcpyAsync(d_qry, qry, size_t(m) * 24, hipMemcpyHostToDevice, c->stream));
   PQ_HIP(hipMemsetAsync(d_mark, 0, size_t(n), c->stream));
   DevGrid g;
-  PQ_TRY(source_grid(c, d_src, n, radius, &g));
+  PQ_TRY(radius_grid(c, d_src, n, radius, &g));
   const GridParams rg = grid_params(g);
   {
     ProfScope ps(c, "radius_mark");
@@ -426,7 +382,7 @@ int pyqsm_radius_knn(const double* src, int64_t n, const double* qry, int64_t m,
   PQ_HIP(hipMemcpyAsync(d_src, src, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
   PQ_HIP(hipMemcpyAsync(d_qry, qry, size_t(m) * 24, hipMemcpyHostToDevice, c->stream));
   DevGrid g;
-  PQ_TRY(source_grid(c, d_src, n, radius, &g));
+  PQ_TRY(radius_grid(c, d_src, n, radius, &g));
   const GridParams rg = grid_params(g);
   {
     ProfScope ps(c, "radius_knn");
@@ -476,7 +432,7 @@ int pyqsm_radius_label(const double* src, int64_t n, const double* qry, int64_t 
   PQ_HIP(hipMemcpyAsync(d_qlab, qry_label, size_t(m) * 4, hipMemcpyHostToDevice, c->stream));
   PQ_HIP(hipMemsetAsync(d_lab, 0x7F, size_t(n) * 4, c->stream));  // 0x7F7F7F7F > any label
   DevGrid g;
-  PQ_TRY(source_grid(c, d_src, n, radius, &g));
+  PQ_TRY(radius_grid(c, d_src, n, radius, &g));
   const GridParams rg = grid_params(g);
   {
     ProfScope ps(c, "radius_label");

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import weakref
+from typing import NamedTuple
 
 import numpy as np
 
@@ -426,6 +427,121 @@ def radius_knn(src, queries, radius: float, k: int = 500, device: int = 0):
     check(_lib.load().pyqsm_radius_knn(_p(s), s.shape[0], _p(q), m, float(radius), int(k), _p(idx),
                                        _p(dist), int(device)))
     return dist, idx
+
+
+# ---------------------------------------------------------------- cluster adjacency
+
+class ClusterAdjacency(NamedTuple):
+    """Rows of the cluster-to-cluster graph, ascending by (a, b) in the caller's label values."""
+    a: np.ndarray          # int64 [r] source cluster label
+    b: np.ndarray          # int64 [r] target cluster label
+    dist: np.ndarray       # float64 [r] minimum distance
+    n_pairs: np.ndarray    # int64 [r] point pairs within the threshold
+    src_idx: np.ndarray | None = None   # int64 [r] closest point pair (return_pairs=True)
+    tgt_idx: np.ndarray | None = None
+
+
+ADJ_SAME_CLOUD, ADJ_WITNESS, ADJ_NO_CACHE = 1, 2, 4
+
+
+def _dense_labels(labels, n: int, what: str):
+    """(int32 [n] dense labels with -1 for ignored points, int64 sorted label values)."""
+    lab = np.asarray(labels).reshape(-1)
+    if lab.shape[0] != n:
+        raise ValueError(f"one label per {what} point: {lab.shape[0]} labels for {n} points")
+    if lab.size and not np.issubdtype(lab.dtype, np.integer):
+        raise ValueError(f"{what} labels must be integers")
+    lab = lab.astype(np.int64)
+    keep = lab >= 0
+    values, inv = np.unique(lab[keep], return_inverse=True)
+    dense = np.full(n, -1, dtype=np.int32)
+    dense[keep] = inv.astype(np.int32)
+    return dense, values
+
+
+def _adjacency_call(s, sl, S, t, tl, T, threshold, flags, stats, device):
+    """One C-ABI call, repeated with a larger capacity when the first guess was too small."""
+    lib = _lib.load()
+    cap = int(min(S * T, max(4096, 16 * (S + T)))) if S and T else 0
+    while True:
+        n_out = max(cap, 1)
+        a, b = np.empty(n_out, np.int32), np.empty(n_out, np.int32)
+        d2, cnt = np.empty(n_out, np.float64), np.empty(n_out, np.int64)
+        wit = bool(flags & ADJ_WITNESS)
+        si = np.empty(n_out, np.int64) if wit else None
+        ti = np.empty(n_out, np.int64) if wit else None
+        st = np.zeros(2, np.int64) if stats is not None else None
+        found = i64(0)
+        check(lib.pyqsm_cluster_adjacency(_p(s), _p(sl), s.shape[0], int(S), _p(t), _p(tl),
+                                          0 if t is None else t.shape[0], int(T), float(threshold), int(flags),
+                                          cap, _p(a), _p(b), _p(d2), _p(cnt), _p(si), _p(ti), ctypes.byref(found),
+                                          _p(st), int(device)))
+        r = int(found.value)
+        if r <= cap:
+            break
+        cap = r
+    if stats is not None:
+        stats["distance_tests"] = stats.get("distance_tests", 0) + int(st[0])
+        stats["atomic_pairs"] = stats.get("atomic_pairs", 0) + int(st[1])
+    return (a[:r].astype(np.int64), b[:r].astype(np.int64), d2[:r], cnt[:r],
+            si[:r] if wit else None, ti[:r] if wit else None)
+
+
+def cluster_adjacency(points, labels, threshold: float, targets=None, target_labels=None,
+                      return_pairs: bool = False, max_table: int = 1 << 26, device: int = 0, *,
+                      cache: bool = True, stats: dict | None = None) -> ClusterAdjacency:
+    """The sparse cluster-to-cluster distance graph of labelled points: for every (source cluster a,
+    target cluster b) with at least one point pair within ``threshold`` (inclusive, fp64), the
+    minimum distance and the number of such point pairs — what pyQSM's ``determine_adjacency``
+    gets from one ``sparse_distance_matrix`` per cluster pair. Labels are any integers; negative
+    ones mean "ignore this point". ``targets=None``: one labelled cloud against itself, rows with
+    a < b only, every unordered point pair counted once. ``return_pairs``: also the indices of the
+    closest point pair (ties: smallest source index, then smallest target index). Rows ascend by
+    (a, b). One call handles ``max_table`` cluster pairs (at most 2^26); beyond that the sources
+    are served in label ranges. ``cache=False`` and ``stats`` (a dict that receives
+    ``distance_tests`` and ``atomic_pairs``) are for measurements and change no result."""
+    s = _points(points)
+    sl, s_vals = _dense_labels(labels, s.shape[0], "source")
+    same = targets is None
+    if same:
+        if target_labels is not None:
+            raise ValueError("target_labels without targets")
+        t, tl, t_vals = s, sl, s_vals
+    else:
+        t = _points(targets)
+        tl, t_vals = _dense_labels(target_labels, t.shape[0], "target")
+    S, T = len(s_vals), len(t_vals)
+    max_table = int(min(max(int(max_table), 1), 1 << 26))
+    flags = (ADJ_WITNESS if return_pairs else 0) | (0 if cache else ADJ_NO_CACHE)
+    if S * T <= max_table:
+        if same:
+            parts = [_adjacency_call(s, sl, S, None, None, S, threshold, flags | ADJ_SAME_CLOUD, stats, device)]
+        else:
+            parts = [_adjacency_call(s, sl, S, t, tl, T, threshold, flags, stats, device)]
+    else:
+        if T > max_table:
+            raise ValueError(f"{T} target clusters exceed max_table = {max_table}")
+        step = max_table // T
+        order = np.argsort(sl, kind="stable")            # source points by dense label
+        bounds = np.searchsorted(sl[order], np.arange(0, S + step, step))
+        parts = []
+        for k, lo in enumerate(range(0, S, step)):
+            sel = order[bounds[k]:bounds[k + 1]]
+            sel.sort()                                   # ascending indices: the witness tie-break holds
+            hi = min(lo + step, S)
+            a, b, d2, cnt, si, ti = _adjacency_call(np.ascontiguousarray(s[sel]), sl[sel] - np.int32(lo), hi - lo,
+                                                    t, tl, T, threshold, flags, stats, device)
+            a = a + lo
+            if si is not None:
+                si = sel[si]
+            if same:                                     # the tile met the whole cloud: keep a < b
+                keep = a < b
+                a, b, d2, cnt = a[keep], b[keep], d2[keep], cnt[keep]
+                if si is not None:
+                    si, ti = si[keep], ti[keep]
+            parts.append((a, b, d2, cnt, si, ti))
+    cat = [np.concatenate([p[k] for p in parts]) if parts[0][k] is not None else None for k in range(6)]
+    return ClusterAdjacency(s_vals[cat[0]], t_vals[cat[1]], np.sqrt(cat[2]), cat[3], cat[4], cat[5])
 
 
 def fps(points, num_samples: int, start_index: int = 0, device: int = 0) -> np.ndarray:
