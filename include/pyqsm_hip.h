@@ -315,6 +315,22 @@ int pyqsm_radius_mark(const double* src, int64_t n, const double* qry, int64_t m
 int pyqsm_radius_knn(const double* src, int64_t n, const double* qry, int64_t m, double radius,
                      int32_t k, int64_t* idx, double* dist, int32_t device);
 /*
+ * pyqsm_radius_knn's neighbours reduced in the kernel: what pyQSM's expand_features_to_orig and
+ * get_smoothed_features (canopy_metrics.py:236-252, 564-570) compute on the host from the padded
+ * tables. The neighbours of query j are exactly the entries pyqsm_radius_knn(src, qry, radius, k)
+ * returns for it: the same strict bound, d2 expression and (distance, index) order. values f64
+ * [n, F] reduced over them into out f64 [m, F]: reducer 0 mean (sum from 0.0, one add at a time in
+ * neighbour order, divided by the count: pyqsm_smooth_values' rule), 2 min, 3 max (NaN propagates
+ * as in NumPy), 4 first (the nearest neighbour's row); anything else: PYQSM_EINVAL. A query with
+ * no neighbour gets values[empty_row] (pyQSM falls back to row 0), or NaN when empty_row is -1.
+ * counts i32 [m] (may be NULL): neighbours found, 0 to k. k in [1, 2048] and F in [1, 64]
+ * (PYQSM_ERANGE); n up to 2^31 - 1; any m, served in chunks. No float atomics: every run gives
+ * the same bits.
+ */
+int pyqsm_radius_reduce(const double* src, int64_t n, const double* qry, int64_t m, double radius, int32_t k,
+                        const double* values, int32_t F, int32_t reducer, int64_t empty_row, double* out,
+                        int32_t* counts, int32_t device);
+/*
  * pyqsm_radius_mark with a label per query point: label[j] = the smallest label among
  * the query points that select source point j (-1: none). One call replaces one cycle
  * of the region growing of pyQSM/tree_isolation.py:207-256 (extend_seed_clusters), where
@@ -686,6 +702,49 @@ int pyqsm_forest_info(const void* forest, int64_t info[8]);
 int pyqsm_forest_stage(void* forest, int32_t staged_nodes);
 int pyqsm_forest_predict(const void* forest, const float* X, int64_t n, double* proba, int32_t* label,
                          int32_t* leaves);
+
+/* ---- voxel-grid occupancy ------------------------------------------------------------------ */
+/*
+ * Open3D's VoxelGrid.create_from_point_cloud + check_if_included, the step with which pyQSM asks
+ * which points of a full-resolution tile belong to a voxelised tree (pyQSM/geometry/
+ * reconstruction.py:266-355, tree_isolation.py:465-516, canopy_metrics.py:635-639). Recollected
+ * from Open3D (VoxelGrid::CreateFromPointCloud / GetVoxel / CheckIfIncluded), parity unpinned;
+ * tests/voxelgrid_restatement.py defines the contract; DESIGN.md section 14.
+ *
+ * pyqsm_voxel_grid_create: origin[a] = min_bound[a] - voxel_size * 0.5; a point's voxel index is
+ *   floor((p[a] - origin[a]) / voxel_size) with a true IEEE fp64 division: the arithmetic of
+ *   pyqsm_voxel_down_sample, so a cloud's grid and its down-sampling have the same voxels in the
+ *   same row order. One voxel per occupied index, rows ordered by the smallest input index they
+ *   hold (Open3D's order is an unordered_map's). With colors f64 [n,3] the voxel colour is the mean
+ *   of its members in ascending index order, one add at a time from 0.0, divided by the count.
+ *   dims[a] = the largest index + 1. voxel_size not positive and finite, or a non-finite
+ *   coordinate: PYQSM_EINVAL; a dimension above 2^31 - 1 or more than 2^62 cells: PYQSM_ERANGE;
+ *   all of these before any device is touched. n == 0: a grid without voxels, origin
+ *   -voxel_size / 2, dims 0, in which nothing is included. The grid stays on `device` until
+ *   pyqsm_voxel_grid_free (NULL: no-op); any number of grids may be alive.
+ * pyqsm_voxel_grid_info: every out-parameter may be NULL.
+ * pyqsm_voxel_grid_voxels: grid_index i32 [M,3] and colors f64 [M,3] in row order (each may be
+ *   NULL; colors of a grid created without: PYQSM_EINVAL).
+ * pyqsm_voxel_grid_query: per query f[a] = floor((q[a] - origin[a]) / voxel_size); included iff
+ *   0 <= f[a] < dims[a] on every axis and that voxel exists. A NaN or infinite coordinate is never
+ *   included. (Open3D casts f to int, which wraps far outside the box: out of contract here.)
+ *   included u8 [m]; row i32 [m]: the voxel's row, -1 if none; idx i64 [capacity m]: the ascending
+ *   query indices that are included, or with PYQSM_VOX_INVERT those that are not; *count: their
+ *   number. Every output may be NULL. The host form streams qry through the device in chunks
+ *   (any m, 64-bit offsets; PYQSM_VOX_CHUNK in the environment lowers the chunk's size); the _dev
+ *   form takes device arrays and writes device arrays (*count stays a host value).
+ */
+#define PYQSM_VOX_INVERT 1
+int pyqsm_voxel_grid_create(const double* xyz, int64_t n, const double* colors, double voxel_size,
+                            int32_t device, void** grid);
+int pyqsm_voxel_grid_free(void* grid);
+int pyqsm_voxel_grid_info(const void* grid, double origin[3], double* voxel_size, int64_t dims[3],
+                          int64_t* n_voxels, int64_t* device_bytes);
+int pyqsm_voxel_grid_voxels(const void* grid, int32_t* grid_index, double* colors);
+int pyqsm_voxel_grid_query(const void* grid, const double* qry, int64_t m, int32_t flags,
+                           uint8_t* included, int32_t* row, int64_t* idx, int64_t* count);
+int pyqsm_voxel_grid_query_dev(const void* grid, const double* qry_dev, int64_t m, int32_t flags,
+                               uint8_t* included_dev, int32_t* row_dev, int64_t* idx_dev, int64_t* count);
 
 #ifdef __cplusplus
 }

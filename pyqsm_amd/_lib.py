@@ -104,6 +104,14 @@ SIGNATURES = {
     "pyqsm_forest_info": (ctypes.c_int, [vp, vp]),
     "pyqsm_forest_stage": (ctypes.c_int, [vp, i32]),
     "pyqsm_forest_predict": (ctypes.c_int, [vp, vp, i64, vp, vp, vp]),
+    "pyqsm_radius_reduce": (ctypes.c_int, [vp, i64, vp, i64, dbl, i32, vp, i32, i32, i64, vp, vp, i32]),
+    "pyqsm_voxel_grid_create": (ctypes.c_int, [vp, i64, vp, dbl, i32, ctypes.POINTER(vp)]),
+    "pyqsm_voxel_grid_free": (ctypes.c_int, [vp]),
+    "pyqsm_voxel_grid_info": (ctypes.c_int, [vp, vp, ctypes.POINTER(dbl), vp, ctypes.POINTER(i64),
+                                             ctypes.POINTER(i64)]),
+    "pyqsm_voxel_grid_voxels": (ctypes.c_int, [vp, vp, vp]),
+    "pyqsm_voxel_grid_query": (ctypes.c_int, [vp, vp, i64, i32, vp, vp, vp, ctypes.POINTER(i64)]),
+    "pyqsm_voxel_grid_query_dev": (ctypes.c_int, [vp, vp, i64, i32, vp, vp, vp, ctypes.POINTER(i64)]),
 }
 
 _lib = None

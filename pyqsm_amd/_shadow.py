@@ -86,7 +86,7 @@ HOT_FUNCTIONS = {
     "geometry.point_cloud_processing": ("cluster_plus", "cluster_and_get_largest"),
     "geometry.skeletonize": ("extract_skeleton", "least_squares_sparse", "extract_topology",
                              "extract_skeletal_graph", "simplify_graph", "skeleton_to_QSM"),
-    "geometry.reconstruction": ("get_neighbors_kdtree",),
+    "geometry.reconstruction": ("get_neighbors_kdtree", "overlap_voxel_grid", "get_nbrs_voxel_grid"),
     "viz.ray_casting": ("cast_rays", "sparse_cast_w_intersections", "get_points_inside_mesh",
                         "project_to_image", "raycast_to_pcd", "mri"),
     "utils.lib_integration": ("find_neighbors_in_ball", "get_neighbors_in_tree"),

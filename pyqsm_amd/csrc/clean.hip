@@ -14,6 +14,7 @@
 #include "common.hpp"
 #include "grid.hpp"
 #include "sparse.hpp"
+#include "voxel.hpp"
 
 namespace pyqsm {
 
@@ -303,13 +304,7 @@ __global__ __launch_bounds__(256) void k_stat_mask(const double* __restrict__ av
 }
 
 // ---- device-resident steps -------------------------------------------------------------------
-struct VoxelDev {
-  int64_t m = 0;                    // voxels (host)
-  int32_t *order, *seg, *offs, *row_of;  // key order, voxel of each sorted position, voxel bounds, rows
-  double *xyz = nullptr, *rgb = nullptr;  // [m,3] means, output-row order
-};
-
-static int voxel_keys_and_sort(Ctx* c, const double* xyz, int64_t n, double size, VoxelDev* v) {
+int voxel_keys_and_sort(Ctx* c, const double* xyz, int64_t n, double size, VoxelDev* v) {
   const int N = int(n);
   double mn[3], mx[3];
   {
@@ -334,6 +329,10 @@ static int voxel_keys_and_sort(Ctx* c, const double* xyz, int64_t n, double size
   g.size = size;
   g.nx = dims[0];
   g.ny = dims[1];
+  for (int a = 0; a < 3; ++a) {
+    v->vmin[a] = vmin[a];
+    v->dims[a] = dims[a];
+  }
   int bits = 0;
   while ((unsigned __int128)1 << bits < cells) ++bits;
   uint64_t* key;
@@ -360,6 +359,7 @@ static int voxel_keys_and_sort(Ctx* c, const double* xyz, int64_t n, double size
     }
   }
   v->order = val;
+  v->key = key;
   int32_t *head, *first;
   PQ_TRY(c->arena.get(size_t(n) + 1, &head));
   PQ_TRY(c->arena.get(size_t(n) + 1, &first));
@@ -383,7 +383,7 @@ static int voxel_keys_and_sort(Ctx* c, const double* xyz, int64_t n, double size
   return 0;
 }
 
-static int voxel_means(Ctx* c, const double* xyz, const double* rgb, int64_t n, VoxelDev* v) {
+int voxel_means(Ctx* c, const double* xyz, const double* rgb, int64_t n, VoxelDev* v) {
   ProfScope ps(c, "clean_means");
   const int M = int(v->m);
   PQ_TRY(c->arena.get(size_t(M) * 3, &v->xyz));

@@ -18,6 +18,7 @@
 // Squared distances are fp64, ((dx*dx)+dy*dy)+dz*dz, the accumulation of cKDTree.
 #include "grid.hpp"
 
+#include <algorithm>
 #include <cmath>
 
 namespace pyqsm {
@@ -156,19 +157,13 @@ __global__ __launch_bounds__(256) void k_radius_mark(int m, const double* __rest
 // LDS, bitonic-sort them by (d2, index) and write k entries, padded with (inf, n).
 static constexpr int kKnnCap = 2048;  // largest k (LDS: 24 KB per wave)
 
+// The front both kernels share: the neighbours of (x, y, z) — at most k, d2 < r2 — into sd / si (this
+// wave's LDS, kKnnCap entries each), ascending by (d2, index). Returns how many. Whole wave.
 template <class CO>
-__global__ __launch_bounds__(128) void k_radius_knn(int m, const double* __restrict__ qry, GridParams g,
-                                                    const int32_t* __restrict__ start,
-                                                    const int32_t* __restrict__ order,
-                                                    CO co, double r2, int k,
-                                                    int n_src, int64_t* __restrict__ out_idx,
-                                                    double* __restrict__ out_dist) {
-  __shared__ double sd[2][kKnnCap];
-  __shared__ int si[2][kKnnCap];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int i = blockIdx.x * 2 + w;
-  if (i >= m) return;  // whole wave
-  const double x = qry[3 * i], y = qry[3 * i + 1], z = qry[3 * i + 2];
+__device__ __forceinline__ int radius_collect_sorted(const GridParams& g, const int32_t* __restrict__ start,
+                                                     const int32_t* __restrict__ order, CO co, double x, double y,
+                                                     double z, double r2, int k, double* sd, int* si) {
+  const int lane = threadIdx.x & 63;
   StencilRuns rr;
   point_stencil_runs(g, start, x, y, z, &rr);
   // count of candidates with d2 < r2 and d2 <= tau
@@ -220,8 +215,8 @@ __global__ __launch_bounds__(128) void k_radius_knn(int m, const double* __restr
         const unsigned long long kb = __ballot(take);
         if (take) {
           const int slot = have + __popcll(kb & ((1ull << lane) - 1ull));
-          sd[w][slot] = d;
-          si[w][slot] = order[q];
+          sd[slot] = d;
+          si[slot] = order[q];
         }
         have += __popcll(kb);
         ties += __popcll(tb);
@@ -230,8 +225,8 @@ __global__ __launch_bounds__(128) void k_radius_knn(int m, const double* __restr
   int np2 = 1;
   while (np2 < have) np2 <<= 1;
   for (int t = have + lane; t < np2; t += 64) {
-    sd[w][t] = __builtin_inf();
-    si[w][t] = 0x7FFFFFFF;
+    sd[t] = __builtin_inf();
+    si[t] = 0x7FFFFFFF;
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -240,26 +235,108 @@ __global__ __launch_bounds__(128) void k_radius_knn(int m, const double* __restr
       for (int t = lane; t < np2; t += 64) {
         const int u = t ^ j;
         if (u > t) {
-          const double da = sd[w][t], db = sd[w][u];
-          const int ia = si[w][t], ib = si[w][u];
+          const double da = sd[t], db = sd[u];
+          const int ia = si[t], ib = si[u];
           const bool a_gt_b = da > db || (da == db && ia > ib);
           const bool up = (t & k2) == 0;
           if (a_gt_b == up) {
-            sd[w][t] = db;
-            si[w][t] = ib;
-            sd[w][u] = da;
-            si[w][u] = ia;
+            sd[t] = db;
+            si[t] = ib;
+            sd[u] = da;
+            si[u] = ia;
           }
         }
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       __builtin_amdgcn_wave_barrier();
     }
+  return have;
+}
+
+template <class CO>
+__global__ __launch_bounds__(128) void k_radius_knn(int m, const double* __restrict__ qry, GridParams g,
+                                                    const int32_t* __restrict__ start,
+                                                    const int32_t* __restrict__ order,
+                                                    CO co, double r2, int k,
+                                                    int n_src, int64_t* __restrict__ out_idx,
+                                                    double* __restrict__ out_dist) {
+  __shared__ double sd[2][kKnnCap];
+  __shared__ int si[2][kKnnCap];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int i = blockIdx.x * 2 + w;
+  if (i >= m) return;  // whole wave
+  const double x = qry[3 * i], y = qry[3 * i + 1], z = qry[3 * i + 2];
+  const int have = radius_collect_sorted(g, start, order, co, x, y, z, r2, k, sd[w], si[w]);
   for (int t = lane; t < k; t += 64) {
     const bool real = t < have;
     out_idx[size_t(i) * k + t] = real ? int64_t(si[w][t]) : int64_t(n_src);
     out_dist[size_t(i) * k + t] = real ? sqrt(sd[w][t]) : __builtin_inf();
   }
+}
+
+// ---- the same neighbours, reduced in the kernel -------------------------------------------
+// pyQSM's expand_features_to_orig / get_smoothed_features (canopy_metrics.py:236-252, 564-570) take
+// the padded tables above to the host and reduce values[nbrs] there: 6 KB per query at k = 500.
+// Here the sorted list stays in LDS. The distances are no longer needed after the sort, so their
+// 16 KB hold the neighbours' value rows, gathered by the whole wave a tile of kKnnCap / F
+// neighbours at a time; lane f < F then folds column f in neighbour order, one operation at a time
+// (the mean's sum from 0.0, as pyqsm_smooth_values): no atomics, the same bits on every run.
+// reducer: 0 mean, 2 min, 3 max (NaN propagates), 4 first.
+static constexpr int kReduceMaxF = 64;
+
+template <class CO>
+__global__ __launch_bounds__(128) void k_radius_reduce(int m, const double* __restrict__ qry, GridParams g,
+                                                       const int32_t* __restrict__ start,
+                                                       const int32_t* __restrict__ order, CO co, double r2, int k,
+                                                       const double* __restrict__ values, int F, int reducer,
+                                                       int64_t empty_row, double* __restrict__ out,
+                                                       int32_t* __restrict__ counts) {
+  __shared__ double sd[2][kKnnCap];
+  __shared__ int si[2][kKnnCap];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int i = blockIdx.x * 2 + w;
+  if (i >= m) return;  // whole wave
+  const double x = qry[3 * i], y = qry[3 * i + 1], z = qry[3 * i + 2];
+  const int have = radius_collect_sorted(g, start, order, co, x, y, z, r2, k, sd[w], si[w]);
+  if (counts && lane == 0) counts[i] = have;
+  double* o = out + size_t(i) * F;
+  if (have == 0) {
+    if (lane < F) o[lane] = empty_row >= 0 ? values[size_t(empty_row) * F + lane] : __builtin_nan("");
+    return;
+  }
+  if (reducer == 4) {
+    if (lane < F) o[lane] = values[size_t(si[w][0]) * F + lane];
+    return;
+  }
+  double* stage = sd[w];
+  const int tile = kKnnCap / F;  // neighbours whose rows fit the stage
+  double acc = 0.0;
+  bool nan = false;
+  for (int t0 = 0; t0 < have; t0 += tile) {
+    const int cnt = min(tile, have - t0);
+    for (int e = lane; e < cnt * F; e += 64) {
+      const int nb = e / F;
+      stage[e] = values[size_t(si[w][t0 + nb]) * F + (e - nb * F)];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (lane < F) {
+      if (reducer == 0) {
+        for (int q = 0; q < cnt; ++q) acc = acc + stage[q * F + lane];
+      } else {
+        for (int q = 0; q < cnt; ++q) {
+          const double v = stage[q * F + lane];
+          nan = nan || v != v;
+          if ((t0 == 0 && q == 0) || (reducer == 2 ? v < acc : v > acc)) acc = v;
+        }
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
+  if (lane < F) o[lane] = reducer == 0 ? acc / double(have) : (nan ? __builtin_nan("") : acc);
 }
 
 }  // namespace pyqsm
@@ -394,6 +471,65 @@ int pyqsm_radius_knn(const double* src, int64_t n, const double* qry, int64_t m,
   }
   PQ_HIP(hipMemcpyAsync(idx, d_idx, size_t(m) * k * 8, hipMemcpyDeviceToHost, c->stream));
   PQ_HIP(hipMemcpyAsync(dist, d_dist, size_t(m) * k * 8, hipMemcpyDeviceToHost, c->stream));
+  PQ_HIP(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int pyqsm_radius_reduce(const double* src, int64_t n, const double* qry, int64_t m, double radius, int32_t k,
+                        const double* values, int32_t F, int32_t reducer, int64_t empty_row, double* out,
+                        int32_t* counts, int32_t device) {
+  PQ_API_RANGE("pyqsm_radius_reduce");
+  if (n < 0 || m < 0) return fail(PYQSM_EINVAL, "negative size");
+  if (k <= 0 || k > kKnnCap) return fail(PYQSM_ERANGE, "k must be in [1, %d]", kKnnCap);
+  if (F < 1 || F > kReduceMaxF) return fail(PYQSM_ERANGE, "F must be in [1, %d]", kReduceMaxF);
+  if (reducer != 0 && reducer != 2 && reducer != 3 && reducer != 4)
+    return fail(PYQSM_EINVAL, "reducer must be 0 (mean), 2 (min), 3 (max) or 4 (first), got %d", int(reducer));
+  if (!(radius > 0) || !std::isfinite(radius)) return fail(PYQSM_EINVAL, "radius must be positive");
+  if (empty_row < -1 || empty_row >= n) return fail(PYQSM_EINVAL, "empty_row must be -1 or a row of values");
+  if (m > 0 && (!qry || !out)) return fail(PYQSM_EINVAL, "pyqsm_radius_reduce: NULL pointer");
+  if (n > 0 && (!src || !values)) return fail(PYQSM_EINVAL, "pyqsm_radius_reduce: NULL pointer");
+  if (n > 0x7FFFFF00LL) return fail(PYQSM_ERANGE, "more than 2^31 source points per call");
+  if (m == 0) return 0;
+  if (n == 0) {  // nothing to find: every neighbourhood is empty (and empty_row is -1)
+    for (int64_t t = 0; t < m * F; ++t) out[t] = std::nan("");
+    if (counts) memset(counts, 0, size_t(m) * 4);
+    return 0;
+  }
+  Ctx* c = ctx_for(device);
+  if (!c) return PYQSM_ENODEV;
+  std::lock_guard<std::mutex> lk(c->mu);
+  c->arena.reset();
+  double *d_src, *d_val;
+  PQ_TRY(c->arena.get(size_t(n) * 3, &d_src));
+  PQ_TRY(c->arena.get(size_t(n) * F, &d_val));
+  PQ_HIP(hipMemcpyAsync(d_src, src, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+  PQ_HIP(hipMemcpyAsync(d_val, values, size_t(n) * F * 8, hipMemcpyHostToDevice, c->stream));
+  DevGrid g;
+  PQ_TRY(radius_grid(c, d_src, n, radius, &g));
+  const GridParams rg = grid_params(g);
+  // queries per pass: about 256 MB of arena for the queries and their results, as pyqsm_forest_predict
+  const size_t per_q = 24 + size_t(F) * 8 + 4;
+  const int64_t chunk = std::min<int64_t>(m, std::max<int64_t>(2, int64_t((size_t(256) << 20) / per_q)));
+  double *d_qry, *d_out;
+  int32_t* d_cnt = nullptr;
+  PQ_TRY(c->arena.get(size_t(chunk) * 3, &d_qry));
+  PQ_TRY(c->arena.get(size_t(chunk) * F, &d_out));
+  if (counts) PQ_TRY(c->arena.get(size_t(chunk), &d_cnt));
+  for (int64_t r0 = 0; r0 < m; r0 += chunk) {
+    const int64_t mc = std::min(chunk, m - r0);
+    PQ_HIP(hipMemcpyAsync(d_qry, qry + size_t(r0) * 3, size_t(mc) * 24, hipMemcpyHostToDevice, c->stream));
+    {
+      ProfScope ps(c, "radius_reduce");
+      on_coords(g, [&](auto co) {
+        hipLaunchKernelGGL(k_radius_reduce<decltype(co)>, dim3(ceil_div(mc, 2)), dim3(128), 0, c->stream, int(mc), d_qry,
+                           rg, g.start, g.order, co, radius * radius, k, static_cast<const double*>(d_val), F, reducer,
+                           empty_row, d_out, d_cnt);
+      });
+      PQ_HIP(hipGetLastError());
+    }
+    PQ_HIP(hipMemcpyAsync(out + size_t(r0) * F, d_out, size_t(mc) * F * 8, hipMemcpyDeviceToHost, c->stream));
+    if (counts) PQ_HIP(hipMemcpyAsync(counts + r0, d_cnt, size_t(mc) * 4, hipMemcpyDeviceToHost, c->stream));
+  }
   PQ_HIP(hipStreamSynchronize(c->stream));
   return 0;
 }

@@ -167,6 +167,60 @@ class PointCloud:
         return self.points.max(axis=0)
 
 
+class Voxel:
+    """Open3D's ``Voxel``: ``grid_index`` int32 [3] and ``color`` f64 [3]."""
+
+    def __init__(self, grid_index, color=None):
+        self.grid_index = np.asarray(grid_index, dtype=np.int32)
+        self.color = np.zeros(3) if color is None else np.asarray(color, dtype=np.float64)
+
+    def __repr__(self):
+        return f"Voxel with grid_index: ({', '.join(str(int(v)) for v in self.grid_index)})"
+
+
+class VoxelGrid:
+    """Open3D's ``VoxelGrid`` as pyQSM uses it, on the GPU (``hip.VoxelGrid``): the occupied voxels
+    of a cloud stay on the device and tiles are checked against them. Recollected from Open3D,
+    parity unpinned. The voxels are ordered by the smallest input index they hold (Open3D's order
+    comes from a hash map), and a query far outside the box is simply not included (Open3D's cast
+    to int wraps there)."""
+
+    def __init__(self, device_grid=None):
+        self._grid = device_grid
+
+    @staticmethod
+    def create_from_point_cloud(input, voxel_size, device: int = 0) -> "VoxelGrid":
+        col = getattr(input, "colors", None)
+        pts = as_points(input)
+        if col is not None and len(np.asarray(col)) != len(pts):
+            col = None
+        return VoxelGrid(_hip().VoxelGrid(pts, voxel_size, colors=col, device=device))
+
+    @property
+    def origin(self):
+        return self._grid.origin
+
+    @property
+    def voxel_size(self):
+        return self._grid.voxel_size
+
+    @property
+    def device_grid(self):
+        """The ``hip.VoxelGrid`` behind this one (rows, indices, inverted queries)."""
+        return self._grid
+
+    def check_if_included(self, queries) -> np.ndarray:
+        """bool [m] (Open3D returns a list of bool)."""
+        return self._grid.query(as_points(queries))
+
+    def get_voxels(self):
+        gi, col = self._grid.voxels()
+        return [Voxel(gi[r], None if col is None else col[r]) for r in range(len(gi))]
+
+    def __repr__(self):
+        return f"VoxelGrid with {self._grid.n_voxels} voxels."
+
+
 class TriangleMesh:
     """vertices f64/f32 [V,3], triangles int [T,3]."""
 

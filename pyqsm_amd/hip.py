@@ -1167,3 +1167,134 @@ class DeviceForest:
             self.free()
         except Exception:
             pass
+
+
+# ---------------------------------------------------------------- detail recovery
+
+VOX_INVERT = 1
+RADIUS_REDUCERS = {"mean": 0, "min": 2, "amin": 2, "max": 3, "amax": 3, "first": 4}
+RADIUS_REDUCE_MAX_K = 2048
+RADIUS_REDUCE_MAX_F = 64
+
+
+class VoxelGrid:
+    """The occupied voxels of a cloud resident in HBM (``pyqsm_voxel_grid_create``): created once,
+    queried by any number of tiles. ``origin`` = min bound - voxel_size / 2, ``dims`` = largest voxel
+    index + 1 per axis, rows ordered by the smallest input index each voxel holds. Context manager
+    like :class:`DeviceForest`."""
+
+    def __init__(self, points, voxel_size: float, colors=None, device: int = 0):
+        pts = _points(points)
+        v = _voxel_size(voxel_size)
+        col = None
+        if colors is not None:
+            col = np.ascontiguousarray(np.asarray(colors), dtype=np.float64)
+            if col.shape != pts.shape:
+                raise ValueError(f"colors must have the points' shape {pts.shape}, got {col.shape}")
+        self.device = int(device)
+        self.has_colors = col is not None
+        self._h = None
+        h = vp()
+        lib = _lib.load()
+        check(lib.pyqsm_voxel_grid_create(_p(pts), pts.shape[0], _p(col), v, self.device, ctypes.byref(h)))
+        self._h = h.value
+        origin, dims = np.zeros(3), np.zeros(3, dtype=np.int64)
+        size, m, nbytes = dbl(0), i64(0), i64(0)
+        check(lib.pyqsm_voxel_grid_info(self._h, _p(origin), ctypes.byref(size), _p(dims), ctypes.byref(m),
+                                        ctypes.byref(nbytes)))
+        self.origin, self.dims, self.voxel_size = origin, dims, float(size.value)
+        self.n_voxels, self.device_bytes = int(m.value), int(nbytes.value)
+
+    def _handle(self):
+        if not self._h:
+            raise ValueError("the voxel grid has been freed")
+        return self._h
+
+    def query(self, points, rows: bool = False, indices: bool = False, invert: bool = False):
+        """``pyqsm_voxel_grid_query``: ``included`` bool [m]; with ``rows`` also the voxel row of every
+        point (int32, -1: none); with ``indices`` also the ascending int64 indices of the included
+        points (``invert``: of those that are not). One value, or a tuple in that order."""
+        h = self._handle()
+        q = _points(points)
+        m = q.shape[0]
+        inc = np.zeros(m, dtype=np.uint8)
+        row = np.empty(m, dtype=np.int32) if rows else None
+        idx = np.empty(max(m, 1), dtype=np.int64) if indices else None
+        cnt = i64(0)
+        check(_lib.load().pyqsm_voxel_grid_query(h, _p(q), m, VOX_INVERT if invert else 0, _p(inc), _p(row), _p(idx),
+                                                 ctypes.byref(cnt)))
+        out = [inc.astype(bool)]
+        if rows:
+            out.append(row)
+        if indices:
+            out.append(idx[:cnt.value].copy())
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def query_dev(self, qry_ptr: int, m: int, included_ptr=None, row_ptr=None, idx_ptr=None,
+                  invert: bool = False) -> int:
+        """``pyqsm_voxel_grid_query_dev`` on device arrays (qry f64 [m,3]; included u8 [m], row i32
+        [m], idx i64 [capacity m], each may be None). Returns the number of listed queries."""
+        cnt = i64(0)
+        check(_lib.load().pyqsm_voxel_grid_query_dev(self._handle(), vp(qry_ptr), int(m), VOX_INVERT if invert else 0,
+                                                     vp(included_ptr), vp(row_ptr), vp(idx_ptr), ctypes.byref(cnt)))
+        return int(cnt.value)
+
+    def voxels(self):
+        """(grid_index int32 [M,3], colour means f64 [M,3] or None) in row order."""
+        h = self._handle()
+        gi = np.zeros((self.n_voxels, 3), dtype=np.int32)
+        col = np.zeros((self.n_voxels, 3), dtype=np.float64) if self.has_colors else None
+        check(_lib.load().pyqsm_voxel_grid_voxels(h, _p(gi), _p(col)))
+        return gi, col
+
+    def close(self) -> None:
+        if self._h:
+            _lib.load().pyqsm_voxel_grid_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def radius_reducer(reducer) -> int:
+    """The device code of a reducer name (``mean``, ``min``, ``max``, ``first``) or of np.mean /
+    np.min / np.max."""
+    if isinstance(reducer, str):
+        if reducer not in RADIUS_REDUCERS:
+            raise ValueError(f"reducer must be one of {sorted(RADIUS_REDUCERS)}, got {reducer!r}")
+        return RADIUS_REDUCERS[reducer]
+    for name in ("mean", "min", "amin", "max", "amax"):
+        if reducer is getattr(np, name, None):
+            return RADIUS_REDUCERS[name]
+    raise ValueError(f"reducer must be one of {sorted(RADIUS_REDUCERS)}, got {reducer!r}")
+
+
+def radius_reduce(src, queries, values, radius: float, k: int = 500, reducer="mean", empty_row: int = 0,
+                  return_counts: bool = False, device: int = 0):
+    """``pyqsm_radius_reduce``: ``reducer`` over ``values`` ([n] or [n, F], as float64) of every query's
+    neighbours — the entries ``radius_knn(src, queries, radius, k)`` returns for it — as float64 [m]
+    or [m, F]. A query without neighbours gets ``values[empty_row]``, NaN for ``empty_row=-1``. With
+    ``return_counts`` also the int32 [m] neighbour counts."""
+    s = _points(src)
+    q = _points(queries)
+    n, m = s.shape[0], q.shape[0]
+    vals = np.asarray(values)
+    if vals.ndim not in (1, 2) or vals.shape[0] != n:
+        raise ValueError(f"values must have shape [{n}] or [{n}, F], got {vals.shape}")
+    F = 1 if vals.ndim == 1 else vals.shape[1]
+    v64 = np.ascontiguousarray(vals.reshape(n, F), dtype=np.float64)
+    out = np.empty((m, F), dtype=np.float64)
+    cnt = np.zeros(m, dtype=np.int32) if return_counts else None
+    check(_lib.load().pyqsm_radius_reduce(_p(s), n, _p(q), m, float(radius), int(k), _p(v64), int(F),
+                                          radius_reducer(reducer), int(empty_row), _p(out), _p(cnt), int(device)))
+    res = out if vals.ndim == 2 else out[:, 0]
+    return (res, cnt) if return_counts else res

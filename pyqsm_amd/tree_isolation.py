@@ -21,14 +21,14 @@ import numpy as np
 try:  # flat import style of the reference (pyqsm_amd on sys.path) or package import
     from . import hip
     from ._shadow import fall_through
-    from .geometry.cloud import PointCloud, as_points
+    from .geometry.cloud import PointCloud, VoxelGrid, as_points
 except ImportError:  # pragma: no cover
     import os
     import sys
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from pyqsm_amd import hip
     from pyqsm_amd._shadow import fall_through
-    from pyqsm_amd.geometry.cloud import PointCloud, as_points
+    from pyqsm_amd.geometry.cloud import PointCloud, VoxelGrid, as_points
 
 # names pyQSM's module of the same name defines and this one does not (pyqsm_amd/_shadow.py)
 __getattr__ = fall_through(__name__)
@@ -176,3 +176,18 @@ def _cycle_with_cutoff(src_pts, owner, frontier, active, k, max_distance, cycle_
             if len(new) == 0:
                 new_sets[i] = None
     return new_sets
+
+
+def unassigned_search_cloud(pcd, cluster_pcds, voxel_size=0.1, device: int = 0):
+    """tree_isolation.py:465-475 (and :506-516): the points of ``pcd`` that lie in no occupied voxel
+    of the union of ``cluster_pcds`` — the cloud ``extend_seed_clusters`` still has to search. One
+    device voxel grid over the clusters, one inverted query. Returns ``(search_pcd, uniques)``: the
+    sub-cloud and the ascending int64 indices into ``pcd``."""
+    parts = [as_points(c) for c in cluster_pcds]
+    comp = np.concatenate(parts) if parts else np.zeros((0, 3))
+    pts = as_points(pcd)
+    grid = VoxelGrid.create_from_point_cloud(comp, voxel_size=voxel_size, device=device)
+    _, uniques = grid.device_grid.query(pts, indices=True, invert=True)
+    grid.device_grid.close()
+    search = pcd.select_by_index(uniques) if hasattr(pcd, "select_by_index") else PointCloud(pts[uniques])
+    return search, uniques
