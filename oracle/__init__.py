@@ -13,7 +13,9 @@ Parity status (details in DESIGN.md):
 * RANSAC (pyransac3d), ray casting (Open3D/Embree), point-cloud Laplacian
   (robust_laplacian): those packages are absent and cannot be installed:
   PARITY UNPINNED. The restatements follow the published algorithms and are
-  pinned only by analytic known answers.
+  pinned only by analytic known answers. Ray hits and point-to-mesh distance / inside-outside
+  sign are in addition checked against INDEPENDENT double-precision evaluations in other
+  formulations (ray_f64.c, meshdist_f64.c), which the mirrors of the kernels cannot give.
 """
 from __future__ import annotations
 
@@ -30,7 +32,7 @@ _LIB = None
 def build(force: bool = False) -> str:
     """Compile liboracle.so with gcc (no-op when it is up to date)."""
     so = os.path.join(_HERE, "liboracle.so")
-    srcs = [os.path.join(_HERE, f) for f in ("pyqsm_oracle.c", "ray_f64.c")]
+    srcs = [os.path.join(_HERE, f) for f in ("pyqsm_oracle.c", "ray_f64.c", "meshdist_f64.c")]
     if force or not os.path.exists(so) or os.path.getmtime(so) < max(map(os.path.getmtime, srcs)):
         subprocess.run(["make", "-C", _HERE, "-B", "liboracle.so"], check=True,
                        stdout=subprocess.DEVNULL)
@@ -64,6 +66,12 @@ def _lib():
         lib.orc_cast_rays_f64.argtypes = [p, p, i64, p, i64, p, p, p, p]
         lib.orc_ray_tri_pairs_f64.restype = ctypes.c_int
         lib.orc_ray_tri_pairs_f64.argtypes = [p, p, p, i64, p, p, p, p]
+        lib.orc_point_mesh_distance_f64.restype = ctypes.c_int
+        lib.orc_point_mesh_distance_f64.argtypes = [p, p, i64, p, i64, p, p]
+        lib.orc_point_tri_pairs_f64.restype = ctypes.c_int
+        lib.orc_point_tri_pairs_f64.argtypes = [p, p, i64, p, i64, p, p]
+        lib.orc_winding_number_f64.restype = ctypes.c_int
+        lib.orc_winding_number_f64.argtypes = [p, p, i64, p, i64, p]
         _LIB = lib
     return _LIB
 
@@ -218,6 +226,50 @@ def point_mesh_distance(verts, tris, queries):
     _lib().orc_point_mesh_distance(_ptr(v), v.shape[0], _ptr(t), t.shape[0], _ptr(q), q.shape[0],
                                    _ptr(dist), _ptr(prim))
     return dist, prim
+
+
+def _mesh_and_queries(verts, tris, queries):
+    v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+    q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, 3)
+    if len(t) and (t.min() < 0 or t.max() >= len(v)):
+        raise IndexError("triangle index outside the vertex array")
+    return v, t, q
+
+
+def point_mesh_distance_f64(verts, tris, queries):
+    """INDEPENDENT (dist f64 [Q], prim i64 [Q]; inf / -1 without triangles): oracle/meshdist_f64.c,
+    the fp32 inputs taken as exact doubles, plane projection inside the three edge half-planes,
+    else the nearest of the three segments — not the region walk of meshdist.hip or of
+    :func:`point_mesh_distance`."""
+    v, t, q = _mesh_and_queries(verts, tris, queries)
+    dist = np.empty(q.shape[0])
+    prim = np.empty(q.shape[0], dtype=np.int64)
+    _lib().orc_point_mesh_distance_f64(_ptr(v), _ptr(t), t.shape[0], _ptr(q), q.shape[0],
+                                       _ptr(dist), _ptr(prim))
+    return dist, prim
+
+
+def point_tri_pairs_f64(verts, tris, queries, prim):
+    """The same fp64 distance from query i to the GIVEN triangle prim[i] alone (NaN for an id
+    outside the mesh): does a reported closest triangle realise the minimum?"""
+    v, t, q = _mesh_and_queries(verts, tris, queries)
+    pr = np.ascontiguousarray(prim, dtype=np.int64).reshape(-1)
+    assert len(pr) == len(q)
+    dist = np.empty(q.shape[0])
+    _lib().orc_point_tri_pairs_f64(_ptr(v), _ptr(t), t.shape[0], _ptr(q), q.shape[0], _ptr(pr),
+                                   _ptr(dist))
+    return dist
+
+
+def inside_closed_mesh_f64(verts, tris, queries):
+    """INDEPENDENT inside/outside: the winding number f64 [Q] of the mesh about every query (Van
+    Oosterom-Strackee solid angles summed over all triangles, / 4 pi). About +-1 inside a closed,
+    consistently oriented mesh (convex or not), about 0 outside; no ray is cast."""
+    v, t, q = _mesh_and_queries(verts, tris, queries)
+    wn = np.empty(q.shape[0])
+    _lib().orc_winding_number_f64(_ptr(v), _ptr(t), t.shape[0], _ptr(q), q.shape[0], _ptr(wn))
+    return wn
 
 
 def list_intersections(verts, tris, rays):

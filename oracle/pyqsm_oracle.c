@@ -917,9 +917,16 @@ void orc_free(void* p) { free(p); }
  * orc_point_mesh_distance — unsigned distance from query points to a triangle mesh and
  * the closest triangle (lowest index on ties), standing in for Open3D's
  * RaycastingScene.compute_distance behind `mri` (pyQSM/viz/ray_casting.py:237-260;
- * Open3D itself is not installable here: PARITY UNPINNED, pinned to analytic cases in
- * tests/). Ericson's closest-point-on-triangle region walk in fp32, products rounded
- * separately, in the operation order of pyqsm_amd/csrc/meshdist.hip. */
+ * Open3D itself is not installable here: PARITY UNPINNED). Ericson's closest-point-on-triangle
+ * region walk in fp32, products rounded separately, in the operation order of
+ * pyqsm_amd/csrc/meshdist.hip — a MIRROR of the kernel; the independent check is
+ * meshdist_f64.c. Thin triangles do not go through the walk (its va, vb, vc are rounding noise
+ * on a sliver): every triangle is classified once, in fp64 from the fp32 edge vectors, as in
+ * k_dist_tris — kind 0 the walk; kind 1 (|ab x ac|^2 <= ORC_THIN_REL2 * (longest edge^2)^2) plane
+ * distance inside the three edge half-planes, else the nearest of the three segments; kind 2
+ * (no normal) the segments alone. */
+#define ORC_THIN_REL2 4e-4
+
 static float orc_dot3f(float ax, float ay, float az, float bx, float by, float bz) {
   float d = ax * bx;
   d = d + ay * by;
@@ -927,60 +934,136 @@ static float orc_dot3f(float ax, float ay, float az, float bx, float by, float b
   return d;
 }
 
+/* squared distance from w = p - u to the segment u .. u + e */
+static float orc_seg_dist2(float ex, float ey, float ez, float wx, float wy, float wz) {
+  const float ee = orc_dot3f(ex, ey, ez, ex, ey, ez);
+  float s = ee > 0.f ? orc_dot3f(wx, wy, wz, ex, ey, ez) / ee : 0.f;
+  s = s < 0.f ? 0.f : (s > 1.f ? 1.f : s);
+  const float rx = wx - s * ex, ry = wy - s * ey, rz = wz - s * ez;
+  return orc_dot3f(rx, ry, rz, rx, ry, rz);
+}
+
+/* m = unit(n x e); 0 if e has no length in fp32 */
+static int orc_edge_normal(const float* n, float ex, float ey, float ez, float* m) {
+  const float cx = n[1] * ez - n[2] * ey, cy = n[2] * ex - n[0] * ez, cz = n[0] * ey - n[1] * ex;
+  const float l2 = orc_dot3f(cx, cy, cz, cx, cy, cz);
+  if (!(l2 > 0.f) || l2 == INFINITY) return 0;
+  const float inv = 1.f / sqrtf(l2);
+  m[0] = cx * inv; m[1] = cy * inv; m[2] = cz * inv;
+  return 1;
+}
+
+#define ORC_DREC 22 /* a, ab, ac, kind, n, m_ab, m_bc, m_ca */
+
 int orc_point_mesh_distance(const float* verts, int64_t V, const int32_t* tris, int64_t T,
                             const float* qry, int64_t Q, float* dist, uint32_t* prim) {
   (void)V;
+  float* rec = (float*)calloc((size_t)(T > 0 ? T : 1) * ORC_DREC, sizeof(float));
+  if (!rec) return -1;
+  for (int64_t j = 0; j < T; ++j) { /* k_dist_tris */
+    const float* a = verts + 3 * (int64_t)tris[3 * j];
+    const float* b = verts + 3 * (int64_t)tris[3 * j + 1];
+    const float* c = verts + 3 * (int64_t)tris[3 * j + 2];
+    const float ax = a[0], ay = a[1], az = a[2];
+    const float abx = b[0] - ax, aby = b[1] - ay, abz = b[2] - az;
+    const float acx = c[0] - ax, acy = c[1] - ay, acz = c[2] - az;
+    const float bcx = acx - abx, bcy = acy - aby, bcz = acz - abz;
+    const double nx = (double)aby * (double)acz - (double)abz * (double)acy;
+    const double ny = (double)abz * (double)acx - (double)abx * (double)acz;
+    const double nz = (double)abx * (double)acy - (double)aby * (double)acx;
+    const double nn = (nx * nx + ny * ny) + nz * nz;
+    const double lab = ((double)abx * (double)abx + (double)aby * (double)aby) + (double)abz * (double)abz;
+    const double lac = ((double)acx * (double)acx + (double)acy * (double)acy) + (double)acz * (double)acz;
+    const double lbc = ((double)bcx * (double)bcx + (double)bcy * (double)bcy) + (double)bcz * (double)bcz;
+    double l2 = lab > lac ? lab : lac;
+    l2 = lbc > l2 ? lbc : l2;
+    double nmax = fabs(nx) > fabs(ny) ? fabs(nx) : fabs(ny);
+    nmax = fabs(nz) > nmax ? fabs(nz) : nmax;
+    float* r = rec + ORC_DREC * j;
+    float kind = 0.f;
+    if (!(nmax > 0.0)) {
+      kind = 2.f;
+    } else if (!(nn > ORC_THIN_REL2 * (l2 * l2))) {
+      kind = 2.f;
+      const float ux = (float)(nx / nmax), uy = (float)(ny / nmax), uz = (float)(nz / nmax);
+      const float inv = 1.f / sqrtf(orc_dot3f(ux, uy, uz, ux, uy, uz));
+      float* n = r + 10;
+      n[0] = ux * inv; n[1] = uy * inv; n[2] = uz * inv;
+      if (orc_edge_normal(n, abx, aby, abz, r + 13) && orc_edge_normal(n, bcx, bcy, bcz, r + 16) &&
+          orc_edge_normal(n, -acx, -acy, -acz, r + 19))
+        kind = 1.f;
+    }
+    r[0] = ax; r[1] = ay; r[2] = az; r[3] = abx; r[4] = aby; r[5] = abz;
+    r[6] = acx; r[7] = acy; r[8] = acz; r[9] = kind;
+  }
 #pragma omp parallel for schedule(static)
   for (int64_t i = 0; i < Q; ++i) {
     const float px = qry[3 * i], py = qry[3 * i + 1], pz = qry[3 * i + 2];
     float best = INFINITY;
     uint32_t bp = 0xFFFFFFFFu;
     for (int64_t j = 0; j < T; ++j) {
-      const float* a = verts + 3 * (int64_t)tris[3 * j];
-      const float* b = verts + 3 * (int64_t)tris[3 * j + 1];
-      const float* c = verts + 3 * (int64_t)tris[3 * j + 2];
-      const float ax = a[0], ay = a[1], az = a[2];
-      const float abx = b[0] - ax, aby = b[1] - ay, abz = b[2] - az;
-      const float acx = c[0] - ax, acy = c[1] - ay, acz = c[2] - az;
+      const float* r = rec + ORC_DREC * j;
+      const float ax = r[0], ay = r[1], az = r[2];
+      const float abx = r[3], aby = r[4], abz = r[5];
+      const float acx = r[6], acy = r[7], acz = r[8];
       const float apx = px - ax, apy = py - ay, apz = pz - az;
-      const float d1 = orc_dot3f(abx, aby, abz, apx, apy, apz);
-      const float d2 = orc_dot3f(acx, acy, acz, apx, apy, apz);
-      float cx, cy, cz;
-      const float bpx = apx - abx, bpy = apy - aby, bpz = apz - abz;
-      const float d3 = orc_dot3f(abx, aby, abz, bpx, bpy, bpz);
-      const float d4 = orc_dot3f(acx, acy, acz, bpx, bpy, bpz);
-      const float cpx = apx - acx, cpy = apy - acy, cpz = apz - acz;
-      const float d5 = orc_dot3f(abx, aby, abz, cpx, cpy, cpz);
-      const float d6 = orc_dot3f(acx, acy, acz, cpx, cpy, cpz);
-      const float vc = d1 * d4 - d3 * d2;
-      const float vb = d5 * d2 - d1 * d6;
-      const float va = d3 * d6 - d5 * d4;
-      if (d1 <= 0.f && d2 <= 0.f) {
-        cx = cy = cz = 0.f;
-      } else if (d3 >= 0.f && d4 <= d3) {
-        cx = abx; cy = aby; cz = abz;
-      } else if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f) {
-        const float v = d1 / (d1 - d3);
-        cx = v * abx; cy = v * aby; cz = v * abz;
-      } else if (d6 >= 0.f && d5 <= d6) {
-        cx = acx; cy = acy; cz = acz;
-      } else if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f) {
-        const float w = d2 / (d2 - d6);
-        cx = w * acx; cy = w * acy; cz = w * acz;
-      } else if (va <= 0.f && (d4 - d3) >= 0.f && (d5 - d6) >= 0.f) {
-        const float w = (d4 - d3) / ((d4 - d3) + (d5 - d6));
-        cx = abx + w * (acx - abx);
-        cy = aby + w * (acy - aby);
-        cz = abz + w * (acz - abz);
+      float d;
+      if (r[9] != 0.f) {
+        const float bpx = apx - abx, bpy = apy - aby, bpz = apz - abz;
+        d = orc_seg_dist2(abx, aby, abz, apx, apy, apz);
+        const float dac = orc_seg_dist2(acx, acy, acz, apx, apy, apz);
+        const float dbc = orc_seg_dist2(acx - abx, acy - aby, acz - abz, bpx, bpy, bpz);
+        d = dac < d ? dac : d;
+        d = dbc < d ? dbc : d;
+        if (r[9] == 1.f) {
+          const float sab = orc_dot3f(r[13], r[14], r[15], apx, apy, apz);
+          const float sbc = orc_dot3f(r[16], r[17], r[18], bpx, bpy, bpz);
+          const float sca = orc_dot3f(r[19], r[20], r[21], apx, apy, apz);
+          if (sab >= 0.f && sbc >= 0.f && sca >= 0.f) {
+            const float sn = orc_dot3f(r[10], r[11], r[12], apx, apy, apz);
+            d = sn * sn;
+          }
+        }
       } else {
-        const float denom = 1.f / (va + vb + vc);
-        const float v = vb * denom, w = vc * denom;
-        cx = abx * v + acx * w;
-        cy = aby * v + acy * w;
-        cz = abz * v + acz * w;
+        const float d1 = orc_dot3f(abx, aby, abz, apx, apy, apz);
+        const float d2 = orc_dot3f(acx, acy, acz, apx, apy, apz);
+        float cx, cy, cz;
+        const float bpx = apx - abx, bpy = apy - aby, bpz = apz - abz;
+        const float d3 = orc_dot3f(abx, aby, abz, bpx, bpy, bpz);
+        const float d4 = orc_dot3f(acx, acy, acz, bpx, bpy, bpz);
+        const float cpx = apx - acx, cpy = apy - acy, cpz = apz - acz;
+        const float d5 = orc_dot3f(abx, aby, abz, cpx, cpy, cpz);
+        const float d6 = orc_dot3f(acx, acy, acz, cpx, cpy, cpz);
+        const float vc = d1 * d4 - d3 * d2;
+        const float vb = d5 * d2 - d1 * d6;
+        const float va = d3 * d6 - d5 * d4;
+        if (d1 <= 0.f && d2 <= 0.f) {
+          cx = cy = cz = 0.f;
+        } else if (d3 >= 0.f && d4 <= d3) {
+          cx = abx; cy = aby; cz = abz;
+        } else if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f) {
+          const float v = d1 / (d1 - d3);
+          cx = v * abx; cy = v * aby; cz = v * abz;
+        } else if (d6 >= 0.f && d5 <= d6) {
+          cx = acx; cy = acy; cz = acz;
+        } else if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f) {
+          const float w = d2 / (d2 - d6);
+          cx = w * acx; cy = w * acy; cz = w * acz;
+        } else if (va <= 0.f && (d4 - d3) >= 0.f && (d5 - d6) >= 0.f) {
+          const float w = (d4 - d3) / ((d4 - d3) + (d5 - d6));
+          cx = abx + w * (acx - abx);
+          cy = aby + w * (acy - aby);
+          cz = abz + w * (acz - abz);
+        } else {
+          const float denom = 1.f / (va + vb + vc);
+          const float v = vb * denom, w = vc * denom;
+          cx = abx * v + acx * w;
+          cy = aby * v + acy * w;
+          cz = abz * v + acz * w;
+        }
+        const float ex = apx - cx, ey = apy - cy, ez = apz - cz;
+        d = orc_dot3f(ex, ey, ez, ex, ey, ez);
       }
-      const float ex = apx - cx, ey = apy - cy, ez = apz - cz;
-      const float d = orc_dot3f(ex, ey, ez, ex, ey, ez);
       if (d < best) {
         best = d;
         bp = (uint32_t)j;
@@ -989,5 +1072,6 @@ int orc_point_mesh_distance(const float* verts, int64_t V, const int32_t* tris, 
     dist[i] = sqrtf(best);
     prim[i] = bp;
   }
+  free(rec);
   return 0;
 }

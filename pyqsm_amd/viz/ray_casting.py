@@ -84,6 +84,21 @@ def create_rays_pinhole(fov_deg, center, eye, up, width_px, height_px) -> np.nda
     return rays
 
 
+# The parity ray of compute_occupancy / compute_signed_distance / get_points_inside_mesh. A fixed
+# GENERIC direction: an axis-aligned ray from a query on a lattice spanned by the mesh's own
+# bounding box (what `mri` asks) runs through the mesh's vertices, edges and face diagonals, where
+# the edge-inclusive triangle test counts a crossing twice or not at all (196 of the 2744 interior
+# points of a unit cube's 16^3 lattice came out "outside" along +x). No component ratio of this
+# direction is a small rational, so it meets an edge or vertex only by accident.
+OCCUPANCY_DIRECTION = np.float32([0.9165, 0.3711, 0.1493])
+
+
+def occupancy_rays(query_points) -> np.ndarray:
+    """float32 [n, 6]: one ray from every query point along ``OCCUPANCY_DIRECTION``."""
+    q = np.ascontiguousarray(_np(query_points), dtype=np.float32).reshape(-1, 3)
+    return np.concatenate([q, np.tile(OCCUPANCY_DIRECTION, (len(q), 1))], axis=1)
+
+
 class RaycastingScene:
     """The subset of ``open3d.t.geometry.RaycastingScene`` the reference uses."""
 
@@ -119,11 +134,10 @@ class RaycastingScene:
         return self.list_intersections(r.reshape(-1, 6))["counts"].reshape(r.shape[:-1])
 
     def compute_occupancy(self, query_points) -> np.ndarray:
-        """1.0 for points inside a closed mesh (odd number of crossings along +x)."""
+        """1.0 for points inside a closed mesh (odd number of crossings along
+        ``OCCUPANCY_DIRECTION``)."""
         q = np.ascontiguousarray(_np(query_points), dtype=np.float32)
-        rays = np.concatenate([q.reshape(-1, 3), np.tile(np.float32([1, 0, 0]), (q.size // 3, 1))],
-                              axis=1)
-        counts = self.count_intersections(rays)
+        counts = self.count_intersections(occupancy_rays(q))
         return (counts % 2).astype(np.float32).reshape(q.shape[:-1])
 
     def compute_distance(self, query_points) -> np.ndarray:
