@@ -2,10 +2,11 @@
 """BASELINE.json configs[2]: N-point synthetic forest, Laplacian-contraction
 skeletonisation (extract_skeleton) on one MI355X, with a per-phase time split.
 
-    python examples/config3_skeleton.py [--points 1000000] [--iters 20] [--contraction 3]
+    python examples/config3_skeleton.py [--points 1000000] [--iters 20] [--contraction 3] [--qsm]
 
 `--contraction 7` reproduces the value quoted in BASELINE.json (the reference's
-active TOML value is 3)."""
+active TOML value is 3). `--qsm` goes on to the cylinder table through the device path
+(extract_topology_arrays, skeleton_to_QSM_arrays) and adds its stage times."""
 import argparse
 import json
 import logging
@@ -29,6 +30,7 @@ def main():
     ap.add_argument("--verbose", action="store_true")
     ap.add_argument("--engine", default="python", help="python (loop over the C-ABI calls) or native "
                                                          "(pyqsm_extract_skeleton: the whole loop in HBM)")
+    ap.add_argument("--qsm", action="store_true", help="also build the skeleton graph and the cylinder table")
     ap.add_argument("--prof-level", type=int, default=1,
                     help="2: also time the level-0 sparse passes one by one (no graphs, slower)")
     args = ap.parse_args()
@@ -62,6 +64,18 @@ def main():
         for k in ("k_bspmv_f", "k_down_l0", "k_up_l0"):
             ms, cnt = hip.prof_get(k)
             out[k + "_us"] = 1e3 * ms / max(cnt, 1)
+    if args.qsm:
+        hip.prof_reset()
+        t0 = time.perf_counter()
+        topo = sk.extract_topology_arrays(got)
+        t1 = time.perf_counter()
+        qsm = sk.skeleton_to_QSM_arrays(topo, total)
+        t2 = time.perf_counter()
+        out.update({"qsm_cylinders": int(len(qsm["radius"])), "qsm_surface_points": int(len(qsm["surface_points"])),
+                    "qsm_skeleton_points": int(len(topo.skeleton_points)), "qsm_chains": int(len(topo.chain_ends)),
+                    "qsm_topology_wall_s": t1 - t0, "qsm_cylinders_wall_s": t2 - t1})
+        for k in ("topo_knn", "topo_forest", "topo_forest_sort", "topo_chains", "topo_radii", "topo_surfaces"):
+            out[k + "_ms"] = hip.prof_get(k)[0]
     print(json.dumps(out))
 
 

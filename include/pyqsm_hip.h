@@ -746,6 +746,63 @@ int pyqsm_voxel_grid_query(const void* grid, const double* qry, int64_t m, int32
 int pyqsm_voxel_grid_query_dev(const void* grid, const double* qry_dev, int64_t m, int32_t flags,
                                uint8_t* included_dev, int32_t* row_dev, int64_t* idx_dev, int64_t* count);
 
+/* ---- skeleton graph and cylinder table ----------------------------------------------------- */
+/*
+ * What follows the contraction and the farthest-point sampling (pyQSM/geometry/skeletonize.py:36-146,
+ * :375-441): the spanning forest of the kNN graph, the collapse of its degree-2 chains, one radius
+ * per chain and the sampled cylinder surfaces. tests/topology_restatement.py states the contract;
+ * DESIGN.md section 15.
+ *
+ * pyqsm_skeletal_forest: minimum spanning forest of the undirected kNN graph of xyz f64 [m,3]:
+ *   {i,j} is an edge when j is among the k nearest of i (itself excluded) or i among those of j,
+ *   weighted with the d2 of pyqsm_knn (the smaller of the two directions' values, should they
+ *   differ). Padded entries are no edges. A pair at distance exactly 0 unites the components of its
+ *   ends but is never listed, as in SciPy's minimum_spanning_tree on explicit zeros (its Kruskal pass
+ *   joins across them, its result drops them); so exact duplicates never get an edge between them
+ *   and the listed edges alone may leave them apart. Edges are ordered by
+ *   (d2, packed (min, max)), a strict total order that refines the order by sqrt(d2): the forest is
+ *   unique, and a minimum spanning forest of the square-root weights as well. k in [1, 192]
+ *   (PYQSM_ERANGE, before any device is touched). edges i32 [capacity m - 1, 2] with a < b in
+ *   every row, rows ascending by (a, b); d2 f64 [capacity m - 1]; *n_edges; *rounds (may be
+ *   NULL): Boruvka rounds that hooked a component. The listed forest has m - *n_edges components. The
+ *   same bits on every run. m < 2: no edge, nothing launched. The _dev form takes and fills device
+ *   arrays; the counts stay host values.
+ * pyqsm_collapse_chains: edges i32 [e,2] over nodes 0 .. m-1 MUST form a forest (an end outside
+ *   [0, m) or a self-loop: PYQSM_EINVAL; a walk that meets no end within m steps, as on a ring
+ *   through a kept node, too - a ring of degree-2 nodes alone is not noticed and not reported).
+ *   kept i32 [capacity m]: the nodes of degree != 2, ascending. Every maximal run of degree-2 nodes
+ *   between kept nodes a < b is a chain: chain_ends i32 [capacity e, 2] rows (a, b) ascending,
+ *   chain_ptr i64 [capacity e + 1], members i32 [capacity m] in walking order from a to b; an edge
+ *   between two kept nodes is a chain without members. counts[3]: kept nodes, chains, members.
+ * pyqsm_chain_radii: radius[c] = mean over the members s of chain c of |shift[s]|, or of
+ *   |shift[index_map[s]]| when index_map i32 [n_map] is not NULL; shift f64 [n,3]; the norm is
+ *   sqrt((x x + y y) + z z); the terms are added in the order of NumPy's pairwise summation (eight
+ *   running sums up to 128 terms, halves above), the contract being the rounding bound of a sum of
+ *   positive terms, |r - mean| <= (len + 4) 2^-52 mean. A chain without members gets
+ *   0. An index out of range: PYQSM_EINVAL.
+ * pyqsm_cylinder_surfaces: params f64 [q,14] = centre, unit axis, u, v (3 each), radius, height;
+ *   cos_sin f64 [40] = the 20 cosines, then the 20 sines. Per cylinder the 100 x 20 points
+ *   (centre + radius (cos u + sin v)) + along axis, along = np.linspace(-height / 2, height / 2, 100),
+ *   rounded to millimetres (rint(x 1000) / 1000.0), distinct rows in lexicographic order, of equal
+ *   rows the first in (level, angle) order. surface_ptr i64 [q + 1]; *points_out f64 [*total_out, 3]
+ *   is allocated by the library (release with pyqsm_free; NULL when q == 0). A cylinder more than
+ *   2^21 mm across: PYQSM_ERANGE; a coordinate that is not finite: PYQSM_EINVAL.
+ */
+int pyqsm_skeletal_forest(const double* xyz, int64_t m, int32_t k, int32_t* edges, double* d2, int64_t* n_edges,
+                          int32_t* rounds, int32_t device);
+int pyqsm_skeletal_forest_dev(const double* xyz_dev, int64_t m, int32_t k, int32_t* edges_dev, double* d2_dev,
+                              int64_t* n_edges, int32_t* rounds, int32_t device);
+int pyqsm_collapse_chains(const int32_t* edges, int64_t e, int64_t m, int32_t* kept, int32_t* chain_ends,
+                          int64_t* chain_ptr, int32_t* members, int64_t* counts, int32_t device);
+int pyqsm_collapse_chains_dev(const int32_t* edges_dev, int64_t e, int64_t m, int32_t* kept_dev,
+                              int32_t* chain_ends_dev, int64_t* chain_ptr_dev, int32_t* members_dev, int64_t* counts,
+                              int32_t device);
+int pyqsm_chain_radii(const double* shift, int64_t n, const int64_t* chain_ptr, int64_t n_chains,
+                      const int32_t* members, const int32_t* index_map, int64_t n_map, double* radius,
+                      int32_t device);
+int pyqsm_cylinder_surfaces(const double* params, int64_t q, const double* cos_sin, int64_t* surface_ptr,
+                            double** points_out, int64_t* total_out, int32_t device);
+
 #ifdef __cplusplus
 }
 #endif

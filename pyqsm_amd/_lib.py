@@ -112,6 +112,13 @@ SIGNATURES = {
     "pyqsm_voxel_grid_voxels": (ctypes.c_int, [vp, vp, vp]),
     "pyqsm_voxel_grid_query": (ctypes.c_int, [vp, vp, i64, i32, vp, vp, vp, ctypes.POINTER(i64)]),
     "pyqsm_voxel_grid_query_dev": (ctypes.c_int, [vp, vp, i64, i32, vp, vp, vp, ctypes.POINTER(i64)]),
+    "pyqsm_skeletal_forest": (ctypes.c_int, [vp, i64, i32, vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i32), i32]),
+    "pyqsm_skeletal_forest_dev": (ctypes.c_int, [vp, i64, i32, vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i32),
+                                                 i32]),
+    "pyqsm_collapse_chains": (ctypes.c_int, [vp, i64, i64, vp, vp, vp, vp, vp, i32]),
+    "pyqsm_collapse_chains_dev": (ctypes.c_int, [vp, i64, i64, vp, vp, vp, vp, vp, i32]),
+    "pyqsm_chain_radii": (ctypes.c_int, [vp, i64, vp, i64, vp, vp, i64, vp, i32]),
+    "pyqsm_cylinder_surfaces": (ctypes.c_int, [vp, i64, vp, vp, ctypes.POINTER(vp), ctypes.POINTER(i64), i32]),
 }
 
 _lib = None

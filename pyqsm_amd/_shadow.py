@@ -85,7 +85,10 @@ HOT_FUNCTIONS = {
     "math_utils.fit": ("cluster_DBSCAN", "fit_shape_RANSAC", "z_align_and_fit", "choose_and_cluster"),
     "geometry.point_cloud_processing": ("cluster_plus", "cluster_and_get_largest"),
     "geometry.skeletonize": ("extract_skeleton", "least_squares_sparse", "extract_topology",
-                             "extract_skeletal_graph", "simplify_graph", "skeleton_to_QSM"),
+                             "extract_skeletal_graph", "simplify_graph", "skeleton_to_QSM",
+                             # array-level additions without a counterpart in the reference (install() skips them)
+                             "skeletal_forest", "collapse_chains", "extract_topology_arrays",
+                             "skeleton_to_QSM_arrays"),
     "geometry.reconstruction": ("get_neighbors_kdtree", "overlap_voxel_grid", "get_nbrs_voxel_grid"),
     "viz.ray_casting": ("cast_rays", "sparse_cast_w_intersections", "get_points_inside_mesh",
                         "project_to_image", "raycast_to_pcd", "mri"),

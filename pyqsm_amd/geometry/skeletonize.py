@@ -681,3 +681,166 @@ def skeleton_to_QSM(topology, topology_graph, total_point_shift, test=True):
         radii.append(radius)
     all_pts = np.concatenate([c.points for c in cyls]) if cyls else np.zeros((0, 3))
     return PointCloud(all_pts), cyls, cyl_objects, radii
+
+
+# --------------------------------------------------------------------------------------
+# The same steps as arrays, computed on the device (csrc/topology.hip): the
+# spanning forest of the kNN graph, the degree-2 chain collapse, the radii and the sampled
+# cylinder surfaces. The functions above keep their code paths; these need no networkx.
+
+def skeletal_forest(points, graph_k_n, device: int = 0):
+    """The minimum spanning forest :func:`extract_skeletal_graph` builds with SciPy, on the device:
+    ``(edges, lengths)`` with edges int32 [e,2] (a < b, rows ascending) and lengths =
+    sqrt(d2) float64 [e]. ``graph_k_n`` is limited to the point count as there."""
+    pts = as_points(points)
+    n = len(pts)
+    k = int(min(int(graph_k_n), max(n - 1, 1)))
+    edges, d2 = hip.skeletal_forest(pts, k, device=device)
+    return edges, np.sqrt(d2)
+
+
+def collapse_chains(edges, n_nodes, device: int = 0):
+    """What :func:`simplify_graph` computes on a forest, as arrays: ``(kept, chain_ends, chain_ptr,
+    members)`` — the nodes of degree != 2 (ascending), one row (a, b), a < b, per maximal run of
+    degree-2 nodes between two of them (rows ascending; a direct edge is a run without members)
+    and the runs' nodes in walking order from a to b as a CSR pair. ``edges`` must be a forest."""
+    return hip.collapse_chains(edges, n_nodes, device=device)
+
+
+class TopologyArrays:
+    """Result of :func:`extract_topology_arrays`. ``skeleton_points`` float64 [m,3], ``sample_idx``
+    int32 [m] (rows of the contracted cloud the samples are), ``edges`` int32 [e,2] (the spanning
+    forest), ``kept`` int32, ``chain_ends`` int32 [c,2], ``chain_ptr`` int64 [c+1], ``members``
+    int32 — node numbers are rows of ``skeleton_points``."""
+
+    def __init__(self, skeleton_points, sample_idx, edges, lengths, kept, chain_ends, chain_ptr, members):
+        self.skeleton_points = skeleton_points
+        self.sample_idx = sample_idx
+        self.edges = edges
+        self.lengths = lengths
+        self.kept = kept
+        self.chain_ends = chain_ends
+        self.chain_ptr = chain_ptr
+        self.members = members
+
+    @property
+    def lines(self):
+        """``chain_ends`` in the numbering of the kept nodes (rows of ``topology.points``)."""
+        return np.searchsorted(self.kept, self.chain_ends).astype(np.int64).reshape(-1, 2)
+
+    @property
+    def topology(self):
+        """The kept nodes and one line per chain (what :func:`extract_topology` returns first)."""
+        return LineSet(self.skeleton_points[self.kept], self.lines)
+
+    def to_networkx(self):
+        """The graph of the kept nodes only, numbered like ``topology.points``, every edge with the
+        ``data`` list of its chain (empty for a direct edge): what :func:`skeleton_to_QSM` takes
+        as ``topology_graph``."""
+        import networkx as nx
+        G = nx.Graph()
+        for i, v in enumerate(self.kept):
+            G.add_node(i, pos=self.skeleton_points[v])
+        ptr, mem = self.chain_ptr, self.members
+        for c, (a, b) in enumerate(self.lines.tolist()):
+            G.add_edge(a, b, data=mem[ptr[c]:ptr[c + 1]].tolist())
+        return G
+
+
+def extract_topology_arrays(contracted, graph_k_n=_SK["graph_k_n"], device: int = 0):
+    """:func:`extract_topology` without the host-side graph steps: the same artefact removal and
+    sample count, farthest-point sampling, then the spanning forest and the chain collapse on the
+    device with the sample and the forest resident between them. Returns :class:`TopologyArrays`."""
+    pts = as_points(contracted)
+    rows = np.arange(len(pts), dtype=np.int64)
+    norms = np.linalg.norm(pts, axis=1)
+    near = int(np.argmin(norms)) if len(pts) else 0
+    if len(pts) and norms[near] <= 0.01:                                 # :118-124
+        keep = np.linalg.norm(pts - pts[near], axis=1) > 0.01
+        pts, rows = pts[keep], rows[keep]
+    fps_points = max(int(pts.shape[0] * 0.1), 15)                       # :128-129
+    fps_points = min(fps_points, pts.shape[0])
+    idx, skeleton_points = farthest_point_down_sample(pts, fps_points, device=device)
+    m = len(skeleton_points)
+    k = int(min(int(graph_k_n), max(m - 1, 1)))
+    empty = np.zeros(0, dtype=np.int32)
+    if m < 2:
+        return TopologyArrays(skeleton_points, rows[idx].astype(np.int32), empty.reshape(0, 2),
+                              np.zeros(0), np.arange(m, dtype=np.int32), empty.reshape(0, 2),
+                              np.zeros(1, dtype=np.int64), empty)
+    bufs = [hip.DeviceBuffer.from_array(np.ascontiguousarray(skeleton_points), device)]
+    try:
+        for nbytes in (8 * (m - 1), 8 * (m - 1), 4 * m, 8 * (m - 1), 8 * m, 4 * m):
+            bufs.append(hip.DeviceBuffer(nbytes, device))
+        xyz, d_edges, d_d2, d_kept, d_ends, d_ptr, d_mem = bufs
+        ne, _ = hip.skeletal_forest_dev(xyz.ptr, m, k, d_edges.ptr, d_d2.ptr, device=device)
+        nk, nc, nm = hip.collapse_chains_dev(d_edges.ptr, ne, m, d_kept.ptr, d_ends.ptr, d_ptr.ptr, d_mem.ptr,
+                                             device=device)
+        edges = d_edges.download((ne, 2), np.int32)
+        lengths = np.sqrt(d_d2.download((ne,), np.float64))
+        kept = d_kept.download((nk,), np.int32)
+        ends = d_ends.download((nc, 2), np.int32)
+        ptr = d_ptr.download((nc + 1,), np.int64)
+        members = d_mem.download((nm,), np.int32)
+    finally:
+        for b in bufs:
+            b.free()
+    return TopologyArrays(skeleton_points, rows[idx].astype(np.int32), edges, lengths, kept, ends, ptr, members)
+
+
+_QSM_ANGLES = np.linspace(0.0, 2.0 * np.pi, 20, endpoint=False)
+
+
+def skeleton_to_QSM_arrays(topo, total_point_shift, use_sample_index: bool = False, surfaces: bool = True,
+                           device: int = 0) -> dict:
+    """:func:`skeleton_to_QSM` on a :class:`TopologyArrays`, as a table: ``start`` / ``end`` float64
+    [q,3], ``radius`` / ``height`` float64 [q], ``chain`` int64 [q] (the row of ``topo.chain_ends``
+    a cylinder comes from), ``surface_points`` float64 [t,3] and ``surface_ptr`` int64 [q+1] (both
+    None with ``surfaces=False``). Chains without members or with coincident ends get no cylinder,
+    as there. Radii and surfaces are computed on the device. Every cylinder runs from a to b with
+    a < b, the row of ``topo.chain_ends``; the surfaces are, bit for bit, the rows
+    ``skeleton_to_QSM(topo.topology, topo.to_networkx(), ...)`` yields. :func:`extract_topology`
+    orients a line the way networkx lists its edge, which may be b to a: a flipped axis has another
+    frame and other rows, so against that path the cylinders agree, the sampled rows need not.
+
+    ``use_sample_index=False`` reads ``total_point_shift`` at the members' own numbers, as the
+    reference does; ``True`` reads it at ``topo.sample_idx[member]``, the rows of the points that
+    were actually sampled."""
+    try:
+        from .cloud import Cylinder
+    except ImportError:
+        from pyqsm_amd.geometry.cloud import Cylinder
+    shift = np.ascontiguousarray(np.asarray(total_point_shift, dtype=np.float64).reshape(-1, 3))
+    ptr = np.asarray(topo.chain_ptr, dtype=np.int64)
+    nc = len(ptr) - 1
+    radius = (hip.chain_radii(shift, ptr, topo.members, topo.sample_idx if use_sample_index else None,
+                              device=device) if nc else np.zeros(0))
+    a = topo.skeleton_points[topo.chain_ends[:, 0]] if nc else np.zeros((0, 3))
+    b = topo.skeleton_points[topo.chain_ends[:, 1]] if nc else np.zeros((0, 3))
+    axis = b - a
+    has = (np.diff(ptr) > 0) & (axis != 0).any(axis=1)
+    chain = np.flatnonzero(has)
+    # the height as skeleton_to_QSM takes it (np.linalg.norm of one vector is a BLAS dot product)
+    height = np.array([float(np.linalg.norm(axis[c])) for c in chain], dtype=np.float64)
+    ok = height != 0
+    chain, height = chain[ok], height[ok]
+    q = len(chain)
+    out = {"start": a[chain], "end": b[chain], "radius": radius[chain], "height": height, "chain": chain,
+           "surface_points": None, "surface_ptr": None}
+    if not surfaces:
+        return out
+    par = np.empty((q, 14), dtype=np.float64)
+    for r, c in enumerate(chain):
+        cyl = Cylinder((a[c] + b[c]) / 2.0, radius[c], height[r], axis[c])
+        u, v = cyl._frame()
+        par[r, 0:3], par[r, 3:6], par[r, 6:9], par[r, 9:12] = cyl.center, cyl.axis, u, v
+        par[r, 12], par[r, 13] = cyl.radius, cyl.height
+    cos_sin = np.concatenate([np.cos(_QSM_ANGLES), np.sin(_QSM_ANGLES)])
+    try:
+        out["surface_points"], out["surface_ptr"] = hip.cylinder_surfaces(par, cos_sin, device=device)
+    except hip._lib.PyQSMHipError as e:
+        if e.code == -4:
+            raise ValueError("skeleton_to_QSM_arrays: a cylinder is more than 2^21 mm across; "
+                             "skeleton_to_QSM handles such input on the host") from e
+        raise
+    return out

@@ -1298,3 +1298,103 @@ def radius_reduce(src, queries, values, radius: float, k: int = 500, reducer="me
                                           radius_reducer(reducer), int(empty_row), _p(out), _p(cnt), int(device)))
     res = out if vals.ndim == 2 else out[:, 0]
     return (res, cnt) if return_counts else res
+
+
+# ---------------------------------------------------------------- skeleton graph and cylinder table
+
+def _edge_list(edges) -> np.ndarray:
+    e = np.ascontiguousarray(np.asarray(edges), dtype=np.int32)
+    if e.size == 0:
+        return e.reshape(0, 2)
+    if e.ndim != 2 or e.shape[1] != 2:
+        raise ValueError(f"expected edges of shape [e,2], got {e.shape}")
+    return e
+
+
+def skeletal_forest(points, k: int, return_rounds: bool = False, device: int = 0):
+    """``pyqsm_skeletal_forest``: the minimum spanning forest of the undirected kNN graph. Returns
+    (edges int32 [e,2] with a < b, rows ascending; d2 float64 [e], the kNN's own squared distances);
+    with ``return_rounds`` also the Boruvka round count. ``len(points) - e`` components."""
+    pts = _points(points)
+    m = pts.shape[0]
+    edges = np.empty((max(m - 1, 0), 2), dtype=np.int32)
+    d2 = np.empty(max(m - 1, 0), dtype=np.float64)
+    ne, rounds = i64(0), i32(0)
+    check(_lib.load().pyqsm_skeletal_forest(_p(pts), m, int(k), _p(edges), _p(d2), ctypes.byref(ne),
+                                            ctypes.byref(rounds), int(device)))
+    edges, d2 = edges[:ne.value].copy(), d2[:ne.value].copy()
+    return (edges, d2, rounds.value) if return_rounds else (edges, d2)
+
+
+def skeletal_forest_dev(xyz_ptr: int, m: int, k: int, edges_ptr: int, d2_ptr: int, device: int = 0):
+    """The same on device arrays (edges int32 [m - 1, 2], d2 float64 [m - 1]): (edge count, rounds)."""
+    ne, rounds = i64(0), i32(0)
+    check(_lib.load().pyqsm_skeletal_forest_dev(xyz_ptr, int(m), int(k), edges_ptr, d2_ptr, ctypes.byref(ne),
+                                                ctypes.byref(rounds), int(device)))
+    return int(ne.value), int(rounds.value)
+
+
+def collapse_chains(edges, n_nodes: int, device: int = 0):
+    """``pyqsm_collapse_chains`` on a forest: (kept int32 ascending, chain_ends int32 [c,2],
+    chain_ptr int64 [c+1], members int32)."""
+    e = _edge_list(edges)
+    m, ne = int(n_nodes), e.shape[0]
+    if m < 0:
+        raise ValueError("n_nodes must not be negative")
+    kept = np.empty(m, dtype=np.int32)
+    ends = np.empty((ne, 2), dtype=np.int32)
+    ptr = np.zeros(ne + 1, dtype=np.int64)
+    members = np.empty(m, dtype=np.int32)
+    counts = np.zeros(3, dtype=np.int64)
+    check(_lib.load().pyqsm_collapse_chains(_p(e), ne, m, _p(kept), _p(ends), _p(ptr), _p(members), _p(counts),
+                                            int(device)))
+    nk, nc, nm = (int(v) for v in counts)
+    return kept[:nk].copy(), ends[:nc].copy(), ptr[:nc + 1].copy(), members[:nm].copy()
+
+
+def collapse_chains_dev(edges_ptr: int, e: int, m: int, kept_ptr: int, ends_ptr: int, ptr_ptr: int,
+                        members_ptr: int, device: int = 0):
+    """The same on device arrays of the worst-case sizes m, e, e + 1, m: (kept, chains, members) counts."""
+    counts = np.zeros(3, dtype=np.int64)
+    check(_lib.load().pyqsm_collapse_chains_dev(edges_ptr, int(e), int(m), kept_ptr, ends_ptr, ptr_ptr,
+                                                members_ptr, _p(counts), int(device)))
+    return tuple(int(v) for v in counts)
+
+
+def chain_radii(shift, chain_ptr, members, index_map=None, device: int = 0) -> np.ndarray:
+    """``pyqsm_chain_radii``: float64 [c], the mean |shift| over every chain's members (through
+    ``index_map`` when given); 0 for a chain without members."""
+    sh = _points(shift)
+    ptr = np.ascontiguousarray(chain_ptr, dtype=np.int64)
+    mem = np.ascontiguousarray(members, dtype=np.int32)
+    if ptr.ndim != 1 or len(ptr) < 1 or mem.ndim != 1 or int(ptr[-1]) != len(mem):
+        raise ValueError("chain_ptr must be [c+1] and end at len(members)")
+    imap = None if index_map is None else np.ascontiguousarray(index_map, dtype=np.int32)
+    nc = len(ptr) - 1
+    out = np.empty(nc, dtype=np.float64)
+    check(_lib.load().pyqsm_chain_radii(_p(sh), sh.shape[0], _p(ptr), nc, _p(mem), _p(imap),
+                                        0 if imap is None else len(imap), _p(out), int(device)))
+    return out
+
+
+def cylinder_surfaces(params, cos_sin, device: int = 0):
+    """``pyqsm_cylinder_surfaces``: params float64 [q,14] (centre, unit axis, u, v, radius, height),
+    cos_sin float64 [40]. Returns (points float64 [t,3], surface_ptr int64 [q+1])."""
+    par = np.ascontiguousarray(params, dtype=np.float64)
+    if par.size == 0:
+        par = par.reshape(0, 14)
+    if par.ndim != 2 or par.shape[1] != 14:
+        raise ValueError(f"expected params of shape [q,14], got {par.shape}")
+    cs = np.ascontiguousarray(cos_sin, dtype=np.float64).ravel()
+    if cs.shape[0] != 40:
+        raise ValueError("cos_sin must hold 20 cosines and 20 sines")
+    q = par.shape[0]
+    lib = _lib.load()
+    ptr = np.zeros(q + 1, dtype=np.int64)
+    out, total = vp(), i64(0)
+    check(lib.pyqsm_cylinder_surfaces(_p(par), q, _p(cs), _p(ptr), ctypes.byref(out), ctypes.byref(total),
+                                      int(device)))
+    if total.value == 0 or not out.value:
+        return np.zeros((0, 3), dtype=np.float64), ptr
+    pts = _adopt(lib, out, ctypes.c_double, total.value * 3, np.float64).reshape(-1, 3)
+    return pts, ptr
