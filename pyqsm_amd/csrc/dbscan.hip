@@ -459,36 +459,95 @@ __global__ __launch_bounds__(1024) void k_sub_rep(int n, const int32_t* __restri
 // of max-norm 1 first, then the 49 of max-norm 2.
 __constant__ signed char kSubOffsets[62][3] = {{1,0,0}, {-1,1,0}, {0,1,0}, {1,1,0}, {-1,-1,1}, {0,-1,1}, {1,-1,1}, {-1,0,1}, {0,0,1}, {1,0,1}, {-1,1,1}, {0,1,1}, {1,1,1}, {2,0,0}, {-2,1,0}, {2,1,0}, {-2,2,0}, {-1,2,0}, {0,2,0}, {1,2,0}, {2,2,0}, {-2,-2,1}, {-1,-2,1}, {0,-2,1}, {1,-2,1}, {2,-2,1}, {-2,-1,1}, {2,-1,1}, {-2,0,1}, {2,0,1}, {-2,1,1}, {2,1,1}, {-2,2,1}, {-1,2,1}, {0,2,1}, {1,2,1}, {2,2,1}, {-2,-2,2}, {-1,-2,2}, {0,-2,2}, {1,-2,2}, {2,-2,2}, {-2,-1,2}, {-1,-1,2}, {0,-1,2}, {1,-1,2}, {2,-1,2}, {-2,0,2}, {-1,0,2}, {0,0,2}, {1,0,2}, {2,0,2}, {-2,1,2}, {-1,1,2}, {0,1,2}, {1,1,2}, {2,1,2}, {-2,2,2}, {-1,2,2}, {0,2,2}, {1,2,2}, {2,2,2}};
 
-// Sub-cells one wave of the two passes below takes: a wave per sub-cell (200 k waves of a
-// few hundred cycles each per million points) was bound by the rate at which waves START
-// (resident waves: 13-21 % of the slots), not by what they did.
-static constexpr int kSubPerWaveDefault = 4;
-
 // Full path compression for the listed representatives (plain accesses: the kernel
 // boundary makes the unions of the previous launch visible, and any value another lane
 // writes meanwhile is an ancestor too).
 // Two launches: the first moves every pointer `max_steps` links up (a hundred and more dependent
 // loads per thread, all threads starting together, was 35 us per million points), the second then
 // reaches the root in depth / max_steps hops over the pointers the first one left.
+// The second launch (rec != null) knows every listed sub-cell's root r and folds it into ONE WORD PER
+// CELL, the fourth word of the cell's first sub-cell record (the binning leaves it 0, grid.hpp):
+//   0      no sub-cell with core points seen yet
+//   r + 1  every such sub-cell of the cell seen so far has root r
+//   -1     mixed
+// The first to arrive installs r + 1; whoever finds another root there stores -1. Whatever the order of
+// arrival, the word ends as r + 1 exactly when all of the cell's listed sub-cells have root r.
+// k_union_sub decides "same tree" per CELL from it.
 __global__ __launch_bounds__(256) void k_flatten_reps(const int4* __restrict__ list,
                                                       const int32_t* __restrict__ m_ptr,
-                                                      int* __restrict__ parent, int max_steps) {
+                                                      int* __restrict__ parent, int max_steps,
+                                                      int4* __restrict__ rec /*null: no summary*/) {
   const int m = *m_ptr;  // number of listed sub-cells, left on the device by k_sub_rep
   int s = blockIdx.x * 256 + threadIdx.x;
   if (s >= m) return;
-  const int p = list[s].x;
+  const int4 me = list[s];
+  const int p = me.x;
   int r = p, steps = 0;
   for (int nx = parent[r]; nx != r && steps < max_steps; nx = parent[r], ++steps) r = nx;
   parent[p] = r;
+  if (rec) {
+    int* const word = reinterpret_cast<int*>(rec + (me.z & ~7)) + 3;  // sub-cell id = first record of the cell * 8 + octant
+    const int old = atomicCAS(word, 0, r + 1);
+    if (old != 0 && old != r + 1 && old != -1) *word = -1;
+  }
+}
+
+// Four sub-cells per wave in the two passes below, side by side in 16-lane groups: a wave per sub-cell
+// (200 k waves of a few hundred cycles each per million points) was bound by the rate at which waves
+// START (resident waves: 13-21 % of the slots), not by what they did.
+static constexpr int kSubPerWave = 4;
+
+// The sub-cell at half-cell offset -(dx, dy, dz) of the sub-cell (cx, cy, cz, octant) = at: its run
+// [q0, q0 + n2) and its representative; rep < 0 where the lane is idle, the cell is empty or the
+// sub-cell has no core point. Three dependent gathers (start twice, the record).
+// (What these kernels cost is the number of cache LINES their gathers touch — one per
+// neighbouring cell and table, taken by the L1 a line at a time. Dropping the second gather
+// start[c2 + 1] by tagging the records with their cell cost more than it saved: lanes of
+// empty cells then fetch the next occupied cell's records.)
+struct SubNbr {
+  int q0, n2, rep;
+};
+__device__ __forceinline__ SubNbr sub_neighbour(bool active, const int4 at, int dx, int dy, int dz, int nx, int ny,
+                                                const int32_t* __restrict__ start,
+                                                const int4* __restrict__ rec) {
+  // half-cell coordinates (cell 1 is the first interior cell; borders are empty)
+  const int gx = 2 * (at.x - 1) + (at.w & 1) - dx, gy = 2 * (at.y - 1) + ((at.w >> 1) & 1) - dy,
+            gz = 2 * (at.z - 1) + ((at.w >> 2) & 1) - dz;
+  const int c2 = (((gz >> 1) + 1) * ny + ((gy >> 1) + 1)) * nx + ((gx >> 1) + 1);
+  const int oct = (gx & 1) | ((gy & 1) << 1) | ((gz & 1) << 2);
+  SubNbr out{0, 0, -1};
+  int b2 = 0, e2 = 0;
+  if (active) {
+    b2 = start[c2];
+    e2 = start[c2 + 1];
+  }
+  if (e2 != b2) {
+    const int4 r = rec[b2 * 8 + oct];
+    if (r.y > 0) {
+      out.q0 = r.x;
+      out.n2 = r.y;
+      out.rep = r.z;
+    }
+  }
+  return out;
 }
 
 // Pass 1 of the union phase, without union-find: every sub-cell hangs itself under the
-// first neighbour it is connected to among the 62 lexicographically NEGATIVE offsets
-// (nearest first). Pointers only go to lexicographically smaller sub-cells, so there is
-// no cycle, every sub-cell writes its own pointer only (plain store, no atomics, no
-// chasing), and what remains after compression is a few trees per cluster — one per
-// sub-cell without a connected smaller neighbour. One wave per sub-cell as below.
-template <int kSubPerWave, class CO>
+// first neighbour it is connected to among the 13 lexicographically NEGATIVE offsets of
+// max-norm 1 (the first 13 of kSubOffsets). Pointers only go to lexicographically smaller
+// sub-cells, so there is no cycle, and every sub-cell writes its own pointer only (plain store,
+// no atomics, no chasing). A sub-cell that finds no such neighbour stays its own root: the pass
+// only has to leave FEW trees, completeness is k_union_sub's business. What remains after
+// compression is a few trees per cluster.
+// Lane t < 13 of a group takes offset t, so one set of gathers serves the wave's four
+// sub-cells; each group then tests its current candidate's point pairs 16 per step (the loop is
+// wave-wide, the ballots are read per group), moves on when a candidate is exhausted and stops
+// at the first hit.
+// (Until this form the pass looked up all 62 offsets per sub-cell, four sub-cells one after the other,
+// and wrote the neighbours found as a 256-byte row per sub-cell for pass 2: 197 002 candidates were
+// tested for 196 884 sub-cells of the benchmark forest — the first one nearly always connects — and
+// the table was the step's largest single piece of traffic.)
+template <class CO>
 __global__ __launch_bounds__(256) void k_hook_sub(const int4* __restrict__ list,
                                                   const int4* __restrict__ list_xyz,
                                                   const int32_t* __restrict__ m_ptr,
@@ -496,195 +555,192 @@ __global__ __launch_bounds__(256) void k_hook_sub(const int4* __restrict__ list,
                                                   const int4* __restrict__ rec, CO co, double r2,
                                                   const uint8_t* __restrict__ core,
                                                   int* __restrict__ parent,
-                                                  int32_t* __restrict__ nbr,
     unsigned long long* __restrict__ st /*stamps or null*/) {
   stamped(st, [&] {
   if (!plan->ok) return;
   const int nx = plan->nx, ny = plan->ny;
   const int m = *m_ptr;
   const int k = threadIdx.x & 63;
-  const int o_dx = k < 62 ? kSubOffsets[k][0] : 0, o_dy = k < 62 ? kSubOffsets[k][1] : 0,
-            o_dz = k < 62 ? kSubOffsets[k][2] : 0;
+  const int t = k & 15, grp = k >> 4;  // offset and sub-cell of the lane
+  const int o_dx = t < 13 ? kSubOffsets[t][0] : 0, o_dy = t < 13 ? kSubOffsets[t][1] : 0,
+            o_dz = t < 13 ? kSubOffsets[t][2] : 0;
   // resident waves stride over the list (wave-uniform bounds): the launch is sized for the chip, not
   // for the upper bound n of m — four waves in five of such a grid found nothing to do and still
   // had to be started (SQ_WAVES 250 k per million points for 49 k with work)
   for (int s0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * kSubPerWave; s0 < m; s0 += gridDim.x * 4 * kSubPerWave) {
-  // the dependent loads (list -> start -> rec) of the wave's sub-cells are issued side by side.
-  // (What these kernels cost is the number of cache LINES their gathers touch — one per
-  // neighbouring cell and table, taken by the L1 a line at a time. Dropping the second gather
-  // start[c2 + 1] by tagging the records with their cell cost more than it saved: lanes of
-  // empty cells then fetch the next occupied cell's records.)
-  int4 me[kSubPerWave], at[kSubPerWave];
-  int b2[kSubPerWave], e2[kSubPerWave], oct[kSubPerWave];
-#pragma unroll
-  for (int u = 0; u < kSubPerWave; ++u) {  // 16 bytes each, wave-uniform
-    me[u] = list[min(s0 + u, m - 1)];
-    at[u] = list_xyz[min(s0 + u, m - 1)];
-  }
-#pragma unroll
-  for (int u = 0; u < kSubPerWave; ++u) {
-    const int cx = at[u].x, cy = at[u].y, cz = at[u].z, o1 = at[u].w;
-    // half-cell coordinates (cell 1 is the first interior cell; borders are empty)
-    const int gx = 2 * (cx - 1) + (o1 & 1) - o_dx, gy = 2 * (cy - 1) + ((o1 >> 1) & 1) - o_dy,
-              gz = 2 * (cz - 1) + ((o1 >> 2) & 1) - o_dz;
-    const int c2 = (((gz >> 1) + 1) * ny + ((gy >> 1) + 1)) * nx + ((gx >> 1) + 1);
-    oct[u] = (gx & 1) | ((gy & 1) << 1) | ((gz & 1) << 2);
-    b2[u] = e2[u] = 0;
-    if (k < 62 && s0 + u < m) {
-      b2[u] = start[c2];
-      e2[u] = start[c2 + 1];
-    }
-  }
-  int q0[kSubPerWave], n2[kSubPerWave], rep2[kSubPerWave];
-#pragma unroll
-  for (int u = 0; u < kSubPerWave; ++u) {
-    q0[u] = n2[u] = 0;
-    rep2[u] = -1;
-    if (e2[u] != b2[u]) {
-      const int4 r = rec[b2[u] * 8 + oct[u]];
-      if (r.y > 0) {
-        q0[u] = r.x;
-        n2[u] = r.y;
-        rep2[u] = r.z;
-      }
-    }
-  }
-  // the neighbours found here are pass 2's work list (one coalesced 256-byte row per
-  // sub-cell): it then starts two dependent loads further down the chain
-#pragma unroll
-  for (int u = 0; u < kSubPerWave; ++u)
-    if (s0 + u < m) nbr[size_t(s0 + u) * 64 + k] = rep2[u];
-#pragma unroll
-  for (int u = 0; u < kSubPerWave; ++u) {
-    const int p = me[u].x, n1 = me[u].w;
-    unsigned long long todo = __ballot(rep2[u] >= 0);
-    bool found = false;
-    while (todo && !found) {
-      const int src = __ffsll(todo) - 1;
-      todo &= todo - 1;
-      const int qb = __shfl(q0[u], src, 64), nb = __shfl(n2[u], src, 64), rb = __shfl(rep2[u], src, 64);
+    const bool live = s0 + grp < m;
+    const int4 me = list[min(s0 + grp, m - 1)], at = list_xyz[min(s0 + grp, m - 1)];
+    const SubNbr nb2 = sub_neighbour(live && t < 13, at, o_dx, o_dy, o_dz, nx, ny, start, rec);
+    const int p = me.x, n1 = me.w;
+    // the group's candidates, nearest first; `base`: the pairs of the current one already tested
+    unsigned todo = unsigned(__ballot(nb2.rep >= 0) >> (16 * grp)) & 0xFFFFu;
+    int base = 0, hooked = -1;
+    while (__ballot(todo != 0)) {
+      const int src = (k & 48) + (todo ? __ffs(todo) - 1 : 0);
+      const int qb = __shfl(nb2.q0, src, 64), nb = __shfl(nb2.n2, src, 64), rb = __shfl(nb2.rep, src, 64);
       // pair (i, j) of the two runs sits at index (i << sh) | j, sh = bits of nb - 1: no division by a
       // run length per lane and step (~40 instructions), at the price of idle lanes where nb is no power of two
       const int sh = nb > 1 ? 32 - __clz(nb - 1) : 0;
       const int pairs = n1 << sh;
-      for (int base = 0; base < pairs && !found; base += 64) {
-        const int idx = base + k;
-        const int j = idx & ((1 << sh) - 1);
-        bool hit = false;
-        if (idx < pairs && j < nb) hit = co.core_pair_within(p + (idx >> sh), qb + j, core, r2);
-        found = __ballot(hit) != 0;
+      const int idx = base + t;
+      const int j = idx & ((1 << sh) - 1);
+      bool hit = false;
+      if (todo && idx < pairs && j < nb) hit = co.core_pair_within(p + (idx >> sh), qb + j, core, r2);
+      const bool found = ((__ballot(hit) >> (16 * grp)) & 0xFFFFull) != 0;
+      if (found) {
+        hooked = rb;
+        todo = 0;
+      } else if (todo) {
+        base += 16;
+        if (base >= pairs) {
+          todo &= todo - 1;
+          base = 0;
+        }
       }
-      // Hang under the neighbour's own pointer rather than under the neighbour: sub-cells are
-      // listed in spatial order, the smaller neighbour's wave has usually finished, and what
-      // it points to is an ancestor still smaller than this sub-cell (no cycles). Chains come
-      // out a few links long instead of as long as a trunk is tall in sub-cells.
-      // (The chains are nevertheless long — 80 % of the benchmark forest's sub-cells sit more than 64
-      // links from their root, PYQSM_DBSCAN_TRACE prints the histogram: a third of the list is in flight
-      // at once, so most neighbours have not hooked yet when their pointer is read, and agent-scope
-      // accesses here change nothing. k_flatten_reps deals with them in two passes.)
-      if (found && k == 0) parent[p] = parent[rb];
     }
-  }
-  // (Taking the wave's sub-cells in rounds — one candidate of each per round, the records of all of them
-  // loaded before the first verdict — was SLOWER both times it was built: 104 us with idle lanes loading a
-  // dummy record, 112 us with predicated loads and finished sub-cells skipped, against 81. The look-ups
-  // above are 48 of those 81 us and live on occupancy (half the resident waves: 118 us); the rounds'
-  // record arrays cost the registers that occupancy needs.)
+    // Hang under the neighbour's own pointer rather than under the neighbour: sub-cells are
+    // listed in spatial order, the smaller neighbour's wave has usually finished, and what
+    // it points to is an ancestor still smaller than this sub-cell (no cycles). Chains come
+    // out a few links long instead of as long as a trunk is tall in sub-cells.
+    // (The chains are nevertheless long — 80 % of the benchmark forest's sub-cells sit more than 64
+    // links from their root, PYQSM_DBSCAN_TRACE prints the histogram: a third of the list is in flight
+    // at once, so most neighbours have not hooked yet when their pointer is read, and agent-scope
+    // accesses here change nothing. k_flatten_reps deals with them in two passes.)
+    if (hooked >= 0 && t == 0) parent[p] = parent[hooked];
   }
   });
 }
 
-// Pass 2: a WAVE per kSubPerWave sub-cells with core points, over the same pairs (sub-cell, neighbour at
-// a lexicographically negative offset) that pass 1 resolved and left in `nbr` — every
-// unordered pair of neighbouring sub-cells exactly once. Lane k decides whether its
-// neighbour still has to be tested (after pass 1 and the compression almost none has: two
-// plain loads show the same root); the wave then takes the ones that do one at a time and
-// tests all |S1| x |S2| point pairs at once, 64 per step. (A lane per pair of sub-cells
-// running the pair loop itself was 3x slower: ~25 dependent iterations per lane, and a wave
-// lasts as long as its slowest lane.)
-template <int kSubPerWave, class CO>
-__global__ __launch_bounds__(256) void k_union_sub(const int4* __restrict__ list,
-                                                   const int32_t* __restrict__ m_ptr,
-                                                   const int32_t* __restrict__ nbr,
-                                                   const int32_t* __restrict__ sub_of,
-                                                   const int4* __restrict__ rec, CO co, double r2,
-                                                   const uint8_t* __restrict__ core, int* parent,
-    unsigned long long* __restrict__ st /*stamps or null*/) {
-  stamped(st, [&] {
-  const int m = *m_ptr;
-  const int k = threadIdx.x & 63;
-  for (int s0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * kSubPerWave; s0 < m; s0 += gridDim.x * 4 * kSubPerWave) {
-  int rep2[kSubPerWave];
-  int4 me[kSubPerWave];
-#pragma unroll
-  for (int u = 0; u < kSubPerWave; ++u) {
-    rep2[u] = s0 + u < m ? nbr[size_t(s0 + u) * 64 + k] : -1;
-    me[u] = list[min(s0 + u, m - 1)];
+// All |S1| x |S2| point pairs of two runs, 64 per wave step: is one core-core pair within eps?
+template <class CO>
+__device__ __forceinline__ bool wave_pair_within(const CO& co, int p, int n1, int qb, int nb, int k,
+                                                 const uint8_t* __restrict__ core, double r2) {
+  const int sh = nb > 1 ? 32 - __clz(nb - 1) : 0;  // (as in k_hook_sub: shift and mask, no division)
+  const int pairs = n1 << sh;
+  bool found = false;
+  for (int base = 0; base < pairs && !found; base += 64) {
+    const int idx = base + k;
+    const int j = idx & ((1 << sh) - 1);
+    bool hit = false;
+    if (idx < pairs && j < nb) hit = co.core_pair_within(p + (idx >> sh), qb + j, core, r2);
+    found = __ballot(hit) != 0;
   }
+  return found;
+}
+
+// The full treatment of ONE sub-cell by a wave: lane k looks up the neighbour at the k-th of the 62
+// lexicographically negative offsets and decides whether it still has to be tested (two plain loads
+// showing the same root say no); the wave then takes the ones that do one at a time and tests all
+// |S1| x |S2| point pairs at once, 64 per step. (A lane per pair of sub-cells running the pair loop
+// itself was 3x slower: ~25 dependent iterations per lane, and a wave lasts as long as its slowest lane.)
+template <class CO>
+__device__ __forceinline__ void seam_unite(const int4 me, const int4 at, int k, int o_dx, int o_dy, int o_dz,
+                                           int nx, int ny, const int32_t* __restrict__ start,
+                                           const int4* __restrict__ rec, const CO& co, double r2,
+                                           const uint8_t* __restrict__ core, int* parent) {
+  const SubNbr nb2 = sub_neighbour(k < 62, at, o_dx, o_dy, o_dz, nx, ny, start, rec);
+  const int p = me.x, n1 = me.w, rep2 = nb2.rep;
   // A plain (cached, possibly stale) read names an ancestor; equal ancestors prove
   // "same tree" (trees only merge). The coherent chase is for the rest.
   const int* vparent = parent;
-  int a1[kSubPerWave], a2[kSubPerWave];
-#pragma unroll
-  for (int u = 0; u < kSubPerWave; ++u) {
-    a1[u] = a2[u] = 0;
-    if (rep2[u] >= 0) {
-      a1[u] = vparent[me[u].x];
-      a2[u] = vparent[rep2[u]];
+  int a1 = 0, a2 = 0;
+  if (rep2 >= 0) {
+    a1 = vparent[p];
+    a2 = vparent[rep2];
+  }
+  bool need = rep2 >= 0 && !(a1 == a2 || a2 == p || a1 == rep2);
+  int root2 = -1;  // the neighbour's tree, as the coherent look found it
+  if (need) {
+    // The coherent look: both chains at once, starting from the ancestors the plain reads named (after
+    // the compression those are the roots unless this launch has hooked them since) — four dependent
+    // agent-scope loads per doubtful pair became one or two.
+    int ra = a1, rb = a2;
+    for (;;) {
+      const int pa = ld_parent(parent, ra), pb = ld_parent(parent, rb);
+      if (pa == ra && pb == rb) break;
+      ra = pa;
+      rb = pb;
+    }
+    need = ra != rb;
+    root2 = rb;
+  }
+  unsigned long long todo = __ballot(need);
+  while (todo) {
+    const int src = __ffsll(todo) - 1;
+    todo &= todo - 1;
+    const int qb = __shfl(nb2.q0, src, 64), nb = __shfl(nb2.n2, src, 64), rb = __shfl(rep2, src, 64);
+    const int tree = __shfl(root2, src, 64);
+    if (wave_pair_within(co, p, n1, qb, nb, k, core, r2)) {
+      if (k == 0) unite(parent, p, rb);
+      // this sub-cell now hangs together with that whole tree: its other doubtful neighbours in the same
+      // tree need no test and no union (a sub-cell on the seam of two trees has ~7 of them, and a wave
+      // went through them one after the other — test, two coherent finds, a CAS on the same hot root)
+      todo &= ~__ballot(root2 == tree);
     }
   }
+}
+
+// Pass 2 joins the trees the hook pass left, and it is what makes the union phase COMPLETE: every
+// unordered pair of neighbouring sub-cells sits at a lexicographically negative offset (dz, dy, dx; at
+// most two half-cells per axis) of exactly one of the two. The sub-cells at the negative offsets of s lie
+// in the 18 cells of s's own z-layer and the layer below: dz >= 0 keeps them out of the layer above, and
+// with dz = 1 inside the own layer dy and dx are free. (NOT in "the cell and its 13 lexicographically
+// smaller neighbours": offset (0, -2, 1) of an upper octant leads to the cell at y + 1 of the same layer.)
+// So a sub-cell s first reads the summary words (k_flatten_reps) of those 18 cells, four sub-cells per
+// wave in 16-lane groups, lane t < 9 one (x, y) column in both layers: when every word is 0 or names the
+// root r_s that a plain read of s's pointer shows, s and all core sub-cells of those cells are in one
+// tree and no pair of s needs a test. The words are a snapshot taken at a kernel boundary and trees only
+// merge, so a pointer that this launch has moved meanwhile (r_s is then another ancestor) can only fail
+// the comparison: an unnecessary full treatment, never a pair skipped wrongly. Only the SEAM sub-cells,
+// where a word is mixed or names another tree, get seam_unite's 62 offsets, one sub-cell per wave step.
+// (Until this form every sub-cell put all its neighbours, 6 million pairs on the benchmark forest,
+// through two parent gathers each, from the table the hook pass wrote: 21 of the pass's 32 us, for
+// 15 800 doubtful pairs in 2 200 sub-cells.)
+template <class CO>
+__global__ __launch_bounds__(256) void k_union_sub(const int4* __restrict__ list,
+                                                   const int4* __restrict__ list_xyz,
+                                                   const int32_t* __restrict__ m_ptr,
+                                                   const GridPlan* __restrict__ plan, const int32_t* __restrict__ start,
+                                                   const int4* __restrict__ rec, CO co, double r2,
+                                                   const uint8_t* __restrict__ core, int* parent,
+                                                   unsigned long long* __restrict__ seam_cnt /*trace or null*/,
+    unsigned long long* __restrict__ st /*stamps or null*/) {
+  stamped(st, [&] {
+  if (!plan->ok) return;
+  const int nx = plan->nx, ny = plan->ny;
+  const int m = *m_ptr;
+  const int k = threadIdx.x & 63;
+  const int t = k & 15, grp = k >> 4;
+  const int o_dx = k < 62 ? kSubOffsets[k][0] : 0, o_dy = k < 62 ? kSubOffsets[k][1] : 0,
+            o_dz = k < 62 ? kSubOffsets[k][2] : 0;
+  // the group's 18 cells: lane t < 9 takes the column (t % 3 - 1, t / 3 - 1), in the layer below and the own one
+  const int c_off = t < 9 ? (t % 3 - 1) + (t / 3 - 1) * nx : 0;
+  const int layer = nx * ny;
+  for (int s0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * kSubPerWave; s0 < m; s0 += gridDim.x * 4 * kSubPerWave) {
+    const bool live = s0 + grp < m;
+    const int4 me = list[min(s0 + grp, m - 1)];
+    const int* vparent = parent;
+    const int r_s = vparent[me.x];
+    const int c2 = me.y + c_off;  // (cells have a border of empty cells all round: c2 - layer - 1 >= 0)
+    int b2[2] = {0, 0}, e2[2] = {0, 0}, word[2] = {0, 0};
+    if (live && t < 9) {
 #pragma unroll
-  for (int u = 0; u < kSubPerWave; ++u) {
-    const int p = me[u].x, n1 = me[u].w;
-    bool need = rep2[u] >= 0 && !(a1[u] == a2[u] || a2[u] == p || a1[u] == rep2[u]);
-    int root2 = -1;  // the neighbour's tree, as the coherent look found it
-    if (need) {
-      // The coherent look: both chains at once, starting from the ancestors the plain reads named (after
-      // the compression those are the roots unless this launch has hooked them since) — four dependent
-      // agent-scope loads per doubtful pair became one or two. (Without this step the pass takes 21 us:
-      // its table and the quick test; the doubtful pairs were the other 44.)
-      int ra = a1[u], rb = a2[u];
-      for (;;) {
-        const int pa = ld_parent(parent, ra), pb = ld_parent(parent, rb);
-        if (pa == ra && pb == rb) break;
-        ra = pa;
-        rb = pb;
-      }
-      need = ra != rb;
-      root2 = rb;
-    }
-    unsigned long long todo = __ballot(need);
-    if (!todo) continue;
-    int q0 = 0, n2 = 0;
-    if (need) {  // the neighbour's run: start and length
-      const int4 r = rec[sub_of[rep2[u]]];
-      q0 = r.x;
-      n2 = r.y;
-    }
-    while (todo) {
-      const int src = __ffsll(todo) - 1;
-      todo &= todo - 1;
-      const int qb = __shfl(q0, src, 64), nb = __shfl(n2, src, 64), rb = __shfl(rep2[u], src, 64);
-      const int tree = __shfl(root2, src, 64);
-      const int sh = nb > 1 ? 32 - __clz(nb - 1) : 0;  // (as in k_hook_sub: shift and mask, no division)
-      const int pairs = n1 << sh;
-      bool found = false;
-      for (int base = 0; base < pairs && !found; base += 64) {
-        const int idx = base + k;
-        const int j = idx & ((1 << sh) - 1);
-        bool hit = false;
-        if (idx < pairs && j < nb) hit = co.core_pair_within(p + (idx >> sh), qb + j, core, r2);
-        found = __ballot(hit) != 0;
-      }
-      if (found) {
-        if (k == 0) unite(parent, p, rb);
-        // this sub-cell now hangs together with that whole tree: its other doubtful neighbours in the same
-        // tree need no test and no union (a sub-cell on the seam of two trees has ~7 of them, and a wave
-        // went through them one after the other — test, two coherent finds, a CAS on the same hot root)
-        todo &= ~__ballot(root2 == tree);
+      for (int l = 0; l < 2; ++l) {
+        b2[l] = start[c2 - l * layer];
+        e2[l] = start[c2 - l * layer + 1];
       }
     }
-  }
+#pragma unroll
+    for (int l = 0; l < 2; ++l)
+      if (e2[l] != b2[l]) word[l] = rec[b2[l] * 8].w;
+    const unsigned long long seams =
+        __ballot((word[0] != 0 && word[0] != r_s + 1) || (word[1] != 0 && word[1] != r_s + 1));
+    if (!seams) continue;
+    for (int u = 0; u < kSubPerWave; ++u) {
+      if (!((seams >> (16 * u)) & 0xFFFFull)) continue;  // wave-uniform
+      if (seam_cnt && k == 0) atomicAdd(seam_cnt, 1ull);
+      seam_unite(list[s0 + u], list_xyz[s0 + u], k, o_dx, o_dy, o_dz, nx, ny, start, rec, co, r2, core, parent);
+    }
   }
   });
 }
@@ -1092,42 +1148,31 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
                          g.order, parent, g.cell_of, sub.rec, run_min, list, list_cnt, d_plan, list_xyz,
                          stamp_slots(c, ceil_div(n, 1024)));
       // The number m of listed sub-cells stays on the device: the passes below are launched for the
-      // upper bound (a sub-cell holds at least one point, in practice ~5) and read m themselves —
+      // upper bound n (a sub-cell holds at least one point, in practice ~5) and read m themselves —
       // waves beyond it leave at once — which spares the host round trip in the middle of the step
-      // (~15 us of an 0.7 ms step). Clouds so large that the neighbour table for n rows would not be
-      // reasonable (> 8 GiB) read m back and size everything exactly.
-      int64_t rows = n;
-      if (size_t(n) * 256 > (size_t(8) << 30)) {
-        int32_t m = 0;
-        PQ_HIP(hipMemcpyAsync(&m, list_cnt, 4, hipMemcpyDeviceToHost, c->stream));
-        PQ_HIP(hipStreamSynchronize(c->stream));
-        rows = m;
-      }
-      if (rows > 0) {
-        // the two wave-per-sub-cells passes: at most the waves the chip holds at their occupancy (8 per
-        // SIMD), striding over the list
-        // the two wave-per-sub-cells passes: resident waves striding over the list, 16 (hook) and 32
-        // (union) blocks per CU — measured against a block per 16 rows of the bound n: hook 91 -> 82 us,
-        // union 68.5 -> 64 us per million points (PYQSM_UNION_BLOCKS_PER_CU=<hook>,<union>; 0 = the bound)
+      // (~15 us of an 0.7 ms step). Nothing in the phase is sized by m any more.
+      {
+        // the two wave-per-four-sub-cells passes: resident waves striding over the list, 16 (hook) and 32
+        // (union) blocks per CU (PYQSM_UNION_BLOCKS_PER_CU=<hook>,<union>; 0 = a block per 16 rows of the
+        // bound n, which starts four waves in five for nothing)
         int per_cu[2] = {16, 32};
         if (const char* e_cu = getenv("PYQSM_UNION_BLOCKS_PER_CU")) {
           per_cu[0] = per_cu[1] = atoi(e_cu);
           if (const char* comma = strchr(e_cu, ',')) per_cu[1] = atoi(comma + 1);
         }
-        const int64_t full = ceil_div(rows, 4 * kSubPerWaveDefault);
+        const int64_t full = ceil_div(n, 4 * kSubPerWave);
         const dim3 gh(per_cu[0] > 0 ? std::min<int64_t>(full, int64_t(c->cu_count) * per_cu[0]) : full),
             gu(per_cu[1] > 0 ? std::min<int64_t>(full, int64_t(c->cu_count) * per_cu[1]) : full),
-            gl(ceil_div(rows, 256));
-        int32_t* nbr;  // [m][64] representatives of the neighbour sub-cells pass 1 resolved
-        PQ_TRY(c->arena.get(size_t(rows) * 64, &nbr));
+            gl(ceil_div(n, 256));
+        const bool trace = getenv("PYQSM_DBSCAN_TRACE") != nullptr;
         {
           const StampKernel pk(c, "k_hook_sub", gh.x);
           on_coords(g, [&](auto co) {
-            hipLaunchKernelGGL((k_hook_sub<kSubPerWaveDefault, decltype(co)>), gh, block, 0, c->stream, list, list_xyz,
-                               list_cnt, d_plan, g.start, sub.rec, co, r2, core, parent, nbr, pk.slots);
+            hipLaunchKernelGGL(k_hook_sub<decltype(co)>, gh, block, 0, c->stream, list, list_xyz, list_cnt, d_plan,
+                               g.start, sub.rec, co, r2, core, parent, pk.slots);
           });
         }
-        if (getenv("PYQSM_DBSCAN_TRACE")) {  // how deep are the chains the hook pass leaves?
+        if (trace) {  // how deep are the chains the hook pass leaves?
           int32_t m = 0;
           PQ_HIP(hipMemcpyAsync(&m, list_cnt, 4, hipMemcpyDeviceToHost, c->stream));
           PQ_HIP(hipStreamSynchronize(c->stream));
@@ -1155,16 +1200,29 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
           const char* e = getenv("PYQSM_FLATTEN_JUMP");
           return e ? atoi(e) : 12;
         }();
-        if (jump > 0) hipLaunchKernelGGL(k_flatten_reps, gl, block, 0, c->stream, list, list_cnt, parent, jump);
-        hipLaunchKernelGGL(k_flatten_reps, gl, block, 0, c->stream, list, list_cnt, parent, 0x7fffffff);
-        // what is left: joining the few trees per cluster. Almost every pair of neighbours
-        // now shows the same root through two plain loads.
+        if (jump > 0)
+          hipLaunchKernelGGL(k_flatten_reps, gl, block, 0, c->stream, list, list_cnt, parent, jump,
+                             static_cast<int4*>(nullptr));
+        // (the pass that reaches the roots also writes the cells' summary words)
+        hipLaunchKernelGGL(k_flatten_reps, gl, block, 0, c->stream, list, list_cnt, parent, 0x7fffffff, sub.rec);
+        // what is left: joining the few trees per cluster along their seams
+        unsigned long long* d_seams = nullptr;  // trace only: sub-cells that took the 62-offset path
+        if (trace) {
+          PQ_TRY(c->arena.get(1, &d_seams));
+          PQ_HIP(hipMemsetAsync(d_seams, 0, 8, c->stream));
+        }
         {
           const StampKernel pk(c, "k_union_sub", gu.x);
           on_coords(g, [&](auto co) {
-            hipLaunchKernelGGL((k_union_sub<kSubPerWaveDefault, decltype(co)>), gu, block, 0, c->stream, list, list_cnt,
-                               nbr, sub.sub_of, sub.rec, co, r2, core, parent, pk.slots);
+            hipLaunchKernelGGL(k_union_sub<decltype(co)>, gu, block, 0, c->stream, list, list_xyz, list_cnt, d_plan,
+                               g.start, sub.rec, co, r2, core, parent, d_seams, pk.slots);
           });
+        }
+        if (trace) {
+          unsigned long long h = 0;
+          PQ_HIP(hipMemcpyAsync(&h, d_seams, 8, hipMemcpyDeviceToHost, c->stream));
+          PQ_HIP(hipStreamSynchronize(c->stream));
+          fprintf(stderr, "seam union: %llu sub-cells took the 62-offset path\n", h);
         }
         hipLaunchKernelGGL(k_rep_root, gl, block, 0, c->stream, list, list_cnt, parent, run_min, min_orig, roots,
                            roots_cnt);

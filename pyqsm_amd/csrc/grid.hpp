@@ -250,7 +250,8 @@ struct SubCells {
   int32_t* sub_cnt;  // [8 n]; null from the two-level sort (k_bk_sort), which writes `rec` alone
   int32_t* sub_beg;  // [8 n]; likewise
   int32_t* sub_of;   // [n] sub-cell id of each sorted position
-  int4* rec;         // [8 n] (sub_beg, sub_cnt, -1, 0) in one 16-byte record; .z is the caller's
+  int4* rec;         // [8 n] (sub_beg, sub_cnt, -1, 0) in one 16-byte record; .z and .w are the caller's
+                     // (DBSCAN: .z the sub-cell's representative, .w of a cell's first record the cell's tree)
   // bin_octants_*: four ints the bounding box's fold left zeroed, for the caller's counters
   // (spares DBSCAN two memset launches per step); nullptr from subsort_octants
   // (+ kZeroedExtra more zeroed ints behind the four: DBSCAN's segmented list counters)
