@@ -340,6 +340,36 @@ int pyqsm_radius_reduce(const double* src, int64_t n, const double* qry, int64_t
 int pyqsm_radius_label(const double* src, int64_t n, const double* qry, int64_t m,
                        const int32_t* qry_label, double radius, int32_t k_cap, int32_t* label,
                        int32_t* counts, int32_t device);
+/*
+ * The whole region growing of pyQSM/tree_isolation.py:98-262 (extend_seed_clusters without
+ * order_cutoff) in one call: the source, its grid, the ownership and the frontier stay on the device
+ * for all cycles.
+ *   src f64 [n,3]; owner_in i32 [n]: -1 free, else a cluster index < n_clusters;
+ *   seed_xyz f64 [m,3] with seed_label i32 [m] in [0, n_clusters): the frontier of cycle 0 (the
+ *   seed points need not be source points).
+ * Cycle c: every frontier point of every cluster that is still growing selects its (at most k_cap
+ * nearest) source points with d < radius: the rule of pyqsm_radius_mark to the bit (same grid, d2
+ * expression, strict bound, k-th distance and tie rule). Owned points count towards the k nearest
+ * but are not acquired. A free point selected in cycle c goes to the smallest cluster index among
+ * the clusters that selected it in that cycle: owner_out = that index, cycle_out = c. What a
+ * cluster acquired in a cycle is its next frontier. A cluster stops after a cycle in which it
+ * acquired fewer than min_new points (it keeps them; pyQSM: 5), none included; a cluster without a
+ * seed point never queries. The loop ends after `cycles` cycles, or when no cluster is growing.
+ *   owner_out i32 [n], cycle_out i32 [n]: points never acquired keep owner_in and get cycle -1;
+ *   finished i32 [n_clusters]: -1 if the cluster was still growing when the cycles ran out, else
+ *     the number of cycles in which it queried (0 without a seed point);
+ *   stats i64 [4] (may be NULL): cycles run, frontier queries served, points acquired, the most
+ *     frontier queries served in one cycle.
+ * n == 0, m == 0 or cycles == 0: answered on the host, no device is touched (an empty source
+ * answers the seeds' first cycle with nothing: finished = 1). PYQSM_EINVAL: NULL pointers, a radius
+ * that is not positive and finite, k_cap <= 0, min_new < 1, cycles < 0, an owner_in outside
+ * [-1, n_clusters) or a seed_label outside [0, n_clusters); PYQSM_ERANGE: n or m of 2^31 or more.
+ * Integer atomics only: every run gives the same bits, whatever the order of the seed points.
+ */
+int pyqsm_grow_clusters(const double* src, int64_t n, const int32_t* owner_in, const double* seed_xyz,
+                        const int32_t* seed_label, int64_t m, int32_t n_clusters, double radius,
+                        int32_t k_cap, int32_t cycles, int32_t min_new, int32_t* owner_out,
+                        int32_t* cycle_out, int32_t* finished, int64_t* stats, int32_t device);
 
 /* ---- cluster adjacency ------------------------------------------------------ */
 /*

@@ -67,6 +67,8 @@ SIGNATURES = {
     "pyqsm_ball_query": (ctypes.c_int, [vp, i64, vp, dbl, vp, ctypes.POINTER(i64), i32]),
     "pyqsm_radius_mark": (ctypes.c_int, [vp, i64, vp, i64, dbl, i32, vp, vp, i32]),
     "pyqsm_radius_label": (ctypes.c_int, [vp, i64, vp, i64, vp, dbl, i32, vp, vp, i32]),
+    "pyqsm_grow_clusters": (ctypes.c_int, [vp, i64, vp, vp, vp, i64, i32, dbl, i32, i32, i32, vp, vp, vp, vp,
+                                           i32]),
     "pyqsm_radius_knn": (ctypes.c_int, [vp, i64, vp, i64, dbl, i32, vp, vp, i32]),
     "pyqsm_cluster_adjacency": (ctypes.c_int, [vp, vp, i64, i32, vp, vp, i64, i32, dbl, i32, i64, vp, vp, vp, vp,
                                                vp, vp, ctypes.POINTER(i64), vp, i32]),

@@ -2209,13 +2209,65 @@ int count_occupied(Ctx* c, const DevGrid& g, int64_t* occupied) {
 // The grid of the source points: cells of the radius, over the cloud without its sparse tails (a few
 // stray returns far outside would otherwise inflate the box until the dense grid cannot have cells
 // of the radius any more — every doubling of the edge is 8x the points per cell).
+// build_grid leaves the points of a cell in the order in which its binning's atomics arrived. A radius query
+// that must choose among several points AT its k-th distance takes them in walk order, so that choice would
+// differ from one grid build to the next (the region growing's host loop builds one per cycle). Here every
+// cell's run is put in ascending ORIGINAL index: the stable radix sort (scan.hip, no global atomics) of
+// (cell, index) pairs taken in index order. start and cell_of stay as they are; order and the coordinates
+// are written again.
+__global__ __launch_bounds__(256) void k_canon_keys(int n, const int32_t* __restrict__ order,
+                                                    const int32_t* __restrict__ cell_of, uint32_t* __restrict__ key,
+                                                    int32_t* __restrict__ ident) {
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= n) return;
+  const int i = order[q];
+  key[i] = uint32_t(cell_of[q]);
+  ident[i] = i;
+}
+
+__global__ __launch_bounds__(256) void k_canon_gather(int n, const double* __restrict__ xyz,
+                                                      const int32_t* __restrict__ sorted, int32_t* __restrict__ order,
+                                                      double* __restrict__ sx, double* __restrict__ sy,
+                                                      double* __restrict__ sz, float4* __restrict__ p4) {
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= n) return;
+  const int i = sorted[q];
+  const double x = xyz[3 * size_t(i)], y = xyz[3 * size_t(i) + 1], z = xyz[3 * size_t(i) + 2];
+  order[q] = i;
+  if (p4) {
+    p4[q] = make_float4(float(x), float(y), float(z), 0.0f);  // exact: fp32 records only for fp32-representable clouds
+  } else {
+    sx[q] = x;
+    sy[q] = y;
+    sz[q] = z;
+  }
+}
+
+static int canonical_cell_order(Ctx* c, const double* d_src, int64_t n, DevGrid* g) {
+  uint32_t* key;
+  int32_t* ident;
+  PQ_TRY(c->arena.get(size_t(n), &key));
+  PQ_TRY(c->arena.get(size_t(n), &ident));
+  hipLaunchKernelGGL(k_canon_keys, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, int(n),
+                     static_cast<const int32_t*>(g->order), static_cast<const int32_t*>(g->cell_of), key, ident);
+  PQ_HIP(hipGetLastError());
+  int bits = 1;
+  while (bits < 32 && (int64_t(1) << bits) < g->ncell) ++bits;
+  PQ_TRY(stable_sort_pairs_u32(c, &key, &ident, n, bits));
+  hipLaunchKernelGGL(k_canon_gather, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, int(n), d_src,
+                     static_cast<const int32_t*>(ident), g->order, g->sx, g->sy, g->sz, g->p4);
+  PQ_HIP(hipGetLastError());
+  return 0;
+}
+
 int radius_grid(Ctx* c, const double* d_src, int64_t n, double radius, DevGrid* g) {
   double box[6];
   bool all_f32 = false;  // every source coordinate fp32-representable: 16-byte fp32 records (grid.hpp: on_coords)
   PQ_TRY(cloud_bbox(c, d_src, n, box, box + 3, &all_f32));
   int64_t outside = 0;
   PQ_TRY(robust_box(c, d_src, n, int(std::min<int64_t>(8192, std::max<int64_t>(256, n / 256))), box, &outside));
-  return build_grid(c, d_src, n, radius * (1.0 + 1.0 / 1048576.0), int64_t(1) << 28, g, box, all_f32);
+  PQ_TRY(build_grid(c, d_src, n, radius * (1.0 + 1.0 / 1048576.0), int64_t(1) << 28, g, box, all_f32));
+  return canonical_cell_order(c, d_src, n, g);
 }
 
 // The queries in the order of the source grid's cells (round 3): a lane per query walks ~850 candidates of

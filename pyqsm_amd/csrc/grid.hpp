@@ -323,6 +323,9 @@ int coarsen_grid(Ctx* c, const DevGrid& fine, int64_t n, int factor, DevGrid* co
 // that an inclusive bound stays inside the 27 cells), over the cloud without its sparse tails
 // (cloud_bbox -> robust_box -> build_grid); fp32 records when every coordinate allows. Points the
 // box gave up sit in its outermost cells, and queries find them through clamped_cell.
+// Inside a cell the points are in ascending original index (not in the arrival order build_grid leaves), so
+// the order in which a query walks its candidates, and with it its choice among ties at the k-th distance,
+// is the same for every build over the same cloud.
 int radius_grid(Ctx* c, const double* d_src, int64_t n, double radius, DevGrid* g);
 // *perm = the m query points (f64 [m,3], device) in the order of the grid's cells, or nullptr for
 // fewer than 1024 queries (or PYQSM_RADIUS_SORT=0): serve them in the caller's order.

@@ -416,6 +416,34 @@ def radius_label(src, queries, query_labels, radius: float, k: int = 500, device
     return lab[:s.shape[0]], counts[:q.shape[0]]
 
 
+def grow_clusters(src, owner, seed_points, seed_labels, n_clusters: int, radius: float, k: int = 200,
+                  cycles: int = 150, min_new: int = 5, device: int = 0):
+    """The region growing of ``tree_isolation.extend_seed_clusters`` in one device-resident call
+    (``pyqsm_grow_clusters``). ``owner`` int32 [n]: -1 free, else a cluster index; ``seed_points``
+    [m,3] with ``seed_labels`` [m]: the frontier of cycle 0. Returns ``(owner int32 [n], cycle
+    int32 [n], finished int32 [n_clusters], stats int64 [4])``: the cluster of every point, the
+    cycle it was acquired in (-1: never), per cluster the cycles it queried in (-1: still growing
+    when ``cycles`` ran out), and (cycles run, frontier queries served, points acquired, most
+    queries in one cycle)."""
+    s = _points(src)
+    q = _points(seed_points)
+    own = np.ascontiguousarray(owner, dtype=np.int32).reshape(-1)
+    ql = np.ascontiguousarray(seed_labels, dtype=np.int32).reshape(-1)
+    if own.shape[0] != s.shape[0]:
+        raise ValueError("one owner per source point")
+    if ql.shape[0] != q.shape[0]:
+        raise ValueError("one label per seed point")
+    n, nc = s.shape[0], int(n_clusters)
+    owner_out = np.empty(max(n, 1), dtype=np.int32)
+    cycle_out = np.empty(max(n, 1), dtype=np.int32)
+    finished = np.empty(max(nc, 1), dtype=np.int32)
+    stats = np.zeros(4, dtype=np.int64)
+    check(_lib.load().pyqsm_grow_clusters(_p(s), n, _p(own), _p(q), _p(ql), q.shape[0], nc, float(radius),
+                                          int(k), int(cycles), int(min_new), _p(owner_out), _p(cycle_out),
+                                          _p(finished), _p(stats), int(device)))
+    return owner_out[:n], cycle_out[:n], finished[:max(nc, 0)], stats
+
+
 def radius_knn(src, queries, radius: float, k: int = 500, device: int = 0):
     """(dist f64 [m,k], idx int64 [m,k]) like ``cKDTree(src).query(queries, k,
     distance_upper_bound=radius)``: ascending by (distance, index), padded with inf / n."""

@@ -7,6 +7,9 @@ keyed by coordinate tuples. Here one cycle is ONE GPU call for all clusters toge
 (``pyqsm_radius_label``: every source point gets the smallest cluster index among the
 frontier points that select it — exactly what visiting the clusters in index order and
 letting the first one keep a free point produces), and ownership is an int32 array.
+``grow_seed_clusters`` / ``engine="device"`` go one step further: all cycles are ONE GPU call
+(``pyqsm_grow_clusters``) in which the cloud, its grid, the ownership and the frontier never
+leave the device.
 
 Not restated: the TensorBoard / drawing / pickling side effects, the ``breakpoint()``s and
 the ``input()`` prompt of the reference.
@@ -64,9 +67,118 @@ def _rows_in(a: np.ndarray, b: np.ndarray) -> np.ndarray:
     return np.where(hit, order[pos], -1)
 
 
+def _prepare_growth(clusters_and_idxs, src_pcd, k, max_distance, exclude_pcd, exclude_pts, device):
+    """What both engines of the region growing start from (tree_isolation.py:98-133): the seeds as
+    ``[(label, float64 [m,3])]``, the source points without the exclusion zone, and the ownership
+    array with the seed points that are source points already assigned."""
+    seeds = [(label, as_points(cl)) for label, cl in clusters_and_idxs]
+    src_pts = as_points(src_pcd)
+    if exclude_pts is None and exclude_pcd is not None:
+        exclude_pts = as_points(exclude_pcd)
+    if exclude_pts is not None and len(exclude_pts) and len(src_pts):      # :120-133
+        mask, _ = hip.radius_mark(src_pts, as_points(exclude_pts), max_distance, k=k, device=device)
+        src_pts = src_pts[~mask.astype(bool)]
+    owner = np.full(len(src_pts), -1, dtype=np.int32)
+    # points of the source that ARE seed points already carry their cluster (dict lookup
+    # by coordinates in the reference); later seeds overwrite earlier ones, as there
+    for idc, (_, pts) in enumerate(seeds):
+        hit = _rows_in(src_pts, pts) >= 0
+        owner[hit] = idc
+    return seeds, src_pts, owner
+
+
+def growth_indices(owner, cycle, n_clusters):
+    """Per cluster, the source indices it acquired: by cycle, then ascending (the order in which the
+    host loop collects them). ``owner`` / ``cycle`` as ``hip.grow_clusters`` returns them. One
+    ``np.lexsort`` for all clusters."""
+    owner = np.asarray(owner)
+    cycle = np.asarray(cycle)
+    sel = np.flatnonzero(cycle >= 0)
+    sel = sel[np.lexsort((sel, cycle[sel], owner[sel]))]
+    cuts = np.searchsorted(owner[sel], np.arange(int(n_clusters) + 1))
+    return [sel[cuts[i]:cuts[i + 1]] for i in range(int(n_clusters))]
+
+
+def growth_clouds(seeds, src_pts, owner, cycle):
+    """The clouds ``extend_seed_clusters`` returns, from the arrays of ``hip.grow_clusters``: what
+    the reference's dict keyed by coordinate tuples holds after the loop (``labeled_pts_to_lists``).
+    Seed points enter cluster by cluster (a later seed overwrites the cluster of an equal point but
+    not its place), then the acquired points cycle by cycle, cluster by cluster, ascending, each
+    only if its coordinates are not in the dict yet. One cloud per label, in the order in which
+    the labels first appear. No GPU work."""
+    src_pts = np.asarray(src_pts, dtype=np.float64).reshape(-1, 3)
+    owner = np.asarray(owner)
+    cycle = np.asarray(cycle)
+    seed_pts = [np.asarray(pts, dtype=np.float64).reshape(-1, 3) for _, pts in seeds]
+    seed_idc = [np.full(len(pts), idc, dtype=np.int64) for idc, pts in enumerate(seed_pts)]
+    sel = np.flatnonzero(cycle >= 0)
+    sel = sel[np.lexsort((sel, owner[sel], cycle[sel]))]
+    pts = np.concatenate(seed_pts + [src_pts[sel]])
+    idc = np.concatenate(seed_idc + [owner[sel].astype(np.int64)])
+    if len(pts) == 0:
+        return []
+    ns = len(pts) - len(sel)
+    _, first, inv = np.unique(pts, axis=0, return_index=True, return_inverse=True)
+    inv = inv.reshape(-1)
+    val = idc[first]                                   # acquired points: the first entry keeps the key
+    last_seed = np.full(len(first), -1, dtype=np.int64)
+    np.maximum.at(last_seed, inv[:ns], np.arange(ns))  # seed points: the last entry sets the value
+    val = np.where(last_seed >= 0, idc[np.maximum(last_seed, 0)], val)
+    keys = np.argsort(first, kind="stable")            # the dict's order: first insertion
+    key_pts, key_val = pts[first[keys]], val[keys]
+    group_of_label, group = {}, np.empty(len(seeds), dtype=np.int64)
+    for i, (label, _) in enumerate(seeds):
+        group[i] = group_of_label.setdefault(label, len(group_of_label))
+    gid = group[key_val]
+    present, first_g = np.unique(gid, return_index=True)
+    by_group = np.argsort(gid, kind="stable")
+    cuts = np.searchsorted(gid[by_group], np.arange(len(group_of_label) + 1))
+    return [PointCloud(key_pts[by_group[cuts[g]:cuts[g + 1]]]) for g in present[np.argsort(first_g, kind="stable")]]
+
+
+class SeedGrowth:
+    """What ``grow_seed_clusters`` returns: the arrays of one ``hip.grow_clusters`` call and the
+    views of them the callers of ``extend_seed_clusters`` use."""
+
+    def __init__(self, seeds, src_points, owner, cycle, finished, stats):
+        self._seeds = seeds
+        self.labels = [label for label, _ in seeds]
+        self.src_points = src_points
+        self.owner = owner
+        self.cycle = cycle
+        self.finished = finished
+        self.stats = stats
+        self._indices = None
+
+    def indices(self, i):
+        """Source indices (rows of ``src_points``) cluster ``i`` acquired: by cycle, then ascending."""
+        if self._indices is None:
+            self._indices = growth_indices(self.owner, self.cycle, len(self.labels))
+        return self._indices[i]
+
+    def clouds(self):
+        """One ``PointCloud`` per label, as ``extend_seed_clusters`` returns them."""
+        return growth_clouds(self._seeds, self.src_points, self.owner, self.cycle)
+
+
+def grow_seed_clusters(clusters_and_idxs, src_pcd, k=200, max_distance=.1, cycles=150, exclude_pcd=None,
+                       exclude_pts=None, device: int = 0):
+    """The region growing of ``extend_seed_clusters`` (no ``order_cutoff``) with the loop on the
+    device: the same preparation, then ONE ``hip.grow_clusters`` call in which the cloud, its grid,
+    the ownership and the frontier stay in HBM for all cycles. Returns a :class:`SeedGrowth`."""
+    seeds, src_pts, owner = _prepare_growth(clusters_and_idxs, src_pcd, k, max_distance, exclude_pcd,
+                                            exclude_pts, device)
+    q = np.concatenate([pts for _, pts in seeds]) if seeds else np.zeros((0, 3))
+    ql = (np.concatenate([np.full(len(pts), i, dtype=np.int32) for i, (_, pts) in enumerate(seeds)])
+          if seeds else np.zeros(0, dtype=np.int32))
+    own, cyc, fin, stats = hip.grow_clusters(src_pts, owner, q, ql, len(seeds), max_distance, k=k,
+                                             cycles=cycles, min_new=5, device=device)
+    return SeedGrowth(seeds, src_pts, own, cyc, fin, stats)
+
+
 def extend_seed_clusters(clusters_and_idxs, src_pcd, file_label="", k=200, max_distance=.1,
                          cycles=150, save_every=10, draw_every=10, tb_every=10, order_cutoff=None,
-                         exclude_pcd=None, exclude_pts=None, device: int = 0):
+                         exclude_pcd=None, exclude_pts=None, device: int = 0, engine: str = "host"):
     """tree_isolation.py:63-283. ``clusters_and_idxs`` is ``[(label, cluster), ...]``
     (clouds or point arrays); ``src_pcd`` the cloud to grow through. Every cycle, every
     unfinished cluster collects the (up to ``k`` nearest) source points within
@@ -80,22 +192,25 @@ def extend_seed_clusters(clusters_and_idxs, src_pcd, file_label="", k=200, max_d
     order of the reference's dict: seeds first, then by cycle) and, per cluster, the source
     indices it acquired (the reference extends one list shared by all clusters there — an
     aliasing slip of ``[[]] * n`` — and its callers ignore the value). ``save_every``,
-    ``draw_every`` and ``tb_every`` are accepted and ignored."""
-    seeds = [(label, as_points(cl)) for label, cl in clusters_and_idxs]
+    ``draw_every`` and ``tb_every`` are accepted and ignored.
+
+    ``engine``: ``"host"`` runs the cycles as a host loop around one ``hip.radius_label`` call
+    each; ``"device"`` runs them in one ``hip.grow_clusters`` call (``grow_seed_clusters``) and
+    returns the same clouds and index lists. ``order_cutoff`` clusters every neighbourhood on the
+    way and exists on the host loop only."""
+    if engine not in ("host", "device"):
+        raise ValueError(f"engine must be 'host' or 'device', got {engine!r}")
+    if engine == "device":
+        if order_cutoff:
+            raise ValueError("engine='device' does not take order_cutoff: that loop runs DBSCAN on every "
+                             "neighbourhood and stays on the host")
+        res = grow_seed_clusters(clusters_and_idxs, src_pcd, k=k, max_distance=max_distance, cycles=cycles,
+                                 exclude_pcd=exclude_pcd, exclude_pts=exclude_pts, device=device)
+        return res.clouds(), [res.indices(i).tolist() for i in range(len(res.labels))]
+    seeds, src_pts, owner = _prepare_growth(clusters_and_idxs, src_pcd, k, max_distance, exclude_pcd,
+                                            exclude_pts, device)
     n_cl = len(seeds)
-    src_pts = as_points(src_pcd)
-    if exclude_pts is None and exclude_pcd is not None:
-        exclude_pts = as_points(exclude_pcd)
-    if exclude_pts is not None and len(exclude_pts) and len(src_pts):      # :120-133
-        mask, _ = hip.radius_mark(src_pts, as_points(exclude_pts), max_distance, k=k, device=device)
-        src_pts = src_pts[~mask.astype(bool)]
     n = len(src_pts)
-    owner = np.full(n, -1, dtype=np.int32)
-    # points of the source that ARE seed points already carry their cluster (dict lookup
-    # by coordinates in the reference); later seeds overwrite earlier ones, as there
-    for idc, (_, pts) in enumerate(seeds):
-        hit = _rows_in(src_pts, pts) >= 0
-        owner[hit] = idc
     frontier = [pts for _, pts in seeds]
     grown = [[] for _ in range(n_cl)]          # source indices per cluster, in order of acquisition
     complete = np.zeros(n_cl, dtype=bool)
