@@ -194,6 +194,8 @@ __global__ __launch_bounds__(256) void k_core_tiled(int n, const GridPlan* __res
 // The 27-cell stencil of one point as ONE sequence of candidates: the nine runs' bounds are loaded side
 // by side (they used to be fetched row by row, a dependent round trip each before the row's candidates
 // could be asked for), and candidate g of the sequence is found by a chain of selects. Wave-uniform.
+// The runs come in kRunOrder, centre row first, as k_core_tiled visits them: a point's near neighbours
+// are among the first candidates, so a walk that stops at min_pts (k_core_rest) stops steps earlier.
 struct Runs9 {
   int qb[9];
   int pre[10];  // pre[r] = candidates before run r, pre[9] = all
@@ -209,7 +211,7 @@ __device__ __forceinline__ Runs9 stencil_runs(int c, Stencil st, const int32_t* 
   int qe[9];
 #pragma unroll
   for (int r = 0; r < 9; ++r) {
-    const int row = c + (r % 3 - 1) * st.nx + (r / 3 - 1) * st.nxy;
+    const int row = c + (kRunOrder[r] % 3 - 1) * st.nx + (kRunOrder[r] / 3 - 1) * st.nxy;
     t.qb[r] = start[row - 1];
     qe[r] = start[row + 2];
   }
@@ -806,6 +808,61 @@ __device__ __forceinline__ void block_append(bool take, int value, int32_t* __re
   if (take) list[wbase[w] + __popcll(b & ((1ull << lane) - 1ull))] = value;
 }
 
+// The list of the non-core points for the label pass (`rest`, reused from the core pass: after k_core_rest),
+// from the final core flags. Block b of the role takes the sorted positions [b * kFlagsPerBlock,
+// (b + 1) * kFlagsPerBlock), sixteen per thread, their loads side by side, and appends its non-core ones with ONE
+// atomic as block_append does (the counter is one address and its atomics are served one at a time, so few
+// large blocks). Every thread of a block of kFlagsThreads calls it; it runs as extra blocks of a launch of the
+// union phase whose own blocks leave most wave slots empty (k_rep_root).
+static constexpr int kFlagsThreads = 256, kFlagsPer = 16, kFlagsPerBlock = kFlagsThreads * kFlagsPer;
+__device__ __forceinline__ void flags_role(int b, int n, const uint8_t* __restrict__ core,
+                                           int32_t* __restrict__ rest, int32_t* __restrict__ rest_cnt) {
+  constexpr int kWaves = kFlagsThreads / 64;
+  __shared__ int fcount[kWaves], fbase[kWaves];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int p0 = b * kFlagsPerBlock + threadIdx.x;
+  unsigned take = 0;  // bit k: position p0 + k * kFlagsThreads is a non-core point
+#pragma unroll
+  for (int k = 0; k < kFlagsPer; ++k) {
+    const int p = p0 + k * kFlagsThreads;
+    take |= unsigned(p < n && !core[p]) << k;
+  }
+  // the wave's count by a butterfly: sixteen ballots kept across the barriers cost the launch a wave per SIMD in
+  // scalar registers
+  int mine = __popc(take);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
+  if (lane == 0) fcount[w] = mine;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int tot = 0;
+    for (int k = 0; k < kWaves; ++k) tot += fcount[k];
+    int base = tot ? atomicAdd(rest_cnt, tot) : 0;
+    for (int k = 0; k < kWaves; ++k) {
+      fbase[k] = base;
+      base += fcount[k];
+    }
+  }
+  __syncthreads();
+  int at = fbase[w];
+#pragma unroll
+  for (int k = 0; k < kFlagsPer; ++k) {
+    const bool t = (take >> k) & 1u;
+    const unsigned long long bal = __ballot(t);
+    if (t) rest[at + __popcll(bal & ((1ull << lane) - 1ull))] = p0 + k * kFlagsThreads;
+    at += __popcll(bal);
+  }
+}
+
+// The same as a launch of its own: the per-point union-find's path.
+__global__ __launch_bounds__(kFlagsThreads) void k_noncore_list(int n, const uint8_t* __restrict__ core,
+                                                                int32_t* __restrict__ rest,
+                                                                int32_t* __restrict__ rest_cnt,
+                                                                const GridPlan* __restrict__ plan) {
+  if (!plan->ok) return;  // block-uniform
+  flags_role(blockIdx.x, n, core, rest, rest_cnt);
+}
+
 // k_flatten ran: parent[p] is the root. Folds the components' smallest original indices and lists the roots.
 __global__ __launch_bounds__(256) void k_point_min(int n, const uint8_t* __restrict__ core,
                                                    const int* __restrict__ parent,
@@ -828,15 +885,28 @@ __global__ __launch_bounds__(256) void k_point_min(int n, const uint8_t* __restr
 // Each representative also points straight at its root, and the roots are listed: the unions only ever
 // rewrote representatives' pointers, so every core point now reaches its root in two hops
 // (point -> representative -> root) and no pass over all points is needed to flatten them.
-__global__ __launch_bounds__(256) void k_rep_root(const int4* __restrict__ list,
+// (Blocks of kRepRootThreads: the flags blocks behind the representatives' run flags_role, which needs its own size.)
+static constexpr int kRepRootThreads = kFlagsThreads;
+static_assert(kRepRootThreads == 256, "gl, the grid of the representatives' blocks, is cut in 256s");
+__global__ __launch_bounds__(kRepRootThreads) void k_rep_root(const int4* __restrict__ list,
                                                   const int32_t* __restrict__ m_ptr,
                                                   int* __restrict__ parent,
                                                   const int* __restrict__ run_min,
                                                   int* __restrict__ min_orig,
                                                   int32_t* __restrict__ roots,
-                                                  int32_t* __restrict__ roots_cnt) {
+                                                  int32_t* __restrict__ roots_cnt, int rep_blocks, int n,
+                                                  const uint8_t* __restrict__ core, int32_t* __restrict__ rest,
+                                                  int32_t* __restrict__ rest_cnt,
+                                                  const GridPlan* __restrict__ plan) {
+  // Two roles, by block index and independent of each other. The representatives' blocks come first, so that
+  // their chains of dependent loads start at once (some 3 k waves with work on a chip of 8 k slots); the
+  // blocks behind them do the flags role in the slots those leave empty.
+  if (int(blockIdx.x) >= rep_blocks) {
+    if (plan->ok) flags_role(blockIdx.x - rep_blocks, n, core, rest, rest_cnt);
+    return;
+  }
   const int m = *m_ptr;
-  int s = blockIdx.x * 256 + threadIdx.x;
+  int s = blockIdx.x * kRepRootThreads + threadIdx.x;
   const bool active = s < m;
   int p = -1, r = -1, v = 0x7FFFFFFF;
   if (active) {
@@ -982,63 +1052,53 @@ __device__ __forceinline__ int cluster_number(int v, int n_roots, const uint32_t
   return wpre[v >> 5] + __popc(bits[v >> 5] & ((1u << (v & 31)) - 1u));
 }
 
-// Labels of the core points; the others (noise and border candidates, a few percent) are
-// listed for k_labels_border. (Walking the stencil per lane here made those few points the
-// tail of the kernel: ~850 dependent gathers each.)
-__global__ __launch_bounds__(1024) void k_labels(int n, const uint8_t* __restrict__ core,
-                                                 const int* __restrict__ parent,
-                                                 const int* __restrict__ min_orig,
-                                                 const int32_t* __restrict__ roots_cnt,
-                                                 const uint32_t* __restrict__ bits,
-                                                 const int32_t* __restrict__ wpre,
-                                                 const int32_t* __restrict__ order,
-                                                 int64_t* __restrict__ labels,
-                                                 uint8_t* __restrict__ is_core,
-                                                 int32_t* __restrict__ rest,
-                                                 int32_t* __restrict__ rest_cnt, const GridPlan* __restrict__ plan,
+// The label pass, two roles in one launch. Core points copy their cluster number (point -> representative ->
+// root): a thread each, one scattered store, and every point's core flag goes out in the caller's order beside
+// it. Then every wave takes the entries wave, wave + waves of the grid, ... of the list of non-core points
+// (flags_role): a WAVE per point, the smallest cluster number among the core neighbours in its stencil, or -1.
+// The roles do not wait on each other and cannot race: the first writes the labels of core points only, the
+// second those of non-core points only, and both only read core / parent / min_orig. (DESIGN section 4 has the
+// forms measured and dropped.)
+static constexpr int kLabelThreads = 256;
+template <class CO>
+__global__ __launch_bounds__(kLabelThreads) void k_labels(int n, const int32_t* __restrict__ rest,
+                                                          const int32_t* __restrict__ rest_cnt,
+                                                          const GridPlan* __restrict__ plan,
+                                                          const int32_t* __restrict__ start,
+                                                          const int32_t* __restrict__ cell_of, CO co, double r2,
+                                                          const uint8_t* __restrict__ core,
+                                                          const int* __restrict__ parent,
+                                                          const int* __restrict__ min_orig,
+                                                          const int32_t* __restrict__ roots_cnt,
+                                                          const uint32_t* __restrict__ bits,
+                                                          const int32_t* __restrict__ wpre,
+                                                          const int32_t* __restrict__ order,
+                                                          int64_t* __restrict__ labels,
+                                                          uint8_t* __restrict__ is_core,
     unsigned long long* __restrict__ st /*stamps or null*/) {
   stamped(st, [&] {
   if (!plan->ok) return;  // block-uniform
-  int p = blockIdx.x * 1024 + threadIdx.x;
-  const bool live = p < n;
-  const bool is_c = live && core[p];
-  if (is_c) {
-    const int v = min_orig[parent[parent[p]]];  // point -> representative -> root
-    labels[order[p]] = int64_t(cluster_number(v, *roots_cnt, bits, wpre));
-  }
-  if (live && is_core) is_core[order[p]] = is_c;
-  block_append<1024>(live && !is_c, p, rest, rest_cnt);
-  });
-}
-
-// One WAVE per non-core point: smallest cluster number among its core neighbours, or -1.
-template <class CO>
-__global__ __launch_bounds__(256) void k_labels_border(const int32_t* __restrict__ rest,
-                                                       const int32_t* __restrict__ rest_cnt,
-                                                       const GridPlan* __restrict__ plan,
-                                                       const int32_t* __restrict__ start,
-                                                       const int32_t* __restrict__ cell_of, CO co, double r2,
-                                                       const uint8_t* __restrict__ core,
-                                                       const int* __restrict__ parent,
-                                                       const int* __restrict__ min_orig,
-                                                       const int32_t* __restrict__ roots_cnt,
-                                                       const uint32_t* __restrict__ bits,
-                                                       const int32_t* __restrict__ wpre,
-                                                       const int32_t* __restrict__ order,
-                                                       int64_t* __restrict__ labels,
-    unsigned long long* __restrict__ st /*stamps or null*/) {
-  stamped(st, [&] {
-  if (!plan->ok) return;
-  const Stencil st = plan_stencil(plan);
-  const int m = *rest_cnt;
+  constexpr int kWaves = kLabelThreads / 64;
   const int n_roots = *roots_cnt;
   const int lane = threadIdx.x & 63;
-  for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < m; i += gridDim.x * 4) {  // wave-uniform
+  {
+    const int p = blockIdx.x * kLabelThreads + threadIdx.x;
+    const bool is_c = p < n && core[p];
+    if (is_c) {
+      const int v = min_orig[parent[parent[p]]];
+      labels[order[p]] = int64_t(cluster_number(v, n_roots, bits, wpre));
+    }
+    if (p < n && is_core) is_core[order[p]] = is_c;
+  }
+  const int m = *rest_cnt;
+  const Stencil sten = plan_stencil(plan);
+  const int first = blockIdx.x * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (int i = first; i < m; i += gridDim.x * kWaves) {  // wave-uniform
     const int p = rest[i];
     double x, y, z;
     co.get(p, x, y, z);
     const int c = __builtin_amdgcn_readfirstlane(cell_of[p]);
-    const Runs9 t = stencil_runs(c, st, start);
+    const Runs9 t = stencil_runs(c, sten, start);
     int best = kNoRoot;
     for (int g0 = 0; g0 < t.pre[9]; g0 += 64) {
       const int g = g0 + lane;
@@ -1138,9 +1198,18 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
                          g.cell_of, co, r2, min_pts, core, st_rest);
     });
     PQ_HIP(hipGetLastError());
+    if (getenv("PYQSM_DBSCAN_TRACE")) {  // how many points did the tiled pass hand on?
+      int32_t h[kRestSegs];
+      PQ_HIP(hipMemcpyAsync(h, rest_segs, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+      PQ_HIP(hipStreamSynchronize(c->stream));
+      long long tot = 0;
+      for (int32_t v : h) tot += v;
+      fprintf(stderr, "core pass: %lld stragglers\n", tot);
+    }
   }
   {
     StampScope ps(c, "dbscan_union");
+    const dim3 gf(ceil_div(n, kFlagsPerBlock));  // blocks of flags_role
     // (parent / min_orig / flag were initialised by k_core_tiled; list_cnt[0..2] are still the zeros the
     // binning left)
     if (fine) {
@@ -1224,8 +1293,9 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
           PQ_HIP(hipStreamSynchronize(c->stream));
           fprintf(stderr, "seam union: %llu sub-cells took the 62-offset path\n", h);
         }
-        hipLaunchKernelGGL(k_rep_root, gl, block, 0, c->stream, list, list_cnt, parent, run_min, min_orig, roots,
-                           roots_cnt);
+        // (with the label pass's list of non-core points behind its own blocks: flags_role)
+        hipLaunchKernelGGL(k_rep_root, dim3(gl.x + gf.x), dim3(kRepRootThreads), 0, c->stream, list, list_cnt, parent,
+                           run_min, min_orig, roots, roots_cnt, int(gl.x), N, core, rest, list_cnt + 3, d_plan);
       }
       PQ_HIP(hipGetLastError());
     } else {
@@ -1237,6 +1307,8 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
       hipLaunchKernelGGL(k_flatten, grid, block, 0, c->stream, N, core, parent, d_plan);
       hipLaunchKernelGGL(k_point_min, grid, block, 0, c->stream, N, core, parent, g.order, min_orig, roots,
                          roots_cnt, d_plan);
+      hipLaunchKernelGGL(k_noncore_list, gf, dim3(kFlagsThreads), 0, c->stream, N, core, rest,
+                         list_cnt + 3, d_plan);
     }
     // one workgroup numbers up to kRankCap clusters; more take the bitmap, a block per CU at most
     const dim3 gn(std::min<int64_t>(ceil_div(n, kNumberThreads), c->cu_count));
@@ -1246,16 +1318,20 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
   }
   {
     StampScope ps(c, "dbscan_label");
-    hipLaunchKernelGGL(k_labels, dim3(ceil_div(n, 1024)), dim3(1024), 0, c->stream, N, core, parent, min_orig,
-                       roots_cnt, bits, wpre, g.order, labels, is_core, rest, list_cnt + 3, d_plan,
-                       stamp_slots(c, ceil_div(n, 1024)));
-    const dim3 gb(std::min<int64_t>(8192, ceil_div(n, 64)));
-    unsigned long long* const st_border = stamp_slots(c, gb.x);
+    const dim3 gb(ceil_div(n, kLabelThreads));
+    unsigned long long* const st_labels = stamp_slots(c, gb.x);
     on_coords(g, [&](auto co) {
-      hipLaunchKernelGGL(k_labels_border<decltype(co)>, gb, block, 0, c->stream, rest, list_cnt + 3, d_plan, g.start,
-                         g.cell_of, co, r2, core, parent, min_orig, roots_cnt, bits, wpre, g.order, labels, st_border);
+      hipLaunchKernelGGL(k_labels<decltype(co)>, gb, dim3(kLabelThreads), 0, c->stream, N, rest, list_cnt + 3, d_plan,
+                         g.start, g.cell_of, co, r2, core, parent, min_orig, roots_cnt, bits, wpre, g.order, labels,
+                         is_core, st_labels);
     });
     PQ_HIP(hipGetLastError());
+    if (getenv("PYQSM_DBSCAN_TRACE")) {
+      int32_t h = 0;
+      PQ_HIP(hipMemcpyAsync(&h, list_cnt + 3, 4, hipMemcpyDeviceToHost, c->stream));
+      PQ_HIP(hipStreamSynchronize(c->stream));
+      fprintf(stderr, "label pass: %d non-core points listed\n", h);
+    }
   }
   *count_out = roots_cnt;
   return 0;

@@ -1,5 +1,5 @@
 """dev aid: kernel sequence of the last DBSCAN call in a rocprofv3 --kernel-trace CSV, then the median
-duration of every kernel of a step and of the gap before it over all traced steps but the first `skip`
+duration (with its smallest and largest value) of every kernel of a step and the median gap before it over all traced steps but the first `skip`
 (python tools/kernel_timeline.py <dir>/<name>_kernel_trace.csv [first_kernel [count [skip]]])"""
 import csv
 import statistics
@@ -43,6 +43,6 @@ for s, b0 in enumerate(begins):
         prev_end = e
 print('# median kernel duration and gap before it over steps %d..%d' % (skip + 1, len(begins)))
 for key in order:
-    print('%-36s %8.2f us  (n=%d)  median gap before %5.1f us' % (key[:36], statistics.median(dur[key]), len(dur[key]),
-                                                                  statistics.median(gaps[key])))
+    print('%-36s %8.2f us  (n=%d, %.2f .. %.2f)  median gap before %5.1f us' % (
+        key[:36], statistics.median(dur[key]), len(dur[key]), min(dur[key]), max(dur[key]), statistics.median(gaps[key])))
 print('# sum of the median durations %.1f us' % sum(statistics.median(v) for v in dur.values()))
