@@ -404,6 +404,37 @@ int pyqsm_cluster_adjacency(const double* src, const int32_t* src_label, int64_t
                             double* min_d2, int64_t* pairs, int64_t* src_idx, int64_t* tgt_idx, int64_t* count,
                             int64_t* stats, int32_t device);
 
+/* ---- projected area: the exact 2-D alpha shape of lattice points --------------- */
+/*
+ * For every segment (an independent cloud) of integer lattice points the total area of the cells of
+ * its Delaunay subdivision whose circumradius^2 <= a2 (cocircular points form one cell, so the
+ * subdivision is unique): what delaunay_2d(alpha).area approximates in pyQSM's
+ * viz/ray_casting.py project_pcd, computed with integer predicates only.
+ *   ij i32 [n,2] lattice coordinates; seg_start i64 [n_seg + 1], ascending from 0 to n: points of
+ *   different segments never meet. a2: alpha^2 in lattice units^2, inclusive bound. Coincident
+ *   points of a segment are merged: the lowest index takes part.
+ *   twice_area i64 [n_seg]: twice the area in lattice units^2; n_live i64 [n_seg]: points after
+ *   merging; n_boundary i64 [n_seg]: directed boundary edges (kept cell on the left, none on the right).
+ * flags: PYQSM_ALPHA_BOUNDARY  *edges receives the boundary edges of all segments, i64 [sum of
+ *          n_boundary, 2] pairs of indices into ij, grouped by segment in segment order, ascending by
+ *          (a, b) inside one; allocated by the library, released with pyqsm_free; NULL when there is
+ *          none (edges itself may be NULL without the flag).
+ * max_tests: the call is refused with PYQSM_ERANGE, before the edge pass, when the estimated number
+ *   of point-against-edge tests, the sum over the points of (points in the 3 x 3 cell stencil)^2,
+ *   exceeds it; <= 0: PYQSM_ALPHA_DEFAULT_MAX_TESTS, ten seconds at the 4.0e11 tests per second measured on
+ *   one MI355X; the executed tests never exceed the estimate.
+ * stats i64 [5] or NULL: estimated tests, executed tests, comparisons decided by the 128-bit
+ *   fallback, directed edges within reach, merged duplicates.
+ * A segment with fewer than three distinct points, or with all points on one line, has area 0 and
+ * no boundary; when every segment is like that no device is touched. The extent of a segment above
+ * 2^20 lattice units on an axis, a2 above 2^40, a seg_start that does not run from 0 to n: PYQSM_EINVAL.
+ */
+#define PYQSM_ALPHA_BOUNDARY 1
+#define PYQSM_ALPHA_DEFAULT_MAX_TESTS 4000000000000LL
+int pyqsm_alpha_area(const int32_t* ij, int64_t n, const int64_t* seg_start, int64_t n_seg, uint64_t a2,
+                     int64_t max_tests, int32_t flags, int64_t* twice_area, int64_t* n_live, int64_t* n_boundary,
+                     int64_t** edges, int64_t* stats, int32_t device);
+
 /* ---- farthest-point down-sampling ---------------------------------------- */
 /*
  * Stands in for open3d PointCloud.farthest_point_down_sample(num_samples) as

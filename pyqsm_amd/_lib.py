@@ -72,6 +72,8 @@ SIGNATURES = {
     "pyqsm_radius_knn": (ctypes.c_int, [vp, i64, vp, i64, dbl, i32, vp, vp, i32]),
     "pyqsm_cluster_adjacency": (ctypes.c_int, [vp, vp, i64, i32, vp, vp, i64, i32, dbl, i32, i64, vp, vp, vp, vp,
                                                vp, vp, ctypes.POINTER(i64), vp, i32]),
+    "pyqsm_alpha_area": (ctypes.c_int, [vp, i64, vp, i64, ctypes.c_uint64, i64, i32, vp, vp, vp,
+                                        ctypes.POINTER(vp), vp, i32]),
     "pyqsm_fps": (ctypes.c_int, [vp, i64, i64, i64, vp, i32]),
     "pyqsm_pc_laplacian": (ctypes.c_int, [vp, i64, i32, dbl, ctypes.POINTER(i64),
                                           ctypes.POINTER(vp), ctypes.POINTER(vp),

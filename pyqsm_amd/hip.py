@@ -572,6 +572,73 @@ def cluster_adjacency(points, labels, threshold: float, targets=None, target_lab
     return ClusterAdjacency(s_vals[cat[0]], t_vals[cat[1]], np.sqrt(cat[2]), cat[3], cat[4], cat[5])
 
 
+# ---------------------------------------------------------------- projected area (alpha shape)
+
+ALPHA_BOUNDARY = 1
+ALPHA_MAX_EXTENT = 1 << 20      # lattice units per axis within a segment
+ALPHA_MAX_A2 = 1 << 40
+
+
+class AlphaArea(NamedTuple):
+    """Per-segment results of :func:`alpha_area`."""
+    twice_area: np.ndarray            # int64 [n_seg] twice the area, lattice units^2
+    n_live: np.ndarray                # int64 [n_seg] points after merging coincident ones
+    n_boundary: np.ndarray            # int64 [n_seg] directed boundary edges
+    edges: np.ndarray | None          # int64 [sum n_boundary, 2] (return_boundary=True)
+    edge_start: np.ndarray | None     # int64 [n_seg + 1] rows of `edges` per segment
+    stats: dict
+
+    def boundary(self, i: int) -> np.ndarray:
+        """The boundary edges of segment i: int64 [r, 2] pairs of indices into the call's points,
+        kept side on the left, ascending by (a, b)."""
+        if self.edges is None:
+            raise ValueError("alpha_area was called without return_boundary=True")
+        return self.edges[self.edge_start[i]:self.edge_start[i + 1]]
+
+
+def alpha_area(ij, a2: int, seg_start=None, return_boundary: bool = False, max_tests: int | None = None,
+               device: int = 0) -> AlphaArea:
+    """Twice the exact alpha-shape area of integer lattice points, per segment: the total area of
+    the cells of the Delaunay subdivision with circumradius^2 <= ``a2`` (inclusive), decided by
+    integer predicates only. ``ij`` int32 [n, 2]; ``seg_start`` [n_seg + 1] splits it into
+    independent clouds (default: one). Coincident points are merged, the lowest index takes part.
+    A segment may span at most 2^20 lattice units per axis and ``a2`` at most 2^40.
+    ``max_tests`` (default: about ten seconds of one MI355X) refuses a call whose estimated
+    point-against-edge tests exceed it, before the edge pass runs."""
+    pts = np.asarray(ij)
+    if pts.ndim != 2 or pts.shape[1] != 2:
+        raise ValueError(f"expected lattice points of shape [n,2], got {pts.shape}")
+    if pts.size and not np.issubdtype(pts.dtype, np.integer):
+        raise ValueError("lattice points must be integers")
+    if pts.size and (pts.min() < -(1 << 31) or pts.max() >= (1 << 31)):
+        raise ValueError("lattice points must fit int32")
+    pts = np.ascontiguousarray(pts, dtype=np.int32)
+    n = pts.shape[0]
+    seg = np.array([0, n], np.int64) if seg_start is None else np.ascontiguousarray(seg_start, dtype=np.int64)
+    if seg.ndim != 1 or seg.shape[0] < 1:
+        raise ValueError("seg_start must hold n_seg + 1 offsets")
+    a2 = int(a2)
+    if a2 < 0 or a2 >= 1 << 64:
+        raise ValueError("a2 must be a non-negative 64-bit integer")
+    n_seg = seg.shape[0] - 1
+    twice, live, nb = (np.zeros(max(n_seg, 1), np.int64) for _ in range(3))
+    st = np.zeros(5, np.int64)
+    lib = _lib.load()
+    out = vp()
+    check(lib.pyqsm_alpha_area(_p(pts), n, _p(seg), n_seg, a2, 0 if max_tests is None else int(max_tests),
+                               ALPHA_BOUNDARY if return_boundary else 0, _p(twice), _p(live), _p(nb),
+                               ctypes.byref(out), _p(st), int(device)))
+    twice, live, nb = twice[:n_seg], live[:n_seg], nb[:n_seg]
+    edges = start = None
+    if return_boundary:
+        start = np.concatenate([[0], np.cumsum(nb)]).astype(np.int64)
+        edges = _adopt(lib, out, i64, 2 * int(start[-1]), np.int64).reshape(-1, 2) if out.value \
+            else np.zeros((0, 2), np.int64)
+    stats = dict(zip(("estimated_tests", "tests", "exact_fallbacks", "edges", "merged_duplicates"),
+                     (int(v) for v in st)))
+    return AlphaArea(twice, live, nb, edges, start, stats)
+
+
 def fps(points, num_samples: int, start_index: int = 0, device: int = 0) -> np.ndarray:
     """Farthest-point sampling: int32 indices in selection order."""
     pts = _points(points)
