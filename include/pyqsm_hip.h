@@ -203,6 +203,17 @@ int pyqsm_dbscan_ex(const double* xyz, int64_t n, double eps, int32_t min_pts,
 int pyqsm_dbscan_dev_ex(const double* xyz_dev, int64_t n, double eps, int32_t min_pts,
                         int32_t radius_inclusive, int64_t* labels_dev, uint8_t* is_core_dev,
                         int64_t* n_clusters, int32_t device);
+/*
+ * A read-out of the cell directory DBSCAN bins with, for tests: plans and bins the cloud exactly as
+ * pyqsm_dbscan does (first call on a context: planned on the host; a repeat: the device plan;
+ * PYQSM_DBSCAN_PLAN, PYQSM_COORD_F32 and PYQSM_DBSCAN_BIN are honoured), then evaluates the
+ * directory on the device. dims_out i32 [3]: the grid's cells per axis, borders included;
+ * begin_out i32 [ncell + 1], ncell = the product of the dims: begin_out[c] = number of points in
+ * cells with id < c. PYQSM_ERANGE when ncell + 1 > cap (the entries begin_out has room for; the
+ * dims are not written then).
+ */
+int pyqsm_octant_directory(const double* xyz, int64_t n, double eps, int32_t* dims_out,
+                           int32_t* begin_out, int64_t cap, int32_t device);
 
 /* ---- k nearest neighbours --------------------------------------------- */
 /*

@@ -40,11 +40,11 @@ __device__ __forceinline__ double sqdist(double ax, double ay, double az, double
 
 // Visit every sorted position q in the 27-cell stencil of cell c:
 // nine contiguous runs (x-1..x+1 for each of the 3x3 (y,z) rows).
-#define FOR_STENCIL(c, st, start, q, body)                         \
+#define FOR_STENCIL(c, st, dir, q, body)                           \
   for (int dz__ = -1; dz__ <= 1; ++dz__)                           \
     for (int dy__ = -1; dy__ <= 1; ++dy__) {                       \
       const int row__ = (c) + dy__ * (st).nx + dz__ * (st).nxy;    \
-      const int qb__ = (start)[row__ - 1], qe__ = (start)[row__ + 2]; \
+      const int qb__ = (dir).begin(row__ - 1), qe__ = (dir).begin(row__ + 2); \
       for (int q = qb__; q < qe__; ++q) {                          \
         body                                                       \
       }                                                            \
@@ -75,9 +75,28 @@ static constexpr int kRestSegs = 64;  // segments (and counters) of the straggle
 // centre, same-z rows, same-y rows, corners (compile-time: the run bounds stay in SGPRs)
 __device__ constexpr int kRunOrder[9] = {4, 3, 5, 1, 7, 0, 2, 6, 8};
 
+// The nine runs [qb[r], qe[r]) of the 27-cell stencil of cell c, in kRunOrder: the eighteen directory
+// words are loaded side by side, then the eighteen slots.
+__device__ __forceinline__ void stencil_bounds(int c, Stencil st, const CellDir& dir, int (&qb)[9], int (&qe)[9]) {
+  int cells[18], q[18];
+#pragma unroll
+  for (int r = 0; r < 9; ++r) {
+    const int row = c + (kRunOrder[r] % 3 - 1) * st.nx + (kRunOrder[r] / 3 - 1) * st.nxy;
+    cells[2 * r] = row - 1;
+    cells[2 * r + 1] = row + 2;
+  }
+  dir.begins(cells, q);
+#pragma unroll
+  for (int r = 0; r < 9; ++r) {
+    qb[r] = q[2 * r];
+    qe[r] = q[2 * r + 1];
+  }
+}
+
 template <class CO>
 __global__ __launch_bounds__(256) void k_core_tiled(int n, const GridPlan* __restrict__ plan,
-                                                    const int32_t* __restrict__ start,
+                                                    const DirWord* __restrict__ dwords,
+                                                    const int32_t* __restrict__ dslots,
                                                     const int32_t* __restrict__ cell_of, CO co, double r2,
                                                     int min_pts, uint8_t* __restrict__ core,
                                                     int32_t* __restrict__ rest,
@@ -90,6 +109,7 @@ __global__ __launch_bounds__(256) void k_core_tiled(int n, const GridPlan* __res
     unsigned long long* __restrict__ st /*stamps or null*/) {
   __shared__ TileLds L;
   stamped(st, [&] {
+  const CellDir dir{dwords, dslots};
   // wave-uniform quantities are forced into SGPRs so that the loops below are scalar
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int p0 = (blockIdx.x * 4 + w) * 64;
@@ -100,7 +120,7 @@ __global__ __launch_bounds__(256) void k_core_tiled(int n, const GridPlan* __res
   const bool live = p < n;
   double x = 0.0, y = 0.0, z = 0.0;
   if (live) co.get(p, x, y, z);
-  const Tile t = wave_tile(p0, n, st, ncell, start, cell_of);
+  const Tile t = wave_tile(p0, n, st, ncell, dir, cell_of);
   int cnt = 0;  // (starting lanes of sub-cells with >= min_pts points as "decided" gained nothing)
   bool deferred = false;
   int chunks = 0;
@@ -118,23 +138,24 @@ __global__ __launch_bounds__(256) void k_core_tiled(int n, const GridPlan* __res
       const int c = __builtin_amdgcn_readlane(mycell, lead);
       const bool mine = mycell == c;
       todo &= ~__ballot(mine);
-      for (int dz = -1; dz <= 1; ++dz)
-        for (int dy = -1; dy <= 1; ++dy) {
-          const int row = c + dy * st.nx + dz * st.nxy;
-          const int qb = __builtin_amdgcn_readfirstlane(start[row - 1]);
-          const int qe = __builtin_amdgcn_readfirstlane(start[row + 2]);
-          for (int base = qb; base < qe; base += 64) {
-            const int q = base + lane;
-            const int m = qe - base < 64 ? qe - base : 64;
-            if (q < qe) co.get(q, L.x[w][lane], L.y[w][lane], L.z[w][lane]);
-            __builtin_amdgcn_wave_barrier();
-            staged += m;
-            if (mine)
-              for (int j = 0; j < m; ++j)
-                cnt += sqdist(x, y, z, L.x[w][j], L.y[w][j], L.z[w][j]) <= r2;
-            __builtin_amdgcn_wave_barrier();
-          }
+      int rqb[9], rqe[9];  // the cell's nine runs (in kRunOrder: every candidate counts, the order is free)
+      stencil_bounds(c, st, dir, rqb, rqe);
+#pragma unroll
+      for (int r = 0; r < 9; ++r) {
+        const int qb = __builtin_amdgcn_readfirstlane(rqb[r]);
+        const int qe = __builtin_amdgcn_readfirstlane(rqe[r]);
+        for (int base = qb; base < qe; base += 64) {
+          const int q = base + lane;
+          const int m = qe - base < 64 ? qe - base : 64;
+          if (q < qe) co.get(q, L.x[w][lane], L.y[w][lane], L.z[w][lane]);
+          __builtin_amdgcn_wave_barrier();
+          staged += m;
+          if (mine)
+            for (int j = 0; j < m; ++j)
+              cnt += sqdist(x, y, z, L.x[w][j], L.y[w][j], L.z[w][j]) <= r2;
+          __builtin_amdgcn_wave_barrier();
         }
+      }
     }
   } else {
 #pragma unroll
@@ -206,36 +227,50 @@ struct Runs9 {
     return q;
   }
 };
-__device__ __forceinline__ Runs9 stencil_runs(int c, Stencil st, const int32_t* __restrict__ start) {
-  Runs9 t;
-  int qe[9];
-#pragma unroll
-  for (int r = 0; r < 9; ++r) {
-    const int row = c + (kRunOrder[r] % 3 - 1) * st.nx + (kRunOrder[r] / 3 - 1) * st.nxy;
-    t.qb[r] = start[row - 1];
-    qe[r] = start[row + 2];
+// The runs of kRunBatch points per wave at once. With the ranked directory a bound is two dependent
+// loads (word, slot), and a wave that takes one point per step pays that chain, on top of the point's
+// own (list entry -> cell -> bounds -> candidates), once per point: k_core_rest went from 16.5 to
+// 25.7 us on the benchmark forest with the bounds fetched per point by scalar loads. So lane
+// 18 k + j looks up bound j of the wave's k-th point (j = 2 r: begin of run r in kRunOrder, 2 r + 1:
+// its end): one gather of words and one of slots serve three points, whose chains overlap.
+static constexpr int kRunBatch = 3;
+__device__ __forceinline__ int lane_bound(bool act, int c, int j, Stencil st, const CellDir& dir) {
+  const int r = int((0x862071534ull >> (4 * (j >> 1))) & 15ull);  // kRunOrder[j >> 1], without a table in memory
+  const int cell = c + (r % 3 - 1) * st.nx + (r / 3 - 1) * st.nxy + ((j & 1) ? 2 : -1);
+  int b = 0;
+  if (act) {
+    const DirWord w = dir.words[cell >> 5];
+    b = dir.slots[CellDir::slot_of(w, cell)];
   }
+  return b;
+}
+// the k-th point's runs out of the lanes' bounds (k is a constant: unrolled loops)
+__device__ __forceinline__ Runs9 runs_of_lanes(int bound, int k) {
+  Runs9 t;
   t.pre[0] = 0;
 #pragma unroll
   for (int r = 0; r < 9; ++r) {
-    t.qb[r] = __builtin_amdgcn_readfirstlane(t.qb[r]);
-    t.pre[r + 1] = t.pre[r] + (__builtin_amdgcn_readfirstlane(qe[r]) - t.qb[r]);
+    t.qb[r] = __builtin_amdgcn_readlane(bound, 18 * k + 2 * r);
+    t.pre[r + 1] = t.pre[r] + (__builtin_amdgcn_readlane(bound, 18 * k + 2 * r + 1) - t.qb[r]);
   }
   return t;
 }
 
 // The stragglers of k_core_tiled, one WAVE each: 64 candidates of the stencil per step,
 // stop at min_pts. (One lane each was 0.13 ms per million points: a noise point walks
-// ~850 candidates one dependent load at a time.)
+// ~850 candidates one dependent load at a time.) A wave takes kRunBatch stragglers per step and
+// looks their bounds up together (lane_bound), then walks them one after the other.
 template <class CO>
 __global__ __launch_bounds__(256) void k_core_rest(const int32_t* __restrict__ rest,
                                                    const int32_t* __restrict__ rest_cnt /*[kRestSegs]*/,
                                                    int seg_cap, const GridPlan* __restrict__ plan,
-                                                   const int32_t* __restrict__ start,
+                                                   const DirWord* __restrict__ dwords,
+                                                   const int32_t* __restrict__ dslots,
                                                    const int32_t* __restrict__ cell_of, CO co, double r2,
                                                    int min_pts, uint8_t* __restrict__ core,
     unsigned long long* __restrict__ st /*stamps or null*/) {
   stamped(st, [&] {
+  const CellDir dir{dwords, dslots};
   if (!plan->ok) return;
   const Stencil st = plan_stencil(plan);
   const int lane = threadIdx.x & 63;
@@ -248,23 +283,41 @@ __global__ __launch_bounds__(256) void k_core_rest(const int32_t* __restrict__ r
     if (lane >= off) incl += v;
   }
   const int m = __shfl(incl, 63, 64);
-  for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < m; i += gridDim.x * 4) {  // wave-uniform
-    const int seg = __popcll(__ballot(incl <= i));  // the first segment whose running total exceeds i
-    const int before = __shfl(incl - mine, seg, 64);
-    const int p = rest[size_t(seg) * seg_cap + (i - before)];
-    double x, y, z;
-    co.get(p, x, y, z);
-    const int c = __builtin_amdgcn_readfirstlane(cell_of[p]);
-    const Runs9 t = stencil_runs(c, st, start);
-    int cnt = 0;
-    for (int g0 = 0; g0 < t.pre[9] && cnt < min_pts; g0 += 64) {
-      const int g = g0 + lane;
-      const bool hit = g < t.pre[9] && co.d2(t.at(g), x, y, z) <= r2;
-      cnt += __popcll(__ballot(hit));
+  const int grp = lane / 18, j = lane % 18;  // (lanes 54 .. 63 look nothing up)
+  for (int i0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * kRunBatch; i0 < m; i0 += gridDim.x * 4 * kRunBatch) {  // wave-uniform
+    int p = 0;
+#pragma unroll
+    for (int k = 0; k < kRunBatch; ++k) {
+      if (i0 + k >= m) break;  // wave-uniform
+      const int seg = __popcll(__ballot(incl <= i0 + k));  // the first segment whose running total exceeds the entry
+      const int before = __shfl(incl - mine, seg, 64);
+      const int pk = rest[size_t(seg) * seg_cap + (i0 + k - before)];
+      p = grp == k ? pk : p;
     }
-    if (lane == 0) {
-      core[p] = cnt >= min_pts;
-      co.mark_core(p, cnt >= min_pts);
+    const bool act = grp < kRunBatch && i0 + grp < m;
+    double x = 0.0, y = 0.0, z = 0.0;
+    int c = 0;
+    if (act) {
+      co.get(p, x, y, z);
+      c = cell_of[p];
+    }
+    const int bound = lane_bound(act, c, j, st, dir);
+#pragma unroll
+    for (int k = 0; k < kRunBatch; ++k) {
+      if (i0 + k >= m) break;  // wave-uniform
+      const Runs9 t = runs_of_lanes(bound, k);
+      const int pk = __builtin_amdgcn_readlane(p, 18 * k);
+      const double xk = __shfl(x, 18 * k, 64), yk = __shfl(y, 18 * k, 64), zk = __shfl(z, 18 * k, 64);
+      int cnt = 0;
+      for (int g0 = 0; g0 < t.pre[9] && cnt < min_pts; g0 += 64) {
+        const int g = g0 + lane;
+        const bool hit = g < t.pre[9] && co.d2(t.at(g), xk, yk, zk) <= r2;
+        cnt += __popcll(__ballot(hit));
+      }
+      if (lane == 0) {
+        core[pk] = cnt >= min_pts;
+        co.mark_core(pk, cnt >= min_pts);
+      }
     }
   }
   });
@@ -501,29 +554,25 @@ static constexpr int kSubPerWave = 4;
 
 // The sub-cell at half-cell offset -(dx, dy, dz) of the sub-cell (cx, cy, cz, octant) = at: its run
 // [q0, q0 + n2) and its representative; rep < 0 where the lane is idle, the cell is empty or the
-// sub-cell has no core point. Three dependent gathers (start twice, the record).
+// sub-cell has no core point. Three dependent gathers (the directory word, the cell's slot, the
+// record); a lane whose neighbour cell is empty stops after the word, whose bit says so.
 // (What these kernels cost is the number of cache LINES their gathers touch — one per
-// neighbouring cell and table, taken by the L1 a line at a time. Dropping the second gather
-// start[c2 + 1] by tagging the records with their cell cost more than it saved: lanes of
-// empty cells then fetch the next occupied cell's records.)
+// neighbouring cell and table, taken by the L1 a line at a time.)
 struct SubNbr {
   int q0, n2, rep;
 };
 __device__ __forceinline__ SubNbr sub_neighbour(bool active, const int4 at, int dx, int dy, int dz, int nx, int ny,
-                                                const int32_t* __restrict__ start,
-                                                const int4* __restrict__ rec) {
+                                                const CellDir& dir, const int4* __restrict__ rec) {
   // half-cell coordinates (cell 1 is the first interior cell; borders are empty)
   const int gx = 2 * (at.x - 1) + (at.w & 1) - dx, gy = 2 * (at.y - 1) + ((at.w >> 1) & 1) - dy,
             gz = 2 * (at.z - 1) + ((at.w >> 2) & 1) - dz;
   const int c2 = (((gz >> 1) + 1) * ny + ((gy >> 1) + 1)) * nx + ((gx >> 1) + 1);
   const int oct = (gx & 1) | ((gy & 1) << 1) | ((gz & 1) << 2);
   SubNbr out{0, 0, -1};
-  int b2 = 0, e2 = 0;
-  if (active) {
-    b2 = start[c2];
-    e2 = start[c2 + 1];
-  }
-  if (e2 != b2) {
+  DirWord w{0u, 0u};
+  if (active) w = dir.words[c2 >> 5];
+  if ((w.bits >> (c2 & 31)) & 1u) {
+    const int b2 = dir.slots[CellDir::slot_of(w, c2)];
     const int4 r = rec[b2 * 8 + oct];
     if (r.y > 0) {
       out.q0 = r.x;
@@ -553,12 +602,15 @@ template <class CO>
 __global__ __launch_bounds__(256) void k_hook_sub(const int4* __restrict__ list,
                                                   const int4* __restrict__ list_xyz,
                                                   const int32_t* __restrict__ m_ptr,
-                                                  const GridPlan* __restrict__ plan, const int32_t* __restrict__ start,
+                                                  const GridPlan* __restrict__ plan,
+                                                  const DirWord* __restrict__ dwords,
+                                                  const int32_t* __restrict__ dslots,
                                                   const int4* __restrict__ rec, CO co, double r2,
                                                   const uint8_t* __restrict__ core,
                                                   int* __restrict__ parent,
     unsigned long long* __restrict__ st /*stamps or null*/) {
   stamped(st, [&] {
+  const CellDir dir{dwords, dslots};
   if (!plan->ok) return;
   const int nx = plan->nx, ny = plan->ny;
   const int m = *m_ptr;
@@ -572,7 +624,7 @@ __global__ __launch_bounds__(256) void k_hook_sub(const int4* __restrict__ list,
   for (int s0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * kSubPerWave; s0 < m; s0 += gridDim.x * 4 * kSubPerWave) {
     const bool live = s0 + grp < m;
     const int4 me = list[min(s0 + grp, m - 1)], at = list_xyz[min(s0 + grp, m - 1)];
-    const SubNbr nb2 = sub_neighbour(live && t < 13, at, o_dx, o_dy, o_dz, nx, ny, start, rec);
+    const SubNbr nb2 = sub_neighbour(live && t < 13, at, o_dx, o_dy, o_dz, nx, ny, dir, rec);
     const int p = me.x, n1 = me.w;
     // the group's candidates, nearest first; `base`: the pairs of the current one already tested
     unsigned todo = unsigned(__ballot(nb2.rep >= 0) >> (16 * grp)) & 0xFFFFu;
@@ -637,10 +689,10 @@ __device__ __forceinline__ bool wave_pair_within(const CO& co, int p, int n1, in
 // itself was 3x slower: ~25 dependent iterations per lane, and a wave lasts as long as its slowest lane.)
 template <class CO>
 __device__ __forceinline__ void seam_unite(const int4 me, const int4 at, int k, int o_dx, int o_dy, int o_dz,
-                                           int nx, int ny, const int32_t* __restrict__ start,
+                                           int nx, int ny, const CellDir& dir,
                                            const int4* __restrict__ rec, const CO& co, double r2,
                                            const uint8_t* __restrict__ core, int* parent) {
-  const SubNbr nb2 = sub_neighbour(k < 62, at, o_dx, o_dy, o_dz, nx, ny, start, rec);
+  const SubNbr nb2 = sub_neighbour(k < 62, at, o_dx, o_dy, o_dz, nx, ny, dir, rec);
   const int p = me.x, n1 = me.w, rep2 = nb2.rep;
   // A plain (cached, possibly stale) read names an ancestor; equal ancestors prove
   // "same tree" (trees only merge). The coherent chase is for the rest.
@@ -702,12 +754,15 @@ template <class CO>
 __global__ __launch_bounds__(256) void k_union_sub(const int4* __restrict__ list,
                                                    const int4* __restrict__ list_xyz,
                                                    const int32_t* __restrict__ m_ptr,
-                                                   const GridPlan* __restrict__ plan, const int32_t* __restrict__ start,
+                                                   const GridPlan* __restrict__ plan,
+                                                   const DirWord* __restrict__ dwords,
+                                                   const int32_t* __restrict__ dslots,
                                                    const int4* __restrict__ rec, CO co, double r2,
                                                    const uint8_t* __restrict__ core, int* parent,
                                                    unsigned long long* __restrict__ seam_cnt /*trace or null*/,
     unsigned long long* __restrict__ st /*stamps or null*/) {
   stamped(st, [&] {
+  const CellDir dir{dwords, dslots};
   if (!plan->ok) return;
   const int nx = plan->nx, ny = plan->ny;
   const int m = *m_ptr;
@@ -724,24 +779,29 @@ __global__ __launch_bounds__(256) void k_union_sub(const int4* __restrict__ list
     const int* vparent = parent;
     const int r_s = vparent[me.x];
     const int c2 = me.y + c_off;  // (cells have a border of empty cells all round: c2 - layer - 1 >= 0)
-    int b2[2] = {0, 0}, e2[2] = {0, 0}, word[2] = {0, 0};
+    int word[2] = {0, 0};
+    DirWord dw[2] = {{0u, 0u}, {0u, 0u}};
     if (live && t < 9) {
 #pragma unroll
-      for (int l = 0; l < 2; ++l) {
-        b2[l] = start[c2 - l * layer];
-        e2[l] = start[c2 - l * layer + 1];
-      }
+      for (int l = 0; l < 2; ++l) dw[l] = dir.words[(c2 - l * layer) >> 5];
+    }
+    int b2[2] = {0, 0};
+    bool occ[2];
+#pragma unroll
+    for (int l = 0; l < 2; ++l) {
+      occ[l] = (dw[l].bits >> ((c2 - l * layer) & 31)) & 1u;
+      if (occ[l]) b2[l] = dir.slots[CellDir::slot_of(dw[l], c2 - l * layer)];
     }
 #pragma unroll
     for (int l = 0; l < 2; ++l)
-      if (e2[l] != b2[l]) word[l] = rec[b2[l] * 8].w;
+      if (occ[l]) word[l] = rec[b2[l] * 8].w;
     const unsigned long long seams =
         __ballot((word[0] != 0 && word[0] != r_s + 1) || (word[1] != 0 && word[1] != r_s + 1));
     if (!seams) continue;
     for (int u = 0; u < kSubPerWave; ++u) {
       if (!((seams >> (16 * u)) & 0xFFFFull)) continue;  // wave-uniform
       if (seam_cnt && k == 0) atomicAdd(seam_cnt, 1ull);
-      seam_unite(list[s0 + u], list_xyz[s0 + u], k, o_dx, o_dy, o_dz, nx, ny, start, rec, co, r2, core, parent);
+      seam_unite(list[s0 + u], list_xyz[s0 + u], k, o_dx, o_dy, o_dz, nx, ny, dir, rec, co, r2, core, parent);
     }
   }
   });
@@ -753,9 +813,11 @@ __global__ __launch_bounds__(256) void k_union_sub(const int4* __restrict__ list
 // take the per-point union-find of the first version (same results, ~3x slower union phase).
 template <class CO>
 __global__ __launch_bounds__(256) void k_union_points(int n, Stencil st,
-                                                      const int32_t* __restrict__ start,
+                                                      const DirWord* __restrict__ dwords,
+                                                      const int32_t* __restrict__ dslots,
                                                       const int32_t* __restrict__ cell_of, CO co, double r2,
                                                       const uint8_t* __restrict__ core, int* parent) {
+  const CellDir dir{dwords, dslots};
   int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= n || !core[p]) return;
   double x, y, z;
@@ -763,7 +825,7 @@ __global__ __launch_bounds__(256) void k_union_points(int n, Stencil st,
   const int c = cell_of[p];
   const volatile int* vparent = parent;
   int rp = find_root(parent, p);
-  FOR_STENCIL(c, st, start, q, {
+  FOR_STENCIL(c, st, dir, q, {
     // each unordered pair once; a plain read equal to p's root proves "same tree"
     if (q < p && core[q] && co.d2(q, x, y, z) <= r2) {
       if (vparent[q] != rp) {
@@ -1055,7 +1117,8 @@ __device__ __forceinline__ int cluster_number(int v, int n_roots, const uint32_t
 // The label pass, two roles in one launch. Core points copy their cluster number (point -> representative ->
 // root): a thread each, one scattered store, and every point's core flag goes out in the caller's order beside
 // it. Then every wave takes the entries wave, wave + waves of the grid, ... of the list of non-core points
-// (flags_role): a WAVE per point, the smallest cluster number among the core neighbours in its stencil, or -1.
+// (flags_role): a WAVE per point (kRunBatch points' bounds looked up together, as in k_core_rest), the smallest
+// cluster number among the core neighbours in its stencil, or -1.
 // The roles do not wait on each other and cannot race: the first writes the labels of core points only, the
 // second those of non-core points only, and both only read core / parent / min_orig. (DESIGN section 4 has the
 // forms measured and dropped.)
@@ -1064,7 +1127,8 @@ template <class CO>
 __global__ __launch_bounds__(kLabelThreads) void k_labels(int n, const int32_t* __restrict__ rest,
                                                           const int32_t* __restrict__ rest_cnt,
                                                           const GridPlan* __restrict__ plan,
-                                                          const int32_t* __restrict__ start,
+                                                          const DirWord* __restrict__ dwords,
+                                                          const int32_t* __restrict__ dslots,
                                                           const int32_t* __restrict__ cell_of, CO co, double r2,
                                                           const uint8_t* __restrict__ core,
                                                           const int* __restrict__ parent,
@@ -1077,6 +1141,7 @@ __global__ __launch_bounds__(kLabelThreads) void k_labels(int n, const int32_t* 
                                                           uint8_t* __restrict__ is_core,
     unsigned long long* __restrict__ st /*stamps or null*/) {
   stamped(st, [&] {
+  const CellDir dir{dwords, dslots};
   if (!plan->ok) return;  // block-uniform
   constexpr int kWaves = kLabelThreads / 64;
   const int n_roots = *roots_cnt;
@@ -1092,31 +1157,43 @@ __global__ __launch_bounds__(kLabelThreads) void k_labels(int n, const int32_t* 
   }
   const int m = *rest_cnt;
   const Stencil sten = plan_stencil(plan);
-  const int first = blockIdx.x * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  for (int i = first; i < m; i += gridDim.x * kWaves) {  // wave-uniform
-    const int p = rest[i];
-    double x, y, z;
-    co.get(p, x, y, z);
-    const int c = __builtin_amdgcn_readfirstlane(cell_of[p]);
-    const Runs9 t = stencil_runs(c, sten, start);
-    int best = kNoRoot;
-    for (int g0 = 0; g0 < t.pre[9]; g0 += 64) {
-      const int g = g0 + lane;
-      if (g < t.pre[9]) {
-        const int q = t.at(g);
-        if (core[q] && co.d2(q, x, y, z) <= r2) {
-          const int mo = min_orig[parent[parent[q]]];
-          best = mo < best ? mo : best;
+  const int first = (blockIdx.x * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) * kRunBatch;
+  const int grp = lane / 18, j = lane % 18;  // (as k_core_rest: three points' bounds per gather)
+  for (int i0 = first; i0 < m; i0 += gridDim.x * kWaves * kRunBatch) {  // wave-uniform
+    const bool act = grp < kRunBatch && i0 + grp < m;
+    double x = 0.0, y = 0.0, z = 0.0;
+    int p = 0, c = 0;
+    if (act) {
+      p = rest[i0 + grp];
+      co.get(p, x, y, z);
+      c = cell_of[p];
+    }
+    const int bound = lane_bound(act, c, j, sten, dir);
+#pragma unroll
+    for (int k = 0; k < kRunBatch; ++k) {
+      if (i0 + k >= m) break;  // wave-uniform
+      const Runs9 t = runs_of_lanes(bound, k);
+      const int pk = __builtin_amdgcn_readlane(p, 18 * k);
+      const double xk = __shfl(x, 18 * k, 64), yk = __shfl(y, 18 * k, 64), zk = __shfl(z, 18 * k, 64);
+      int best = kNoRoot;
+      for (int g0 = 0; g0 < t.pre[9]; g0 += 64) {
+        const int g = g0 + lane;
+        if (g < t.pre[9]) {
+          const int q = t.at(g);
+          if (core[q] && co.d2(q, xk, yk, zk) <= r2) {
+            const int mo = min_orig[parent[parent[q]]];
+            best = mo < best ? mo : best;
+          }
         }
       }
-    }
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const int o = __shfl_xor(best, off, 64);
-      best = o < best ? o : best;
+      for (int off = 32; off > 0; off >>= 1) {
+        const int o = __shfl_xor(best, off, 64);
+        best = o < best ? o : best;
+      }
+      if (lane == 0)
+        labels[order[pk]] = best == kNoRoot ? int64_t(-1) : int64_t(cluster_number(best, n_roots, bits, wpre));
     }
-    if (lane == 0)
-      labels[order[p]] = best == kNoRoot ? int64_t(-1) : int64_t(cluster_number(best, n_roots, bits, wpre));
   }
   });
 }
@@ -1131,6 +1208,7 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
   const int N = int(n);
   const dim3 grid(ceil_div(n, 256)), block(256);
   const Stencil st{g.nx, g.nx * g.ny};  // (host-planned grids only: k_union_points)
+  const CellDir dir = cell_dir(g);
   // Every kernel tests d2 <= r2. The STRICT neighbourhood d2 < eps^2 (radius_inclusive = 0: what
   // Open3D's cluster_dbscan computes if nanoflann's radius search compares strictly; SURVEY.md
   // §8 a2) is the same test against the double just below eps^2 — no fp64 value lies between
@@ -1178,7 +1256,7 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
     {
       const StampKernel pk(c, "k_core_tiled", grid.x);
       on_coords(g, [&](auto co) {
-        hipLaunchKernelGGL(k_core_tiled<decltype(co)>, grid, block, 0, c->stream, N, d_plan, g.start, g.cell_of, co, r2,
+        hipLaunchKernelGGL(k_core_tiled<decltype(co)>, grid, block, 0, c->stream, N, d_plan, dir.words, dir.slots, g.cell_of, co, r2,
                            min_pts, core, rest, rest_segs, seg_cap, parent, min_orig, flag, max_chunks, d_tests,
                            pk.slots);
       });
@@ -1194,7 +1272,7 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
     const dim3 gr(std::min<int64_t>(8192, ceil_div(n, 64)));
     unsigned long long* const st_rest = stamp_slots(c, gr.x);
     on_coords(g, [&](auto co) {
-      hipLaunchKernelGGL(k_core_rest<decltype(co)>, gr, block, 0, c->stream, rest, rest_segs, seg_cap, d_plan, g.start,
+      hipLaunchKernelGGL(k_core_rest<decltype(co)>, gr, block, 0, c->stream, rest, rest_segs, seg_cap, d_plan, dir.words, dir.slots,
                          g.cell_of, co, r2, min_pts, core, st_rest);
     });
     PQ_HIP(hipGetLastError());
@@ -1238,7 +1316,7 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
           const StampKernel pk(c, "k_hook_sub", gh.x);
           on_coords(g, [&](auto co) {
             hipLaunchKernelGGL(k_hook_sub<decltype(co)>, gh, block, 0, c->stream, list, list_xyz, list_cnt, d_plan,
-                               g.start, sub.rec, co, r2, core, parent, pk.slots);
+                               dir.words, dir.slots, sub.rec, co, r2, core, parent, pk.slots);
           });
         }
         if (trace) {  // how deep are the chains the hook pass leaves?
@@ -1284,7 +1362,7 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
           const StampKernel pk(c, "k_union_sub", gu.x);
           on_coords(g, [&](auto co) {
             hipLaunchKernelGGL(k_union_sub<decltype(co)>, gu, block, 0, c->stream, list, list_xyz, list_cnt, d_plan,
-                               g.start, sub.rec, co, r2, core, parent, d_seams, pk.slots);
+                               dir.words, dir.slots, sub.rec, co, r2, core, parent, d_seams, pk.slots);
           });
         }
         if (trace) {
@@ -1301,7 +1379,7 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
     } else {
       PQ_TRY(stamp_mark(c));  // (the per-point union-find is not stamped itself)
       on_coords(g, [&](auto co) {
-        hipLaunchKernelGGL(k_union_points<decltype(co)>, grid, block, 0, c->stream, N, st, g.start, g.cell_of, co,
+        hipLaunchKernelGGL(k_union_points<decltype(co)>, grid, block, 0, c->stream, N, st, dir.words, dir.slots, g.cell_of, co,
                            r2, core, parent);
       });
       hipLaunchKernelGGL(k_flatten, grid, block, 0, c->stream, N, core, parent, d_plan);
@@ -1322,7 +1400,7 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
     unsigned long long* const st_labels = stamp_slots(c, gb.x);
     on_coords(g, [&](auto co) {
       hipLaunchKernelGGL(k_labels<decltype(co)>, gb, dim3(kLabelThreads), 0, c->stream, N, rest, list_cnt + 3, d_plan,
-                         g.start, g.cell_of, co, r2, core, parent, min_orig, roots_cnt, bits, wpre, g.order, labels,
+                         dir.words, dir.slots, g.cell_of, co, r2, core, parent, min_orig, roots_cnt, bits, wpre, g.order, labels,
                          is_core, st_labels);
     });
     PQ_HIP(hipGetLastError());
@@ -1364,8 +1442,16 @@ static int wait_plan(Ctx* c, const GridPlan* h_plan, unsigned seq) {
 // covers axis-compressed and doubled grids, fp64 records, bits = 13 and non-finite input.
 // PYQSM_DBSCAN_PLAN=host: the host plans every call (A/B comparisons). A missed speculation records
 // its (empty) profiling scopes as well.
+// `readout` (pyqsm_octant_directory): plan and bin as every call does, then, instead of clustering, hand
+// back the grid's dims and the directory's begin(c) for c = 0 .. ncell as the device evaluates it.
+struct DirReadout {
+  int64_t cap;       // entries begin_host has room for
+  int32_t* begin_host;
+  int32_t dims[3];
+};
 static int dbscan_device(Ctx* c, const double* xyz, int64_t n, double eps, int32_t min_pts,
-                         bool radius_inclusive, int64_t* labels, uint8_t* is_core, int64_t* n_clusters) {
+                         bool radius_inclusive, int64_t* labels, uint8_t* is_core, int64_t* n_clusters,
+                         DirReadout* readout = nullptr) {
   if (!(eps > 0) || !std::isfinite(eps)) return fail(PYQSM_EINVAL, "eps must be positive");
   if (n == 0) {
     if (n_clusters) *n_clusters = 0;
@@ -1404,7 +1490,8 @@ static int dbscan_device(Ctx* c, const double* xyz, int64_t n, double eps, int32
   if (speculate) {
     PQ_TRY(bin_octants_planned(c, xyz, n, cell, hint, d_plan, zeroed, &g, &sub));
     bin_scope.reset();
-    PQ_TRY(cluster_binned(c, n, eps, min_pts, radius_inclusive, g, sub, d_plan, labels, is_core, &count));
+    if (!readout)
+      PQ_TRY(cluster_binned(c, n, eps, min_pts, radius_inclusive, g, sub, d_plan, labels, is_core, &count));
   }
   PQ_TRY(wait_plan(c, h_plan, seq));
   const bool hit = speculate && h_plan[0].ok;
@@ -1419,11 +1506,29 @@ static int dbscan_device(Ctx* c, const double* xyz, int64_t n, double eps, int32
     PQ_TRY(stamp_mark(c));
     bin_scope.reset();
     if (next.valid) c->plan_hint = next;  // (a grid of another kind keeps the hint there is)
-    PQ_TRY(cluster_binned(c, n, eps, min_pts, radius_inclusive, g, sub, d_plan + 1, labels, is_core, &count));
+    if (!readout)
+      PQ_TRY(cluster_binned(c, n, eps, min_pts, radius_inclusive, g, sub, d_plan + 1, labels, is_core, &count));
   }
   if (c->prof >= 1) {
     c->timers["dbscan_f32_records"].launches += g.p4 ? 1 : 0;  // which storage form ran
     c->timers[hit ? "dbscan_plan_hit" : "dbscan_plan_miss"].launches += 1;  // which planning ran
+  }
+  if (readout) {
+    const GridPlan& pl = hit ? h_plan[0] : h_plan[1];  // the fold's plan, or the one the host uploaded
+    readout->dims[0] = pl.nx;
+    readout->dims[1] = pl.ny;
+    readout->dims[2] = pl.nz;
+    const int64_t entries = int64_t(pl.ncell) + 1;
+    if (entries > readout->cap)
+      return fail(PYQSM_ERANGE, "octant directory: %lld entries, room for %lld", (long long)entries,
+                  (long long)readout->cap);
+    int32_t* d_begin;
+    PQ_TRY(c->arena.get(size_t(entries), &d_begin));
+    read_directory(c, g, pl.ncell, d_begin);
+    PQ_HIP(hipGetLastError());
+    PQ_HIP(hipMemcpyAsync(readout->begin_host, d_begin, size_t(entries) * 4, hipMemcpyDeviceToHost, c->stream));
+    PQ_HIP(hipStreamSynchronize(c->stream));
+    return 0;
   }
   if (n_clusters) {
     int32_t h = 0;
@@ -1487,6 +1592,24 @@ int pyqsm_dbscan_ex(const double* xyz, int64_t n, double eps, int32_t min_pts, i
   PQ_HIP(hipMemcpyAsync(labels, d_lab, size_t(n) * 8, hipMemcpyDeviceToHost, c->stream));
   if (is_core) PQ_HIP(hipMemcpyAsync(is_core, d_core, size_t(n), hipMemcpyDeviceToHost, c->stream));
   PQ_HIP(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int pyqsm_octant_directory(const double* xyz, int64_t n, double eps, int32_t* dims_out, int32_t* begin_out,
+                           int64_t cap, int32_t device) {
+  PQ_API_RANGE("pyqsm_octant_directory");
+  if (n <= 0) return fail(PYQSM_EINVAL, "pyqsm_octant_directory: empty cloud");
+  if (!xyz || !dims_out || !begin_out) return fail(PYQSM_EINVAL, "pyqsm_octant_directory: NULL pointer");
+  Ctx* c = ctx_for(device);
+  if (!c) return PYQSM_ENODEV;
+  std::lock_guard<std::mutex> lk(c->mu);
+  c->arena.reset();
+  double* d_xyz;
+  PQ_TRY(c->arena.get(size_t(n) * 3, &d_xyz));
+  PQ_HIP(hipMemcpyAsync(d_xyz, xyz, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+  DirReadout ro{cap, begin_out, {0, 0, 0}};
+  PQ_TRY(dbscan_device(c, d_xyz, n, eps, 1, true, nullptr, nullptr, nullptr, &ro));
+  for (int a = 0; a < 3; ++a) dims_out[a] = ro.dims[a];
   return 0;
 }
 

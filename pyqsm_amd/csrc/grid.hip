@@ -808,8 +808,10 @@ __global__ __launch_bounds__(256) void k_order_big(const int32_t* __restrict__ b
 //                     clouds) or 32, and the 4-byte key in an array of its own
 //   B   k_bk_sort     one block per bucket, everything in LDS: a count per cell (arrival rank) and
 //                     eight 8-bit counts per cell packed in a u64 (rank inside the octant), a block
-//                     scan of the bucket's cell counts -> the bucket's directory entries,
-//                     written once and coalesced; every point then goes straight to its final,
+//                     scan of the bucket's cell counts -> the bucket's piece of the ranked directory
+//                     (grid.hpp, CellDir: a word per 32 cells, a slot per occupied cell; a dense
+//                     start[ncell + 1] was 60 MB per step for a forest's 0.4 % of occupied cells),
+//                     written once; every point then goes straight to its final,
 //                     octant-ordered place. Cells with more than 255 points (a packed count could
 //                     overflow) are ordered by the same block afterwards, as k_order_big does. A
 //                     bucket of at most 64 points skips the counters: one wave ranks its points.
@@ -1055,6 +1057,7 @@ struct BkLds {
   int32_t cnt[1 << BITS];             // points per cell, then (in place) the cell's offset in the bucket
   uint32_t big[(1 << BITS) / 32];     // cells with more than kBkBig points
   int32_t wsum[16];
+  int32_t osum[16];                   // per wave: occupied cells (the directory's slot ranks)
   int32_t any_big;                    // some cell of the bucket is in `big`
   int32_t btot[8], bbase[8];          // a big cell's octant totals and running bases
   int32_t bw[(1 << BITS) / 512][8];   // per wave: points of each octant in the current chunk
@@ -1085,14 +1088,15 @@ static constexpr int kBkGrp = F32 ? 2 : 1;
 // takes further rounds of the same register tile, whose words alone go through word_tmp.
 template <int BITS, bool F32>
 __global__ __launch_bounds__((1 << BITS) / 8, BITS == 12 ? 6 : 4) void k_bk_sort(
-    int64_t ncell1 /*directory entries: ncell + 1*/, const int32_t* __restrict__ bstart,
+    const int32_t* __restrict__ bstart,
     const typename BkRec<F32>::type* __restrict__ bucketed, const int32_t* __restrict__ keyb,
-    uint32_t* __restrict__ word_tmp, int32_t* __restrict__ rank_tmp, int32_t* __restrict__ start,
+    uint32_t* __restrict__ word_tmp, int32_t* __restrict__ rank_tmp,
+    DirWord* __restrict__ words /*[nbk << (BITS - 5)]*/, int32_t* __restrict__ slots /*[n + nbk + 1]*/,
     int32_t* __restrict__ order, int32_t* __restrict__ cell_of, int32_t* __restrict__ sub_of,
     double* __restrict__ sx, double* __restrict__ sy, double* __restrict__ sz,
     float4* __restrict__ p4 /*non-null: fp32 records instead of sx / sy / sz*/, int4* __restrict__ rec,
     PointRec* __restrict__ keyed /*big cells' runs in arrival order*/,
-    const GridPlan* __restrict__ plan /*ncell1 and the number of buckets (the launch may have more blocks)*/,
+    const GridPlan* __restrict__ plan /*the number of buckets (the launch may have more blocks)*/,
     unsigned long long* __restrict__ st /*stamps or null*/) {
   constexpr int CELLS = 1 << BITS, T = CELLS / 8, CAP = T * kBkPer, G = kBkGrp<F32>;
   using Rec = typename BkRec<F32>::type;
@@ -1101,29 +1105,29 @@ __global__ __launch_bounds__((1 << BITS) / 8, BITS == 12 ? 6 : 4) void k_bk_sort
   stamped(st, [&] {
   const int bk = blockIdx.x, t = threadIdx.x;
   if (!plan->ok || bk >= plan->nbk) return;
-  ncell1 = int64_t(plan->ncell) + 1;
   const int s = bstart[bk], e = bstart[bk + 1];
   const int64_t c0 = int64_t(bk) << BITS;  // first cell (directory entry) of the bucket
-  if (s == e) {  // nothing in the bucket: its directory entries all say "the next point is s"
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const int64_t cidx = c0 + int64_t(k * T + t) * 4;
-      if (cidx + 3 < ncell1) {
-        *reinterpret_cast<int4*>(start + cidx) = make_int4(s, s, s, s);
-      } else {
-        for (int u = 0; u < 4; ++u)
-          if (cidx + u < ncell1) start[cidx + u] = s;
-      }
-    }
+  // The bucket's piece of the ranked directory (grid.hpp, CellDir): its WORDS words, and the begins of
+  // its occupied cells in id order at slots[sb ...], closed by the next bucket's first point. A bucket
+  // has at most as many occupied cells as points, so sb = s + bk leaves every bucket room for its
+  // cells and the closing entry. Every word is written on every step (the arena is reused).
+  constexpr int WORDS = CELLS / 32;
+  DirWord* const wds = words + size_t(bk) * WORDS;
+  const uint32_t sb = uint32_t(s) + uint32_t(bk);
+  if (s == e) {  // nothing in the bucket: whatever is looked up in it reads "the next point is s"
+    if (t < WORDS) wds[t] = DirWord{0u, sb};
+    if (t == 0) slots[sb] = s;
     return;
   }
   if (e - s <= 64) {
     // A wave's worth of points (two buckets in three on a forest: the grid's box is mostly air): no
-    // counters, no scan. Wave 0 ranks the points against each other, key by key, and places them; every
-    // thread then counts the points in the cells below each of its eight. (3 642 buckets of the 1 M-point
+    // counters, no scan. Wave 0 ranks the points against each other, key by key, and places them; the
+    // occupied cells are the distinct cells of those points, found in key order through LDS; a thread
+    // per directory word then collects its bits and its base from that list. (3 642 buckets of the 1 M-point
     // forest's grid took 13.5 us when all were empty, 28.6 us with eleven points each through the
     // counters: what a block pays for the counters, not the bytes, was the cost of these buckets.)
-    int32_t* const cells = L.cnt;  // [64] the points' cells
+    int32_t* const cells = L.cnt;       // [64] the points' cells in key order
+    int32_t* const dcell = L.cnt + 64;  // [<= 64] the distinct ones, ascending
     const int m = e - s;
     if (t < 64) {
       const bool live = t < m;
@@ -1140,7 +1144,7 @@ __global__ __launch_bounds__((1 << BITS) / 8, BITS == 12 ? 6 : 4) void k_bk_sort
       }
       if (live) {
         const int cl = lk >> 3, o = lk & 7, b = s + below_cell, f = s + below_key;
-        cells[t] = cl;
+        cells[below_key] = cl;
         cell_of[f] = int(c0) + cl;
         sub_of[f] = b * 8 + o;
         if constexpr (F32) {
@@ -1164,20 +1168,33 @@ __global__ __launch_bounds__((1 << BITS) / 8, BITS == 12 ? 6 : 4) void k_bk_sort
       }
     }
     __syncthreads();
-    int32_t pre[8] = {s, s, s, s, s, s, s, s};
-    for (int q = 0; q < m; ++q) {
-      const int d = cells[q] - 8 * t;  // the same address in every lane
-#pragma unroll
-      for (int k = 0; k < 8; ++k) pre[k] += d < k ? 1 : 0;
+    if (t < 64) {
+      const bool live = t < m;
+      // lane i now looks at the i-th point in key order: a cell begins where the cell changes, at
+      // sorted position s + i, and its rank among the bucket's occupied cells is a ballot away
+      const int ci = live ? cells[t] : -1;
+      const bool head = live && (t == 0 || cells[t - 1] != ci);
+      const unsigned long long hm = __ballot(head);
+      const int rk = __popcll(hm & ((1ull << t) - 1ull));
+      if (head) {
+        slots[sb + rk] = s + t;
+        dcell[rk] = ci;
+      }
+      if (t == 0) {
+        slots[sb + __popcll(hm)] = e;
+        L.wsum[0] = __popcll(hm);
+      }
     }
-    const int64_t cidx = c0 + 8 * t;
-    if (cidx + 7 < ncell1) {
-      *reinterpret_cast<int4*>(start + cidx) = make_int4(pre[0], pre[1], pre[2], pre[3]);
-      *reinterpret_cast<int4*>(start + cidx + 4) = make_int4(pre[4], pre[5], pre[6], pre[7]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 8; ++k)
-        if (cidx + k < ncell1) start[cidx + k] = pre[k];
+    __syncthreads();
+    if (t < WORDS) {
+      const int nd = L.wsum[0];
+      uint32_t bits = 0u, before = 0u;
+      for (int q = 0; q < nd; ++q) {
+        const int c = dcell[q];  // the same address in every lane
+        before += c < 32 * t ? 1u : 0u;
+        bits |= (c >> 5) == t ? 1u << (c & 31) : 0u;
+      }
+      wds[t] = DirWord{bits, sb + before};
     }
     return;
   }
@@ -1240,17 +1257,31 @@ __global__ __launch_bounds__((1 << BITS) / 8, BITS == 12 ? 6 : 4) void k_bk_sort
 #pragma unroll
     for (int k = 0; k < 8; ++k) tot += v[k];
   }
+  // (the same scan carries the number of occupied cells before the thread's eight: their slots)
+  uint32_t occ8 = 0u;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) occ8 |= v[k] ? 1u << k : 0u;
+  const int nocc = __popc(occ8);
   const int lane = t & 63, w = t >> 6;
-  int32_t incl = tot;
+  int32_t incl = tot, oincl = nocc;
 #pragma unroll
   for (int off = 1; off < 64; off <<= 1) {
-    const int32_t u = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += u;
+    const int32_t u = __shfl_up(incl, off, 64), uo = __shfl_up(oincl, off, 64);
+    if (lane >= off) {
+      incl += u;
+      oincl += uo;
+    }
   }
-  if (lane == 63) L.wsum[w] = incl;
+  if (lane == 63) {
+    L.wsum[w] = incl;
+    L.osum[w] = oincl;
+  }
   __syncthreads();
-  int32_t run = incl - tot;
-  for (int q = 0; q < w; ++q) run += L.wsum[q];
+  int32_t run = incl - tot, orun = oincl - nocc;
+  for (int q = 0; q < w; ++q) {
+    run += L.wsum[q];
+    orun += L.osum[q];
+  }
   int32_t pre[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
@@ -1258,15 +1289,10 @@ __global__ __launch_bounds__((1 << BITS) / 8, BITS == 12 ? 6 : 4) void k_bk_sort
     run += v[k];
   }
   {
-    const int64_t cidx = c0 + 8 * t;
-    if (cidx + 7 < ncell1) {
-      *reinterpret_cast<int4*>(start + cidx) = make_int4(s + pre[0], s + pre[1], s + pre[2], s + pre[3]);
-      *reinterpret_cast<int4*>(start + cidx + 4) = make_int4(s + pre[4], s + pre[5], s + pre[6], s + pre[7]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 8; ++k)
-        if (cidx + k < ncell1) start[cidx + k] = s + pre[k];
-    }
+    // a directory word is four threads' cells: the first of the four collects the others' bits
+    const uint32_t b1 = __shfl_down(occ8, 1, 64), b2 = __shfl_down(occ8, 2, 64), b3 = __shfl_down(occ8, 3, 64);
+    if ((t & 3) == 0) wds[t >> 2] = DirWord{occ8 | (b1 << 8) | (b2 << 16) | (b3 << 24), sb + uint32_t(orun)};
+    if (t == T - 1) slots[sb + uint32_t(orun + nocc)] = e;  // closes the bucket's slots
   }
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
@@ -1274,6 +1300,7 @@ __global__ __launch_bounds__((1 << BITS) / 8, BITS == 12 ? 6 : 4) void k_bk_sort
     L.cnt[cl] = pre[k];
     if (v[k] == 0) continue;
     const int b = s + pre[k];  // the cell's first sorted position: identifies its sub-cells
+    slots[sb + uint32_t(orun) + __popc(occ8 & ((1u << k) - 1u))] = b;
     if (v[k] > kBkBig) {  // rare: the block orders the cell after sweep 2
       atomicOr(&L.big[cl >> 5], 1u << (cl & 31));
       L.any_big = 1;
@@ -1786,17 +1813,18 @@ int octant_zeroed_ints() { return 2 * kBkMax + 5 + kZeroedExtra; }
 // most ncell cells in nbk buckets (the plan's exact numbers, or the hint's bounds); the kernels
 // read the grid itself from d_plan.
 template <int BITS, bool F32>
-static void launch_bk_sort(Ctx* c, int64_t ncell, int64_t nbk, const int32_t* bstart, const void* bucketed,
+static void launch_bk_sort(Ctx* c, int64_t nbk, const int32_t* bstart, const void* bucketed,
                            const int32_t* keyb, uint32_t* word_tmp, int32_t* rank_tmp, PointRec* keyed,
                            const GridPlan* d_plan, DevGrid* g, SubCells* sub) {
   unsigned long long* const st_sort = stamp_slots(c, nbk);  // the binning's last kernel
-  hipLaunchKernelGGL((k_bk_sort<BITS, F32>), dim3(unsigned(nbk)), dim3((1 << BITS) / 8), 0, c->stream, ncell + 1, bstart,
-                     static_cast<const typename BkRec<F32>::type*>(bucketed), keyb, word_tmp, rank_tmp, g->start, g->order,
+  hipLaunchKernelGGL((k_bk_sort<BITS, F32>), dim3(unsigned(nbk)), dim3((1 << BITS) / 8), 0, c->stream, bstart,
+                     static_cast<const typename BkRec<F32>::type*>(bucketed), keyb, word_tmp, rank_tmp, g->dir_words,
+                     g->dir_slots, g->order,
                      g->cell_of, sub->sub_of, g->sx, g->sy, g->sz, g->p4, sub->rec, keyed, d_plan, st_sort);
 }
 
 static int enqueue_bucketed(Ctx* c, const double* xyz, int64_t n, const GridParams& gp, const int raw[3],
-                            AxisMap am, bool mapped, int64_t ncell, int64_t nbk, int bits, bool f32,
+                            AxisMap am, bool mapped, int64_t nbk, int bits, bool f32,
                             int32_t* zeroed, const GridPlan* d_plan, DevGrid* g, SubCells* sub) {
   int32_t *cell_tmp, *keyb, *rank_tmp, *bstart;
   uint32_t* word_tmp;
@@ -1806,7 +1834,11 @@ static int enqueue_bucketed(Ctx* c, const double* xyz, int64_t n, const GridPara
   g->p4 = nullptr;
   g->sx = g->sy = g->sz = nullptr;
   sub->sub_cnt = sub->sub_beg = nullptr;  // nothing reads them on this path: `rec` holds both
-  PQ_TRY(c->arena.get(size_t(ncell) + 1, &g->start));
+  // the ranked directory (grid.hpp, CellDir) instead of a dense start[ncell + 1]: a word per 32 cells of
+  // every bucket, and a slot per occupied cell plus one per bucket
+  g->start = nullptr;
+  PQ_TRY(c->arena.get(size_t(nbk) << (bits - 5), &g->dir_words));
+  PQ_TRY(c->arena.get(size_t(n) + size_t(nbk) + 1, &g->dir_slots));
   PQ_TRY(c->arena.get(size_t(n), &g->order));
   PQ_TRY(c->arena.get(size_t(n), &g->cell_of));
   if (f32) {
@@ -1834,17 +1866,58 @@ static int enqueue_bucketed(Ctx* c, const double* xyz, int64_t n, const GridPara
                d_plan);
   if (bits == 12) {
     if (f32)
-      launch_bk_sort<12, true>(c, ncell, nbk, bstart, bucketed, keyb, word_tmp, rank_tmp, keyed, d_plan, g, sub);
+      launch_bk_sort<12, true>(c, nbk, bstart, bucketed, keyb, word_tmp, rank_tmp, keyed, d_plan, g, sub);
     else
-      launch_bk_sort<12, false>(c, ncell, nbk, bstart, bucketed, keyb, word_tmp, rank_tmp, keyed, d_plan, g, sub);
+      launch_bk_sort<12, false>(c, nbk, bstart, bucketed, keyb, word_tmp, rank_tmp, keyed, d_plan, g, sub);
   } else {
     if (f32)
-      launch_bk_sort<13, true>(c, ncell, nbk, bstart, bucketed, keyb, word_tmp, rank_tmp, keyed, d_plan, g, sub);
+      launch_bk_sort<13, true>(c, nbk, bstart, bucketed, keyb, word_tmp, rank_tmp, keyed, d_plan, g, sub);
     else
-      launch_bk_sort<13, false>(c, ncell, nbk, bstart, bucketed, keyb, word_tmp, rank_tmp, keyed, d_plan, g, sub);
+      launch_bk_sort<13, false>(c, nbk, bstart, bucketed, keyb, word_tmp, rank_tmp, keyed, d_plan, g, sub);
   }
   PQ_HIP(hipGetLastError());
   return 0;
+}
+
+// The ranked directory from a dense one (the A/B binnings and grids beyond kBkMax buckets, which still
+// count into start[ncell + 1]): the per-bucket rule of k_bk_sort applied per word. Word w owns the slots
+// from start[32 w] + w: the begins of its occupied cells, then start[32 w + 32], the begin of whatever
+// comes next. A word has at most as many occupied cells as points, so the ranges do not overlap, and no
+// scan is needed. A thread per cell, two words per wave.
+__global__ __launch_bounds__(256) void k_dir_from_dense(int64_t ncell, const int32_t* __restrict__ start,
+                                                        DirWord* __restrict__ words, int32_t* __restrict__ slots) {
+  const int64_t c = int64_t(blockIdx.x) * 256 + threadIdx.x;  // the launch covers whole words
+  const int lane = threadIdx.x & 63, half = lane >> 5;
+  const int a = start[c < ncell ? c : ncell];
+  const int b = start[c + 1 < ncell ? c + 1 : ncell];
+  const uint32_t bits = uint32_t(__ballot(b != a) >> (32 * half));
+  const int64_t w = c >> 5;
+  const uint32_t base = uint32_t(__shfl(a, half * 32, 64)) + uint32_t(w);
+  if (w > (ncell >> 5)) return;  // (the launch's last block may reach past the last word)
+  if (b != a) slots[base + __popc(bits & ((1u << (lane & 31)) - 1u))] = a;
+  if ((lane & 31) == 31) slots[base + __popc(bits)] = b;
+  if ((lane & 31) == 0) words[w] = DirWord{bits, base};
+}
+
+static int dir_from_dense(Ctx* c, int64_t n, DevGrid* g) {
+  const int64_t nwords = (g->ncell >> 5) + 1;
+  PQ_TRY(c->arena.get(size_t(nwords), &g->dir_words));
+  PQ_TRY(c->arena.get(size_t(n) + size_t(nwords) + 1, &g->dir_slots));
+  hipLaunchKernelGGL(k_dir_from_dense, dim3(unsigned(ceil_div(nwords * 32, 256))), dim3(256), 0, c->stream, g->ncell,
+                     g->start, g->dir_words, g->dir_slots);
+  PQ_HIP(hipGetLastError());
+  return 0;
+}
+
+__global__ __launch_bounds__(256) void k_read_directory(int64_t ncell, const CellDir dir,
+                                                        int32_t* __restrict__ out) {
+  const int64_t c = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (c <= ncell) out[c] = dir.begin(int(c));
+}
+
+void read_directory(Ctx* c, const DevGrid& g, int64_t ncell, int32_t* begin_out) {
+  hipLaunchKernelGGL(k_read_directory, dim3(unsigned(ceil_div(ncell + 1, 256))), dim3(256), 0, c->stream, ncell,
+                     cell_dir(g), begin_out);
 }
 
 int bin_octants_planned(Ctx* c, const double* xyz, int64_t n, double cell, const PlanHint& hint,
@@ -1857,8 +1930,8 @@ int bin_octants_planned(Ctx* c, const double* xyz, int64_t n, double cell, const
   g->ncell = hint.ncell;
   sub->zeroed4 = zeroed + 2 * kBkMax + 1;
   const int raw[3] = {0, 0, 0};
-  return enqueue_bucketed(c, xyz, n, GridParams{}, raw, AxisMap{nullptr, nullptr, nullptr}, false, hint.ncell,
-                          hint.nbk, 12, true, zeroed, d_plan, g, sub);
+  return enqueue_bucketed(c, xyz, n, GridParams{}, raw, AxisMap{nullptr, nullptr, nullptr}, false, hint.nbk, 12,
+                          true, zeroed, d_plan, g, sub);
 }
 
 static int upload_plan(Ctx* c, const GridPlan& p, GridPlan* h_up, GridPlan* d_plan) {
@@ -1901,6 +1974,7 @@ int bin_octants_host(Ctx* c, const double* xyz, int64_t n, double min_cell, int6
     int32_t* zeroed4 = sub->zeroed4;
     PQ_TRY(subsort_octants(c, g, n, sub));
     sub->zeroed4 = zeroed4;
+    PQ_TRY(dir_from_dense(c, n, g));
     hp.nx = g->nx;
     hp.ny = g->ny;
     hp.nz = g->nz;
@@ -1993,7 +2067,7 @@ int bin_octants_host(Ctx* c, const double* xyz, int64_t n, double min_cell, int6
   PQ_TRY(upload_plan(c, hp, h_up, d_plan));
   const GridParams gp = grid_params(*g);
   if (bucketed_path) {
-    PQ_TRY(enqueue_bucketed(c, xyz, n, gp, raw, am, mapped, g->ncell, nbk, bits, hp.all_f32, zeroed, d_plan, g, sub));
+    PQ_TRY(enqueue_bucketed(c, xyz, n, gp, raw, am, mapped, nbk, bits, hp.all_f32, zeroed, d_plan, g, sub));
     // the kind of grid the bounding box's fold can plan: a hint with some headroom on the directory
     // (the same bucket size and the same side of the fused-scan threshold)
     if (!mapped && cell == min_cell && bits == 12 && hp.all_f32) {
@@ -2043,7 +2117,7 @@ int bin_octants_host(Ctx* c, const double* xyz, int64_t n, double min_cell, int6
                      c->stream, big_list, big_cnt, g->start, keyed, g->order, g->cell_of, sub->sub_of,
                      g->sx, g->sy, g->sz, g->p4, sub->sub_cnt, sub->sub_beg, sub->rec, d_plan);
   PQ_HIP(hipGetLastError());
-  return 0;
+  return dir_from_dense(c, n, g);
 }
 
 // ---- pyramid coarsening: a grid with cells `factor` times larger, without atomics ----

@@ -6,10 +6,53 @@
 // array: [start[row + cx - 1], start[row + cx + 2]) for each of the 9 (y,z) rows.
 // Points are counting-sorted by cell into SoA coordinate arrays (coalesced,
 // 8-byte loads per lane).
+//
+// Two forms of the directory `start`. build_grid (kNN, radius, features, normals, adjacency) keeps the
+// dense array, 4 bytes per cell. DBSCAN's octant binning keeps a RANKED directory instead (CellDir
+// below): an occupancy bitmap and a slot base per 32 cells plus the begins of the occupied cells
+// only, because a forest's grid is 99.6 % air and the dense array was a quarter of the binning's
+// traffic and far larger than an L2.
 #pragma once
 #include "common.hpp"
 
 namespace pyqsm {
+
+// ---- the ranked cell directory ----------------------------------------------------------------
+// Cell ids 32 w .. 32 w + 31 share words[w]: bit i says cell 32 w + i holds a point, and the begins
+// of the word's occupied cells lie at slots[base], slots[base + 1], ... in id order, followed by the
+// begin of the next occupied cell after them. So
+//   occupied(c) = (words[c >> 5].bits >> (c & 31)) & 1
+//   begin(c)    = slots[w.base + popc(w.bits & ((1u << (c & 31)) - 1))],   w = words[c >> 5]
+// and for every 0 <= c <= ncell, begin(c) is what a dense start[c] holds: the number of points in
+// cells with id < c (for an empty cell the begin of the next occupied one; begin(ncell) = n). The
+// count of a cell is begin(c + 1) - begin(c), and the stencil runs [begin(row - 1), begin(row + 2))
+// and wave_tile's linear intervals read as from the dense array. Any producer that keeps this
+// contract will do (k_bk_sort per bucket, k_dir_from_dense per word); consumers know only CellDir.
+struct alignas(8) DirWord {
+  uint32_t bits, base;
+};
+// (Kernels take the two arrays as `const ... __restrict__` parameters of their own and build the CellDir
+// in their first line: only then does the compiler know the tables as read-only, and a look-up at a
+// wave-uniform cell stays on the scalar path. With the struct as the parameter k_core_tiled's eighteen
+// bounds became vector loads: 58 VGPRs instead of 42.)
+struct CellDir {
+  const DirWord* words;
+  const int32_t* slots;
+  __device__ __forceinline__ static int slot_of(const DirWord w, int c) {
+    return int(w.base) + __popc(w.bits & ((1u << (c & 31)) - 1u));
+  }
+  __device__ __forceinline__ int begin(int c) const { return slots[slot_of(words[c >> 5], c)]; }
+  // begin() of N cells: the word loads side by side, then the slot loads side by side (two round
+  // trips, not N chains)
+  template <int N>
+  __device__ __forceinline__ void begins(const int (&c)[N], int (&out)[N]) const {
+    DirWord w[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) w[i] = words[c[i] >> 5];
+#pragma unroll
+    for (int i = 0; i < N; ++i) out[i] = slots[slot_of(w[i], c[i])];
+  }
+};
 
 struct DevGrid {
   double minx, miny, minz;
@@ -17,7 +60,10 @@ struct DevGrid {
   double cell;
   int nx, ny, nz;        // including the border cells
   int64_t ncell;         // nx*ny*nz
-  int32_t* start;        // [ncell + 1] first sorted position of each cell
+  int32_t* start;        // [ncell + 1] first sorted position of each cell (null from the two-level octant binning)
+  // the ranked directory (DBSCAN's octant binning only; see CellDir)
+  DirWord* dir_words = nullptr;
+  int32_t* dir_slots = nullptr;
   int32_t* order;        // [n] sorted position -> original index
   int32_t* cell_of;      // [n] cell id of each sorted position
   double *sx, *sy, *sz;  // [n] sorted coordinates (fp64 storage)
@@ -38,6 +84,7 @@ struct GridParams {
   double minx, miny, minz, inv_cell;
   int nx, ny, nz;
 };
+inline CellDir cell_dir(const DevGrid& g) { return CellDir{g.dir_words, g.dir_slots}; }
 inline GridParams grid_params(const DevGrid& g) { return GridParams{g.minx, g.miny, g.minz, g.inv_cell, g.nx, g.ny, g.nz}; }
 
 // The cell a point is binned into, and the cell every lookup of it must use: interior cells are
@@ -189,8 +236,7 @@ struct Tile {
   int total;
 };
 
-__device__ __forceinline__ Tile wave_tile(int p0, int n, Stencil st, int ncell,
-                                          const int32_t* __restrict__ start,
+__device__ __forceinline__ Tile wave_tile(int p0, int n, Stencil st, int ncell, const CellDir& dir,
                                           const int32_t* __restrict__ cell_of) {
   Tile t;
   const int plast = p0 + 63 < n ? p0 + 63 : n - 1;
@@ -200,33 +246,45 @@ __device__ __forceinline__ Tile wave_tile(int p0, int n, Stencil st, int ncell,
   // fewer than three rows), then clipped against what the earlier ones cover: a wave
   // that spans more than a grid row makes neighbouring intervals overlap
   int lo[9], hi[9];
-  int w = 0;
-  for (int dz = -1; dz <= 1; ++dz)
-    for (int dy = -1; dy <= 1; ++dy) {
-      const int o = dy * st.nx + dz * st.nxy;
-      int a = c_first + o - 1, b = c_last + o + 1;
-      a = a < 0 ? 0 : a;
-      b = b > ncell - 1 ? ncell - 1 : b;
-      int k = w++;
-      while (k > 0 && lo[k - 1] > a) {
-        lo[k] = lo[k - 1];
-        hi[k] = hi[k - 1];
-        --k;
-      }
-      lo[k] = a;
-      hi[k] = b;
+#pragma unroll
+  for (int w = 0; w < 9; ++w) {
+    const int o = (w % 3 - 1) * st.nx + (w / 3 - 1) * st.nxy;
+    const int a = c_first + o - 1, b = c_last + o + 1;
+    lo[w] = a < 0 ? 0 : a;
+    hi[w] = b > ncell - 1 ? ncell - 1 : b;
+  }
+  // (a stable insertion sort as compare-and-swap steps at fixed positions: everything stays in SGPRs)
+#pragma unroll
+  for (int i = 1; i < 9; ++i)
+#pragma unroll
+    for (int k = i; k > 0; --k) {
+      const bool sw = lo[k - 1] > lo[k];
+      const int l0 = lo[k - 1], h0 = hi[k - 1];
+      lo[k - 1] = sw ? lo[k] : l0;
+      hi[k - 1] = sw ? hi[k] : h0;
+      lo[k] = sw ? l0 : lo[k];
+      hi[k] = sw ? h0 : hi[k];
     }
-  t.total = 0;
+  // the eighteen bounds are wave-uniform: their words are asked for together, then their slots
+  // (an interval that the earlier ones cover reads entry 0 twice: an empty run)
+  int cells[18], q[18];
   int prev_hi = -1;
+#pragma unroll
   for (int r = 0; r < 9; ++r) {
     const int a = lo[r] <= prev_hi ? prev_hi + 1 : lo[r];
+    cells[2 * r] = cells[2 * r + 1] = 0;
     if (a <= hi[r]) {
-      t.qb[r] = __builtin_amdgcn_readfirstlane(start[a]);
-      t.qe[r] = __builtin_amdgcn_readfirstlane(start[hi[r] + 1]);
+      cells[2 * r] = a;
+      cells[2 * r + 1] = hi[r] + 1;
       prev_hi = hi[r];
-    } else {
-      t.qb[r] = t.qe[r] = 0;
     }
+  }
+  dir.begins(cells, q);
+  t.total = 0;
+#pragma unroll
+  for (int r = 0; r < 9; ++r) {
+    t.qb[r] = __builtin_amdgcn_readfirstlane(q[2 * r]);
+    t.qe[r] = __builtin_amdgcn_readfirstlane(q[2 * r + 1]);
     t.total += t.qe[r] - t.qb[r];
   }
   return t;
@@ -313,6 +371,10 @@ int bin_octants_planned(Ctx* c, const double* xyz, int64_t n, double cell, const
 int bin_octants_host(Ctx* c, const double* xyz, int64_t n, double min_cell, int64_t max_cells, const GridPlan& box,
                      int32_t* zeroed, GridPlan* h_up, GridPlan* d_plan, DevGrid* g, SubCells* sub,
                      PlanHint* hint_out);
+
+// The device begin(c) of g's ranked directory for c = 0 .. ncell into begin_out (device, [ncell + 1]):
+// the read-out the tests compare with a dense count (ncell: the plan's, read on the host by the caller).
+void read_directory(Ctx* c, const DevGrid& g, int64_t ncell, int32_t* begin_out);
 
 // A grid with cells `factor` times larger over the same points, derived from `fine`
 // by block sums and a deterministic scatter (no atomics, no second pass over xyz).

@@ -229,6 +229,18 @@ def dbscan_dev(xyz_ptr: int, n: int, eps: float, min_pts: int, labels_ptr: int,
     return int(cnt.value) if want_count else None
 
 
+def octant_directory(points, eps: float, device: int = 0, cap: int = 1 << 25):
+    """The cell directory DBSCAN bins ``points`` with at ``eps``, read out on the device (for tests):
+    ``dims`` int32 [3] (cells per axis, borders included) and ``begin`` int32 [prod(dims) + 1],
+    ``begin[c]`` = points in cells with id < c. Grids of more than ``cap`` entries: PYQSM_ERANGE."""
+    pts = _points(points)
+    dims = np.zeros(3, dtype=np.int32)
+    begin = np.empty(int(cap), dtype=np.int32)
+    check(_lib.load().pyqsm_octant_directory(_p(pts), pts.shape[0], float(eps), _p(dims), _p(begin), int(cap),
+                                             int(device)))
+    return dims, begin[: int(np.prod(dims.astype(np.int64))) + 1].copy()
+
+
 def knn(points, k: int, exclude_self: bool = True, device: int = 0):
     """idx int32 [n,k], squared distances float64 [n,k], ascending by (d2, index)."""
     pts = _points(points)
