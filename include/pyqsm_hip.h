@@ -446,6 +446,65 @@ int pyqsm_alpha_area(const int32_t* ij, int64_t n, const int64_t* seg_start, int
                      int64_t max_tests, int32_t flags, int64_t* twice_area, int64_t* n_live, int64_t* n_boundary,
                      int64_t** edges, int64_t* stats, int32_t device);
 
+/* ---- mesh checks: edge table, clusters, manifoldness, self-intersection -------- */
+/*
+ * What pyQSM's geometry/mesh_processing.py asks of Open3D before a mesh is cast at, by a contract
+ * of integer decisions and a fixed output order. Everything is decided by
+ * vertex INDEX, as Open3D does: nothing is welded.
+ *
+ * pyqsm_mesh_topology
+ *   tris i32 [n_tris,3]; verts f64 [n_verts,3] or NULL (then no areas: *cluster_area stays NULL).
+ *   Allocated by the library, released with pyqsm_free (NULL when n_tris == 0):
+ *     *edges i32 [E,2]       the undirected edges (a < b), ascending by (a, b)
+ *     *edge_count i32 [E]    triangles at each edge
+ *     *edge_flags u8 [E]     1 boundary (one triangle); 2 more than two triangles; 4 exactly two
+ *                            triangles that traverse the edge in the SAME direction (a winding
+ *                            conflict as the mesh is given)
+ *     *cluster_n i64 [C], *cluster_area f64 [C]
+ *   tri_cluster i32 [n_tris]: triangles that share an edge are connected; the clusters are numbered
+ *     by ascending smallest member triangle. The area of a triangle is
+ *     0.5 * sqrt((cx*cx + cy*cy) + cz*cz), c = (v1 - v0) x (v2 - v0), every component a*b - c*d
+ *     without fused multiply-adds; a cluster's areas are added in a fixed order without
+ *     floating-point atomics (the same bits on every run), |sum - exact| <= (n_c + 4) 2^-52 exact.
+ *   vertex_flags u8 [n_verts]: 1 where the triangles at the vertex are not ONE set under "share an
+ *     edge that contains this vertex" (Open3D's fan test); a vertex without triangles is manifold.
+ *   summary i64 [8]: E, boundary edges, edges with more than two triangles, same-direction edges,
+ *     non-manifold vertices, clusters, orientable (0 / 1), vertices without a triangle.
+ *     Orientable: some choice of flips makes every two triangles at a shared edge traverse it in
+ *     opposite directions; an edge with more than two triangles rules that out.
+ *   An index outside [0, n_verts) or a triangle that repeats an index: PYQSM_EINVAL;
+ *   n_tris >= 2^29: PYQSM_ERANGE; both before any launch. n_tris == 0 launches nothing.
+ *
+ * pyqsm_mesh_self_intersections
+ *   ijk i32 [n_verts,3] lattice coordinates, at most 2^20 units of extent per axis (PYQSM_EINVAL
+ *   beyond: every orient3d determinant then fits int64). A pair i < j of triangles is reported iff
+ *   they share no vertex index, neither is degenerate (its three lattice vertices collinear or
+ *   coincident) and the two closed triangles have a common point: piercing, touching at a vertex,
+ *   an edge or a face, coplanar overlap. Integer predicates only.
+ *   *n_pairs: the number of such pairs; tri_hit u8 [n_tris]: 1 for a triangle of some pair.
+ *   flags: PYQSM_MESH_PAIRS  *pairs receives i32 [*n_pairs,2], ascending by (i, j), never truncated;
+ *            allocated by the library, released with pyqsm_free; NULL when there is none (pairs
+ *            itself may be NULL without the flag).
+ *   max_tests: n_tris (n_tris - 1) / 2 above it is refused with PYQSM_ERANGE before any launch;
+ *     <= 0: PYQSM_MESH_DEFAULT_MAX_TESTS = 1.6e13, ten seconds at 1.6e12 box tests per second: one
+ *     MI355X sweeps the 1.25e11 pairs of 500 000 triangles at 1.66e12 pairs per second on an unwelded
+ *     canopy soup and at 2.17e12 on a welded closed surface (tools/mesh_perf.py,
+ *     profiles/mesh_perf.jsonl); the lower rate, rounded down. A value of 0
+ *     would mean "no default": max_tests <= 0 is then refused with PYQSM_EINVAL.
+ *   stats i64 [6] or NULL: pairs considered, pairs whose boxes overlap, of those skipped for a
+ *     shared index, degenerate triangles, exact tests run, pairs reported.
+ *   The sweep works on tiles of PYQSM_MESH_TILE_ROWS triangles. More than 2^26 triangles: PYQSM_ERANGE.
+ */
+#define PYQSM_MESH_PAIRS 1
+#define PYQSM_MESH_TILE_ROWS 256
+#define PYQSM_MESH_DEFAULT_MAX_TESTS 16000000000000LL
+int pyqsm_mesh_topology(const int32_t* tris, int64_t n_tris, int64_t n_verts, const double* verts, int32_t** edges,
+                        int32_t** edge_count, uint8_t** edge_flags, int32_t* tri_cluster, int64_t** cluster_n,
+                        double** cluster_area, uint8_t* vertex_flags, int64_t* summary, int32_t device);
+int pyqsm_mesh_self_intersections(const int32_t* ijk, int64_t n_verts, const int32_t* tris, int64_t n_tris,
+                                  int32_t flags, int64_t max_tests, int64_t* n_pairs, int32_t** pairs,
+                                  uint8_t* tri_hit, int64_t* stats, int32_t device);
+
 /* ---- farthest-point down-sampling ---------------------------------------- */
 /*
  * Stands in for open3d PointCloud.farthest_point_down_sample(num_samples) as

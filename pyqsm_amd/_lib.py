@@ -75,6 +75,11 @@ SIGNATURES = {
                                                vp, vp, ctypes.POINTER(i64), vp, i32]),
     "pyqsm_alpha_area": (ctypes.c_int, [vp, i64, vp, i64, ctypes.c_uint64, i64, i32, vp, vp, vp,
                                         ctypes.POINTER(vp), vp, i32]),
+    "pyqsm_mesh_topology": (ctypes.c_int, [vp, i64, i64, vp, ctypes.POINTER(vp), ctypes.POINTER(vp),
+                                           ctypes.POINTER(vp), vp, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp,
+                                           i32]),
+    "pyqsm_mesh_self_intersections": (ctypes.c_int, [vp, i64, vp, i64, i32, i64, ctypes.POINTER(i64),
+                                                     ctypes.POINTER(vp), vp, vp, i32]),
     "pyqsm_fps": (ctypes.c_int, [vp, i64, i64, i64, vp, i32]),
     "pyqsm_pc_laplacian": (ctypes.c_int, [vp, i64, i32, dbl, ctypes.POINTER(i64),
                                           ctypes.POINTER(vp), ctypes.POINTER(vp),

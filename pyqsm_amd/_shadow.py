@@ -6,7 +6,7 @@ pyQSM/pipeline.py:8). With this directory AHEAD of pyQSM's on ``sys.path``:
 
 * ``geometry/``, ``math_utils/``, ``viz/`` and ``utils/`` hold no ``__init__.py`` on either side,
   so they are namespace packages whose portions merge: ``math_utils.fit`` is this package's,
-  ``utils.io`` / ``geometry.mesh_processing`` / ``viz.color`` are still pyQSM's;
+  ``utils.io`` / ``geometry.surf_recon`` / ``viz.color`` are still pyQSM's;
 * a module that exists on BOTH sides (``math_utils/fit.py``, ``geometry/point_cloud_processing.py``,
   ``qsm_generation.py`` …) resolves to this package's, which only restates the hot-path functions.
   Every other name of the shadowed module (``kmeans``, ``clean_cloud``, ``crop_by_percentile``,

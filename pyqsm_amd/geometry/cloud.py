@@ -254,6 +254,87 @@ class TriangleMesh:
         keep = (tris >= 0).all(axis=1)
         return TriangleMesh(self.vertices[vid], tris[keep])
 
+    # ---- mesh checks on the GPU (hip.mesh_topology / hip.mesh_self_intersections).
+    # Everything is decided by vertex index, as in Open3D: coincident vertices are not welded.
+    # Every method below runs the whole topology call (or the whole sweep) for its one answer: for
+    # several answers about one mesh call mesh_processing.check_properties, or hip.mesh_topology, once.
+
+    def _topology(self, areas: bool = False, device: int = 0):
+        verts = np.asarray(self.vertices, dtype=np.float64) if areas else None
+        return _hip().mesh_topology(self.triangles, len(self.vertices), verts, device=device)
+
+    def _intersections(self, return_pairs: bool, max_tests=None, device: int = 0):
+        from .mesh_processing import quantize_mesh
+        ijk = quantize_mesh(self.vertices)[0]
+        return _hip().mesh_self_intersections(ijk, self.triangles, return_pairs=return_pairs, max_tests=max_tests,
+                                              device=device)
+
+    def cluster_connected_triangles(self, device: int = 0):
+        """Open3D's ``cluster_connected_triangles``: ``(triangle_clusters int32 [T],
+        cluster_n_triangles int64 [C], cluster_area float64 [C])``; triangles that share an edge are
+        connected. Unlike Open3D (whose numbering follows its search order) the clusters are
+        numbered by their smallest triangle."""
+        top = self._topology(areas=True, device=device)
+        return top.tri_cluster, top.cluster_n, top.cluster_area
+
+    def get_non_manifold_edges(self, allow_boundary_edges: bool = True, device: int = 0) -> np.ndarray:
+        """int32 [r, 2]: the edges with more than two triangles, and with
+        ``allow_boundary_edges=False`` those with one triangle too; ascending by (a, b)."""
+        top = self._topology(device=device)
+        bad = top.edge_count > 2 if allow_boundary_edges else top.edge_count != 2
+        return top.edges[bad]
+
+    def is_edge_manifold(self, allow_boundary_edges: bool = True, device: int = 0) -> bool:
+        """No edge with more than two triangles (nor, with ``allow_boundary_edges=False``, with one).
+        One topology call per answer: ``mesh_processing.check_properties`` gives all of them at once."""
+        s = self._topology(device=device).summary
+        return s["over_two_edges"] == 0 and (allow_boundary_edges or s["boundary_edges"] == 0)
+
+    def get_non_manifold_vertices(self, device: int = 0) -> np.ndarray:
+        """int64 indices, ascending, of the vertices whose triangles do not form one fan."""
+        return np.nonzero(self._topology(device=device).vertex_flags)[0]
+
+    def is_vertex_manifold(self, device: int = 0) -> bool:
+        """The triangles at every vertex form one fan (see ``check_properties`` for several answers)."""
+        return self._topology(device=device).summary["non_manifold_vertices"] == 0
+
+    def is_orientable(self, device: int = 0) -> bool:
+        """Some choice of flips makes all triangles at shared edges agree. A mesh with an edge of
+        more than two triangles is not orientable here (Open3D's answer there depends on its
+        search order)."""
+        return bool(self._topology(device=device).summary["orientable"])
+
+    def get_self_intersecting_triangles(self, max_tests=None, device: int = 0) -> np.ndarray:
+        """int32 [n, 2] pairs ``i < j`` of intersecting triangles, ascending (Open3D's order comes
+        from its loop). Exact for the mesh snapped to a lattice: ``mesh_processing.quantize_mesh``."""
+        return self._intersections(True, max_tests, device).pairs
+
+    def is_self_intersecting(self, max_tests=None, device: int = 0) -> bool:
+        """``max_tests`` caps the brute-force sweep's T (T - 1) / 2 pairs (``hip.mesh_self_intersections``)."""
+        return self._intersections(False, max_tests, device).n_pairs > 0
+
+    def is_watertight(self, max_tests=None, device: int = 0) -> bool:
+        """Edge-manifold without boundary, vertex-manifold and not self-intersecting (Open3D): one
+        topology call and one sweep, as ``mesh_processing.check_properties``, which also says why not."""
+        s = self._topology(device=device).summary
+        return (s["over_two_edges"] == 0 and s["boundary_edges"] == 0 and s["non_manifold_vertices"] == 0
+                and not self.is_self_intersecting(max_tests=max_tests, device=device))
+
+    def remove_triangles_by_mask(self, mask) -> "TriangleMesh":
+        """Open3D's ``remove_triangles_by_mask``: drops the triangles where ``mask`` is true, in
+        place; the vertices stay. Host NumPy."""
+        m = np.asarray(mask, dtype=bool).reshape(-1)
+        if m.shape[0] != len(self.triangles):
+            raise ValueError(f"one mask entry per triangle: {m.shape[0]} for {len(self.triangles)}")
+        self.triangles = self.triangles[~m]
+        return self
+
+    def remove_degenerate_triangles(self) -> "TriangleMesh":
+        """Open3D's ``remove_degenerate_triangles``: drops the triangles that repeat a vertex index,
+        in place. Host NumPy."""
+        t = self.triangles
+        return self.remove_triangles_by_mask((t[:, 0] == t[:, 1]) | (t[:, 1] == t[:, 2]) | (t[:, 0] == t[:, 2]))
+
 
 class Cylinder:
     """The primitive fit_shape_RANSAC returns (the reference builds an Open3D
