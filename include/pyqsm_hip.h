@@ -505,6 +505,46 @@ int pyqsm_mesh_self_intersections(const int32_t* ijk, int64_t n_verts, const int
                                   int32_t flags, int64_t max_tests, int64_t* n_pairs, int32_t** pairs,
                                   uint8_t* tri_hit, int64_t* stats, int32_t device);
 
+/* ---- surface reconstruction: exact ball pivoting of lattice points ------------- */
+/*
+ * The triangles a ball of radius rho can rest on from the normals' side (the alpha-exposed facets of
+ * the alpha shape, alpha = rho): an order-free, exact stand-in for Open3D's
+ * create_from_point_cloud_ball_pivoting, whose front depends on its traversal.
+ *   ijk i32 [n,3] lattice coordinates (at most 2^31 - 1 units of extent per axis); normals i16 [n,3],
+ *   rint(n * 2^14). rho2 u64 [n_levels]: rho^2 in lattice units^2, ascending, each in
+ *   [1, PYQSM_RECON_MAX_RHO2] (PYQSM_EINVAL beyond, with the factor by which the quantum must grow).
+ * An oriented triple (a, b, c), n = (b - a) x (c - a), is emitted at a level iff the three vertex
+ * normals have a strictly positive dot product with n, the ball of radius rho through a, b, c with
+ * its centre on the +n side exists (circumradius <= rho) and holds no other point strictly inside.
+ * Points exactly on the ball: if all of them lie in the triangle's plane the triple is kept iff its
+ * smallest index is the smallest among them too and none lies strictly beyond the edge opposite that
+ * vertex (the fan from the smallest index); otherwise it is kept and counted in stats[4].
+ * Levels after the first accept a triple only if none of its vertices is inner (has triangles, and
+ * every incident half-edge has its reverse) and none of its directed half-edges exists already.
+ *   *tris receives i32 [*n_tris,4] rows (a, b, c, level), a the smallest index, ascending by
+ *   (a, b, c); allocated by the library, released with pyqsm_free; NULL when there is none. The same
+ *   bytes on every run. More than 8 n + 1024 triangles, or more than 2^26 points: PYQSM_ERANGE.
+ * max_tests: the call is refused with PYQSM_ERANGE when the estimated pair tests of a level, the sum over
+ *   the points of (points in the 27-cell stencil)^2, exceed it; <= 0: PYQSM_RECON_DEFAULT_MAX_TESTS = 1e12,
+ *   ten seconds at the 1.1e11 estimated pair tests per second of the triangle pass measured on one MI355X
+ *   (profiles/recon_perf.jsonl), rounded down. The estimate needs the level's grid:
+ *   the binning kernels of the levels up to the refused one have run by then, but no triangle pass of ANY
+ *   level has (with several radii every level is binned and estimated first).
+ * stats i64 [8] or NULL: estimated pair tests (all levels so far), ball tests run (candidates x stencil),
+ *   of those classified by the wide integers, candidate triples, triangles kept with a tie point off
+ *   their plane, the largest stencil, the most points in one cell, blocks launched. All but one are the
+ *   same on every run; the count of wide-integer classifications is not: a lane stops at the first point
+ *   inside its ball, and the order of the points within a grid cell, which decides what it meets before
+ *   that, is the binning's arrival order. No triangle depends on it.
+ * Fewer than three points: no triangle, no device work.
+ */
+#define PYQSM_RECON_MAX_RHO2 4194304ULL /* 2^22: rho <= 2^11 lattice units */
+#define PYQSM_RECON_CHUNK 1024
+#define PYQSM_RECON_SLICE 16
+#define PYQSM_RECON_DEFAULT_MAX_TESTS 1000000000000LL
+int pyqsm_ball_pivot(const int32_t* ijk, const int16_t* normals, int64_t n, const uint64_t* rho2, int32_t n_levels,
+                     int64_t max_tests, int64_t* n_tris, int32_t** tris, int64_t* stats, int32_t device);
+
 /* ---- farthest-point down-sampling ---------------------------------------- */
 /*
  * Stands in for open3d PointCloud.farthest_point_down_sample(num_samples) as

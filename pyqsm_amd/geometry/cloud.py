@@ -160,6 +160,14 @@ class PointCloud:
         ind = _hip().stat_outlier(self.points, nb_neighbors, std_ratio, device=device)
         return self.select_by_index(ind), ind
 
+    def compute_nearest_neighbor_distance(self, device: int = 0) -> np.ndarray:
+        """Open3D's ``compute_nearest_neighbor_distance``: float64 [n], the distance from every point
+        to its nearest other point (``hip.knn`` with k = 1; 0 for coincident points). Open3D returns
+        a list; fewer than two points give zeros, as there."""
+        if len(self.points) < 2:
+            return np.zeros(len(self.points))
+        return np.sqrt(_hip().knn(self.points, 1, exclude_self=True, device=device)[1][:, 0])
+
     def get_min_bound(self):
         return self.points.min(axis=0)
 
@@ -227,6 +235,89 @@ class TriangleMesh:
     def __init__(self, vertices, triangles):
         self.vertices = np.asarray(vertices)
         self.triangles = np.asarray(triangles, dtype=np.int64)
+
+    # ---- surface reconstruction on the GPU (hip.ball_pivot)
+
+    @staticmethod
+    def create_from_point_cloud_ball_pivoting(pcd, radii, quantum=None, device: int = 0, *, max_tests=None):
+        """Open3D's ``create_from_point_cloud_ball_pivoting`` by a contract of its own: every triangle
+        of cloud points on which a ball of one of the ``radii`` can rest from the normals' side
+        without holding another point, decided exactly on the cloud SNAPPED to a lattice
+        (``hip.ball_pivot``). Order-free and the same bits on every run; it is NOT
+        Open3D's triangle list, whose front depends on its traversal order, and parity with it is
+        unverified. Non-manifold configurations are not repaired:
+        ``mesh_processing.check_properties`` reports them.
+
+        ``pcd`` needs ``.points`` and ``.normals``. ``radii`` (any order) are processed ascending.
+        ``quantum``: the lattice pitch, a power of two; default the larger of
+        ``mesh_processing.quantize_mesh``'s (extent / 2^20) and the smallest at which the largest
+        radius is at most 2^11 lattice units, the kernel's bound. Points snap to
+        ``rint(p / quantum)``, normals to ``rint(n * 2^14)``, a radius to
+        ``floor((r / quantum)^2)`` as its square. ``max_tests``: ``hip.ball_pivot``'s work cap. The result keeps the cloud's points as vertices
+        (all of them, in order) and carries ``triangle_levels`` (index into the ascending radii),
+        ``n_unresolved_ties`` and ``quantum``."""
+        import math
+        from .mesh_processing import _check_quantum, _quantum_for
+        hip = _hip()
+        pts = as_points(pcd)
+        nrm = getattr(pcd, "normals", None)
+        if nrm is None or len(np.asarray(nrm)) != len(pts):
+            raise ValueError("the cloud has no normals: estimate_normals and "
+                             "orient_normals_consistent_tangent_plane first")
+        if not np.isfinite(pts).all():
+            raise ValueError("point coordinates must be finite")
+        r = np.sort(np.asarray(list(radii), dtype=np.float64).reshape(-1))
+        if r.size == 0 or not np.isfinite(r).all() or r[0] <= 0:
+            raise ValueError("radii must be positive and finite")
+        max_rho = float(1 << 11)
+        m, e = math.frexp(float(r[-1]) / max_rho)          # the smallest power of two >= r / 2^11
+        q_fit = math.ldexp(1.0, e - 1 if m == 0.5 else e)
+        if quantum is None:
+            ext = float((pts.max(axis=0) - pts.min(axis=0)).max()) if len(pts) else 0.0
+            q = max(_quantum_for(ext), q_fit)
+        else:
+            q = _check_quantum(quantum)
+            if r[-1] / q > max_rho:
+                raise ValueError(f"radius {float(r[-1])!r} is {r[-1] / q:.0f} lattice units at quantum {q!r}, more "
+                                 f"than 2^11: a quantum of {q_fit!r} would fit")
+        rho2 = [int(np.floor((x / q) ** 2)) for x in r]
+        if rho2[0] < 1:
+            raise ValueError(f"radius {float(r[0])!r} is below the quantum {q!r}")
+        scaled = np.rint(pts / q)
+        if len(pts) and np.abs(scaled).max() >= 2.0 ** 62:
+            raise ValueError("quantum is too small for these coordinates")
+        lat = scaled.astype(np.int64)
+        if len(pts):
+            lat -= lat.min(axis=0)
+            if lat.max() >= 1 << 31:
+                raise ValueError(f"the cloud spans {int(lat.max())} lattice units at quantum {q!r}, more than "
+                                 "2^31: use a larger quantum")
+        res = hip.ball_pivot(lat.astype(np.int32), hip.snap_normals(_normalized(nrm)), rho2, max_tests=max_tests,
+                             device=device)
+        mesh = TriangleMesh(pts, res.triangles)
+        mesh.triangle_levels = res.levels
+        mesh.n_unresolved_ties = res.n_unresolved_ties
+        mesh.quantum = q
+        mesh.stats = res.stats
+        return mesh
+
+    def compute_vertex_normals(self, normalized: bool = True) -> "TriangleMesh":
+        """Open3D's ``compute_vertex_normals``, minimal: the sum of the (area-weighted) normals of
+        the triangles at each vertex, normalised; a vertex without triangles gets (0, 0, 1) as in
+        Open3D. Host NumPy; sets ``vertex_normals`` and ``triangle_normals``."""
+        v = np.asarray(self.vertices, dtype=np.float64)
+        t = self.triangles
+        fn = np.cross(v[t[:, 1]] - v[t[:, 0]], v[t[:, 2]] - v[t[:, 0]]) if len(t) else np.zeros((0, 3))
+        vn = np.zeros_like(v)
+        for k in range(3):
+            np.add.at(vn, t[:, k], fn)
+        if normalized:
+            ln = np.linalg.norm(vn, axis=1)
+            vn[ln > 0] /= ln[ln > 0, None]
+            vn[ln == 0] = (0.0, 0.0, 1.0)
+        self.triangle_normals = _normalized(fn)
+        self.vertex_normals = vn
+        return self
 
     def get_center(self):
         return self.vertices.mean(axis=0)

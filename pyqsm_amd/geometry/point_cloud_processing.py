@@ -15,7 +15,7 @@ try:
     from .. import hip
     from .._shadow import fall_through
     from ..set_config import config, log
-    from .cloud import PointCloud, as_points
+    from .cloud import PointCloud, TriangleMesh, as_points
 except ImportError:  # flat import (pyqsm_amd/ on sys.path)
     import os
     import sys
@@ -23,7 +23,7 @@ except ImportError:  # flat import (pyqsm_amd/ on sys.path)
     from pyqsm_amd import hip
     from pyqsm_amd._shadow import fall_through
     from pyqsm_amd.set_config import config, log
-    from pyqsm_amd.geometry.cloud import PointCloud, as_points
+    from pyqsm_amd.geometry.cloud import PointCloud, TriangleMesh, as_points
 
 # names pyQSM's module of the same name defines and this one does not (pyqsm_amd/_shadow.py)
 __getattr__ = fall_through(__name__)
@@ -99,3 +99,10 @@ def filter_by_norm(pcd, angle_thresh=10, rev=False):
     else:
         stem_idxs = np.where((angles > -angle_thresh) & (angles < angle_thresh))[0]
     return pcd.select_by_index(stem_idxs)
+
+
+def get_ball_mesh(pcd, radii=[0.005, 0.01, 0.02, 0.04], device: int = 0):
+    """point_cloud_processing.py:259-263: the ball-pivoted mesh of a cloud with oriented normals, by
+    ``TriangleMesh.create_from_point_cloud_ball_pivoting`` of this package (exact on the snapped
+    cloud, order-free; not Open3D's triangle list: DESIGN.md §19)."""
+    return TriangleMesh.create_from_point_cloud_ball_pivoting(pcd, radii, device=device)

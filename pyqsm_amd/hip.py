@@ -766,6 +766,102 @@ def mesh_self_intersections(ijk, tris, return_pairs: bool = True, max_tests: int
     return MeshIntersections(int(n_pairs.value), pairs, hit[:nt], stats)
 
 
+# ---------------------------------------------------------------- surface reconstruction (ball pivoting)
+
+RECON_MAX_RHO2 = 1 << 22        # PYQSM_RECON_MAX_RHO2: rho <= 2^11 lattice units
+RECON_CHUNK = 1024              # PYQSM_RECON_CHUNK: stencil points staged in LDS at a time
+RECON_SLICE = 16                # PYQSM_RECON_SLICE: points of a cell one block serves
+RECON_DEFAULT_MAX_TESTS = 1_000_000_000_000   # PYQSM_RECON_DEFAULT_MAX_TESTS: ten seconds at 1.1e11 pair tests/s
+RECON_NORMAL_SCALE = 1 << 14    # normals are snapped to rint(n * 2^14), int16
+
+
+class BallPivotRefused(_lib.PyQSMHipError, ValueError):
+    """``pyqsm_ball_pivot`` refused its input (``PYQSM_EINVAL``, ``PYQSM_ERANGE``: a radius or a cloud
+    outside the bounds, an estimate above ``max_tests``, too many triangles). A ``ValueError`` like the
+    refusals :func:`ball_pivot` raises before it calls the library; ``.stats`` holds the call's counters."""
+
+
+class BallPivot(NamedTuple):
+    """Results of :func:`ball_pivot`."""
+    triangles: np.ndarray           # int32 [T, 3], smallest index first, ascending by (a, b, c)
+    levels: np.ndarray              # int32 [T] index into the ascending radii
+    n_unresolved_ties: int          # triangles kept although a point off their plane lies on their ball
+    stats: dict
+
+
+def snap_normals(normals) -> np.ndarray:
+    """int16 [n,3]: ``rint(n * 2^14)`` of unit (or shorter) normals, as :func:`ball_pivot` takes them."""
+    v = np.asarray(normals, dtype=np.float64)
+    if v.ndim != 2 or v.shape[1] != 3:
+        raise ValueError(f"expected normals of shape [n,3], got {v.shape}")
+    if not np.isfinite(v).all():
+        raise ValueError("normals must be finite")
+    if v.size and np.abs(v).max() > 1.0 + 1e-9:
+        raise ValueError("normals must have unit length or less")
+    return np.rint(v * RECON_NORMAL_SCALE).astype(np.int16)
+
+
+def ball_pivot(ijk, normals_i16, rho2_list, max_tests: int | None = None, device: int = 0) -> BallPivot:
+    """The triangles of lattice points a ball of radius rho rests on from the normals' side, decided by
+    integer predicates only: ``ijk`` int32 [n,3], ``normals_i16`` int16 [n,3]
+    (:func:`snap_normals`), ``rho2_list`` the squared radii in lattice units^2, processed ascending,
+    each at most ``RECON_MAX_RHO2``. ``max_tests`` (default ``RECON_DEFAULT_MAX_TESTS``) refuses a call in
+    which the estimated pair tests of a level exceed it, before the triangle pass of any level runs
+    (the binning that the estimate needs has run). Refusals are ``ValueError``s: raised here, or as
+    :class:`BallPivotRefused` when the library refuses. ``stats["exact_fallbacks"]`` may differ between
+    runs (it depends on the order of the points within a grid cell); nothing else does."""
+    p = np.asarray(ijk)
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise ValueError(f"expected lattice points of shape [n,3], got {p.shape}")
+    if p.size and not np.issubdtype(p.dtype, np.integer):
+        raise ValueError("lattice points must be integers")
+    if p.size and (p.min() < -(1 << 31) or p.max() >= (1 << 31)):
+        raise ValueError("lattice points must fit int32")
+    if p.size and int(p.max()) - int(p.min()) >= (1 << 31):
+        raise ValueError("the cloud spans more than 2^31 lattice units")
+    p = np.ascontiguousarray(p, dtype=np.int32)
+    n = p.shape[0]
+    nr = np.asarray(normals_i16)
+    if nr.shape != (n, 3):
+        raise ValueError(f"expected normals of shape [{n},3], got {nr.shape}")
+    if nr.size and not np.issubdtype(nr.dtype, np.integer):
+        raise ValueError("normals must be integers: snap_normals")
+    if nr.size and (nr.min() < -(1 << 15) or nr.max() >= (1 << 15)):
+        raise ValueError("normals must fit int16")
+    nr = np.ascontiguousarray(nr, dtype=np.int16)
+    r2 = sorted(int(r) for r in np.asarray(rho2_list).reshape(-1).tolist())
+    if not r2:
+        raise ValueError("at least one radius is needed")
+    for r in r2:
+        if r < 1:
+            raise ValueError("rho^2 must be a positive integer (lattice units^2)")
+        if r > RECON_MAX_RHO2:
+            shift = 1
+            while (r >> (2 * shift)) > RECON_MAX_RHO2:
+                shift += 1
+            raise ValueError(f"rho^2 = {r} exceeds 2^22 lattice units^2 (rho <= 2048): "
+                             f"a quantum 2^{shift} times as large would fit")
+    radii = np.asarray(r2, dtype=np.uint64)
+    st = np.zeros(8, np.int64)
+    n_tris = i64(0)
+    out = vp()
+    lib = _lib.load()
+    code = lib.pyqsm_ball_pivot(_p(p), _p(nr), n, _p(radii), len(r2), 0 if max_tests is None else int(max_tests),
+                                ctypes.byref(n_tris), ctypes.byref(out), _p(st), int(device))
+    stats = dict(zip(("estimated_tests", "tests", "exact_fallbacks", "candidates", "unresolved_ties",
+                      "max_stencil", "max_cell_points", "blocks"), (int(x) for x in st)))
+    if code in (-1, -4):            # PYQSM_EINVAL, PYQSM_ERANGE: a refusal, in ValueError style
+        msg = lib.pyqsm_last_error()
+        err = BallPivotRefused(code, msg.decode("utf-8", "replace") if msg else "")
+        err.stats = stats           # what ran before the refusal
+        raise err
+    check(code)
+    rows = _adopt(lib, out, i32, 4 * n_tris.value, np.int32).reshape(-1, 4) if out.value \
+        else np.zeros((0, 4), np.int32)
+    return BallPivot(np.ascontiguousarray(rows[:, :3]), np.ascontiguousarray(rows[:, 3]),
+                     stats["unresolved_ties"], stats)
+
+
 def fps(points, num_samples: int, start_index: int = 0, device: int = 0) -> np.ndarray:
     """Farthest-point sampling: int32 indices in selection order."""
     pts = _points(points)
