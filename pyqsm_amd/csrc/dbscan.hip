@@ -517,10 +517,24 @@ __constant__ signed char kSubOffsets[62][3] = {{1,0,0}, {-1,1,0}, {0,1,0}, {1,1,
 // Full path compression for the listed representatives (plain accesses: the kernel
 // boundary makes the unions of the previous launch visible, and any value another lane
 // writes meanwhile is an ancestor too).
-// Two launches: the first moves every pointer `max_steps` links up (a hundred and more dependent
-// loads per thread, all threads starting together, was 35 us per million points), the second then
-// reaches the root in depth / max_steps hops over the pointers the first one left.
-// The second launch (rec != null) knows every listed sub-cell's root r and folds it into ONE WORD PER
+// Several launches of one kernel, by mode:
+//   kFlattenJump   moves every pointer `max_steps` links up (a hundred and more dependent loads per
+//                  thread, all threads starting together, was 35 us per million points); the launch
+//                  after it then reaches the root in depth / max_steps hops over the pointers it left.
+//   kFlattenLink   reaches the root r of the sub-cell and, side by side (both sets of loads in flight
+//                  together), the root r2 of its SECOND LINK (k_hook_sub), and unites the two where they
+//                  differ. The hook pass follows the first connected neighbour only, which leaves thin
+//                  basins side by side along every stem (386 trees for the 20 clusters of the benchmark
+//                  forest, and 37 k sub-cells on their seams for k_union_sub); the second links cross
+//                  nearly all of those boundaries (23 trees, 86 seam sub-cells), and only the few thousand
+//                  that join two different trees cost a union.
+//   kFlattenWords  chases the one to three links those unions left and folds the root into the cell's word.
+//   kFlattenRoots  the sequence without second links (PYQSM_DBSCAN_LINK2=0): root and word in one launch.
+// kFlattenLink runs concurrently with its own CAS hooks on roots, so no mode stores a pointer that is
+// unchanged: `parent[p] = p` could overwrite the hook another thread has just installed on the root p.
+// A sub-cell that is not a root is never the target of a CAS, and whatever is stored there is an ancestor.
+// Plain reads that race with the unions still name ancestors (trees only merge).
+// The launch that knows every listed sub-cell's final root r folds it into ONE WORD PER
 // CELL, the fourth word of the cell's first sub-cell record (the binning leaves it 0, grid.hpp):
 //   0      no sub-cell with core points seen yet
 //   r + 1  every such sub-cell of the cell seen so far has root r
@@ -528,22 +542,56 @@ __constant__ signed char kSubOffsets[62][3] = {{1,0,0}, {-1,1,0}, {0,1,0}, {1,1,
 // The first to arrive installs r + 1; whoever finds another root there stores -1. Whatever the order of
 // arrival, the word ends as r + 1 exactly when all of the cell's listed sub-cells have root r.
 // k_union_sub decides "same tree" per CELL from it.
+enum FlattenMode { kFlattenJump, kFlattenRoots, kFlattenLink, kFlattenWords };
+
+template <FlattenMode MODE>
 __global__ __launch_bounds__(256) void k_flatten_reps(const int4* __restrict__ list,
                                                       const int32_t* __restrict__ m_ptr,
-                                                      int* __restrict__ parent, int max_steps,
-                                                      int4* __restrict__ rec /*null: no summary*/) {
+                                                      int* parent, int max_steps /*kFlattenJump*/,
+                                                      const int32_t* __restrict__ link2 /*kFlattenLink*/,
+                                                      int4* __restrict__ rec /*kFlattenRoots, kFlattenWords*/) {
   const int m = *m_ptr;  // number of listed sub-cells, left on the device by k_sub_rep
-  int s = blockIdx.x * 256 + threadIdx.x;
-  if (s >= m) return;
-  const int4 me = list[s];
-  const int p = me.x;
-  int r = p, steps = 0;
-  for (int nx = parent[r]; nx != r && steps < max_steps; nx = parent[r], ++steps) r = nx;
-  parent[p] = r;
-  if (rec) {
-    int* const word = reinterpret_cast<int*>(rec + (me.z & ~7)) + 3;  // sub-cell id = first record of the cell * 8 + octant
-    const int old = atomicCAS(word, 0, r + 1);
-    if (old != 0 && old != r + 1 && old != -1) *word = -1;
+  const int s = blockIdx.x * 256 + threadIdx.x;
+  const bool active = s < m;
+  if constexpr (MODE == kFlattenJump || MODE == kFlattenLink) {
+    if (!active) return;
+  }
+  int p = -1, r = -1, cell8 = -1;  // (cell8: the cell's first sub-cell record = sub-cell id without the octant)
+  if (active) {
+    const int4 me = list[s];
+    p = r = me.x;
+    cell8 = me.z & ~7;
+  }
+  if constexpr (MODE == kFlattenJump) {
+    int steps = 0;
+    for (int nx = parent[r]; nx != r && steps < max_steps; nx = parent[r], ++steps) r = nx;
+    if (r != p) parent[p] = r;
+  } else if constexpr (MODE == kFlattenLink) {
+    const int l = link2[s];
+    int r2 = l >= 0 ? l : p;  // (no second link: the same chain twice, the second from the cache)
+    for (;;) {
+      const int a = parent[r], b = parent[r2];
+      if (a == r && b == r2) break;
+      r = a;
+      r2 = b;
+    }
+    if (r != p) parent[p] = r;
+    if (r2 != r) unite(parent, r, r2);
+  } else {
+    if (active) {
+      for (int nx = parent[r]; nx != r; nx = parent[r]) r = nx;
+      if (r != p) parent[p] = r;
+    }
+    // The list follows the sorted order within a block of k_sub_rep, so the sub-cells of a cell mostly sit
+    // in neighbouring lanes: a lane whose predecessor brings the same root to the same word leaves the
+    // atomic to it (the word depends only on the SET of roots folded into it).
+    const int pc = __shfl_up(cell8, 1, 64), pr = __shfl_up(r, 1, 64);
+    const bool dup = (threadIdx.x & 63) != 0 && pc == cell8 && pr == r;
+    if (active && !dup) {
+      int* const word = reinterpret_cast<int*>(rec + cell8) + 3;
+      const int old = atomicCAS(word, 0, r + 1);
+      if (old != 0 && old != r + 1 && old != -1) *word = -1;
+    }
   }
 }
 
@@ -593,12 +641,16 @@ __device__ __forceinline__ SubNbr sub_neighbour(bool active, const int4 at, int 
 // Lane t < 13 of a group takes offset t, so one set of gathers serves the wave's four
 // sub-cells; each group then tests its current candidate's point pairs 16 per step (the loop is
 // wave-wide, the ballots are read per group), moves on when a candidate is exhausted and stops
-// at the first hit.
+// at the first hit: the hook.
+// LINK2: the group then goes on through its remaining candidates in the same order to the next one that
+// is connected as well, and records that one's representative as the sub-cell's second link (-1: none) for
+// k_flatten_reps to unite across. Nothing is chased or united here: the chains are hundreds of links long
+// while this pass runs.
 // (Until this form the pass looked up all 62 offsets per sub-cell, four sub-cells one after the other,
 // and wrote the neighbours found as a 256-byte row per sub-cell for pass 2: 197 002 candidates were
 // tested for 196 884 sub-cells of the benchmark forest — the first one nearly always connects — and
 // the table was the step's largest single piece of traffic.)
-template <class CO>
+template <class CO, bool LINK2>
 __global__ __launch_bounds__(256) void k_hook_sub(const int4* __restrict__ list,
                                                   const int4* __restrict__ list_xyz,
                                                   const int32_t* __restrict__ m_ptr,
@@ -608,6 +660,7 @@ __global__ __launch_bounds__(256) void k_hook_sub(const int4* __restrict__ list,
                                                   const int4* __restrict__ rec, CO co, double r2,
                                                   const uint8_t* __restrict__ core,
                                                   int* __restrict__ parent,
+                                                  int32_t* __restrict__ link2 /*[m], LINK2 only*/,
     unsigned long long* __restrict__ st /*stamps or null*/) {
   stamped(st, [&] {
   const CellDir dir{dwords, dslots};
@@ -628,7 +681,7 @@ __global__ __launch_bounds__(256) void k_hook_sub(const int4* __restrict__ list,
     const int p = me.x, n1 = me.w;
     // the group's candidates, nearest first; `base`: the pairs of the current one already tested
     unsigned todo = unsigned(__ballot(nb2.rep >= 0) >> (16 * grp)) & 0xFFFFu;
-    int base = 0, hooked = -1;
+    int base = 0, hooked = -1, second = -1;
     while (__ballot(todo != 0)) {
       const int src = (k & 48) + (todo ? __ffs(todo) - 1 : 0);
       const int qb = __shfl(nb2.q0, src, 64), nb = __shfl(nb2.n2, src, 64), rb = __shfl(nb2.rep, src, 64);
@@ -642,8 +695,14 @@ __global__ __launch_bounds__(256) void k_hook_sub(const int4* __restrict__ list,
       if (todo && idx < pairs && j < nb) hit = co.core_pair_within(p + (idx >> sh), qb + j, core, r2);
       const bool found = ((__ballot(hit) >> (16 * grp)) & 0xFFFFull) != 0;
       if (found) {
-        hooked = rb;
-        todo = 0;
+        if (LINK2 && hooked < 0) {  // on to the next candidate, for the second link
+          hooked = rb;
+          todo &= todo - 1;
+          base = 0;
+        } else {
+          if (LINK2) second = rb; else hooked = rb;
+          todo = 0;
+        }
       } else if (todo) {
         base += 16;
         if (base >= pairs) {
@@ -661,6 +720,7 @@ __global__ __launch_bounds__(256) void k_hook_sub(const int4* __restrict__ list,
     // at once, so most neighbours have not hooked yet when their pointer is read, and agent-scope
     // accesses here change nothing. k_flatten_reps deals with them in two passes.)
     if (hooked >= 0 && t == 0) parent[p] = parent[hooked];
+    if (LINK2 && live && t == 0) link2[s0 + grp] = second;  // every slot below m, every call: the arena is reused
   }
   });
 }
@@ -1232,6 +1292,8 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
   PQ_TRY(c->arena.get(size_t(n), &list));
   int4* list_xyz;  // [n] grid coordinates and octant of every listed sub-cell
   PQ_TRY(c->arena.get(size_t(n), &list_xyz));
+  int32_t* link2;  // [n] second link of every listed sub-cell (k_hook_sub), indexed like list
+  PQ_TRY(c->arena.get(size_t(n), &link2));
   // [0] listed sub-cells, [1] roots (= clusters), [2] blocks k_number has seen finish, [3] non-core
   // points of the label pass. The binning leaves four zeroed ints behind for this (no memset launches).
   list_cnt = sub.zeroed4;
@@ -1299,10 +1361,19 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
       // waves beyond it leave at once — which spares the host round trip in the middle of the step
       // (~15 us of an 0.7 ms step). Nothing in the phase is sized by m any more.
       {
-        // the two wave-per-four-sub-cells passes: resident waves striding over the list, 16 (hook) and 32
-        // (union) blocks per CU (PYQSM_UNION_BLOCKS_PER_CU=<hook>,<union>; 0 = a block per 16 rows of the
-        // bound n, which starts four waves in five for nothing)
-        int per_cu[2] = {16, 32};
+        // PYQSM_DBSCAN_LINK2=0: the sequence without second links (no second search in the hook pass, two
+        // compression launches, the words written by the second)
+        static const bool use_link2 = [] {
+          const char* e = getenv("PYQSM_DBSCAN_LINK2");
+          return e ? atoi(e) != 0 : true;
+        }();
+        // the two wave-per-four-sub-cells passes: resident waves striding over the list, 8 (hook; 16 without
+        // the second search) and 32 (union) blocks per CU (PYQSM_UNION_BLOCKS_PER_CU=<hook>,<union>; 0 = a
+        // block per 16 rows of the bound n, which starts four waves in five for nothing). Eight blocks are what
+        // a CU holds of either kernel: the hook pass with its second search is shortest when no wave waits for
+        // a slot (30.5 us against 32.8 with 16 and 36.3 with 6); the union pass, mostly its filter now, is the
+        // same 20-22 us with 8, 16, 32 and 64.
+        int per_cu[2] = {use_link2 ? 8 : 16, 32};
         if (const char* e_cu = getenv("PYQSM_UNION_BLOCKS_PER_CU")) {
           per_cu[0] = per_cu[1] = atoi(e_cu);
           if (const char* comma = strchr(e_cu, ',')) per_cu[1] = atoi(comma + 1);
@@ -1315,43 +1386,84 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
         {
           const StampKernel pk(c, "k_hook_sub", gh.x);
           on_coords(g, [&](auto co) {
-            hipLaunchKernelGGL(k_hook_sub<decltype(co)>, gh, block, 0, c->stream, list, list_xyz, list_cnt, d_plan,
-                               dir.words, dir.slots, sub.rec, co, r2, core, parent, pk.slots);
+            if (use_link2)
+              hipLaunchKernelGGL((k_hook_sub<decltype(co), true>), gh, block, 0, c->stream, list, list_xyz, list_cnt,
+                                 d_plan, dir.words, dir.slots, sub.rec, co, r2, core, parent, link2, pk.slots);
+            else
+              hipLaunchKernelGGL((k_hook_sub<decltype(co), false>), gh, block, 0, c->stream, list, list_xyz, list_cnt,
+                                 d_plan, dir.words, dir.slots, sub.rec, co, r2, core, parent, link2, pk.slots);
           });
         }
-        if (trace) {  // how deep are the chains the hook pass leaves?
-          int32_t m = 0;
-          PQ_HIP(hipMemcpyAsync(&m, list_cnt, 4, hipMemcpyDeviceToHost, c->stream));
+        // trace only: the list and the pointers on the host, every listed sub-cell's root and depth
+        int32_t tm = 0;
+        std::vector<int32_t> hp, root_of;
+        std::vector<int4> hl;
+        const auto snapshot = [&](std::vector<int64_t>* hist) -> int {
+          PQ_HIP(hipMemcpyAsync(&tm, list_cnt, 4, hipMemcpyDeviceToHost, c->stream));
           PQ_HIP(hipStreamSynchronize(c->stream));
-          std::vector<int32_t> hp(static_cast<size_t>(n), 0);
-          std::vector<int4> hl(static_cast<size_t>(m), make_int4(0, 0, 0, 0));
+          hp.assign(static_cast<size_t>(n), 0);
+          hl.assign(static_cast<size_t>(tm), make_int4(0, 0, 0, 0));
           PQ_HIP(hipMemcpy(hp.data(), parent, size_t(n) * 4, hipMemcpyDeviceToHost));
-          PQ_HIP(hipMemcpy(hl.data(), list, size_t(m) * 16, hipMemcpyDeviceToHost));
-          std::vector<int64_t> hist(66, 0);
-          int64_t roots = 0;
-          for (int32_t s2 = 0; s2 < m; ++s2) {
+          PQ_HIP(hipMemcpy(hl.data(), list, size_t(tm) * 16, hipMemcpyDeviceToHost));
+          root_of.assign(static_cast<size_t>(n), -1);
+          for (int32_t s2 = 0; s2 < tm; ++s2) {
             int d = 0, r = hl[size_t(s2)].x;
-            while (hp[size_t(r)] != r && d < 65) {
+            while (hp[size_t(r)] != r) {
               r = hp[size_t(r)];
               ++d;
             }
-            hist[size_t(d)]++;
-            roots += d == 0;
+            root_of[size_t(hl[size_t(s2)].x)] = r;
+            if (hist) (*hist)[size_t(std::min(d, 65))]++;
           }
-          fprintf(stderr, "hook pass: %d sub-cells, %lld roots; chain depth histogram:", m, (long long)roots);
+          return 0;
+        };
+        const auto count_roots = [&] {
+          int64_t roots = 0;
+          for (int32_t s2 = 0; s2 < tm; ++s2) roots += root_of[size_t(hl[size_t(s2)].x)] == hl[size_t(s2)].x;
+          return roots;
+        };
+        int64_t links = 0, crossing = 0;
+        if (trace) {  // how deep are the chains the hook pass leaves?
+          std::vector<int64_t> hist(66, 0);
+          PQ_TRY(snapshot(&hist));
+          fprintf(stderr, "hook pass: %d sub-cells, %lld roots; chain depth histogram:", tm, (long long)count_roots());
           for (int d = 0; d < 66; ++d)
             if (hist[size_t(d)]) fprintf(stderr, " %d:%lld", d, (long long)hist[size_t(d)]);
           fprintf(stderr, "\n");
+          if (use_link2) {  // second links, and how many of them lead into another of the hook pass's trees
+            std::vector<int32_t> h2(static_cast<size_t>(tm), -1);
+            PQ_HIP(hipMemcpy(h2.data(), link2, size_t(tm) * 4, hipMemcpyDeviceToHost));
+            for (int32_t s2 = 0; s2 < tm; ++s2) {
+              if (h2[size_t(s2)] < 0) continue;
+              ++links;
+              crossing += root_of[size_t(h2[size_t(s2)])] != root_of[size_t(hl[size_t(s2)].x)];
+            }
+          }
         }
         static const int jump = [] {  // PYQSM_FLATTEN_JUMP: links of the first pass (0: one pass, the earlier form)
           const char* e = getenv("PYQSM_FLATTEN_JUMP");
           return e ? atoi(e) : 12;
         }();
         if (jump > 0)
-          hipLaunchKernelGGL(k_flatten_reps, gl, block, 0, c->stream, list, list_cnt, parent, jump,
-                             static_cast<int4*>(nullptr));
-        // (the pass that reaches the roots also writes the cells' summary words)
-        hipLaunchKernelGGL(k_flatten_reps, gl, block, 0, c->stream, list, list_cnt, parent, 0x7fffffff, sub.rec);
+          hipLaunchKernelGGL(k_flatten_reps<kFlattenJump>, gl, block, 0, c->stream, list, list_cnt, parent, jump,
+                             link2, sub.rec);
+        if (use_link2) {
+          // the pass that reaches the roots unites across the second links; a short third one then writes
+          // the cells' summary words
+          hipLaunchKernelGGL(k_flatten_reps<kFlattenLink>, gl, block, 0, c->stream, list, list_cnt, parent, 0, link2,
+                             sub.rec);
+          if (trace) {
+            PQ_TRY(snapshot(nullptr));
+            fprintf(stderr, "link pass: %lld recorded, %lld crossed trees, %lld roots left\n", (long long)links,
+                    (long long)crossing, (long long)count_roots());
+          }
+          hipLaunchKernelGGL(k_flatten_reps<kFlattenWords>, gl, block, 0, c->stream, list, list_cnt, parent, 0, link2,
+                             sub.rec);
+        } else {
+          // (the pass that reaches the roots also writes the cells' summary words)
+          hipLaunchKernelGGL(k_flatten_reps<kFlattenRoots>, gl, block, 0, c->stream, list, list_cnt, parent, 0, link2,
+                             sub.rec);
+        }
         // what is left: joining the few trees per cluster along their seams
         unsigned long long* d_seams = nullptr;  // trace only: sub-cells that took the 62-offset path
         if (trace) {
