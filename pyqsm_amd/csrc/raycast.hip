@@ -1296,6 +1296,10 @@ int pyqsm_list_intersections(const float* verts, int64_t V, const int32_t* tris,
     return fail(PYQSM_EINVAL, "pyqsm_list_intersections: hits_cap > 0 needs every record array");
   Ctx* c = ctx_for(device);
   if (!c) return PYQSM_ENODEV;
+  if (T == 0) {  // empty mesh: no crossing; nothing is uploaded, so no copy outlives the call
+    memset(counts, 0, size_t(R) * 4);
+    return 0;
+  }
   std::lock_guard<std::mutex> lk(c->mu);
   c->arena.reset();
   float *d_verts, *d_rays;
@@ -1309,17 +1313,11 @@ int pyqsm_list_intersections(const float* verts, int64_t V, const int32_t* tris,
   PQ_TRY(c->arena.get(size_t(R), &d_counts));
   PQ_TRY(c->arena.get(size_t(R), &d_off));
   PQ_TRY(c->arena.get(1, &d_total));
-  if (T > 0) {
-    PQ_HIP(hipMemcpyAsync(d_verts, verts, size_t(V) * 12, hipMemcpyHostToDevice, c->stream));
-    PQ_HIP(hipMemcpyAsync(d_tris, tris, size_t(T) * 12, hipMemcpyHostToDevice, c->stream));
-  }
+  PQ_HIP(hipMemcpyAsync(d_verts, verts, size_t(V) * 12, hipMemcpyHostToDevice, c->stream));
+  PQ_HIP(hipMemcpyAsync(d_tris, tris, size_t(T) * 12, hipMemcpyHostToDevice, c->stream));
   PQ_HIP(hipMemcpyAsync(d_rays, rays, size_t(R) * 24, hipMemcpyHostToDevice, c->stream));
   PQ_TRY(expand(c, d_verts, V, d_tris, T, d_rec));
   const dim3 grid(ceil_div(R, 256));
-  if (T == 0) {
-    memset(counts, 0, size_t(R) * 4);
-    return 0;
-  }
   {
     ProfScope ps(c, "all_hits");
     hipLaunchKernelGGL(k_all_hits<0>, grid, dim3(256), 0, c->stream, d_rec, int(T), d_rays, R,

@@ -164,7 +164,7 @@ def test_list_intersections_vs_oracle(gpu):
     assert got["counts"].max() >= 2                    # some rays cross several leaves
     # closest hit == minimum over the list
     t, _, _ = hip.cast_rays(verts, tris, rays, device=gpu)
-    for r in np.flatnonzero(got["counts"])[:50]:
+    for r in np.flatnonzero(got["counts"]):
         assert t[r] == got["t_hit"][got["ray_ids"] == r].min()
 
 
