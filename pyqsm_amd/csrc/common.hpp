@@ -134,7 +134,7 @@ struct Ctx {
 Ctx* ctx_for(int device);
 
 // RAII bracket: records a start/stop event pair on the stream under `name`
-// when profiling is enabled; otherwise does nothing.
+// when profiling is enabled and `name` is not null; otherwise does nothing.
 class ProfScope {
  public:
   ProfScope(Ctx* c, const char* name, int weight = 1, int level = 1);

@@ -274,7 +274,7 @@ Ctx* ctx_for(int device) {
 // ---- timers ---------------------------------------------------------------
 
 ProfScope::ProfScope(Ctx* c, const char* name, int weight, int level) : c_(c) {
-  if (c->prof < level) return;
+  if (!name || c->prof < level) return;
   t_ = &c->timers[name];
   hipEvent_t a = nullptr, b = nullptr;
   if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) {

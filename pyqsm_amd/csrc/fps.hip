@@ -22,6 +22,7 @@
 // instead of the whole cloud, and a round costs its launch and three dependent memory round
 // trips: 1 M -> 100 k samples in 0.60 s instead of 0.89 s (5.9 us a round; the whole-cloud round
 // moves 32 MB in 8.9 us). Same distances, same comparison, same indices.
+#include "boruvka.hpp"  // ord_bits
 #include "common.hpp"
 #include "grid.hpp"
 
@@ -452,10 +453,6 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned k) {
   const unsigned a = unsigned(__builtin_amdgcn_readlane(int(k), 0)), b = unsigned(__builtin_amdgcn_readlane(int(k), 16)),
                  c = unsigned(__builtin_amdgcn_readlane(int(k), 32)), d = unsigned(__builtin_amdgcn_readlane(int(k), 48));
   return step(step(a, b), step(c, d));
-}
-__device__ __forceinline__ unsigned long long ord_bits(double x) {  // order-preserving double -> uint64
-  const unsigned long long b = static_cast<unsigned long long>(__double_as_longlong(x));
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
 __device__ __forceinline__ double lane_double(double v, int src) {
   const long long b = __double_as_longlong(v);

@@ -14,18 +14,15 @@
 // covariance entries, one add at a time in neighbour order; k_normal_finish then runs the Jacobi
 // solve (pca.hpp) and the sign rule on one lane per point.
 //
-// Orientation. Boruvka over the directed kNN edges with union-find labels that carry a parity bit
-// (label = root << 1 | parity of the point relative to its root). Every cross edge proposes itself
-// to both of its components with a two-phase 64-bit atomicMin (orderable weight bits, then the packed
-// (min, max) among equal weights): a total order, so the spanning forest is unique and a mutual pair
-// of components picks the same edge. Components hook along their edge (the lower id of a mutual
-// pair stays a root), the hook forest is compressed by pointer jumping in place and every label is
-// rewritten. A point's parity ends up the XOR of the flip bits along its tree path; the component's
-// highest point (lowest index on ties) fixes the sign. Only integer atomics, and every outcome is
-// independent of their arrival order.
+// Orientation. Boruvka over the directed kNN edges (boruvka.hpp has the rounds and why their outcome
+// does not depend on the order of the atomics) with labels that carry a parity bit (label = root << 1
+// | parity of the point relative to its root): the weight of an edge is 1 - |n_i . n_j|, its flip bit
+// the sign of the dot. A point's parity ends up the XOR of the flip bits along its tree path; the
+// component's highest point (lowest index on ties) fixes the sign.
 #include <algorithm>
 #include <cmath>
 
+#include "boruvka.hpp"
 #include "common.hpp"
 #include "grid.hpp"
 #include "pca.hpp"
@@ -219,103 +216,29 @@ __global__ __launch_bounds__(256) void k_normal_finish(int n, const double* __re
   o[2] = flip ? -v[2] : v[2];
 }
 
-// ---- orientation: Boruvka with parity ----------------------------------------------------------
-// A double's bits mapped so that unsigned order is numeric order (negative values included).
-__device__ __forceinline__ unsigned long long ord_bits(double v) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-
+// ---- orientation: the edge policy of boruvka.hpp, then the sign --------------------------------
 __device__ __forceinline__ double dot3(const double* __restrict__ nrm, int a, int b) {
   const double* p = nrm + 3 * size_t(a);
   const double* q = nrm + 3 * size_t(b);
   return (p[0] * q[0] + p[1] * q[1]) + p[2] * q[2];
 }
 
-__global__ __launch_bounds__(256) void k_label_init(int n, uint32_t* __restrict__ lab) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) lab[i] = uint32_t(i) << 1;
-}
-
-// Phase 1: the smallest orderable weight 1 - |dot| of the cross edges of every component.
-__global__ __launch_bounds__(256) void k_min_w(int64_t ne, int k, const int32_t* __restrict__ idx,
-                                               const double* __restrict__ nrm, const uint32_t* __restrict__ lab,
-                                               unsigned long long* __restrict__ bw) {
-  const int64_t e = int64_t(blockIdx.x) * 256 + threadIdx.x;
-  if (e >= ne) return;
-  const int i = int(e / k), j = idx[e];
-  if (j == i) return;
-  const uint32_t ci = lab[i] >> 1, cj = lab[j] >> 1;
-  if (ci == cj) return;
-  const unsigned long long key = ord_bits(1.0 - fabs(dot3(nrm, i, j)));
-  // the minima only fall: an edge no lighter than what is already there (a stale read is no lower
-  // than the true value) cannot change them, and skipping it spares the atomic
-  if (key < bw[ci]) atomicMin(&bw[ci], key);
-  if (key < bw[cj]) atomicMin(&bw[cj], key);
-}
-
-// Phase 2: among the edges of that weight, the smallest packed (min, max).
-__global__ __launch_bounds__(256) void k_min_e(int64_t ne, int k, const int32_t* __restrict__ idx,
-                                               const double* __restrict__ nrm, const uint32_t* __restrict__ lab,
-                                               const unsigned long long* __restrict__ bw,
-                                               unsigned long long* __restrict__ be) {
-  const int64_t e = int64_t(blockIdx.x) * 256 + threadIdx.x;
-  if (e >= ne) return;
-  const int i = int(e / k), j = idx[e];
-  if (j == i) return;
-  const uint32_t ci = lab[i] >> 1, cj = lab[j] >> 1;
-  if (ci == cj) return;
-  const unsigned long long key = ord_bits(1.0 - fabs(dot3(nrm, i, j)));
-  const unsigned long long pk = (i < j) ? ((unsigned long long)i << 32 | uint32_t(j))
-                                        : ((unsigned long long)j << 32 | uint32_t(i));
-  if (key == bw[ci]) atomicMin(&be[ci], pk);
-  if (key == bw[cj]) atomicMin(&be[cj], pk);
-}
-
-// Every root with an edge hooks to the component across it: hk[c] = other << 1 | parity of c
-// relative to other. A mutual pair has chosen the same edge; its lower id stays a root.
-__global__ __launch_bounds__(256) void k_hook(int n, const double* __restrict__ nrm, const uint32_t* __restrict__ lab,
-                                              const unsigned long long* __restrict__ be, uint32_t* __restrict__ hk,
-                                              int32_t* __restrict__ hooks) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= n) return;
-  if ((lab[c] >> 1) != uint32_t(c)) return;
-  const unsigned long long pk = be[c];
-  hk[c] = uint32_t(c) << 1;
-  if (pk == ~0ull) return;
-  const int a = int(pk >> 32), b = int(pk & 0xFFFFFFFFu);
-  const uint32_t la = lab[a], lb = lab[b];
-  const uint32_t ca = la >> 1, cb = lb >> 1;
-  const uint32_t other = ca == uint32_t(c) ? cb : ca;
-  if (be[other] == pk && uint32_t(c) < other) return;
-  const uint32_t f = dot3(nrm, a, b) < 0.0 ? 1u : 0u;
-  hk[c] = (other << 1) | ((la ^ lb ^ f) & 1u);
-  atomicAdd(hooks, 1);
-}
-
-// Pointer jumping on the hook forest, in place: an entry always names an ancestor with the parity
-// relative to it, so concurrent jumps by other roots only shorten the walk.
-__global__ __launch_bounds__(256) void k_compress(int n, const uint32_t* __restrict__ lab, uint32_t* hk) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= n) return;
-  if ((lab[c] >> 1) != uint32_t(c)) return;
-  for (;;) {
-    const uint32_t h = __hip_atomic_load(&hk[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const uint32_t p = h >> 1;
-    if (p == uint32_t(c)) break;
-    const uint32_t hp = __hip_atomic_load(&hk[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if ((hp >> 1) == p) break;
-    __hip_atomic_store(&hk[c], (hp & ~1u) | ((h ^ hp) & 1u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+// Every entry of the kNN table but the point itself is an edge, of weight 1 - |n_i . n_j|; it flips
+// when the dot is negative. A hook records nothing beyond the parity.
+struct OrientEdges {
+  const int32_t* idx;
+  const double* nrm;
+  int k;
+  __device__ void init(int) const {}
+  __device__ bool ends(int64_t e, int* i, int* j) const {
+    *i = int(e / k);
+    *j = idx[e];
+    return *j != *i;
   }
-}
-
-__global__ __launch_bounds__(256) void k_relabel(int n, uint32_t* __restrict__ lab, const uint32_t* __restrict__ hk) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t l = lab[i];
-  const uint32_t h = hk[l >> 1];
-  lab[i] = (h & ~1u) | ((l ^ h) & 1u);
-}
+  __device__ unsigned long long key(int64_t, int i, int j) const { return ord_bits(1.0 - fabs(dot3(nrm, i, j))); }
+  __device__ uint32_t flip(int a, int b) const { return dot3(nrm, a, b) < 0.0 ? 1u : 0u; }
+  __device__ void hooked(uint32_t, unsigned long long, unsigned long long) const {}
+};
 
 // The highest point of every component, lowest index on ties: orderable z first, then the index.
 __global__ __launch_bounds__(256) void k_top_z(int n, const double* __restrict__ xyz, const uint32_t* __restrict__ lab,
@@ -324,7 +247,7 @@ __global__ __launch_bounds__(256) void k_top_z(int n, const double* __restrict__
   if (i >= n) return;
   const uint32_t r = lab[i] >> 1;
   const unsigned long long z = ord_bits(xyz[3 * size_t(i) + 2]);
-  if (z > tz[r]) atomicMax(&tz[r], z);  // the maxima only rise: see k_min_w
+  if (z > tz[r]) atomicMax(&tz[r], z);  // the maxima only rise: see k_bv_min_w
 }
 
 __global__ __launch_bounds__(256) void k_top_i(int n, const double* __restrict__ xyz, const uint32_t* __restrict__ lab,
@@ -456,7 +379,7 @@ static int orient_device(Ctx* c, const double* d_xyz, int64_t n, int32_t k, cons
   const int N = int(n);
   const int kk = int(std::min<int64_t>(k, n));
   const int64_t ne = int64_t(n) * kk;
-  int32_t *idx, *hooks;
+  int32_t *idx, *ctl;
   double* d2;
   uint32_t *lab, *hk, *ti;
   unsigned long long *bw, *be, *tz;
@@ -468,42 +391,14 @@ static int orient_device(Ctx* c, const double* d_xyz, int64_t n, int32_t k, cons
   PQ_TRY(c->arena.get(size_t(n), &bw));
   PQ_TRY(c->arena.get(size_t(n), &be));
   PQ_TRY(c->arena.get(size_t(n), &tz));
-  PQ_TRY(c->arena.get(1, &hooks));
+  PQ_TRY(c->arena.get(size_t(kBvCtlWords), &ctl));
   {
     ProfScope ps(c, "orient_knn");
     PQ_TRY(knn_device(c, d_xyz, n, kk, 0, idx, d2));
   }
-  hipLaunchKernelGGL(k_label_init, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, N, lab);
-  PQ_HIP(hipGetLastError());
-  const int eb = ceil_div(ne, 256), pb = ceil_div(n, 256);
-  for (;;) {
-    {
-      ProfScope ps(c, "orient_min_edge");
-      PQ_HIP(hipMemsetAsync(bw, 0xFF, size_t(n) * 8, c->stream));
-      PQ_HIP(hipMemsetAsync(be, 0xFF, size_t(n) * 8, c->stream));
-      PQ_HIP(hipMemsetAsync(hooks, 0, 4, c->stream));
-      hipLaunchKernelGGL(k_min_w, dim3(eb), dim3(256), 0, c->stream, ne, kk, static_cast<const int32_t*>(idx), d_nrm,
-                         static_cast<const uint32_t*>(lab), bw);
-      hipLaunchKernelGGL(k_min_e, dim3(eb), dim3(256), 0, c->stream, ne, kk, static_cast<const int32_t*>(idx), d_nrm,
-                         static_cast<const uint32_t*>(lab), static_cast<const unsigned long long*>(bw), be);
-      PQ_HIP(hipGetLastError());
-    }
-    int32_t h = 0;
-    {
-      ProfScope ps(c, "orient_hook");
-      hipLaunchKernelGGL(k_hook, dim3(pb), dim3(256), 0, c->stream, N, d_nrm, static_cast<const uint32_t*>(lab),
-                         static_cast<const unsigned long long*>(be), hk, hooks);
-      PQ_HIP(hipGetLastError());
-      PQ_HIP(hipMemcpyAsync(&h, hooks, 4, hipMemcpyDeviceToHost, c->stream));
-      PQ_HIP(hipStreamSynchronize(c->stream));
-    }
-    if (h == 0) break;
-    ++*rounds;
-    ProfScope ps(c, "orient_jump");
-    hipLaunchKernelGGL(k_compress, dim3(pb), dim3(256), 0, c->stream, N, static_cast<const uint32_t*>(lab), hk);
-    hipLaunchKernelGGL(k_relabel, dim3(pb), dim3(256), 0, c->stream, N, lab, static_cast<const uint32_t*>(hk));
-    PQ_HIP(hipGetLastError());
-  }
+  PQ_TRY(boruvka_forest(c, "orientation", n, ne, OrientEdges{idx, d_nrm, kk},
+                        BvScopes{"orient_min_edge", "orient_hook", "orient_jump"}, lab, hk, bw, be, ctl, rounds));
+  const int pb = ceil_div(n, 256);
   ProfScope ps(c, "orient_sign");
   PQ_HIP(hipMemsetAsync(tz, 0, size_t(n) * 8, c->stream));
   PQ_HIP(hipMemsetAsync(ti, 0xFF, size_t(n) * 4, c->stream));

@@ -8,22 +8,22 @@
 // name the point itself or whose d2 is not finite are no edges. A pair at distance exactly 0 joins the
 // components of its ends but is never put out: what SciPy's minimum_spanning_tree does with explicit
 // zeros (its Kruskal pass unites across them, its result drops them). The order on edges
-// is (orderable bits of d2, packed (min, max)): strict and total, so every component has ONE lightest
-// cross edge, a mutual pair of components picks the same one, and hook cycles longer than two cannot
-// form (along a hook path the chosen keys fall strictly). Two-phase 64-bit atomicMin as in
-// normals.hip (the pair does not fit beside the 64 weight bits in one key). A component hooks once
-// in its life, so the edge it hooked along is kept in its own slot; the slots are compacted
-// (scan.hip) and sorted by the packed pair with the atomic-free radix sort: the same bits every run.
+// is (orderable bits of d2, packed (min, max)), strict and total. boruvka.hpp has the rounds, shared
+// with the normal orientation, and what that order buys; the parity bit of its labels stays 0 here.
+// A component hooks once in its life, so the edge it hooked along is kept in its own slot; the slots
+// are compacted (scan.hip) and sorted by the packed pair with the atomic-free radix sort: the same
+// bits every run.
 //
 // Chains. Degrees by integer atomics, a two-slot neighbour record per degree-2 node (slot order is
 // irrelevant: a walk takes "the one I did not come from"), one walker per (kept node, incident
 // edge); the walk from the smaller end emits. Count pass, sort by (a, b), scan, write pass.
 //
-// No device loop here is unbounded: pointer jumping stops after kTopoJumps jumps per thread and the
-// host relaunches while a flag says so; chain walks stop after m steps and raise an error bit.
+// No device loop here is unbounded: pointer jumping and the rounds carry the caps of boruvka.hpp;
+// chain walks stop after m steps and raise an error bit.
 #include <algorithm>
 #include <cmath>
 
+#include "boruvka.hpp"
 #include "common.hpp"
 
 namespace pyqsm {
@@ -31,133 +31,46 @@ namespace pyqsm {
 int knn_device(Ctx* c, const double* xyz, int64_t n, int32_t k, int32_t exclude_self, int32_t* idx,
                double* d2);                   // knn.hip
 static constexpr int kTopoMaxK = 192;          // knn.hip kMaxK
-static constexpr int kTopoMaxRounds = 32;      // components at least halve per round: 2^31 points need 31
-static constexpr int kTopoJumps = 64;          // pointer jumps per thread per launch
-static constexpr int kTopoMaxRelaunch = 64;    // launches of the jump kernel per round
 static constexpr int kSurfLevels = 100, kSurfAngles = 20, kSurfPts = kSurfLevels * kSurfAngles;
 static constexpr int kSurfSlots = 2048;        // keys sorted per cylinder (16 KB of LDS)
 
 // bits of the error word the kernels raise
 enum : int32_t { kErrWalk = 1, kErrEdge = 2, kErrIndex = 4, kErrWide = 8, kErrNonFinite = 16 };
-// control words: hooks of the round, "jump again" flag, error bits
-enum { kCtlHooks = 0, kCtlAgain = 1, kCtlErr = 2, kCtlWords = 4 };
+// control words, one 16-byte block: error bits
+enum { kCtlErr = 0, kCtlWords = 4 };
 
 // ---- spanning forest ----------------------------------------------------------------------------
-// A double's bits mapped so that unsigned order is numeric order, and back.
-__device__ __forceinline__ unsigned long long tp_ord_bits(double v) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double tp_from_ord(unsigned long long o) {
-  const unsigned long long u = (o >> 63) ? (o & 0x7FFFFFFFFFFFFFFFull) : ~o;
-  return __longlong_as_double((long long)u);
-}
+static constexpr unsigned long long kZeroKey = 0x8000000000000000ull;  // ord_bits(+0.0)
 
-static constexpr unsigned long long kZeroKey = 0x8000000000000000ull;  // tp_ord_bits(+0.0)
-
-__global__ __launch_bounds__(256) void k_tp_init(int m, uint32_t* __restrict__ lab, unsigned long long* __restrict__ ek,
-                                                 unsigned long long* __restrict__ ew) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= m) return;
-  lab[i] = uint32_t(i);
-  ek[i] = ~0ull;
-  ew[i] = ~0ull;
-}
-
-// Entry e of the kNN table as a cross edge: false for padded rows, the point itself, a weight that
-// is negative or not finite, and both ends in one component.
-__device__ __forceinline__ bool tp_cross_edge(int64_t e, int k, int m, const int32_t* __restrict__ idx,
-                                              const double* __restrict__ d2, const uint32_t* __restrict__ lab, int* i,
-                                              int* j, uint32_t* ci, uint32_t* cj, unsigned long long* key) {
-  *i = int(e / k);
-  *j = idx[e];
-  if (*j < 0 || *j >= m || *j == *i) return false;
-  const double w = d2[e];
-  if (!(w >= 0.0) || !(w < __builtin_inf())) return false;
-  *ci = lab[*i];
-  *cj = lab[*j];
-  if (*ci == *cj) return false;
-  *key = w == 0.0 ? kZeroKey : tp_ord_bits(w);
-  return true;
-}
-
-// Phase 1: the smallest weight among the cross edges of every component.
-__global__ __launch_bounds__(256) void k_tp_min_w(int64_t ne, int k, int m, const int32_t* __restrict__ idx,
-                                                  const double* __restrict__ d2, const uint32_t* __restrict__ lab,
-                                                  unsigned long long* __restrict__ bw) {
-  const int64_t e = int64_t(blockIdx.x) * 256 + threadIdx.x;
-  if (e >= ne) return;
-  int i, j;
-  uint32_t ci, cj;
-  unsigned long long key;
-  if (!tp_cross_edge(e, k, m, idx, d2, lab, &i, &j, &ci, &cj, &key)) return;
-  // the minima only fall: a stale read is no lower than the true value, so skipping is safe
-  if (key < bw[ci]) atomicMin(&bw[ci], key);
-  if (key < bw[cj]) atomicMin(&bw[cj], key);
-}
-
-// Phase 2: among the edges of that weight, the smallest packed (min, max).
-__global__ __launch_bounds__(256) void k_tp_min_e(int64_t ne, int k, int m, const int32_t* __restrict__ idx,
-                                                  const double* __restrict__ d2, const uint32_t* __restrict__ lab,
-                                                  const unsigned long long* __restrict__ bw,
-                                                  unsigned long long* __restrict__ be) {
-  const int64_t e = int64_t(blockIdx.x) * 256 + threadIdx.x;
-  if (e >= ne) return;
-  int i, j;
-  uint32_t ci, cj;
-  unsigned long long key;
-  if (!tp_cross_edge(e, k, m, idx, d2, lab, &i, &j, &ci, &cj, &key)) return;
-  const unsigned long long pk = (i < j) ? ((unsigned long long)i << 32 | uint32_t(j))
-                                        : ((unsigned long long)j << 32 | uint32_t(i));
-  if (key == bw[ci]) atomicMin(&be[ci], pk);
-  if (key == bw[cj]) atomicMin(&be[cj], pk);
-}
-
-// Every root with an edge hooks to the component across it and keeps the edge in its own slot. A
-// mutual pair has chosen the same edge; its lower id stays a root, the higher one records it.
-__global__ __launch_bounds__(256) void k_tp_hook(int m, const uint32_t* __restrict__ lab,
-                                                 const unsigned long long* __restrict__ bw,
-                                                 const unsigned long long* __restrict__ be, uint32_t* __restrict__ hk,
-                                                 unsigned long long* __restrict__ ek, unsigned long long* __restrict__ ew,
-                                                 int32_t* __restrict__ ctl) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= m) return;
-  if (lab[c] != uint32_t(c)) return;
-  hk[c] = uint32_t(c);
-  const unsigned long long pk = be[c];
-  if (pk == ~0ull) return;
-  const uint32_t a = uint32_t(pk >> 32), b = uint32_t(pk & 0xFFFFFFFFu);
-  const uint32_t ca = lab[a], cb = lab[b];
-  const uint32_t other = ca == uint32_t(c) ? cb : ca;
-  if (be[other] == pk && uint32_t(c) < other) return;
-  hk[c] = other;
-  ek[c] = pk;
-  ew[c] = bw[c];
-  atomicAdd(&ctl[kCtlHooks], 1);
-}
-
-// Pointer jumping on the hook forest, in place: an entry always names an ancestor, so concurrent
-// jumps by other roots only shorten the walk. At most kTopoJumps jumps; a thread that has not
-// reached a child of a root by then asks for another launch.
-__global__ __launch_bounds__(256) void k_tp_jump(int m, const uint32_t* __restrict__ lab, uint32_t* hk,
-                                                 int32_t* __restrict__ ctl) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= m) return;
-  if (lab[c] != uint32_t(c)) return;
-  for (int t = 0; t < kTopoJumps; ++t) {
-    const uint32_t h = __hip_atomic_load(&hk[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (h == uint32_t(c)) return;
-    const uint32_t hp = __hip_atomic_load(&hk[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (hp == h) return;
-    __hip_atomic_store(&hk[c], hp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+// The edge policy of boruvka.hpp. No edges: padded entries, the point itself, a weight that is
+// negative or not finite. The weight is d2, an exact zero of either sign as kZeroKey; nothing flips.
+// A hooking root keeps the edge and its weight in its own slot.
+struct ForestEdges {
+  const int32_t* idx;
+  const double* d2;
+  int k, m;
+  unsigned long long *ek, *ew;
+  __device__ void init(int i) const {
+    ek[i] = ~0ull;
+    ew[i] = ~0ull;
   }
-  ctl[kCtlAgain] = 1;
-}
-
-__global__ __launch_bounds__(256) void k_tp_relabel(int m, uint32_t* __restrict__ lab, const uint32_t* __restrict__ hk) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < m) lab[i] = hk[lab[i]];
-}
+  __device__ bool ends(int64_t e, int* i, int* j) const {
+    *i = int(e / k);
+    *j = idx[e];
+    if (*j < 0 || *j >= m || *j == *i) return false;
+    const double w = d2[e];
+    return w >= 0.0 && w < __builtin_inf();
+  }
+  __device__ unsigned long long key(int64_t e, int, int) const {
+    const double w = d2[e];
+    return w == 0.0 ? kZeroKey : ord_bits(w);
+  }
+  __device__ uint32_t flip(int, int) const { return 0u; }
+  __device__ void hooked(uint32_t c, unsigned long long pk, unsigned long long key) const {
+    ek[c] = pk;
+    ew[c] = key;
+  }
+};
 
 // flags [m + 1] for compact_flagged: the slots that hold an edge of positive length
 __global__ __launch_bounds__(256) void k_tp_flag(int m, const unsigned long long* __restrict__ ek,
@@ -189,7 +102,7 @@ __global__ __launch_bounds__(256) void k_tp_edges_out(int ne, const int32_t* __r
   const unsigned long long pk = ek[r];
   edges[2 * size_t(p)] = int32_t(pk >> 32);
   edges[2 * size_t(p) + 1] = int32_t(pk & 0xFFFFFFFFu);
-  d2[p] = tp_from_ord(ew[r]);
+  d2[p] = from_ord(ew[r]);
 }
 
 // ---- ordering rows by a packed pair ---------------------------------------------------------------
@@ -260,47 +173,15 @@ static int forest_device(Ctx* c, const double* d_xyz, int64_t m, int32_t k, int3
   PQ_TRY(c->arena.get(size_t(m), &ek));
   PQ_TRY(c->arena.get(size_t(m), &ew));
   PQ_TRY(c->arena.get(size_t(m) + 1, &flags));
-  PQ_TRY(c->arena.get(size_t(kCtlWords), &ctl));
+  PQ_TRY(c->arena.get(size_t(kBvCtlWords), &ctl));
   {
     ProfScope ps(c, "topo_knn");
     PQ_TRY(knn_device(c, d_xyz, m, k, 1, idx, d2));
   }
-  const int eb = ceil_div(ne, 256), pb = ceil_div(m, 256);
-  int32_t h[kCtlWords];
   {
     ProfScope ps(c, "topo_forest");
-    hipLaunchKernelGGL(k_tp_init, dim3(pb), dim3(256), 0, c->stream, M, lab, ek, ew);
-    PQ_HIP(hipGetLastError());
-    for (int round = 0;; ++round) {
-      PQ_HIP(hipMemsetAsync(bw, 0xFF, size_t(m) * 8, c->stream));
-      PQ_HIP(hipMemsetAsync(be, 0xFF, size_t(m) * 8, c->stream));
-      PQ_HIP(hipMemsetAsync(ctl, 0, kCtlWords * 4, c->stream));
-      hipLaunchKernelGGL(k_tp_min_w, dim3(eb), dim3(256), 0, c->stream, ne, int(k), M, static_cast<const int32_t*>(idx),
-                         static_cast<const double*>(d2), static_cast<const uint32_t*>(lab), bw);
-      hipLaunchKernelGGL(k_tp_min_e, dim3(eb), dim3(256), 0, c->stream, ne, int(k), M, static_cast<const int32_t*>(idx),
-                         static_cast<const double*>(d2), static_cast<const uint32_t*>(lab),
-                         static_cast<const unsigned long long*>(bw), be);
-      hipLaunchKernelGGL(k_tp_hook, dim3(pb), dim3(256), 0, c->stream, M, static_cast<const uint32_t*>(lab),
-                         static_cast<const unsigned long long*>(bw), static_cast<const unsigned long long*>(be), hk, ek,
-                         ew, ctl);
-      PQ_HIP(hipGetLastError());
-      PQ_HIP(hipMemcpyAsync(h, ctl, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-      PQ_HIP(hipStreamSynchronize(c->stream));
-      if (h[kCtlHooks] == 0) break;
-      if (round >= kTopoMaxRounds) return fail(PYQSM_EHIP, "skeletal forest: components left after %d rounds", round);
-      ++*rounds;
-      for (int launch = 0;; ++launch) {
-        hipLaunchKernelGGL(k_tp_jump, dim3(pb), dim3(256), 0, c->stream, M, static_cast<const uint32_t*>(lab), hk, ctl);
-        PQ_HIP(hipGetLastError());
-        PQ_HIP(hipMemcpyAsync(h, ctl, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-        PQ_HIP(hipStreamSynchronize(c->stream));
-        if (!h[kCtlAgain]) break;
-        if (launch >= kTopoMaxRelaunch) return fail(PYQSM_EHIP, "skeletal forest: pointer jumping did not settle");
-        PQ_HIP(hipMemsetAsync(ctl + kCtlAgain, 0, 4, c->stream));
-      }
-      hipLaunchKernelGGL(k_tp_relabel, dim3(pb), dim3(256), 0, c->stream, M, lab, static_cast<const uint32_t*>(hk));
-      PQ_HIP(hipGetLastError());
-    }
+    PQ_TRY(boruvka_forest(c, "skeletal forest", m, ne, ForestEdges{idx, d2, int(k), M, ek, ew}, BvScopes{}, lab, hk,
+                          bw, be, ctl, rounds));
   }
   ProfScope ps(c, "topo_forest_sort");
   int64_t* slot;

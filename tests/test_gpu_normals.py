@@ -6,6 +6,7 @@ import pytest
 
 from pyqsm_amd import _lib, hip, qsm_generation, synth
 from pyqsm_amd.geometry.cloud import KDTreeSearchParamHybrid, KDTreeSearchParamKNN, PointCloud
+from tests import deep_chain
 from tests import normals_restatement as R
 
 pytestmark = pytest.mark.gpu
@@ -137,6 +138,29 @@ def test_orientation_sphere_outward(gpu):
     got = hip.orient_normals_tangent_plane(P, N, 30, device=gpu)
     _same(got, R.orient_tangent_plane(P, N, 30))
     assert np.all(np.sum(got * S, axis=1) > 0)
+
+
+@pytest.mark.parametrize("permuted", [False, True])
+def test_orientation_single_deep_chain(gpu, permuted):
+    """Points on the y axis whose normals turn by strictly decreasing angles: the first round hooks
+    all m points into one tree of depth m - 2 (tests/deep_chain.py), and every parity is the XOR of
+    the flips along a path that the bounded pointer jumping has composed."""
+    m = 4096
+    theta = 0.1 + np.r_[0.0, np.cumsum((1.0 + (m - np.arange(m - 1)) / m) / (2.0 * m))]
+    assert theta[-1] < 0.85
+    sign = np.where(np.random.default_rng(3).random(m) < 0.5, -1.0, 1.0)
+    chain_n = np.c_[np.sin(theta), np.zeros(m), np.cos(theta)] * sign[:, None]
+    y = 0.25 * np.arange(m)
+    label = deep_chain.relabel(m, permuted, 22)
+    a, b = deep_chain.line_graph(y, 2)                      # k = 3 counts the point itself
+    deep_chain.assert_one_chain(a, b, 1.0 - np.abs(R.dot3(chain_n[a], chain_n[b])), label)
+    P, N = np.zeros((m, 3)), np.empty((m, 3))
+    P[label, 1] = y
+    N[label] = chain_n
+    got, rounds = hip.orient_normals_tangent_plane(P, N, 3, return_rounds=True, device=gpu)
+    assert rounds == 1
+    _same(got, R.orient_tangent_plane(P, N, 3))
+    assert np.all(got[:, 2] > 0)                            # rooted at the top point: index 0 on the all-equal z
 
 
 def _tree(seed, flat=False):

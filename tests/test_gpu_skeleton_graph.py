@@ -8,6 +8,7 @@ import pytest
 
 from pyqsm_amd import _lib, hip, synth
 from pyqsm_amd.geometry import skeletonize as sk
+from tests import deep_chain
 from tests import topology_restatement as tr
 
 pytestmark = pytest.mark.gpu
@@ -153,6 +154,28 @@ def test_forest_small_and_invalid_inputs(gpu):
         with pytest.raises(_lib.PyQSMHipError) as e:
             hip.skeletal_forest(P, k, device=gpu)
         assert e.value.code == -4
+
+
+@pytest.mark.parametrize("permuted", [False, True])
+def test_forest_single_deep_chain(gpu, permuted):
+    """Strictly decreasing gaps along the x axis: the first round hooks all m points into one tree of
+    depth m - 2 (tests/deep_chain.py), which the bounded pointer jumping has to flatten."""
+    m = 4096
+    gaps = 1.0 + (m - np.arange(m - 1)) / m
+    x = np.r_[0.0, np.cumsum(gaps)]
+    label = deep_chain.relabel(m, permuted, 21)
+    a, b = deep_chain.line_graph(x, 2)
+    deep_chain.assert_one_chain(a, b, (x[b] - x[a]) ** 2, label)
+    P = np.zeros((m, 3))
+    P[label, 0] = x
+    edges, d2, rounds = hip.skeletal_forest(P, 2, return_rounds=True, device=gpu)
+    assert rounds == 1
+    _check_layout(edges, m)
+    want, _ = tr.skeletal_forest(P, 2)
+    assert len(want) == m - 1 and np.array_equal(edges, want)
+    if not permuted:
+        assert np.array_equal(edges, np.stack([np.arange(m - 1), np.arange(1, m)], axis=1))
+    assert np.array_equal(d2.view(np.uint64), _knn_d2_of(P, 2, edges, gpu).view(np.uint64))
 
 
 # ---- chains ---------------------------------------------------------------------------------
