@@ -13,14 +13,12 @@
 
 #include "common.hpp"
 #include "grid.hpp"
+#include "knn.hpp"
 #include "sparse.hpp"
 #include "voxel.hpp"
 
 namespace pyqsm {
 
-int knn_device(Ctx* c, const double* xyz, int64_t n, int32_t k, int32_t exclude_self, int32_t* idx,
-               double* d2);                // knn.hip
-static constexpr int kKnnMaxK = 192;        // knn.hip kMaxK
 static constexpr int kLaneMax = 64;         // voxels with at most this many members: one lane each
 static constexpr int kWaveTile = 256;       // members a wave stages per step for a larger voxel
 static constexpr int kTilePad = kWaveTile + 1;  // column stride in LDS: the six columns on distinct banks

@@ -5,8 +5,9 @@
 // points). Recollected from jakteristics, parity unpinned; tests/features_restatement.py states the
 // contract in NumPy/SciPy.
 //
-// Features. The cloud is binned into cells of the radius; one wave per point, in the grid's sorted
-// order, walks the nine stencil runs 64 candidates at a time. Candidates inside the ball (d2 <= r2,
+// Features. The cloud is binned into cells of the radius (grid.hpp: ball_grid); one wave per point, in
+// the grid's sorted order, walks the nine stencil runs 64 candidates at a time with the pieces of
+// wave_select.hpp (the count, the two bisections, the append). Candidates inside the ball (d2 <= r2,
 // or the L1 distance <= r) have their offsets o = p_j - p_i staged in LDS; every 64 staged offsets
 // each lane adds one neighbour's first and second moments. The moments are fixed point: every
 // term o_a (and the fp64 product o_a * o_b) is scaled by a power of two that maps the largest
@@ -14,14 +15,15 @@
 // by a butterfly. The sum is then exact, so the result does not depend on the order in which the
 // grid's binning left the points of a cell, nor on the order of the input (integer additions only,
 // no atomics). A point with more than max_k points in its ball keeps the max_k first by (distance,
-// index): the threshold distance by bisection on its bit pattern, then the index bound among the
-// ties at it by bisection on the index. k_feat_finish turns the moments' covariance into the
+// index): the threshold distance (kth_by_bits), then the index bound among the ties at it
+// (kth_index). k_feat_finish turns the moments' covariance into the
 // eigenvalues and e3 (pca.hpp sym3_eigh_desc) and writes the requested features in fp64.
 //
 // Smoothing. The k nearest of every query, ascending by (d2, index): the exact kNN (knn.hip) when
 // the queries are the points themselves; otherwise k_query_knn, one wave per query over a grid of
-// cells of R: with at least k points within R the k first by (d2, index) are exact, the others are
-// served again with R doubled. The neighbour table stays in the arena; k_smooth_reduce gathers each
+// cells of R: with at least k points within R the k first by (d2, index) are exact (selected and
+// sorted as wave_select.hpp says, ties at the k-th distance cut by index), the others are served
+// again with R doubled. The neighbour table stays in the arena; k_smooth_reduce gathers each
 // row's values into LDS and reduces them (mean: fp64 sum in neighbour order over k; median: ranks by
 // (value, position), the mean of the two middle values for even k; min, max), NaN propagating as in
 // NumPy.
@@ -30,23 +32,17 @@
 
 #include "common.hpp"
 #include "grid.hpp"
+#include "knn.hpp"
 #include "pca.hpp"
+#include "wave_select.hpp"
 
 namespace pyqsm {
 
-int knn_device(Ctx* c, const double* xyz, int64_t n, int32_t k, int32_t exclude_self, int32_t* idx,
-               double* d2);                // knn.hip
-static constexpr int kSmoothMaxK = 192;    // knn.hip kMaxK: largest k of a smoothing
+// (kKnnMaxK, knn.hpp: largest k of a smoothing)
 static constexpr int kFeatCount = 14;      // jakteristics' FEATURE_NAMES
 static constexpr int kFeatMaxCols = 32;    // columns one call may ask for
 static constexpr int kFeatWaves = 4;       // waves per block of k_feat_moments
 static constexpr int kQueryCap = 512;      // (d2, index) pairs k_query_knn sorts without bisection
-
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // ---- fixed-point moments -------------------------------------------------------------------------
 // A signed 128-bit integer as (low word, high word).
@@ -126,75 +122,51 @@ __global__ __launch_bounds__(64 * kFeatWaves) void k_feat_moments(
   const double x = xyz[3 * size_t(i)], y = xyz[3 * size_t(i) + 1], z = xyz[3 * size_t(i) + 2];
   StencilRuns rr;  // clamped like the points were binned
   point_stencil_runs(g, start, x, y, z, &rr);
-  // in the ball and (d < tau, or d == tau and index <= ilim)
+  // candidate q at (a, b, c): in the ball and (d < tau, or d == tau and index <= ilim)
+  auto kept = [&](int q, double tau, int ilim, double& a, double& b, double& c) {
+    const double d = feat_dist<CO, L1>(co, q, x, y, z, a, b, c);
+    return d <= lim && (d < tau || (d == tau && order[q] <= ilim));
+  };
   auto count = [&](double tau, int ilim) {
-    int cnt = 0;
-    for (int r = 0; r < 9; ++r)
-      for (int base = rr.qb[r]; base < rr.qe[r]; base += 64) {
-        const int q = base + lane;
-        bool in = false;
-        if (q < rr.qe[r]) {
-          double a, b, c;
-          const double d = feat_dist<CO, L1>(co, q, x, y, z, a, b, c);
-          in = d <= lim && (d < tau || (d == tau && order[q] <= ilim));
-        }
-        cnt += __popcll(__ballot(in));
-      }
-    return cnt;
+    return wave_count(rr, [&](int q) {
+      double a, b, c;
+      return kept(q, tau, ilim, a, b, c);
+    });
   };
   const int total = count(__builtin_inf(), 0x7FFFFFFF);
   double tau = __builtin_inf();
   int ilim = 0x7FFFFFFF;
-  if (total > max_k) {
-    unsigned long long lo = 0, hi = (unsigned long long)__double_as_longlong(lim);
-    while (lo < hi) {  // smallest t with #{d <= t} >= max_k (d >= 0 orders as its bits)
-      const unsigned long long mid = lo + ((hi - lo) >> 1);
-      if (count(__longlong_as_double((long long)mid), 0x7FFFFFFF) >= max_k) hi = mid;
-      else lo = mid + 1;
-    }
-    tau = __longlong_as_double((long long)lo);
-    int ia = 0, ib = n - 1;  // smallest index bound that completes max_k among the ties at tau
-    while (ia < ib) {
-      const int mid = ia + ((ib - ia) >> 1);
-      if (count(tau, mid) >= max_k) ib = mid;
-      else ia = mid + 1;
-    }
-    ilim = ia;
+  if (total > max_k) {  // the max_k-th distance, then the index bound that completes max_k among its ties
+    tau = kth_by_bits(lim, max_k, [&](double t) { return count(t, 0x7FFFFFFF); });
+    ilim = kth_index(n, max_k, [&](int ib) { return count(tau, ib); });
   }
   I128 M[9];
   for (int t = 0; t < 9; ++t) M[t] = I128{0ull, 0LL};
   int have = 0, N = 0;
-  for (int r = 0; r < 9; ++r)
-    for (int base = rr.qb[r]; base < rr.qe[r]; base += 64) {
-      const int q = base + lane;
-      bool take = false;
-      double a = 0.0, b = 0.0, c = 0.0;
-      if (q < rr.qe[r]) {
-        const double d = feat_dist<CO, L1>(co, q, x, y, z, a, b, c);
-        take = d <= lim && (d < tau || (d == tau && order[q] <= ilim));
-      }
-      const unsigned long long kb = __ballot(take);
-      if (take) {  // have < 64 here, so slot < 128
-        const int slot = have + __popcll(kb & ((1ull << lane) - 1ull));
-        sb[w][0][slot] = a - x;
-        sb[w][1][slot] = b - y;
-        sb[w][2][slot] = c - z;
-      }
-      have += __popcll(kb);
-      if (have >= 64) {
-        wave_sync();
-        add_moments(M, sc, sb[w][0][lane], sb[w][1][lane], sb[w][2][lane]);
-        wave_sync();
-        if (lane < have - 64) {
-          sb[w][0][lane] = sb[w][0][lane + 64];
-          sb[w][1][lane] = sb[w][1][lane + 64];
-          sb[w][2][lane] = sb[w][2][lane + 64];
-        }
-        wave_sync();
-        have -= 64;
-        N += 64;
-      }
+  wave_candidates(rr, [&](int q, bool live) {
+    double a = 0.0, b = 0.0, c = 0.0;
+    bool take = false;
+    if (live) take = kept(q, tau, ilim, a, b, c);
+    const int slot = wave_append(take, have);
+    if (take) {  // have was < 64, so slot < 128
+      sb[w][0][slot] = a - x;
+      sb[w][1][slot] = b - y;
+      sb[w][2][slot] = c - z;
     }
+    if (have >= 64) {
+      wave_sync();
+      add_moments(M, sc, sb[w][0][lane], sb[w][1][lane], sb[w][2][lane]);
+      wave_sync();
+      if (lane < have - 64) {
+        sb[w][0][lane] = sb[w][0][lane + 64];
+        sb[w][1][lane] = sb[w][1][lane + 64];
+        sb[w][2][lane] = sb[w][2][lane + 64];
+      }
+      wave_sync();
+      have -= 64;
+      N += 64;
+    }
+  });
   wave_sync();
   if (lane < have) add_moments(M, sc, sb[w][0][lane], sb[w][1][lane], sb[w][2][lane]);
   N += have;
@@ -302,18 +274,10 @@ __global__ __launch_bounds__(128) void k_query_knn(int m_list, const int32_t* __
   StencilRuns rr;
   point_stencil_runs(g, start, x, y, z, &rr);
   auto count = [&](double tau, int ilim) {  // d2 <= R2 and (d2 < tau, or d2 == tau and index <= ilim)
-    int cnt = 0;
-    for (int r = 0; r < 9; ++r)
-      for (int base = rr.qb[r]; base < rr.qe[r]; base += 64) {
-        const int q = base + lane;
-        bool in = false;
-        if (q < rr.qe[r]) {
-          const double d = co.d2(q, x, y, z);
-          in = d <= R2 && (d < tau || (d == tau && order[q] <= ilim));
-        }
-        cnt += __popcll(__ballot(in));
-      }
-    return cnt;
+    return wave_count(rr, [=](int q) {
+      const double d = co.d2(q, x, y, z);
+      return d <= R2 && (d < tau || (d == tau && order[q] <= ilim));
+    });
   };
   const int total = count(__builtin_inf(), 0x7FFFFFFF);
   if (total < k) {
@@ -323,67 +287,28 @@ __global__ __launch_bounds__(128) void k_query_knn(int m_list, const int32_t* __
   double tau = __builtin_inf();
   int ilim = 0x7FFFFFFF;
   if (total > kQueryCap) {  // exactly k survive: the k-th d2, then the index bound among its ties
-    unsigned long long lo = 0, hi = (unsigned long long)__double_as_longlong(R2);
-    while (lo < hi) {
-      const unsigned long long mid = lo + ((hi - lo) >> 1);
-      if (count(__longlong_as_double((long long)mid), 0x7FFFFFFF) >= k) hi = mid;
-      else lo = mid + 1;
-    }
-    tau = __longlong_as_double((long long)lo);
-    int ia = 0, ib = n_src - 1;
-    while (ia < ib) {
-      const int mid = ia + ((ib - ia) >> 1);
-      if (count(tau, mid) >= k) ib = mid;
-      else ia = mid + 1;
-    }
-    ilim = ia;
+    tau = kth_by_bits(R2, k, [&](double t) { return count(t, 0x7FFFFFFF); });
+    ilim = kth_index(n_src, k, [&](int ib) { return count(tau, ib); });
   }
   int have = 0;  // at most kQueryCap (all of them) or exactly k (after the bisections)
-  for (int r = 0; r < 9; ++r)
-    for (int base = rr.qb[r]; base < rr.qe[r]; base += 64) {
-      const int q = base + lane;
-      double d = 0.0;
-      bool take = false;
-      int id = 0;
-      if (q < rr.qe[r]) {
-        d = co.d2(q, x, y, z);
-        id = order[q];
-        take = d <= R2 && (d < tau || (d == tau && id <= ilim));
-      }
-      const unsigned long long kb = __ballot(take);
-      const int slot = have + __popcll(kb & ((1ull << lane) - 1ull));
-      if (take && slot < kQueryCap) {
-        sd[w][slot] = d;
-        si[w][slot] = id;
-      }
-      have += __popcll(kb);
+  wave_candidates(rr, [=, &have](int q, bool live) {
+    double d = 0.0;
+    int id = 0;
+    bool take = false;
+    if (live) {
+      d = co.d2(q, x, y, z);
+      id = order[q];
+      const bool in = d <= R2, below = d < tau, tie = d == tau && id <= ilim;
+      take = in && (below || tie);
     }
+    const int slot = wave_append(take, have);
+    if (take && slot < kQueryCap) {
+      sd[w][slot] = d;
+      si[w][slot] = id;
+    }
+  });
   have = have < kQueryCap ? have : kQueryCap;
-  int np2 = 1;
-  while (np2 < have) np2 <<= 1;
-  for (int u = have + lane; u < np2; u += 64) {
-    sd[w][u] = __builtin_inf();
-    si[w][u] = 0x7FFFFFFF;
-  }
-  wave_sync();
-  for (int k2 = 2; k2 <= np2; k2 <<= 1)
-    for (int j = k2 >> 1; j > 0; j >>= 1) {
-      for (int a = lane; a < np2; a += 64) {
-        const int b = a ^ j;
-        if (b > a) {
-          const double da = sd[w][a], db = sd[w][b];
-          const int ia = si[w][a], ib = si[w][b];
-          const bool a_gt_b = da > db || (da == db && ia > ib);
-          if (a_gt_b == ((a & k2) == 0)) {
-            sd[w][a] = db;
-            si[w][a] = ib;
-            sd[w][b] = da;
-            si[w][b] = ia;
-          }
-        }
-      }
-      wave_sync();
-    }
+  wave_sort_pairs(sd[w], si[w], have);
   for (int u = lane; u < k; u += 64) idx[size_t(qi) * k + u] = si[w][u];
 }
 
@@ -393,8 +318,8 @@ __global__ __launch_bounds__(128) void k_query_knn(int m_list, const int32_t* __
 __global__ __launch_bounds__(128) void k_smooth_reduce(int m, const int32_t* __restrict__ idx, int k,
                                                        const double* __restrict__ vals, int F, int reducer,
                                                        double* __restrict__ out) {
-  __shared__ double sv[2][kSmoothMaxK];
-  __shared__ double ss[2][kSmoothMaxK];
+  __shared__ double sv[2][kKnnMaxK];
+  __shared__ double ss[2][kKnnMaxK];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int q = blockIdx.x * 2 + w;
   if (q >= m) return;  // whole wave
@@ -471,18 +396,6 @@ static FeatScale feat_scale(const double bound[3]) {
   return sc;
 }
 
-// The grid the neighbourhood kernels walk: cells of at least `cell`, over the cloud without its
-// sparse tails (they clamp into the outermost cells), as normals.hip builds it.
-static int feature_grid(Ctx* c, const double* d_xyz, int64_t n, double cell, DevGrid* g, double box[6],
-                        bool* all_f32) {
-  PQ_TRY(cloud_bbox(c, d_xyz, n, box, box + 3, all_f32));
-  double rb[6];
-  std::copy(box, box + 6, rb);
-  int64_t outside = 0;
-  PQ_TRY(robust_box(c, d_xyz, n, int(std::min<int64_t>(8192, std::max<int64_t>(256, n / 256))), rb, &outside));
-  return build_grid(c, d_xyz, n, cell, int64_t(1) << 28, g, rb, *all_f32);
-}
-
 // The k nearest of the m queries d_qry among the n points d_src into d_idx [m, k] (k <= n).
 static int query_knn_device(Ctx* c, const double* d_src, int64_t n, const double* d_qry, int64_t m, int k,
                             int32_t* d_idx) {
@@ -505,9 +418,7 @@ static int query_knn_device(Ctx* c, const double* d_src, int64_t n, const double
     if (!std::isfinite(R * R)) return fail(PYQSM_ERANGE, "query kNN: no radius holds k points");
     const Arena::Mark mk = c->arena.mark();
     DevGrid g;
-    double gb[6];
-    bool f32 = false;
-    PQ_TRY(feature_grid(c, d_src, n, R * (1.0 + 1.0 / 1048576.0), &g, gb, &f32));
+    PQ_TRY(ball_grid(c, d_src, n, R, &g));
     PQ_HIP(hipMemsetAsync(n_next, 0, 4, c->stream));
     on_coords(g, [&](auto co) {
       hipLaunchKernelGGL(k_query_knn<decltype(co)>, dim3(ceil_div(left, 2)), dim3(128), 0, c->stream, int(left),
@@ -570,8 +481,7 @@ int pyqsm_geometric_features(const double* xyz, int64_t n, double radius, int32_
   double box[6];
   {
     ProfScope ps(c, "features_grid");
-    bool all_f32 = false;
-    PQ_TRY(feature_grid(c, d_xyz, n, radius * (1.0 + 1.0 / 1048576.0), &g, box, &all_f32));
+    PQ_TRY(ball_grid(c, d_xyz, n, radius, &g, box));
   }
   // an offset inside the ball is at most the radius (one rounding more) and at most the extent
   double bound[3];
@@ -612,7 +522,7 @@ int pyqsm_smooth_values(const double* xyz, int64_t n, const double* qry, int64_t
   PQ_TRY(check_count(n));
   PQ_TRY(check_count(m));
   if (!qry && m != n) return fail(PYQSM_EINVAL, "without queries m must equal n");
-  if (k < 1 || k > kSmoothMaxK) return fail(PYQSM_ERANGE, "k must be in [1, %d]", kSmoothMaxK);
+  if (k < 1 || k > kKnnMaxK) return fail(PYQSM_ERANGE, "k must be in [1, %d]", kKnnMaxK);
   if (k > n) return fail(PYQSM_EINVAL, "k = %d is larger than the %lld points", int(k), (long long)n);
   if (reducer < -1 || reducer > 3) return fail(PYQSM_EINVAL, "reducer must be in [-1, 3]");
   if (reducer >= 0 && (F < 1 || !values || !out)) return fail(PYQSM_EINVAL, "pyqsm_smooth_values: values and out needed");

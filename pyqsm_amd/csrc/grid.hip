@@ -2334,13 +2334,19 @@ static int canonical_cell_order(Ctx* c, const double* d_src, int64_t n, DevGrid*
   return 0;
 }
 
-int radius_grid(Ctx* c, const double* d_src, int64_t n, double radius, DevGrid* g) {
+int ball_grid(Ctx* c, const double* d_src, int64_t n, double radius, DevGrid* g, double* cloud_box) {
   double box[6];
   bool all_f32 = false;  // every source coordinate fp32-representable: 16-byte fp32 records (grid.hpp: on_coords)
   PQ_TRY(cloud_bbox(c, d_src, n, box, box + 3, &all_f32));
+  if (cloud_box)
+    for (int a = 0; a < 6; ++a) cloud_box[a] = box[a];
   int64_t outside = 0;
   PQ_TRY(robust_box(c, d_src, n, int(std::min<int64_t>(8192, std::max<int64_t>(256, n / 256))), box, &outside));
-  PQ_TRY(build_grid(c, d_src, n, radius * (1.0 + 1.0 / 1048576.0), int64_t(1) << 28, g, box, all_f32));
+  return build_grid(c, d_src, n, radius * (1.0 + 1.0 / 1048576.0), int64_t(1) << 28, g, box, all_f32);
+}
+
+int radius_grid(Ctx* c, const double* d_src, int64_t n, double radius, DevGrid* g) {
+  PQ_TRY(ball_grid(c, d_src, n, radius, g));
   return canonical_cell_order(c, d_src, n, g);
 }
 

@@ -380,14 +380,17 @@ void read_directory(Ctx* c, const DevGrid& g, int64_t ncell, int32_t* begin_out)
 // by block sums and a deterministic scatter (no atomics, no second pass over xyz).
 int coarsen_grid(Ctx* c, const DevGrid& fine, int64_t n, int factor, DevGrid* coarse);
 
-// ---- what the fixed-radius kernels share (radius.hip, adjacency.hip) --------------------------
-// The grid a fixed-radius query walks: `d_src` binned into cells of edge `radius` (a hair more, so
-// that an inclusive bound stays inside the 27 cells), over the cloud without its sparse tails
-// (cloud_bbox -> robust_box -> build_grid); fp32 records when every coordinate allows. Points the
-// box gave up sit in its outermost cells, and queries find them through clamped_cell.
-// Inside a cell the points are in ascending original index (not in the arrival order build_grid leaves), so
-// the order in which a query walks its candidates, and with it its choice among ties at the k-th distance,
-// is the same for every build over the same cloud.
+// ---- what the fixed-radius kernels share (radius, adjacency, grow, normals, features) -----------
+// The grid a ball query walks: `d_src` binned into cells of edge `radius` (times 1 + 2^-20, so that an
+// inclusive bound stays inside the 27 cells), at most 2^28 cells, over the cloud without its sparse
+// tails (cloud_bbox -> robust_box -> build_grid; the tails may hold one point in 256, no fewer than
+// 256 and no more than 8192); fp32 records when every coordinate allows. Points the box gave up sit in its outermost
+// cells, and queries find them through clamped_cell. cloud_box (optional): min xyz, max xyz of the
+// whole cloud, tails included.
+int ball_grid(Ctx* c, const double* d_src, int64_t n, double radius, DevGrid* g, double* cloud_box = nullptr);
+// ball_grid, and inside a cell the points in ascending original index (not in the arrival order
+// build_grid leaves), so the order in which a query walks its candidates, and with it its choice among
+// ties at the k-th distance, is the same for every build over the same cloud.
 int radius_grid(Ctx* c, const double* d_src, int64_t n, double radius, DevGrid* g);
 // *perm = the m query points (f64 [m,3], device) in the order of the grid's cells, or nullptr for
 // fewer than 1024 queries (or PYQSM_RADIUS_SORT=0): serve them in the caller's order.

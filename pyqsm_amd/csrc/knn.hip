@@ -30,6 +30,7 @@
 #include <atomic>
 
 #include "grid.hpp"
+#include "knn.hpp"
 
 #include <cmath>
 
@@ -46,7 +47,6 @@ static constexpr int kMaxRing = 3;
 // does walk all 16 shells looks up 13 000 row segments (200 rounds of 64), about what a launch
 // of the next level costs. PYQSM_KNN_WIDE overrides.
 static constexpr int kWideRing = 16;
-static constexpr int kMaxK = 192;
 
 struct KnnGrid {
   int nx, ny, nz;
@@ -786,7 +786,7 @@ static int launch_knn(Ctx* c, int n_query, const int32_t* list, const int32_t* p
 
 int knn_device(Ctx* c, const double* xyz, int64_t n, int32_t k, int32_t exclude_self,
                int32_t* idx, double* d2) {
-  if (k <= 0 || k > kMaxK) return fail(PYQSM_ERANGE, "k must be in [1, %d]", kMaxK);
+  if (k <= 0 || k > kKnnMaxK) return fail(PYQSM_ERANGE, "k must be in [1, %d]", kKnnMaxK);
   if (n == 0) return 0;
   const int N = int(n);
   // ---- level-0 cell edge: aim at ~k/3 points per occupied cell -----------

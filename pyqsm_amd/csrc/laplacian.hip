@@ -35,14 +35,12 @@
 // floating-point operation below in the same order, so discrete decisions
 // (which neighbours form the fan) agree even in degenerate configurations.
 #include "grid.hpp"
+#include "knn.hpp"
 #include "pca.hpp"
 
 #include <cmath>
 
 namespace pyqsm {
-
-int knn_device(Ctx* c, const double* xyz, int64_t n, int32_t k, int32_t exclude_self,
-               int32_t* idx, double* d2);
 
 // Orthonormal basis (e1, e2) of the plane normal to the unit vector n.
 __host__ __device__ inline void tangent_basis(const double n[3], double e1[3], double e2[3]) {

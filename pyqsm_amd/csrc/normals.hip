@@ -5,10 +5,10 @@
 // for bit.
 //
 // Normals. Hybrid search (radius > 0 and finite): the source cloud is binned into cells of the
-// radius; one wave per query (in the grid's sorted order) counts its candidates with d2 < r2 in the
-// 27 cells around it, collects them in LDS (or, when more than kNormCap lie inside, first finds the
-// max_nn-th smallest d2 exactly by bisection on its bit pattern, and collects those below it and
-// every tie at it), bitonic-sorts them by (d2, index) and keeps the first max_nn. KNN search: the
+// radius (grid.hpp: ball_grid); one wave per query (in the grid's sorted order) selects and sorts its
+// candidates with d2 < r2 in the 27 cells around it with the pieces of wave_select.hpp: all of them,
+// or, when more than kNormCap lie inside, those up to the max_nn-th smallest d2 and every tie at it
+// (more than kNormCap of those: the overflow flag); it keeps the first max_nn. KNN search: the
 // exact kNN (knn.hip, the point itself counted) already comes ascending by (d2, index). Either way
 // the wave gathers the offsets p_j - p_i into LDS, three lanes sum the mean and six lanes the
 // covariance entries, one add at a time in neighbour order; k_normal_finish then runs the Jacobi
@@ -25,23 +25,17 @@
 #include "boruvka.hpp"
 #include "common.hpp"
 #include "grid.hpp"
+#include "knn.hpp"
 #include "pca.hpp"
+#include "wave_select.hpp"
 
 namespace pyqsm {
 
-int knn_device(Ctx* c, const double* xyz, int64_t n, int32_t k, int32_t exclude_self, int32_t* idx,
-               double* d2);                  // knn.hip
-static constexpr int kKnnMaxK = 192;          // knn.hip kMaxK: largest k of a KNN search and orientation
+// (kKnnMaxK, knn.hpp: largest max_nn of a KNN search and largest k of the orientation)
 static constexpr int kNormMaxNN = 256;        // largest max_nn of a hybrid search
 static constexpr int kNormCap = 512;          // (d2, index) pairs a wave sorts in LDS
 
 // ---- neighbourhoods and covariance --------------------------------------------------------------
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // Covariance of the first cnt neighbours listed in nb (LDS, ascending (d2, index)) of point i:
 // o_j = p_j - p_i, m = (sum o) / cnt, C = (sum (o - m)(o - m)^T) / cnt, every sum from 0.0 one add
 // at a time in list order. o: LDS [3][kNormMaxNN], scratch: LDS, at least 3 doubles. Lane c < 6
@@ -95,77 +89,33 @@ __global__ __launch_bounds__(128) void k_normal_hybrid(int n, const double* __re
   StencilRuns rr;  // clamped like the points were binned: the grid may cover less than the cloud
   point_stencil_runs(g, start, x, y, z, &rr);
   auto count_le = [&](double tau) {  // candidates with d2 < r2 and d2 <= tau
-    int cnt = 0;
-    for (int r = 0; r < 9; ++r)
-      for (int base = rr.qb[r]; base < rr.qe[r]; base += 64) {
-        const int q = base + lane;
-        bool in = false;
-        if (q < rr.qe[r]) {
-          const double d = co.d2(q, x, y, z);
-          in = d < r2 && d <= tau;
-        }
-        cnt += __popcll(__ballot(in));
-      }
-    return cnt;
+    return wave_count(rr, [=](int q) {
+      const double d = co.d2(q, x, y, z);
+      return d < r2 && d <= tau;
+    });
   };
   const int total = count_le(__builtin_inf());
-  double tau = __builtin_inf();  // collect d2 < tau, and d2 == tau
-  if (total > kNormCap) {
-    unsigned long long lo = 0, hi = (unsigned long long)__double_as_longlong(r2);
-    while (lo < hi) {  // smallest t with #{d2 <= t} >= k (k < total; d2 >= 0 orders as its bits)
-      const unsigned long long mid = lo + ((hi - lo) >> 1);
-      if (count_le(__longlong_as_double((long long)mid)) >= k) hi = mid;
-      else lo = mid + 1;
-    }
-    tau = __longlong_as_double((long long)lo);
-  }
+  // too many for the LDS: only those up to the k-th smallest d2 (k < total), every tie at it included
+  const double tau = total > kNormCap ? kth_by_bits(r2, k, count_le) : __builtin_inf();
   int have = 0;
-  for (int r = 0; r < 9; ++r)
-    for (int base = rr.qb[r]; base < rr.qe[r]; base += 64) {
-      const int q = base + lane;
-      double d = 0.0;
-      bool take = false;
-      if (q < rr.qe[r]) {
-        d = co.d2(q, x, y, z);
-        take = d < r2 && d <= tau;
-      }
-      const unsigned long long kb = __ballot(take);
-      const int slot = have + __popcll(kb & ((1ull << lane) - 1ull));
-      if (take && slot < kNormCap) {
-        sd[w][slot] = d;
-        si[w][slot] = order[q];
-      }
-      have += __popcll(kb);
+  wave_candidates(rr, [=, &have](int q, bool live) {
+    double d = 0.0;
+    bool take = false;
+    if (live) {
+      d = co.d2(q, x, y, z);
+      take = d < r2 && d <= tau;
     }
+    const int slot = wave_append(take, have);
+    if (take && slot < kNormCap) {
+      sd[w][slot] = d;
+      si[w][slot] = order[q];
+    }
+  });
   if (have > kNormCap) {
     if (lane == 0) *overflow = 1;
     have = kNormCap;
   }
-  int np2 = 1;
-  while (np2 < have) np2 <<= 1;
-  for (int t = have + lane; t < np2; t += 64) {
-    sd[w][t] = __builtin_inf();
-    si[w][t] = 0x7FFFFFFF;
-  }
-  wave_sync();
-  for (int k2 = 2; k2 <= np2; k2 <<= 1)
-    for (int j = k2 >> 1; j > 0; j >>= 1) {
-      for (int t = lane; t < np2; t += 64) {
-        const int u = t ^ j;
-        if (u > t) {
-          const double da = sd[w][t], db = sd[w][u];
-          const int ia = si[w][t], ib = si[w][u];
-          const bool a_gt_b = da > db || (da == db && ia > ib);
-          if (a_gt_b == ((t & k2) == 0)) {
-            sd[w][t] = db;
-            si[w][t] = ib;
-            sd[w][u] = da;
-            si[w][u] = ia;
-          }
-        }
-      }
-      wave_sync();
-    }
+  wave_sort_pairs(sd[w], si[w], have);
   covariance_of_list(lane, i, min(have, k), si[w], xyz, so[w], sd[w], cov, cnt_out);
 }
 
@@ -327,12 +277,7 @@ static int normals_device(Ctx* c, const double* d_xyz, int64_t n, double radius,
     DevGrid g;
     {
       ProfScope ps(c, "normals_grid");
-      double box[6];
-      bool all_f32 = false;
-      PQ_TRY(cloud_bbox(c, d_xyz, n, box, box + 3, &all_f32));
-      int64_t outside = 0;
-      PQ_TRY(robust_box(c, d_xyz, n, int(std::min<int64_t>(8192, std::max<int64_t>(256, n / 256))), box, &outside));
-      PQ_TRY(build_grid(c, d_xyz, n, radius * (1.0 + 1.0 / 1048576.0), int64_t(1) << 28, &g, box, all_f32));
+      PQ_TRY(ball_grid(c, d_xyz, n, radius, &g));
     }
     ProfScope ps(c, "normals_cov");
     on_coords(g, [&](auto co) {

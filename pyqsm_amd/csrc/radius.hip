@@ -12,11 +12,15 @@
 //                       pyQSM/geometry/reconstruction.py:238-244 and
 //                       pyQSM/tree_isolation.py:126-131,207-209. Strict d < dist, like
 //                       cKDTree. The source cloud is binned into cells of edge `dist`;
-//                       one lane per query walks its 27 cells. When more than k points
-//                       lie inside the bound, the k-th smallest squared distance is found
-//                       exactly by bisection on its bit pattern and only those are marked.
+//                       one lane per query walks its 27 cells (radius_walk.hpp). When more
+//                       than k points lie inside the bound, the k-th smallest squared distance
+//                       is found exactly and only those are marked.
+//   pyqsm_radius_knn    the same neighbours as sorted padded tables, and pyqsm_radius_reduce,
+//                       which reduces their value rows in the kernel: one wave per query
+//                       (wave_select.hpp), the same selection as the walk to the bit.
 // Squared distances are fp64, ((dx*dx)+dy*dy)+dz*dz, the accumulation of cKDTree.
 #include "radius_walk.hpp"
+#include "wave_select.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -53,10 +57,10 @@ __global__ __launch_bounds__(256) void k_radius_mark(int m, const double* __rest
 
 
 // ---- k nearest within a bound, as sorted padded tables (cKDTree.query semantics) --------
-// One wave per query. Count the source points inside the bound (64 candidates per step);
-// if there are more than k, find the k-th smallest squared distance exactly by bisection
-// on its bit pattern (rare: k defaults to 500 at a 5 cm bound); collect the survivors in
-// LDS, bitonic-sort them by (d2, index) and write k entries, padded with (inf, n).
+// One wave per query, with the pieces of wave_select.hpp: count the source points inside the bound;
+// if there are more than k, find the k-th smallest squared distance (rare: k defaults to 500 at a
+// 5 cm bound); collect the survivors in LDS, sort them by (d2, index) and write k entries, padded
+// with (inf, n).
 static constexpr int kKnnCap = 2048;  // largest k (LDS: 24 KB per wave)
 
 // The front both kernels share: the neighbours of (x, y, z) — at most k, d2 < r2 — into sd / si (this
@@ -65,93 +69,45 @@ template <class CO>
 __device__ __forceinline__ int radius_collect_sorted(const GridParams& g, const int32_t* __restrict__ start,
                                                      const int32_t* __restrict__ order, CO co, double x, double y,
                                                      double z, double r2, int k, double* sd, int* si) {
-  const int lane = threadIdx.x & 63;
   StencilRuns rr;
   point_stencil_runs(g, start, x, y, z, &rr);
-  // count of candidates with d2 < r2 and d2 <= tau
-  auto count_le = [&](double tau) {
-    int cnt = 0;
-    for (int r = 0; r < 9; ++r)
-      for (int base = rr.qb[r]; base < rr.qe[r]; base += 64) {
-        const int q = base + lane;
-        bool in = false;
-        if (q < rr.qe[r]) {
-          const double d = co.d2(q, x, y, z);
-          in = d < r2 && d <= tau;
-        }
-        cnt += __popcll(__ballot(in));
-      }
-    return cnt;
+  auto count_le = [&](double tau) {  // candidates with d2 < r2 and d2 <= tau
+    return wave_count(rr, [=](int q) {
+      const double d = co.d2(q, x, y, z);
+      return d < r2 && d <= tau;
+    });
   };
   int total = count_le(__builtin_inf());
   double tau = __builtin_inf();
   int budget = 0;  // ties at tau that still fit
   if (total > k) {
-    unsigned long long lo = 0, hi = (unsigned long long)__double_as_longlong(r2);
-    while (lo < hi) {  // smallest t with #{d2 <= t} >= k
-      const unsigned long long mid = lo + ((hi - lo) >> 1);
-      if (count_le(__longlong_as_double((long long)mid)) >= k) hi = mid;
-      else lo = mid + 1;
-    }
-    tau = __longlong_as_double((long long)lo);
-    const int n_below = lo == 0 ? 0 : count_le(__longlong_as_double((long long)(lo - 1)));
+    tau = kth_by_bits(r2, k, count_le);
+    const long long tb = __double_as_longlong(tau);
+    const int n_below = tb == 0 ? 0 : count_le(__longlong_as_double(tb - 1));
     budget = k - n_below;
     total = k;
   }
-  // collect (ties at tau in candidate order until the budget is used up)
+  // everything below tau, and the ties at tau in candidate order until the budget is used up: the
+  // tie rule of radius_walk.hpp's walk<2>
   int have = 0, ties = 0;
   if (total > 0)
-    for (int r = 0; r < 9; ++r)
-      for (int base = rr.qb[r]; base < rr.qe[r]; base += 64) {
-        const int q = base + lane;
-        double d = 0.0;
-        bool below = false, tie = false;
-        if (q < rr.qe[r]) {
-          d = co.d2(q, x, y, z);
-          below = d < r2 && d < tau;
-          tie = d < r2 && d == tau;
-        }
-        const unsigned long long tb = __ballot(tie);
-        const int tie_rank = ties + __popcll(tb & ((1ull << lane) - 1ull));
-        const bool take = below || (tie && tie_rank < budget);
-        const unsigned long long kb = __ballot(take);
-        if (take) {
-          const int slot = have + __popcll(kb & ((1ull << lane) - 1ull));
-          sd[slot] = d;
-          si[slot] = order[q];
-        }
-        have += __popcll(kb);
-        ties += __popcll(tb);
+    wave_candidates(rr, [=, &have, &ties](int q, bool live) {
+      double d = 0.0;
+      bool below = false, tie = false;
+      if (live) {
+        d = co.d2(q, x, y, z);
+        below = d < r2 && d < tau;
+        tie = d < r2 && d == tau;
       }
-  // pad to a power of two and sort by (d2, index)
-  int np2 = 1;
-  while (np2 < have) np2 <<= 1;
-  for (int t = have + lane; t < np2; t += 64) {
-    sd[t] = __builtin_inf();
-    si[t] = 0x7FFFFFFF;
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  for (int k2 = 2; k2 <= np2; k2 <<= 1)
-    for (int j = k2 >> 1; j > 0; j >>= 1) {
-      for (int t = lane; t < np2; t += 64) {
-        const int u = t ^ j;
-        if (u > t) {
-          const double da = sd[t], db = sd[u];
-          const int ia = si[t], ib = si[u];
-          const bool a_gt_b = da > db || (da == db && ia > ib);
-          const bool up = (t & k2) == 0;
-          if (a_gt_b == up) {
-            sd[t] = db;
-            si[t] = ib;
-            sd[u] = da;
-            si[u] = ia;
-          }
-        }
+      const int tie_rank = wave_append(tie, ties);
+      const bool take = below || (tie && tie_rank < budget);
+      const int slot = wave_append(take, have);
+      if (take) {
+        sd[slot] = d;
+        si[slot] = order[q];
       }
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-    }
+    });
+  wave_sort_pairs(sd, si, have);
   return have;
 }
 
@@ -220,9 +176,7 @@ __global__ __launch_bounds__(128) void k_radius_reduce(int m, const double* __re
       const int nb = e / F;
       stage[e] = values[size_t(si[w][t0 + nb]) * F + (e - nb * F)];
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
     if (lane < F) {
       if (reducer == 0) {
         for (int q = 0; q < cnt; ++q) acc = acc + stage[q * F + lane];
@@ -234,9 +188,7 @@ __global__ __launch_bounds__(128) void k_radius_reduce(int m, const double* __re
         }
       }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
   }
   if (lane < F) o[lane] = reducer == 0 ? acc / double(have) : (nan ? __builtin_nan("") : acc);
 }

@@ -25,12 +25,10 @@
 
 #include "boruvka.hpp"
 #include "common.hpp"
+#include "knn.hpp"
 
 namespace pyqsm {
 
-int knn_device(Ctx* c, const double* xyz, int64_t n, int32_t k, int32_t exclude_self, int32_t* idx,
-               double* d2);                   // knn.hip
-static constexpr int kTopoMaxK = 192;          // knn.hip kMaxK
 static constexpr int kSurfLevels = 100, kSurfAngles = 20, kSurfPts = kSurfLevels * kSurfAngles;
 static constexpr int kSurfSlots = 2048;        // keys sorted per cylinder (16 KB of LDS)
 
@@ -725,7 +723,7 @@ static int check_nodes(int64_t m) {
 }
 
 static int check_forest_k(int32_t k) {
-  if (k < 1 || k > kTopoMaxK) return fail(PYQSM_ERANGE, "k must be in [1, %d]", kTopoMaxK);
+  if (k < 1 || k > kKnnMaxK) return fail(PYQSM_ERANGE, "k must be in [1, %d]", kKnnMaxK);
   return 0;
 }
 

@@ -136,12 +136,18 @@ def knn(P, Q, k, tree=None):
     Q = np.asarray(Q, dtype=np.float64)
     tree = cKDTree(P) if tree is None else tree
     kk = min(len(P), k + 16)
-    _, idx = tree.query(Q, k=kk, workers=16)
-    idx = idx.reshape(len(Q), kk)
-    d = P[idx] - Q[:, None, :]
-    d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
-    order = np.lexsort((idx, d2), axis=1)
-    return np.take_along_axis(idx, order, 1)[:, :k]
+    while True:
+        _, idx = tree.query(Q, k=kk, workers=16)
+        idx = idx.reshape(len(Q), kk)
+        d = P[idx] - Q[:, None, :]
+        d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+        order = np.lexsort((idx, d2), axis=1)
+        d2 = np.take_along_axis(d2, order, 1)
+        # cKDTree cuts a tie group at kk wherever it likes: take more until the ties at the k-th
+        # place all lie inside the table (a lattice ties in groups of more than 16)
+        if kk == len(P) or (d2[:, k - 1] < d2[:, kk - 1]).all():
+            return np.take_along_axis(idx, order, 1)[:, :k]
+        kk = min(len(P), 2 * kk)
 
 
 def smooth(values, idx, reducer):

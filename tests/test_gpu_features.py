@@ -8,6 +8,7 @@ import pytest
 from pyqsm_amd import exploration, hip, synth
 from pyqsm_amd.utils import algo
 from tests import features_restatement as R
+from tests import wave_select_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -92,6 +93,27 @@ def test_lattice_inclusive_and_cap(gpu):
     want2, wcnt2, lam2 = R.compute_features(P, 2.0, max_k=20)
     assert np.array_equal(cnt2, wcnt2)
     _check(got2, want2, lam2)
+
+
+@pytest.mark.parametrize("jitter", [False, True])
+@pytest.mark.parametrize("mk", [4, 64, 100000])
+def test_clumps_on_both_sides_of_the_cap_and_the_staging_flush(gpu, jitter, mk):
+    """Balls of exactly 1 ... 700 points (tests/wave_select_cases.py): at max_k = 64 the clumps of 63 / 64 /
+    65 straddle the cap, those of 127 / 128 / 129 the 64-entry flush of the moment staging."""
+    P, size = wave_select_cases.clumps(jitter=jitter)
+    got, cnt = hip.geometric_features(P, 0.1, max_k=mk, return_counts=True, device=gpu)
+    want, wcnt, lam = R.compute_features(P, 0.1, max_k=mk)
+    assert np.array_equal(wcnt, size) and np.array_equal(cnt, wcnt)
+    _check(got, want, lam)
+
+
+def test_lattice_ties_at_the_cap_are_cut_by_index(gpu):
+    P = wave_select_cases.lattice_clump(513)
+    assert wave_select_cases.tie_at(P, P, 100).any()   # the 100th and 101st distances of some point are equal
+    got, cnt = hip.geometric_features(P, 2.0, max_k=100, return_counts=True, device=gpu)
+    want, wcnt, lam = R.compute_features(P, 2.0, max_k=100)
+    assert (wcnt == 513).all() and np.array_equal(cnt, wcnt)
+    _check(got, want, lam)
 
 
 def test_fp64_negative_coordinates(gpu):
@@ -196,6 +218,21 @@ def test_smooth_separate_queries_with_far_outliers(gpu, cloud):
         assert np.all(np.abs(mean - want) <= 1e-12 * np.abs(want) + 1e-300)
     sep = exploration.smooth_feature(cloud, V[:, 0], query_pts=cloud[:5000], n_nbrs=25, smoothing_func=np.max)
     assert np.array_equal(sep, hip.smooth_values(cloud, V[:, 0], 25, "max", device=gpu)[:5000])
+
+
+@pytest.mark.parametrize("m", [511, 512, 513, 700])
+def test_smooth_far_queries_see_the_whole_cloud_on_both_sides_of_the_cap(gpu, m):
+    """A query 50 m away is first served at a radius that holds all m sources: k_query_knn sorts 511 or 512
+    pairs as they are and bisects (distance, then index among the ties of a lattice) for 513 and 700."""
+    src = wave_select_cases.random_cube(m) if m == 700 else wave_select_cases.lattice_clump(m)
+    Q = wave_select_cases.far_queries(src)
+    V = np.random.default_rng(m).normal(size=len(src))
+    for k in wave_select_cases.SMOOTH_KS:
+        assert all(wave_select_cases.first_sufficient_radius(src, q, k)[1] == m for q in Q[:6])
+        if m == 513:
+            assert wave_select_cases.tie_at(src, Q[:6], k).any()
+        _, idx = hip.smooth_values(src, V, k, "mean", queries=Q, return_indices=True, device=gpu)
+        assert np.array_equal(idx, R.knn(src, Q, k))
 
 
 def test_end_to_end_reference_defaults(gpu):

@@ -8,6 +8,7 @@ from pyqsm_amd import _lib, hip, qsm_generation, synth
 from pyqsm_amd.geometry.cloud import KDTreeSearchParamHybrid, KDTreeSearchParamKNN, PointCloud
 from tests import deep_chain
 from tests import normals_restatement as R
+from tests import wave_select_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -75,6 +76,28 @@ def test_max_nn_out_of_range_raises(gpu):
     with pytest.raises(ValueError):
         hip.estimate_normals(P, None, 193, device=gpu)
     hip.estimate_normals(P, 0.1, 256, device=gpu)
+
+
+@pytest.mark.parametrize("jitter", [False, True])
+def test_normals_clumps_on_both_sides_of_the_step_the_padding_and_the_cap(gpu, jitter):
+    """Balls of exactly 1 ... 700 points (tests/wave_select_cases.py): 63 / 64 / 65 candidates around the
+    64-candidate step, 127 / 128 / 129 around a power of two of the sort, 511 / 512 without and 513 / 700
+    with the bisection for the max_nn-th distance."""
+    P, _ = wave_select_cases.clumps(jitter=jitter)
+    for radius, nn in ((0.1, 5), (0.1, 30), (0.1, 256)):
+        _same(hip.estimate_normals(P, radius, nn, device=gpu), R.estimate_normals(P, radius, nn))
+
+
+def test_normals_overflow_of_ties_at_the_max_nn_th_distance(gpu):
+    """601 points in the origin's ball, more than a wave sorts: with 600 of them tied at the 30th
+    distance the call fails with PYQSM_ERANGE; with 400 tied there (and 200 farther) the ties fit
+    and the result is the contract's."""
+    lib = _lib.load()
+    P = np.ascontiguousarray(wave_select_cases.stacked(600))
+    out = np.empty((len(P), 3))
+    assert lib.pyqsm_estimate_normals(hip._p(P), len(P), 0.1, 30, None, hip._p(out), gpu) == -4  # PYQSM_ERANGE
+    P = wave_select_cases.stacked(400, 200)
+    _same(hip.estimate_normals(P, 0.1, 30, device=gpu), R.estimate_normals(P, 0.1, 30))
 
 
 def test_georeferenced_cloud(gpu, forest):

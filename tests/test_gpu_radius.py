@@ -7,6 +7,7 @@ from scipy.spatial import cKDTree
 from pyqsm_amd import hip, synth
 from pyqsm_amd.geometry.reconstruction import get_neighbors_kdtree
 from pyqsm_amd.utils.lib_integration import find_neighbors_in_ball, get_neighbors_in_tree
+from tests import wave_select_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -91,6 +92,22 @@ def test_radius_knn_tables_match_ckdtree(gpu, k, radius):
     assert (np.isinf(d[:, 0])).sum() > 100             # some queries find nothing
     if k <= 40:
         assert full > 100                              # the k cap is exercised
+
+
+@pytest.mark.parametrize("jitter", [False, True])
+@pytest.mark.parametrize("k", [64, 512])
+def test_radius_knn_clumps_on_both_sides_of_k_the_step_and_the_padding(gpu, jitter, k):
+    """Queries with exactly 1 ... 700 sources in range (tests/wave_select_cases.py): k - 1, k and k + 1 of
+    them at k = 64 and 512, where the bisection for the k-th distance starts; one query finds nothing."""
+    src, size = wave_select_cases.clumps(jitter=jitter)
+    qry = wave_select_cases.clump_queries(src)
+    d0, i0 = cKDTree(src).query(qry, k=k, distance_upper_bound=wave_select_cases.RADIUS)
+    d, i = hip.radius_knn(src, qry, wave_select_cases.RADIUS, k=k, device=gpu)
+    assert np.array_equal(np.isfinite(d0).sum(axis=1), np.r_[np.minimum(size, k), 0])
+    assert np.array_equal(d, d0)                       # includes the inf padding
+    assert np.array_equal(np.isinf(d), i == len(src))
+    for r in np.flatnonzero(~(i == i0).all(1)):        # ties in distance: compare per distinct distance
+        assert sorted(zip(d[r], i[r])) == sorted(zip(d0[r], i0[r]))
 
 
 def test_stray_source_points_far_outside_keep_radius_queries_exact(gpu):

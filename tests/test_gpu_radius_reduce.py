@@ -6,6 +6,7 @@ import pytest
 from pyqsm_amd import hip
 from pyqsm_amd.geometry.cloud import PointCloud
 from tests import voxelgrid_restatement as R
+from tests import wave_select_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -41,6 +42,24 @@ def test_reductions_equal_restatement_bit_for_bit(gpu, radius, k, F):
     vals = _values(F)
     for reducer in REDUCERS:
         out, got_cnt = hip.radius_reduce(comp, tree, vals, radius, k=k, reducer=reducer, empty_row=0,
+                                         return_counts=True)
+        assert np.array_equal(got_cnt, cnt), reducer
+        assert _same_bits(out, R.reduce_values(idx, cnt, vals, reducer, 0)), reducer
+
+
+@pytest.mark.parametrize("jitter", [False, True])
+@pytest.mark.parametrize("k", [64, 512])
+def test_clumps_on_both_sides_of_k_the_step_and_the_padding(gpu, jitter, k):
+    """Queries with exactly 1 ... 700 sources in range (tests/wave_select_cases.py): k - 1, k and k + 1 of
+    them at k = 64 and 512; one query finds nothing. No row has a tie at the k-th place
+    (tests/test_wave_select_host.py), so the restatement's (d2, index) order settles every row."""
+    src, size = wave_select_cases.clumps(jitter=jitter)
+    qry = wave_select_cases.clump_queries(src)
+    idx, cnt, _ = R.neighbours(src, qry, wave_select_cases.RADIUS, k)
+    assert np.array_equal(cnt, np.r_[np.minimum(size, k), 0])
+    vals = np.random.default_rng(k).normal(0.0, 3.0, (len(src), 3))
+    for reducer in ("mean", "first"):
+        out, got_cnt = hip.radius_reduce(src, qry, vals, wave_select_cases.RADIUS, k=k, reducer=reducer, empty_row=0,
                                          return_counts=True)
         assert np.array_equal(got_cnt, cnt), reducer
         assert _same_bits(out, R.reduce_values(idx, cnt, vals, reducer, 0)), reducer

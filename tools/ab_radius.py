@@ -1,5 +1,5 @@
 """A/B of the radius queries (fp32 records vs fp64 arrays for the sorted source points)."""
-import os, sys, time
+import hashlib, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pyqsm_amd import hip, synth, _lib
@@ -26,5 +26,6 @@ for rnd in range(2):
             kern = hip.prof_get(what)[0]
             hip.prof_enable(False)
             same = all(np.array_equal(a, b) for a, b in zip(got, ref.setdefault(what, got)))
-            out[what] = f"{dt*1e3:.2f} ms wall, kernel {kern:.3f} ms, same: {same}"
+            sha = hashlib.sha256(b"".join(np.ascontiguousarray(a).tobytes() for a in got)).hexdigest()[:24]
+            out[what] = f"{dt*1e3:.2f} ms wall, kernel {kern:.3f} ms, same: {same}, sha256 {sha}"
         print(f"{name:13s} {out}", flush=True)

@@ -22,6 +22,7 @@ hip.radius_knn's padded [m, 500] tables brought to the host in chunks and reduce
     python tools/detail_perf.py --cpu [--tiles n ...] [--voxels v ...]
 """
 import argparse
+import hashlib
 import json
 import os
 import sys
@@ -152,6 +153,7 @@ def transfer_gpu(m, F, radius=0.05, k=500, chunk=100_000):
                 table_bytes_per_query=k * 16, fused_bytes_per_query=24 + 8 * F,
                 table_over_fused_wall=round(table_ms / float(np.median(walls)), 2),
                 max_abs_difference=float(np.abs(fused - tab).max()), difference_bound=float(scale),
+                sha256=hashlib.sha256(fused.tobytes() + cnt.tobytes()).hexdigest()[:24],
                 note="table route: hip.radius_knn in chunks of %d queries + NumPy mean over the real entries" % chunk)
 
 

@@ -8,6 +8,7 @@ reference's sklearn NearestNeighbors call for the smoothing. One JSON line per c
                                                   (default: 1000000 5000000; 0.1 0.3 0.6; 25 50 100)
 """
 import argparse
+import hashlib
 import json
 import os
 import sys
@@ -24,6 +25,14 @@ PEAK_FP64 = 78.6e12
 FOUR = ["planarity", "linearity", "verticality", "surface_variation"]
 F_PHASES = ("features_grid", "features_moments", "features_finish")
 S_PHASES = ("smooth_knn", "smooth_reduce")
+
+
+def _digest(*arrays):
+    """SHA-256 over the arrays' bytes (the first 24 hex digits): equal digests, equal bits."""
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()[:24]
 
 
 def _runs(fn, phases):
@@ -68,7 +77,7 @@ def features_case(P, radius, names, cpu):
     mom = rep["phase_ms"]["features_moments"]["min"] * 1e-3
     rep.update(n=len(P), radius=radius, features=len(names), in_ball_pairs=int(cnt.astype(np.int64).sum()),
                pair_tests=int(tests), fp64_peak_share=round(tests * 8 / mom / PEAK_FP64, 4) if mom > 0 else None,
-               nan_rows=int(np.isnan(out[:, 0]).sum()))
+               nan_rows=int(np.isnan(out[:, 0]).sum()), sha256=_digest(out, cnt))
     if cpu:
         q = np.random.default_rng(0).choice(len(P), 2000, replace=False)
         t = time.perf_counter()
@@ -80,8 +89,8 @@ def features_case(P, radius, names, cpu):
 
 def smooth_case(P, k, cpu):
     V = np.random.default_rng(1).normal(size=len(P))
-    _, rep = _runs(lambda: hip.smooth_values(P, V, k, "mean"), S_PHASES)
-    rep.update(n=len(P), k=k)
+    out, rep = _runs(lambda: hip.smooth_values(P, V, k, "mean"), S_PHASES)
+    rep.update(n=len(P), k=k, sha256=_digest(out))
     if cpu and len(P) <= 1_000_000:
         from sklearn.neighbors import NearestNeighbors
         t = time.perf_counter()

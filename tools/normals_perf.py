@@ -10,6 +10,7 @@ restatement's Kruskal is a Python loop).
                                                          (default: 1000000 5000000; 1000000; 200000)
 """
 import argparse
+import hashlib
 import json
 import os
 import sys
@@ -25,6 +26,14 @@ RADIUS, NN, K, CUTOFF, REPS = 0.1, 30, 100, 10.0, 5
 N_PHASES = ("normals_grid", "normals_cov", "normals_eig")
 O_PHASES = ("orient_knn", "orient_min_edge", "orient_hook", "orient_jump", "orient_sign")
 S_PHASES = ("stem_crop",) + N_PHASES + O_PHASES + ("stem_filter",)
+
+
+def _digest(*arrays):
+    """SHA-256 over the arrays' bytes (the first 24 hex digits): equal digests, equal bits."""
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()[:24]
 
 
 def _runs(fn, phases):
@@ -81,7 +90,8 @@ def measure(n, check_normals, check_orient, mst_max):
     O, ori = _runs(lambda: hip.orient_normals_tangent_plane(P, N, K), O_PHASES)
     S, stem = _runs(lambda: hip.stem_cloud(P, RADIUS, NN, K, CUTOFF), S_PHASES)
     res = {"n": n, "estimate_normals": nrm, "orient_k100": dict(ori, boruvka_rounds=rounds),
-           "stem_cloud": dict(stem, kept=len(S[0])), "cpu_normals_ms": round(cpu_normals(P), 1)}
+           "stem_cloud": dict(stem, kept=len(S[0])),
+           "sha256": {"normals": _digest(N), "oriented": _digest(O), "stem": _digest(*S)}, "cpu_normals_ms": round(cpu_normals(P), 1)}
     if n <= mst_max:
         res["cpu_scipy_mst_k100_ms"] = round(cpu_mst(P, N), 1)
     if n <= check_normals:
