@@ -266,6 +266,58 @@ int pyqsm_ransac_batch(const double* pts, int64_t n, const int64_t* seg_start, i
                        double* centers, double* axes, double* radii, int64_t* inliers,
                        int64_t* n_inliers, int64_t* best, int32_t device);
 
+/* ---- plane segmentation -------------------------------------------------- */
+/*
+ * Stands in for Open3D's PointCloud.segment_plane, which the reference calls at
+ * pyQSM/geometry/point_cloud_processing.py:182-183 (recollected from Open3D, parity
+ * unpinned; tests/plane_restatement.py states this contract).
+ * A plane is (a, b, c, d) with a unit normal whose sign makes c > 0, or c == 0 and
+ * b > 0, or c == b == 0 and a > 0. A hypothesis comes from m sampled points, 3 <= m <= 32:
+ * the plane through them for m == 3, their least-squares plane otherwise. A sample
+ * outside [0, n), a degenerate or non-finite construction, or, with cos_limit > 0,
+ * |normal . axis| < cos_limit make the hypothesis invalid: a row of zeros that counts 0.
+ * A point is an inlier iff |((a x + b y) + c z) + d| < thresh, strictly.
+ *   pts f64 [n,3]; samples i64 [H,m]; axis f64 [3] (unit) or NULL; planes f64 [H,4];
+ *   counts i32 [H].
+ * PYQSM_EINVAL, before any device is touched: m outside 3 ... 32, a threshold that is
+ * not finite and > 0, a probability outside (0, 1], non-finite coordinates, H < 0,
+ * P < 1, and n < m in the two segment calls. H == 0 is valid and finds nothing.
+ */
+int pyqsm_plane_models(const double* pts, int64_t n, const int64_t* samples, int64_t H, int32_t m,
+                       const double* axis, double cos_limit, double* planes, int32_t device);
+int pyqsm_plane_count(const double* pts, int64_t n, const double* planes, int64_t H, double thresh,
+                      int32_t* counts, int32_t device);
+/*
+ * One plane. The rows are looked at in order; the first row with the largest count so far
+ * wins (ties keep the lower row), and after every new winner with inlier fraction f the
+ * rows beyond min(log(1 - probability) / log(1 - f^m), H) are not looked at (Open3D's
+ * adaptive bound; none with probability == 1, or where f^m vanishes next to 1). *used = the
+ * rows looked at, *best = the winning row (-1: no row has an inlier; then zeros and no inliers).
+ *   plane_hyp: the winning hypothesis. plane_fit: the least-squares plane through its
+ *   inliers from exact fixed-point moments, the same bits whatever the order of the
+ *   points (plane_hyp with fewer than 3 inliers or a non-finite refit).
+ *   inliers i64 [n] capacity, ascending; *n_inliers = their number.
+ */
+int pyqsm_segment_plane(const double* pts, int64_t n, const int64_t* samples, int64_t H, int32_t m,
+                        double thresh, double probability, const double* axis, double cos_limit,
+                        double plane_fit[4], double plane_hyp[4], int64_t* inliers, int64_t* n_inliers,
+                        int64_t* best, int64_t* used, int32_t device);
+/*
+ * Up to P planes peeled off a cloud that stays on the device. Round r works on the points
+ * not labelled yet, in ascending index order; sample j of hypothesis h is the alive point
+ * number mulhi64(draws[r,h,j], n_alive) (the high 64 bits of the product), so the caller
+ * need not know which points are left. A round is pyqsm_segment_plane on the alive points;
+ * its inliers get label r. The call stops before a round with n_alive < m, at a round whose
+ * winner has fewer than min_inliers inliers (it labels nothing), or after P rounds.
+ *   draws u64 [P,H,m]; labels i32 [n] (-1: no plane); planes_fit / planes_hyp f64 [P,4],
+ *   counts / best / used i64 [P] (zeros, 0, -1, 0 from row *n_planes on).
+ */
+int pyqsm_segment_planes(const double* pts, int64_t n, const uint64_t* draws, int64_t P, int64_t H,
+                         int32_t m, double thresh, double probability, int64_t min_inliers,
+                         const double* axis, double cos_limit, int32_t* labels, double* planes_fit,
+                         double* planes_hyp, int64_t* counts, int64_t* best, int64_t* used,
+                         int64_t* n_planes, int32_t device);
+
 /* ---- Laplacian-contraction solve --------------------------------------- */
 /*
  * One contraction solve of pyQSM/geometry/skeletonize.py:148-180

@@ -31,6 +31,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "fixed128.hpp"
 #include "grid.hpp"
 #include "knn.hpp"
 #include "pca.hpp"
@@ -44,58 +45,7 @@ static constexpr int kFeatMaxCols = 32;    // columns one call may ask for
 static constexpr int kFeatWaves = 4;       // waves per block of k_feat_moments
 static constexpr int kQueryCap = 512;      // (d2, index) pairs k_query_knn sorts without bisection
 
-// ---- fixed-point moments -------------------------------------------------------------------------
-// A signed 128-bit integer as (low word, high word).
-struct I128 {
-  unsigned long long lo;
-  long long hi;
-};
-
-// a += x, x an integral double with |x| <= 2^62
-__device__ __forceinline__ void acc128(I128& a, double x) {
-  const long long v = (long long)x;
-  const unsigned long long lo = a.lo + (unsigned long long)v;
-  a.hi += (v < 0 ? -1LL : 0LL) + (lo < a.lo ? 1LL : 0LL);
-  a.lo = lo;
-}
-
-// a += the value lane ^ off holds
-__device__ __forceinline__ void fold128(I128& a, int off) {
-  const unsigned long long blo = __shfl_xor(a.lo, off, 64);
-  const long long bhi = __shfl_xor(a.hi, off, 64);
-  const unsigned long long lo = a.lo + blo;
-  a.hi = a.hi + bhi + (lo < a.lo ? 1LL : 0LL);
-  a.lo = lo;
-}
-
-// the magnitude as hi * 2^64 + lo, the sign applied after: small negative sums stay exact
-__device__ __forceinline__ double to_double(I128 a) {
-  const bool neg = a.hi < 0;
-  if (neg) {
-    a.lo = ~a.lo + 1ull;
-    a.hi = ~a.hi + (a.lo == 0ull ? 1LL : 0LL);
-  }
-  const double v = double((unsigned long long)a.hi) * 18446744073709551616.0 + double(a.lo);
-  return neg ? -v : v;
-}
-
-// Powers of two per axis: s1[a] maps the largest offset along a to at most 2^61, s2 the products
-// of the pairs (00, 01, 02, 11, 12, 22); u1, u2 their inverses.
-struct FeatScale {
-  double s1[3], s2[6], u1[3], u2[6];
-};
-
-__device__ __forceinline__ void add_moments(I128* M, const FeatScale& sc, double ox, double oy, double oz) {
-  acc128(M[0], rint(ox * sc.s1[0]));
-  acc128(M[1], rint(oy * sc.s1[1]));
-  acc128(M[2], rint(oz * sc.s1[2]));
-  acc128(M[3], rint((ox * ox) * sc.s2[0]));
-  acc128(M[4], rint((ox * oy) * sc.s2[1]));
-  acc128(M[5], rint((ox * oz) * sc.s2[2]));
-  acc128(M[6], rint((oy * oy) * sc.s2[3]));
-  acc128(M[7], rint((oy * oz) * sc.s2[4]));
-  acc128(M[8], rint((oz * oz) * sc.s2[5]));
-}
+// ---- fixed-point moments: fixed128.hpp (I128, acc128, fold128, to_double, FeatScale, add_moments) ----
 
 // The distance the ball is tested with: d2 = ((dx*dx) + dy*dy) + dz*dz, or (|dx| + |dy|) + |dz|.
 template <class CO, bool L1>
@@ -374,26 +324,6 @@ static int check_count(int64_t n) {
   if (n < 0) return fail(PYQSM_EINVAL, "negative size");
   if (n > 0x7FFFFF00LL) return fail(PYQSM_ERANGE, "more than 2^31 points per call");
   return 0;
-}
-
-// The scales for offsets bounded by bound[a] along each axis (zero extents: any scale).
-static FeatScale feat_scale(const double bound[3]) {
-  FeatScale sc;
-  int sh[3];
-  for (int a = 0; a < 3; ++a) {
-    const double b = std::max(bound[a], std::ldexp(1.0, -400));
-    int e = 0;
-    std::frexp(b, &e);  // b < 2^e
-    sh[a] = 61 - e;
-    sc.s1[a] = std::ldexp(1.0, sh[a]);
-    sc.u1[a] = std::ldexp(1.0, -sh[a]);
-  }
-  const int A[6] = {0, 0, 0, 1, 1, 2}, B[6] = {0, 1, 2, 1, 2, 2};
-  for (int e = 0; e < 6; ++e) {
-    sc.s2[e] = std::ldexp(1.0, sh[A[e]] + sh[B[e]] - 61);
-    sc.u2[e] = std::ldexp(1.0, 61 - sh[A[e]] - sh[B[e]]);
-  }
-  return sc;
 }
 
 // The k nearest of the m queries d_qry among the n points d_src into d_idx [m, k] (k <= n).

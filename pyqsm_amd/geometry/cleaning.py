@@ -73,3 +73,19 @@ def clean_cloud(pcd,
     out = hip.clean_cloud(pts, float(voxels) if run_voxels else 0.0, neighbors, ratio, int(iters),
                           device=device)
     return PointCloud(out)
+
+
+def split_ground(pcd, distance_threshold=0.1, max_slope_deg=30, ransac_n=3, num_iterations=1000,
+                 probability=0.99999999, seed=None, draws=None, device: int = 0):
+    """The ground as one plane: ``(ground, rest, plane)``, the sub-clouds of the points within
+    ``distance_threshold`` of the best plane whose normal lies within ``max_slope_deg`` of +z, of all
+    the others, and the refitted plane ``(a, b, c, d)`` with c > 0 (``PointCloud.segment_planes`` with
+    one plane and the cone about +z). On sloping ground this takes a slab where a cut by z
+    percentiles takes a wedge. No plane inside the cone: an empty ground and a zero plane."""
+    pts = as_points(pcd)
+    cloud = pcd if isinstance(pcd, PointCloud) else PointCloud(pts)
+    seg = cloud.segment_planes(distance_threshold, max_planes=1, min_inliers=1, ransac_n=ransac_n,
+                               num_iterations=num_iterations, probability=probability, axis=(0.0, 0.0, 1.0),
+                               max_angle_deg=max_slope_deg, seed=seed, draws=draws, device=device)
+    plane = seg.planes[0] if len(seg) else np.zeros(4)
+    return cloud.select_by_index(seg.indices(0)), cloud.select_by_index(seg.rest()), plane

@@ -174,6 +174,62 @@ class PointCloud:
     def get_max_bound(self):
         return self.points.max(axis=0)
 
+    def segment_plane(self, distance_threshold=0.01, ransac_n=3, num_iterations=100, probability=0.99999999,
+                      seed=None, samples=None, device: int = 0):
+        """Open3D's ``segment_plane`` on the GPU (``hip.segment_plane``): returns ``(plane_model [4],
+        inliers)``, the least-squares plane ``(a, b, c, d)`` through the inliers of the best of
+        ``num_iterations`` hypotheses of ``ransac_n`` points each, and the inliers as an int64 array
+        in ascending order (``select_by_index`` takes it). Recollected from Open3D, parity unpinned
+        (DESIGN.md §20): the normal's sign makes c > 0, hypotheses with equal counts keep the earlier
+        one (Open3D compares an error sum whose value depends on the summation order), and the
+        hypotheses are drawn from ``seed`` (``math_utils.fit.draw_plane_samples``) or given as
+        ``samples`` int64 [num_iterations, ransac_n]. No hypothesis with an inlier: a zero plane and
+        no inliers."""
+        if samples is None:
+            samples = _fit().draw_plane_samples(len(self.points), int(num_iterations), int(ransac_n), seed=seed)
+        fit, _, inliers, _, _ = _hip().segment_plane(self.points, samples, distance_threshold, probability,
+                                                     device=device)
+        return fit, inliers
+
+    def segment_planes(self, distance_threshold, max_planes=4, min_inliers=100, ransac_n=3, num_iterations=1000,
+                       probability=0.99999999, axis=None, max_angle_deg=None, seed=None, draws=None,
+                       device: int = 0):
+        """Up to ``max_planes`` planes peeled off the cloud in one device-resident call
+        (``hip.segment_planes``): every round is ``segment_plane`` on the points no earlier plane
+        took, until a round's best plane has fewer than ``min_inliers`` inliers. With ``axis`` and
+        ``max_angle_deg`` only planes whose normal lies within that angle of ``axis`` (either sign)
+        are considered. Returns a ``hip.PlaneSegments``: ``.planes``, ``.hypothesis_planes``,
+        ``.labels``, ``.counts``, ``.indices(i)``, ``.rest()``. ``draws``: uint64 [max_planes,
+        num_iterations, ransac_n] (``math_utils.fit.draw_u64``), drawn from ``seed`` when omitted."""
+        if draws is None:
+            draws = _fit().draw_u64((int(max_planes), int(num_iterations), int(ransac_n)), seed=seed)
+        axis, cos_limit = cone_args(axis, max_angle_deg)
+        return _hip().segment_planes(self.points, draws, distance_threshold, probability, min_inliers, axis=axis,
+                                     cos_limit=cos_limit, device=device)
+
+
+def _fit():
+    """``math_utils.fit``, imported on first use (it imports this module)."""
+    try:
+        from ..math_utils import fit
+    except ImportError:  # flat import (pyqsm_amd/ on sys.path)
+        _hip()
+        from pyqsm_amd.math_utils import fit
+    return fit
+
+
+def cone_args(axis, max_angle_deg):
+    """``(unit axis or None, cos_limit)`` as the plane kernels take them: ``cos_limit =
+    cos(radians(max_angle_deg))``, 0 (no cone) without an axis or an angle."""
+    import math
+    if axis is None or max_angle_deg is None:
+        return None, 0.0
+    ax = np.asarray(axis, dtype=np.float64).reshape(3)
+    ln = float(np.sqrt((ax * ax).sum()))
+    if not ln > 0 or not np.isfinite(ln):
+        raise ValueError("the cone's axis must be a finite non-zero vector")
+    return ax / ln, math.cos(math.radians(float(max_angle_deg)))
+
 
 class Voxel:
     """Open3D's ``Voxel``: ``grid_index`` int32 [3] and ``color`` f64 [3]."""

@@ -35,6 +35,10 @@ def _select(pcd, pts, idx):
     return PointCloud(pts[idx])
 
 
+# what cluster_plus(ransac=True) seeds its plane hypotheses with (its signature is the reference's)
+PLANE_SEED = None
+
+
 def cluster_plus(pcd, eps=config["trunk"]["cluster_eps"], min_points=config["trunk"]["cluster_nn"],
                  draw_result=True, color_clusters=True, from_points=True, return_pcds=True,
                  ransac=False, device: int = 0, radius_inclusive: bool = True):
@@ -42,15 +46,23 @@ def cluster_plus(pcd, eps=config["trunk"]["cluster_eps"], min_points=config["tru
     ``pcd`` is an array of points. Returns the list of sub-clouds, one per label in
     ascending label order (noise -1 first when present), or ``{label: indices}``
     when ``return_pcds`` is false. ``draw_result`` / ``color_clusters`` are accepted
-    and ignored (no GUI); ``ransac=True`` (Open3D plane segmentation) is out of scope.
+    and ignored (no GUI). ``ransac=True`` labels by plane segmentation instead of DBSCAN, as the
+    reference's ``pcd.segment_plane(distance_threshold=eps, ransac_n=10, num_iterations=1000)`` means
+    to (its branch ends in a NameError on ``labels``): label 0 for the inliers of the plane
+    (``PointCloud.segment_plane``), -1 for the rest. The hypotheses are drawn from the module's
+    ``PLANE_SEED``: None, the reference's unseeded behaviour, or an int for reproducible runs.
     ``radius_inclusive=False`` switches the neighbourhood to d < eps — Open3D's compare if
     nanoflann's radius search is strict (unverifiable here: parity unpinned, default inclusive)."""
-    if ransac:
-        raise NotImplementedError("plane segmentation (ransac=True) is not part of the HIP hot path")
     pts = as_points(pcd)
     if from_points:
         pcd = PointCloud(pts)
-    labels, _ = hip.dbscan(pts, eps, min_points, device=device, radius_inclusive=radius_inclusive)
+    if ransac:
+        _, inliers = PointCloud(pts).segment_plane(distance_threshold=eps, ransac_n=10, num_iterations=1000,
+                                                   seed=PLANE_SEED, device=device)
+        labels = np.full(len(pts), -1, dtype=np.int32)
+        labels[inliers] = 0
+    else:
+        labels, _ = hip.dbscan(pts, eps, min_points, device=device, radius_inclusive=radius_inclusive)
     unique_lbs, counts = np.unique(labels, return_counts=True)
     log.info(f"point cloud has {counts} clusters")
     label_to_cluster = {ulabel: np.where(labels == ulabel)[0] for ulabel in unique_lbs}

@@ -329,6 +329,115 @@ def ransac_count(points, models, shape: str = "circle", thresh: float = 0.2, dev
     return counts
 
 
+# ---------------------------------------------------------------- plane segmentation
+
+def _plane_samples(samples) -> np.ndarray:
+    smp = np.ascontiguousarray(np.asarray(samples), dtype=np.int64)
+    if smp.ndim != 2:
+        raise ValueError(f"expected samples of shape [H,m], got {smp.shape}")
+    return smp
+
+
+def _plane_axis(axis):
+    if axis is None:
+        return None
+    ax = np.ascontiguousarray(np.asarray(axis, dtype=np.float64).reshape(3))
+    return ax
+
+
+def plane_models(points, samples, axis=None, cos_limit: float = 0.0, device: int = 0):
+    """``pyqsm_plane_models``: the hypothesis planes f64 [H,4] = (a, b, c, d) of ``samples`` int64
+    [H,m]; invalid hypotheses are rows of zeros. ``axis`` (unit) and ``cos_limit`` > 0 restrict the
+    normals to a cone."""
+    pts = _points(points)
+    smp = _plane_samples(samples)
+    H, m = smp.shape
+    ax = _plane_axis(axis)
+    planes = np.zeros((H, 4))
+    check(_lib.load().pyqsm_plane_models(_p(pts), pts.shape[0], _p(smp), H, m, _p(ax), float(cos_limit),
+                                         _p(planes), int(device)))
+    return planes
+
+
+def plane_count(points, planes, thresh: float, device: int = 0):
+    """``pyqsm_plane_count``: int32 [H], the points strictly within ``thresh`` of every plane."""
+    pts = _points(points)
+    pl = np.ascontiguousarray(planes, dtype=np.float64).reshape(-1, 4)
+    counts = np.zeros(pl.shape[0], dtype=np.int32)
+    check(_lib.load().pyqsm_plane_count(_p(pts), pts.shape[0], _p(pl), pl.shape[0], float(thresh), _p(counts),
+                                        int(device)))
+    return counts
+
+
+def segment_plane(points, samples, thresh: float, probability: float = 0.99999999, axis=None,
+                  cos_limit: float = 0.0, device: int = 0):
+    """``pyqsm_segment_plane``: ``(plane_fit [4], plane_hyp [4], inliers int64 ascending, best, used)``."""
+    pts = _points(points)
+    smp = _plane_samples(samples)
+    H, m = smp.shape
+    ax = _plane_axis(axis)
+    fit, hyp = np.zeros(4), np.zeros(4)
+    inl = np.empty(max(pts.shape[0], 1), dtype=np.int64)
+    n_in, best, used = i64(0), i64(-1), i64(0)
+    check(_lib.load().pyqsm_segment_plane(_p(pts), pts.shape[0], _p(smp), H, m, float(thresh), float(probability),
+                                          _p(ax), float(cos_limit), _p(fit), _p(hyp), _p(inl), ctypes.byref(n_in),
+                                          ctypes.byref(best), ctypes.byref(used), int(device)))
+    return fit, hyp, inl[:n_in.value].copy(), int(best.value), int(used.value)
+
+
+class PlaneSegments:
+    """What ``segment_planes`` found: ``planes`` f64 [k,4] (refitted), ``hypothesis_planes`` f64 [k,4],
+    ``labels`` int32 [n] (the plane of every point, -1: none), ``counts`` / ``best`` / ``used`` int64
+    [k]."""
+
+    def __init__(self, planes, hypothesis_planes, labels, counts, best, used):
+        self.planes = planes
+        self.hypothesis_planes = hypothesis_planes
+        self.labels = labels
+        self.counts = counts
+        self.best = best
+        self.used = used
+
+    def __len__(self):
+        return len(self.planes)
+
+    def indices(self, i: int) -> np.ndarray:
+        """The points of plane ``i``: int64, ascending."""
+        return np.flatnonzero(self.labels == int(i)).astype(np.int64)
+
+    def rest(self) -> np.ndarray:
+        """The points on no plane: int64, ascending."""
+        return np.flatnonzero(self.labels < 0).astype(np.int64)
+
+    def __repr__(self):
+        return f"PlaneSegments with {len(self.planes)} planes over {len(self.labels)} points."
+
+
+def segment_planes(points, draws, thresh: float, probability: float = 0.99999999, min_inliers: int = 1,
+                   axis=None, cos_limit: float = 0.0, device: int = 0) -> PlaneSegments:
+    """``pyqsm_segment_planes``: up to P planes peeled off the cloud on the device; ``draws`` uint64
+    [P,H,m] (sample j of hypothesis h in round r is alive point ``mulhi64(draws[r,h,j], n_alive)``)."""
+    pts = _points(points)
+    dr = np.ascontiguousarray(np.asarray(draws), dtype=np.uint64)
+    if dr.ndim != 3:
+        raise ValueError(f"expected draws of shape [P,H,m], got {dr.shape}")
+    P, H, m = dr.shape
+    ax = _plane_axis(axis)
+    n = pts.shape[0]
+    labels = np.full(max(n, 1), -1, dtype=np.int32)
+    fit, hyp = np.zeros((max(P, 1), 4)), np.zeros((max(P, 1), 4))
+    counts = np.zeros(max(P, 1), dtype=np.int64)
+    best = np.full(max(P, 1), -1, dtype=np.int64)
+    used = np.zeros(max(P, 1), dtype=np.int64)
+    k = i64(0)
+    check(_lib.load().pyqsm_segment_planes(_p(pts), n, _p(dr), P, H, m, float(thresh), float(probability),
+                                           int(min_inliers), _p(ax), float(cos_limit), _p(labels), _p(fit), _p(hyp),
+                                           _p(counts), _p(best), _p(used), ctypes.byref(k), int(device)))
+    k = int(k.value)
+    return PlaneSegments(fit[:k].copy(), hyp[:k].copy(), labels[:n], counts[:k].copy(), best[:k].copy(),
+                         used[:k].copy())
+
+
 # ---------------------------------------------------------------- contraction solve
 
 def _csr(L):

@@ -149,6 +149,47 @@ def draw_samples(n_points: int, iterations: int, seed=None, method: str = "numpy
     return np.stack([a, b, c], axis=1).astype(np.int64)
 
 
+def draw_plane_samples(n_points: int, iterations: int, m: int = 3, seed=None) -> np.ndarray:
+    """``iterations`` rows of ``m`` distinct indices below ``n_points`` (int64 [iterations, m]), each
+    row uniform over the ordered m-tuples: the hypotheses of ``PointCloud.segment_plane``. Seeded
+    like ``draw_samples``, which draws the rows itself when ``m == 3``."""
+    m = int(m)
+    if m < 3:
+        raise ValueError("a plane hypothesis needs at least three points")
+    if n_points < m:
+        raise ValueError(f"need at least {m} points to draw a hypothesis")
+    if m == 3:
+        return draw_samples(n_points, iterations, seed=seed)
+    rng = seed if isinstance(seed, np.random.Generator) else np.random.default_rng(seed)
+    out = np.empty((iterations, m), dtype=np.int64)
+    for j in range(m):
+        r = rng.integers(0, n_points - j, iterations)     # the r-th of the values not taken yet
+        taken = np.sort(out[:, :j], axis=1)
+        for t in range(j):
+            r += r >= taken[:, t]
+        out[:, j] = r
+    return out
+
+
+def draw_u64(shape, seed=None) -> np.ndarray:
+    """Uniform uint64 draws of the given shape: ``segment_planes`` turns draw ``u`` into the alive point
+    number ``mulhi64(u, n_alive)`` on the device. Seeded like ``draw_samples``."""
+    rng = seed if isinstance(seed, np.random.Generator) else np.random.default_rng(seed)
+    return rng.integers(0, np.iinfo(np.uint64).max, size=shape, dtype=np.uint64, endpoint=True)
+
+
+def mulhi64(u, n) -> np.ndarray:
+    """The high 64 bits of the 128-bit product ``u * n`` of unsigned 64-bit integers, elementwise:
+    for a uniform draw ``u`` an index below ``n`` (what the device's ``__umul64hi`` computes)."""
+    u = np.asarray(u, dtype=np.uint64)
+    n = np.asarray(n, dtype=np.uint64)
+    mask, s = np.uint64(0xFFFFFFFF), np.uint64(32)
+    u0, u1, n0, n1 = u & mask, u >> s, n & mask, n >> s
+    mid = u1 * n0 + ((u0 * n0) >> s)                      # < 2^64: (2^32-1)^2 + 2^32 - 1
+    mid2 = u0 * n1 + (mid & mask)
+    return u1 * n1 + (mid >> s) + (mid2 >> s)
+
+
 _NO_FIT = (None, None, None, None, None)
 
 
