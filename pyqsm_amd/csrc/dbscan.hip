@@ -102,7 +102,9 @@ __global__ __launch_bounds__(256) void k_core_tiled(int n, const GridPlan* __res
                                                     int32_t* __restrict__ rest,
                                                     int32_t* __restrict__ rest_cnt /*[kRestSegs]*/, int seg_cap,
                                                     int* __restrict__ parent, int* __restrict__ min_orig,
-                                                    int32_t* __restrict__ flag /*[n + 1]*/, int max_chunks,
+                                                    uint32_t* __restrict__ bits /*[n / 32 + 2]*/,
+                                                    int32_t* __restrict__ seam /*[seam_cap]*/, int seam_cap,
+                                                    int max_chunks,
                                                     unsigned long long* __restrict__ tests /*may be null:
                                                     [256] slots, candidates staged per wave (x 64 lanes
                                                     = lane-tests executed)*/,
@@ -201,12 +203,15 @@ __global__ __launch_bounds__(256) void k_core_tiled(int n, const GridPlan* __res
     co.mark_core(p, cnt >= min_pts);
   }
   // the start of the union phase rides along (it was a launch of its own, ~5 us): every point its own
-  // parent, no smallest index yet, no cluster flags
+  // parent, no smallest index yet, k_number's bitmap (n / 32 + 1 words: nothing reads more of it) and the
+  // cells' seam words empty (k_flatten_reps; a word per directory slot, n of them and a few per bucket
+  // more: the n live threads stride over them), no pre-root listed (the count lies behind the bitmap)
   if (live) {
     parent[p] = p;
     min_orig[p] = 0x7F7F7F7F;  // > any index
-    flag[p] = 0;
-    if (p == n - 1) flag[n] = 0;
+    if (p <= n / 32) bits[p] = 0u;
+    if (p == 0) bits[n / 32 + 1] = 0u;
+    for (int i = p; i < seam_cap; i += n) seam[i] = 0;
   }
   if (tests && lane == 0) atomicAdd(tests + (blockIdx.x & 255), static_cast<unsigned long long>(staged));
   });
@@ -402,6 +407,7 @@ __global__ __launch_bounds__(1024) void k_sub_rep(int n, const int32_t* __restri
                                                  int4* __restrict__ list,
                                                  int32_t* __restrict__ list_cnt, const GridPlan* __restrict__ plan,
                                                  int4* __restrict__ list_xyz,
+                                                 const DirWord* __restrict__ dwords,
     unsigned long long* __restrict__ st /*stamps or null*/) {
   stamped(st, [&] {
   if (!plan->ok) return;
@@ -497,14 +503,16 @@ __global__ __launch_bounds__(1024) void k_sub_rep(int n, const int32_t* __restri
     }
   }
   __syncthreads();
-  // list record: representative, its cell, its sub-cell id, points from it to the run's end
+  // list record: representative, its cell, its cell's directory slot (where the cell's seam word lies,
+  // k_flatten_reps: the directory word is looked up HERE, where the neighbouring lanes ask for the same
+  // one), points from it to the run's end
   // ... and, for k_hook_sub, its cell's grid coordinates and its octant: the two integer divisions by the
   // grid's dimensions happen HERE, once per sub-cell — in the hook pass every wave did twelve of them per
   // four sub-cells (~40 instructions each; the pass's look-ups were 48 us of its 81, a third of that this)
   if (is_rep) {
     const int slot = wbase[w] + __popcll(b & ((1ull << lane) - 1ull));
     const int c1 = cell;
-    list[slot] = make_int4(rep, c1, sid, e - rep);
+    list[slot] = make_int4(rep, c1, CellDir::slot_of(dwords[c1 >> 5], c1), e - rep);
     list_xyz[slot] = make_int4(c1 % nx, (c1 / nx) % ny, c1 / (nx * ny), sid & 7);
   }
   });
@@ -513,6 +521,76 @@ __global__ __launch_bounds__(1024) void k_sub_rep(int n, const int32_t* __restri
 // The 62 lexicographically positive (dz, dy, dx) offsets in [-2,2]^3 as (dx, dy, dz): the 13
 // of max-norm 1 first, then the 49 of max-norm 2.
 __constant__ signed char kSubOffsets[62][3] = {{1,0,0}, {-1,1,0}, {0,1,0}, {1,1,0}, {-1,-1,1}, {0,-1,1}, {1,-1,1}, {-1,0,1}, {0,0,1}, {1,0,1}, {-1,1,1}, {0,1,1}, {1,1,1}, {2,0,0}, {-2,1,0}, {2,1,0}, {-2,2,0}, {-1,2,0}, {0,2,0}, {1,2,0}, {2,2,0}, {-2,-2,1}, {-1,-2,1}, {0,-2,1}, {1,-2,1}, {2,-2,1}, {-2,-1,1}, {2,-1,1}, {-2,0,1}, {2,0,1}, {-2,1,1}, {2,1,1}, {-2,2,1}, {-1,2,1}, {0,2,1}, {1,2,1}, {2,2,1}, {-2,-2,2}, {-1,-2,2}, {0,-2,2}, {1,-2,2}, {2,-2,2}, {-2,-1,2}, {-1,-1,2}, {0,-1,2}, {1,-1,2}, {2,-1,2}, {-2,0,2}, {-1,0,2}, {0,0,2}, {1,0,2}, {2,0,2}, {-2,1,2}, {-1,1,2}, {0,1,2}, {1,1,2}, {2,1,2}, {-2,2,2}, {-1,2,2}, {0,2,2}, {1,2,2}, {2,2,2}};
+
+// Block-aggregated append of the flagged threads' values to list[*cnt]: one atomic per block (atomics on one
+// address are served one at a time). Every thread of the block calls it.
+template <int kThreads>
+__device__ __forceinline__ void block_append(bool take, int value, int32_t* __restrict__ list,
+                                             int32_t* __restrict__ cnt) {
+  constexpr int kWaves = kThreads / 64;
+  __shared__ int wcount[kWaves], wbase[kWaves];
+  const unsigned long long b = __ballot(take);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (lane == 0) wcount[w] = __popcll(b);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int tot = 0;
+    for (int k = 0; k < kWaves; ++k) tot += wcount[k];
+    int base = tot ? atomicAdd(cnt, tot) : 0;
+    for (int k = 0; k < kWaves; ++k) {
+      wbase[k] = base;
+      base += wcount[k];
+    }
+  }
+  __syncthreads();
+  if (take) list[wbase[w] + __popcll(b & ((1ull << lane) - 1ull))] = value;
+}
+
+// The list of the non-core points for the label pass (`rest`, reused from the core pass: after k_core_rest),
+// from the final core flags. Block b of the role takes the sorted positions [b * kFlagsPerBlock,
+// (b + 1) * kFlagsPerBlock), sixteen per thread, their loads side by side, and appends its non-core ones with ONE
+// atomic as block_append does (the counter is one address and its atomics are served one at a time, so few
+// large blocks). Every thread of a block of kFlagsThreads calls it; it runs as extra blocks of a launch of the
+// union phase whose own blocks leave most wave slots empty (k_flatten_reps).
+static constexpr int kFlagsThreads = 256, kFlagsPer = 16, kFlagsPerBlock = kFlagsThreads * kFlagsPer;
+__device__ __forceinline__ void flags_role(int b, int n, const uint8_t* __restrict__ core,
+                                           int32_t* __restrict__ rest, int32_t* __restrict__ rest_cnt) {
+  constexpr int kWaves = kFlagsThreads / 64;
+  __shared__ int fcount[kWaves], fbase[kWaves];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int p0 = b * kFlagsPerBlock + threadIdx.x;
+  unsigned take = 0;  // bit k: position p0 + k * kFlagsThreads is a non-core point
+#pragma unroll
+  for (int k = 0; k < kFlagsPer; ++k) {
+    const int p = p0 + k * kFlagsThreads;
+    take |= unsigned(p < n && !core[p]) << k;
+  }
+  // the wave's count by a butterfly: sixteen ballots kept across the barriers cost the launch a wave per SIMD in
+  // scalar registers
+  int mine = __popc(take);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
+  if (lane == 0) fcount[w] = mine;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int tot = 0;
+    for (int k = 0; k < kWaves; ++k) tot += fcount[k];
+    int base = tot ? atomicAdd(rest_cnt, tot) : 0;
+    for (int k = 0; k < kWaves; ++k) {
+      fbase[k] = base;
+      base += fcount[k];
+    }
+  }
+  __syncthreads();
+  int at = fbase[w];
+#pragma unroll
+  for (int k = 0; k < kFlagsPer; ++k) {
+    const bool t = (take >> k) & 1u;
+    const unsigned long long bal = __ballot(t);
+    if (t) rest[at + __popcll(bal & ((1ull << lane) - 1ull))] = p0 + k * kFlagsThreads;
+    at += __popcll(bal);
+  }
+}
 
 // Full path compression for the listed representatives (plain accesses: the kernel
 // boundary makes the unions of the previous launch visible, and any value another lane
@@ -534,33 +612,139 @@ __constant__ signed char kSubOffsets[62][3] = {{1,0,0}, {-1,1,0}, {0,1,0}, {1,1,
 // unchanged: `parent[p] = p` could overwrite the hook another thread has just installed on the root p.
 // A sub-cell that is not a root is never the target of a CAS, and whatever is stored there is an ancestor.
 // Plain reads that race with the unions still name ancestors (trees only merge).
-// The launch that knows every listed sub-cell's final root r folds it into ONE WORD PER
-// CELL, the fourth word of the cell's first sub-cell record (the binning leaves it 0, grid.hpp):
+// The launch that knows every listed sub-cell's root r (the WORDS launch: kFlattenWords, or kFlattenRoots
+// without second links; no union runs while it does, so r is exact) does two things with it.
+// It folds r into ONE WORD PER CELL, seam[slot]: a table of its own indexed by the cell's slot in the
+// ranked directory (CellDir::slot_of, which k_sub_rep left in the list entry), so that the words of
+// x-neighbouring occupied cells share a line (k_core_tiled zeroes it):
 //   0      no sub-cell with core points seen yet
 //   r + 1  every such sub-cell of the cell seen so far has root r
 //   -1     mixed
 // The first to arrive installs r + 1; whoever finds another root there stores -1. Whatever the order of
 // arrival, the word ends as r + 1 exactly when all of the cell's listed sub-cells have root r.
 // k_union_sub decides "same tree" per CELL from it.
+// And it lists the PRE-ROOTS, the sub-cells that are their own root now. From here on every representative
+// points at a pre-root: k_union_sub's unions only hook pre-roots under pre-roots, and the path halving of
+// their finds moves a pointer to another ancestor, a pre-root again. The smallest indices are folded into
+// the pre-roots beside the seams (fold_role) and k_fold_roots settles the pre-roots after them; a launch
+// over all representatives (k_rep_root, 16.8 us per million points for the benchmark forest's 23
+// pre-roots) is not needed for it.
+// The hosting launch (kFlattenLink, or kFlattenRoots without second links) also carries flags_role in the
+// blocks behind its own: its threads spend their time waiting on chains of dependent loads.
 enum FlattenMode { kFlattenJump, kFlattenRoots, kFlattenLink, kFlattenWords };
 
+// The minimum of v over the active lanes that share a root r, for every root of the wave: returned in the
+// root's first lane, 0x7FFFFFFF in every other lane. One root at a time, shuffles only.
+__device__ __forceinline__ int wave_fold_by_root(bool active, int r, int v) {
+  const int lane = threadIdx.x & 63;
+  int fold = 0x7FFFFFFF;
+  unsigned long long rem = __ballot(active);
+  while (rem) {
+    const int lead = __ffsll(rem) - 1;
+    const int r0 = __shfl(r, lead, 64);
+    const bool mine = active && r == r0;
+    int mn = mine ? v : 0x7FFFFFFF;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const int o = __shfl_xor(mn, off, 64);
+      mn = o < mn ? o : mn;
+    }
+    if (lane == lead) fold = mn;
+    rem &= ~__ballot(mine);
+  }
+  return fold;
+}
+
+// The components' smallest original core indices, folded from the per-run minima of the representatives
+// (run_min, k_sub_rep: 5x fewer values than points) into min_orig of the pre-root each representative
+// points at. It runs as extra blocks of k_union_sub's launch, entry s of the list per thread: that launch's own
+// blocks leave the chip nearly empty (a few waves on the seams), and this role is what cost k_rep_root its
+// time — a wave of representatives spans a dozen clusters (grid rows run across the whole scene), and
+// folding them one root at a time is some four hundred cycles per root. The unions of the same launch only
+// move a representative's pointer to another pre-root above it, and k_fold_roots hands every pre-root's
+// minimum on to its final root afterwards, so whichever pre-root the plain read names will do.
+// Each group of four waves puts its (root, minimum) pairs together in LDS, the group's first wave folds
+// those the same way, and only what is left goes to min_orig, behind a plain pre-check: an atomic only if it
+// can still lower the stored minimum. (Atomics on one address are served one at a time; folding all core
+// points with them cost 0.23 ms per million points.) Every thread of a block of kThreads calls it.
+static constexpr int kFoldSlots = 64;  // pairs of a group of four waves: what one wave folds
+static constexpr int kFoldRuns = 24;   // runs of equal roots in a wave beyond which it does not fold
+template <int kThreads>
+__device__ __forceinline__ void fold_role(int s, int m, const int4* __restrict__ list, const int* parent,
+                                          const int* __restrict__ run_min, int* min_orig) {
+  constexpr int kGroups = kThreads / 256;
+  __shared__ int f_root[kGroups][kFoldSlots], f_min[kGroups][kFoldSlots], f_cnt[kGroups];
+  const int lane = threadIdx.x & 63, grp = threadIdx.x >> 8;
+  if ((threadIdx.x & 255) == 0) f_cnt[grp] = 0;
+  const bool active = s < m;
+  int r = -1, v = 0x7FFFFFFF;
+  if (active) {
+    const int p = list[s].x;
+    v = run_min[p];
+    r = parent[p];
+  }
+  __syncthreads();
+  const volatile int* vmin = min_orig;  // a stale value only costs an atomic
+  // Where nearly every sub-cell is its own tree (a sparse cloud with min_pts = 1) there is nothing to fold and
+  // no address is hot: a wave with more than kFoldRuns runs of equal roots sends every value straight to its root.
+  const int before = __shfl_up(r, 1, 64);
+  const bool many = __popcll(__ballot(lane == 0 || before != r)) > kFoldRuns;  // wave-uniform
+  if (many && active && v < vmin[r]) atomicMin(min_orig + r, v);
+  const int fold = many ? 0x7FFFFFFF : wave_fold_by_root(active, r, v);
+  const bool has = fold != 0x7FFFFFFF;
+  const unsigned long long hb = __ballot(has);
+  int at = 0;
+  if (lane == 0 && hb) at = atomicAdd(&f_cnt[grp], __popcll(hb));
+  at = __shfl(at, 0, 64) + __popcll(hb & ((1ull << lane) - 1ull));
+  if (has) {
+    if (at < kFoldSlots) {
+      f_root[grp][at] = r;
+      f_min[grp][at] = fold;
+    } else if (fold < vmin[r]) {  // (more roots in the group than slots: straight to the root)
+      atomicMin(min_orig + r, fold);
+    }
+  }
+  __syncthreads();
+  if ((threadIdx.x & 255) < 64) {
+    const bool mine = lane < min(f_cnt[grp], kFoldSlots);
+    const int r1 = mine ? f_root[grp][lane] : -1;
+    const int fold1 = wave_fold_by_root(mine, r1, mine ? f_min[grp][lane] : 0x7FFFFFFF);
+    if (fold1 != 0x7FFFFFFF && fold1 < vmin[r1]) atomicMin(min_orig + r1, fold1);
+  }
+}
+
 template <FlattenMode MODE>
-__global__ __launch_bounds__(256) void k_flatten_reps(const int4* __restrict__ list,
+__global__ __launch_bounds__(kFlagsThreads) void k_flatten_reps(const int4* __restrict__ list,
                                                       const int32_t* __restrict__ m_ptr,
                                                       int* parent, int max_steps /*kFlattenJump*/,
                                                       const int32_t* __restrict__ link2 /*kFlattenLink*/,
-                                                      int4* __restrict__ rec /*kFlattenRoots, kFlattenWords*/) {
+                                                      int32_t* __restrict__ seam /*the words launch, as below*/,
+                                                      int32_t* __restrict__ pre, int32_t* __restrict__ pre_cnt,
+                                                      int rep_blocks /*the hosting launch, as below*/, int n,
+                                                      const uint8_t* __restrict__ core,
+                                                      int32_t* __restrict__ rest, int32_t* __restrict__ rest_cnt,
+                                                      const GridPlan* __restrict__ plan) {
+  constexpr int kThreads = kFlagsThreads;
+  static_assert(kThreads == 256, "the list is cut in 256s");
+  if constexpr (MODE == kFlattenLink || MODE == kFlattenRoots) {
+    // Two roles, by block index and independent of each other. The representatives' blocks come first, so
+    // that their chains of dependent loads start at once; the blocks behind them do the flags role.
+    if (int(blockIdx.x) >= rep_blocks) {
+      if (plan->ok) flags_role(blockIdx.x - rep_blocks, n, core, rest, rest_cnt);
+      return;
+    }
+  }
   const int m = *m_ptr;  // number of listed sub-cells, left on the device by k_sub_rep
-  const int s = blockIdx.x * 256 + threadIdx.x;
+  const int s = blockIdx.x * kThreads + threadIdx.x;
   const bool active = s < m;
   if constexpr (MODE == kFlattenJump || MODE == kFlattenLink) {
     if (!active) return;
   }
-  int p = -1, r = -1, cell8 = -1;  // (cell8: the cell's first sub-cell record = sub-cell id without the octant)
+  int p = -1, r = -1, slot = -1;  // (slot: of the sub-cell's cell in the directory)
   if (active) {
     const int4 me = list[s];
     p = r = me.x;
-    cell8 = me.z & ~7;
+    slot = me.z;
   }
   if constexpr (MODE == kFlattenJump) {
     int steps = 0;
@@ -582,16 +766,18 @@ __global__ __launch_bounds__(256) void k_flatten_reps(const int4* __restrict__ l
       for (int nx = parent[r]; nx != r; nx = parent[r]) r = nx;
       if (r != p) parent[p] = r;
     }
+    const int lane = threadIdx.x & 63;
     // The list follows the sorted order within a block of k_sub_rep, so the sub-cells of a cell mostly sit
     // in neighbouring lanes: a lane whose predecessor brings the same root to the same word leaves the
     // atomic to it (the word depends only on the SET of roots folded into it).
-    const int pc = __shfl_up(cell8, 1, 64), pr = __shfl_up(r, 1, 64);
-    const bool dup = (threadIdx.x & 63) != 0 && pc == cell8 && pr == r;
+    const int pc = __shfl_up(slot, 1, 64), pr = __shfl_up(r, 1, 64);
+    const bool dup = lane != 0 && pc == slot && pr == r;
     if (active && !dup) {
-      int* const word = reinterpret_cast<int*>(rec + cell8) + 3;
+      int* const word = seam + slot;
       const int old = atomicCAS(word, 0, r + 1);
       if (old != 0 && old != r + 1 && old != -1) *word = -1;
     }
+    block_append<kThreads>(active && r == p, p, pre, pre_cnt);
   }
 }
 
@@ -800,69 +986,120 @@ __device__ __forceinline__ void seam_unite(const int4 me, const int4 at, int k, 
 // in the 18 cells of s's own z-layer and the layer below: dz >= 0 keeps them out of the layer above, and
 // with dz = 1 inside the own layer dy and dx are free. (NOT in "the cell and its 13 lexicographically
 // smaller neighbours": offset (0, -2, 1) of an upper octant leads to the cell at y + 1 of the same layer.)
-// So a sub-cell s first reads the summary words (k_flatten_reps) of those 18 cells, four sub-cells per
-// wave in 16-lane groups, lane t < 9 one (x, y) column in both layers: when every word is 0 or names the
-// root r_s that a plain read of s's pointer shows, s and all core sub-cells of those cells are in one
-// tree and no pair of s needs a test. The words are a snapshot taken at a kernel boundary and trees only
-// merge, so a pointer that this launch has moved meanwhile (r_s is then another ancestor) can only fail
-// the comparison: an unnecessary full treatment, never a pair skipped wrongly. Only the SEAM sub-cells,
-// where a word is mixed or names another tree, get seam_unite's 62 offsets, one sub-cell per wave step.
-// (Until this form every sub-cell put all its neighbours, 6 million pairs on the benchmark forest,
-// through two parent gathers each, from the table the hook pass wrote: 21 of the pass's 32 us, for
-// 15 800 doubtful pairs in 2 200 sub-cells.)
+// Every listed sub-cell of a cell C looks at the SAME 18 cells, C among them, so whether its pairs can
+// need a test is decided once per CELL, from the seam words alone (k_flatten_reps): when C's own word names
+// a root r and each of the 18 words is 0 or names r too, every core sub-cell of those cells, C's own
+// included, is in the tree r and no pair of C's sub-cells needs a test. C is a SEAM cell when its own word
+// is mixed (-1) or one of the 18 names something else; every listed sub-cell of a seam cell gets
+// seam_unite's 62 offsets, one sub-cell per wave step. The words are a snapshot taken at a kernel boundary
+// and trees only merge: two sub-cells the snapshot shows in one tree stay in one tree, whatever this launch
+// does meanwhile, and nothing but the snapshot enters the decision (no pointer that this launch moves).
+// A wave takes 64 consecutive list entries. A cell's listed sub-cells are consecutive in the list (it
+// follows the sorted order within a block of k_sub_rep), so the wave filters the LEADERS only, the entries
+// whose predecessor has another cell, seven per step: nine lanes per leader, a lane per (x, y) column in
+// both layers, two dependent gathers each (directory word, then the seam word at the cell's slot; a lane
+// whose cell is empty stops after the first). The first entry of a wave's stretch always counts as a
+// leader, and so does the first one after the end of a k_sub_rep block: a cell cut in two there or at a
+// stretch's end is filtered twice with the same answer, and each of its entries belongs to exactly one run.
+// (Until this form the filter ran per sub-cell, 197 k times for the benchmark forest's ~60 k cells, with
+// three dependent gathers per cell — the last one into the sub-cell records, a line of its own per cell —
+// and a gather of the sub-cell's pointer: 19.9 us for 86 seam sub-cells. Before that every sub-cell put
+// all its neighbours, 6 million pairs on the benchmark forest, through two parent gathers each, from the
+// table the hook pass wrote: 21 of the pass's 32 us, for 15 800 doubtful pairs in 2 200 sub-cells.)
+// The seam entries a block's waves find go on a list in LDS, and the block's sixteen waves then take them in
+// turn: seam cells lie side by side, a seam sub-cell is a chain of some twenty dependent memory accesses, and
+// with every wave treating what it had found itself the one whose stretch held a seam's cells set the
+// launch's time (filter alone 6.4 us on the benchmark forest, with its 86 seam sub-cells 18 us).
+static constexpr int kSeamStretch = 64;   // list entries per wave step
+static constexpr int kSeamThreads = 1024;  // ... and per block step
 template <class CO>
-__global__ __launch_bounds__(256) void k_union_sub(const int4* __restrict__ list,
+__global__ __launch_bounds__(kSeamThreads) void k_union_sub(const int4* __restrict__ list,
                                                    const int4* __restrict__ list_xyz,
                                                    const int32_t* __restrict__ m_ptr,
                                                    const GridPlan* __restrict__ plan,
                                                    const DirWord* __restrict__ dwords,
                                                    const int32_t* __restrict__ dslots,
+                                                   const int32_t* __restrict__ seam,
                                                    const int4* __restrict__ rec, CO co, double r2,
                                                    const uint8_t* __restrict__ core, int* parent,
+                                                   int seam_blocks, const int* __restrict__ run_min,
+                                                   int* min_orig,
                                                    unsigned long long* __restrict__ seam_cnt /*trace or null*/,
     unsigned long long* __restrict__ st /*stamps or null*/) {
+  __shared__ int todo_list[kSeamThreads], todo_cnt;
   stamped(st, [&] {
   const CellDir dir{dwords, dslots};
   if (!plan->ok) return;
   const int nx = plan->nx, ny = plan->ny;
   const int m = *m_ptr;
-  const int k = threadIdx.x & 63;
-  const int t = k & 15, grp = k >> 4;
+  // Two roles, by block index and independent of each other: the seams' blocks first, so that their chains
+  // of dependent accesses start at once; the blocks behind them fold the smallest indices (fold_role).
+  if (int(blockIdx.x) >= seam_blocks) {
+    fold_role<kSeamThreads>((blockIdx.x - seam_blocks) * kSeamThreads + threadIdx.x, m, list, parent, run_min,
+                            min_orig);
+    return;
+  }
+  const int k = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int o_dx = k < 62 ? kSubOffsets[k][0] : 0, o_dy = k < 62 ? kSubOffsets[k][1] : 0,
             o_dz = k < 62 ? kSubOffsets[k][2] : 0;
-  // the group's 18 cells: lane t < 9 takes the column (t % 3 - 1, t / 3 - 1), in the layer below and the own one
-  const int c_off = t < 9 ? (t % 3 - 1) + (t / 3 - 1) * nx : 0;
+  // the filter's groups: lane j of group g9 < 7 takes the column (j % 3 - 1, j / 3 - 1) of the group's cell,
+  // in the own layer and the one below (lane 63 idles there)
+  const int g9 = k / 9, j = k % 9;
+  const int c_off = (j % 3 - 1) + (j / 3 - 1) * nx;
   const int layer = nx * ny;
-  for (int s0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * kSubPerWave; s0 < m; s0 += gridDim.x * 4 * kSubPerWave) {
-    const bool live = s0 + grp < m;
-    const int4 me = list[min(s0 + grp, m - 1)];
-    const int* vparent = parent;
-    const int r_s = vparent[me.x];
-    const int c2 = me.y + c_off;  // (cells have a border of empty cells all round: c2 - layer - 1 >= 0)
-    int word[2] = {0, 0};
-    DirWord dw[2] = {{0u, 0u}, {0u, 0u}};
-    if (live && t < 9) {
+  for (int b0 = blockIdx.x * kSeamThreads; b0 < m; b0 += seam_blocks * kSeamThreads) {  // block-uniform
+    if (threadIdx.x == 0) todo_cnt = 0;
+    __syncthreads();
+    const int s0 = b0 + wv * kSeamStretch;
+    const bool live = s0 + k < m;
+    const int cell = live ? list[s0 + k].y : -1;
+    const int before = __shfl_up(cell, 1, 64);
+    const unsigned long long leaders = __ballot(live && (k == 0 || before != cell));
+    unsigned long long rem = leaders, seam_leaders = 0;
+    while (rem) {  // wave-uniform: the next seven leaders
+      unsigned long long mine = rem;  // ... the g9-th of them for this lane
 #pragma unroll
-      for (int l = 0; l < 2; ++l) dw[l] = dir.words[(c2 - l * layer) >> 5];
-    }
-    int b2[2] = {0, 0};
-    bool occ[2];
+      for (int i = 0; i < 6; ++i)
+        if (i < g9) mine &= mine - 1;
+      const bool act = g9 < 7 && mine != 0;
+      const int src = act ? __ffsll(mine) - 1 : 0;
+      const int c2 = __shfl(cell, src, 64) + c_off;  // (cells have a border of empty cells all round: c2 - layer - 1 >= 0)
+      int word[2] = {0, 0};
+      DirWord dw[2] = {{0u, 0u}, {0u, 0u}};
+      if (act) {
 #pragma unroll
-    for (int l = 0; l < 2; ++l) {
-      occ[l] = (dw[l].bits >> ((c2 - l * layer) & 31)) & 1u;
-      if (occ[l]) b2[l] = dir.slots[CellDir::slot_of(dw[l], c2 - l * layer)];
-    }
+        for (int l = 0; l < 2; ++l) dw[l] = dir.words[(c2 - l * layer) >> 5];
+      }
 #pragma unroll
-    for (int l = 0; l < 2; ++l)
-      if (occ[l]) word[l] = rec[b2[l] * 8].w;
-    const unsigned long long seams =
-        __ballot((word[0] != 0 && word[0] != r_s + 1) || (word[1] != 0 && word[1] != r_s + 1));
-    if (!seams) continue;
-    for (int u = 0; u < kSubPerWave; ++u) {
-      if (!((seams >> (16 * u)) & 0xFFFFull)) continue;  // wave-uniform
-      if (seam_cnt && k == 0) atomicAdd(seam_cnt, 1ull);
-      seam_unite(list[s0 + u], list_xyz[s0 + u], k, o_dx, o_dy, o_dz, nx, ny, dir, rec, co, r2, core, parent);
+      for (int l = 0; l < 2; ++l)
+        if ((dw[l].bits >> ((c2 - l * layer) & 31)) & 1u) word[l] = seam[CellDir::slot_of(dw[l], c2 - l * layer)];
+      const int own = __shfl(word[0], g9 * 9 + 4, 64);  // the group's cell itself: column (0, 0), own layer
+      const unsigned long long bad = __ballot(
+          act && (own == -1 || (word[0] != 0 && word[0] != own) || (word[1] != 0 && word[1] != own)));
+#pragma unroll
+      for (int g = 0; g < 7; ++g) {
+        if ((bad >> (9 * g)) & 0x1FFull) seam_leaders |= rem & (~rem + 1ull);  // the g-th leader of this step
+        rem &= rem - 1;
+      }
     }
+    if (seam_leaders) {  // wave-uniform
+      // the entries of the seam cells' runs: a lane's leader is the last one at or before it (lane 0 is one)
+      const int leader = 63 - __clzll(leaders & (~0ull >> (63 - k)));
+      const bool take = live && ((seam_leaders >> leader) & 1ull);
+      const unsigned long long todo = __ballot(take);
+      int at = 0;
+      if (k == 0) at = atomicAdd(&todo_cnt, __popcll(todo));
+      at = __shfl(at, 0, 64);
+      if (take) todo_list[at + __popcll(todo & ((1ull << k) - 1ull))] = s0 + k;
+    }
+    __syncthreads();
+    const int cnt = todo_cnt;
+    if (seam_cnt && threadIdx.x == 0 && cnt) atomicAdd(seam_cnt, static_cast<unsigned long long>(cnt));
+    for (int i = wv; i < cnt; i += kSeamThreads / 64) {  // wave-uniform
+      const int s = __builtin_amdgcn_readfirstlane(todo_list[i]);
+      seam_unite(list[s], list_xyz[s], k, o_dx, o_dy, o_dz, nx, ny, dir, rec, co, r2, core, parent);
+    }
+    __syncthreads();  // the list is rewritten in the next step
   }
   });
 }
@@ -906,76 +1143,6 @@ __global__ __launch_bounds__(256) void k_flatten(int n, const uint8_t* __restric
   parent[p] = r;  // benign: r is still an ancestor for concurrent readers
 }
 
-// Block-aggregated append of the flagged threads' values to list[*cnt]: one atomic per block (atomics on one
-// address are served one at a time). Every thread of the block calls it.
-template <int kThreads>
-__device__ __forceinline__ void block_append(bool take, int value, int32_t* __restrict__ list,
-                                             int32_t* __restrict__ cnt) {
-  constexpr int kWaves = kThreads / 64;
-  __shared__ int wcount[kWaves], wbase[kWaves];
-  const unsigned long long b = __ballot(take);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) wcount[w] = __popcll(b);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int tot = 0;
-    for (int k = 0; k < kWaves; ++k) tot += wcount[k];
-    int base = tot ? atomicAdd(cnt, tot) : 0;
-    for (int k = 0; k < kWaves; ++k) {
-      wbase[k] = base;
-      base += wcount[k];
-    }
-  }
-  __syncthreads();
-  if (take) list[wbase[w] + __popcll(b & ((1ull << lane) - 1ull))] = value;
-}
-
-// The list of the non-core points for the label pass (`rest`, reused from the core pass: after k_core_rest),
-// from the final core flags. Block b of the role takes the sorted positions [b * kFlagsPerBlock,
-// (b + 1) * kFlagsPerBlock), sixteen per thread, their loads side by side, and appends its non-core ones with ONE
-// atomic as block_append does (the counter is one address and its atomics are served one at a time, so few
-// large blocks). Every thread of a block of kFlagsThreads calls it; it runs as extra blocks of a launch of the
-// union phase whose own blocks leave most wave slots empty (k_rep_root).
-static constexpr int kFlagsThreads = 256, kFlagsPer = 16, kFlagsPerBlock = kFlagsThreads * kFlagsPer;
-__device__ __forceinline__ void flags_role(int b, int n, const uint8_t* __restrict__ core,
-                                           int32_t* __restrict__ rest, int32_t* __restrict__ rest_cnt) {
-  constexpr int kWaves = kFlagsThreads / 64;
-  __shared__ int fcount[kWaves], fbase[kWaves];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int p0 = b * kFlagsPerBlock + threadIdx.x;
-  unsigned take = 0;  // bit k: position p0 + k * kFlagsThreads is a non-core point
-#pragma unroll
-  for (int k = 0; k < kFlagsPer; ++k) {
-    const int p = p0 + k * kFlagsThreads;
-    take |= unsigned(p < n && !core[p]) << k;
-  }
-  // the wave's count by a butterfly: sixteen ballots kept across the barriers cost the launch a wave per SIMD in
-  // scalar registers
-  int mine = __popc(take);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
-  if (lane == 0) fcount[w] = mine;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int tot = 0;
-    for (int k = 0; k < kWaves; ++k) tot += fcount[k];
-    int base = tot ? atomicAdd(rest_cnt, tot) : 0;
-    for (int k = 0; k < kWaves; ++k) {
-      fbase[k] = base;
-      base += fcount[k];
-    }
-  }
-  __syncthreads();
-  int at = fbase[w];
-#pragma unroll
-  for (int k = 0; k < kFlagsPer; ++k) {
-    const bool t = (take >> k) & 1u;
-    const unsigned long long bal = __ballot(t);
-    if (t) rest[at + __popcll(bal & ((1ull << lane) - 1ull))] = p0 + k * kFlagsThreads;
-    at += __popcll(bal);
-  }
-}
-
 // The same as a launch of its own: the per-point union-find's path.
 __global__ __launch_bounds__(kFlagsThreads) void k_noncore_list(int n, const uint8_t* __restrict__ core,
                                                                 int32_t* __restrict__ rest,
@@ -999,66 +1166,37 @@ __global__ __launch_bounds__(256) void k_point_min(int n, const uint8_t* __restr
   block_append<256>(is_c && parent[p] == p, p, roots, roots_cnt);
 }
 
-// Smallest original core index of every component, folded from the per-run minima of
-// the representatives (k_sub_rep): 5x fewer values than points, wave-folded when the
-// wave's representatives share a root (the common case), and an atomic only if it can
-// still lower the stored minimum. (Folding all core points this way cost 0.23 ms per
-// million points: atomics and coherent loads on a handful of hot addresses.)
-// Each representative also points straight at its root, and the roots are listed: the unions only ever
-// rewrote representatives' pointers, so every core point now reaches its root in two hops
-// (point -> representative -> root) and no pass over all points is needed to flatten them.
-// (Blocks of kRepRootThreads: the flags blocks behind the representatives' run flags_role, which needs its own size.)
-static constexpr int kRepRootThreads = kFlagsThreads;
-static_assert(kRepRootThreads == 256, "gl, the grid of the representatives' blocks, is cut in 256s");
-__global__ __launch_bounds__(kRepRootThreads) void k_rep_root(const int4* __restrict__ list,
-                                                  const int32_t* __restrict__ m_ptr,
-                                                  int* __restrict__ parent,
-                                                  const int* __restrict__ run_min,
-                                                  int* __restrict__ min_orig,
-                                                  int32_t* __restrict__ roots,
-                                                  int32_t* __restrict__ roots_cnt, int rep_blocks, int n,
-                                                  const uint8_t* __restrict__ core, int32_t* __restrict__ rest,
-                                                  int32_t* __restrict__ rest_cnt,
-                                                  const GridPlan* __restrict__ plan) {
-  // Two roles, by block index and independent of each other. The representatives' blocks come first, so that
-  // their chains of dependent loads start at once (some 3 k waves with work on a chip of 8 k slots); the
-  // blocks behind them do the flags role in the slots those leave empty.
-  if (int(blockIdx.x) >= rep_blocks) {
-    if (plan->ok) flags_role(blockIdx.x - rep_blocks, n, core, rest, rest_cnt);
-    return;
-  }
-  const int m = *m_ptr;
-  int s = blockIdx.x * kRepRootThreads + threadIdx.x;
-  const bool active = s < m;
-  int p = -1, r = -1, v = 0x7FFFFFFF;
-  if (active) {
-    p = list[s].x;
-    // the root: after the compression that preceded k_union_sub and its few unions the chain is
-    // one to three links long (a second compression pass over the list cost 20 us for this)
-    r = p;
-    for (int nx = parent[r]; nx != r; nx = parent[r]) r = nx;
-    if (r != p) parent[p] = r;  // benign: r is still an ancestor for concurrent readers
-    v = run_min[p];
-  }
-  const volatile int* vmin = min_orig;  // plain pre-check: a stale value only costs an atomic
-  const int lane = threadIdx.x & 63;
-  // a wave of representatives spans a few clusters (grid rows run across the whole scene):
-  // fold one root at a time
-  unsigned long long rem = __ballot(active);
-  while (rem) {
-    const int lead = __ffsll(rem) - 1;
-    const int r0 = __shfl(r, lead, 64);
-    const bool mine = active && r == r0;
-    int mn = mine ? v : 0x7FFFFFFF;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const int o = __shfl_xor(mn, off, 64);
-      mn = o < mn ? o : mn;
+// After the seams: only the PRE-ROOTS (k_flatten_reps) can have got a parent since the words launch knew
+// every representative's root, so only they are chased again — 23 on the benchmark forest, where a launch
+// over all 197 k representatives did this before (k_rep_root). A pre-root q that is still its own root is a
+// component: it goes on the list of roots that k_number and the cluster count read. One that k_union_sub
+// hooked hands the smallest index folded into it on to its final root f and points straight at f. Nobody
+// folds into a pre-root that is not final (every chase ends at a final one), so the value read there is
+// stable; the pointers written name ancestors. Every core point then reaches its component's smallest
+// index in THREE hops: point -> representative -> pre-root -> root (a root points at itself), k_labels.
+// Resident blocks stride over the list; its length is read here, nothing is sized by it on the host.
+static constexpr int kFoldThreads = 256;
+__global__ __launch_bounds__(kFoldThreads) void k_fold_roots(const int32_t* __restrict__ pre,
+                                                             const int32_t* __restrict__ pre_cnt,
+                                                             int* parent, int* min_orig,
+                                                             int32_t* __restrict__ roots,
+                                                             int32_t* __restrict__ roots_cnt,
+                                                             const GridPlan* __restrict__ plan) {
+  if (!plan->ok) return;  // block-uniform
+  const int m = *pre_cnt;
+  for (int i0 = blockIdx.x * kFoldThreads; i0 < m; i0 += gridDim.x * kFoldThreads) {  // block-uniform
+    const int i = i0 + threadIdx.x;
+    int q = -1, f = -1;
+    if (i < m) {
+      q = f = pre[i];
+      for (int nx = parent[f]; nx != f; nx = parent[f]) f = nx;
+      if (f != q) {
+        atomicMin(min_orig + f, min_orig[q]);
+        parent[q] = f;
+      }
     }
-    if (lane == lead && mn < vmin[r0]) atomicMin(min_orig + r0, mn);
-    rem &= ~__ballot(mine);
+    block_append<kFoldThreads>(i < m && f == q, q, roots, roots_cnt);
   }
-  block_append<256>(active && r == p, p, roots, roots_cnt);
 }
 
 // Cluster number = rank of the component's smallest original index among all components'. Up to kRankCap
@@ -1175,7 +1313,8 @@ __device__ __forceinline__ int cluster_number(int v, int n_roots, const uint32_t
 }
 
 // The label pass, two roles in one launch. Core points copy their cluster number (point -> representative ->
-// root): a thread each, one scattered store, and every point's core flag goes out in the caller's order beside
+// pre-root -> root, k_fold_roots; the per-point union-find's points name their root at once, and a root
+// names itself, so three hops serve every path): a thread each, one scattered store, and every point's core flag goes out in the caller's order beside
 // it. Then every wave takes the entries wave, wave + waves of the grid, ... of the list of non-core points
 // (flags_role): a WAVE per point (kRunBatch points' bounds looked up together, as in k_core_rest), the smallest
 // cluster number among the core neighbours in its stencil, or -1.
@@ -1210,7 +1349,7 @@ __global__ __launch_bounds__(kLabelThreads) void k_labels(int n, const int32_t* 
     const int p = blockIdx.x * kLabelThreads + threadIdx.x;
     const bool is_c = p < n && core[p];
     if (is_c) {
-      const int v = min_orig[parent[parent[p]]];
+      const int v = min_orig[parent[parent[parent[p]]]];
       labels[order[p]] = int64_t(cluster_number(v, n_roots, bits, wpre));
     }
     if (p < n && is_core) is_core[order[p]] = is_c;
@@ -1241,7 +1380,7 @@ __global__ __launch_bounds__(kLabelThreads) void k_labels(int n, const int32_t* 
         if (g < t.pre[9]) {
           const int q = t.at(g);
           if (core[q] && co.d2(q, xk, yk, zk) <= r2) {
-            const int mo = min_orig[parent[parent[q]]];
+            const int mo = min_orig[parent[parent[parent[q]]]];
             best = mo < best ? mo : best;
           }
         }
@@ -1276,12 +1415,24 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
   const double r2 = radius_inclusive ? eps * eps : nextafter(eps * eps, 0.0);
   uint8_t* core;
   int *parent, *min_orig;
-  int32_t* flag;  // [n + 1], zeroed by k_core_tiled: the bitmap of k_number's large-count numbering
+  // [n / 32 + 1] the bitmap of k_number's large-count numbering, [1] the number of pre-roots (k_flatten_reps,
+  // k_fold_roots): zeroed by k_core_tiled
+  uint32_t* bits;
   PQ_TRY(c->arena.get(size_t(n), &core));
   PQ_TRY(c->arena.get(size_t(n), &parent));
   PQ_TRY(c->arena.get(size_t(n), &min_orig));
-  PQ_TRY(c->arena.get(size_t(n) + 1, &flag));
-  uint32_t* const bits = reinterpret_cast<uint32_t*>(flag);
+  PQ_TRY(c->arena.get(size_t(n / 32) + 2, &bits));
+  int32_t* const pre_cnt = reinterpret_cast<int32_t*>(bits + n / 32 + 1);
+  // The cells' seam words (k_flatten_reps), one per slot of the ranked directory: a slot index stays below
+  // n + buckets + 1 from the two-level sort (a bucket has at least 2^12 cells) and below n + words + 1 of a
+  // directory made from a dense one (grid.hip). k_core_tiled zeroes the first kind, n stores and a few
+  // more; the second, the rare paths' with up to 2^23 words, takes a memset.
+  // (The per-point union-find of a doubled grid has no use for them.)
+  const size_t seam_cap = fine ? size_t(n) + size_t(g.start ? g.ncell >> 5 : g.ncell >> 12) + 3 : 0;
+  int32_t *seam, *pre;  // ... and the list of the pre-roots
+  PQ_TRY(c->arena.get(seam_cap, &seam));
+  PQ_TRY(c->arena.get(size_t(n), &pre));
+  if (fine && g.start) PQ_HIP(hipMemsetAsync(seam, 0, seam_cap * 4, c->stream));
   int32_t *roots, *wpre;  // the components' roots; k_number's word prefix (n / 32 + 1)
   PQ_TRY(c->arena.get(size_t(n), &roots));
   PQ_TRY(c->arena.get(size_t(n / 32) + 1, &wpre));
@@ -1319,7 +1470,8 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
       const StampKernel pk(c, "k_core_tiled", grid.x);
       on_coords(g, [&](auto co) {
         hipLaunchKernelGGL(k_core_tiled<decltype(co)>, grid, block, 0, c->stream, N, d_plan, dir.words, dir.slots, g.cell_of, co, r2,
-                           min_pts, core, rest, rest_segs, seg_cap, parent, min_orig, flag, max_chunks, d_tests,
+                           min_pts, core, rest, rest_segs, seg_cap, parent, min_orig, bits, seam,
+                           g.start ? 0 : int(seam_cap), max_chunks, d_tests,
                            pk.slots);
       });
     }
@@ -1350,11 +1502,11 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
   {
     StampScope ps(c, "dbscan_union");
     const dim3 gf(ceil_div(n, kFlagsPerBlock));  // blocks of flags_role
-    // (parent / min_orig / flag were initialised by k_core_tiled; list_cnt[0..2] are still the zeros the
-    // binning left)
+    // (parent / min_orig / bits / seam / pre_cnt were initialised by k_core_tiled; list_cnt[0..2] are still
+    // the zeros the binning left)
     if (fine) {
       hipLaunchKernelGGL(k_sub_rep, dim3(ceil_div(n, 1024)), dim3(1024), 0, c->stream, N, sub.sub_of, core,
-                         g.order, parent, g.cell_of, sub.rec, run_min, list, list_cnt, d_plan, list_xyz,
+                         g.order, parent, g.cell_of, sub.rec, run_min, list, list_cnt, d_plan, list_xyz, dir.words,
                          stamp_slots(c, ceil_div(n, 1024)));
       // The number m of listed sub-cells stays on the device: the passes below are launched for the
       // upper bound n (a sub-cell holds at least one point, in practice ~5) and read m themselves —
@@ -1371,17 +1523,18 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
         // the second search) and 32 (union) blocks per CU (PYQSM_UNION_BLOCKS_PER_CU=<hook>,<union>; 0 = a
         // block per 16 rows of the bound n, which starts four waves in five for nothing). Eight blocks are what
         // a CU holds of either kernel: the hook pass with its second search is shortest when no wave waits for
-        // a slot (30.5 us against 32.8 with 16 and 36.3 with 6); the union pass, mostly its filter now, is the
-        // same 20-22 us with 8, 16, 32 and 64.
+        // a slot (30.5 us against 32.8 with 16 and 36.3 with 6); the union pass, mostly its filter, was the
+        // same 20-22 us with 8, 16, 32 and 64 when it filtered per sub-cell. (It takes kSeamThreads list
+        // entries per block step now, so its bound grid is a block per kSeamThreads rows of n.)
         int per_cu[2] = {use_link2 ? 8 : 16, 32};
         if (const char* e_cu = getenv("PYQSM_UNION_BLOCKS_PER_CU")) {
           per_cu[0] = per_cu[1] = atoi(e_cu);
           if (const char* comma = strchr(e_cu, ',')) per_cu[1] = atoi(comma + 1);
         }
-        const int64_t full = ceil_div(n, 4 * kSubPerWave);
+        const int64_t full = ceil_div(n, 4 * kSubPerWave), full_u = ceil_div(n, kSeamThreads);
+        const int64_t cu_u = std::max(1, per_cu[1] * 256 / kSeamThreads);  // (the figure counts blocks of 256 threads)
         const dim3 gh(per_cu[0] > 0 ? std::min<int64_t>(full, int64_t(c->cu_count) * per_cu[0]) : full),
-            gu(per_cu[1] > 0 ? std::min<int64_t>(full, int64_t(c->cu_count) * per_cu[1]) : full),
-            gl(ceil_div(n, 256));
+            gu(per_cu[1] > 0 ? std::min<int64_t>(full_u, int64_t(c->cu_count) * cu_u) : full_u);
         const bool trace = getenv("PYQSM_DBSCAN_TRACE") != nullptr;
         {
           const StampKernel pk(c, "k_hook_sub", gh.x);
@@ -1444,25 +1597,29 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
           const char* e = getenv("PYQSM_FLATTEN_JUMP");
           return e ? atoi(e) : 12;
         }();
-        if (jump > 0)
-          hipLaunchKernelGGL(k_flatten_reps<kFlattenJump>, gl, block, 0, c->stream, list, list_cnt, parent, jump,
-                             link2, sub.rec);
+        // one launch of k_flatten_reps; `host_flags`: with the label pass's list of non-core points in gf
+        // blocks behind its own (flags_role)
+        const auto flatten = [&](auto mode, int max_steps, bool host_flags) {
+          constexpr int threads = kFlagsThreads;
+          const int rep_blocks = int(ceil_div(n, threads));
+          hipLaunchKernelGGL(k_flatten_reps<decltype(mode)::value>, dim3(rep_blocks + (host_flags ? gf.x : 0)),
+                             dim3(threads), 0, c->stream, list, list_cnt, parent, max_steps, link2, seam,
+                             pre, pre_cnt, rep_blocks, N, core, rest, list_cnt + 3, d_plan);
+        };
+        if (jump > 0) flatten(std::integral_constant<FlattenMode, kFlattenJump>{}, jump, false);
         if (use_link2) {
           // the pass that reaches the roots unites across the second links; a short third one then writes
-          // the cells' summary words
-          hipLaunchKernelGGL(k_flatten_reps<kFlattenLink>, gl, block, 0, c->stream, list, list_cnt, parent, 0, link2,
-                             sub.rec);
+          // the cells' seam words, folds the smallest indices and lists the pre-roots
+          flatten(std::integral_constant<FlattenMode, kFlattenLink>{}, 0, true);
           if (trace) {
             PQ_TRY(snapshot(nullptr));
             fprintf(stderr, "link pass: %lld recorded, %lld crossed trees, %lld roots left\n", (long long)links,
                     (long long)crossing, (long long)count_roots());
           }
-          hipLaunchKernelGGL(k_flatten_reps<kFlattenWords>, gl, block, 0, c->stream, list, list_cnt, parent, 0, link2,
-                             sub.rec);
+          flatten(std::integral_constant<FlattenMode, kFlattenWords>{}, 0, false);
         } else {
-          // (the pass that reaches the roots also writes the cells' summary words)
-          hipLaunchKernelGGL(k_flatten_reps<kFlattenRoots>, gl, block, 0, c->stream, list, list_cnt, parent, 0, link2,
-                             sub.rec);
+          // (the pass that reaches the roots is the words launch as well)
+          flatten(std::integral_constant<FlattenMode, kFlattenRoots>{}, 0, true);
         }
         // what is left: joining the few trees per cluster along their seams
         unsigned long long* d_seams = nullptr;  // trace only: sub-cells that took the 62-offset path
@@ -1471,10 +1628,12 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
           PQ_HIP(hipMemsetAsync(d_seams, 0, 8, c->stream));
         }
         {
-          const StampKernel pk(c, "k_union_sub", gu.x);
+          const int fold_blocks = int(ceil_div(n, kSeamThreads));  // (fold_role behind the seams' blocks)
+          const StampKernel pk(c, "k_union_sub", gu.x + fold_blocks);
           on_coords(g, [&](auto co) {
-            hipLaunchKernelGGL(k_union_sub<decltype(co)>, gu, block, 0, c->stream, list, list_xyz, list_cnt, d_plan,
-                               dir.words, dir.slots, sub.rec, co, r2, core, parent, d_seams, pk.slots);
+            hipLaunchKernelGGL(k_union_sub<decltype(co)>, dim3(gu.x + fold_blocks), dim3(kSeamThreads), 0, c->stream, list,
+                               list_xyz, list_cnt, d_plan, dir.words, dir.slots, seam, sub.rec, co, r2, core, parent,
+                               int(gu.x), run_min, min_orig, d_seams, pk.slots);
           });
         }
         if (trace) {
@@ -1483,9 +1642,10 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
           PQ_HIP(hipStreamSynchronize(c->stream));
           fprintf(stderr, "seam union: %llu sub-cells took the 62-offset path\n", h);
         }
-        // (with the label pass's list of non-core points behind its own blocks: flags_role)
-        hipLaunchKernelGGL(k_rep_root, dim3(gl.x + gf.x), dim3(kRepRootThreads), 0, c->stream, list, list_cnt, parent,
-                           run_min, min_orig, roots, roots_cnt, int(gl.x), N, core, rest, list_cnt + 3, d_plan);
+        // the pre-roots the seams hooked hand their smallest index on; the others are the components
+        const dim3 gp(std::min<int64_t>(ceil_div(n, kFoldThreads), int64_t(c->cu_count) * 8));
+        hipLaunchKernelGGL(k_fold_roots, gp, dim3(kFoldThreads), 0, c->stream, pre, pre_cnt, parent, min_orig, roots,
+                           roots_cnt, d_plan);
       }
       PQ_HIP(hipGetLastError());
     } else {
