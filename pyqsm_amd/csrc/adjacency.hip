@@ -277,10 +277,9 @@ int pyqsm_cluster_adjacency(const double* src, const int32_t* src_label, int64_t
   if (entries > kAdjMaxTable)
     return fail(PYQSM_ERANGE, "%d x %d cluster pairs exceed the table of 2^26 entries: split the sources by label",
                 n_src_labels, n_tgt_labels);
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   const int64_t cap = std::min(capacity, entries);
   double *d_src, *d_tgt, *d_min;
   int32_t *d_slab, *d_tlab, *d_tlab_sorted, *d_flags, *d_a, *d_b;
@@ -289,16 +288,16 @@ int pyqsm_cluster_adjacency(const double* src, const int32_t* src_label, int64_t
   unsigned long long *d_wit = nullptr, *d_stats = nullptr;
   PQ_TRY(c->arena.get(size_t(n) * 3, &d_src));
   PQ_TRY(c->arena.get(size_t(n), &d_slab));
-  PQ_HIP(hipMemcpyAsync(d_src, src, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_slab, src_label, size_t(n) * 4, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_src, src, size_t(n) * 3));
+  PQ_TRY(copy_in(c, d_slab, src_label, size_t(n)));
   if (same) {
     d_tgt = d_src;
     d_tlab = d_slab;
   } else {
     PQ_TRY(c->arena.get(size_t(m) * 3, &d_tgt));
     PQ_TRY(c->arena.get(size_t(m), &d_tlab));
-    PQ_HIP(hipMemcpyAsync(d_tgt, tgt, size_t(m) * 24, hipMemcpyHostToDevice, c->stream));
-    PQ_HIP(hipMemcpyAsync(d_tlab, tgt_label, size_t(m) * 4, hipMemcpyHostToDevice, c->stream));
+    PQ_TRY(copy_in(c, d_tgt, tgt, size_t(m) * 3));
+    PQ_TRY(copy_in(c, d_tlab, tgt_label, size_t(m)));
   }
   PQ_TRY(c->arena.get(size_t(m), &d_tlab_sorted));
   PQ_TRY(c->arena.get(size_t(entries), &d_table));
@@ -369,18 +368,18 @@ int pyqsm_cluster_adjacency(const double* src, const int32_t* src_label, int64_t
     }
   }
   int32_t total = 0;
-  PQ_HIP(hipMemcpyAsync(&total, d_flags + entries, 4, hipMemcpyDeviceToHost, c->stream));
-  if (stats) PQ_HIP(hipMemcpyAsync(stats, d_stats, 16, hipMemcpyDeviceToHost, c->stream));
+  PQ_TRY(download(c, &total, d_flags + entries, 1));
+  if (stats) PQ_TRY(download(c, reinterpret_cast<unsigned long long*>(stats), d_stats, 2));
   PQ_HIP(hipStreamSynchronize(c->stream));
   const size_t rows = size_t(std::min<int64_t>(total, cap));
   if (rows) {
-    PQ_HIP(hipMemcpyAsync(a, d_a, rows * 4, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipMemcpyAsync(b, d_b, rows * 4, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipMemcpyAsync(min_d2, d_min, rows * 8, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipMemcpyAsync(pairs, d_pairs, rows * 8, hipMemcpyDeviceToHost, c->stream));
+    PQ_TRY(download(c, a, d_a, rows));
+    PQ_TRY(download(c, b, d_b, rows));
+    PQ_TRY(download(c, min_d2, d_min, rows));
+    PQ_TRY(download(c, pairs, d_pairs, rows));
     if (witness) {
-      PQ_HIP(hipMemcpyAsync(src_idx, d_si, rows * 8, hipMemcpyDeviceToHost, c->stream));
-      PQ_HIP(hipMemcpyAsync(tgt_idx, d_ti, rows * 8, hipMemcpyDeviceToHost, c->stream));
+      PQ_TRY(download(c, src_idx, d_si, rows));
+      PQ_TRY(download(c, tgt_idx, d_ti, rows));
     }
     PQ_HIP(hipStreamSynchronize(c->stream));
   }

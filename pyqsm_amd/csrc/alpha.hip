@@ -440,16 +440,6 @@ __global__ __launch_bounds__(256) void k_alpha_edges(int ncell, const int32_t* _
   }
 }
 
-__global__ __launch_bounds__(256) void k_alpha_sort_init(int e, const int32_t* __restrict__ key_src,
-                                                         const int32_t* __restrict__ perm /*may be null*/,
-                                                         uint32_t* __restrict__ keys, int32_t* __restrict__ vals) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= e) return;
-  const int j = perm ? perm[i] : i;
-  keys[i] = uint32_t(key_src[j]);
-  vals[i] = j;
-}
-
 __global__ __launch_bounds__(256) void k_alpha_edge_rows(int e, const int32_t* __restrict__ perm,
                                                          const int32_t* __restrict__ ea,
                                                          const int32_t* __restrict__ eb, int64_t* __restrict__ out) {
@@ -458,15 +448,6 @@ __global__ __launch_bounds__(256) void k_alpha_edge_rows(int e, const int32_t* _
   const int j = perm[i];
   out[2 * size_t(i)] = ea[j];
   out[2 * size_t(i) + 1] = eb[j];
-}
-
-static int bit_length(uint64_t v) {
-  int b = 0;
-  while (v) {
-    ++b;
-    v >>= 1;
-  }
-  return b;
 }
 
 // The live points of a segment the host settles (fewer than three points, or all on one line).
@@ -567,10 +548,9 @@ int pyqsm_alpha_area(const int32_t* ij, int64_t n, const int64_t* seg_start, int
   if (stats) stats[4] = host_merged;
   if (!any) return 0;  // every segment is degenerate: no device work
 
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   int32_t *d_ij, *d_seg_of, *d_cell0, *d_vals, *d_start, *d_flags, *d_lx, *d_ly, *d_lorig, *d_lstart, *d_blk;
   uint32_t* d_keys;
   AlphaSeg* d_segs;
@@ -594,11 +574,10 @@ int pyqsm_alpha_area(const int32_t* ij, int64_t n, const int64_t* seg_start, int
   PQ_TRY(c->arena.get(n_counters, &d_counters));
   unsigned long long *d_est = d_counters, *d_stats = d_counters + 2, *d_cursor = d_counters + 5,
                      *d_acc = d_counters + 6, *d_nb = d_acc + n_seg;
-  PQ_HIP(hipMemcpyAsync(d_ij, ij, size_t(n) * 8, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_seg_of, seg_of.data(), size_t(n) * 4, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_cell0, cell0.data(), (size_t(n_seg) + 1) * 4, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_segs, segs.data(), (size_t(n_seg) + 1) * sizeof(AlphaSeg), hipMemcpyHostToDevice,
-                        c->stream));
+  PQ_TRY(copy_in(c, d_ij, ij, size_t(n) * 2));
+  PQ_TRY(copy_in(c, d_seg_of, seg_of.data(), size_t(n)));
+  PQ_TRY(copy_in(c, d_cell0, cell0.data(), size_t(n_seg) + 1));
+  PQ_TRY(copy_in(c, d_segs, segs.data(), size_t(n_seg) + 1));
   PQ_HIP(hipMemsetAsync(d_counters, 0, n_counters * 8, c->stream));
 
   const int nc = int(ncell);
@@ -614,8 +593,7 @@ int pyqsm_alpha_area(const int32_t* ij, int64_t n, const int64_t* seg_start, int
     hipLaunchKernelGGL(k_alpha_cell_start, dim3(ceil_div(nc + 1, 256)), dim3(256), 0, c->stream, nc,
                        static_cast<const uint32_t*>(d_keys), int(n), d_start);
     PQ_HIP(hipGetLastError());
-    PQ_HIP(hipMemcpyAsync(&n_part, d_start + nc, 4, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipStreamSynchronize(c->stream));  // points of the segments that take part, a host-known number
+    PQ_TRY(fetch(c, &n_part, d_start + nc));  // points of the segments that take part, a host-known number
     hipLaunchKernelGGL(k_alpha_live, dim3(ceil_div(n_part + 1, 256)), dim3(256), 0, c->stream, n_part,
                        static_cast<const int32_t*>(d_vals), static_cast<const uint32_t*>(d_keys),
                        static_cast<const int32_t*>(d_start), d_ij, d_flags);
@@ -638,10 +616,10 @@ int pyqsm_alpha_area(const int32_t* ij, int64_t n, const int64_t* seg_start, int
                        static_cast<const int32_t*>(d_lstart), d_blk);
     PQ_HIP(hipGetLastError());
     PQ_TRY(exclusive_scan_i32(c, d_blk, int64_t(nc) + 1));
-    PQ_HIP(hipMemcpyAsync(&n_blocks, d_blk + nc, 4, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipMemcpyAsync(seg_live.data(), d_seg_live, size_t(n_seg) * 8, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipMemcpyAsync(est, d_est, 16, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipMemcpyAsync(&total_live, d_lstart + nc, 4, hipMemcpyDeviceToHost, c->stream));
+    PQ_TRY(download(c, &n_blocks, d_blk + nc, 1));
+    PQ_TRY(download(c, seg_live.data(), d_seg_live, size_t(n_seg)));
+    PQ_TRY(download(c, est, d_est, 2));
+    PQ_TRY(download(c, &total_live, d_lstart + nc, 1));
     PQ_HIP(hipStreamSynchronize(c->stream));
   }
   for (int64_t s = 0; s < n_seg; ++s)
@@ -676,8 +654,7 @@ int pyqsm_alpha_area(const int32_t* ij, int64_t n, const int64_t* seg_start, int
     PQ_HIP(hipGetLastError());
   }
   std::vector<unsigned long long> host(n_counters);
-  PQ_HIP(hipMemcpyAsync(host.data(), d_counters, n_counters * 8, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, host.data(), d_counters, n_counters));
   int64_t total_edges = 0;
   for (int64_t s = 0; s < n_seg; ++s) {
     twice_area[s] = int64_t(host[6 + size_t(s)]);
@@ -696,39 +673,23 @@ int pyqsm_alpha_area(const int32_t* ij, int64_t n, const int64_t* seg_start, int
   // ascending (a, b): a stable sort by b, then by a. Both indices belong to one segment and segments
   // are index ranges, so the rows are grouped by segment as well.
   const int e = int(total_edges), bits = bit_length(uint64_t(n));
-  uint32_t* d_k;
-  int32_t* d_v;
   int64_t* d_rows;
-  PQ_TRY(c->arena.get(size_t(e), &d_k));
-  PQ_TRY(c->arena.get(size_t(e), &d_v));
   PQ_TRY(c->arena.get(size_t(e) * 2, &d_rows));
   {
     ProfScope ps(c, "alpha_boundary_sort");
-    hipLaunchKernelGGL(k_alpha_sort_init, dim3(ceil_div(e, 256)), dim3(256), 0, c->stream, e,
-                       static_cast<const int32_t*>(d_eb), static_cast<const int32_t*>(nullptr), d_k, d_v);
-    PQ_HIP(hipGetLastError());
-    PQ_TRY(stable_sort_pairs_u32(c, &d_k, &d_v, e, bits));
-    uint32_t* d_k2;
-    int32_t* d_v2;
-    PQ_TRY(c->arena.get(size_t(e), &d_k2));
-    PQ_TRY(c->arena.get(size_t(e), &d_v2));
-    hipLaunchKernelGGL(k_alpha_sort_init, dim3(ceil_div(e, 256)), dim3(256), 0, c->stream, e,
-                       static_cast<const int32_t*>(d_ea), static_cast<const int32_t*>(d_v), d_k2, d_v2);
-    PQ_HIP(hipGetLastError());
-    PQ_TRY(stable_sort_pairs_u32(c, &d_k2, &d_v2, e, bits));
+    int32_t* perm = nullptr;
+    PQ_TRY(refine_order_by_key(c, e, d_eb, &perm, bits));
+    PQ_TRY(refine_order_by_key(c, e, d_ea, &perm, bits));
     hipLaunchKernelGGL(k_alpha_edge_rows, dim3(ceil_div(e, 256)), dim3(256), 0, c->stream, e,
-                       static_cast<const int32_t*>(d_v2), static_cast<const int32_t*>(d_ea),
+                       static_cast<const int32_t*>(perm), static_cast<const int32_t*>(d_ea),
                        static_cast<const int32_t*>(d_eb), d_rows);
     PQ_HIP(hipGetLastError());
   }
-  int64_t* rows = static_cast<int64_t*>(out_alloc(size_t(e) * 16));
+  OutBufs out;
+  int64_t* rows = out.get<int64_t>(size_t(e) * 2);
   if (!rows) return fail(PYQSM_ENOMEM, "pyqsm_alpha_area: no host memory for %d boundary edges", e);
-  hipError_t err = hipMemcpyAsync(rows, d_rows, size_t(e) * 16, hipMemcpyDeviceToHost, c->stream);
-  if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
-  if (err != hipSuccess) {
-    out_free(rows);
-    return fail(PYQSM_EHIP, "pyqsm_alpha_area: copying the boundary edges failed: %s", hipGetErrorString(err));
-  }
+  PQ_TRY(fetch(c, rows, d_rows, size_t(e) * 2));
+  out.kept = true;
   *edges = rows;
   return 0;
 }

@@ -956,14 +956,12 @@ static int alloc_vectors(Ctx* c, AmgLevel& L, bool coarse, int nnz) {
 static int coarse_inverse(Ctx* c, const AmgLevel& L, double** d_inv) {
   const int n = L.n;
   std::vector<int32_t> ip(size_t(n) + 1);
-  PQ_HIP(hipMemcpyAsync(ip.data(), L.A.indptr, (size_t(n) + 1) * 4, hipMemcpyDeviceToHost,
-                        c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, ip.data(), L.A.indptr, size_t(n) + 1));
   const int nnz = ip[size_t(n)];
   std::vector<int32_t> ix(size_t(nnz) + 1);
   std::vector<double> va(size_t(nnz) + 1);
-  PQ_HIP(hipMemcpyAsync(ix.data(), L.A.indices, size_t(nnz) * 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipMemcpyAsync(va.data(), L.A.vals, size_t(nnz) * 8, hipMemcpyDeviceToHost, c->stream));
+  PQ_TRY(download(c, ix.data(), L.A.indices, size_t(nnz)));
+  PQ_TRY(download(c, va.data(), L.A.vals, size_t(nnz)));
   PQ_HIP(hipStreamSynchronize(c->stream));
   std::vector<double> A(size_t(n) * n, 0.0), G(size_t(n) * n, 0.0), inv(size_t(n) * n, 0.0);
   for (int i = 0; i < n; ++i)
@@ -999,8 +997,7 @@ static int coarse_inverse(Ctx* c, const AmgLevel& L, double** d_inv) {
   // consecutive i
   for (int i = 0; i < n; ++i)
     for (int j = 0; j < n; ++j) A[size_t(j) * n + i] = inv[size_t(i) * n + j];
-  PQ_TRY(c->arena.get(size_t(n) * n, d_inv));
-  PQ_HIP(hipMemcpyAsync(*d_inv, A.data(), size_t(n) * n * 8, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(upload(c, A.data(), size_t(n) * n, d_inv));
   PQ_HIP(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -1031,8 +1028,7 @@ static int coarse_inverse_device(Ctx* c, const AmgLevel& L, double** d_inv, int*
   }
   PQ_HIP(hipGetLastError());
   int32_t bad = 0;
-  PQ_HIP(hipMemcpyAsync(&bad, d_flag, 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, &bad, d_flag));
   if (bad) return fail(PYQSM_EINVAL, "multigrid: coarsest matrix is not positive definite");
   *d_inv = A;
   *ld_out = ld;
@@ -1073,8 +1069,7 @@ static int aggregate(Ctx* c, AmgLevel& F, int32_t* d_counter, int* nc_out) {
       hipLaunchKernelGGL(k_mis_update, g, blk, 0, c->stream, n, t2, state, key, left + round, prev);
     }
     int32_t open = 0;
-    PQ_HIP(hipMemcpyAsync(&open, left + (round - 1), 4, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipStreamSynchronize(c->stream));
+    PQ_TRY(fetch(c, &open, left + (round - 1)));
     if (open == 0) break;
     if (round >= kMisRounds) return fail(PYQSM_EHIP, "multigrid: independent-set selection did not finish");
   }
@@ -1082,8 +1077,7 @@ static int aggregate(Ctx* c, AmgLevel& F, int32_t* d_counter, int* nc_out) {
   hipLaunchKernelGGL(k_root_flags, g, blk, 0, c->stream, n, state, flags);
   PQ_TRY(exclusive_scan_i32(c, flags, int64_t(n) + 1));
   int32_t nc = 0;
-  PQ_HIP(hipMemcpyAsync(&nc, flags + n, 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, &nc, flags + n));
   *nc_out = nc;
   if (nc <= 0) return 0;
   int32_t* cursor;

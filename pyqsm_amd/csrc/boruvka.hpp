@@ -200,8 +200,7 @@ static int boruvka_forest(Ctx* c, const char* what, int64_t n, int64_t ne, P pol
                          static_cast<const unsigned long long*>(bw), static_cast<const unsigned long long*>(be), hk,
                          ctl);
       PQ_HIP(hipGetLastError());
-      PQ_HIP(hipMemcpyAsync(h, ctl, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-      PQ_HIP(hipStreamSynchronize(c->stream));
+      PQ_TRY(fetch(c, h, ctl, kBvCtlWords));
     }
     if (h[kBvHooks] == 0) return 0;
     if (round >= kBvMaxRounds) return fail(PYQSM_EHIP, "%s: components left after %d rounds", what, round);
@@ -211,8 +210,7 @@ static int boruvka_forest(Ctx* c, const char* what, int64_t n, int64_t ne, P pol
       hipLaunchKernelGGL(k_bv_jump<P>, dim3(pb), dim3(256), 0, c->stream, N, static_cast<const uint32_t*>(lab), hk,
                          ctl);
       PQ_HIP(hipGetLastError());
-      PQ_HIP(hipMemcpyAsync(h, ctl, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-      PQ_HIP(hipStreamSynchronize(c->stream));
+      PQ_TRY(fetch(c, h, ctl, kBvCtlWords));
       if (!h[kBvAgain]) break;
       if (launch >= kBvMaxRelaunch) return fail(PYQSM_EHIP, "%s: pointer jumping did not settle", what);
       PQ_HIP(hipMemsetAsync(ctl + kBvAgain, 0, 4, c->stream));

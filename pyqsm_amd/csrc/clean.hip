@@ -368,8 +368,7 @@ int voxel_keys_and_sort(Ctx* c, const double* xyz, int64_t n, double size, Voxel
     PQ_TRY(exclusive_scan_i32(c, head, n + 1));
     PQ_TRY(exclusive_scan_i32(c, first, n + 1));
     int32_t m = 0;
-    PQ_HIP(hipMemcpyAsync(&m, head + n, 4, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipStreamSynchronize(c->stream));
+    PQ_TRY(fetch(c, &m, head + n));
     v->m = m;
     PQ_TRY(c->arena.get(size_t(m) + 1, &v->offs));
     PQ_TRY(c->arena.get(size_t(m), &v->row_of));
@@ -474,14 +473,11 @@ int pyqsm_voxel_down_sample(const double* xyz, int64_t n, const double* colors, 
     if (offsets) offsets[0] = 0;
     return 0;
   }
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
+  Call call(c);
   double *d_xyz, *d_rgb = nullptr;
-  PQ_TRY(c->arena.get(size_t(n) * 3, &d_xyz));
-  PQ_HIP(hipMemcpyAsync(d_xyz, xyz, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(upload(c, xyz, size_t(n) * 3, &d_xyz));
   if (colors) {
-    PQ_TRY(c->arena.get(size_t(n) * 3, &d_rgb));
-    PQ_HIP(hipMemcpyAsync(d_rgb, colors, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+    PQ_TRY(upload(c, colors, size_t(n) * 3, &d_rgb));
   }
   VoxelDev v;
   PQ_TRY(voxel_keys_and_sort(c, d_xyz, n, voxel_size, &v));
@@ -504,31 +500,19 @@ int pyqsm_voxel_down_sample(const double* xyz, int64_t n, const double* colors, 
       PQ_HIP(hipGetLastError());
     }
   }
-  double* h_xyz = static_cast<double*>(out_alloc(size_t(M) * 24));
-  double* h_rgb = colors ? static_cast<double*>(out_alloc(size_t(M) * 24)) : nullptr;
-  if (!h_xyz || (colors && !h_rgb)) {
-    out_free(h_xyz);
-    out_free(h_rgb);
-    return fail(PYQSM_ENOMEM, "host allocation failed");
+  OutBufs out;
+  double* h_xyz = out.get<double>(size_t(M) * 3);
+  double* h_rgb = colors ? out.get<double>(size_t(M) * 3) : nullptr;
+  if (!h_xyz || (colors && !h_rgb)) return fail(PYQSM_ENOMEM, "host allocation failed");
+  PQ_TRY(download(c, h_xyz, v.xyz, size_t(M) * 3));
+  if (colors) PQ_TRY(download(c, h_rgb, v.rgb, size_t(M) * 3));
+  if (inverse) PQ_TRY(download(c, inverse, d_inv, size_t(n)));
+  if (offsets) {
+    PQ_TRY(download(c, offsets, d_offsets, size_t(M) + 1));
+    PQ_TRY(download(c, members, d_members, size_t(n)));
   }
-  int rc = 0;
-  auto copy = [&]() -> int {
-    PQ_HIP(hipMemcpyAsync(h_xyz, v.xyz, size_t(M) * 24, hipMemcpyDeviceToHost, c->stream));
-    if (colors) PQ_HIP(hipMemcpyAsync(h_rgb, v.rgb, size_t(M) * 24, hipMemcpyDeviceToHost, c->stream));
-    if (inverse) PQ_HIP(hipMemcpyAsync(inverse, d_inv, size_t(n) * 8, hipMemcpyDeviceToHost, c->stream));
-    if (offsets) {
-      PQ_HIP(hipMemcpyAsync(offsets, d_offsets, (size_t(M) + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-      PQ_HIP(hipMemcpyAsync(members, d_members, size_t(n) * 8, hipMemcpyDeviceToHost, c->stream));
-    }
-    PQ_HIP(hipStreamSynchronize(c->stream));
-    return 0;
-  };
-  rc = copy();
-  if (rc != 0) {
-    out_free(h_xyz);
-    out_free(h_rgb);
-    return rc;
-  }
+  PQ_HIP(hipStreamSynchronize(c->stream));
+  out.kept = true;
   *m_out = M;
   *out_xyz = h_xyz;
   if (colors) *out_colors = h_rgb;
@@ -547,24 +531,22 @@ int pyqsm_stat_outlier(const double* xyz, int64_t n, int32_t nb_neighbors, doubl
   Ctx* c = ctx_for(device);
   if (!c) return PYQSM_ENODEV;
   if (n == 0) return 0;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
+  Call call(c);
   double *d_xyz, *d_avg = nullptr, *d_stats;
   int64_t* d_keep;
   PQ_TRY(c->arena.get(size_t(n) * 3, &d_xyz));
   PQ_TRY(c->arena.get(size_t(n), &d_keep));
   PQ_TRY(c->arena.get(4, &d_stats));
   if (avg) PQ_TRY(c->arena.get(size_t(n), &d_avg));
-  PQ_HIP(hipMemcpyAsync(d_xyz, xyz, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_xyz, xyz, size_t(n) * 3));
   int32_t* pos;
   PQ_TRY(stat_device(c, d_xyz, n, nb_neighbors, std_ratio, d_avg, d_stats, d_keep, nullptr, &pos));
   int32_t cnt = 0;
-  PQ_HIP(hipMemcpyAsync(&cnt, pos + n, 4, hipMemcpyDeviceToHost, c->stream));
-  if (avg) PQ_HIP(hipMemcpyAsync(avg, d_avg, size_t(n) * 8, hipMemcpyDeviceToHost, c->stream));
-  if (stats) PQ_HIP(hipMemcpyAsync(stats, d_stats, 24, hipMemcpyDeviceToHost, c->stream));
+  PQ_TRY(download(c, &cnt, pos + n, 1));
+  if (avg) PQ_TRY(download(c, avg, d_avg, size_t(n)));
+  if (stats) PQ_TRY(download(c, stats, d_stats, 3));
   PQ_HIP(hipStreamSynchronize(c->stream));
-  PQ_HIP(hipMemcpyAsync(keep, d_keep, size_t(cnt) * 8, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, keep, d_keep, size_t(cnt)));
   *n_keep = cnt;
   return 0;
 }
@@ -582,16 +564,14 @@ int pyqsm_clean_cloud(const double* xyz, int64_t n, double voxel_size, double ne
   if (iters > 0 && std::ldexp(neighbors, iters - 1) >= 2147483648.0)
     return fail(PYQSM_ERANGE, "neighbors doubled %d times exceeds int32", iters - 1);
   if (n > 0 && !xyz) return fail(PYQSM_EINVAL, "pyqsm_clean_cloud: NULL pointer");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   const double* cur = nullptr;
   int64_t m = n;
   if (n > 0) {
     double* d_xyz;
-    PQ_TRY(c->arena.get(size_t(n) * 3, &d_xyz));
-    PQ_HIP(hipMemcpyAsync(d_xyz, xyz, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+    PQ_TRY(upload(c, xyz, size_t(n) * 3, &d_xyz));
     cur = d_xyz;
     if (voxel_size > 0) {
       VoxelDev v;
@@ -611,8 +591,7 @@ int pyqsm_clean_cloud(const double* xyz, int64_t n, double voxel_size, double ne
       int32_t* pos;
       PQ_TRY(stat_device(c, cur, m, int32_t(nb), r, nullptr, stats, nullptr, next, &pos));
       int32_t cnt = 0;
-      PQ_HIP(hipMemcpyAsync(&cnt, pos + m, 4, hipMemcpyDeviceToHost, c->stream));
-      PQ_HIP(hipStreamSynchronize(c->stream));
+      PQ_TRY(fetch(c, &cnt, pos + m));
       c->arena.rewind(mk);
       cur = next;
       m = cnt;
@@ -620,16 +599,11 @@ int pyqsm_clean_cloud(const double* xyz, int64_t n, double voxel_size, double ne
       r = r / 1.5;
     }
   }
-  double* h = static_cast<double*>(out_alloc(size_t(m) * 24));
+  OutBufs out;
+  double* h = out.get<double>(size_t(m) * 3);
   if (!h) return fail(PYQSM_ENOMEM, "host allocation failed");
-  if (m > 0) {
-    const hipError_t e1 = hipMemcpyAsync(h, cur, size_t(m) * 24, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t e2 = e1 == hipSuccess ? hipStreamSynchronize(c->stream) : e1;
-    if (e2 != hipSuccess) {
-      out_free(h);
-      return fail(PYQSM_EHIP, "pyqsm_clean_cloud: copy-back failed: %s", hipGetErrorString(e2));
-    }
-  }
+  if (m > 0) PQ_TRY(fetch(c, h, cur, size_t(m) * 3));
+  out.kept = true;
   *m_out = m;
   *out_xyz = h;
   return 0;

@@ -133,6 +133,80 @@ struct Ctx {
 // message when the device does not exist.
 Ctx* ctx_for(int device);
 
+// Typed copies on the context's stream: the element type is the device pointer's, the host pointer
+// has to convert to it, and the byte count follows from it. A count of zero enqueues nothing, so
+// (nullptr, 0) is a valid host side.
+template <typename T>
+struct Elem {
+  using type = T;
+};
+template <typename T>
+int copy_in(Ctx* c, T* d, const typename Elem<T>::type* h, size_t count) {
+  if (count) PQ_HIP(hipMemcpyAsync(d, h, count * sizeof(T), hipMemcpyHostToDevice, c->stream));
+  return 0;
+}
+template <typename T>
+int download(Ctx* c, typename Elem<T>::type* h, const T* d, size_t count) {
+  if (count) PQ_HIP(hipMemcpyAsync(h, d, count * sizeof(T), hipMemcpyDeviceToHost, c->stream));
+  return 0;
+}
+inline int stream_sync(Ctx* c) {
+  PQ_HIP(hipStreamSynchronize(c->stream));
+  return 0;
+}
+// arena scratch of `count` elements filled from the host
+template <typename T>
+int upload(Ctx* c, const typename Elem<T>::type* h, size_t count, T** d) {
+  PQ_TRY(c->arena.get(count, d));
+  return copy_in(c, *d, h, count);
+}
+// download, then wait for it: the read-back of a count that sizes what comes next
+template <typename T>
+int fetch(Ctx* c, typename Elem<T>::type* h, const T* d, size_t count = 1) {
+  PQ_TRY(download(c, h, d, count));
+  return stream_sync(c);
+}
+
+// One C-ABI call on a device: holds the context's lock for its lifetime and, unless told to keep
+// it, resets the scratch arena, so the arena is only ever touched under the lock. c == nullptr
+// (device form only): ctx_for failed and has set the message; the caller returns PYQSM_ENODEV.
+// The Ctx* form is for entry points that return early between ctx_for and the lock.
+class Call {
+ public:
+  enum ArenaUse { kResetArena, kKeepArena };  // kKeepArena: for a call that takes no scratch
+  explicit Call(int device, ArenaUse use = kResetArena) : Call(ctx_for(device), use) {}
+  explicit Call(Ctx* ctx, ArenaUse use = kResetArena) : c(ctx) {
+    if (!c) return;
+    lk_ = std::unique_lock<std::mutex>(c->mu);
+    if (use == kResetArena) c->arena.reset();
+  }
+  Ctx* const c;
+
+ private:
+  std::unique_lock<std::mutex> lk_;
+};
+
+// Host buffers handed to the caller (released by the caller with pyqsm_free): released again here
+// unless `kept` is set, which an entry point does in one place, at the end, where it writes the
+// caller's out-pointers.
+struct OutBufs {
+  std::vector<void*> p;
+  bool kept = false;
+  OutBufs() = default;
+  OutBufs(const OutBufs&) = delete;
+  OutBufs& operator=(const OutBufs&) = delete;
+  ~OutBufs() {
+    if (!kept)
+      for (void* q : p) out_free(q);
+  }
+  template <typename T>
+  T* get(size_t count) {
+    void* q = out_alloc((count ? count : 1) * sizeof(T));
+    if (q) p.push_back(q);
+    return static_cast<T*>(q);
+  }
+};
+
 // RAII bracket: records a start/stop event pair on the stream under `name`
 // when profiling is enabled and `name` is not null; otherwise does nothing.
 class ProfScope {
@@ -248,5 +322,12 @@ int compact_flagged(Ctx* c, int32_t* flags, int64_t n, int64_t* idx, const int64
 // without global atomics, so the order is reproducible). *keys / *vals are the inputs and, on
 // return, point at the sorted arrays (the inputs themselves or arena buffers of the same size).
 int stable_sort_pairs_u32(Ctx* c, uint32_t** keys, int32_t** vals, int64_t n, int bits);
+
+// *perm [n] (null: the identity) refined by a stable sort on the low `bits` bits of key_src[perm[i]]
+// (scan.hip); on return *perm is an arena array. Rows are ordered by several keys by calling this once
+// per key, least significant key first.
+int refine_order_by_key(Ctx* c, int64_t n, const int32_t* key_src, int32_t** perm, int bits);
+// The bits needed to write v: 0 for 0, 3 for 4 to 7.
+int bit_length(uint64_t v);
 
 }  // namespace pyqsm

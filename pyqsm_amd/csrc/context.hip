@@ -540,18 +540,18 @@ void pyqsm_free(void* p) { out_free(p); }
 void* pyqsm_host_alloc(size_t bytes) { return out_alloc(bytes); }
 
 int pyqsm_prof_enable(int device, int on) {
-  Ctx* c = ctx_for(device);
+  Call call(device, Call::kKeepArena);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
   c->prof = on < 0 ? 0 : on;
   if (c->prof && c->stamp_chunks.empty()) (void)stamp_chunk_add(c, 0);  // not inside a timed loop
   return 0;
 }
 
 int pyqsm_prof_reset(int device) {
-  Ctx* c = ctx_for(device);
+  Call call(device, Call::kKeepArena);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
   drain_timers(c);
   c->timers.clear();
   return 0;
@@ -561,7 +561,7 @@ int pyqsm_prof_get(int device, const char* name, double* total_ms, int64_t* laun
   Ctx* c = ctx_for(device);
   if (!c) return PYQSM_ENODEV;
   if (!name) return fail(PYQSM_EINVAL, "pyqsm_prof_get: name is NULL");
-  std::lock_guard<std::mutex> lk(c->mu);
+  Call call(c, Call::kKeepArena);
   drain_timers(c);
   auto it = c->timers.find(name);
   if (total_ms) *total_ms = it == c->timers.end() ? 0.0 : it->second.ms;

@@ -1477,8 +1477,7 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
     }
     if (d_tests) {  // profiling level 2 only: read the counter back (synchronises)
       unsigned long long h[256];
-      PQ_HIP(hipMemcpyAsync(h, d_tests, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-      PQ_HIP(hipStreamSynchronize(c->stream));
+      PQ_TRY(fetch(c, h, d_tests, 256));
       unsigned long long tot = 0;
       for (unsigned long long v : h) tot += v;
       c->timers["core_pair_tests"].launches += int64_t(tot) * 64;  // lane-tests executed
@@ -1492,8 +1491,7 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
     PQ_HIP(hipGetLastError());
     if (getenv("PYQSM_DBSCAN_TRACE")) {  // how many points did the tiled pass hand on?
       int32_t h[kRestSegs];
-      PQ_HIP(hipMemcpyAsync(h, rest_segs, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-      PQ_HIP(hipStreamSynchronize(c->stream));
+      PQ_TRY(fetch(c, h, rest_segs, kRestSegs));
       long long tot = 0;
       for (int32_t v : h) tot += v;
       fprintf(stderr, "core pass: %lld stragglers\n", tot);
@@ -1552,8 +1550,7 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
         std::vector<int32_t> hp, root_of;
         std::vector<int4> hl;
         const auto snapshot = [&](std::vector<int64_t>* hist) -> int {
-          PQ_HIP(hipMemcpyAsync(&tm, list_cnt, 4, hipMemcpyDeviceToHost, c->stream));
-          PQ_HIP(hipStreamSynchronize(c->stream));
+          PQ_TRY(fetch(c, &tm, list_cnt));
           hp.assign(static_cast<size_t>(n), 0);
           hl.assign(static_cast<size_t>(tm), make_int4(0, 0, 0, 0));
           PQ_HIP(hipMemcpy(hp.data(), parent, size_t(n) * 4, hipMemcpyDeviceToHost));
@@ -1638,8 +1635,7 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
         }
         if (trace) {
           unsigned long long h = 0;
-          PQ_HIP(hipMemcpyAsync(&h, d_seams, 8, hipMemcpyDeviceToHost, c->stream));
-          PQ_HIP(hipStreamSynchronize(c->stream));
+          PQ_TRY(fetch(c, &h, d_seams));
           fprintf(stderr, "seam union: %llu sub-cells took the 62-offset path\n", h);
         }
         // the pre-roots the seams hooked hand their smallest index on; the others are the components
@@ -1678,8 +1674,7 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
     PQ_HIP(hipGetLastError());
     if (getenv("PYQSM_DBSCAN_TRACE")) {
       int32_t h = 0;
-      PQ_HIP(hipMemcpyAsync(&h, list_cnt + 3, 4, hipMemcpyDeviceToHost, c->stream));
-      PQ_HIP(hipStreamSynchronize(c->stream));
+      PQ_TRY(fetch(c, &h, list_cnt + 3));
       fprintf(stderr, "label pass: %d non-core points listed\n", h);
     }
   }
@@ -1798,14 +1793,12 @@ static int dbscan_device(Ctx* c, const double* xyz, int64_t n, double eps, int32
     PQ_TRY(c->arena.get(size_t(entries), &d_begin));
     read_directory(c, g, pl.ncell, d_begin);
     PQ_HIP(hipGetLastError());
-    PQ_HIP(hipMemcpyAsync(readout->begin_host, d_begin, size_t(entries) * 4, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipStreamSynchronize(c->stream));
+    PQ_TRY(fetch(c, readout->begin_host, d_begin, size_t(entries)));
     return 0;
   }
   if (n_clusters) {
     int32_t h = 0;
-    PQ_HIP(hipMemcpyAsync(&h, count, 4, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipStreamSynchronize(c->stream));
+    PQ_TRY(fetch(c, &h, count));
     *n_clusters = h;
   }
   return 0;
@@ -1823,10 +1816,9 @@ int pyqsm_dbscan_dev_ex(const double* xyz_dev, int64_t n, double eps, int32_t mi
   PQ_API_RANGE("pyqsm_dbscan_dev");
   if (n < 0) return fail(PYQSM_EINVAL, "negative size");
   if (n > 0 && (!xyz_dev || !labels_dev)) return fail(PYQSM_EINVAL, "pyqsm_dbscan_dev: NULL pointer");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   StampScope ps(c, "dbscan_total");
   return dbscan_device(c, xyz_dev, n, eps, min_pts, radius_inclusive != 0, labels_dev, is_core_dev,
                        n_clusters);
@@ -1849,20 +1841,19 @@ int pyqsm_dbscan_ex(const double* xyz, int64_t n, double eps, int32_t min_pts, i
   if (n < 0) return fail(PYQSM_EINVAL, "negative size");
   if (n == 0) return 0;
   if (!xyz || !labels) return fail(PYQSM_EINVAL, "pyqsm_dbscan: NULL pointer");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   double* d_xyz;
   int64_t* d_lab;
   uint8_t* d_core;
   PQ_TRY(c->arena.get(size_t(n) * 3, &d_xyz));
   PQ_TRY(c->arena.get(size_t(n), &d_lab));
   PQ_TRY(c->arena.get(size_t(n), &d_core));
-  PQ_HIP(hipMemcpyAsync(d_xyz, xyz, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_xyz, xyz, size_t(n) * 3));
   PQ_TRY(dbscan_device(c, d_xyz, n, eps, min_pts, radius_inclusive != 0, d_lab, d_core, nullptr));
-  PQ_HIP(hipMemcpyAsync(labels, d_lab, size_t(n) * 8, hipMemcpyDeviceToHost, c->stream));
-  if (is_core) PQ_HIP(hipMemcpyAsync(is_core, d_core, size_t(n), hipMemcpyDeviceToHost, c->stream));
+  PQ_TRY(download(c, labels, d_lab, size_t(n)));
+  if (is_core) PQ_TRY(download(c, is_core, d_core, size_t(n)));
   PQ_HIP(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -1872,13 +1863,11 @@ int pyqsm_octant_directory(const double* xyz, int64_t n, double eps, int32_t* di
   PQ_API_RANGE("pyqsm_octant_directory");
   if (n <= 0) return fail(PYQSM_EINVAL, "pyqsm_octant_directory: empty cloud");
   if (!xyz || !dims_out || !begin_out) return fail(PYQSM_EINVAL, "pyqsm_octant_directory: NULL pointer");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   double* d_xyz;
-  PQ_TRY(c->arena.get(size_t(n) * 3, &d_xyz));
-  PQ_HIP(hipMemcpyAsync(d_xyz, xyz, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(upload(c, xyz, size_t(n) * 3, &d_xyz));
   DirReadout ro{cap, begin_out, {0, 0, 0}};
   PQ_TRY(dbscan_device(c, d_xyz, n, eps, 1, true, nullptr, nullptr, nullptr, &ro));
   for (int a = 0; a < 3; ++a) dims_out[a] = ro.dims[a];

@@ -357,8 +357,7 @@ static int query_knn_device(Ctx* c, const double* d_src, int64_t n, const double
     });
     PQ_HIP(hipGetLastError());
     int32_t nn = 0;
-    PQ_HIP(hipMemcpyAsync(&nn, n_next, 4, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipStreamSynchronize(c->stream));
+    PQ_TRY(fetch(c, &nn, n_next));
     c->arena.rewind(mk);
     std::swap(list, next);
     left = nn;
@@ -394,10 +393,9 @@ int pyqsm_geometric_features(const double* xyz, int64_t n, double radius, int32_
   }
   if (n > 0 && (!xyz || !out)) return fail(PYQSM_EINVAL, "pyqsm_geometric_features: NULL pointer");
   if (n == 0) return 0;
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   const int N = int(n);
   double *d_xyz, *cov, *d_out;
   int32_t *used, *cnt;
@@ -406,7 +404,7 @@ int pyqsm_geometric_features(const double* xyz, int64_t n, double radius, int32_
   PQ_TRY(c->arena.get(size_t(n) * n_features, &d_out));
   PQ_TRY(c->arena.get(size_t(n), &used));
   PQ_TRY(c->arena.get(size_t(n), &cnt));
-  PQ_HIP(hipMemcpyAsync(d_xyz, xyz, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_xyz, xyz, size_t(n) * 3));
   DevGrid g;
   double box[6];
   {
@@ -440,8 +438,8 @@ int pyqsm_geometric_features(const double* xyz, int64_t n, double radius, int32_
                        static_cast<const double*>(cov), static_cast<const int32_t*>(used), fl, d_out);
     PQ_HIP(hipGetLastError());
   }
-  PQ_HIP(hipMemcpyAsync(out, d_out, size_t(n) * n_features * 8, hipMemcpyDeviceToHost, c->stream));
-  if (counts) PQ_HIP(hipMemcpyAsync(counts, cnt, size_t(n) * 4, hipMemcpyDeviceToHost, c->stream));
+  PQ_TRY(download(c, out, d_out, size_t(n) * n_features));
+  if (counts) PQ_TRY(download(c, counts, cnt, size_t(n)));
   PQ_HIP(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -464,23 +462,21 @@ int pyqsm_smooth_values(const double* xyz, int64_t n, const double* qry, int64_t
     for (int64_t t = 0; t < 3 * m; ++t)
       if (!std::isfinite(qry[t])) return fail(PYQSM_EINVAL, "query coordinates must be finite");
   if (m == 0) return 0;
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   double *d_xyz, *d_qry = nullptr, *d_d2 = nullptr;
   int32_t* d_idx;
   PQ_TRY(c->arena.get(size_t(n) * 3, &d_xyz));
   PQ_TRY(c->arena.get(size_t(m) * k, &d_idx));
-  PQ_HIP(hipMemcpyAsync(d_xyz, xyz, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_xyz, xyz, size_t(n) * 3));
   {
     ProfScope ps(c, "smooth_knn");
     if (!qry) {
       PQ_TRY(c->arena.get(size_t(n) * k, &d_d2));
       PQ_TRY(knn_device(c, d_xyz, n, k, 0, d_idx, d_d2));
     } else {
-      PQ_TRY(c->arena.get(size_t(m) * 3, &d_qry));
-      PQ_HIP(hipMemcpyAsync(d_qry, qry, size_t(m) * 24, hipMemcpyHostToDevice, c->stream));
+      PQ_TRY(upload(c, qry, size_t(m) * 3, &d_qry));
       PQ_TRY(query_knn_device(c, d_xyz, n, d_qry, m, k, d_idx));
     }
   }
@@ -488,15 +484,15 @@ int pyqsm_smooth_values(const double* xyz, int64_t n, const double* qry, int64_t
     double *d_vals, *d_out;
     PQ_TRY(c->arena.get(size_t(n) * F, &d_vals));
     PQ_TRY(c->arena.get(size_t(m) * F, &d_out));
-    PQ_HIP(hipMemcpyAsync(d_vals, values, size_t(n) * F * 8, hipMemcpyHostToDevice, c->stream));
+    PQ_TRY(copy_in(c, d_vals, values, size_t(n) * F));
     ProfScope ps(c, "smooth_reduce");
     hipLaunchKernelGGL(k_smooth_reduce, dim3(ceil_div(m, 2)), dim3(128), 0, c->stream, int(m),
                        static_cast<const int32_t*>(d_idx), int(k), static_cast<const double*>(d_vals), int(F),
                        int(reducer), d_out);
     PQ_HIP(hipGetLastError());
-    PQ_HIP(hipMemcpyAsync(out, d_out, size_t(m) * F * 8, hipMemcpyDeviceToHost, c->stream));
+    PQ_TRY(download(c, out, d_out, size_t(m) * F));
   }
-  if (idx) PQ_HIP(hipMemcpyAsync(idx, d_idx, size_t(m) * k * 4, hipMemcpyDeviceToHost, c->stream));
+  if (idx) PQ_TRY(download(c, idx, d_idx, size_t(m) * k));
   PQ_HIP(hipStreamSynchronize(c->stream));
   return 0;
 }

@@ -394,10 +394,9 @@ int pyqsm_forest_predict(const void* forest, const float* X, int64_t n, double* 
   if (n < 0) return fail(PYQSM_EINVAL, "negative size");
   if (n > 0 && !X) return fail(PYQSM_EINVAL, "pyqsm_forest_predict: X is NULL");
   if (n == 0 || (!proba && !label && !leaves)) return 0;
-  Ctx* c = ctx_for(f->device);
+  Call call(f->device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   const int T = f->d.T, C = f->d.C, F = f->d.F;
   // rows per chunk: about 256 MB of arena for the rows and everything asked for, whole blocks
   const size_t per_row = size_t(F) * 4 + (proba ? size_t(C) * 8 : 0) + (label ? 4 : 0) + (leaves ? size_t(T) * 4 : 0);
@@ -413,7 +412,7 @@ int pyqsm_forest_predict(const void* forest, const float* X, int64_t n, double* 
   if (leaves) PQ_TRY(c->arena.get(size_t(chunk) * T, &d_leaves));
   for (int64_t r0 = 0; r0 < n; r0 += chunk) {
     const int64_t m = std::min(chunk, n - r0);
-    PQ_HIP(hipMemcpyAsync(d_X, X + size_t(r0) * F, size_t(m) * F * 4, hipMemcpyHostToDevice, c->stream));
+    PQ_TRY(copy_in(c, d_X, X + size_t(r0) * F, size_t(m) * F));
     {
       ProfScope ps(c, "forest_walk");
       int rc;
@@ -424,9 +423,9 @@ int pyqsm_forest_predict(const void* forest, const float* X, int64_t n, double* 
       PQ_TRY(rc);
       PQ_HIP(hipGetLastError());
     }
-    if (proba) PQ_HIP(hipMemcpyAsync(proba + size_t(r0) * C, d_proba, size_t(m) * C * 8, hipMemcpyDeviceToHost, c->stream));
-    if (label) PQ_HIP(hipMemcpyAsync(label + size_t(r0), d_label, size_t(m) * 4, hipMemcpyDeviceToHost, c->stream));
-    if (leaves) PQ_HIP(hipMemcpyAsync(leaves + size_t(r0) * T, d_leaves, size_t(m) * T * 4, hipMemcpyDeviceToHost, c->stream));
+    if (proba) PQ_TRY(download(c, proba + size_t(r0) * C, d_proba, size_t(m) * C));
+    if (label) PQ_TRY(download(c, label + size_t(r0), d_label, size_t(m)));
+    if (leaves) PQ_TRY(download(c, leaves + size_t(r0) * T, d_leaves, size_t(m) * T));
   }
   PQ_HIP(hipStreamSynchronize(c->stream));
   return 0;

@@ -894,8 +894,7 @@ static int fps_pruned(Ctx* c, const double* d_xyz, int N, int S, int start_index
   PQ_HIP(hipGetLastError());
   PQ_TRY(exclusive_scan_i32(c, nbk, int64_t(ncell) + 1));
   int32_t nb = 0;
-  PQ_HIP(hipMemcpyAsync(&nb, nbk + ncell, 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, &nb, nbk + ncell));
   if (nb <= 0) return 0;
   static constexpr int kMaxBlocks = 1024;
   Far *va, *vb, *pa, *pb;
@@ -919,8 +918,7 @@ static int fps_pruned(Ctx* c, const double* d_xyz, int N, int S, int start_index
   for (int s = 0; s < S; ++s) {
     if (!late && s > 0 && s % kPruneLook == 0) {
       double D = 0.0;
-      PQ_HIP(hipMemcpyAsync(&D, dlog + (s - 1), 8, hipMemcpyDeviceToHost, c->stream));
-      PQ_HIP(hipStreamSynchronize(c->stream));
+      PQ_TRY(fetch(c, &D, dlog + (s - 1)));
       if (std::sqrt(D) < 3.0 * g.cell) late = true;
       // from here on a round touches a dozen small buckets: all the remaining rounds in one launch of one
       // workgroup (k_fps_tail; PYQSM_FPS_TAIL=0 keeps a launch per round). Measured, 1 M points -> 100 k
@@ -976,8 +974,7 @@ static int fps_pruned(Ctx* c, const double* d_xyz, int N, int S, int start_index
         PQ_HIP(hipGetLastError());
         if (d_dbg) {
           unsigned long long h[8];
-          PQ_HIP(hipMemcpyAsync(h, d_dbg, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-          PQ_HIP(hipStreamSynchronize(c->stream));
+          PQ_TRY(fetch(c, h, d_dbg, 8));
           const double r = double(S - s);
           fprintf(stderr, "fps tail per round (100 MHz ticks): argmax %.1f, group test %.1f, bucket gather %.1f, update %.1f, "
                   "fold %.1f; groups in reach %.2f, buckets updated %.2f; shader clock %.0f MHz\n", h[0] / r, h[1] / r,
@@ -1032,10 +1029,9 @@ int pyqsm_fps(const double* xyz, int64_t n, int64_t num_samples, int64_t start_i
   if (start_index < 0 || start_index >= n) return fail(PYQSM_EINVAL, "start_index out of range");
   if (!xyz || !out_idx) return fail(PYQSM_EINVAL, "pyqsm_fps: NULL pointer");
   if (n > 0x7FFFFF00LL) return fail(PYQSM_ERANGE, "more than 2^31 points per call");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   const int N = int(n), S = int(num_samples);
   double *d_xyz, *d_x, *d_y, *d_z, *d_dist;
   Best *d_pa, *d_pb;
@@ -1048,7 +1044,7 @@ int pyqsm_fps(const double* xyz, int64_t n, int64_t num_samples, int64_t start_i
   PQ_TRY(c->arena.get(size_t(kFpsBlocks), &d_pa));
   PQ_TRY(c->arena.get(size_t(kFpsBlocks), &d_pb));
   PQ_TRY(c->arena.get(size_t(S), &d_out));
-  PQ_HIP(hipMemcpyAsync(d_xyz, xyz, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_xyz, xyz, size_t(n) * 3));
   hipLaunchKernelGGL(k_fps_split, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, N, d_xyz, d_x,
                      d_y, d_z, d_dist);
   bool pruned = false;
@@ -1066,8 +1062,7 @@ int pyqsm_fps(const double* xyz, int64_t n, int64_t num_samples, int64_t start_i
     }
     PQ_HIP(hipGetLastError());
   }
-  PQ_HIP(hipMemcpyAsync(out_idx, d_out, size_t(S) * 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, out_idx, d_out, size_t(S)));
   return 0;
 }
 

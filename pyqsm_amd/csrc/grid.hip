@@ -242,8 +242,7 @@ int probe_occupancy(Ctx* c, const double* xyz, int64_t n, const double box[6], d
                      counts + ncell);
   PQ_HIP(hipGetLastError());
   int32_t occ = 0;
-  PQ_HIP(hipMemcpyAsync(&occ, counts + ncell, 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, &occ, counts + ncell));
   *cell_used = cell;
   *per_cell = double(n) / double(occ > 0 ? occ : 1);
   return 0;
@@ -316,8 +315,7 @@ int robust_box(Ctx* c, const double* xyz, int64_t n, int budget, double box[6], 
     hipLaunchKernelGGL(k_axis_fold, dim3(3 * kAxisBins), dim3(64), 0, c->stream, d_part, blocks, d_hist);
     PQ_HIP(hipGetLastError());
     int32_t h[3 * kAxisBins];
-    PQ_HIP(hipMemcpyAsync(h, d_hist, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipStreamSynchronize(c->stream));
+    PQ_TRY(fetch(c, h, d_hist, 3 * kAxisBins));
     bool cut = false;
     for (int a = 0; a < 3; ++a) {
       const int32_t* ha = h + a * kAxisBins;
@@ -356,8 +354,7 @@ int cloud_bbox(Ctx* c, const double* xyz, int64_t n, double mn[3], double mx[3],
                      static_cast<GridPlan*>(nullptr));
   PQ_HIP(hipGetLastError());
   unsigned long long h_box[kBoxVals];
-  PQ_HIP(hipMemcpyAsync(h_box, d_box, sizeof(h_box), hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, h_box, d_box, kBoxVals));
   if (all_f32) *all_f32 = h_box[6] != 0;
   for (int a = 0; a < 3; ++a) {
     mn[a] = ord_val(h_box[a]);
@@ -1936,7 +1933,7 @@ int bin_octants_planned(Ctx* c, const double* xyz, int64_t n, double cell, const
 
 static int upload_plan(Ctx* c, const GridPlan& p, GridPlan* h_up, GridPlan* d_plan) {
   *h_up = p;  // the previous call's upload has run: the host waited on an event recorded after it
-  PQ_HIP(hipMemcpyAsync(d_plan, h_up, sizeof(GridPlan), hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_plan, h_up, 1));
   return 0;
 }
 
@@ -2018,8 +2015,7 @@ int bin_octants_host(Ctx* c, const double* xyz, int64_t n, double min_cell, int6
         PQ_HIP(hipGetLastError());
         PQ_TRY(exclusive_scan_i32(c, map[a], int64_t(raw[a]) + 1));
         int32_t kept = 0;
-        PQ_HIP(hipMemcpyAsync(&kept, map[a] + raw[a], 4, hipMemcpyDeviceToHost, c->stream));
-        PQ_HIP(hipStreamSynchronize(c->stream));
+        PQ_TRY(fetch(c, &kept, map[a] + raw[a]));
         hipLaunchKernelGGL(k_axis_shift, dim3(ceil_div(raw[a], 256)), blk, 0, c->stream, raw[a], map[a]);
         dims[a] = kept + 2;
         ctot *= double(dims[a]);
@@ -2259,8 +2255,7 @@ int coarsen_grid(Ctx* c, const DevGrid& fine, int64_t n, int factor, DevGrid* g)
 int count_occupied(Ctx* c, const DevGrid& g, int64_t* occupied) {
   if (g.occ_part) {  // left by build_grid's counting pass
     std::vector<int32_t> h(size_t(g.occ_blocks));
-    PQ_HIP(hipMemcpyAsync(h.data(), g.occ_part, h.size() * 4, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipStreamSynchronize(c->stream));
+    PQ_TRY(fetch(c, h.data(), g.occ_part, h.size()));
     int64_t t = 0;
     for (int32_t v : h) t += v;
     *occupied = t;
@@ -2273,8 +2268,7 @@ int count_occupied(Ctx* c, const DevGrid& g, int64_t* occupied) {
   hipLaunchKernelGGL(k_count_occupied, dim3(blocks), dim3(256), 0, c->stream, g.start, g.ncell, d);
   PQ_HIP(hipGetLastError());
   int32_t h = 0;
-  PQ_HIP(hipMemcpyAsync(&h, d, 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, &h, d));
   *occupied = h;
   return 0;
 }

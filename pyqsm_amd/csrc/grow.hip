@@ -192,10 +192,9 @@ int pyqsm_grow_clusters(const double* src, int64_t n, const int32_t* owner_in, c
     if (stats) memcpy(stats, st, sizeof st);
     return 0;
   }
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   double *d_src, *d_qry;
   int32_t *d_io, *d_qlab, *d_owner, *d_cand, *d_cycle, *d_flags, *d_active, *d_newcount, *d_finished;
   int64_t* d_front;
@@ -213,14 +212,14 @@ int pyqsm_grow_clusters(const double* src, int64_t n, const int32_t* owner_in, c
   PQ_TRY(c->arena.get(size_t(n_clusters), &d_newcount));
   PQ_TRY(c->arena.get(size_t(n_clusters), &d_finished));
   PQ_TRY(c->arena.get(1, &d_rec));
-  PQ_HIP(hipMemcpyAsync(d_src, src, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_qry, seed_xyz, size_t(m) * 24, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_qlab, seed_label, size_t(m) * 4, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_io, owner_in, size_t(n) * 4, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_active, active.data(), size_t(n_clusters) * 4, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_src, src, size_t(n) * 3));
+  PQ_TRY(copy_in(c, d_qry, seed_xyz, size_t(m) * 3));
+  PQ_TRY(copy_in(c, d_qlab, seed_label, size_t(m)));
+  PQ_TRY(copy_in(c, d_io, owner_in, size_t(n)));
+  PQ_TRY(copy_in(c, d_active, active.data(), size_t(n_clusters)));
   PQ_HIP(hipMemsetAsync(d_newcount, 0, size_t(n_clusters) * 4, c->stream));
   for (int32_t i = 0; i < n_clusters; ++i) finished[i] = active[size_t(i)] ? -1 : 0;
-  PQ_HIP(hipMemcpyAsync(d_finished, finished, size_t(n_clusters) * 4, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_finished, finished, size_t(n_clusters)));
   DevGrid g;
   PQ_TRY(radius_grid(c, d_src, n, radius, &g));
   const GridParams rg = grid_params(g);
@@ -274,8 +273,7 @@ int pyqsm_grow_clusters(const double* src, int64_t n, const int32_t* owner_in, c
       PQ_HIP(hipGetLastError());
     }
     unsigned long long rec = 0;  // the cycle's one read-back
-    PQ_HIP(hipMemcpyAsync(&rec, d_rec, 8, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipStreamSynchronize(c->stream));
+    PQ_TRY(fetch(c, &rec, d_rec));
     st[0] += 1;
     st[1] += served;
     st[3] = std::max(st[3], served);
@@ -286,9 +284,9 @@ int pyqsm_grow_clusters(const double* src, int64_t n, const int32_t* owner_in, c
   hipLaunchKernelGGL(k_grow_scatter, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, n, g.order,
                      static_cast<const int32_t*>(d_owner), static_cast<const int32_t*>(d_cycle), d_io, d_io + n);
   PQ_HIP(hipGetLastError());
-  PQ_HIP(hipMemcpyAsync(owner_out, d_io, size_t(n) * 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipMemcpyAsync(cycle_out, d_io + n, size_t(n) * 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipMemcpyAsync(finished, d_finished, size_t(n_clusters) * 4, hipMemcpyDeviceToHost, c->stream));
+  PQ_TRY(download(c, owner_out, d_io, size_t(n)));
+  PQ_TRY(download(c, cycle_out, d_io + n, size_t(n)));
+  PQ_TRY(download(c, finished, d_finished, size_t(n_clusters)));
   PQ_HIP(hipStreamSynchronize(c->stream));
   if (stats) memcpy(stats, st, sizeof st);
   return 0;

@@ -83,23 +83,21 @@ int pyqsm_extreme_points(const double* xyz, int64_t n, const double* dirs, int32
   PQ_API_RANGE("pyqsm_extreme_points");
   if (n <= 0 || n_dirs <= 0) return fail(PYQSM_EINVAL, "pyqsm_extreme_points: empty input");
   if (!xyz || !dirs || !idx) return fail(PYQSM_EINVAL, "pyqsm_extreme_points: NULL pointer");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   double* d_xyz = nullptr;
   DirBest* d_part = nullptr;
   PQ_TRY(c->arena.get(size_t(n) * 3, &d_xyz));
   PQ_TRY(c->arena.get(size_t(n_dirs) * kHullBlocks, &d_part));
-  PQ_HIP(hipMemcpyAsync(d_xyz, xyz, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_xyz, xyz, size_t(n) * 3));
   const unsigned blocks = unsigned(std::min<int64_t>(ceil_div(n, 256), kHullBlocks));
   for (int d = 0; d < n_dirs; ++d)
     hipLaunchKernelGGL(k_extreme, dim3(blocks), dim3(256), 0, c->stream, d_xyz, n, dirs[3 * d], dirs[3 * d + 1],
                        dirs[3 * d + 2], d_part + size_t(d) * kHullBlocks);
   PQ_HIP(hipGetLastError());
   std::vector<DirBest> h(size_t(n_dirs) * kHullBlocks);
-  PQ_HIP(hipMemcpyAsync(h.data(), d_part, h.size() * sizeof(DirBest), hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, h.data(), d_part, h.size()));
   for (int d = 0; d < n_dirs; ++d) {
     DirBest b = h[size_t(d) * kHullBlocks];
     for (unsigned k = 1; k < blocks; ++k) {
@@ -120,10 +118,9 @@ int pyqsm_outside_halfspaces(const double* xyz, int64_t n, const double* eq, int
   if (n == 0) return 0;
   if (!xyz || !eq || !idx || !count) return fail(PYQSM_EINVAL, "pyqsm_outside_halfspaces: NULL pointer");
   if (n > 0x7FFFFF00LL) return fail(PYQSM_ERANGE, "more than 2^31 points");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   double* d_xyz = nullptr;
   Planes* d_pl = nullptr;
   int32_t* d_flags = nullptr;
@@ -136,17 +133,15 @@ int pyqsm_outside_halfspaces(const double* xyz, int64_t n, const double* eq, int
   hp.count = n_planes;
   for (int f = 0; f < n_planes; ++f)
     for (int a = 0; a < 4; ++a) hp.eq[f][a] = eq[4 * f + a];
-  PQ_HIP(hipMemcpyAsync(d_xyz, xyz, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_pl, &hp, sizeof(Planes), hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_xyz, xyz, size_t(n) * 3));
+  PQ_TRY(copy_in(c, d_pl, &hp, 1));
   hipLaunchKernelGGL(k_outside, dim3(ceil_div(n + 1, 256)), dim3(256), 0, c->stream, d_xyz, n, d_pl, margin, d_flags);
   PQ_HIP(hipGetLastError());
   PQ_TRY(compact_flagged(c, d_flags, n, d_idx));
   int32_t m = 0;
-  PQ_HIP(hipMemcpyAsync(&m, d_flags + n, 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));  // hp may go
+  PQ_TRY(fetch(c, &m, d_flags + n));  // hp may go
   if (m > 0) {
-    PQ_HIP(hipMemcpyAsync(idx, d_idx, size_t(m) * 8, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipStreamSynchronize(c->stream));
+    PQ_TRY(fetch(c, idx, d_idx, size_t(m)));
   }
   *count = m;
   return 0;

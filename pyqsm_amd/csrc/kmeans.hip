@@ -335,8 +335,8 @@ static int lloyd_device(Ctx* c, const double* d_xyz, int64_t m, const int32_t* k
   PQ_TRY(c->arena.get(size_t(nq) * nch * kKmMaxK * 2, &d_part));
   PQ_TRY(c->arena.get(size_t(nq) * nch * kKmMaxK, &d_pcnt));
   PQ_TRY(c->arena.get(size_t(nq), &d_ks));
-  PQ_HIP(hipMemcpyAsync(d_init, init_pad.data(), init_pad.size() * 8, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_ks, ks, size_t(nq) * 4, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_init, init_pad.data(), init_pad.size()));
+  PQ_TRY(copy_in(c, d_ks, ks, size_t(nq)));
   {
     ProfScope ps(c, "kmeans_lloyd");
     hipLaunchKernelGGL(k_lloyd, dim3(nq), dim3(kLloydThreads), 0, c->stream, d_xyz, m, d_ks, d_init, iters,
@@ -345,8 +345,7 @@ static int lloyd_device(Ctx* c, const double* d_xyz, int64_t m, const int32_t* k
   }
   if (d_ks_out) *d_ks_out = d_ks;
   if (cent) {
-    PQ_HIP(hipMemcpyAsync(init_pad.data(), d_cent, init_pad.size() * 8, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipStreamSynchronize(c->stream));
+    PQ_TRY(fetch(c, init_pad.data(), d_cent, init_pad.size()));
     for (int q = 0, o = 0; q < nq; o += ks[q], ++q)
       for (int j = 0; j < ks[q] * 2; ++j) cent[size_t(o) * 2 + j] = init_pad[size_t(q) * kKmMaxK * 2 + j];
   }
@@ -393,9 +392,7 @@ static int silhouette_device(Ctx* c, const double* d_xyz, int64_t m, const int32
 }
 
 static int upload_points(Ctx* c, const double* xyz, int64_t m, double** d_xyz) {
-  PQ_TRY(c->arena.get(size_t(m) * 3, d_xyz));
-  PQ_HIP(hipMemcpyAsync(*d_xyz, xyz, size_t(m) * 24, hipMemcpyHostToDevice, c->stream));
-  return 0;
+  return upload(c, xyz, size_t(m) * 3, d_xyz);
 }
 
 static int kmeans_select_impl(Ctx* c, const double* d_xyz, int64_t m, int32_t k0, int32_t nk, int32_t iters,
@@ -417,8 +414,7 @@ static int kmeans_select_impl(Ctx* c, const double* d_xyz, int64_t m, int32_t k0
   PQ_TRY(lloyd_device(c, d_xyz, m, ks.data(), nk, iters, init, d_labels, &d_ks, nullptr));
   PQ_TRY(silhouette_device(c, d_xyz, m, d_labels, d_ks, nk, kKmMaxK, d_samples, d_scores, d_present));
   std::vector<char> h(bytes);
-  PQ_HIP(hipMemcpyAsync(h.data(), d_out, bytes, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, h.data(), d_out, bytes));
   memcpy(scores, h.data(), size_t(nk) * 8);
   memcpy(present, h.data() + size_t(nk) * 8, size_t(nk) * 4);
   memcpy(labels, h.data() + head, size_t(nk) * m * 4);
@@ -439,17 +435,15 @@ int pyqsm_kmeans(const double* xyz, int64_t m, int32_t k, int32_t iters, const d
   if (iters < 1) return fail(PYQSM_EINVAL, "iters must be >= 1");
   if (m > 0x7FFFFF00LL) return fail(PYQSM_ERANGE, "more than 2^31 points per call");
   PQ_TRY(check_ks(&k, 1));
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   double* d_xyz;
   int32_t* d_lab;
   PQ_TRY(upload_points(c, xyz, m, &d_xyz));
   PQ_TRY(c->arena.get(size_t(m), &d_lab));
   PQ_TRY(lloyd_device(c, d_xyz, m, &k, 1, iters, init, d_lab, nullptr, centroids));
-  PQ_HIP(hipMemcpyAsync(labels, d_lab, size_t(m) * 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, labels, d_lab, size_t(m)));
   return 0;
 }
 
@@ -462,10 +456,9 @@ int pyqsm_silhouette(const double* xyz, int64_t m, const int32_t* labels, int32_
   if (m > 0x7FFFFF00LL) return fail(PYQSM_ERANGE, "more than 2^31 points per call");
   for (int64_t i = 0; i < m; ++i)
     if (labels[i] < 0 || labels[i] >= k) return fail(PYQSM_EINVAL, "label outside [0, k)");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   double *d_xyz, *d_samples, *d_score;
   int32_t *d_lab, *d_ks, *d_present;
   PQ_TRY(upload_points(c, xyz, m, &d_xyz));
@@ -474,12 +467,12 @@ int pyqsm_silhouette(const double* xyz, int64_t m, const int32_t* labels, int32_
   PQ_TRY(c->arena.get(1, &d_score));
   PQ_TRY(c->arena.get(1, &d_present));
   PQ_TRY(c->arena.get(1, &d_ks));
-  PQ_HIP(hipMemcpyAsync(d_lab, labels, size_t(m) * 4, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_ks, &k, 4, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_lab, labels, size_t(m)));
+  PQ_TRY(copy_in(c, d_ks, &k, 1));
   PQ_TRY(silhouette_device(c, d_xyz, m, d_lab, d_ks, 1, k, d_samples, d_score, d_present));
-  PQ_HIP(hipMemcpyAsync(score, d_score, 8, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipMemcpyAsync(n_present, d_present, 4, hipMemcpyDeviceToHost, c->stream));
-  if (samples) PQ_HIP(hipMemcpyAsync(samples, d_samples, size_t(m) * 8, hipMemcpyDeviceToHost, c->stream));
+  PQ_TRY(download(c, score, d_score, 1));
+  PQ_TRY(download(c, n_present, d_present, 1));
+  if (samples) PQ_TRY(download(c, samples, d_samples, size_t(m)));
   PQ_HIP(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -493,10 +486,9 @@ int pyqsm_kmeans_select_dev(const double* xyz_dev, int64_t m, int32_t k0, int32_
     return fail(PYQSM_EINVAL, "pyqsm_kmeans_select: NULL pointer");
   if (iters < 1) return fail(PYQSM_EINVAL, "iters must be >= 1");
   if (m > 0x7FFFFF00LL / PYQSM_KMEANS_MAX_Q) return fail(PYQSM_ERANGE, "too many points per call");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   ProfScope ps(c, "kmeans_select");
   return kmeans_select_impl(c, xyz_dev, m, k0, nk, iters, init, labels, scores, present);
 }
@@ -510,10 +502,9 @@ int pyqsm_kmeans_select(const double* xyz, int64_t m, int32_t k0, int32_t nk, in
     return fail(PYQSM_EINVAL, "pyqsm_kmeans_select: NULL pointer");
   if (iters < 1) return fail(PYQSM_EINVAL, "iters must be >= 1");
   if (m > 0x7FFFFF00LL / PYQSM_KMEANS_MAX_Q) return fail(PYQSM_ERANGE, "too many points per call");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   double* d_xyz;
   PQ_TRY(upload_points(c, xyz, m, &d_xyz));
   return kmeans_select_impl(c, d_xyz, m, k0, nk, iters, init, labels, scores, present);
@@ -531,10 +522,9 @@ int pyqsm_ball_excl_dev(const double* xyz_dev, int64_t n, const uint8_t* found_d
     return fail(PYQSM_EINVAL, "pyqsm_ball_excl_dev: NULL pointer");
   if (!(radius >= 0)) return fail(PYQSM_EINVAL, "radius must be >= 0");
   if (n > 0x7FFFFF00LL) return fail(PYQSM_ERANGE, "more than 2^31 points per call");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   int32_t* d_flags;
   PQ_TRY(c->arena.get(size_t(n) + 1, &d_flags));
   {
@@ -544,8 +534,7 @@ int pyqsm_ball_excl_dev(const double* xyz_dev, int64_t n, const uint8_t* found_d
     PQ_TRY(compact_flagged(c, d_flags, n, idx_dev, nullptr, xyz_dev, out_xyz_dev));
   }
   int32_t total = 0;
-  PQ_HIP(hipMemcpyAsync(&total, d_flags + n, 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, &total, d_flags + n));
   *count = total;
   return 0;
 }
@@ -555,13 +544,11 @@ int pyqsm_mark_found_dev(uint8_t* found_dev, int64_t n, const int64_t* idx, int6
   if (n < 0 || cnt < 0) return fail(PYQSM_EINVAL, "negative size");
   if (cnt == 0) return 0;
   if (!found_dev || !idx) return fail(PYQSM_EINVAL, "pyqsm_mark_found_dev: NULL pointer");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   int64_t* d_idx;
-  PQ_TRY(c->arena.get(size_t(cnt), &d_idx));
-  PQ_HIP(hipMemcpyAsync(d_idx, idx, size_t(cnt) * 8, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(upload(c, idx, size_t(cnt), &d_idx));
   hipLaunchKernelGGL(k_mark_found, dim3(ceil_div(cnt, 256)), dim3(256), 0, c->stream, found_dev, n, d_idx, cnt);
   PQ_HIP(hipGetLastError());
   PQ_HIP(hipStreamSynchronize(c->stream));  // the caller's index array may go away on return

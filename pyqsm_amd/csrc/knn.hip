@@ -895,8 +895,7 @@ int knn_device(Ctx* c, const double* xyz, int64_t n, int32_t k, int32_t exclude_
     }
     if (last) break;
     int32_t nf = 0;
-    PQ_HIP(hipMemcpyAsync(&nf, fail_count, 4, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipStreamSynchronize(c->stream));
+    PQ_TRY(fetch(c, &nf, fail_count));
     if (level == 0 && getenv("PYQSM_KNN_TRACE")) {
       int32_t nt = 0;
       PQ_HIP(hipMemcpy(&nt, tie_count, 4, hipMemcpyDeviceToHost));
@@ -960,10 +959,9 @@ int pyqsm_knn_dev(const double* xyz_dev, int64_t n, int32_t k, int32_t exclude_s
   if (n < 0) return fail(PYQSM_EINVAL, "negative size");
   if (n > 0 && (!xyz_dev || !idx_dev || !d2_dev))
     return fail(PYQSM_EINVAL, "pyqsm_knn_dev: NULL pointer");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   ProfScope ps(c, "knn_total");
   return knn_device(c, xyz_dev, n, k, exclude_self, idx_dev, d2_dev);
 }
@@ -974,19 +972,18 @@ int pyqsm_knn(const double* xyz, int64_t n, int32_t k, int32_t exclude_self, int
   if (n < 0) return fail(PYQSM_EINVAL, "negative size");
   if (n == 0) return 0;
   if (!xyz || !idx || !d2) return fail(PYQSM_EINVAL, "pyqsm_knn: NULL pointer");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   double *d_xyz, *d_d2;
   int32_t* d_idx;
   PQ_TRY(c->arena.get(size_t(n) * 3, &d_xyz));
   PQ_TRY(c->arena.get(size_t(n) * size_t(k > 0 ? k : 1), &d_idx));
   PQ_TRY(c->arena.get(size_t(n) * size_t(k > 0 ? k : 1), &d_d2));
-  PQ_HIP(hipMemcpyAsync(d_xyz, xyz, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_xyz, xyz, size_t(n) * 3));
   PQ_TRY(knn_device(c, d_xyz, n, k, exclude_self, d_idx, d_d2));
-  PQ_HIP(hipMemcpyAsync(idx, d_idx, size_t(n) * k * 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipMemcpyAsync(d2, d_d2, size_t(n) * k * 8, hipMemcpyDeviceToHost, c->stream));
+  PQ_TRY(download(c, idx, d_idx, size_t(n) * k));
+  PQ_TRY(download(c, d2, d_d2, size_t(n) * k));
   PQ_HIP(hipStreamSynchronize(c->stream));
   return 0;
 }

@@ -1175,8 +1175,8 @@ int laplacian_device(Ctx* c, const double* d_xyz, int64_t n, const int64_t* seg_
     PQ_TRY(c->arena.get(2, &d_seg_bad));
     for (int64_t q = 0; q <= n_seg; ++q) h_seg[size_t(q)] = int32_t(seg_start[q]);
     h_bad[1] = 0x7fffffff;
-    PQ_HIP(hipMemcpyAsync(d_seg_start, h_seg.data(), (size_t(n_seg) + 1) * 4, hipMemcpyHostToDevice, c->stream));
-    PQ_HIP(hipMemcpyAsync(d_seg_bad, h_bad.data(), 8, hipMemcpyHostToDevice, c->stream));
+    PQ_TRY(copy_in(c, d_seg_start, h_seg.data(), size_t(n_seg) + 1));
+    PQ_TRY(copy_in(c, d_seg_bad, h_bad.data(), 2));
     hipLaunchKernelGGL(k_check_segments, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, N, k, int(n_seg),
                        d_seg_start, d_nbr, d_seg_bad);
     PQ_HIP(hipGetLastError());
@@ -1202,8 +1202,8 @@ int laplacian_device(Ctx* c, const double* d_xyz, int64_t n, const int64_t* seg_
   ProfScope ps(c, "lap_assemble");
   PQ_TRY(exclusive_scan_i32(c, d_tcount, n + 1));
   int32_t T = 0;
-  PQ_HIP(hipMemcpyAsync(&T, d_tcount + n, 4, hipMemcpyDeviceToHost, c->stream));
-  if (n_seg > 1) PQ_HIP(hipMemcpyAsync(h_bad.data(), d_seg_bad, 8, hipMemcpyDeviceToHost, c->stream));
+  PQ_TRY(download(c, &T, d_tcount + n, 1));
+  if (n_seg > 1) PQ_TRY(download(c, h_bad.data(), d_seg_bad, 2));
   PQ_HIP(hipStreamSynchronize(c->stream));
   if (n_seg > 1 && h_bad[0] != 0) {
     int64_t sidx = 0;
@@ -1293,8 +1293,7 @@ int laplacian_device(Ctx* c, const double* d_xyz, int64_t n, const int64_t* seg_
     hipLaunchKernelGGL(k_flip_seed, dim3(ceil_div(std::max(3 * F, 1), 256 * kSeedPer)), blk, 0, c->stream, 3 * F, d_fl,
                        d_fn, d_list[0], d_cnt);
     int32_t hc[2] = {0, 0};
-    PQ_HIP(hipMemcpyAsync(hc, d_cnt, 8, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipStreamSynchronize(c->stream));
+    PQ_TRY(fetch(c, hc, d_cnt, 2));
     int m = hc[0];  // last list length the host has seen (sizes the next launches)
     // PYQSM_FLIP_PUSH_ALL=1: a flip lists its four outer edges unseen (the earlier form; same flips, same result)
     const char* e_push = getenv("PYQSM_FLIP_PUSH_ALL");
@@ -1315,8 +1314,7 @@ int laplacian_device(Ctx* c, const double* d_xyz, int64_t n, const int64_t* seg_
                            round, d_fv, d_fl, d_fn, d_claim, d_mark, nxt, d_cnt + 2 * (round + 1), push_all);
       }
       PQ_HIP(hipGetLastError());
-      PQ_HIP(hipMemcpyAsync(hc, d_cnt + 2 * round, 8, hipMemcpyDeviceToHost, c->stream));
-      PQ_HIP(hipStreamSynchronize(c->stream));
+      PQ_TRY(fetch(c, hc, d_cnt + 2 * round, 2));
       if (hc[1] == 0) break;  // the last round of the batch flipped nothing: done (or stuck)
       // A handful of edges flipping back and forth for good: on nearly degenerate faces of
       // a contracted cloud the rounding of the two cotangents can exceed the tolerance on
@@ -1335,17 +1333,7 @@ int laplacian_device(Ctx* c, const double* d_xyz, int64_t n, const int64_t* seg_
     }
     if (getenv("PYQSM_LBC_TRACE")) {  // the rounds' own counters: list length going in, flips made
       std::vector<int32_t> hcnt(size_t(kMaxFlipRounds + 2) * 2);
-      PQ_HIP(hipMemcpyAsync(hcnt.data(), d_cnt, hcnt.size() * 4, hipMemcpyDeviceToHost, c->stream));
-      PQ_HIP(hipStreamSynchronize(c->stream));
-      fprintf(stderr, "flip rounds of a cover of %d faces (list, flips):", F);
-      for (int r = 0; r < kMaxFlipRounds && hcnt[2 * size_t(r)] > 0; ++r)
-        fprintf(stderr, " %d:%d", hcnt[2 * size_t(r)], hcnt[2 * size_t(r) + 3]);
-      fprintf(stderr, "\n");
-    }
-    if (getenv("PYQSM_LBC_TRACE")) {  // the rounds' own counters: list length going in, flips made
-      std::vector<int32_t> hcnt(size_t(kMaxFlipRounds + 2) * 2);
-      PQ_HIP(hipMemcpyAsync(hcnt.data(), d_cnt, hcnt.size() * 4, hipMemcpyDeviceToHost, c->stream));
-      PQ_HIP(hipStreamSynchronize(c->stream));
+      PQ_TRY(fetch(c, hcnt.data(), d_cnt, hcnt.size()));
       fprintf(stderr, "flip rounds of a cover of %d faces (list, flips):", F);
       for (int r = 0; r < kMaxFlipRounds && hcnt[2 * size_t(r)] > 0; ++r)
         fprintf(stderr, " %d:%d", hcnt[2 * size_t(r)], hcnt[2 * size_t(r) + 3]);
@@ -1361,8 +1349,7 @@ int laplacian_device(Ctx* c, const double* d_xyz, int64_t n, const int64_t* seg_
   }
   if (getenv("PYQSM_LBC_TRACE")) {  // longest row of contributions
     std::vector<int32_t> rs(size_t(n) + 1);
-    PQ_HIP(hipMemcpyAsync(rs.data(), d_vcount, (size_t(n) + 1) * 4, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipStreamSynchronize(c->stream));
+    PQ_TRY(fetch(c, rs.data(), d_vcount, size_t(n) + 1));
     int mx = 0;
     int64_t over = 0;
     for (int64_t i = 0; i < n; ++i) {
@@ -1378,8 +1365,7 @@ int laplacian_device(Ctx* c, const double* d_xyz, int64_t n, const int64_t* seg_
   PQ_HIP(hipGetLastError());
   PQ_TRY(exclusive_scan_i32(c, d_nnzrow, n + 1));  // indptr
   int32_t nnz = 0;
-  PQ_HIP(hipMemcpyAsync(&nnz, d_nnzrow + n, 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, &nnz, d_nnzrow + n));
   int32_t* d_indices;
   double* d_vals;
   PQ_TRY(c->arena.get(size_t(nnz) + 1, &d_indices));
@@ -1423,55 +1409,35 @@ static int pc_laplacian_impl(const double* xyz, int64_t n, const int64_t* seg_st
   if (n > 0 && (!xyz || !mass)) return fail(PYQSM_EINVAL, "pyqsm_pc_laplacian: NULL pointer");
   if (n > (int64_t(1) << 30) / k) return fail(PYQSM_ERANGE, "n * n_neighbors exceeds 2^30");
   if (!(moll >= 0)) return fail(PYQSM_EINVAL, "mollify factor must be >= 0");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
-  int32_t* h_indptr = static_cast<int32_t*>(out_alloc((size_t(n) + 1) * 4));
+  OutBufs out;
+  int32_t* h_indptr = out.get<int32_t>(size_t(n) + 1);
   if (!h_indptr) return fail(PYQSM_ENOMEM, "host allocation failed");
-  if (n == 0) {
-    h_indptr[0] = 0;
-    *indptr_out = h_indptr;
-    *indices_out = static_cast<int32_t*>(malloc(4));
-    *vals_out = static_cast<double*>(malloc(8));
-    return 0;
-  }
-  int rc = 0;
-  auto body = [&]() -> int {
+  LapOut lo{};  // n == 0: an empty matrix, nothing runs on the device
+  if (n > 0) {
     double* d_xyz;
-    PQ_TRY(c->arena.get(size_t(n) * 3, &d_xyz));
-    PQ_HIP(hipMemcpyAsync(d_xyz, xyz, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
-    LapOut lo;
+    PQ_TRY(upload(c, xyz, size_t(n) * 3, &d_xyz));
     PQ_TRY(laplacian_device(c, d_xyz, n, seg_start, n_seg, k, moll, &lo));
-    const int32_t nnz = lo.nnz;
-    int32_t *d_nnzrow = lo.indptr, *d_indices = lo.indices;
-    double *d_vals = lo.vals, *d_mass = lo.mass;
-    int32_t* h_indices = static_cast<int32_t*>(out_alloc((size_t(nnz) + 1) * 4));
-    double* h_vals = static_cast<double*>(out_alloc((size_t(nnz) + 1) * 8));
-    if (!h_indices || !h_vals) {
-      out_free(h_indices);
-      out_free(h_vals);
-      return fail(PYQSM_ENOMEM, "host allocation failed");
-    }
-    *indices_out = h_indices;
-    *vals_out = h_vals;
-    PQ_HIP(hipMemcpyAsync(h_indptr, d_nnzrow, (size_t(n) + 1) * 4, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipMemcpyAsync(h_indices, d_indices, size_t(nnz) * 4, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipMemcpyAsync(h_vals, d_vals, size_t(nnz) * 8, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipMemcpyAsync(mass, d_mass, size_t(n) * 8, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipStreamSynchronize(c->stream));
-    *nnz_out = nnz;
-    return 0;
-  };
-  rc = body();
-  if (rc != 0) {
-    out_free(h_indptr);
-    out_free(*indices_out);
-    out_free(*vals_out);
-    *indices_out = nullptr;
-    *vals_out = nullptr;
-    return rc;
+  } else {
+    h_indptr[0] = 0;
   }
+  const int32_t nnz = lo.nnz;
+  int32_t* h_indices = out.get<int32_t>(size_t(nnz) + 1);
+  double* h_vals = out.get<double>(size_t(nnz) + 1);
+  if (!h_indices || !h_vals) return fail(PYQSM_ENOMEM, "host allocation failed");
+  if (n > 0) {
+    PQ_TRY(download(c, h_indptr, lo.indptr, size_t(n) + 1));
+    PQ_TRY(download(c, h_indices, lo.indices, size_t(nnz)));
+    PQ_TRY(download(c, h_vals, lo.vals, size_t(nnz)));
+    PQ_TRY(download(c, mass, lo.mass, size_t(n)));
+    PQ_HIP(hipStreamSynchronize(c->stream));
+  }
+  out.kept = true;
+  *nnz_out = nnz;
+  *indices_out = h_indices;
+  *vals_out = h_vals;
   *indptr_out = h_indptr;
   return 0;
 }

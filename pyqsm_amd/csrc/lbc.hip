@@ -340,10 +340,10 @@ static int upload_csr(Ctx* c, const int32_t* indptr, const int32_t* indices, con
   PQ_TRY(c->arena.get(size_t(n) + 1, &d->indptr));
   PQ_TRY(c->arena.get(size_t(nnz) + 1, &d->indices));
   PQ_TRY(c->arena.get(size_t(nnz) + 1, &d->vals));
-  PQ_HIP(hipMemcpyAsync(d->indptr, indptr, (size_t(n) + 1) * 4, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d->indptr, indptr, size_t(n) + 1));
   if (nnz) {
-    PQ_HIP(hipMemcpyAsync(d->indices, indices, size_t(nnz) * 4, hipMemcpyHostToDevice, c->stream));
-    PQ_HIP(hipMemcpyAsync(d->vals, vals, size_t(nnz) * 8, hipMemcpyHostToDevice, c->stream));
+    PQ_TRY(copy_in(c, d->indices, indices, size_t(nnz)));
+    PQ_TRY(copy_in(c, d->vals, vals, size_t(nnz)));
   }
   *nnz_out = nnz;
   return 0;
@@ -545,8 +545,7 @@ static int dot3_host(Ctx* c, int n, const double* a, const double* b, double* d_
 int part_totals_host(Ctx* c, const double* const* parts, int m, double (*out)[3]) {
   std::vector<double> h(size_t(m) * 3 * kPart);
   for (int a = 0; a < m; ++a)
-    PQ_HIP(hipMemcpyAsync(h.data() + size_t(a) * 3 * kPart, parts[a], sizeof(double) * 3 * kPart,
-                          hipMemcpyDeviceToHost, c->stream));
+    PQ_TRY(download(c, h.data() + size_t(a) * 3 * kPart, parts[a], kPart * 3));
   PQ_HIP(hipStreamSynchronize(c->stream));
   for (int a = 0; a < m; ++a)
     for (int k = 0; k < 3; ++k) {
@@ -1535,8 +1534,7 @@ int lbc_solve_device(Ctx* c, const DevCsr& L, int64_t n, const double* wl, bool 
   while (bits < 32 && (int64_t(1) << bits) < g.ncell) ++bits;
   PQ_TRY(stable_sort_pairs_u32(c, &keys, &order, n, bits));
   int32_t nnz = 0;
-  PQ_HIP(hipMemcpyAsync(&nnz, L.indptr + n, 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, &nnz, L.indptr + n));
   int32_t* pos_of;
   DevCsr Lp;
   double *wh_p, *wl_p, *pts_p, *x_p;
@@ -1573,25 +1571,23 @@ int pyqsm_spmv3(const int32_t* indptr, const int32_t* indices, const double* val
   if (n < 0) return fail(PYQSM_EINVAL, "negative size");
   if (n == 0) return 0;
   if (!indptr || !x || !y) return fail(PYQSM_EINVAL, "pyqsm_spmv3: NULL pointer");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   DevCsr L;
   int64_t nnz;
   PQ_TRY(upload_csr(c, indptr, indices, vals, n, &L, &nnz));
   double *dx, *dy;
   PQ_TRY(c->arena.get(size_t(n) * 3, &dx));
   PQ_TRY(c->arena.get(size_t(n) * 3, &dy));
-  PQ_HIP(hipMemcpyAsync(dx, x, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, dx, x, size_t(n) * 3));
   {
     ProfScope ps(c, "spmv3");
     hipLaunchKernelGGL(k_spmv3, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, int(n), L.indptr,
                        L.indices, L.vals, static_cast<const double*>(nullptr), dx, dy);
     PQ_HIP(hipGetLastError());
   }
-  PQ_HIP(hipMemcpyAsync(y, dy, size_t(n) * 24, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, y, dy, size_t(n) * 3));
   return 0;
 }
 
@@ -1616,10 +1612,9 @@ int pyqsm_lbc_solve(const int32_t* indptr, const int32_t* indices, const double*
   for (int64_t i = 0; i < n; ++i)
     if (!(wh[i] > 0.0) || !std::isfinite(wh[i]))
       return fail(PYQSM_EINVAL, "positional weights must be positive and finite");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   DevCsr L;
   int64_t nnz;
   PQ_TRY(upload_csr(c, indptr, indices, vals, n, &L, &nnz));
@@ -1628,9 +1623,9 @@ int pyqsm_lbc_solve(const int32_t* indptr, const int32_t* indices, const double*
   PQ_TRY(c->arena.get(size_t(n), &d_wh));
   PQ_TRY(c->arena.get(size_t(n) * 3, &d_pts));
   PQ_TRY(c->arena.get(size_t(n) * 3, &d_x));
-  PQ_HIP(hipMemcpyAsync(d_wl, wl, size_t(n) * 8, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_wh, wh, size_t(n) * 8, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_pts, pts, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_wl, wl, size_t(n)));
+  PQ_TRY(copy_in(c, d_wh, wh, size_t(n)));
+  PQ_TRY(copy_in(c, d_pts, pts, size_t(n) * 3));
   int32_t it = 0;
   double rs[3] = {0, 0, 0};
   bool wl_edge_const = wl_positive;
@@ -1641,8 +1636,7 @@ int pyqsm_lbc_solve(const int32_t* indptr, const int32_t* indices, const double*
     hipLaunchKernelGGL(k_edge_const, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, int(n), L.indptr,
                        L.indices, d_wl, d_flag);
     int32_t h_flag = 0;
-    PQ_HIP(hipMemcpyAsync(&h_flag, d_flag, 4, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipStreamSynchronize(c->stream));
+    PQ_TRY(fetch(c, &h_flag, d_flag));
     wl_edge_const = h_flag == 0;
   }
   int rc = lbc_solve_device(c, L, n, d_wl, wl_edge_const, d_wh, d_pts, rtol, max_it, d_x, &it, rs);
@@ -1653,8 +1647,7 @@ int pyqsm_lbc_solve(const int32_t* indptr, const int32_t* indices, const double*
     resid[2] = rs[2];
   }
   if (rc != 0 && rc != PYQSM_ENOCONV) return rc;
-  PQ_HIP(hipMemcpyAsync(out, d_x, size_t(n) * 24, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, out, d_x, size_t(n) * 3));
   return rc;
 }
 
@@ -1663,21 +1656,18 @@ int pyqsm_clamp(double* pts, int64_t n, const double lo[3], const double hi[3], 
   if (n < 0) return fail(PYQSM_EINVAL, "negative size");
   if (n == 0) return 0;
   if (!pts || !lo || !hi) return fail(PYQSM_EINVAL, "pyqsm_clamp: NULL pointer");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   double* d;
-  PQ_TRY(c->arena.get(size_t(n) * 3, &d));
-  PQ_HIP(hipMemcpyAsync(d, pts, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(upload(c, pts, size_t(n) * 3, &d));
   {
     ProfScope ps(c, "clamp");
     hipLaunchKernelGGL(k_clamp, dim3(ceil_div(n * 3, 256)), dim3(256), 0, c->stream, n * 3, d,
                        lo[0], lo[1], lo[2], hi[0], hi[1], hi[2]);
     PQ_HIP(hipGetLastError());
   }
-  PQ_HIP(hipMemcpyAsync(pts, d, size_t(n) * 24, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, pts, d, size_t(n) * 3));
   return 0;
 }
 

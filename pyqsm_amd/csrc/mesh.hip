@@ -26,31 +26,6 @@ constexpr int kColTiles = 8;                            // column tiles one bloc
 constexpr int64_t kSweepMaxTris = int64_t(1) << 26;     // grid.y = tiles / kColTiles <= 65535
 static_assert(kRows == 256, "one thread per row triangle of a 256-thread block");
 
-int bit_length(uint64_t v) {
-  int b = 0;
-  while (v) {
-    ++b;
-    v >>= 1;
-  }
-  return b;
-}
-
-// Host buffers handed to the caller: released again unless `kept` is set.
-struct OutBufs {
-  std::vector<void*> p;
-  bool kept = false;
-  ~OutBufs() {
-    if (!kept)
-      for (void* q : p) out_free(q);
-  }
-  template <typename T>
-  T* get(size_t count) {
-    void* q = out_alloc(std::max<size_t>(count, 1) * sizeof(T));
-    if (q) p.push_back(q);
-    return static_cast<T*>(q);
-  }
-};
-
 // ---------------------------------------------------------------- topology
 
 // Half-edge h = 3 t + k runs from corner k of triangle t to corner (k + 1) % 3.
@@ -438,16 +413,6 @@ __global__ __launch_bounds__(256) void k_mesh_sweep(int nt, int ntile, const int
   if (threadIdx.x < 3 && s_cnt[threadIdx.x]) atomicAdd(&counters[threadIdx.x], s_cnt[threadIdx.x]);
 }
 
-__global__ __launch_bounds__(256) void k_mesh_pair_keys(int n, const int32_t* __restrict__ src,
-                                                        const int32_t* __restrict__ perm /*may be null*/,
-                                                        uint32_t* __restrict__ keys, int32_t* __restrict__ vals) {
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= n) return;
-  const int q = perm ? perm[p] : p;
-  keys[p] = uint32_t(src[q]);
-  vals[p] = q;
-}
-
 __global__ __launch_bounds__(256) void k_mesh_pair_rows(int n, const int32_t* __restrict__ perm,
                                                         const int32_t* __restrict__ pi, const int32_t* __restrict__ pj,
                                                         int32_t* __restrict__ rows) {
@@ -502,10 +467,9 @@ int pyqsm_mesh_topology(const int32_t* tris, int64_t n_tris, int64_t n_verts, co
   if (n_verts > 0) std::fill(vertex_flags, vertex_flags + n_verts, uint8_t(0));
   if (n_tris == 0) return 0;  // nothing to launch
 
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   const int nt = int(n_tris), nh = 3 * nt, nv = int(n_verts);
   int32_t *d_tris, *d_vals, *d_flags, *d_par_tri, *d_par_corner, *d_par_cover, *d_vroots, *d_cl;
   uint32_t* d_keys;
@@ -524,8 +488,8 @@ int pyqsm_mesh_topology(const int32_t* tris, int64_t n_tris, int64_t n_verts, co
   PQ_TRY(c->arena.get(size_t(8), &d_counters));
   PQ_TRY(c->arena.get(size_t(nv), &d_vflags));
   if (verts) PQ_TRY(c->arena.get(size_t(nv) * 3, &d_verts));
-  PQ_HIP(hipMemcpyAsync(d_tris, tris, size_t(nh) * 4, hipMemcpyHostToDevice, c->stream));
-  if (verts) PQ_HIP(hipMemcpyAsync(d_verts, verts, size_t(nv) * 24, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_tris, tris, size_t(nh)));
+  if (verts) PQ_TRY(copy_in(c, d_verts, verts, size_t(nv) * 3));
   PQ_HIP(hipMemsetAsync(d_counters, 0, 64, c->stream));
   PQ_HIP(hipMemsetAsync(d_vroots, 0, size_t(nv) * 4, c->stream));
 
@@ -550,8 +514,7 @@ int pyqsm_mesh_topology(const int32_t* tris, int64_t n_tris, int64_t n_verts, co
     PQ_LAUNCH(k_mesh_he_heads, ceil_div(nh + 1, 256), nh, static_cast<const int32_t*>(d_tris),
               static_cast<const int32_t*>(d_hs), d_flags);
     PQ_TRY(exclusive_scan_i32(c, d_flags, int64_t(nh) + 1));
-    PQ_HIP(hipMemcpyAsync(&e_total, d_flags + nh, 4, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipStreamSynchronize(c->stream));  // E sizes the edge table
+    PQ_TRY(fetch(c, &e_total, d_flags + nh));  // E sizes the edge table
   }
   if (e_total < 1 || e_total > nh) return fail(PYQSM_EHIP, "pyqsm_mesh_topology: %d edges counted", e_total);
   const int ne = e_total;
@@ -578,7 +541,7 @@ int pyqsm_mesh_topology(const int32_t* tris, int64_t n_tris, int64_t n_verts, co
     // d_flags is free again: the roots of the triangle sets, scanned, number the clusters
     PQ_LAUNCH(k_mesh_root_flags, ceil_div(nt + 1, 256), nt, static_cast<const int32_t*>(d_par_tri), d_flags);
     PQ_TRY(exclusive_scan_i32(c, d_flags, int64_t(nt) + 1));
-    PQ_HIP(hipMemcpyAsync(&n_clusters, d_flags + nt, 4, hipMemcpyDeviceToHost, c->stream));
+    PQ_TRY(download(c, &n_clusters, d_flags + nt, 1));
     PQ_LAUNCH(k_mesh_vertex_roots, ceil_div(nh, 256), nh, static_cast<const int32_t*>(d_par_corner),
               static_cast<const int32_t*>(d_tris), d_vroots);
     PQ_LAUNCH(k_mesh_vertex_flags, ceil_div(nv, 256), nv, static_cast<const int32_t*>(d_vroots), d_vflags,
@@ -615,14 +578,14 @@ int pyqsm_mesh_topology(const int32_t* tris, int64_t n_tris, int64_t n_verts, co
   if (!h_edges || !h_ecount || !h_eflags || !h_cn || (verts && !h_carea))
     return fail(PYQSM_ENOMEM, "pyqsm_mesh_topology: no host memory for %d edges and %d clusters", ne, ncl);
   unsigned long long counters[8];
-  PQ_HIP(hipMemcpyAsync(h_edges, d_edges, size_t(ne) * 8, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipMemcpyAsync(h_ecount, d_ecount, size_t(ne) * 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipMemcpyAsync(h_eflags, d_eflags, size_t(ne), hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipMemcpyAsync(h_cn, d_cn, size_t(ncl) * 8, hipMemcpyDeviceToHost, c->stream));
-  if (verts) PQ_HIP(hipMemcpyAsync(h_carea, d_carea, size_t(ncl) * 8, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipMemcpyAsync(tri_cluster, d_cl, size_t(nt) * 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipMemcpyAsync(vertex_flags, d_vflags, size_t(nv), hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipMemcpyAsync(counters, d_counters, 64, hipMemcpyDeviceToHost, c->stream));
+  PQ_TRY(download(c, h_edges, d_edges, size_t(ne) * 2));
+  PQ_TRY(download(c, h_ecount, d_ecount, size_t(ne)));
+  PQ_TRY(download(c, h_eflags, d_eflags, size_t(ne)));
+  PQ_TRY(download(c, h_cn, d_cn, size_t(ncl)));
+  if (verts) PQ_TRY(download(c, h_carea, d_carea, size_t(ncl)));
+  PQ_TRY(download(c, tri_cluster, d_cl, size_t(nt)));
+  PQ_TRY(download(c, vertex_flags, d_vflags, size_t(nv)));
+  PQ_TRY(download(c, counters, d_counters, 8));
   PQ_HIP(hipStreamSynchronize(c->stream));
   summary[0] = ne;
   summary[1] = int64_t(counters[0]);
@@ -686,10 +649,9 @@ int pyqsm_mesh_self_intersections(const int32_t* ijk, int64_t n_verts, const int
   if (stats) stats[0] = considered;
   if (n_tris == 0) return 0;
 
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   const int nt = int(n_tris), nv = int(n_verts), ntile = ceil_div(nt, kRows), nword = ceil_div(nt, 4);
   int32_t *d_ijk, *d_tris;
   int4 *d_box, *d_tv;
@@ -701,8 +663,8 @@ int pyqsm_mesh_self_intersections(const int32_t* ijk, int64_t n_verts, const int
   PQ_TRY(c->arena.get(size_t(nt) * 3, &d_tv));
   PQ_TRY(c->arena.get(size_t(nword), &d_hit));
   PQ_TRY(c->arena.get(size_t(8), &d_counters));
-  PQ_HIP(hipMemcpyAsync(d_ijk, ijk, size_t(nv) * 12, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_tris, tris, size_t(nt) * 12, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_ijk, ijk, size_t(nv) * 3));
+  PQ_TRY(copy_in(c, d_tris, tris, size_t(nt) * 3));
   PQ_HIP(hipMemsetAsync(d_hit, 0, size_t(nword) * 4, c->stream));
   PQ_HIP(hipMemsetAsync(d_counters, 0, 64, c->stream));
   PQ_LAUNCH(k_mesh_tri_setup, ceil_div(nt, 256), nt, static_cast<const int32_t*>(d_ijk),
@@ -725,8 +687,7 @@ int pyqsm_mesh_self_intersections(const int32_t* ijk, int64_t n_verts, const int
     hipLaunchKernelGGL(k_mesh_sweep, grid, dim3(256), 0, c->stream, nt, ntile, static_cast<const int4*>(d_box),
                        static_cast<const int4*>(d_tv), d_hit, d_counters, (long long)cap, d_pi, d_pj);
     PQ_HIP(hipGetLastError());
-    PQ_HIP(hipMemcpyAsync(counters, d_counters, 64, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipStreamSynchronize(c->stream));
+    PQ_TRY(fetch(c, counters, d_counters, 8));
     if (!want_pairs || int64_t(counters[4]) <= cap) break;
     if (pass == 1) return fail(PYQSM_EHIP, "pyqsm_mesh_self_intersections: the pair count changed between sweeps");
     if (counters[4] > 0x7FFFFF00ULL)
@@ -744,8 +705,7 @@ int pyqsm_mesh_self_intersections(const int32_t* ijk, int64_t n_verts, const int
     stats[4] = int64_t(counters[2]);
     stats[5] = found;
   }
-  PQ_HIP(hipMemcpyAsync(tri_hit, d_hit, size_t(nt), hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, tri_hit, reinterpret_cast<const uint8_t*>(d_hit), size_t(nt)));  // one byte per triangle
   *n_pairs = found;
   if (!want_pairs || found == 0) return 0;
   if (found > 0x7FFFFF00LL) return fail(PYQSM_ERANGE, "pyqsm_mesh_self_intersections: more than 2^31 intersecting pairs");
@@ -753,29 +713,20 @@ int pyqsm_mesh_self_intersections(const int32_t* ijk, int64_t n_verts, const int
   // ascending (i, j): a stable pass by j, then one by i; the pairs are unique, so the list is the
   // same whatever order the cursor handed the slots out in
   const int np = int(found), bits = bit_length(uint64_t(nt));
-  uint32_t *d_k, *d_k2;
-  int32_t *d_v, *d_v2, *d_rows;
-  PQ_TRY(c->arena.get(size_t(np), &d_k));
-  PQ_TRY(c->arena.get(size_t(np), &d_v));
-  PQ_TRY(c->arena.get(size_t(np), &d_k2));
-  PQ_TRY(c->arena.get(size_t(np), &d_v2));
+  int32_t* d_rows;
   PQ_TRY(c->arena.get(size_t(np) * 2, &d_rows));
   {
     ProfScope ps(c, "mesh_pair_sort");
-    PQ_LAUNCH(k_mesh_pair_keys, ceil_div(np, 256), np, static_cast<const int32_t*>(d_pj),
-              static_cast<const int32_t*>(nullptr), d_k, d_v);
-    PQ_TRY(stable_sort_pairs_u32(c, &d_k, &d_v, np, bits));
-    PQ_LAUNCH(k_mesh_pair_keys, ceil_div(np, 256), np, static_cast<const int32_t*>(d_pi),
-              static_cast<const int32_t*>(d_v), d_k2, d_v2);
-    PQ_TRY(stable_sort_pairs_u32(c, &d_k2, &d_v2, np, bits));
-    PQ_LAUNCH(k_mesh_pair_rows, ceil_div(np, 256), np, static_cast<const int32_t*>(d_v2),
+    int32_t* perm = nullptr;
+    PQ_TRY(refine_order_by_key(c, np, d_pj, &perm, bits));
+    PQ_TRY(refine_order_by_key(c, np, d_pi, &perm, bits));
+    PQ_LAUNCH(k_mesh_pair_rows, ceil_div(np, 256), np, static_cast<const int32_t*>(perm),
               static_cast<const int32_t*>(d_pi), static_cast<const int32_t*>(d_pj), d_rows);
   }
   OutBufs out;
   int32_t* rows = out.get<int32_t>(size_t(np) * 2);
   if (!rows) return fail(PYQSM_ENOMEM, "pyqsm_mesh_self_intersections: no host memory for %d pairs", np);
-  PQ_HIP(hipMemcpyAsync(rows, d_rows, size_t(np) * 8, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, rows, d_rows, size_t(np) * 2));
   out.kept = true;
   *pairs = rows;
   return 0;

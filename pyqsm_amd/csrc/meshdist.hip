@@ -249,10 +249,9 @@ int pyqsm_point_mesh_distance(const float* verts, int64_t V, const int32_t* tris
     }
     return 0;
   }
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   float *d_v, *d_q, *d_dist;
   int32_t* d_t;
   uint32_t* d_prim;
@@ -267,15 +266,14 @@ int pyqsm_point_mesh_distance(const float* verts, int64_t V, const int32_t* tris
   PQ_TRY(c->arena.get(size_t(T), &d_rec));
   PQ_TRY(c->arena.get(size_t(T), &d_thin));
   PQ_TRY(c->arena.get(2, &d_flags));
-  PQ_HIP(hipMemcpyAsync(d_v, verts, size_t(V) * 12, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_t, tris, size_t(T) * 12, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_q, qry, size_t(Q) * 12, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_v, verts, size_t(V) * 3));
+  PQ_TRY(copy_in(c, d_t, tris, size_t(T) * 3));
+  PQ_TRY(copy_in(c, d_q, qry, size_t(Q) * 3));
   PQ_HIP(hipMemsetAsync(d_flags, 0, 8, c->stream));
   hipLaunchKernelGGL(k_dist_tris, dim3(ceil_div(T, 256)), dim3(256), 0, c->stream, d_v, V, d_t, T, d_rec,
                      d_thin, d_flags);
   int flags[2] = {0, 0};  // a triangle index out of range; the length of the thin list
-  PQ_HIP(hipMemcpyAsync(flags, d_flags, 8, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, flags, d_flags, 2));
   if (flags[0]) return fail(PYQSM_EINVAL, "triangle index outside the vertex array");
   {
     ProfScope ps(c, "point_mesh_distance");
@@ -283,8 +281,8 @@ int pyqsm_point_mesh_distance(const float* verts, int64_t V, const int32_t* tris
                        flags[1], int(T), d_q, Q, d_dist, d_prim);
     PQ_HIP(hipGetLastError());
   }
-  PQ_HIP(hipMemcpyAsync(dist, d_dist, size_t(Q) * 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipMemcpyAsync(prim, d_prim, size_t(Q) * 4, hipMemcpyDeviceToHost, c->stream));
+  PQ_TRY(download(c, dist, d_dist, size_t(Q)));
+  PQ_TRY(download(c, prim, d_prim, size_t(Q)));
   PQ_HIP(hipStreamSynchronize(c->stream));
   return 0;
 }

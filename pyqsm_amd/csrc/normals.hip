@@ -308,8 +308,7 @@ static int normals_device(Ctx* c, const double* d_xyz, int64_t n, double radius,
   }
   if (overflow) {
     int32_t of = 0;
-    PQ_HIP(hipMemcpyAsync(&of, overflow, 4, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipStreamSynchronize(c->stream));
+    PQ_TRY(fetch(c, &of, overflow));
     if (of) return fail(PYQSM_ERANGE, "more than %d points tie at the max_nn-th distance of a query", kNormCap);
   }
   return 0;
@@ -380,21 +379,18 @@ int pyqsm_estimate_normals(const double* xyz, int64_t n, double radius, int32_t 
   PQ_TRY(check_max_nn(radius, max_nn));
   if (n > 0 && (!xyz || !normals)) return fail(PYQSM_EINVAL, "pyqsm_estimate_normals: NULL pointer");
   if (n == 0) return 0;
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   double *d_xyz, *d_prev = nullptr, *d_out;
   PQ_TRY(c->arena.get(size_t(n) * 3, &d_xyz));
   PQ_TRY(c->arena.get(size_t(n) * 3, &d_out));
-  PQ_HIP(hipMemcpyAsync(d_xyz, xyz, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_xyz, xyz, size_t(n) * 3));
   if (prev_normals) {
-    PQ_TRY(c->arena.get(size_t(n) * 3, &d_prev));
-    PQ_HIP(hipMemcpyAsync(d_prev, prev_normals, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+    PQ_TRY(upload(c, prev_normals, size_t(n) * 3, &d_prev));
   }
   PQ_TRY(normals_device(c, d_xyz, n, radius, max_nn, d_prev, d_out));
-  PQ_HIP(hipMemcpyAsync(normals, d_out, size_t(n) * 24, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, normals, d_out, size_t(n) * 3));
   return 0;
 }
 
@@ -406,20 +402,18 @@ int pyqsm_orient_normals_tangent_plane(const double* xyz, int64_t n, const doubl
   if (n > 0 && (!xyz || !normals || !oriented)) return fail(PYQSM_EINVAL, "pyqsm_orient_normals_tangent_plane: NULL pointer");
   if (rounds) *rounds = 0;
   if (n == 0) return 0;
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   double *d_xyz, *d_nrm, *d_out;
   PQ_TRY(c->arena.get(size_t(n) * 3, &d_xyz));
   PQ_TRY(c->arena.get(size_t(n) * 3, &d_nrm));
   PQ_TRY(c->arena.get(size_t(n) * 3, &d_out));
-  PQ_HIP(hipMemcpyAsync(d_xyz, xyz, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_nrm, normals, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_xyz, xyz, size_t(n) * 3));
+  PQ_TRY(copy_in(c, d_nrm, normals, size_t(n) * 3));
   int32_t r = 0;
   PQ_TRY(orient_device(c, d_xyz, n, k, d_nrm, d_out, &r));
-  PQ_HIP(hipMemcpyAsync(oriented, d_out, size_t(n) * 24, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, oriented, d_out, size_t(n) * 3));
   if (rounds) *rounds = r;
   return 0;
 }
@@ -437,17 +431,14 @@ int pyqsm_stem_cloud(const double* xyz, int64_t n, const double* prev_normals, d
   if (std::isnan(angle_cutoff)) return fail(PYQSM_EINVAL, "angle_cutoff must not be NaN");
   if (n > 0 && (!xyz || !keep || !normals)) return fail(PYQSM_EINVAL, "pyqsm_stem_cloud: NULL pointer");
   if (n == 0) return 0;
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   const int N = int(n);
   double *d_xyz, *d_prev = nullptr;
-  PQ_TRY(c->arena.get(size_t(n) * 3, &d_xyz));
-  PQ_HIP(hipMemcpyAsync(d_xyz, xyz, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(upload(c, xyz, size_t(n) * 3, &d_xyz));
   if (prev_normals) {
-    PQ_TRY(c->arena.get(size_t(n) * 3, &d_prev));
-    PQ_HIP(hipMemcpyAsync(d_prev, prev_normals, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+    PQ_TRY(upload(c, prev_normals, size_t(n) * 3, &d_prev));
   }
   // crop: pyQSM removes z <= min z + offset, and skips the crop when that bound is exactly 0
   double mn[3], mx[3];
@@ -469,8 +460,7 @@ int pyqsm_stem_cloud(const double* xyz, int64_t n, const double* prev_normals, d
     PQ_HIP(hipGetLastError());
     PQ_TRY(compact_flagged(c, pos, n, c_idx, nullptr, d_xyz, nx, d_prev, np));
     int32_t cnt = 0;
-    PQ_HIP(hipMemcpyAsync(&cnt, pos + n, 4, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipStreamSynchronize(c->stream));
+    PQ_TRY(fetch(c, &cnt, pos + n));
     m = cnt;
     if (m == 0) return 0;
     cxyz = nx;
@@ -496,11 +486,10 @@ int pyqsm_stem_cloud(const double* xyz, int64_t n, const double* prev_normals, d
     PQ_TRY(compact_flagged(c, pos, m, k_idx, c_idx, ori, k_nrm));
   }
   int32_t cnt = 0;
-  PQ_HIP(hipMemcpyAsync(&cnt, pos + m, 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, &cnt, pos + m));
   if (cnt > 0) {
-    PQ_HIP(hipMemcpyAsync(keep, k_idx, size_t(cnt) * 8, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipMemcpyAsync(normals, k_nrm, size_t(cnt) * 24, hipMemcpyDeviceToHost, c->stream));
+    PQ_TRY(download(c, keep, k_idx, size_t(cnt)));
+    PQ_TRY(download(c, normals, k_nrm, size_t(cnt) * 3));
     PQ_HIP(hipStreamSynchronize(c->stream));
   }
   *m_out = cnt;

@@ -209,17 +209,16 @@ int pyqsm_ball_query(const double* xyz, int64_t n, const double center[3], doubl
     return fail(PYQSM_EINVAL, "pyqsm_ball_query: NULL pointer");
   if (!(radius >= 0)) return fail(PYQSM_EINVAL, "radius must be >= 0");
   if (n > 0x7FFFFF00LL) return fail(PYQSM_ERANGE, "more than 2^31 points per call");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   double* d_xyz;
   int32_t* d_flags;
   int64_t* d_out;
   PQ_TRY(c->arena.get(size_t(n) * 3, &d_xyz));
   PQ_TRY(c->arena.get(size_t(n) + 1, &d_flags));
   PQ_TRY(c->arena.get(size_t(n), &d_out));
-  PQ_HIP(hipMemcpyAsync(d_xyz, xyz, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_xyz, xyz, size_t(n) * 3));
   {
     ProfScope ps(c, "ball_query");
     hipLaunchKernelGGL(k_ball_flags, dim3(ceil_div(n + 1, 256)), dim3(256), 0, c->stream, n, d_xyz,
@@ -227,10 +226,9 @@ int pyqsm_ball_query(const double* xyz, int64_t n, const double center[3], doubl
     PQ_TRY(compact_flagged(c, d_flags, n, d_out));
   }
   int32_t total = 0;
-  PQ_HIP(hipMemcpyAsync(&total, d_flags + n, 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, &total, d_flags + n));
   if (total)
-    PQ_HIP(hipMemcpyAsync(out_idx, d_out, size_t(total) * 8, hipMemcpyDeviceToHost, c->stream));
+    PQ_TRY(download(c, out_idx, d_out, size_t(total)));
   PQ_HIP(hipStreamSynchronize(c->stream));
   *count = total;
   return 0;
@@ -248,10 +246,9 @@ int pyqsm_radius_mark(const double* src, int64_t n, const double* qry, int64_t m
   if (m > 0) memset(counts, 0, size_t(m) * 4);
   if (n == 0 || m == 0) return 0;
   if (m > 0x7FFFFF00LL) return fail(PYQSM_ERANGE, "more than 2^31 query points per call");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   double *d_src, *d_qry;
   uint8_t* d_mark;
   int32_t* d_counts;
@@ -259,8 +256,8 @@ int pyqsm_radius_mark(const double* src, int64_t n, const double* qry, int64_t m
   PQ_TRY(c->arena.get(size_t(m) * 3, &d_qry));
   PQ_TRY(c->arena.get(size_t(n), &d_mark));
   PQ_TRY(c->arena.get(size_t(m), &d_counts));
-  PQ_HIP(hipMemcpyAsync(d_src, src, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_qry, qry, size_t(m) * 24, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_src, src, size_t(n) * 3));
+  PQ_TRY(copy_in(c, d_qry, qry, size_t(m) * 3));
   PQ_HIP(hipMemsetAsync(d_mark, 0, size_t(n), c->stream));
   DevGrid g;
   PQ_TRY(radius_grid(c, d_src, n, radius, &g));
@@ -277,8 +274,8 @@ int pyqsm_radius_mark(const double* src, int64_t n, const double* qry, int64_t m
     });
     PQ_HIP(hipGetLastError());
   }
-  PQ_HIP(hipMemcpyAsync(mark, d_mark, size_t(n), hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipMemcpyAsync(counts, d_counts, size_t(m) * 4, hipMemcpyDeviceToHost, c->stream));
+  PQ_TRY(download(c, mark, d_mark, size_t(n)));
+  PQ_TRY(download(c, counts, d_counts, size_t(m)));
   PQ_HIP(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -300,18 +297,17 @@ int pyqsm_radius_knn(const double* src, int64_t n, const double* qry, int64_t m,
     }
     return 0;
   }
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   double *d_src, *d_qry, *d_dist;
   int64_t* d_idx;
   PQ_TRY(c->arena.get(size_t(n) * 3, &d_src));
   PQ_TRY(c->arena.get(size_t(m) * 3, &d_qry));
   PQ_TRY(c->arena.get(size_t(m) * k, &d_idx));
   PQ_TRY(c->arena.get(size_t(m) * k, &d_dist));
-  PQ_HIP(hipMemcpyAsync(d_src, src, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_qry, qry, size_t(m) * 24, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_src, src, size_t(n) * 3));
+  PQ_TRY(copy_in(c, d_qry, qry, size_t(m) * 3));
   DevGrid g;
   PQ_TRY(radius_grid(c, d_src, n, radius, &g));
   const GridParams rg = grid_params(g);
@@ -323,8 +319,8 @@ int pyqsm_radius_knn(const double* src, int64_t n, const double* qry, int64_t m,
     });
     PQ_HIP(hipGetLastError());
   }
-  PQ_HIP(hipMemcpyAsync(idx, d_idx, size_t(m) * k * 8, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipMemcpyAsync(dist, d_dist, size_t(m) * k * 8, hipMemcpyDeviceToHost, c->stream));
+  PQ_TRY(download(c, idx, d_idx, size_t(m) * k));
+  PQ_TRY(download(c, dist, d_dist, size_t(m) * k));
   PQ_HIP(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -349,15 +345,14 @@ int pyqsm_radius_reduce(const double* src, int64_t n, const double* qry, int64_t
     if (counts) memset(counts, 0, size_t(m) * 4);
     return 0;
   }
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   double *d_src, *d_val;
   PQ_TRY(c->arena.get(size_t(n) * 3, &d_src));
   PQ_TRY(c->arena.get(size_t(n) * F, &d_val));
-  PQ_HIP(hipMemcpyAsync(d_src, src, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_val, values, size_t(n) * F * 8, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_src, src, size_t(n) * 3));
+  PQ_TRY(copy_in(c, d_val, values, size_t(n) * F));
   DevGrid g;
   PQ_TRY(radius_grid(c, d_src, n, radius, &g));
   const GridParams rg = grid_params(g);
@@ -371,7 +366,7 @@ int pyqsm_radius_reduce(const double* src, int64_t n, const double* qry, int64_t
   if (counts) PQ_TRY(c->arena.get(size_t(chunk), &d_cnt));
   for (int64_t r0 = 0; r0 < m; r0 += chunk) {
     const int64_t mc = std::min(chunk, m - r0);
-    PQ_HIP(hipMemcpyAsync(d_qry, qry + size_t(r0) * 3, size_t(mc) * 24, hipMemcpyHostToDevice, c->stream));
+    PQ_TRY(copy_in(c, d_qry, qry + size_t(r0) * 3, size_t(mc) * 3));
     {
       ProfScope ps(c, "radius_reduce");
       on_coords(g, [&](auto co) {
@@ -381,8 +376,8 @@ int pyqsm_radius_reduce(const double* src, int64_t n, const double* qry, int64_t
       });
       PQ_HIP(hipGetLastError());
     }
-    PQ_HIP(hipMemcpyAsync(out + size_t(r0) * F, d_out, size_t(mc) * F * 8, hipMemcpyDeviceToHost, c->stream));
-    if (counts) PQ_HIP(hipMemcpyAsync(counts + r0, d_cnt, size_t(mc) * 4, hipMemcpyDeviceToHost, c->stream));
+    PQ_TRY(download(c, out + size_t(r0) * F, d_out, size_t(mc) * F));
+    if (counts) PQ_TRY(download(c, counts + r0, d_cnt, size_t(mc)));
   }
   PQ_HIP(hipStreamSynchronize(c->stream));
   return 0;
@@ -404,10 +399,9 @@ int pyqsm_radius_label(const double* src, int64_t n, const double* qry, int64_t 
   for (int64_t i = 0; i < m; ++i)
     if (qry_label[i] < 0) return fail(PYQSM_EINVAL, "query labels must be >= 0");
   if (m > 0x7FFFFF00LL) return fail(PYQSM_ERANGE, "more than 2^31 query points per call");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   double *d_src, *d_qry;
   int32_t *d_lab, *d_counts, *d_qlab;
   uint8_t* d_mark;
@@ -417,9 +411,9 @@ int pyqsm_radius_label(const double* src, int64_t n, const double* qry, int64_t 
   PQ_TRY(c->arena.get(size_t(m), &d_counts));
   PQ_TRY(c->arena.get(size_t(m), &d_qlab));
   PQ_TRY(c->arena.get(1, &d_mark));
-  PQ_HIP(hipMemcpyAsync(d_src, src, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_qry, qry, size_t(m) * 24, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_qlab, qry_label, size_t(m) * 4, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_src, src, size_t(n) * 3));
+  PQ_TRY(copy_in(c, d_qry, qry, size_t(m) * 3));
+  PQ_TRY(copy_in(c, d_qlab, qry_label, size_t(m)));
   PQ_HIP(hipMemsetAsync(d_lab, 0x7F, size_t(n) * 4, c->stream));  // 0x7F7F7F7F > any label
   DevGrid g;
   PQ_TRY(radius_grid(c, d_src, n, radius, &g));
@@ -435,8 +429,8 @@ int pyqsm_radius_label(const double* src, int64_t n, const double* qry, int64_t 
     });
     PQ_HIP(hipGetLastError());
   }
-  PQ_HIP(hipMemcpyAsync(label, d_lab, size_t(n) * 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipMemcpyAsync(counts, d_counts, size_t(m) * 4, hipMemcpyDeviceToHost, c->stream));
+  PQ_TRY(download(c, label, d_lab, size_t(n)));
+  PQ_TRY(download(c, counts, d_counts, size_t(m)));
   PQ_HIP(hipStreamSynchronize(c->stream));
   for (int64_t i = 0; i < n; ++i)
     if (label[i] == 0x7F7F7F7F) label[i] = -1;

@@ -646,8 +646,7 @@ static int plane_pick(Ctx* c, const double* d_pts, int64_t n, const PlaneScratch
                       double probability, int64_t* best, int64_t* best_cnt, int64_t* used) {
   PQ_TRY(count_on_device(c, d_pts, n, s.models, H, 2, thresh, s.counts));
   std::vector<int32_t> h_counts(size_t(H), 0);
-  PQ_HIP(hipMemcpyAsync(h_counts.data(), s.counts, size_t(H) * 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, h_counts.data(), s.counts, size_t(H)));
   plane_select(h_counts.data(), H, n, m, probability, best, best_cnt, used);
   return 0;
 }
@@ -718,24 +717,21 @@ int pyqsm_ransac_models(const double* pts, int64_t n, const int64_t* triples, in
   PQ_TRY(check_args(pts, n, H, 0));
   if (H == 0) return 0;
   if (!triples || !models) return fail(PYQSM_EINVAL, "pyqsm_ransac_models: NULL pointer");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   double* d_pts;
   int64_t* d_tri;
   Model* d_models;
   PQ_TRY(c->arena.get(size_t(n) * 3 + 1, &d_pts));
   PQ_TRY(c->arena.get(size_t(H) * 3, &d_tri));
   PQ_TRY(c->arena.get(size_t(H), &d_models));
-  if (n) PQ_HIP(hipMemcpyAsync(d_pts, pts, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_tri, triples, size_t(H) * 24, hipMemcpyHostToDevice, c->stream));
+  if (n) PQ_TRY(copy_in(c, d_pts, pts, size_t(n) * 3));
+  PQ_TRY(copy_in(c, d_tri, triples, size_t(H) * 3));
   hipLaunchKernelGGL(k_models, dim3(ceil_div(H, 256)), dim3(256), 0, c->stream, d_pts, n, d_tri, H,
                      d_models);
   PQ_HIP(hipGetLastError());
-  PQ_HIP(hipMemcpyAsync(models, d_models, size_t(H) * sizeof(Model), hipMemcpyDeviceToHost,
-                        c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, reinterpret_cast<Model*>(models), d_models, size_t(H)));
   return 0;
 }
 
@@ -745,22 +741,19 @@ int pyqsm_ransac_count(const double* pts, int64_t n, const double* models, int64
   PQ_TRY(check_args(pts, n, H, shape));
   if (H == 0) return 0;
   if (!models || !counts) return fail(PYQSM_EINVAL, "pyqsm_ransac_count: NULL pointer");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   double* d_pts;
   Model* d_models;
   int32_t* d_counts;
   PQ_TRY(c->arena.get(size_t(n) * 3 + 1, &d_pts));
   PQ_TRY(c->arena.get(size_t(H), &d_models));
   PQ_TRY(c->arena.get(size_t(H), &d_counts));
-  if (n) PQ_HIP(hipMemcpyAsync(d_pts, pts, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_models, models, size_t(H) * sizeof(Model), hipMemcpyHostToDevice,
-                        c->stream));
+  if (n) PQ_TRY(copy_in(c, d_pts, pts, size_t(n) * 3));
+  PQ_TRY(copy_in(c, d_models, reinterpret_cast<const Model*>(models), size_t(H)));
   PQ_TRY(count_on_device(c, d_pts, n, d_models, H, shape, thresh, d_counts));
-  PQ_HIP(hipMemcpyAsync(counts, d_counts, size_t(H) * 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, counts, d_counts, size_t(H)));
   return 0;
 }
 
@@ -774,10 +767,9 @@ int pyqsm_ransac(const double* pts, int64_t n, const int64_t* triples, int64_t H
   if (n == 0 || H == 0) return 0;
   if (!triples || !center || !axis || !radius || !inliers || !n_inliers)
     return fail(PYQSM_EINVAL, "pyqsm_ransac: NULL pointer");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   double* d_pts;
   int64_t *d_tri, *d_out;
   Model* d_models;
@@ -788,8 +780,8 @@ int pyqsm_ransac(const double* pts, int64_t n, const int64_t* triples, int64_t H
   PQ_TRY(c->arena.get(size_t(H), &d_counts));
   PQ_TRY(c->arena.get(size_t(n) + 1, &d_flags));
   PQ_TRY(c->arena.get(size_t(n), &d_out));
-  PQ_HIP(hipMemcpyAsync(d_pts, pts, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_tri, triples, size_t(H) * 24, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_pts, pts, size_t(n) * 3));
+  PQ_TRY(copy_in(c, d_tri, triples, size_t(H) * 3));
   {
     ProfScope ps(c, "ransac_models");
     hipLaunchKernelGGL(k_models, dim3(ceil_div(H, 256)), dim3(256), 0, c->stream, d_pts, n, d_tri,
@@ -798,9 +790,7 @@ int pyqsm_ransac(const double* pts, int64_t n, const int64_t* triples, int64_t H
   }
   PQ_TRY(count_on_device(c, d_pts, n, d_models, H, shape, thresh, d_counts));
   std::vector<int32_t> h_counts(size_t(H), 0);
-  PQ_HIP(hipMemcpyAsync(h_counts.data(), d_counts, size_t(H) * 4, hipMemcpyDeviceToHost,
-                        c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, h_counts.data(), d_counts, size_t(H)));
   // first hypothesis with a strictly larger count wins (best starts empty)
   int64_t best = -1;
   int32_t best_cnt = 0;
@@ -823,9 +813,8 @@ int pyqsm_ransac(const double* pts, int64_t n, const int64_t* triples, int64_t H
     PQ_TRY(compact_flagged(c, d_flags, n, d_out));
   }
   Model m;
-  PQ_HIP(hipMemcpyAsync(&m, d_models + best, sizeof(Model), hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipMemcpyAsync(inliers, d_out, size_t(best_cnt) * 8, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(download(c, &m, d_models + best, 1));
+  PQ_TRY(fetch(c, inliers, d_out, size_t(best_cnt)));
   center[0] = m.cx; center[1] = m.cy; center[2] = m.cz;
   axis[0] = m.ax; axis[1] = m.ay; axis[2] = m.az;
   *radius = m.r;
@@ -861,10 +850,9 @@ int pyqsm_ransac_batch(const double* pts, int64_t n, const int64_t* seg_start, i
   if (n == 0 || H == 0) return 0;
   if (!triples) return fail(PYQSM_EINVAL, "pyqsm_ransac_batch: triples is NULL");
   if (double(n_seg) * double(H) > 2.0e9) return fail(PYQSM_ERANGE, "more than 2^31 hypotheses per call");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   const int64_t S = n_seg, SH = S * H;
   // the tiles of all sets
   std::vector<int32_t> h_tile_set;
@@ -893,11 +881,11 @@ int pyqsm_ransac_batch(const double* pts, int64_t n, const int64_t* seg_start, i
   PQ_TRY(c->arena.get(size_t(n) + 1, &d_flags));
   PQ_TRY(c->arena.get(size_t(n), &d_set_of));
   PQ_TRY(c->arena.get(size_t(n), &d_out));
-  PQ_HIP(hipMemcpyAsync(d_pts, pts, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_seg, seg_start, (size_t(S) + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_tri, triples, size_t(SH) * 24, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_tile_base, h_tile_base.data(), size_t(tiles) * 8, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_tile_set, h_tile_set.data(), size_t(tiles) * 4, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_pts, pts, size_t(n) * 3));
+  PQ_TRY(copy_in(c, d_seg, seg_start, size_t(S) + 1));
+  PQ_TRY(copy_in(c, d_tri, triples, size_t(SH) * 3));
+  PQ_TRY(copy_in(c, d_tile_base, h_tile_base.data(), size_t(tiles)));
+  PQ_TRY(copy_in(c, d_tile_set, h_tile_set.data(), size_t(tiles)));
   PQ_HIP(hipMemsetAsync(d_counts, 0, size_t(SH) * 4, c->stream));
   {
     ProfScope ps(c, "ransac_models");
@@ -937,14 +925,13 @@ int pyqsm_ransac_batch(const double* pts, int64_t n, const int64_t* seg_start, i
   std::vector<Model> h_win(static_cast<size_t>(S), Model{0, 0, 0, 0, 0, 0, 0, 0});
   std::vector<int32_t> h_cnt(static_cast<size_t>(S), 0);
   int32_t total = 0;
-  PQ_HIP(hipMemcpyAsync(h_win.data(), d_win, size_t(S) * sizeof(Model), hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipMemcpyAsync(h_cnt.data(), d_best_cnt, size_t(S) * 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipMemcpyAsync(best_out, d_best, size_t(S) * 8, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipMemcpyAsync(&total, d_flags + n, 4, hipMemcpyDeviceToHost, c->stream));
+  PQ_TRY(download(c, h_win.data(), d_win, size_t(S)));
+  PQ_TRY(download(c, h_cnt.data(), d_best_cnt, size_t(S)));
+  PQ_TRY(download(c, best_out, d_best, size_t(S)));
+  PQ_TRY(download(c, &total, d_flags + n, 1));
   PQ_HIP(hipStreamSynchronize(c->stream));
   if (total > 0) {
-    PQ_HIP(hipMemcpyAsync(inliers, d_out, size_t(total) * 8, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipStreamSynchronize(c->stream));
+    PQ_TRY(fetch(c, inliers, d_out, size_t(total)));
   }
   for (int64_t s = 0; s < S; ++s) {
     const Model& m = h_win[size_t(s)];
@@ -964,10 +951,9 @@ int pyqsm_plane_models(const double* pts, int64_t n, const int64_t* samples, int
   PQ_TRY(plane_check("pyqsm_plane_models", pts, n, H, m, false, 1.0, 1.0, axis, cos_limit));
   if (H == 0) return 0;
   if (!samples || !planes) return fail(PYQSM_EINVAL, "pyqsm_plane_models: NULL pointer");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   double *d_pts, *d_planes;
   int64_t* d_smp;
   Model* d_models;
@@ -975,11 +961,10 @@ int pyqsm_plane_models(const double* pts, int64_t n, const int64_t* samples, int
   PQ_TRY(c->arena.get(size_t(H) * m, &d_smp));
   PQ_TRY(c->arena.get(size_t(H), &d_models));
   PQ_TRY(c->arena.get(size_t(H) * 4, &d_planes));
-  if (n) PQ_HIP(hipMemcpyAsync(d_pts, pts, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_smp, samples, size_t(H) * m * 8, hipMemcpyHostToDevice, c->stream));
+  if (n) PQ_TRY(copy_in(c, d_pts, pts, size_t(n) * 3));
+  PQ_TRY(copy_in(c, d_smp, samples, size_t(H) * m));
   PQ_TRY(plane_models_device(c, d_pts, n, d_smp, false, H, m, cone_of(axis, cos_limit), d_models, d_planes));
-  PQ_HIP(hipMemcpyAsync(planes, d_planes, size_t(H) * 32, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, planes, d_planes, size_t(H) * 4));
   return 0;
 }
 
@@ -995,21 +980,19 @@ int pyqsm_plane_count(const double* pts, int64_t n, const double* planes, int64_
     const bool ok = p[0] != 0.0 || p[1] != 0.0 || p[2] != 0.0;
     h_models[size_t(h)] = Model{0.0, 0.0, 0.0, p[0], p[1], p[2], p[3], ok ? 1.0 : 0.0};
   }
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   double* d_pts;
   Model* d_models;
   int32_t* d_counts;
   PQ_TRY(c->arena.get(size_t(n) * 3 + 1, &d_pts));
   PQ_TRY(c->arena.get(size_t(H), &d_models));
   PQ_TRY(c->arena.get(size_t(H), &d_counts));
-  if (n) PQ_HIP(hipMemcpyAsync(d_pts, pts, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_models, h_models.data(), size_t(H) * sizeof(Model), hipMemcpyHostToDevice, c->stream));
+  if (n) PQ_TRY(copy_in(c, d_pts, pts, size_t(n) * 3));
+  PQ_TRY(copy_in(c, d_models, h_models.data(), size_t(H)));
   PQ_TRY(count_on_device(c, d_pts, n, d_models, H, 2, thresh, d_counts));
-  PQ_HIP(hipMemcpyAsync(counts, d_counts, size_t(H) * 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, counts, d_counts, size_t(H)));
   return 0;
 }
 
@@ -1027,10 +1010,9 @@ int pyqsm_segment_plane(const double* pts, int64_t n, const int64_t* samples, in
   *used_out = 0;
   if (H == 0) return 0;
   if (!samples) return fail(PYQSM_EINVAL, "pyqsm_segment_plane: samples is NULL");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   double *d_pts, *d_out;
   int64_t *d_smp, *d_idx;
   PlaneScratch s;
@@ -1039,8 +1021,8 @@ int pyqsm_segment_plane(const double* pts, int64_t n, const int64_t* samples, in
   PQ_TRY(c->arena.get(size_t(n), &d_idx));
   PQ_TRY(c->arena.get(8, &d_out));
   PQ_TRY(plane_scratch(c, n, H, &s));
-  PQ_HIP(hipMemcpyAsync(d_pts, pts, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_smp, samples, size_t(H) * m * 8, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_pts, pts, size_t(n) * 3));
+  PQ_TRY(copy_in(c, d_smp, samples, size_t(H) * m));
   PQ_TRY(plane_models_device(c, d_pts, n, d_smp, false, H, m, cone_of(axis, cos_limit), s.models, s.planes));
   int64_t best = -1, bc = 0, used = 0;
   PQ_TRY(plane_pick(c, d_pts, n, s, H, m, thresh, probability, &best, &bc, &used));
@@ -1049,8 +1031,8 @@ int pyqsm_segment_plane(const double* pts, int64_t n, const int64_t* samples, in
   PQ_TRY(plane_flag(c, d_pts, n, s, best, thresh, d_idx));
   PQ_TRY(plane_refit(c, d_pts, n, s, best, d_out, d_out + 4));
   double h_out[8];
-  PQ_HIP(hipMemcpyAsync(h_out, d_out, 64, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipMemcpyAsync(inliers, d_idx, size_t(bc) * 8, hipMemcpyDeviceToHost, c->stream));
+  PQ_TRY(download(c, h_out, d_out, 8));
+  PQ_TRY(download(c, inliers, d_idx, size_t(bc)));
   PQ_HIP(hipStreamSynchronize(c->stream));
   for (int a = 0; a < 4; ++a) {
     plane_fit[a] = h_out[a];
@@ -1083,10 +1065,9 @@ int pyqsm_segment_planes(const double* pts, int64_t n, const uint64_t* draws, in
   *n_planes = 0;
   if (H == 0) return 0;
   if (!draws) return fail(PYQSM_EINVAL, "pyqsm_segment_planes: draws is NULL");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   // the loop's scratch, taken once
   double *d_pts, *d_alive_pts, *d_out;
   uint64_t* d_draws;
@@ -1102,8 +1083,8 @@ int pyqsm_segment_planes(const double* pts, int64_t n, const uint64_t* draws, in
   PQ_TRY(c->arena.get(size_t(n) + 1, &d_aflags));
   PQ_TRY(c->arena.get(size_t(P) * 8, &d_out));
   PQ_TRY(plane_scratch(c, n, H, &s));
-  PQ_HIP(hipMemcpyAsync(d_pts, pts, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_draws, draws, size_t(P) * per_round * 8, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_pts, pts, size_t(n) * 3));
+  PQ_TRY(copy_in(c, d_draws, draws, size_t(P) * per_round));
   PQ_HIP(hipMemsetAsync(d_labels, 0xFF, size_t(n) * 4, c->stream));  // -1: alive
   const Cone cone = cone_of(axis, cos_limit);
   int64_t n_alive = n, np = 0;
@@ -1133,8 +1114,8 @@ int pyqsm_segment_planes(const double* pts, int64_t n, const uint64_t* draws, in
     c->arena.rewind(mk);
   }
   std::vector<double> h_out(size_t(P) * 8, 0.0);
-  PQ_HIP(hipMemcpyAsync(labels, d_labels, size_t(n) * 4, hipMemcpyDeviceToHost, c->stream));
-  if (np) PQ_HIP(hipMemcpyAsync(h_out.data(), d_out, size_t(np) * 64, hipMemcpyDeviceToHost, c->stream));
+  PQ_TRY(download(c, labels, d_labels, size_t(n)));
+  if (np) PQ_TRY(download(c, h_out.data(), d_out, size_t(np) * 8));
   PQ_HIP(hipStreamSynchronize(c->stream));
   for (int64_t r = 0; r < np; ++r)
     for (int a = 0; a < 4; ++a) {

@@ -953,8 +953,7 @@ static int launch_cast(Ctx* c, const TriRec* tri, int64_t T, const float* rays, 
                      c->stream, rays, R, d_flag);
   PQ_HIP(hipGetLastError());
   int uni_bits = 0;
-  PQ_HIP(hipMemcpyAsync(&uni_bits, d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, &uni_bits, d_flag));
   const int varied = uni_bits & 1;          // directions differ
   const bool one_origin = !(uni_bits & 2);  // every ray starts at ray 0's origin
   // Rays per lane: 8 when there are enough rays to fill the chip that way,
@@ -973,8 +972,7 @@ static int launch_cast(Ctx* c, const TriRec* tri, int64_t T, const float* rays, 
   if (!varied && cull && T >= 4 * kCluster) {
     // ---- sort triangles on the plane normal to d, build clusters, culled sweep ------
     float hd[3];
-    PQ_HIP(hipMemcpyAsync(hd, rays + 3, 12, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipStreamSynchronize(c->stream));
+    PQ_TRY(fetch(c, hd, rays + 3, 3));
     const double dn = std::sqrt(double(hd[0]) * hd[0] + double(hd[1]) * hd[1] + double(hd[2]) * hd[2]);
     if (dn > 0.0 && std::isfinite(dn)) {
       const double d[3] = {hd[0] / dn, hd[1] / dn, hd[2] / dn};
@@ -984,8 +982,7 @@ static int launch_cast(Ctx* c, const TriRec* tri, int64_t T, const float* rays, 
       double u[3] = {0, 0, 0}, un = 0.0;
       if (R >= 2) {
         float ho[12];
-        PQ_HIP(hipMemcpyAsync(ho, rays, 48, hipMemcpyDeviceToHost, c->stream));
-        PQ_HIP(hipStreamSynchronize(c->stream));
+        PQ_TRY(fetch(c, ho, rays, 12));
         const double s0[3] = {double(ho[6]) - ho[0], double(ho[7]) - ho[1], double(ho[8]) - ho[2]};
         const double along = s0[0] * d[0] + s0[1] * d[1] + s0[2] * d[2];
         for (int a = 0; a < 3; ++a) u[a] = s0[a] - along * d[a];
@@ -1056,8 +1053,8 @@ static int launch_cast(Ctx* c, const TriRec* tri, int64_t T, const float* rays, 
                        c->stream, rays, R, d_sum);
     double hs[3];
     float ho[12];
-    PQ_HIP(hipMemcpyAsync(hs, d_sum, 24, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipMemcpyAsync(ho, rays, 48, hipMemcpyDeviceToHost, c->stream));
+    PQ_TRY(download(c, hs, d_sum, 3));
+    PQ_TRY(download(c, ho, rays, 12));
     PQ_HIP(hipStreamSynchronize(c->stream));
     const double nn = std::sqrt(hs[0] * hs[0] + hs[1] * hs[1] + hs[2] * hs[2]);
     if (nn > 1e-3 * double(R) && std::isfinite(nn)) {
@@ -1100,8 +1097,7 @@ static int launch_cast(Ctx* c, const TriRec* tri, int64_t T, const float* rays, 
       double mn[3], mx[3];
       PQ_TRY(cloud_bbox(c, img, R, mn, mx));  // synchronises
       int bad = 0;
-      PQ_HIP(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, c->stream));
-      PQ_HIP(hipStreamSynchronize(c->stream));
+      PQ_TRY(fetch(c, &bad, d_bad));
       if (!bad) {
         double ext = std::max(mx[0] - mn[0], mx[1] - mn[1]);
         if (!(ext > 0)) ext = 1.0;
@@ -1189,8 +1185,7 @@ static int expand(Ctx* c, const float* verts, int64_t V, const int32_t* tris, in
                      T, out, bad);
   PQ_HIP(hipGetLastError());
   int h = 0;
-  PQ_HIP(hipMemcpyAsync(&h, bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, &h, bad));
   if (h) return fail(PYQSM_EINVAL, "triangle index outside [0, V)");
   return 0;
 }
@@ -1224,10 +1219,9 @@ int pyqsm_expand_tris_dev(const float* verts_dev, int64_t V, const int32_t* tris
   PQ_TRY(check_sizes(V, T, 0));
   if (T > 0 && (!verts_dev || !tris_dev || !tri12_dev))
     return fail(PYQSM_EINVAL, "pyqsm_expand_tris_dev: NULL pointer");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   return expand(c, verts_dev, V, tris_dev, T, reinterpret_cast<TriRec*>(tri12_dev));
 }
 
@@ -1237,10 +1231,9 @@ int pyqsm_cast_rays_dev(const float* tri12_dev, int64_t T, const float* rays_dev
   PQ_TRY(check_sizes(0, T, R));
   if (R > 0 && (!rays_dev || !t_hit_dev || !prim_id_dev || (T > 0 && !tri12_dev)))
     return fail(PYQSM_EINVAL, "pyqsm_cast_rays_dev: NULL pointer");
-  Ctx* c = ctx_for(device);
+  Call call(device);  // scratch of the previous call (per-direction records, sort buffers)
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();  // scratch of the previous call (per-direction records, sort buffers)
   return launch_cast(c, reinterpret_cast<const TriRec*>(tri12_dev), T, rays_dev, R, t_hit_dev,
                      prim_id_dev, uv_dev);
 }
@@ -1253,10 +1246,9 @@ int pyqsm_cast_rays(const float* verts, int64_t V, const int32_t* tris, int64_t 
   if (R == 0) return 0;
   if (!rays || !t_hit || !prim_id || (T > 0 && (!verts || !tris)))
     return fail(PYQSM_EINVAL, "pyqsm_cast_rays: NULL pointer");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   float *d_verts, *d_rays, *d_t, *d_uv = nullptr;
   int32_t* d_tris;
   uint32_t* d_p;
@@ -1269,15 +1261,15 @@ int pyqsm_cast_rays(const float* verts, int64_t V, const int32_t* tris, int64_t 
   PQ_TRY(c->arena.get(size_t(R), &d_p));
   if (uv) PQ_TRY(c->arena.get(size_t(R) * 2, &d_uv));
   if (T > 0) {
-    PQ_HIP(hipMemcpyAsync(d_verts, verts, size_t(V) * 12, hipMemcpyHostToDevice, c->stream));
-    PQ_HIP(hipMemcpyAsync(d_tris, tris, size_t(T) * 12, hipMemcpyHostToDevice, c->stream));
+    PQ_TRY(copy_in(c, d_verts, verts, size_t(V) * 3));
+    PQ_TRY(copy_in(c, d_tris, tris, size_t(T) * 3));
   }
-  PQ_HIP(hipMemcpyAsync(d_rays, rays, size_t(R) * 24, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_rays, rays, size_t(R) * 6));
   PQ_TRY(expand(c, d_verts, V, d_tris, T, d_rec));
   PQ_TRY(launch_cast(c, d_rec, T, d_rays, R, d_t, d_p, d_uv));
-  PQ_HIP(hipMemcpyAsync(t_hit, d_t, size_t(R) * 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipMemcpyAsync(prim_id, d_p, size_t(R) * 4, hipMemcpyDeviceToHost, c->stream));
-  if (uv) PQ_HIP(hipMemcpyAsync(uv, d_uv, size_t(R) * 8, hipMemcpyDeviceToHost, c->stream));
+  PQ_TRY(download(c, t_hit, d_t, size_t(R)));
+  PQ_TRY(download(c, prim_id, d_p, size_t(R)));
+  if (uv) PQ_TRY(download(c, uv, d_uv, size_t(R) * 2));
   PQ_HIP(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -1300,8 +1292,7 @@ int pyqsm_list_intersections(const float* verts, int64_t V, const int32_t* tris,
     memset(counts, 0, size_t(R) * 4);
     return 0;
   }
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
+  Call call(c);
   float *d_verts, *d_rays;
   int32_t *d_tris, *d_counts;
   TriRec* d_rec;
@@ -1313,9 +1304,9 @@ int pyqsm_list_intersections(const float* verts, int64_t V, const int32_t* tris,
   PQ_TRY(c->arena.get(size_t(R), &d_counts));
   PQ_TRY(c->arena.get(size_t(R), &d_off));
   PQ_TRY(c->arena.get(1, &d_total));
-  PQ_HIP(hipMemcpyAsync(d_verts, verts, size_t(V) * 12, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_tris, tris, size_t(T) * 12, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_rays, rays, size_t(R) * 24, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_verts, verts, size_t(V) * 3));
+  PQ_TRY(copy_in(c, d_tris, tris, size_t(T) * 3));
+  PQ_TRY(copy_in(c, d_rays, rays, size_t(R) * 6));
   PQ_TRY(expand(c, d_verts, V, d_tris, T, d_rec));
   const dim3 grid(ceil_div(R, 256));
   {
@@ -1324,13 +1315,12 @@ int pyqsm_list_intersections(const float* verts, int64_t V, const int32_t* tris,
                        d_counts, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
     PQ_HIP(hipGetLastError());
   }
-  PQ_HIP(hipMemcpyAsync(counts, d_counts, size_t(R) * 4, hipMemcpyDeviceToHost, c->stream));
+  PQ_TRY(download(c, counts, d_counts, size_t(R)));
   hipLaunchKernelGGL(k_scan_counts_serial, dim3(1), dim3(1024), 0, c->stream, d_counts, R, d_off,
                      d_total);
   PQ_HIP(hipGetLastError());
   int64_t total = 0;
-  PQ_HIP(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, &total, d_total));
   if (n_hits) *n_hits = total;
   if (hits_cap > 0 && total > 0) {
     const int64_t cap = hits_cap < total ? hits_cap : total;
@@ -1343,10 +1333,10 @@ int pyqsm_list_intersections(const float* verts, int64_t V, const int32_t* tris,
     hipLaunchKernelGGL(k_all_hits<1>, grid, dim3(256), 0, c->stream, d_rec, int(T), d_rays, R,
                        nullptr, d_off, cap, d_r, d_p, d_t, d_uv);
     PQ_HIP(hipGetLastError());
-    PQ_HIP(hipMemcpyAsync(ray_ids, d_r, size_t(cap) * 4, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipMemcpyAsync(prim_ids, d_p, size_t(cap) * 4, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipMemcpyAsync(t, d_t, size_t(cap) * 4, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipMemcpyAsync(uv, d_uv, size_t(cap) * 8, hipMemcpyDeviceToHost, c->stream));
+    PQ_TRY(download(c, ray_ids, d_r, size_t(cap)));
+    PQ_TRY(download(c, prim_ids, d_p, size_t(cap)));
+    PQ_TRY(download(c, t, d_t, size_t(cap)));
+    PQ_TRY(download(c, uv, d_uv, size_t(cap) * 2));
     PQ_HIP(hipStreamSynchronize(c->stream));
   }
   return 0;

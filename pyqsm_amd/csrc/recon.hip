@@ -418,16 +418,6 @@ __global__ __launch_bounds__(256) void k_recon_half_edges(int n_he, const int4* 
   ev[h] = k == 0 ? r.y : k == 1 ? r.z : r.x;
 }
 
-__global__ __launch_bounds__(256) void k_recon_sort_init(int e, const int32_t* __restrict__ key_src,
-                                                         const int32_t* __restrict__ perm /*may be null*/,
-                                                         uint32_t* __restrict__ keys, int32_t* __restrict__ vals) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= e) return;
-  const int j = perm ? perm[i] : i;
-  keys[i] = uint32_t(key_src[j]);
-  vals[i] = j;
-}
-
 __global__ __launch_bounds__(256) void k_recon_permute2(int e, const int32_t* __restrict__ perm,
                                                         const int32_t* __restrict__ eu,
                                                         const int32_t* __restrict__ ev, int32_t* __restrict__ hu,
@@ -465,29 +455,6 @@ __global__ __launch_bounds__(256) void k_recon_permute_rows(int e, const int32_t
                                                             const int4* __restrict__ rows, int4* __restrict__ out) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < e) out[i] = rows[perm[i]];
-}
-
-static int bit_length(uint64_t v) {
-  int b = 0;
-  while (v) {
-    ++b;
-    v >>= 1;
-  }
-  return b;
-}
-
-// *perm (null: the identity) refined by a stable sort on key_src[perm[i]]: least significant key first
-static int recon_sort_pass(Ctx* c, int e, const int32_t* key_src, int32_t** perm, int bits) {
-  uint32_t* d_k;
-  int32_t* d_v;
-  PQ_TRY(c->arena.get(size_t(e), &d_k));
-  PQ_TRY(c->arena.get(size_t(e), &d_v));
-  hipLaunchKernelGGL(k_recon_sort_init, dim3(ceil_div(e, 256)), dim3(256), 0, c->stream, e, key_src,
-                     static_cast<const int32_t*>(*perm), d_k, d_v);
-  PQ_HIP(hipGetLastError());
-  PQ_TRY(stable_sort_pairs_u32(c, &d_k, &d_v, e, bits));
-  *perm = d_v;
-  return 0;
 }
 
 }  // namespace pyqsm
@@ -534,10 +501,9 @@ int pyqsm_ball_pivot(const int32_t* ijk, const int16_t* normals, int64_t n, cons
       return fail(PYQSM_EINVAL, "pyqsm_ball_pivot: the cloud spans more than 2^31 lattice units");
   const double bbox[6] = {double(mn[0]), double(mn[1]), double(mn[2]), double(mx[0]), double(mx[1]), double(mx[2])};
 
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   const int N = int(n);
   const int64_t tri_cap = 8 * n + 1024;
   int32_t *d_ijk, *d_state = nullptr, *d_lx, *d_ly, *d_lz;
@@ -557,8 +523,8 @@ int pyqsm_ball_pivot(const int32_t* ijk, const int16_t* normals, int64_t n, cons
   PQ_TRY(c->arena.get(size_t(tri_cap), &d_rows));
   PQ_TRY(c->arena.get(n_counters, &d_counters));
   if (n_levels > 1) PQ_TRY(c->arena.get(size_t(n), &d_state));
-  PQ_HIP(hipMemcpyAsync(d_ijk, ijk, size_t(n) * 12, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_nrm, normals, size_t(n) * 6, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_ijk, ijk, size_t(n) * 3));
+  PQ_TRY(copy_in(c, d_nrm, normals, size_t(n) * 3));
   PQ_HIP(hipMemsetAsync(d_counters, 0, n_counters * 8, c->stream));
   hipLaunchKernelGGL(k_recon_to_f64, dim3(ceil_div(3 * n, 256)), dim3(256), 0, c->stream, 3 * n,
                      static_cast<const int32_t*>(d_ijk), d_xyz);
@@ -603,8 +569,8 @@ int pyqsm_ball_pivot(const int32_t* ijk, const int16_t* normals, int64_t n, cons
                        lp->g.nz, static_cast<const int32_t*>(lp->g.start), lp->d_blk, d_est);
     PQ_HIP(hipGetLastError());
     PQ_TRY(exclusive_scan_i32(c, lp->d_blk, int64_t(nc) + 1));
-    PQ_HIP(hipMemcpyAsync(&lp->n_blocks, lp->d_blk + nc, 4, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipMemcpyAsync(est, d_est, 32, hipMemcpyDeviceToHost, c->stream));
+    PQ_TRY(download(c, &lp->n_blocks, lp->d_blk + nc, 1));
+    PQ_TRY(download(c, est, d_est, 4));
     PQ_HIP(hipStreamSynchronize(c->stream));
     const unsigned __int128 est_all = ((unsigned __int128)est[1] << 32) + est[0];
     lp->est_tests = est_all > (unsigned __int128)INT64_MAX ? INT64_MAX : int64_t(est_all);
@@ -666,8 +632,7 @@ int pyqsm_ball_pivot(const int32_t* ijk, const int16_t* normals, int64_t n, cons
     }
     blocks_sum += lp.n_blocks;
     unsigned long long cursor = 0;
-    PQ_HIP(hipMemcpyAsync(&cursor, d_counters, 8, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipStreamSynchronize(c->stream));
+    PQ_TRY(fetch(c, &cursor, d_counters));
     // the pass is over: its grid and the table of the levels before go back (the table is built anew
     // from all rows; until then n_he = 0 says that there is none)
     c->arena.rewind(base);
@@ -690,8 +655,8 @@ int pyqsm_ball_pivot(const int32_t* ijk, const int16_t* normals, int64_t n, cons
     hipLaunchKernelGGL(k_recon_half_edges, dim3(ceil_div(n_he, 256)), dim3(256), 0, c->stream, n_he,
                        static_cast<const int4*>(d_rows), d_eu, d_ev);
     PQ_HIP(hipGetLastError());
-    PQ_TRY(recon_sort_pass(c, n_he, d_ev, &perm, id_bits));
-    PQ_TRY(recon_sort_pass(c, n_he, d_eu, &perm, id_bits));
+    PQ_TRY(refine_order_by_key(c, n_he, d_ev, &perm, id_bits));
+    PQ_TRY(refine_order_by_key(c, n_he, d_eu, &perm, id_bits));
     hipLaunchKernelGGL(k_recon_permute2, dim3(ceil_div(n_he, 256)), dim3(256), 0, c->stream, n_he,
                        static_cast<const int32_t*>(perm), static_cast<const int32_t*>(d_eu),
                        static_cast<const int32_t*>(d_ev), d_hu, d_hv);
@@ -703,8 +668,7 @@ int pyqsm_ball_pivot(const int32_t* ijk, const int16_t* normals, int64_t n, cons
     c->arena.rewind(table);  // the stream orders the next level's writes behind these kernels
   }
   unsigned long long host[5];
-  PQ_HIP(hipMemcpyAsync(host, d_counters, sizeof(host), hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, host, d_counters, 5));
   if (stats) {
     stats[1] = int64_t(host[1]);
     stats[2] = int64_t(host[2]);
@@ -726,22 +690,19 @@ int pyqsm_ball_pivot(const int32_t* ijk, const int16_t* normals, int64_t n, cons
     hipLaunchKernelGGL(k_recon_split_rows, dim3(ceil_div(e, 256)), dim3(256), 0, c->stream, e,
                        static_cast<const int4*>(d_rows), d_ka, d_kb, d_kc);
     PQ_HIP(hipGetLastError());
-    PQ_TRY(recon_sort_pass(c, e, d_kc, &perm, id_bits));
-    PQ_TRY(recon_sort_pass(c, e, d_kb, &perm, id_bits));
-    PQ_TRY(recon_sort_pass(c, e, d_ka, &perm, id_bits));
+    PQ_TRY(refine_order_by_key(c, e, d_kc, &perm, id_bits));
+    PQ_TRY(refine_order_by_key(c, e, d_kb, &perm, id_bits));
+    PQ_TRY(refine_order_by_key(c, e, d_ka, &perm, id_bits));
     hipLaunchKernelGGL(k_recon_permute_rows, dim3(ceil_div(e, 256)), dim3(256), 0, c->stream, e,
                        static_cast<const int32_t*>(perm), static_cast<const int4*>(d_rows), d_sorted);
     PQ_HIP(hipGetLastError());
   }
-  int32_t* out = static_cast<int32_t*>(out_alloc(size_t(e) * 16));
-  if (!out) return fail(PYQSM_ENOMEM, "pyqsm_ball_pivot: no host memory for %d triangles", e);
-  hipError_t err = hipMemcpyAsync(out, d_sorted, size_t(e) * 16, hipMemcpyDeviceToHost, c->stream);
-  if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
-  if (err != hipSuccess) {
-    out_free(out);
-    return fail(PYQSM_EHIP, "pyqsm_ball_pivot: copying the triangles failed: %s", hipGetErrorString(err));
-  }
-  *tris = out;
+  OutBufs out;
+  int32_t* rows = out.get<int32_t>(size_t(e) * 4);
+  if (!rows) return fail(PYQSM_ENOMEM, "pyqsm_ball_pivot: no host memory for %d triangles", e);
+  PQ_TRY(fetch(c, reinterpret_cast<int4*>(rows), d_sorted, size_t(e)));  // (a, b, c, level) per row
+  out.kept = true;
+  *tris = rows;
   *n_tris = total;
   return 0;
 }

@@ -275,4 +275,37 @@ int stable_sort_pairs_u32(Ctx* c, uint32_t** keys, int32_t** vals, int64_t n, in
   return 0;
 }
 
+__global__ __launch_bounds__(256) void k_order_keys(int n, const int32_t* __restrict__ key_src,
+                                                    const int32_t* __restrict__ perm /*may be null*/,
+                                                    uint32_t* __restrict__ keys, int32_t* __restrict__ vals) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int j = perm ? perm[i] : i;
+  keys[i] = uint32_t(key_src[j]);
+  vals[i] = j;
+}
+
+int bit_length(uint64_t v) {
+  int b = 0;
+  while (v) {
+    ++b;
+    v >>= 1;
+  }
+  return b;
+}
+
+int refine_order_by_key(Ctx* c, int64_t n, const int32_t* key_src, int32_t** perm, int bits) {
+  if (n > 0x7FFFFF00LL) return fail(PYQSM_ERANGE, "more than 2^31 pairs to sort");
+  uint32_t* d_k;
+  int32_t* d_v;
+  PQ_TRY(c->arena.get(size_t(n), &d_k));
+  PQ_TRY(c->arena.get(size_t(n), &d_v));
+  hipLaunchKernelGGL(k_order_keys, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, int(n), key_src,
+                     static_cast<const int32_t*>(*perm), d_k, d_v);
+  PQ_HIP(hipGetLastError());
+  PQ_TRY(stable_sort_pairs_u32(c, &d_k, &d_v, n, bits));
+  *perm = d_v;
+  return 0;
+}
+
 }  // namespace pyqsm

@@ -218,10 +218,9 @@ int pyqsm_extract_skeleton(const double* xyz, int64_t n, const int64_t* seg_star
     n_steps[s] = 0;
   }
   if (n == 0) return 0;
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   // host-side wall clock of the loop's phases (PYQSM_LBC_TRACE)
   const bool trace_t = getenv("PYQSM_LBC_TRACE") != nullptr;
   double t_acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // setup, build, solve, means, step, tail, flags, kstep, copy
@@ -254,10 +253,10 @@ int pyqsm_extract_skeleton(const double* xyz, int64_t n, const int64_t* seg_star
   PQ_TRY(mem.get(size_t(S), &d_flags));
   std::vector<int32_t> h_start(size_t(S) + 1);
   for (int s = 0; s <= S; ++s) h_start[size_t(s)] = int32_t(seg_start[s]);
-  PQ_HIP(hipMemcpyAsync(cur, xyz, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_lo, lo, size_t(S) * 24, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_hi, hi, size_t(S) * 24, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_seg_start, h_start.data(), (size_t(S) + 1) * 4, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, cur, xyz, size_t(n) * 3));
+  PQ_TRY(copy_in(c, d_lo, lo, size_t(S) * 3));
+  PQ_TRY(copy_in(c, d_hi, hi, size_t(S) * 3));
+  PQ_TRY(copy_in(c, d_seg_start, h_start.data(), size_t(S) + 1));
   PQ_HIP(hipMemsetAsync(total, 0, size_t(n) * 24, c->stream));
   hipLaunchKernelGGL(k_seg_of, gn, blk, 0, c->stream, N, S, d_seg_start, seg_of);
   hipLaunchKernelGGL(k_fill_const, gn, blk, 0, c->stream, N, attraction_factor, wh);  // :264
@@ -295,8 +294,7 @@ int pyqsm_extract_skeleton(const double* xyz, int64_t n, const int64_t* seg_star
   // returns, bit for bit); 8 bytes per point come to the host for it, once per step
   std::vector<double> h_vec(static_cast<size_t>(n));
   auto seg_means = [&](const double* v, std::vector<double>& out) -> int {
-    PQ_HIP(hipMemcpyAsync(h_vec.data(), v, size_t(n) * 8, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipStreamSynchronize(c->stream));
+    PQ_TRY(fetch(c, h_vec.data(), v, size_t(n)));
     for (int s = 0; s < S; ++s)
       pyqsm_mean_f64(h_vec.data() + seg_start[s], seg_start[s + 1] - seg_start[s], &out[size_t(s)]);
     return 0;
@@ -321,7 +319,7 @@ int pyqsm_extract_skeleton(const double* xyz, int64_t n, const int64_t* seg_star
       if (!(vr[size_t(s)] > termination_ratio)) active[size_t(s)] = 0;                 // :279
     if (!any_active()) break;
     // ---- solve (:281-285) ------------------------------------------------------------
-    PQ_HIP(hipMemcpyAsync(d_segval, wl_seg.data(), size_t(S) * 8, hipMemcpyHostToDevice, c->stream));
+    PQ_TRY(copy_in(c, d_segval, wl_seg.data(), size_t(S)));
     hipLaunchKernelGGL(k_fill_by_seg, gn, blk, 0, c->stream, N, seg_of, d_segval, wl);
     PQ_HIP(hipGetLastError());
     int32_t it = 0;
@@ -338,8 +336,7 @@ int pyqsm_extract_skeleton(const double* xyz, int64_t n, const int64_t* seg_star
     PQ_HIP(hipMemsetAsync(d_flags, 0, size_t(S) * 4, c->stream));
     hipLaunchKernelGGL(k_seg_flags, gn, blk, 0, c->stream, N, seg_of, nw, cur, d_flags);
     PQ_HIP(hipGetLastError());
-    PQ_HIP(hipMemcpyAsync(h_flags.data(), d_flags, size_t(S) * 4, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipStreamSynchronize(c->stream));
+    PQ_TRY(fetch(c, h_flags.data(), d_flags, size_t(S)));
     lap(6);
     for (int s = 0; s < S; ++s)
       if (active[size_t(s)] && (!(h_flags[size_t(s)] & 1) || !(h_flags[size_t(s)] & 2))) active[size_t(s)] = 0;
@@ -351,12 +348,11 @@ int pyqsm_extract_skeleton(const double* xyz, int64_t n, const int64_t* seg_star
       break;
     }
     // ---- clamp, shift, accumulate (:291-307) -----------------------------------------
-    PQ_HIP(hipMemcpyAsync(d_active, active.data(), size_t(S) * 4, hipMemcpyHostToDevice, c->stream));
+    PQ_TRY(copy_in(c, d_active, active.data(), size_t(S)));
     hipLaunchKernelGGL(k_step, gn, blk, 0, c->stream, N, seg_of, d_active, d_lo, d_hi, nw, cur, total, shift);
     lap(7);
     if (steps)
-      PQ_HIP(hipMemcpyAsync(steps + size_t(step - 1) * size_t(n) * 3, shift, size_t(n) * 24,
-                            hipMemcpyDeviceToHost, c->stream));
+      PQ_TRY(download(c, steps + size_t(step - 1) * size_t(n) * 3, shift, size_t(n) * 3));
     lap(8);
     // ---- weights (:329-335) with the mass of the Laplacian just used ---------------------
     hipLaunchKernelGGL(k_wh_update, gn, blk, 0, c->stream, N, seg_of, d_active, m0, m_used, max_attraction, wh);
@@ -382,8 +378,8 @@ int pyqsm_extract_skeleton(const double* xyz, int64_t n, const int64_t* seg_star
       }
   }
   lap(4);
-  PQ_HIP(hipMemcpyAsync(out_pts, cur, size_t(n) * 24, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipMemcpyAsync(total_shift, total, size_t(n) * 24, hipMemcpyDeviceToHost, c->stream));
+  PQ_TRY(download(c, out_pts, cur, size_t(n) * 3));
+  PQ_TRY(download(c, total_shift, total, size_t(n) * 3));
   PQ_HIP(hipStreamSynchronize(c->stream));
   lap(5);
   if (trace_t)

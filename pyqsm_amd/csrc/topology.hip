@@ -189,8 +189,7 @@ static int forest_device(Ctx* c, const double* d_xyz, int64_t m, int32_t k, int3
   PQ_HIP(hipGetLastError());
   PQ_TRY(compact_flagged(c, flags, m, slot));
   int32_t cnt = 0;
-  PQ_HIP(hipMemcpyAsync(&cnt, flags + m, 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, &cnt, flags + m));
   if (cnt < 0 || cnt > m - 1) return fail(PYQSM_EHIP, "skeletal forest: %d edges for %lld points", cnt, (long long)m);
   *n_edges = cnt;
   if (cnt == 0) return 0;
@@ -401,9 +400,9 @@ static int chains_device(Ctx* c, const int32_t* d_edges, int64_t e, int64_t m, i
                      static_cast<const int32_t*>(kflags), d_kept);
   PQ_HIP(hipGetLastError());
   int32_t n_kept = 0, nc = 0, h[kCtlWords] = {0, 0, 0, 0};
-  PQ_HIP(hipMemcpyAsync(&n_kept, kflags + m, 4, hipMemcpyDeviceToHost, c->stream));
-  if (e > 0) PQ_HIP(hipMemcpyAsync(&nc, flags + 2 * e, 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipMemcpyAsync(h, ctl, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  PQ_TRY(download(c, &n_kept, kflags + m, 1));
+  if (e > 0) PQ_TRY(download(c, &nc, flags + 2 * e, 1));
+  PQ_TRY(download(c, h, ctl, kCtlWords));
   PQ_HIP(hipStreamSynchronize(c->stream));
   if (h[kCtlErr]) return fail(PYQSM_EINVAL, "collapse_chains: %s", topo_error_text(h[kCtlErr]));
   if (nc < 0 || nc > e) return fail(PYQSM_EHIP, "collapse_chains: %d chains for %lld edges", nc, (long long)e);
@@ -427,8 +426,7 @@ static int chains_device(Ctx* c, const int32_t* d_edges, int64_t e, int64_t m, i
   PQ_HIP(hipGetLastError());
   PQ_TRY(exclusive_scan_i32(c, len, int64_t(nc) + 1));
   int32_t total = 0;
-  PQ_HIP(hipMemcpyAsync(&total, len + nc, 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, &total, len + nc));
   // every degree-2 node lies on one run and a run is emitted once, so this holds for any edge list
   if (total < 0 || total > m) return fail(PYQSM_EHIP, "collapse_chains: %d members for %lld nodes", total, (long long)m);
   hipLaunchKernelGGL(k_tc_write, dim3(ceil_div(nc + 1, 256)), dim3(256), 0, c->stream, int(nc), M, d_edges,
@@ -743,10 +741,9 @@ int pyqsm_skeletal_forest_dev(const double* xyz_dev, int64_t m, int32_t k, int32
   if (rounds) *rounds = 0;
   if (m > 1 && (!xyz_dev || !edges_dev || !d2_dev)) return fail(PYQSM_EINVAL, "pyqsm_skeletal_forest_dev: NULL pointer");
   if (m < 2) return 0;
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   int32_t r = 0;
   PQ_TRY(forest_device(c, xyz_dev, m, k, edges_dev, d2_dev, n_edges, &r));
   PQ_HIP(hipStreamSynchronize(c->stream));
@@ -764,22 +761,21 @@ int pyqsm_skeletal_forest(const double* xyz, int64_t m, int32_t k, int32_t* edge
   if (rounds) *rounds = 0;
   if (m > 1 && (!xyz || !edges || !d2)) return fail(PYQSM_EINVAL, "pyqsm_skeletal_forest: NULL pointer");
   if (m < 2) return 0;
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   double *d_xyz, *d_d2;
   int32_t* d_edges;
   PQ_TRY(c->arena.get(size_t(m) * 3, &d_xyz));
   PQ_TRY(c->arena.get(size_t(m) * 2, &d_edges));
   PQ_TRY(c->arena.get(size_t(m), &d_d2));
-  PQ_HIP(hipMemcpyAsync(d_xyz, xyz, size_t(m) * 24, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_xyz, xyz, size_t(m) * 3));
   int32_t r = 0;
   int64_t ne = 0;
   PQ_TRY(forest_device(c, d_xyz, m, k, d_edges, d_d2, &ne, &r));
   if (ne > 0) {
-    PQ_HIP(hipMemcpyAsync(edges, d_edges, size_t(ne) * 8, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipMemcpyAsync(d2, d_d2, size_t(ne) * 8, hipMemcpyDeviceToHost, c->stream));
+    PQ_TRY(download(c, edges, d_edges, size_t(ne) * 2));
+    PQ_TRY(download(c, d2, d_d2, size_t(ne)));
   }
   PQ_HIP(hipStreamSynchronize(c->stream));
   *n_edges = ne;
@@ -804,10 +800,9 @@ int pyqsm_collapse_chains_dev(const int32_t* edges_dev, int64_t e, int64_t m, in
   PQ_API_RANGE("pyqsm_collapse_chains_dev");
   PQ_TRY(check_chain_args("pyqsm_collapse_chains_dev", e, m, edges_dev, kept_dev, chain_ends_dev, chain_ptr_dev,
                           members_dev, counts));
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   PQ_TRY(chains_device(c, edges_dev, e, m, kept_dev, chain_ends_dev, chain_ptr_dev, members_dev, counts));
   PQ_HIP(hipStreamSynchronize(c->stream));
   return 0;
@@ -820,10 +815,9 @@ int pyqsm_collapse_chains(const int32_t* edges, int64_t e, int64_t m, int32_t* k
   counts[0] = counts[1] = counts[2] = 0;
   chain_ptr[0] = 0;
   if (m == 0) return 0;
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   int32_t *d_edges = nullptr, *d_kept, *d_ends, *d_members;
   int64_t* d_ptr;
   PQ_TRY(c->arena.get(size_t(std::max<int64_t>(e, 1)) * 2, &d_edges));
@@ -831,14 +825,14 @@ int pyqsm_collapse_chains(const int32_t* edges, int64_t e, int64_t m, int32_t* k
   PQ_TRY(c->arena.get(size_t(std::max<int64_t>(e, 1)) * 2, &d_ends));
   PQ_TRY(c->arena.get(size_t(e) + 1, &d_ptr));
   PQ_TRY(c->arena.get(size_t(m), &d_members));
-  if (e > 0) PQ_HIP(hipMemcpyAsync(d_edges, edges, size_t(e) * 8, hipMemcpyHostToDevice, c->stream));
+  if (e > 0) PQ_TRY(copy_in(c, d_edges, edges, size_t(e) * 2));
   PQ_TRY(chains_device(c, d_edges, e, m, d_kept, d_ends, d_ptr, d_members, counts));
-  if (counts[0] > 0) PQ_HIP(hipMemcpyAsync(kept, d_kept, size_t(counts[0]) * 4, hipMemcpyDeviceToHost, c->stream));
+  if (counts[0] > 0) PQ_TRY(download(c, kept, d_kept, size_t(counts[0])));
   if (counts[1] > 0) {
-    PQ_HIP(hipMemcpyAsync(chain_ends, d_ends, size_t(counts[1]) * 8, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipMemcpyAsync(chain_ptr, d_ptr, size_t(counts[1] + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    PQ_TRY(download(c, chain_ends, d_ends, size_t(counts[1]) * 2));
+    PQ_TRY(download(c, chain_ptr, d_ptr, size_t(counts[1] + 1)));
   }
-  if (counts[2] > 0) PQ_HIP(hipMemcpyAsync(members, d_members, size_t(counts[2]) * 4, hipMemcpyDeviceToHost, c->stream));
+  if (counts[2] > 0) PQ_TRY(download(c, members, d_members, size_t(counts[2])));
   PQ_HIP(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -857,10 +851,9 @@ int pyqsm_chain_radii(const double* shift, int64_t n, const int64_t* chain_ptr, 
     if (chain_ptr[p + 1] < chain_ptr[p]) return fail(PYQSM_EINVAL, "pyqsm_chain_radii: chain_ptr must not decrease");
   if (n_members > 0 && (!members || !shift)) return fail(PYQSM_EINVAL, "pyqsm_chain_radii: NULL pointer");
   if (index_map == nullptr) n_map = 0;
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   ProfScope ps(c, "topo_radii");
   double *d_shift, *d_rad;
   int64_t* d_ptr;
@@ -871,12 +864,11 @@ int pyqsm_chain_radii(const double* shift, int64_t n, const int64_t* chain_ptr, 
   PQ_TRY(c->arena.get(size_t(std::max<int64_t>(n_members, 1)), &d_mem));
   PQ_TRY(c->arena.get(size_t(kCtlWords), &ctl));
   PQ_HIP(hipMemsetAsync(ctl, 0, kCtlWords * 4, c->stream));
-  if (n > 0) PQ_HIP(hipMemcpyAsync(d_shift, shift, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_ptr, chain_ptr, size_t(n_chains + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  if (n_members > 0) PQ_HIP(hipMemcpyAsync(d_mem, members, size_t(n_members) * 4, hipMemcpyHostToDevice, c->stream));
+  if (n > 0) PQ_TRY(copy_in(c, d_shift, shift, size_t(n) * 3));
+  PQ_TRY(copy_in(c, d_ptr, chain_ptr, size_t(n_chains + 1)));
+  if (n_members > 0) PQ_TRY(copy_in(c, d_mem, members, size_t(n_members)));
   if (index_map && n_map > 0) {
-    PQ_TRY(c->arena.get(size_t(n_map), &d_map));
-    PQ_HIP(hipMemcpyAsync(d_map, index_map, size_t(n_map) * 4, hipMemcpyHostToDevice, c->stream));
+    PQ_TRY(upload(c, index_map, size_t(n_map), &d_map));
   } else if (index_map) {
     PQ_TRY(c->arena.get(size_t(1), &d_map));  // an empty map: every member is out of range
   }
@@ -885,9 +877,8 @@ int pyqsm_chain_radii(const double* shift, int64_t n, const int64_t* chain_ptr, 
                      static_cast<const double*>(d_shift), n, static_cast<const int32_t*>(d_map), n_map, d_rad, ctl);
   PQ_HIP(hipGetLastError());
   int32_t h[kCtlWords];
-  PQ_HIP(hipMemcpyAsync(h, ctl, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipMemcpyAsync(radius, d_rad, size_t(n_chains) * 8, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(download(c, h, ctl, kCtlWords));
+  PQ_TRY(fetch(c, radius, d_rad, size_t(n_chains)));
   if (h[kCtlErr]) return fail(PYQSM_EINVAL, "pyqsm_chain_radii: %s", topo_error_text(h[kCtlErr]));
   return 0;
 }
@@ -903,10 +894,9 @@ int pyqsm_cylinder_surfaces(const double* params, int64_t q, const double* cos_s
   surface_ptr[0] = 0;
   if (q == 0) return 0;
   if (!params || !cos_sin) return fail(PYQSM_EINVAL, "pyqsm_cylinder_surfaces: NULL pointer");
-  Ctx* c = ctx_for(device);
+  Call call(device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   ProfScope ps(c, "topo_surfaces");
   double *d_par, *d_cs, *d_out;
   int32_t *cnt, *ctl;
@@ -916,8 +906,8 @@ int pyqsm_cylinder_surfaces(const double* params, int64_t q, const double* cos_s
   PQ_TRY(c->arena.get(size_t(kCtlWords), &ctl));
   PQ_HIP(hipMemsetAsync(ctl, 0, kCtlWords * 4, c->stream));
   PQ_HIP(hipMemsetAsync(cnt, 0, size_t(q + 1) * 4, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_par, params, size_t(q) * 14 * 8, hipMemcpyHostToDevice, c->stream));
-  PQ_HIP(hipMemcpyAsync(d_cs, cos_sin, size_t(2 * kSurfAngles) * 8, hipMemcpyHostToDevice, c->stream));
+  PQ_TRY(copy_in(c, d_par, params, size_t(q) * 14));
+  PQ_TRY(copy_in(c, d_cs, cos_sin, size_t(2 * kSurfAngles)));
   hipLaunchKernelGGL(k_cyl_surface<false>, dim3(unsigned(q)), dim3(256), 0, c->stream, int(q),
                      static_cast<const double*>(d_par), static_cast<const double*>(d_cs), cnt,
                      static_cast<double*>(nullptr), ctl);
@@ -925,8 +915,8 @@ int pyqsm_cylinder_surfaces(const double* params, int64_t q, const double* cos_s
   PQ_TRY(exclusive_scan_i32(c, cnt, q + 1));
   std::vector<int32_t> off(size_t(q) + 1);
   int32_t h[kCtlWords];
-  PQ_HIP(hipMemcpyAsync(off.data(), cnt, size_t(q + 1) * 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipMemcpyAsync(h, ctl, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  PQ_TRY(download(c, off.data(), cnt, size_t(q + 1)));
+  PQ_TRY(download(c, h, ctl, kCtlWords));
   PQ_HIP(hipStreamSynchronize(c->stream));
   if (h[kCtlErr])
     return fail((h[kCtlErr] & kErrWide) ? PYQSM_ERANGE : PYQSM_EINVAL, "pyqsm_cylinder_surfaces: %s",
@@ -937,14 +927,11 @@ int pyqsm_cylinder_surfaces(const double* params, int64_t q, const double* cos_s
   hipLaunchKernelGGL(k_cyl_surface<true>, dim3(unsigned(q)), dim3(256), 0, c->stream, int(q),
                      static_cast<const double*>(d_par), static_cast<const double*>(d_cs), cnt, d_out, ctl);
   PQ_HIP(hipGetLastError());
-  double* host = static_cast<double*>(out_alloc(size_t(total) * 24));
+  OutBufs out;
+  double* host = out.get<double>(size_t(total) * 3);
   if (!host) return fail(PYQSM_ENOMEM, "pyqsm_cylinder_surfaces: host allocation of %lld rows failed", (long long)total);
-  hipError_t e1 = hipMemcpyAsync(host, d_out, size_t(total) * 24, hipMemcpyDeviceToHost, c->stream);
-  if (e1 == hipSuccess) e1 = hipStreamSynchronize(c->stream);
-  if (e1 != hipSuccess) {
-    out_free(host);
-    return fail(PYQSM_EHIP, "pyqsm_cylinder_surfaces: read-back failed: %s", hipGetErrorString(e1));
-  }
+  PQ_TRY(fetch(c, host, d_out, size_t(total) * 3));
+  out.kept = true;
   for (int64_t p = 0; p <= q; ++p) surface_ptr[p] = off[size_t(p)];
   *points_out = host;
   *total_out = total;

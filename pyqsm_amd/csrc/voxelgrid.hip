@@ -250,8 +250,7 @@ static int build_table(Ctx* c, VoxGrid* g, const int32_t* rows) {
   PQ_HIP(hipGetLastError());
   PQ_TRY(exclusive_scan_i32(c, head, int64_t(M) + 1));
   int32_t nb = 0;
-  PQ_HIP(hipMemcpyAsync(&nb, head + M, 4, hipMemcpyDeviceToHost, c->stream));
-  PQ_HIP(hipStreamSynchronize(c->stream));
+  PQ_TRY(fetch(c, &nb, head + M));
   uint64_t cap = 64;  // nb <= M < 2^31: at most 2^32 slots, and the mask fits 32 bits
   while (cap < 2 * uint64_t(nb)) cap <<= 1;
   g->cap_mask = uint32_t(cap - 1);
@@ -297,10 +296,9 @@ static int query_impl(const VoxGrid* g, const double* qry, int64_t m, int32_t fl
   if (m > 0 && !qry) return fail(PYQSM_EINVAL, "voxel grid query: qry is NULL");
   if (count) *count = 0;
   if (m == 0 || (!included && !row && !idx && !count)) return 0;
-  Ctx* c = ctx_for(g->device);
+  Call call(g->device);
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
   const int invert = (flags & PYQSM_VOX_INVERT) ? 1 : 0;
   const bool listing = idx || count;
   const int64_t chunk = std::min(m, chunk_rows(host ? kVoxChunk : kVoxChunkDev));
@@ -321,14 +319,14 @@ static int query_impl(const VoxGrid* g, const double* qry, int64_t m, int32_t fl
     const int64_t mc = std::min(chunk, m - r0);
     const double* q = qry + size_t(r0) * 3;
     if (host) {
-      PQ_HIP(hipMemcpyAsync(d_q, q, size_t(mc) * 24, hipMemcpyHostToDevice, c->stream));
+      PQ_TRY(copy_in(c, d_q, q, size_t(mc) * 3));
       q = d_q;
     }
     uint8_t* inc = host ? d_inc : (included ? included + r0 : nullptr);
     int32_t* rw = host ? d_row : (row ? row + r0 : nullptr);
     PQ_TRY(launch_query(c, g, q, mc, invert, inc, rw, d_flags));
-    if (host && included) PQ_HIP(hipMemcpyAsync(included + r0, d_inc, size_t(mc), hipMemcpyDeviceToHost, c->stream));
-    if (host && row) PQ_HIP(hipMemcpyAsync(row + r0, d_row, size_t(mc) * 4, hipMemcpyDeviceToHost, c->stream));
+    if (host && included) PQ_TRY(download(c, included + r0, d_inc, size_t(mc)));
+    if (host && row) PQ_TRY(download(c, row + r0, d_row, size_t(mc)));
     if (!listing) continue;
     // the chunk's listed queries, ascending; the running total places them (one 4-byte read-back per pass)
     int64_t* out = idx ? (host ? d_idx : idx + total) : nullptr;
@@ -342,10 +340,9 @@ static int query_impl(const VoxGrid* g, const double* qry, int64_t m, int32_t fl
       }
     }
     int32_t cnt = 0;
-    PQ_HIP(hipMemcpyAsync(&cnt, d_flags + mc, 4, hipMemcpyDeviceToHost, c->stream));
-    PQ_HIP(hipStreamSynchronize(c->stream));
+    PQ_TRY(fetch(c, &cnt, d_flags + mc));
     if (host && idx && cnt > 0)
-      PQ_HIP(hipMemcpyAsync(idx + total, d_idx, size_t(cnt) * 8, hipMemcpyDeviceToHost, c->stream));
+      PQ_TRY(download(c, idx + total, d_idx, size_t(cnt)));
     total += cnt;
     c->arena.rewind(mk);  // the scan's block sums
   }
@@ -409,15 +406,12 @@ int pyqsm_voxel_grid_create(const double* xyz, int64_t n, const double* colors, 
     *grid = g;
     return 0;
   }
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->arena.reset();
+  Call call(c);
   auto build = [&]() -> int {
     double *d_xyz, *d_rgb = nullptr;
-    PQ_TRY(c->arena.get(size_t(n) * 3, &d_xyz));
-    PQ_HIP(hipMemcpyAsync(d_xyz, xyz, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+    PQ_TRY(upload(c, xyz, size_t(n) * 3, &d_xyz));
     if (colors) {
-      PQ_TRY(c->arena.get(size_t(n) * 3, &d_rgb));
-      PQ_HIP(hipMemcpyAsync(d_rgb, colors, size_t(n) * 24, hipMemcpyHostToDevice, c->stream));
+      PQ_TRY(upload(c, colors, size_t(n) * 3, &d_rgb));
     }
     VoxelDev v;
     PQ_TRY(voxel_keys_and_sort(c, d_xyz, n, voxel_size, &v));
@@ -480,11 +474,11 @@ int pyqsm_voxel_grid_voxels(const void* grid, int32_t* grid_index, double* color
   if (!g) return fail(PYQSM_EINVAL, "pyqsm_voxel_grid_voxels: not a voxel grid");
   if (colors && !g->colored) return fail(PYQSM_EINVAL, "pyqsm_voxel_grid_voxels: the grid was created without colours");
   if (g->m == 0 || (!grid_index && !colors)) return 0;
-  Ctx* c = ctx_for(g->device);
+  Call call(g->device, Call::kKeepArena);  // copies only: no scratch
+  Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  std::lock_guard<std::mutex> lk(c->mu);
-  if (grid_index) PQ_HIP(hipMemcpyAsync(grid_index, g->gidx, size_t(g->m) * 12, hipMemcpyDeviceToHost, c->stream));
-  if (colors) PQ_HIP(hipMemcpyAsync(colors, g->colors, size_t(g->m) * 24, hipMemcpyDeviceToHost, c->stream));
+  if (grid_index) PQ_TRY(download(c, grid_index, g->gidx, size_t(g->m) * 3));
+  if (colors) PQ_TRY(download(c, colors, g->colors, size_t(g->m) * 3));
   PQ_HIP(hipStreamSynchronize(c->stream));
   return 0;
 }

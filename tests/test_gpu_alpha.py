@@ -118,6 +118,25 @@ def test_dense_cell_chunks_and_slices(gpu):
     assert int(two.twice_area[0]) == int(two.twice_area[1]) == int(res.twice_area[0])
 
 
+def test_boundary_of_2049_edges(gpu):
+    """683 small triangles far apart, points shuffled: 2049 boundary edges, one radix tile of 2048 and one
+    row, in the two sort passes by (a, b) over ids of two 8-bit digits. Ids of one digit with many edges
+    are test_small_groups, far larger lists test_big_cloud; a boundary has at least three edges, so the
+    one-row list does not exist here."""
+    rng = np.random.default_rng(12)
+    k = np.arange(683)
+    at = np.stack([k % 27, k // 27], axis=1) * 1000 + rng.integers(0, 200, (683, 2))
+    legs = rng.integers(20, 31, (683, 2))                        # right triangles: R^2 <= (30^2 + 30^2) / 4 = 450
+    zero = np.zeros(683, np.int64)
+    tri = at[:, None, :] + np.stack([np.stack([zero, zero], 1), np.stack([legs[:, 0], zero], 1),
+                                     np.stack([zero, legs[:, 1]], 1)], axis=1)
+    P = tri.reshape(-1, 2)[rng.permutation(3 * 683)].astype(np.int32)
+    A2 = 500
+    ref = R.delaunay_filtered(P, A2)
+    assert len(ref[1]) == 2049 and ref[0] == int((legs[:, 0] * legs[:, 1]).sum())
+    assert_same(run(P, A2), 0, ref, P)
+
+
 @pytest.fixture(scope="module")
 def batch():
     rnd, lat = R.random_points(), R.holey_lattice()

@@ -131,6 +131,26 @@ def test_tile_seams(gpu, n):
         assert_intersections(ijk, tris, [list(pair)])
 
 
+def pierced_pairs(p, seed=5):
+    """p pairs of small triangles far apart along x, the second of a pair piercing the first, the 2 p
+    triangles in shuffled order: p intersecting pairs whose (i, j) are spread over [0, 2 p)."""
+    x = 20 * np.arange(p)[:, None, None] * np.array([1, 0, 0])
+    flat = np.array([[0, 0, 1], [4, 0, 1], [0, 4, 1]]) + x
+    spike = np.array([[1, 1, 0], [1, 1, 2], [3, 3, 2]]) + x
+    tri = np.concatenate([flat, spike])[np.random.default_rng(seed).permutation(2 * p)]
+    return tri.reshape(-1, 3).astype(np.int32), np.arange(6 * p, dtype=np.int32).reshape(2 * p, 3)
+
+
+@pytest.mark.parametrize("p", [100, 2049])
+def test_pair_list_sizes(gpu, p):
+    """The pair list's two sort passes by (i, j): 100 pairs of 200 triangles (ids of one 8-bit digit),
+    and 2049 pairs (one radix tile of 2048 and one row) of 4098 triangles (two digits). One pair, which
+    the sort returns as it is, is test_catalogue and test_tile_seams; two digits also test_random_soup."""
+    ijk, tris = pierced_pairs(p)
+    got = assert_intersections(ijk, tris)
+    assert got.n_pairs == p and got.tri_hit.all()
+
+
 BASE = [[0, 0, 0], [8, 0, 0], [0, 8, 0]]
 CATALOGUE = {
     "vertex_on_face": ([[2, 2, 0], [2, 2, 6], [5, 2, 6]], True),

@@ -173,6 +173,32 @@ def test_tiny_clouds_and_unresolved_ties(gpu):
     assert_same(res, ref)
 
 
+@pytest.mark.parametrize("count", [683, 2049])
+def test_lone_triangles(gpu, count):
+    """`count` right triangles of legs 30, more than 2 rho + 30 apart, normals up or down, points shuffled.
+    683 triangles are 2049 half-edges, 2049 triangles 2049 rows: one radix tile of 2048 and one row in the
+    sort passes by (u, v) and by (a, b, c), over ids of two 8-bit digits. One row is the single triangle of
+    test_tiny_clouds, ids of one digit test_plane_grid_tie_rule, long lists test_nested_surfaces.
+    The reference is the brute-force statement on each triangle by itself: a ball of radius rho on three
+    points neither holds nor touches a point farther than 2 rho from them."""
+    rng = np.random.default_rng(count)
+    k = np.arange(count)
+    at = np.stack([k % 46, k // 46, np.zeros(count, np.int64)], axis=1) * 100
+    P = (at[:, None, :] + np.array([[0, 0, 0], [30, 0, 0], [0, 30, 0]])).reshape(-1, 3).astype(np.int32)
+    up = rng.integers(0, 2, count) * 2 - 1
+    Nr = (np.repeat(up, 3)[:, None] * np.array([0, 0, 1 << 14])).astype(np.int16)
+    perm = rng.permutation(3 * count)                            # new index i holds old point perm[i]
+    new_of = np.argsort(perm)
+    rows = []
+    for t in range(count):
+        T, lv, unresolved = R.brute(P[3 * t:3 * t + 3], Nr[3 * t:3 * t + 3], (900,))
+        assert len(T) == 1 and unresolved == 0
+        a, b, c = new_of[3 * t + T[0]].tolist()
+        rows.append(min((a, b, c), (b, c, a), (c, a, b)))        # the same cycle, lowest index first
+    res = hip.ball_pivot(P[perm], Nr[perm], (900,))
+    assert_same(res, (np.array(sorted(rows), np.int32), np.zeros(count, np.int32), 0))
+
+
 def test_wrappers_return_a_closed_mesh(gpu):
     P, Nr, rho2 = R.sphere()
     cloud = float_cloud(P, Nr)
