@@ -1,6 +1,8 @@
 // grid.hip — bounding box, cell counting sort (see grid.hpp).
 #include "grid.hpp"
 
+#include "block_scan.hpp"
+
 #include <atomic>
 #include <cmath>
 #include <type_traits>
@@ -12,11 +14,43 @@ __device__ __forceinline__ unsigned long long ord_key(double x) {
   unsigned long long b = static_cast<unsigned long long>(__double_as_longlong(x));
   return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
-static double ord_val(unsigned long long k) {
-  unsigned long long b = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
+__host__ __device__ static inline double ord_val(unsigned long long k) {
+  const unsigned long long b = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
   double d;
   memcpy(&d, &b, 8);
   return d;
+}
+
+// ---- the shape rules every planner of a grid shares -----------------------------------------------
+static constexpr int kBkMax = 16384;  // buckets (LDS histogram of the two-level sort's A passes: <= 64 KB)
+
+// The two-level sort's buckets for a directory of ncell + 1 entries: 2^12 cells each, 2^13 beyond
+// kBkMax of those; nbk = ceil((ncell + 1) / bucket). More than kBkMax buckets: no two-level sort.
+struct BucketShape {
+  int bits;
+  int64_t nbk;
+};
+__host__ __device__ static inline BucketShape bucket_shape(int64_t ncell) {
+  const int bits = ncell + 1 <= (int64_t(kBkMax) << 12) ? 12 : 13;
+  return BucketShape{bits, (ncell + (int64_t(1) << bits)) >> bits};
+}
+
+// Interior slabs per axis of a grid of edge `cell` over the box [mn, mx] (raw[a]; 0 from the first
+// axis on that has 2e9 or more) and *tot = the cells of that grid with `border` more slabs per axis,
+// as a double. One function for the host and the device: where both plan the same box they do the
+// same fp64 operations in the same order, and every point lands in the same cell.
+__host__ __device__ static inline bool interior_slabs(const double* mn, const double* mx, double cell, double border,
+                                                      int raw[3], double* tot) {
+  bool ok = true;
+  double t = 1.0;
+  for (int a = 0; a < 3; ++a) {
+    const double d = floor((mx[a] - mn[a]) / cell) + 1.0;
+    if (!(d < 2.0e9)) ok = false;
+    raw[a] = ok ? int(d) : 0;
+    t *= d + border;
+  }
+  *tot = t;
+  return ok;
 }
 
 // Stage 1: one (min, max) record per block, no atomics (94 k same-address atomics
@@ -165,15 +199,11 @@ __global__ __launch_bounds__(256) void k_cell_scatter(const double* __restrict__
                                                       double* __restrict__ sx,
                                                       double* __restrict__ sy,
                                                       double* __restrict__ sz) {
+  const SortedStore out{order, cell_of, nullptr, nullptr, sx, sy, sz};
   int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
   if (i >= n) return;
   int c = cell_tmp[i];
-  int p = start[c] + rank_tmp[i];
-  order[p] = int32_t(i);
-  cell_of[p] = c;
-  sx[p] = xyz[3 * i];
-  sy[p] = xyz[3 * i + 1];
-  sz[p] = xyz[3 * i + 2];
+  out.put(start[c] + rank_tmp[i], int32_t(i), c, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
 }
 
 // wave sums -> one atomic per block (atomics on one address are served one at a time)
@@ -386,17 +416,14 @@ int build_grid(Ctx* c, const double* xyz, int64_t n, double min_cell, int64_t ma
   double cell = min_cell;
   int dims[3];
   for (;;) {
-    double tot = 1.0;
-    bool ok = true;
-    for (int a = 0; a < 3; ++a) {
-      double d = std::floor((mx[a] - mn[a]) / cell) + 3.0;  // +1 interior, +2 border
-      if (!(d < 2.0e9)) ok = false;
-      dims[a] = ok ? int(d) : 0;
-      tot *= d;
-    }
+    double tot;
+    const bool ok = interior_slabs(mn, mx, cell, 2.0, dims, &tot);
+    // (a grid that fits has far fewer than 2^52 slabs per axis: + 1 and + 2 are exact, the doubles those of
+    // floor(...) + 3)
     if (ok && tot <= double(max_cells)) break;
     cell *= 2.0;
   }
+  for (int a = 0; a < 3; ++a) dims[a] += 2;  // the border
   g->minx = mn[0];
   g->miny = mn[1];
   g->minz = mn[2];
@@ -446,106 +473,6 @@ int build_grid(Ctx* c, const double* xyz, int64_t n, double min_cell, int64_t ma
 }
 
 
-// ---- octant sub-cells ------------------------------------------------------------------
-
-__device__ __forceinline__ int octant_bit(double v, double mn, double inv_cell, int ccoord) {
-  // position in half cells relative to the cell the point was binned into
-  const int h = int(floor((v - mn) * (2.0 * inv_cell))) - 2 * (ccoord - 1);
-  return h < 1 ? 0 : 1;
-}
-
-__global__ __launch_bounds__(256) void k_sub_count(int n, GridParams g,
-                                                   const int32_t* __restrict__ start,
-                                                   const int32_t* __restrict__ cell_of,
-                                                   const double* __restrict__ sx,
-                                                   const double* __restrict__ sy,
-                                                   const double* __restrict__ sz,
-                                                   int32_t* __restrict__ sub_cnt,
-                                                   int32_t* __restrict__ oct_rank) {
-  int p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= n) return;
-  const int c = cell_of[p];
-  const int cx = c % g.nx, cy = (c / g.nx) % g.ny, cz = c / (g.nx * g.ny);
-  const int oct = octant_bit(sx[p], g.minx, g.inv_cell, cx) |
-                  (octant_bit(sy[p], g.miny, g.inv_cell, cy) << 1) |
-                  (octant_bit(sz[p], g.minz, g.inv_cell, cz) << 2);
-  const int rank = atomicAdd(&sub_cnt[size_t(start[c]) * 8 + oct], 1);
-  oct_rank[p] = (rank << 3) | oct;
-}
-
-// the first point of every cell turns its eight counts into run starts
-__global__ __launch_bounds__(256) void k_sub_prefix(int n, const int32_t* __restrict__ start,
-                                                    const int32_t* __restrict__ cell_of,
-                                                    const int32_t* __restrict__ sub_cnt,
-                                                    int32_t* __restrict__ sub_beg,
-                                                    int4* __restrict__ rec) {
-  int p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= n || start[cell_of[p]] != p) return;
-  int run = p;
-#pragma unroll
-  for (int o = 0; o < 8; ++o) {
-    const int cnt = sub_cnt[size_t(p) * 8 + o];
-    sub_beg[size_t(p) * 8 + o] = run;
-    rec[size_t(p) * 8 + o] = make_int4(run, cnt, -1, 0);
-    run += cnt;
-  }
-}
-
-__global__ __launch_bounds__(256) void k_sub_scatter(int n, const int32_t* __restrict__ start,
-                                                     const int32_t* __restrict__ cell_of,
-                                                     const int32_t* __restrict__ oct_rank,
-                                                     const int32_t* __restrict__ sub_beg,
-                                                     const int32_t* __restrict__ order,
-                                                     const double* __restrict__ sx,
-                                                     const double* __restrict__ sy,
-                                                     const double* __restrict__ sz,
-                                                     int32_t* __restrict__ order2,
-                                                     double* __restrict__ sx2,
-                                                     double* __restrict__ sy2,
-                                                     double* __restrict__ sz2,
-                                                     int32_t* __restrict__ sub_of) {
-  int p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= n) return;
-  const int orc = oct_rank[p];
-  const int sid = start[cell_of[p]] * 8 + (orc & 7);
-  const int q = sub_beg[sid] + (orc >> 3);
-  order2[q] = order[p];
-  sx2[q] = sx[p];
-  sy2[q] = sy[p];
-  sz2[q] = sz[p];
-  sub_of[q] = sid;
-}
-
-int subsort_octants(Ctx* c, DevGrid* g, int64_t n, SubCells* sub) {
-  if (n > (int64_t(1) << 27)) return fail(PYQSM_ERANGE, "octant sub-cells: more than 2^27 points");
-  int32_t *oct_rank, *order2;
-  double *sx2, *sy2, *sz2;
-  PQ_TRY(c->arena.get(size_t(n) * 8, &sub->sub_cnt));
-  PQ_TRY(c->arena.get(size_t(n) * 8, &sub->sub_beg));
-  PQ_TRY(c->arena.get(size_t(n), &sub->sub_of));
-  PQ_TRY(c->arena.get(size_t(n) * 8, &sub->rec));
-  PQ_TRY(c->arena.get(size_t(n), &oct_rank));
-  PQ_TRY(c->arena.get(size_t(n), &order2));
-  PQ_TRY(c->arena.get(size_t(n), &sx2));
-  PQ_TRY(c->arena.get(size_t(n), &sy2));
-  PQ_TRY(c->arena.get(size_t(n), &sz2));
-  PQ_HIP(hipMemsetAsync(sub->sub_cnt, 0, size_t(n) * 32, c->stream));
-  const GridParams gp = grid_params(*g);
-  const dim3 grid(ceil_div(n, 256)), blk(256);
-  hipLaunchKernelGGL(k_sub_count, grid, blk, 0, c->stream, int(n), gp, g->start, g->cell_of, g->sx,
-                     g->sy, g->sz, sub->sub_cnt, oct_rank);
-  hipLaunchKernelGGL(k_sub_prefix, grid, blk, 0, c->stream, int(n), g->start, g->cell_of,
-                     sub->sub_cnt, sub->sub_beg, sub->rec);
-  hipLaunchKernelGGL(k_sub_scatter, grid, blk, 0, c->stream, int(n), g->start, g->cell_of, oct_rank,
-                     sub->sub_beg, g->order, g->sx, g->sy, g->sz, order2, sx2, sy2, sz2, sub->sub_of);
-  PQ_HIP(hipGetLastError());
-  g->order = order2;
-  g->sx = sx2;
-  g->sy = sy2;
-  g->sz = sz2;
-  return 0;
-}
-
 // ---- grid + octant sub-cells in one pass (DBSCAN's binning) ------------------------------
 
 struct AxisMap {  // raw slab index -> compressed slab index (+1 for the border); null = identity
@@ -569,7 +496,7 @@ __device__ __forceinline__ RawCell raw_cell(const GridParams& g, int rx, int ry,
   cx = cx < 0 ? 0 : (cx > rx - 1 ? rx - 1 : cx);
   cy = cy < 0 ? 0 : (cy > ry - 1 ? ry - 1 : cy);
   cz = cz < 0 ? 0 : (cz > rz - 1 ? rz - 1 : cz);
-  // octant relative to the cell the point was binned into (as k_sub_count: h - 2 c < 1 ? 0 : 1)
+  // octant relative to the cell the point was binned into (half cells past the cell's first: h - 2 c < 1 ? 0 : 1)
   const int ox = hx - 2 * cx < 1 ? 0 : 1, oy = hy - 2 * cy < 1 ? 0 : 1, oz = hz - 2 * cz < 1 ? 0 : 1;
   return RawCell{cx, cy, cz, ox | (oy << 1) | (oz << 2)};
 }
@@ -656,11 +583,10 @@ __global__ __launch_bounds__(256) void k_order_cells(int n, const int32_t* __res
                                                      int32_t* __restrict__ sub_of,
                                                      double* __restrict__ sx, double* __restrict__ sy,
                                                      double* __restrict__ sz,
-                                                     int32_t* __restrict__ sub_cnt,
-                                                     int32_t* __restrict__ sub_beg,
                                                      int4* __restrict__ rec,
                                                      int32_t* __restrict__ big_list,
                                                      int32_t* __restrict__ big_cnt) {
+  const SortedStore out{order, cell_of, sub_of, nullptr, sx, sy, sz};
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= n) return;
   const PointRec me = keyed[p];
@@ -682,81 +608,50 @@ __global__ __launch_bounds__(256) void k_order_cells(int n, const int32_t* __res
       for (int k = 0; k < 8; ++k) cnt[k] += oq == k;
     }
   }
-  const int f = b + less + same_before;
-  order[f] = me.idx;
-  cell_of[f] = c;
-  sub_of[f] = b * 8 + o;
-  sx[f] = me.x;
-  sy[f] = me.y;
-  sz[f] = me.z;
-  if (first) {
-    int run = b;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      sub_beg[size_t(b) * 8 + k] = run;
-      sub_cnt[size_t(b) * 8 + k] = cnt[k];
-      rec[size_t(b) * 8 + k] = make_int4(run, cnt[k], -1, 0);
-      run += cnt[k];
-    }
-  }
+  out.put(b + less + same_before, me.idx, c, me.x, me.y, me.z, b * 8 + o);
+  if (first) write_sub_records(rec, b, cnt);
 }
 
-// A block per big cell: stable counting sort of the run by octant (two sweeps over the run).
-__global__ __launch_bounds__(256) void k_order_big(const int32_t* __restrict__ big_list,
-                                                   const int32_t* __restrict__ big_cnt,
-                                                   const int32_t* __restrict__ start,
-                                                   const PointRec* __restrict__ keyed,
-                                                   int32_t* __restrict__ order,
-                                                   int32_t* __restrict__ cell_of,
-                                                   int32_t* __restrict__ sub_of,
-                                                   double* __restrict__ sx, double* __restrict__ sy,
-                                                   double* __restrict__ sz, float4* __restrict__ p4,
-                                                   int32_t* __restrict__ sub_cnt,
-                                                   int32_t* __restrict__ sub_beg,
-                                                   int4* __restrict__ rec, const GridPlan* __restrict__ plan) {
-  __shared__ int tot[8], base[8], wcnt[4][8];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (!plan->ok) return;
-  const int nbig = *big_cnt;  // usually 0: the launch is then a few idle blocks
-  for (int bi = blockIdx.x; bi < nbig; bi += gridDim.x) {  // block-uniform
-  const int c = big_list[bi];
-  const int b = start[c], e = start[c + 1];
-  __syncthreads();
-  if (threadIdx.x < 8) tot[threadIdx.x] = 0;
-  __syncthreads();
-  // sweep 1: octant totals
+// A block of W threads orders one run [b, e) of `keyed` (a cell's points in arrival order, key = cell * 8 +
+// octant) by octant, stable in arrival order: octant totals, the cell's eight sub-cell records, then chunks
+// of W in run order, ranked inside the chunk by ballots, with chunk bases that advance. tot, base and wcnt
+// are the caller's LDS; whoever wrote the run has passed a barrier, and the call ends on one.
+template <int W>
+__device__ __forceinline__ void order_run_by_octant(const PointRec* __restrict__ keyed, int b, int e, int32_t (&tot)[8],
+                                                    int32_t (&base)[8], int32_t (&wcnt)[W / 64][8],
+                                                    const SortedStore& out, int4* __restrict__ rec) {
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   int loc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (int q = b + threadIdx.x; q < e; q += 256) {
+  for (int q = b + t; q < e; q += W) {
     const int oq = keyed[q].key & 7;
 #pragma unroll
     for (int k = 0; k < 8; ++k) loc[k] += oq == k;
   }
+  if (t < 8) tot[t] = 0;
+  __syncthreads();
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    int v = loc[k];
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if (lane == 0 && v) atomicAdd(&tot[k], v);  // LDS, four adders
+    int cnt = loc[k];
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
+    if (lane == 0 && cnt) atomicAdd(&tot[k], cnt);  // LDS
   }
   __syncthreads();
-  if (threadIdx.x == 0) {
-    int run = b;
+  if (t == 0) {
+    int r2 = b;
     for (int k = 0; k < 8; ++k) {
-      base[k] = run;
-      sub_beg[size_t(b) * 8 + k] = run;
-      sub_cnt[size_t(b) * 8 + k] = tot[k];
-      rec[size_t(b) * 8 + k] = make_int4(run, tot[k], -1, 0);
-      run += tot[k];
+      base[k] = r2;
+      r2 += tot[k];
     }
+    write_sub_records(rec, b, tot);
   }
   __syncthreads();
-  // sweep 2: chunks of 256 in run order; rank inside the chunk by ballots, chunk bases advance
-  for (int q0 = b; q0 < e; q0 += 256) {
-    const int q = q0 + threadIdx.x;
+  for (int q0 = b; q0 < e; q0 += W) {
+    const int q = q0 + t;
     const bool live = q < e;
-    PointRec me;
-    me.key = 0;
-    if (live) me = keyed[q];
-    const int o = me.key & 7;
+    PointRec pr;
+    pr.key = 0;
+    if (live) pr = keyed[q];
+    const int o = pr.key & 7;
     int before = 0;  // same octant, earlier lane of this wave
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
@@ -768,23 +663,36 @@ __global__ __launch_bounds__(256) void k_order_big(const int32_t* __restrict__ b
     if (live) {
       int f = base[o] + before;
       for (int ww = 0; ww < w; ++ww) f += wcnt[ww][o];
-      order[f] = me.idx;
-      cell_of[f] = c;
-      sub_of[f] = b * 8 + o;
-      if (p4) {
-        p4[f] = make_float4(float(me.x), float(me.y), float(me.z), 0.f);
-      } else {
-        sx[f] = me.x;
-        sy[f] = me.y;
-        sz[f] = me.z;
-      }
+      out.put(f, pr.idx, pr.key >> 3, pr.x, pr.y, pr.z, b * 8 + o);
     }
     __syncthreads();
-    if (threadIdx.x < 8)
-      base[threadIdx.x] += wcnt[0][threadIdx.x] + wcnt[1][threadIdx.x] + wcnt[2][threadIdx.x] +
-                           wcnt[3][threadIdx.x];
+    if (t < 8) {
+      int add = 0;
+      for (int ww = 0; ww < W / 64; ++ww) add += wcnt[ww][t];
+      base[t] += add;
+    }
     __syncthreads();
   }
+}
+
+// A block per big cell of the atomic binning.
+__global__ __launch_bounds__(256) void k_order_big(const int32_t* __restrict__ big_list,
+                                                   const int32_t* __restrict__ big_cnt,
+                                                   const int32_t* __restrict__ start,
+                                                   const PointRec* __restrict__ keyed,
+                                                   int32_t* __restrict__ order,
+                                                   int32_t* __restrict__ cell_of,
+                                                   int32_t* __restrict__ sub_of,
+                                                   double* __restrict__ sx, double* __restrict__ sy,
+                                                   double* __restrict__ sz, float4* __restrict__ p4,
+                                                   int4* __restrict__ rec, const GridPlan* __restrict__ plan) {
+  __shared__ int32_t tot[8], base[8], wcnt[4][8];
+  const SortedStore out{order, cell_of, sub_of, p4, sx, sy, sz};
+  if (!plan->ok) return;
+  const int nbig = *big_cnt;  // usually 0: the launch is then a few idle blocks
+  for (int bi = blockIdx.x; bi < nbig; bi += gridDim.x) {  // block-uniform
+    const int c = big_list[bi];
+    order_run_by_octant<256>(keyed, start[c], start[c + 1], tot, base, wcnt, out, rec);
   }
 }
 
@@ -803,18 +711,18 @@ __global__ __launch_bounds__(256) void k_order_big(const int32_t* __restrict__ b
 //                     a block reserves its share of every bucket with one returning atomic
 //                     (same shape) and writes the records bucket by bucket: 16 bytes (fp32-representable
 //                     clouds) or 32, and the 4-byte key in an array of its own
-//   B   k_bk_sort     one block per bucket, everything in LDS: a count per cell (arrival rank) and
-//                     eight 8-bit counts per cell packed in a u64 (rank inside the octant), a block
-//                     scan of the bucket's cell counts -> the bucket's piece of the ranked directory
-//                     (grid.hpp, CellDir: a word per 32 cells, a slot per occupied cell; a dense
-//                     start[ncell + 1] was 60 MB per step for a forest's 0.4 % of occupied cells),
-//                     written once; every point then goes straight to its final,
-//                     octant-ordered place. Cells with more than 255 points (a packed count could
-//                     overflow) are ordered by the same block afterwards, as k_order_big does. A
-//                     bucket of at most 64 points skips the counters: one wave ranks its points.
-// Same arrays as build_grid_octants leaves (the order inside a sub-cell is the arrival order of
+//   B   k_bk_sort     one block per bucket, everything in LDS (bk_two_sweeps with the policy BkOctants): a
+//                     count per cell (arrival rank) and eight 8-bit counts per cell packed in a u64 (rank
+//                     inside the octant), a block scan of the bucket's cell counts -> the bucket's piece of
+//                     the ranked directory (grid.hpp, CellDir: a word per 32 cells, a slot per occupied
+//                     cell; a dense start[ncell + 1] was 60 MB per step for a forest's 0.4 % of occupied
+//                     cells), written once; every point then goes straight to its final, octant-ordered
+//                     place. Cells with more than 255 points (a packed count could overflow) are ordered
+//                     by the same block afterwards (order_run_by_octant, as in k_order_big). A bucket of
+//                     at most 64 points skips the counters: one wave ranks its points.
+//       k_bk_sort_plain  the same two sweeps for build_grid (the policy BkPlain): cells only, the dense start
+// Same arrays as the atomic binning leaves (the order inside a sub-cell is the arrival order of
 // atomics in both versions, and nothing downstream depends on it).
-static constexpr int kBkMax = 16384;            // buckets (LDS histogram of the A passes: <= 64 KB)
 static constexpr int kBkBig = 255;              // cells above this are ordered after k_bk_sort's sweep
 static constexpr int kBkPer = 12;               // points of a bucket whose key and ranks a thread of k_bk_sort keeps
                                                 // in registers, one word each: a bucket of up to 512 * 12 = 6144
@@ -904,17 +812,7 @@ __global__ __launch_bounds__(1024) void k_bk_scan(int nbk, const int32_t* __rest
     v[k] = b0 + k < nbk ? tot[b0 + k] : 0;
     s += v[k];
   }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int32_t incl = s;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int32_t t = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += t;
-  }
-  if (lane == 63) wsum[w] = incl;
-  __syncthreads();
-  int32_t run = incl - s;
-  for (int q = 0; q < w; ++q) run += wsum[q];
+  int32_t run = block_excl_scan<1024>(s, wsum);
   for (int k = 0; k < per; ++k) {
     if (b0 + k < nbk) bstart[b0 + k] = run;
     run += v[k];
@@ -972,17 +870,7 @@ __global__ __launch_bounds__(256) void k_bk_scatter(const double* __restrict__ x
       v[k] = b0 + k < nbk ? tot[b0 + k] : 0;
       s += v[k];
     }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int32_t incl = s;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int32_t t = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += t;
-    }
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    int32_t run = incl - s;
-    for (int q = 0; q < w; ++q) run += wsum[q];
+    int32_t run = block_excl_scan<256>(s, wsum);
 #pragma unroll
     for (int k = 0; k < kPer; ++k) {
       if (b0 + k < nbk) {
@@ -1040,6 +928,144 @@ __global__ __launch_bounds__(256) void k_bk_scatter(const double* __restrict__ x
   }
 }
 
+// records of a bucket that a thread of sweep 2 fetches together, one group ahead of the one it places:
+// two of 16 bytes or one of 32 (more cost over 90 VGPRs, or scratch under the cap of 80 that keeps
+// three blocks on a CU)
+template <bool F32>
+static constexpr int kBkGrp = F32 ? 2 : 1;
+
+__device__ __forceinline__ int rec_idx(const float4& p) { return __float_as_int(p.w); }
+__device__ __forceinline__ int rec_idx(const PointRec& p) { return p.idx; }
+
+// ---- the second level: one block sorts one bucket, in two sweeps ---------------------------------------
+// One block per bucket of 2^BITS cells, a thread per eight cells (BITS = 12: 512 threads, three blocks per
+// CU; BITS = 13 for directories beyond 2^26 cells). Sweep 1 reads only the 4-byte keys and counts in LDS:
+// P.rank_of packs what it learns of a point (its cell inside the bucket, its arrival rank, saturated) into
+// one word, and the words of the bucket's first T * kBkPer points stay in registers between the sweeps (on
+// the 1 M-point forest of the benchmark the largest of the 3 687 buckets holds 4 891 points: every bucket).
+// Thread t then owns cells 8 t .. 8 t + 7: P.scan carries their counts across the block, P.directory writes
+// the bucket's piece of the directory and leaves each cell's offset in the bucket where its count was.
+// Sweep 2 fetches the records in unrolled groups, the next group's loads issued before the current one is
+// placed (P.place). The block's chain of dependent memory round trips is bstart -> keys (and the first
+// group of records) -> records -> stores. A bucket beyond the capacity takes further rounds of the same
+// register tile, whose words alone go through word_tmp.
+// A policy P supplies: cnt() (the LDS counts, [2^BITS]), clear(t), rank_of(key, j), scan(v, tot, t) -> the
+// points in the cells before the thread's eight, directory(v, pre, t), place(rec, word, j).
+template <int BITS, bool F32, class Policy>
+__device__ __forceinline__ void bk_two_sweeps(Policy& P, int s, int e,
+                                              const typename BkRec<F32>::type* __restrict__ bucketed,
+                                              const int32_t* __restrict__ keyb, uint32_t* __restrict__ word_tmp) {
+  constexpr int CELLS = 1 << BITS, T = CELLS / 8, CAP = T * kBkPer, G = kBkGrp<F32>;
+  using Rec = typename BkRec<F32>::type;
+  static_assert(kBkPer % G == 0, "whole groups");
+  const int t = threadIdx.x;
+  // the loads are issued before the LDS is cleared: the keys of the register tile (point k * T + t of
+  // the bucket is thread t's k-th) and the first group of records
+  uint32_t wd[kBkPer];
+#pragma unroll
+  for (int k = 0; k < kBkPer; ++k) {
+    const int j = s + k * T + t;
+    wd[k] = j < e ? uint32_t(keyb[j]) : 0u;
+  }
+  Rec cur[G] = {};
+#pragma unroll
+  for (int k = 0; k < G; ++k) {
+    const int j = s + k * T + t;
+    if (j < e) cur[k] = bucketed[j];
+  }
+  P.clear(t);
+  __syncthreads();
+  // sweep 1
+#pragma unroll
+  for (int k = 0; k < kBkPer; ++k) {
+    const int j = s + k * T + t;
+    if (j < e) wd[k] = P.rank_of(wd[k], j);
+  }
+  for (int base = s + CAP; base < e; base += CAP) {  // block-uniform: further rounds of the tile
+    uint32_t kk[kBkPer];
+#pragma unroll
+    for (int k = 0; k < kBkPer; ++k) {
+      const int j = base + k * T + t;
+      kk[k] = j < e ? uint32_t(keyb[j]) : 0u;
+    }
+#pragma unroll
+    for (int k = 0; k < kBkPer; ++k) {
+      const int j = base + k * T + t;
+      if (j < e) word_tmp[j] = P.rank_of(kk[k], j);
+    }
+  }
+  __syncthreads();
+  // the bucket's cells: thread t owns eight consecutive ones
+  int32_t* const cnt = P.cnt();
+  int32_t v[8], tot = 0;
+  {
+    const int4 a = *reinterpret_cast<const int4*>(&cnt[8 * t]);
+    const int4 b = *reinterpret_cast<const int4*>(&cnt[8 * t + 4]);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+    v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) tot += v[k];
+  }
+  int32_t run = P.scan(v, tot, t);
+  int32_t pre[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    pre[k] = run;
+    run += v[k];
+  }
+  P.directory(v, pre, t);
+  __syncthreads();
+  // sweep 2: every point to its place
+#pragma unroll
+  for (int g = 0; g < kBkPer / G; ++g) {
+    if (s + g * G * T >= e) break;  // block-uniform
+    Rec nxt[G] = {};
+    if (g + 1 < kBkPer / G) {
+#pragma unroll
+      for (int k = 0; k < G; ++k) {
+        const int j = s + ((g + 1) * G + k) * T + t;
+        if (j < e) nxt[k] = bucketed[j];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < G; ++k) {
+      const int j = s + (g * G + k) * T + t;
+      if (j < e) P.place(cur[k], wd[g * G + k], j);
+    }
+#pragma unroll
+    for (int k = 0; k < G; ++k) cur[k] = nxt[k];
+  }
+  for (int base = s + CAP; base < e; base += CAP) {  // block-uniform
+#pragma unroll
+    for (int g = 0; g < kBkPer / G; ++g) {
+      if (base + g * G * T >= e) break;
+      Rec r[G] = {};
+      uint32_t w[G];
+#pragma unroll
+      for (int k = 0; k < G; ++k) {
+        const int j = base + (g * G + k) * T + t;
+        w[k] = 0u;
+        if (j < e) {
+          r[k] = bucketed[j];
+          w[k] = word_tmp[j];
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < G; ++k) {
+        const int j = base + (g * G + k) * T + t;
+        if (j < e) P.place(r[k], w[k], j);
+      }
+    }
+  }
+}
+
+// ---- DBSCAN's policy: cells AND octants, the ranked directory ------------------------------------------
+// A count per cell (arrival rank) and eight 8-bit counts per cell packed in a u64 (rank inside the octant);
+// the scan carries the occupied cells beside the points (their ranks are the directory's slots); every
+// point goes straight to its final, octant-ordered place. Cells with more than kBkBig points (a packed
+// count could overflow) go to their run of `keyed` in arrival order instead, and the block orders them
+// after the sweeps.
+
 // sum of the bytes of x below byte o (eight 8-bit counts packed in a u64)
 __device__ __forceinline__ int bytes_below(unsigned long long x, int o) {
   x &= (1ull << (8 * o)) - 1ull;
@@ -1069,20 +1095,95 @@ __device__ __forceinline__ uint32_t bk_word(int lk, int rr, int r8) {
   return (uint32_t(lk) << 16) | (uint32_t(rr < 255 ? rr : 255) << 8) | uint32_t(r8);
 }
 
-// records of a bucket that a thread of sweep 2 fetches together, one group ahead of the one it places:
-// two of 16 bytes or one of 32 (more cost over 90 VGPRs, or scratch under the cap of 80 that keeps
-// three blocks on a CU)
-template <bool F32>
-static constexpr int kBkGrp = F32 ? 2 : 1;
+template <int BITS, bool F32>
+struct BkOctants {
+  static constexpr int CELLS = 1 << BITS, T = CELLS / 8;
+  using Rec = typename BkRec<F32>::type;
+  BkLds<BITS>& L;
+  const int s, e;         // the bucket's points
+  const int64_t c0;       // its first cell
+  DirWord* const wds;     // its piece of the ranked directory: the words, and the slots from sb
+  int32_t* const slots;
+  const uint32_t sb;
+  int4* const rec;
+  PointRec* const keyed;  // big cells' runs in arrival order
+  int32_t* const rank_tmp;
+  const SortedStore& out;
+  uint32_t occ8;          // which of the thread's eight cells hold a point; how many; how many before them
+  int nocc;
+  int32_t orun;
 
-// One block per bucket of 2^BITS cells, a thread per eight cells (BITS = 12: 512 threads and 49 KB of
-// LDS, three blocks per CU; BITS = 13 for directories beyond 2^26 cells). Sweep 1 reads only the
-// 4-byte keys; the keys and ranks of the bucket's first T * kBkPer points stay in registers between
-// the sweeps (on the 1 M-point forest of the benchmark the largest of the 3 687 buckets holds 4 891
-// points: every bucket), and sweep 2 fetches the records in unrolled groups, the next group's loads
-// issued before the current one is placed. The block's chain of dependent memory round trips is
-// bstart -> keys (and the first group of records) -> records -> stores. A bucket beyond the capacity
-// takes further rounds of the same register tile, whose words alone go through word_tmp.
+  __device__ __forceinline__ int32_t* cnt() const { return L.cnt; }
+  __device__ __forceinline__ void clear(int t) const {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      L.oct[k * T + t] = 0ull;
+      L.cnt[k * T + t] = 0;
+    }
+    if (t < CELLS / 32) L.big[t] = 0u;
+    if (t == 0) L.any_big = 0;
+  }
+  // arrival rank in the cell and in the octant
+  __device__ __forceinline__ uint32_t rank_of(uint32_t ky, int j) const {
+    const int lk = int(ky) & (8 * CELLS - 1), cl = lk >> 3, o = lk & 7;
+    const int rr = atomicAdd(&L.cnt[cl], 1);
+    const int r8 = int((atomicAdd(&L.oct[cl], 1ull << (8 * o)) >> (8 * o)) & 255ull);
+    if (rr >= 255) rank_tmp[j] = rr;
+    return bk_word(lk, rr, r8);
+  }
+  // (the same scan carries the number of occupied cells before the thread's eight: their slots)
+  __device__ __forceinline__ int32_t scan(const int32_t (&v)[8], int32_t tot, int) {
+    occ8 = 0u;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) occ8 |= v[k] ? 1u << k : 0u;
+    nocc = __popc(occ8);
+    int32_t run;
+    block_excl_scan<T>(tot, nocc, L.wsum, L.osum, &run, &orun);
+    return run;
+  }
+  __device__ __forceinline__ void directory(const int32_t (&v)[8], const int32_t (&pre)[8], int t) const {
+    {
+      // a directory word is four threads' cells: the first of the four collects the others' bits
+      const uint32_t b1 = __shfl_down(occ8, 1, 64), b2 = __shfl_down(occ8, 2, 64), b3 = __shfl_down(occ8, 3, 64);
+      if ((t & 3) == 0) wds[t >> 2] = DirWord{occ8 | (b1 << 8) | (b2 << 16) | (b3 << 24), sb + uint32_t(orun)};
+      if (t == T - 1) slots[sb + uint32_t(orun + nocc)] = e;  // closes the bucket's slots
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int cl = 8 * t + k;
+      L.cnt[cl] = pre[k];
+      if (v[k] == 0) continue;
+      const int b = s + pre[k];  // the cell's first sorted position: identifies its sub-cells
+      slots[sb + uint32_t(orun) + __popc(occ8 & ((1u << k) - 1u))] = b;
+      if (v[k] > kBkBig) {  // rare: the block orders the cell after sweep 2
+        atomicOr(&L.big[cl >> 5], 1u << (cl & 31));
+        L.any_big = 1;
+        continue;
+      }
+      write_sub_records(rec, b, L.oct[cl]);
+    }
+  }
+  // every point to its final place (big cells: to the cell's run of `keyed`, in arrival order)
+  __device__ __forceinline__ void place(const Rec& p, uint32_t w, int j) const {
+    const int lk = int(w >> 16), cl = lk >> 3, o = lk & 7, arr = int((w >> 8) & 255u);
+    const int b = s + L.cnt[cl];
+    if ((L.big[cl >> 5] >> (cl & 31)) & 1u) {
+      PointRec q;
+      q.x = p.x;
+      q.y = p.y;
+      q.z = p.z;
+      q.key = int(c0 << 3) + lk;
+      q.idx = rec_idx(p);
+      keyed[b + (arr < 255 ? arr : rank_tmp[j])] = q;
+      return;
+    }
+    out.put(b + bytes_below(L.oct[cl], o) + int(w & 255u), rec_idx(p), int(c0) + cl, p.x, p.y, p.z, b * 8 + o);
+  }
+};
+
+// k_bk_sort: a bucket of DBSCAN's binning. A bucket of at most 64 points skips the counters: one wave
+// ranks its points. Otherwise the two sweeps (BITS = 12: 49 KB of LDS), and after them the whole block
+// orders each cell above kBkBig points, as k_order_big does for the atomic binning.
 template <int BITS, bool F32>
 __global__ __launch_bounds__((1 << BITS) / 8, BITS == 12 ? 6 : 4) void k_bk_sort(
     const int32_t* __restrict__ bstart,
@@ -1095,11 +1196,11 @@ __global__ __launch_bounds__((1 << BITS) / 8, BITS == 12 ? 6 : 4) void k_bk_sort
     PointRec* __restrict__ keyed /*big cells' runs in arrival order*/,
     const GridPlan* __restrict__ plan /*the number of buckets (the launch may have more blocks)*/,
     unsigned long long* __restrict__ st /*stamps or null*/) {
-  constexpr int CELLS = 1 << BITS, T = CELLS / 8, CAP = T * kBkPer, G = kBkGrp<F32>;
+  constexpr int CELLS = 1 << BITS, T = CELLS / 8;
   using Rec = typename BkRec<F32>::type;
-  static_assert(kBkPer % G == 0, "whole groups");
   __shared__ BkLds<BITS> L;
   stamped(st, [&] {
+  const SortedStore out{order, cell_of, sub_of, F32 ? p4 : nullptr, sx, sy, sz};
   const int bk = blockIdx.x, t = threadIdx.x;
   if (!plan->ok || bk >= plan->nbk) return;
   const int s = bstart[bk], e = bstart[bk + 1];
@@ -1140,28 +1241,11 @@ __global__ __launch_bounds__((1 << BITS) / 8, BITS == 12 ? 6 : 4) void k_bk_sort
         if ((kq >> 3) == (lk >> 3)) oc += 1ull << (8 * (kq & 7));
       }
       if (live) {
-        const int cl = lk >> 3, o = lk & 7, b = s + below_cell, f = s + below_key;
+        const int cl = lk >> 3, o = lk & 7, b = s + below_cell;
         cells[below_key] = cl;
-        cell_of[f] = int(c0) + cl;
-        sub_of[f] = b * 8 + o;
-        if constexpr (F32) {
-          order[f] = __float_as_int(p.w);
-          p4[f] = make_float4(p.x, p.y, p.z, 0.f);
-        } else {
-          order[f] = p.idx;
-          sx[f] = p.x;
-          sy[f] = p.y;
-          sz[f] = p.z;
-        }
-        if (below_key == below_cell) {  // the first point of its cell: the cell's sub-cell records
-          int r2 = b;
-#pragma unroll
-          for (int o2 = 0; o2 < 8; ++o2) {
-            const int cnt = int((oc >> (8 * o2)) & 255ull);
-            rec[size_t(b) * 8 + o2] = make_int4(r2, cnt, -1, 0);
-            r2 += cnt;
-          }
-        }
+        out.put(s + below_key, rec_idx(p), int(c0) + cl, p.x, p.y, p.z, b * 8 + o);
+        // the first point of its cell: the cell's sub-cell records
+        if (below_key == below_cell) write_sub_records(rec, b, oc);
       }
     }
     __syncthreads();
@@ -1195,274 +1279,91 @@ __global__ __launch_bounds__((1 << BITS) / 8, BITS == 12 ? 6 : 4) void k_bk_sort
     }
     return;
   }
-  // the loads are issued before the LDS is cleared: the keys of the register tile (point k * T + t of
-  // the bucket is thread t's k-th) and the first group of records
-  uint32_t wd[kBkPer];
-#pragma unroll
-  for (int k = 0; k < kBkPer; ++k) {
-    const int j = s + k * T + t;
-    wd[k] = j < e ? uint32_t(keyb[j]) : 0u;
-  }
-  Rec cur[G] = {};
-#pragma unroll
-  for (int k = 0; k < G; ++k) {
-    const int j = s + k * T + t;
-    if (j < e) cur[k] = bucketed[j];
-  }
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    L.oct[k * T + t] = 0ull;
-    L.cnt[k * T + t] = 0;
-  }
-  if (t < CELLS / 32) L.big[t] = 0u;
-  if (t == 0) L.any_big = 0;
-  __syncthreads();
-  // sweep 1: arrival rank in the cell and in the octant
-  auto rank_of = [&](uint32_t ky, int j) {
-    const int lk = int(ky) & (8 * CELLS - 1), cl = lk >> 3, o = lk & 7;
-    const int rr = atomicAdd(&L.cnt[cl], 1);
-    const int r8 = int((atomicAdd(&L.oct[cl], 1ull << (8 * o)) >> (8 * o)) & 255ull);
-    if (rr >= 255) rank_tmp[j] = rr;
-    return bk_word(lk, rr, r8);
-  };
-#pragma unroll
-  for (int k = 0; k < kBkPer; ++k) {
-    const int j = s + k * T + t;
-    if (j < e) wd[k] = rank_of(wd[k], j);
-  }
-  for (int base = s + CAP; base < e; base += CAP) {  // block-uniform: further rounds of the tile
-    uint32_t kk[kBkPer];
-#pragma unroll
-    for (int k = 0; k < kBkPer; ++k) {
-      const int j = base + k * T + t;
-      kk[k] = j < e ? uint32_t(keyb[j]) : 0u;
-    }
-#pragma unroll
-    for (int k = 0; k < kBkPer; ++k) {
-      const int j = base + k * T + t;
-      if (j < e) word_tmp[j] = rank_of(kk[k], j);
-    }
-  }
-  __syncthreads();
-  // the bucket's cells: thread t owns eight consecutive ones
-  int32_t v[8], tot = 0;
-  {
-    const int4 a = *reinterpret_cast<const int4*>(&L.cnt[8 * t]);
-    const int4 b = *reinterpret_cast<const int4*>(&L.cnt[8 * t + 4]);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-    v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) tot += v[k];
-  }
-  // (the same scan carries the number of occupied cells before the thread's eight: their slots)
-  uint32_t occ8 = 0u;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) occ8 |= v[k] ? 1u << k : 0u;
-  const int nocc = __popc(occ8);
-  const int lane = t & 63, w = t >> 6;
-  int32_t incl = tot, oincl = nocc;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int32_t u = __shfl_up(incl, off, 64), uo = __shfl_up(oincl, off, 64);
-    if (lane >= off) {
-      incl += u;
-      oincl += uo;
-    }
-  }
-  if (lane == 63) {
-    L.wsum[w] = incl;
-    L.osum[w] = oincl;
-  }
-  __syncthreads();
-  int32_t run = incl - tot, orun = oincl - nocc;
-  for (int q = 0; q < w; ++q) {
-    run += L.wsum[q];
-    orun += L.osum[q];
-  }
-  int32_t pre[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    pre[k] = run;
-    run += v[k];
-  }
-  {
-    // a directory word is four threads' cells: the first of the four collects the others' bits
-    const uint32_t b1 = __shfl_down(occ8, 1, 64), b2 = __shfl_down(occ8, 2, 64), b3 = __shfl_down(occ8, 3, 64);
-    if ((t & 3) == 0) wds[t >> 2] = DirWord{occ8 | (b1 << 8) | (b2 << 16) | (b3 << 24), sb + uint32_t(orun)};
-    if (t == T - 1) slots[sb + uint32_t(orun + nocc)] = e;  // closes the bucket's slots
-  }
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const int cl = 8 * t + k;
-    L.cnt[cl] = pre[k];
-    if (v[k] == 0) continue;
-    const int b = s + pre[k];  // the cell's first sorted position: identifies its sub-cells
-    slots[sb + uint32_t(orun) + __popc(occ8 & ((1u << k) - 1u))] = b;
-    if (v[k] > kBkBig) {  // rare: the block orders the cell after sweep 2
-      atomicOr(&L.big[cl >> 5], 1u << (cl & 31));
-      L.any_big = 1;
-      continue;
-    }
-    const unsigned long long c64 = L.oct[cl];
-    int r2 = b;
-#pragma unroll
-    for (int o = 0; o < 8; ++o) {
-      const int cnt = int((c64 >> (8 * o)) & 255ull);
-      rec[size_t(b) * 8 + o] = make_int4(r2, cnt, -1, 0);
-      r2 += cnt;
-    }
-  }
-  __syncthreads();
-  // sweep 2: every point to its final place (big cells: to the cell's run of `keyed`, in arrival order)
-  auto place = [&](const Rec& p, uint32_t w, int j) {
-    const int lk = int(w >> 16), cl = lk >> 3, o = lk & 7, arr = int((w >> 8) & 255u);
-    const int b = s + L.cnt[cl];
-    if ((L.big[cl >> 5] >> (cl & 31)) & 1u) {
-      PointRec q;
-      q.x = p.x;
-      q.y = p.y;
-      q.z = p.z;
-      q.key = int(c0 << 3) + lk;
-      if constexpr (F32)
-        q.idx = __float_as_int(p.w);
-      else
-        q.idx = p.idx;
-      keyed[b + (arr < 255 ? arr : rank_tmp[j])] = q;
-      return;
-    }
-    const int f = b + bytes_below(L.oct[cl], o) + int(w & 255u);
-    cell_of[f] = int(c0) + cl;
-    sub_of[f] = b * 8 + o;
-    if constexpr (F32) {
-      order[f] = __float_as_int(p.w);
-      p4[f] = make_float4(p.x, p.y, p.z, 0.f);
-    } else {
-      order[f] = p.idx;
-      sx[f] = p.x;
-      sy[f] = p.y;
-      sz[f] = p.z;
-    }
-  };
-#pragma unroll
-  for (int g = 0; g < kBkPer / G; ++g) {
-    if (s + g * G * T >= e) break;  // block-uniform
-    Rec nxt[G] = {};
-    if (g + 1 < kBkPer / G) {
-#pragma unroll
-      for (int k = 0; k < G; ++k) {
-        const int j = s + ((g + 1) * G + k) * T + t;
-        if (j < e) nxt[k] = bucketed[j];
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < G; ++k) {
-      const int j = s + (g * G + k) * T + t;
-      if (j < e) place(cur[k], wd[g * G + k], j);
-    }
-#pragma unroll
-    for (int k = 0; k < G; ++k) cur[k] = nxt[k];
-  }
-  for (int base = s + CAP; base < e; base += CAP) {  // block-uniform
-#pragma unroll
-    for (int g = 0; g < kBkPer / G; ++g) {
-      if (base + g * G * T >= e) break;
-      Rec r[G] = {};
-      uint32_t w[G];
-#pragma unroll
-      for (int k = 0; k < G; ++k) {
-        const int j = base + (g * G + k) * T + t;
-        w[k] = 0u;
-        if (j < e) {
-          r[k] = bucketed[j];
-          w[k] = word_tmp[j];
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < G; ++k) {
-        const int j = base + (g * G + k) * T + t;
-        if (j < e) place(r[k], w[k], j);
-      }
-    }
-  }
-  // Cells above kBkBig points (none on a scan at eps ~ 10 x the point spacing): the whole block sorts each
-  // one's run of `keyed` by octant, stable in arrival order, as k_order_big does for the atomic binning (two
-  // sweeps, ranks inside a chunk by ballots). Without such a cell nothing more runs, and no kernel is
-  // launched for them.
+  BkOctants<BITS, F32> P{L, s, e, c0, wds, slots, sb, rec, keyed, rank_tmp, out, 0u, 0, 0};
+  bk_two_sweeps<BITS, F32>(P, s, e, bucketed, keyb, word_tmp);
+  // Cells above kBkBig points (none on a scan at eps ~ 10 x the point spacing). Without such a cell nothing
+  // more runs, and no kernel is launched for them.
   __syncthreads();  // the big cells' runs of `keyed` are written, L.any_big is final
   if (!L.any_big) return;  // block-uniform
   for (int wd = 0; wd < CELLS / 32; ++wd) {
     for (uint32_t bm = L.big[wd]; bm; bm &= bm - 1u) {  // block-uniform
       const int cl = wd * 32 + __ffs(bm) - 1;
-      const int b = s + L.cnt[cl], e2 = s + (cl + 1 < CELLS ? L.cnt[cl + 1] : e - s);
-      int loc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      for (int q = b + t; q < e2; q += T) {
-        const int oq = keyed[q].key & 7;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) loc[k] += oq == k;
-      }
-      if (t < 8) L.btot[t] = 0;
-      __syncthreads();
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        int cnt = loc[k];
-        for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
-        if (lane == 0 && cnt) atomicAdd(&L.btot[k], cnt);  // LDS
-      }
-      __syncthreads();
-      if (t == 0) {
-        int r2 = b;
-        for (int k = 0; k < 8; ++k) {
-          L.bbase[k] = r2;
-          rec[size_t(b) * 8 + k] = make_int4(r2, L.btot[k], -1, 0);
-          r2 += L.btot[k];
-        }
-      }
-      __syncthreads();
-      for (int q0 = b; q0 < e2; q0 += T) {
-        const int q = q0 + t;
-        const bool live = q < e2;
-        PointRec pr;
-        pr.key = 0;
-        if (live) pr = keyed[q];
-        const int o = pr.key & 7;
-        int before = 0;  // same octant, earlier lane of this wave
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const unsigned long long m = __ballot(live && o == k);
-          if (lane == 0) L.bw[w][k] = __popcll(m);
-          if (o == k) before = __popcll(m & ((1ull << lane) - 1ull));
-        }
-        __syncthreads();
-        if (live) {
-          int f = L.bbase[o] + before;
-          for (int ww = 0; ww < w; ++ww) f += L.bw[ww][o];
-          order[f] = pr.idx;
-          cell_of[f] = pr.key >> 3;
-          sub_of[f] = b * 8 + o;
-          if (p4) {
-            p4[f] = make_float4(float(pr.x), float(pr.y), float(pr.z), 0.f);
-          } else {
-            sx[f] = pr.x;
-            sy[f] = pr.y;
-            sz[f] = pr.z;
-          }
-        }
-        __syncthreads();
-        if (t < 8) {
-          int add = 0;
-          for (int ww = 0; ww < T / 64; ++ww) add += L.bw[ww][t];
-          L.bbase[t] += add;
-        }
-        __syncthreads();
-      }
+      order_run_by_octant<T>(keyed, s + L.cnt[cl], s + (cl + 1 < CELLS ? L.cnt[cl + 1] : e - s), L.btot, L.bbase,
+                             L.bw, out, rec);
     }
   }
   });
 }
 
-// The same second level without octants (build_grid): a count per cell is all there is, so a bucket
-// of 2^BITS cells needs 4 bytes of LDS per cell, the arrival rank IS the place inside the cell, and
-// no cell is too big. occ[bucket] = occupied cells of the bucket (count_occupied adds them up).
+// ---- build_grid's policy: cells only, the dense directory ----------------------------------------------
+// A count per cell is all there is, so a bucket of 2^BITS cells needs 4 bytes of LDS per cell, the arrival
+// rank IS the place inside the cell, and no cell is too big. A point's word: the cell inside the bucket in
+// the top BITS bits, below it the arrival rank, saturated (the exact value of a rank that does not fit goes
+// through rank_tmp). The directory is the dense `start`, written as int4 pairs; beside the points the
+// block adds up its occupied cells: occ[bucket] (count_occupied adds them up).
+template <int BITS>
+struct BkPlainLds {
+  int32_t cnt[1 << BITS];
+  int32_t wsum[16], wocc[16];
+};
+
+template <int BITS, bool F32>
+struct BkPlain {
+  static constexpr int CELLS = 1 << BITS, T = CELLS / 8, RB = 32 - BITS, RMAX = (1 << RB) - 1;
+  using Rec = typename BkRec<F32>::type;
+  BkPlainLds<BITS>& L;
+  const int s, bk;
+  const int64_t c0, ncell1;
+  int32_t* const start;
+  int32_t* const occ;
+  int32_t* const rank_tmp;
+  const SortedStore& out;
+
+  __device__ __forceinline__ int32_t* cnt() const { return L.cnt; }
+  __device__ __forceinline__ void clear(int t) const {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) L.cnt[k * T + t] = 0;
+  }
+  __device__ __forceinline__ uint32_t rank_of(uint32_t ky, int j) const {
+    const int cl = int(ky >> 3) & (CELLS - 1);
+    const int rr = atomicAdd(&L.cnt[cl], 1);
+    if (rr >= RMAX) rank_tmp[j] = rr;
+    return (uint32_t(cl) << RB) | uint32_t(rr < RMAX ? rr : RMAX);
+  }
+  __device__ __forceinline__ int32_t scan(const int32_t (&v)[8], int32_t tot, int t) const {
+    int32_t nocc = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) nocc += v[k] > 0;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) nocc += __shfl_down(nocc, off, 64);
+    if ((t & 63) == 0) L.wocc[t >> 6] = nocc;
+    const int32_t run = block_excl_scan<T>(tot, L.wsum);
+    if (t == 0) {
+      int o = 0;
+      for (int q = 0; q < T / 64; ++q) o += L.wocc[q];
+      occ[bk] = o;
+    }
+    return run;
+  }
+  __device__ __forceinline__ void directory(const int32_t (&)[8], const int32_t (&pre)[8], int t) const {
+    const int64_t cidx = c0 + 8 * t;
+    if (cidx + 7 < ncell1) {
+      *reinterpret_cast<int4*>(start + cidx) = make_int4(s + pre[0], s + pre[1], s + pre[2], s + pre[3]);
+      *reinterpret_cast<int4*>(start + cidx + 4) = make_int4(s + pre[4], s + pre[5], s + pre[6], s + pre[7]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (cidx + k < ncell1) start[cidx + k] = s + pre[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) L.cnt[8 * t + k] = pre[k];
+  }
+  __device__ __forceinline__ void place(const Rec& p, uint32_t w, int j) const {
+    const int cl = int(w >> RB), arr = int(w & uint32_t(RMAX));
+    out.put(s + L.cnt[cl] + (arr < RMAX ? arr : rank_tmp[j]), rec_idx(p), int(c0) + cl, p.x, p.y, p.z);
+  }
+};
+
 template <int BITS, bool F32>
 __global__ __launch_bounds__((1 << BITS) / 8, BITS == 12 ? 6 : 4) void k_bk_sort_plain(
     int64_t ncell1, const int32_t* __restrict__ bstart, const typename BkRec<F32>::type* __restrict__ bucketed,
@@ -1470,10 +1371,9 @@ __global__ __launch_bounds__((1 << BITS) / 8, BITS == 12 ? 6 : 4) void k_bk_sort
     int32_t* __restrict__ start, int32_t* __restrict__ order,
     int32_t* __restrict__ cell_of, double* __restrict__ sx, double* __restrict__ sy, double* __restrict__ sz,
     float4* __restrict__ p4 /*non-null: fp32 records instead of sx / sy / sz*/, int32_t* __restrict__ occ) {
-  constexpr int CELLS = 1 << BITS, T = CELLS / 8, CAP = T * kBkPer, G = kBkGrp<F32>;
-  using Rec = typename BkRec<F32>::type;
-  __shared__ int32_t cnt[CELLS];
-  __shared__ int32_t wsum[16], wocc[16];
+  constexpr int T = (1 << BITS) / 8;
+  __shared__ BkPlainLds<BITS> L;
+  const SortedStore out{order, cell_of, nullptr, F32 ? p4 : nullptr, sx, sy, sz};
   const int bk = blockIdx.x, t = threadIdx.x;
   const int s = bstart[bk], e = bstart[bk + 1];
   const int64_t c0 = int64_t(bk) << BITS;
@@ -1491,168 +1391,38 @@ __global__ __launch_bounds__((1 << BITS) / 8, BITS == 12 ? 6 : 4) void k_bk_sort
     if (t == 0) occ[bk] = 0;
     return;
   }
-  // as k_bk_sort: a word per point of the first CAP points in registers (the cell inside the bucket in
-  // the top BITS bits, below it the arrival rank, saturated: the exact value of a rank that does not fit
-  // goes through rank_tmp), the records fetched in groups by the second sweep, further rounds of the
-  // tile for a bucket beyond CAP
-  constexpr int RB = 32 - BITS;
-  constexpr int RMAX = (1 << RB) - 1;
-  uint32_t wd[kBkPer];
-#pragma unroll
-  for (int k = 0; k < kBkPer; ++k) {
-    const int j = s + k * T + t;
-    wd[k] = j < e ? uint32_t(keyb[j]) : 0u;
-  }
-  Rec cur[G] = {};
-#pragma unroll
-  for (int k = 0; k < G; ++k) {
-    const int j = s + k * T + t;
-    if (j < e) cur[k] = bucketed[j];
-  }
-#pragma unroll
-  for (int k = 0; k < 8; ++k) cnt[k * T + t] = 0;
-  __syncthreads();
-  auto rank_of = [&](uint32_t ky, int j) {
-    const int cl = int(ky >> 3) & (CELLS - 1);
-    const int rr = atomicAdd(&cnt[cl], 1);
-    if (rr >= RMAX) rank_tmp[j] = rr;
-    return (uint32_t(cl) << RB) | uint32_t(rr < RMAX ? rr : RMAX);
-  };
-#pragma unroll
-  for (int k = 0; k < kBkPer; ++k) {
-    const int j = s + k * T + t;
-    if (j < e) wd[k] = rank_of(wd[k], j);
-  }
-  for (int base = s + CAP; base < e; base += CAP) {  // block-uniform
-    uint32_t kk[kBkPer];
-#pragma unroll
-    for (int k = 0; k < kBkPer; ++k) {
-      const int j = base + k * T + t;
-      kk[k] = j < e ? uint32_t(keyb[j]) : 0u;
-    }
-#pragma unroll
-    for (int k = 0; k < kBkPer; ++k) {
-      const int j = base + k * T + t;
-      if (j < e) word_tmp[j] = rank_of(kk[k], j);
-    }
-  }
-  __syncthreads();
-  int32_t v[8], tot = 0, nocc = 0;
-  {
-    const int4 a = *reinterpret_cast<const int4*>(&cnt[8 * t]);
-    const int4 b = *reinterpret_cast<const int4*>(&cnt[8 * t + 4]);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-    v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      tot += v[k];
-      nocc += v[k] > 0;
-    }
-  }
-  const int lane = t & 63, w = t >> 6;
-  int32_t incl = tot;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int32_t u = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += u;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) nocc += __shfl_down(nocc, off, 64);
-  if (lane == 63) wsum[w] = incl;
-  if (lane == 0) wocc[w] = nocc;
-  __syncthreads();
-  int32_t run = incl - tot;
-  for (int q = 0; q < w; ++q) run += wsum[q];
-  if (t == 0) {
-    int o = 0;
-    for (int q = 0; q < T / 64; ++q) o += wocc[q];
-    occ[bk] = o;
-  }
-  int32_t pre[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    pre[k] = run;
-    run += v[k];
-  }
-  {
-    const int64_t cidx = c0 + 8 * t;
-    if (cidx + 7 < ncell1) {
-      *reinterpret_cast<int4*>(start + cidx) = make_int4(s + pre[0], s + pre[1], s + pre[2], s + pre[3]);
-      *reinterpret_cast<int4*>(start + cidx + 4) = make_int4(s + pre[4], s + pre[5], s + pre[6], s + pre[7]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 8; ++k)
-        if (cidx + k < ncell1) start[cidx + k] = s + pre[k];
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 8; ++k) cnt[8 * t + k] = pre[k];
-  __syncthreads();
-  auto place = [&](const Rec& p, uint32_t w, int j) {
-    const int cl = int(w >> RB), arr = int(w & uint32_t(RMAX));
-    const int f = s + cnt[cl] + (arr < RMAX ? arr : rank_tmp[j]);
-    cell_of[f] = int(c0) + cl;
-    if constexpr (F32) {
-      order[f] = __float_as_int(p.w);
-      p4[f] = make_float4(p.x, p.y, p.z, 0.f);
-    } else {
-      order[f] = p.idx;
-      sx[f] = p.x;
-      sy[f] = p.y;
-      sz[f] = p.z;
-    }
-  };
-#pragma unroll
-  for (int g = 0; g < kBkPer / G; ++g) {
-    if (s + g * G * T >= e) break;  // block-uniform
-    Rec nxt[G] = {};
-    if (g + 1 < kBkPer / G) {
-#pragma unroll
-      for (int k = 0; k < G; ++k) {
-        const int j = s + ((g + 1) * G + k) * T + t;
-        if (j < e) nxt[k] = bucketed[j];
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < G; ++k) {
-      const int j = s + (g * G + k) * T + t;
-      if (j < e) place(cur[k], wd[g * G + k], j);
-    }
-#pragma unroll
-    for (int k = 0; k < G; ++k) cur[k] = nxt[k];
-  }
-  for (int base = s + CAP; base < e; base += CAP) {  // block-uniform
-#pragma unroll
-    for (int g = 0; g < kBkPer / G; ++g) {
-      if (base + g * G * T >= e) break;
-      Rec r[G] = {};
-      uint32_t w[G];
-#pragma unroll
-      for (int k = 0; k < G; ++k) {
-        const int j = base + (g * G + k) * T + t;
-        w[k] = 0u;
-        if (j < e) {
-          r[k] = bucketed[j];
-          w[k] = word_tmp[j];
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < G; ++k) {
-        const int j = base + (g * G + k) * T + t;
-        if (j < e) place(r[k], w[k], j);
-      }
-    }
-  }
+  BkPlain<BITS, F32> P{L, s, bk, c0, ncell1, start, occ, rank_tmp, out};
+  bk_two_sweeps<BITS, F32>(P, s, e, bucketed, keyb, word_tmp);
 }
 
 // build_grid through the two-level sort; returns false (nothing launched) when the directory has
 // more buckets than the A passes' LDS histogram holds or PYQSM_GRID_BIN=atomic asks for the
 // one-atomic-per-point path.
 static bool bucketed_fits(const DevGrid& g) {
-  const int bits = g.ncell + 1 <= (int64_t(kBkMax) << 12) ? 12 : 13;
-  const int64_t nbk = (g.ncell + (int64_t(1) << bits)) >> bits;
   const char* env = getenv("PYQSM_GRID_BIN");
-  return nbk <= kBkMax && !(env && !strcmp(env, "atomic"));
+  return bucket_shape(g.ncell).nbk <= kBkMax && !(env && !strcmp(env, "atomic"));
+}
+
+// launch(Sort<BITS, F32>{}) for the bucket size and the record form of a second-level launch
+template <int BITS_, bool F32_>
+struct Sort {
+  static constexpr int BITS = BITS_;
+  static constexpr bool F32 = F32_;
+  using Rec = typename BkRec<F32_>::type;
+};
+template <class F>
+static void on_sort_shape(int bits, bool f32, F&& launch) {
+  if (bits == 12) {
+    if (f32)
+      launch(Sort<12, true>{});
+    else
+      launch(Sort<12, false>{});
+  } else {
+    if (f32)
+      launch(Sort<13, true>{});
+    else
+      launch(Sort<13, false>{});
+  }
 }
 
 // the A passes; `bucketed` holds float4 (f32) or PointRec records
@@ -1681,17 +1451,9 @@ static void enqueue_bk_a(Ctx* c, int mode, bool f32, const double* xyz, int64_t 
                        key_tmp, tot, cursor, bstart, fused, static_cast<PointRec*>(bucketed), keyb, d_plan);
 }
 
-template <int BITS, bool F32>
-static void launch_bk_sort_plain(Ctx* c, int64_t nbk, const int32_t* bstart, const void* bucketed, const int32_t* keyb,
-                                 uint32_t* word_tmp, int32_t* rank_tmp, DevGrid* g) {
-  hipLaunchKernelGGL((k_bk_sort_plain<BITS, F32>), dim3(unsigned(nbk)), dim3((1 << BITS) / 8), 0, c->stream,
-                     g->ncell + 1, bstart, static_cast<const typename BkRec<F32>::type*>(bucketed), keyb, word_tmp,
-                     rank_tmp, g->start, g->order, g->cell_of, g->sx, g->sy, g->sz, g->p4, g->occ_part);
-}
-
 static int build_grid_bucketed(Ctx* c, const double* xyz, int64_t n, DevGrid* g) {
-  const int bits = g->ncell + 1 <= (int64_t(kBkMax) << 12) ? 12 : 13;
-  const int64_t nbk = (g->ncell + (int64_t(1) << bits)) >> bits;
+  const int bits = bucket_shape(g->ncell).bits;
+  const int64_t nbk = bucket_shape(g->ncell).nbk;
   const bool f32 = g->p4 != nullptr;  // float4 records in, float4 records out
   int32_t *tot, *bstart, *cursor, *key_tmp, *keyb, *rank_tmp;
   uint32_t* word_tmp;
@@ -1718,48 +1480,33 @@ static int build_grid_bucketed(Ctx* c, const double* xyz, int64_t n, DevGrid* g)
   const int raw[3] = {0, 0, 0};
   enqueue_bk_a(c, 2, f32, xyz, n, grid_params(*g), raw, AxisMap{nullptr, nullptr, nullptr}, nbk, bits, key_tmp, tot,
                cursor, bstart, bucketed, keyb, nullptr);
-  if (bits == 12) {
-    if (f32)
-      launch_bk_sort_plain<12, true>(c, nbk, bstart, bucketed, keyb, word_tmp, rank_tmp, g);
-    else
-      launch_bk_sort_plain<12, false>(c, nbk, bstart, bucketed, keyb, word_tmp, rank_tmp, g);
-  } else {
-    if (f32)
-      launch_bk_sort_plain<13, true>(c, nbk, bstart, bucketed, keyb, word_tmp, rank_tmp, g);
-    else
-      launch_bk_sort_plain<13, false>(c, nbk, bstart, bucketed, keyb, word_tmp, rank_tmp, g);
-  }
+  on_sort_shape(bits, f32, [&](auto S) {
+    using K = decltype(S);
+    hipLaunchKernelGGL((k_bk_sort_plain<K::BITS, K::F32>), dim3(unsigned(nbk)), dim3((1 << K::BITS) / 8), 0, c->stream,
+                       g->ncell + 1, bstart, static_cast<const typename K::Rec*>(bucketed), keyb, word_tmp, rank_tmp,
+                       g->start, g->order, g->cell_of, g->sx, g->sy, g->sz, g->p4, g->occ_part);
+  });
   PQ_HIP(hipGetLastError());
   return 0;
 }
 
 // ---- DBSCAN's grid plan ---------------------------------------------------------------------------
 
-__device__ __forceinline__ double ord_val_dev(unsigned long long k) {
-  const unsigned long long b = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
-  return __longlong_as_double(static_cast<long long>(b));
-}
-
-// bin_octants_host's first trial in the same fp64 operations (floor((mx - mn) / cell) + 1 interior
-// slabs, + 2 border slabs, the same bucket rounding), so that every point lands in the same cell
+// bin_octants_host's first trial: interior_slabs and bucket_shape are the host's own, so that every
+// point lands in the same cell
 __device__ void write_plan(const unsigned long long* box, const PlanIn& in, GridPlan* __restrict__ plan) {
   GridPlan p;
   bool ok = in.hint.valid != 0;
   for (int a = 0; a < 3; ++a) {
-    p.mn[a] = ord_val_dev(box[a]);
-    p.mx[a] = ord_val_dev(box[3 + a]);
+    p.mn[a] = ord_val(box[a]);
+    p.mx[a] = ord_val(box[3 + a]);
     ok = ok && isfinite(p.mn[a]) && isfinite(p.mx[a]);
   }
   p.all_f32 = box[6] != 0 ? 1 : 0;
   ok = ok && p.all_f32;
-  double tot = 1.0;
+  double tot;
   int raw[3];
-  for (int a = 0; a < 3; ++a) {
-    const double d = floor((p.mx[a] - p.mn[a]) / in.cell) + 1.0;
-    if (!(d < 2.0e9)) ok = false;
-    raw[a] = ok ? int(d) : 0;
-    tot *= d + 2.0;
-  }
+  ok = interior_slabs(p.mn, p.mx, in.cell, 2.0, raw, &tot) && ok;
   ok = ok && tot <= double(in.max_cells);  // beyond: compressed axes or a doubled cell, which the host plans
   p.inv_cell = 1.0 / in.cell;
   p.rx = raw[0];
@@ -1769,8 +1516,9 @@ __device__ void write_plan(const unsigned long long* box, const PlanIn& in, Grid
   p.ny = raw[1] + 2;
   p.nz = raw[2] + 2;
   const int64_t ncell = ok ? int64_t(p.nx) * p.ny * p.nz : 0;
-  const int64_t nbk = (ncell + 4096) >> 12;
-  ok = ok && ncell + 1 <= (int64_t(kBkMax) << 12) && ncell <= in.hint.ncell && nbk <= in.hint.nbk &&
+  const BucketShape bs = bucket_shape(ncell);
+  const int64_t nbk = bs.nbk;
+  ok = ok && bs.bits == 12 && ncell <= in.hint.ncell && nbk <= in.hint.nbk &&
        (nbk <= kBkFusedScan) == (in.hint.fused != 0);
   p.ncell = ok ? int(ncell) : 0;
   p.nbk = ok ? int(nbk) : 0;
@@ -1809,17 +1557,6 @@ int octant_zeroed_ints() { return 2 * kBkMax + 5 + kZeroedExtra; }
 // The output arrays of the octant binning and the two-level sort's launches, for a directory of at
 // most ncell cells in nbk buckets (the plan's exact numbers, or the hint's bounds); the kernels
 // read the grid itself from d_plan.
-template <int BITS, bool F32>
-static void launch_bk_sort(Ctx* c, int64_t nbk, const int32_t* bstart, const void* bucketed,
-                           const int32_t* keyb, uint32_t* word_tmp, int32_t* rank_tmp, PointRec* keyed,
-                           const GridPlan* d_plan, DevGrid* g, SubCells* sub) {
-  unsigned long long* const st_sort = stamp_slots(c, nbk);  // the binning's last kernel
-  hipLaunchKernelGGL((k_bk_sort<BITS, F32>), dim3(unsigned(nbk)), dim3((1 << BITS) / 8), 0, c->stream, bstart,
-                     static_cast<const typename BkRec<F32>::type*>(bucketed), keyb, word_tmp, rank_tmp, g->dir_words,
-                     g->dir_slots, g->order,
-                     g->cell_of, sub->sub_of, g->sx, g->sy, g->sz, g->p4, sub->rec, keyed, d_plan, st_sort);
-}
-
 static int enqueue_bucketed(Ctx* c, const double* xyz, int64_t n, const GridParams& gp, const int raw[3],
                             AxisMap am, bool mapped, int64_t nbk, int bits, bool f32,
                             int32_t* zeroed, const GridPlan* d_plan, DevGrid* g, SubCells* sub) {
@@ -1830,7 +1567,6 @@ static int enqueue_bucketed(Ctx* c, const double* xyz, int64_t n, const GridPara
   void* bucketed;
   g->p4 = nullptr;
   g->sx = g->sy = g->sz = nullptr;
-  sub->sub_cnt = sub->sub_beg = nullptr;  // nothing reads them on this path: `rec` holds both
   // the ranked directory (grid.hpp, CellDir) instead of a dense start[ncell + 1]: a word per 32 cells of
   // every bucket, and a slot per occupied cell plus one per bucket
   g->start = nullptr;
@@ -1861,22 +1597,19 @@ static int enqueue_bucketed(Ctx* c, const double* xyz, int64_t n, const GridPara
   PQ_TRY(c->arena.get(size_t(nbk) + 1, &bstart));
   enqueue_bk_a(c, mapped ? 1 : 0, f32, xyz, n, gp, raw, am, nbk, bits, cell_tmp, tot, cursor, bstart, bucketed, keyb,
                d_plan);
-  if (bits == 12) {
-    if (f32)
-      launch_bk_sort<12, true>(c, nbk, bstart, bucketed, keyb, word_tmp, rank_tmp, keyed, d_plan, g, sub);
-    else
-      launch_bk_sort<12, false>(c, nbk, bstart, bucketed, keyb, word_tmp, rank_tmp, keyed, d_plan, g, sub);
-  } else {
-    if (f32)
-      launch_bk_sort<13, true>(c, nbk, bstart, bucketed, keyb, word_tmp, rank_tmp, keyed, d_plan, g, sub);
-    else
-      launch_bk_sort<13, false>(c, nbk, bstart, bucketed, keyb, word_tmp, rank_tmp, keyed, d_plan, g, sub);
-  }
+  on_sort_shape(bits, f32, [&](auto S) {
+    using K = decltype(S);
+    unsigned long long* const st_sort = stamp_slots(c, nbk);  // the binning's last kernel
+    hipLaunchKernelGGL((k_bk_sort<K::BITS, K::F32>), dim3(unsigned(nbk)), dim3((1 << K::BITS) / 8), 0, c->stream,
+                       bstart, static_cast<const typename K::Rec*>(bucketed), keyb, word_tmp, rank_tmp, g->dir_words,
+                       g->dir_slots, g->order, g->cell_of, sub->sub_of, g->sx, g->sy, g->sz, g->p4, sub->rec, keyed,
+                       d_plan, st_sort);
+  });
   PQ_HIP(hipGetLastError());
   return 0;
 }
 
-// The ranked directory from a dense one (the A/B binnings and grids beyond kBkMax buckets, which still
+// The ranked directory from a dense one (the atomic binning and grids beyond kBkMax buckets, which still
 // count into start[ncell + 1]): the per-bucket rule of k_bk_sort applied per word. Word w owns the slots
 // from start[32 w] + w: the begins of its occupied cells, then start[32 w + 32], the begin of whatever
 // comes next. A word has at most as many occupied cells as points, so the ranges do not overlap, and no
@@ -1965,35 +1698,15 @@ int bin_octants_host(Ctx* c, const double* xyz, int64_t n, double min_cell, int6
     if (f32_env && !strcmp(f32_env, "0")) all_f32 = false;
   }
   const char* bin_env = getenv("PYQSM_DBSCAN_BIN");
-  if (bin_env && !strcmp(bin_env, "2pass")) {  // the round-1 binning (A/B comparisons)
-    const double bbox[6] = {mn[0], mn[1], mn[2], mx[0], mx[1], mx[2]};
-    PQ_TRY(build_grid(c, xyz, n, min_cell, max_cells, g, bbox));
-    int32_t* zeroed4 = sub->zeroed4;
-    PQ_TRY(subsort_octants(c, g, n, sub));
-    sub->zeroed4 = zeroed4;
-    PQ_TRY(dir_from_dense(c, n, g));
-    hp.nx = g->nx;
-    hp.ny = g->ny;
-    hp.nz = g->nz;
-    hp.ncell = int(g->ncell);
-    hp.ok = 1;
-    return upload_plan(c, hp, h_up, d_plan);
-  }
   const dim3 grid(ceil_div(n, 256)), blk(256);
   double cell = min_cell;
   int raw[3], dims[3];
   AxisMap am{nullptr, nullptr, nullptr};
   bool mapped = false;
   for (;;) {
-    double tot = 1.0;
-    bool ok = true;
-    for (int a = 0; a < 3; ++a) {
-      const double d = std::floor((mx[a] - mn[a]) / cell) + 1.0;  // interior slabs
-      if (!(d < 2.0e9)) ok = false;
-      raw[a] = ok ? int(d) : 0;
-      dims[a] = raw[a] + 2;
-      tot *= d + 2.0;
-    }
+    double tot;
+    const bool ok = interior_slabs(mn, mx, cell, 2.0, raw, &tot);
+    for (int a = 0; a < 3; ++a) dims[a] = raw[a] + 2;
     if (ok && tot <= double(max_cells)) break;
     // too many cells of this edge: drop the empty slabs (per axis) before giving up on the edge
     const int64_t raw_sum = ok ? int64_t(raw[0]) + raw[1] + raw[2] : int64_t(1) << 40;
@@ -2041,8 +1754,8 @@ int bin_octants_host(Ctx* c, const double* xyz, int64_t n, double min_cell, int6
   // Two-level counting sort (k_bk_*): no scattered global atomics, the directory written once.
   // PYQSM_DBSCAN_BIN=atomic keeps round 2's one-atomic-per-point path (A/B comparisons); grids of
   // more than kBkMax buckets (2^27 cells) keep it too.
-  const int bits = g->ncell + 1 <= (int64_t(kBkMax) << 12) ? 12 : 13;
-  const int64_t nbk = (g->ncell + (int64_t(1) << bits)) >> bits;  // ceil((ncell + 1) / bucket)
+  const int bits = bucket_shape(g->ncell).bits;
+  const int64_t nbk = bucket_shape(g->ncell).nbk;
   const bool bucketed_path = nbk <= kBkMax && !(bin_env && !strcmp(bin_env, "atomic"));
   for (int a = 0; a < 3; ++a) {
     hp.mn[a] = mn[a];
@@ -2071,7 +1784,7 @@ int bin_octants_host(Ctx* c, const double* xyz, int64_t n, double min_cell, int6
       if (nbk <= kBkFusedScan) ncell_h = std::min<int64_t>(ncell_h, (int64_t(kBkFusedScan) << 12) - 1);
       hint_out->valid = 1;
       hint_out->ncell = int(ncell_h);
-      hint_out->nbk = int((ncell_h + 4096) >> 12);
+      hint_out->nbk = int(bucket_shape(ncell_h).nbk);  // (bits = 12 for every ncell_h below the bound above)
       hint_out->fused = nbk <= kBkFusedScan;
     }
     return 0;
@@ -2088,8 +1801,6 @@ int bin_octants_host(Ctx* c, const double* xyz, int64_t n, double min_cell, int6
   PQ_TRY(c->arena.get(size_t(n), &cell_tmp));
   PQ_TRY(c->arena.get(size_t(n), &rank_tmp));
   PQ_TRY(c->arena.get(size_t(n), &keyed));
-  PQ_TRY(c->arena.get(size_t(n) * 8, &sub->sub_cnt));
-  PQ_TRY(c->arena.get(size_t(n) * 8, &sub->sub_beg));
   PQ_TRY(c->arena.get(size_t(n), &sub->sub_of));
   PQ_TRY(c->arena.get(size_t(n) * 8, &sub->rec));
   PQ_TRY(c->arena.get(size_t(n) / kBigCell + 2, &big_list));
@@ -2104,14 +1815,13 @@ int bin_octants_host(Ctx* c, const double* xyz, int64_t n, double min_cell, int6
   PQ_TRY(exclusive_scan_i32(c, g->start, g->ncell + 1));
   hipLaunchKernelGGL(k_scatter_keys, grid, blk, 0, c->stream, xyz, n, g->start, cell_tmp, rank_tmp, keyed);
   hipLaunchKernelGGL(k_order_cells, grid, blk, 0, c->stream, int(n), g->start, keyed, g->order,
-                     g->cell_of, sub->sub_of, g->sx, g->sy, g->sz, sub->sub_cnt, sub->sub_beg, sub->rec,
-                     big_list, big_cnt);
+                     g->cell_of, sub->sub_of, g->sx, g->sy, g->sz, sub->rec, big_list, big_cnt);
   PQ_HIP(hipGetLastError());
   // cells with more than kBigCell points (none on a scan at eps ~ 10 x the point spacing): a fixed
   // grid reads their number on the device, so that no host round trip is needed
   hipLaunchKernelGGL(k_order_big, dim3(unsigned(std::min<int64_t>(n / kBigCell + 1, 2048))), blk, 0,
                      c->stream, big_list, big_cnt, g->start, keyed, g->order, g->cell_of, sub->sub_of,
-                     g->sx, g->sy, g->sz, g->p4, sub->sub_cnt, sub->sub_beg, sub->rec, d_plan);
+                     g->sx, g->sy, g->sz, g->p4, sub->rec, d_plan);
   PQ_HIP(hipGetLastError());
   return dir_from_dense(c, n, g);
 }
@@ -2193,19 +1903,17 @@ __global__ __launch_bounds__(256) void k_pyr_scatter(int n, Pyr P, const int32_t
                                                      double* __restrict__ sx,
                                                      double* __restrict__ sy,
                                                      double* __restrict__ sz, float4* __restrict__ p4) {
+  const SortedStore out{order, cell_of, nullptr, p4, sx, sy, sz};
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= n) return;
   const int f = f_cell_of[p];
   const int C = coarse_of(P, f);
   const int q = cstart[C] + foff[f] + (p - fstart[f]);
-  order[q] = f_order[p];
-  cell_of[q] = C;
   if (fp4) {
-    p4[q] = fp4[p];
+    const float4 v = fp4[p];  // (.w is 0 in every grid that is coarsened: build_grid's)
+    out.put(q, f_order[p], C, v.x, v.y, v.z);
   } else {
-    sx[q] = fx[p];
-    sy[q] = fy[p];
-    sz[q] = fz[p];
+    out.put(q, f_order[p], C, fx[p], fy[p], fz[p]);
   }
 }
 
@@ -2297,18 +2005,11 @@ __global__ __launch_bounds__(256) void k_canon_gather(int n, const double* __res
                                                       const int32_t* __restrict__ sorted, int32_t* __restrict__ order,
                                                       double* __restrict__ sx, double* __restrict__ sy,
                                                       double* __restrict__ sz, float4* __restrict__ p4) {
+  const SortedStore out{order, nullptr, nullptr, p4, sx, sy, sz};  // (start and cell_of stay as they are)
   const int q = blockIdx.x * 256 + threadIdx.x;
   if (q >= n) return;
   const int i = sorted[q];
-  const double x = xyz[3 * size_t(i)], y = xyz[3 * size_t(i) + 1], z = xyz[3 * size_t(i) + 2];
-  order[q] = i;
-  if (p4) {
-    p4[q] = make_float4(float(x), float(y), float(z), 0.0f);  // exact: fp32 records only for fp32-representable clouds
-  } else {
-    sx[q] = x;
-    sy[q] = y;
-    sz[q] = z;
-  }
+  out.put(q, i, 0, xyz[3 * size_t(i)], xyz[3 * size_t(i) + 1], xyz[3 * size_t(i) + 2]);
 }
 
 static int canonical_cell_order(Ctx* c, const double* d_src, int64_t n, DevGrid* g) {

@@ -299,32 +299,82 @@ inline void on_coords(const DevGrid& g, F&& fn) {
     fn(CoordsF64{g.sx, g.sy, g.sz});
 }
 
-// Octant sub-cells: the points of every cell re-sorted by the octant (half cell per axis)
-// they fall in. A sub-cell is identified by start[cell] * 8 + octant (first sorted
-// position of its cell, so ids are unique and need no compaction); its points are the run
-// [sub_beg[id], sub_beg[id] + sub_cnt[id]). sub_cnt is zero for empty octants of an
-// occupied cell; entries of unoccupied ids are never written and must not be read.
+// ---- where a binning kernel writes a sorted point ----------------------------------------------
+// The output arrays of a grid as the kernel that fills them sees them: position f of the sorted order
+// gets the point's original index, its cell, its sub-cell (octant binning only) and its coordinates,
+// in whichever form the grid keeps (p4, or sx / sy / sz). A kernel builds the store in its first line
+// from its own `__restrict__` parameters (see the note at CellDir); arrays it does not write are null
+// there, as a literal, so that their stores fold away. (The stores keep the order k_bk_sort had them in, cell_of
+// and sub_of first: with `order` first that kernel spilled under its cap of 80 VGPRs,
+// profiles/grid_sort_resource_usage.txt.)
+struct SortedStore {
+  int32_t* order;
+  int32_t* cell_of;  // null: the cells are written already
+  int32_t* sub_of;   // null: a grid without sub-cells
+  float4* p4;        // non-null: fp32 records instead of sx / sy / sz
+  double *sx, *sy, *sz;
+  __device__ __forceinline__ void put(int f, int idx, int cell, double x, double y, double z, int sub = 0) const {
+    if (cell_of) cell_of[f] = cell;
+    if (sub_of) sub_of[f] = sub;
+    order[f] = idx;
+    if (p4) {  // exact: fp32 records only for fp32-representable clouds
+      p4[f] = make_float4(float(x), float(y), float(z), 0.f);
+    } else {
+      sx[f] = x;
+      sy[f] = y;
+      sz[f] = z;
+    }
+  }
+  // from an fp32 record: the grid that is sorted from them keeps fp32 records too
+  __device__ __forceinline__ void put(int f, int idx, int cell, float x, float y, float z, int sub = 0) const {
+    if (cell_of) cell_of[f] = cell;
+    if (sub_of) sub_of[f] = sub;
+    order[f] = idx;
+    p4[f] = make_float4(x, y, z, 0.f);
+  }
+};
+
+// Octant sub-cells: the points of every cell ordered by the octant (half cell per axis) they fall
+// in. A sub-cell is identified by begin(cell) * 8 + octant (first sorted position of its cell, so
+// ids are unique and need no compaction); its points are the run [rec[id].x, rec[id].x + rec[id].y).
+// The count is zero for empty octants of an occupied cell; entries of unoccupied ids are never
+// written and must not be read.
 struct SubCells {
-  int32_t* sub_cnt;  // [8 n]; null from the two-level sort (k_bk_sort), which writes `rec` alone
-  int32_t* sub_beg;  // [8 n]; likewise
   int32_t* sub_of;   // [n] sub-cell id of each sorted position
-  int4* rec;         // [8 n] (sub_beg, sub_cnt, -1, 0) in one 16-byte record; .z and .w are the caller's
+  int4* rec;         // [8 n] (begin, count, -1, 0) in one 16-byte record; .z and .w are the caller's
                      // (DBSCAN: .z the sub-cell's representative, .w of a cell's first record the cell's tree)
-  // bin_octants_*: four ints the bounding box's fold left zeroed, for the caller's counters
-  // (spares DBSCAN two memset launches per step); nullptr from subsort_octants
+  // four ints the bounding box's fold left zeroed, for the caller's counters (spares DBSCAN two
+  // memset launches per step)
   // (+ kZeroedExtra more zeroed ints behind the four: DBSCAN's segmented list counters)
   int32_t* zeroed4 = nullptr;
 };
 static constexpr int kZeroedExtra = 64;
 
-// Re-sorts g's point arrays in place (order, sx, sy, sz are replaced by new arena arrays;
-// start and cell_of stay valid: the permutation is within cells).
-int subsort_octants(Ctx* c, DevGrid* g, int64_t n, SubCells* sub);
+// The eight sub-cell records of the cell whose run begins at sorted position b, from its octant counts.
+// (count_of(o): each count is fetched where its record is written, not all eight ahead of the stores)
+template <class CountOf>
+__device__ __forceinline__ void write_sub_records_of(int4* __restrict__ rec, int b, CountOf&& count_of) {
+  int run = b;
+#pragma unroll
+  for (int o = 0; o < 8; ++o) {
+    const int cnt = count_of(o);
+    rec[size_t(b) * 8 + o] = make_int4(run, cnt, -1, 0);
+    run += cnt;
+  }
+}
+__device__ __forceinline__ void write_sub_records(int4* __restrict__ rec, int b, const int (&cnt)[8]) {
+  write_sub_records_of(rec, b, [&](int o) { return cnt[o]; });
+}
+// the same from eight 8-bit counts packed in a u64
+__device__ __forceinline__ void write_sub_records(int4* __restrict__ rec, int b, unsigned long long packed) {
+  write_sub_records_of(rec, b, [&](int o) { return int((packed >> (8 * o)) & 255ull); });
+}
 
-// The grid AND its octant sub-cells in one go (what DBSCAN bins with): one returning atomic per
-// point (its arrival rank in the cell), one scatter of (index, cell, octant) and one pass that
-// orders every cell's run by octant from the run's own octant bytes (no second counting pass, no
-// per-octant counters), gathers the coordinates and writes every output array once.
+// The grid AND its octant sub-cells in one go (what DBSCAN bins with). The two-level sort (grid.hip:
+// k_bk_hist, k_bk_scatter, k_bk_sort) writes every output array once, with no scattered global atomic;
+// PYQSM_DBSCAN_BIN=atomic and grids beyond 2^27 cells take one returning atomic per point (its arrival
+// rank in the cell), one scatter of (index, cell, octant) and one pass that orders every cell's run by
+// octant from the run's own octant bytes.
 // Extents that would need more than `max_cells` cells of edge `min_cell` are first COMPRESSED
 // per axis: runs of empty slabs collapse to one empty slab, which keeps exactly the adjacencies
 // the 27-cell stencil and the sub-cell offsets use (two points in neighbouring slabs stay in

@@ -3,6 +3,7 @@
 // 2 reads + 1 write of the array, all as whole cache lines per wave.
 #include <utility>
 
+#include "block_scan.hpp"
 #include "common.hpp"
 
 namespace pyqsm {
@@ -10,35 +11,6 @@ namespace pyqsm {
 static constexpr int kScanThreads = 256;
 static constexpr int kScanItems = 8;
 static constexpr int kScanTile = kScanThreads * kScanItems;  // 2048 per block
-
-__device__ __forceinline__ int32_t wave_incl_scan(int32_t v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    int32_t t = __shfl_up(v, off, 64);
-    if (lane >= off) v += t;
-  }
-  return v;
-}
-
-// Exclusive scan of one value per thread across a 256-thread block; returns the
-// exclusive prefix and writes the block total to *total.
-__device__ __forceinline__ int32_t block_excl_scan(int32_t v, int32_t* total) {
-  __shared__ int32_t wsum[kScanThreads / 64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int32_t incl = wave_incl_scan(v);
-  if (lane == 63) wsum[w] = incl;
-  __syncthreads();
-  int32_t base = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < kScanThreads / 64; ++i) {
-    if (i < w) base += wsum[i];
-    tot += wsum[i];
-  }
-  *total = tot;
-  __syncthreads();
-  return base + incl - v;
-}
 
 __global__ __launch_bounds__(kScanThreads) void k_scan_reduce(const int32_t* __restrict__ in,
                                                               int64_t n,
@@ -50,8 +22,9 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_reduce(const int32_t* __r
     int64_t i = base + int64_t(k) * kScanThreads + threadIdx.x;
     if (i < n) s += in[i];
   }
+  __shared__ int32_t wsum[kScanThreads / 64];
   int32_t tot;
-  (void)block_excl_scan(s, &tot);
+  (void)block_excl_scan<kScanThreads>(s, wsum, &tot);
   if (threadIdx.x == 0) sums[blockIdx.x] = tot;
 }
 
@@ -77,9 +50,10 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_apply(int32_t* __restrict
     }
     s[j] = v[j].x + v[j].y + v[j].z + v[j].w;
   }
+  __shared__ int32_t wsum[kScanThreads / 64];
   int32_t tot0, tot1;
-  const int32_t r0 = block_excl_scan(s[0], &tot0);
-  const int32_t r1 = block_excl_scan(s[1], &tot1);
+  const int32_t r0 = block_excl_scan<kScanThreads>(s[0], wsum, &tot0);
+  const int32_t r1 = block_excl_scan<kScanThreads>(s[1], wsum, &tot1);
   const int32_t off = offs ? offs[blockIdx.x] : 0;
   const int32_t run[2] = {off + r0, off + tot0 + r1};
 #pragma unroll
@@ -111,8 +85,9 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_apply_unaligned(int32_t* 
     v[k] = (base + k < n) ? data[base + k] : 0;
     s += v[k];
   }
+  __shared__ int32_t wsum[kScanThreads / 64];
   int32_t tot;
-  int32_t run = block_excl_scan(s, &tot) + (offs ? offs[blockIdx.x] : 0);
+  int32_t run = block_excl_scan<kScanThreads>(s, wsum, &tot) + (offs ? offs[blockIdx.x] : 0);
 #pragma unroll
   for (int k = 0; k < kScanItems; ++k) {
     if (base + k < n) data[base + k] = run;

@@ -43,7 +43,8 @@ def tile(bits):
 
 
 def size_class(ncell):
-    """(class, bits, nbk) of a directory of ncell cells (bin_octants_host, bucketed_fits)."""
+    """(class, bits, nbk) of a directory of ncell cells (grid.hip: bucket_shape, as bin_octants_host,
+    bucketed_fits and the device's write_plan read it)."""
     ncell = int(ncell)
     bits = 12 if ncell + 1 <= (BK_MAX << 12) else 13
     nbk = (ncell + (1 << bits)) >> bits
@@ -302,6 +303,19 @@ def axis_mapped_cloud():
     return _f32(np.concatenate([blob, far]))
 
 
+# populations of one bucket on either side of the 4096 cells of a bucket and of tile(12), the points
+# k_bk_sort_plain<12, .> keeps in registers, up to ten rounds of the tile (below 1500 points
+# robust_box cuts the slab's box)
+ONE_BUCKET_SIZES = (1500, 4096, 4097, 6143, 6144, 6145, 8193, 60_000)
+ONE_BUCKET_RADIUS = 0.1
+
+
+def one_bucket_slab(m, seed=0):
+    """tests/test_gpu_dbscan_buckets.py::slab: 40 x 0.3 x 0.1, a single bucket of a grid of edge 0.1."""
+    rng = np.random.default_rng(seed)
+    return _f32(rng.uniform(0, 1, (m, 3)) * [40, 0.3, 0.1])
+
+
 # ---- what every cloud claims -----------------------------------------------------------------------
 
 def claim_class_cloud(P, cls):
@@ -344,6 +358,17 @@ def claim_dashed(P, cls):
     assert (pl.cls, pl.mapped, pl.doubled) == (cls, True, False), pl[:7]
     assert 3500 <= len(P) <= 6000
     return pl
+
+
+def claim_one_bucket_slab(P, m):
+    """The radius grid of the slab is of the fused class, over the whole bounding box, and all m
+    points share one bucket of it."""
+    rp = radius_plan(P, ONE_BUCKET_RADIUS)
+    assert (rp.cls, rp.bits, rp.doubled) == ("fused", 12, False), rp[:7]
+    pop, _ = populations(rp)
+    assert pop[pop > 0].tolist() == [m] == [len(P)], "exactly one bucket holds points: all of them"
+    assert not robust_box_cuts(P), "the radius grid is built over the bounding box"
+    return rp
 
 
 def claim_queries(Q, P, rp):

@@ -6,8 +6,8 @@ device evaluates, ``hip.octant_directory``, against ``np.searchsorted`` over the
 tests/grid_restatement.py::dbscan_plan computes, entry by entry, and ``hip.dbscan`` against
 ``oracle.dbscan``. Integers throughout: ``array_equal``, no tolerance. The modes: planned on the host,
 planned on the device (a hit where the grid is of the plannable kind), fp64 records
-(PYQSM_COORD_F32=0), and the two binnings that still count into a dense array and convert it
-(PYQSM_DBSCAN_BIN=atomic, =2pass). The clouds and what each one claims (word and bucket edges, the
+(PYQSM_COORD_F32=0), and the binning that still counts into a dense array and converts it
+(PYQSM_DBSCAN_BIN=atomic). The clouds and what each one claims (word and bucket edges, the
 directory's end, every path of the producer, buckets of 8192 cells, compressed axes, doubled cells,
 tiny clouds) are tests/directory_restatement.py's; the claims are recomputed here."""
 import functools
@@ -26,7 +26,7 @@ pytestmark = pytest.mark.gpu
 ENV = ("PYQSM_DBSCAN_PLAN", "PYQSM_COORD_F32", "PYQSM_DBSCAN_BIN")
 # name -> (PYQSM_DBSCAN_PLAN, PYQSM_COORD_F32, PYQSM_DBSCAN_BIN)
 MODES = {"host": ("host", None, None), "device": (None, None, None), "fp64": (None, "0", None),
-         "atomic": (None, None, "atomic"), "2pass": (None, None, "2pass")}
+         "atomic": (None, None, "atomic")}
 
 
 def _call(fn, gpu, mode):
@@ -75,9 +75,7 @@ def test_directory_and_labels_in_every_mode(gpu, name):
     for mode in MODES:
         # (the device mode follows the host mode on the same cloud: the hint is this cloud's)
         want = "hit" if mode == "device" and plannable else "miss"
-        # (the 2pass binning plans with build_grid, which doubles the edge where dbscan_plan compresses the
-        # axes: another grid, and one beyond what is read out here)
-        if read and not (mode == "2pass" and pl.mapped):
+        if read:
             (dims, begin), path = _call(lambda: hip.octant_directory(P, eps, device=gpu), gpu, mode)
             assert path == want, (mode, "directory")
             assert tuple(dims.tolist()) == pl.dims, mode

@@ -26,6 +26,7 @@ from tests import features_restatement as RF
 from tests import grid_restatement as G
 from tests import normals_restatement as RN
 from tests.test_gpu_adjacency import assert_same as assert_same_adjacency
+from tests.test_gpu_dbscan_buckets import slab as one_bucket_slab_of_dbscan
 from tests.test_gpu_features import _check as check_features
 from tests.test_gpu_normals import _same as same_bits
 
@@ -170,11 +171,11 @@ def test_dbscan_compressed_axes_with_a_large_directory(gpu, cls):
 
 # ---- DBSCAN: the binning switches, at small size -------------------------------------------------------
 
-@pytest.mark.parametrize("bin", ["atomic", "2pass"])
+@pytest.mark.parametrize("bin", ["atomic"])
 @pytest.mark.parametrize("kind,key", [("forest", 30_000), ("bigcell", None), ("mapped", None)])
 def test_dbscan_binning_switches(gpu, kind, key, bin):
-    """PYQSM_DBSCAN_BIN=atomic (one atomic per point) and =2pass (build_grid + subsort_octants) on a
-    forest, on cells of more than 255 points and on a compressed grid."""
+    """PYQSM_DBSCAN_BIN=atomic (one atomic per point) on a forest, on cells of more than 255 points
+    and on a compressed grid."""
     cloud = _cloud(kind, key)
     _expect(cloud, gpu, [(bin, dict(bin=bin), "miss"), (bin + ", fp64 records", dict(bin=bin, f64=True), "miss")])
 
@@ -298,3 +299,26 @@ def test_radius_mark_on_the_atomic_grid(gpu, monkeypatch):
     assert np.array_equal(counts, want_counts)
     assert np.array_equal(np.flatnonzero(mask), want_idx)
     assert counts.max() == 40
+
+
+# ---- build_grid's second level across the register tile's capacity -------------------------------------
+
+@pytest.mark.parametrize("f64", [False, True], ids=["fp32", "fp64"])
+@pytest.mark.parametrize("m", G.ONE_BUCKET_SIZES)
+def test_radius_queries_on_one_bucket_of_m_points(gpu, m, f64):
+    """tests/test_gpu_dbscan_buckets.py::test_one_bucket_of_m_points for k_bk_sort_plain, which shares
+    the two sweeps with DBSCAN's k_bk_sort: the same slab, all of it in one bucket of build_grid's
+    directory, on either side of the 6144 points a block keeps in registers."""
+    P = G.one_bucket_slab(m)
+    assert np.array_equal(P, one_bucket_slab_of_dbscan(m))
+    G.claim_one_bucket_slab(P, m)
+    tree, r = cKDTree(P), G.ONE_BUCKET_RADIUS
+    qry = P[::7]
+    with _env(COORD_F32="0" if f64 else None):
+        mask, counts = hip.radius_mark(P, qry, r, k=40, device=gpu)
+        want_idx, want_counts = _kdtree_union(tree, m, qry, r, 40)
+        assert np.array_equal(counts, want_counts)
+        assert np.array_equal(np.flatnonzero(mask), want_idx)
+        for center in (0.5 * (P.min(0) + P.max(0)), P.max(0) - 0.004):
+            got = hip.ball_query(P, center, r, device=gpu)
+            assert np.array_equal(got, np.sort(tree.query_ball_point(center, r)))

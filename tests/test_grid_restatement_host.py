@@ -87,6 +87,15 @@ def test_small_clouds_of_the_switch_tests():
     assert (pl.cls, pl.mapped, pl.doubled) == ("fused", True, False)
 
 
+@pytest.mark.parametrize("m", G.ONE_BUCKET_SIZES)
+def test_one_bucket_slabs_of_the_radius_grid(m):
+    """tests/test_gpu_grid_classes.py::test_radius_queries_on_one_bucket_of_m_points: the sizes lie on
+    either side of a bucket's 4096 cells and of the register tile of k_bk_sort_plain<12, .>."""
+    rp = G.claim_one_bucket_slab(G.one_bucket_slab(m), m)
+    assert rp.dims == (402, 5, 3)
+    assert {G.tile(12) - 1, G.tile(12), G.tile(12) + 1} <= set(G.ONE_BUCKET_SIZES)
+
+
 def test_robust_box_restatement_sees_a_cut():
     rng = np.random.default_rng(1)
     P = np.concatenate([rng.uniform(0, 1, (20_000, 3)), [[40.0, 0.5, 0.5]]])
