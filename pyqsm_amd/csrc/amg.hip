@@ -427,13 +427,7 @@ __global__ __launch_bounds__(256) void k_ap_fill(int n, const int32_t* __restric
 // The cycle's fp32 vectors hold one float4 (x, y, z, 0) per row: a neighbour's entry is ONE
 // 16-byte gather instead of three 4-byte ones. These kernels are bound by the number of
 // cache lines their gathers touch (the L1 takes a divergent access a line at a time), and
-// three gathers at the same columns touch the same lines three times.
-__device__ __forceinline__ float4 ld4(const float* v, int i) {
-  return reinterpret_cast<const float4*>(v)[i];
-}
-__device__ __forceinline__ void st4(float* v, int i, float a, float b, float c) {
-  reinterpret_cast<float4*>(v)[i] = make_float4(a, b, c, 0.f);
-}
+// three gathers at the same columns touch the same lines three times (ld4 / st4, sparse.hpp).
 
 // rows of a caller-side vector: float4 for fp32, three doubles for fp64
 __device__ __forceinline__ void ld_row(const float* v, int i, float& a, float& b, float& c) {

@@ -102,6 +102,12 @@ int amg_levels(const AmgHierarchy* h);
 int amg_vcycle(Ctx* c, AmgHierarchy* h, const double* b, double* x, double* dot = nullptr);
 // Floats per row of an fp32 solver vector: (x, y, z, 0), so that a row is one 16-byte access.
 static constexpr int kVecStride = 4;
+__device__ __forceinline__ float4 ld4(const float* v, int i) {
+  return reinterpret_cast<const float4*>(v)[i];
+}
+__device__ __forceinline__ void st4(float* v, int i, float a, float b, float c) {
+  reinterpret_cast<float4*>(v)[i] = make_float4(a, b, c, 0.f);
+}
 
 // The same with fp32 vectors of kVecStride floats per row (no conversion pass), and the fp32
 // copy of B the cycle uses on its finest level (for a CG that runs in fp32 altogether).

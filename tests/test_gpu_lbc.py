@@ -1,5 +1,6 @@
 """HIP contraction solve vs SciPy spsolve fixtures (skeletonize.py:148-180);
 tolerance 1e-5 relative on vertex positions (BASELINE.json north_star)."""
+import functools
 import glob
 import os
 
@@ -74,20 +75,52 @@ def _small_system(n=1500, seed=3):
     return P, L.tocsr(), np.asarray(M)
 
 
-@pytest.mark.parametrize("path_env", [{}, {"PYQSM_AMG": "0"}, {"PYQSM_LBC_SORT": "0"}, {"PYQSM_NO_GRAPH": "1"}])
-def test_solver_variants_agree_with_spsolve(gpu, monkeypatch, path_env):
-    """Multigrid (default), Jacobi-PCG B-solves, unsorted unknowns, plain launches: every variant
-    must reproduce the SciPy direct solve of the same system to the parity bound."""
-    for k, v in path_env.items():
-        monkeypatch.setenv(k, v)
+@functools.lru_cache(maxsize=None)
+def _rough_system():
+    """6000 points (above the 4096 rows of the sorted path, a multigrid hierarchy of at least two
+    levels) with rough positional weights, and the SciPy direct solve of it; shared, not modified."""
     P, L, M = _small_system(6000)
     wl = np.full(len(P), 3e3 * np.sqrt(M.mean()))
     rng = np.random.default_rng(0)
     wh = 3.0 * np.sqrt(M.mean() / M) ** rng.uniform(0.5, 1.5, len(P))     # rough positional weights
-    x, iters, resid, ok = hip.lbc_solve(L, wl, wh, P, rtol=1e-9, max_it=500000, device=gpu)
-    ref = oracle.least_squares_sparse(P, L, wl, wh)
+    return P, L, wl, wh, oracle.least_squares_sparse(P, L, wl, wh)
+
+
+def _solve_rough(gpu, monkeypatch, env):
+    P, L, wl, wh, _ = _rough_system()
+    with monkeypatch.context() as m:
+        for k, v in env.items():
+            m.setenv(k, v)
+        return hip.lbc_solve(L, wl, wh, P, rtol=1e-9, max_it=500000, device=gpu)
+
+
+@pytest.mark.parametrize("path_env", [{}, {"PYQSM_AMG": "0"}, {"PYQSM_LBC_SORT": "0"}, {"PYQSM_NO_GRAPH": "1"},
+                                      {"PYQSM_LBC_F32": "0"}, {"PYQSM_AMG_GRAPH": "1"},
+                                      {"PYQSM_AMG_GRAPH": "1", "PYQSM_LBC_F32": "0"}])
+def test_solver_variants_agree_with_spsolve(gpu, monkeypatch, path_env):
+    """Multigrid (default), Jacobi-PCG B-solves, unsorted unknowns, plain launches, the fp64 multigrid
+    rung, multigrid bursts as graphs (fp32 and fp64): every variant must reproduce the SciPy direct
+    solve of the same system to the parity bound."""
+    x, iters, resid, ok = _solve_rough(gpu, monkeypatch, path_env)
+    ref = _rough_system()[4]
     assert ok, (iters, resid)
     assert np.abs(x - ref).max() <= RTOL * np.abs(ref).max()
+
+
+@pytest.mark.parametrize("base,switch", [({}, {"PYQSM_AMG_GRAPH": "1"}),
+                                         ({"PYQSM_LBC_F32": "0"}, {"PYQSM_AMG_GRAPH": "1"}),
+                                         ({"PYQSM_AMG": "0"}, {"PYQSM_NO_GRAPH": "1"})])
+def test_graphs_replay_the_same_launches(gpu, monkeypatch, base, switch):
+    """A burst of CG iterations replayed as a hipGraph is the same kernels on the same arguments as the
+    burst launched plainly, and every reduction goes through fixed partial slots (sparse.hpp): flipping
+    the graph switch of the fp32 multigrid loop, the fp64 multigrid loop and the Jacobi-PCG B-solves
+    changes no bit of the solution, the iteration count, the residuals or the verdict."""
+    x0, it0, rs0, ok0 = _solve_rough(gpu, monkeypatch, base)
+    x1, it1, rs1, ok1 = _solve_rough(gpu, monkeypatch, {**base, **switch})
+    print(f"{base} -> {switch}: iterations {it0} / {it1}, ok {ok0} / {ok1}, "
+          f"max |dx| {np.abs(x0 - x1).max():.3e}, resid {rs0} / {rs1}")
+    assert np.array_equal(x0, x1)
+    assert it0 == it1 and np.array_equal(rs0, rs1) and ok0 == ok1
 
 
 def test_non_uniform_laplacian_weights_take_the_general_path(gpu):
