@@ -1026,6 +1026,39 @@ int pyqsm_chain_radii(const double* shift, int64_t n, const int64_t* chain_ptr, 
 int pyqsm_cylinder_surfaces(const double* params, int64_t q, const double* cos_sin, int64_t* surface_ptr,
                             double** points_out, int64_t* total_out, int32_t device);
 
+/* ---- stem width: order statistics of the pairwise distances ------------------- */
+/*
+ * For every segment (an independent cloud) the elements of given ranks of its sorted pairwise
+ * distances, scipy.spatial.distance.pdist bit for bit, without the distances ever being stored: what
+ * pyQSM's canopy_metrics.width_at_height reads off np.percentile(pdist(slab[:, :2]), q)
+ * (DESIGN.md section 21).
+ *   pts f64 [n, dim], dim 2 or 3 (anything else: PYQSM_EINVAL), finite and of magnitude below 1e150
+ *   (a precondition, not checked); seg_start i64 [n_seg + 1], ascending from 0 to n (PYQSM_EINVAL
+ *   otherwise). Segment s with n_s points has M_s = n_s (n_s - 1) / 2 pairs i < j, written to n_pairs
+ *   i64 [n_seg]. The key of a pair is d2 = (dx*dx) + (dy*dy), for dim 3 with + (dz*dz) added last, in
+ *   fp64 without contraction; keys are ordered by their bit pattern.
+ *   ranks i64 [n_seg, n_ranks], 0-based; values f64 [n_seg, n_ranks]: values[s, r] = sqrt of the key
+ *   of rank ranks[s, r] among segment s's keys in ascending order. A rank < 0 marks an unused slot,
+ *   which receives 0.0; a rank >= M_s: PYQSM_EINVAL (so a segment with M_s = 0 takes unused slots
+ *   only). Equal ranks in one segment are fine. n_ranks from 0 to PYQSM_PDIST_MAX_RANKS, above it
+ *   PYQSM_EINVAL.
+ *   max_pair i64 [n_seg, 2] or NULL: the pair (i, j), i < j, of indices local to the segment with the
+ *   largest key, of equal keys the smallest (i, j) in lexicographic order; (-1, -1) when M_s = 0.
+ * max_pairs: the call is refused with PYQSM_ERANGE, before any launch, when the sum of M_s exceeds
+ *   it; <= 0: PYQSM_PDIST_DEFAULT_MAX_PAIRS, ten seconds of the eight passes at the 9.3e11 pair
+ *   evaluations per second measured on one MI355X (profiles/width_perf.jsonl, case "single", n = 100000).
+ * stats i64 [3] or NULL: the sum of M_s, the pair evaluations executed (every pass evaluates every pair
+ *   once), the passes run.
+ * Memory is O(n + n_seg * n_ranks * 256); nothing is read back between the passes; all counters are
+ * integers summed by integer atomics, so every run gives the same bits. When every M_s is 0 no device
+ * is touched.
+ */
+#define PYQSM_PDIST_MAX_RANKS 32
+#define PYQSM_PDIST_DEFAULT_MAX_PAIRS 1200000000000LL
+int pyqsm_pdist_select(const double* pts, int64_t n, int32_t dim, const int64_t* seg_start, int64_t n_seg,
+                       const int64_t* ranks, int32_t n_ranks, int64_t max_pairs, double* values, int64_t* n_pairs,
+                       int64_t* max_pair, int64_t* stats, int32_t device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -760,6 +760,51 @@ def alpha_area(ij, a2: int, seg_start=None, return_boundary: bool = False, max_t
     return AlphaArea(twice, live, nb, edges, start, stats)
 
 
+# ---------------------------------------------------------------- pairwise-distance order statistics
+
+PDIST_MAX_RANKS = 32                          # PYQSM_PDIST_MAX_RANKS
+PDIST_DEFAULT_MAX_PAIRS = 1_200_000_000_000   # PYQSM_PDIST_DEFAULT_MAX_PAIRS: ten seconds at 9.3e11 evaluations/s
+
+
+class PdistSelect(NamedTuple):
+    """Per-segment results of :func:`pdist_select`."""
+    values: np.ndarray      # float64 [n_seg, n_ranks] the distances of the given ranks (0.0 in unused slots)
+    n_pairs: np.ndarray     # int64 [n_seg] M_s = n_s (n_s - 1) / 2
+    max_pair: np.ndarray    # int64 [n_seg, 2] the farthest pair (i < j, local to the segment), (-1, -1) without pairs
+    stats: dict
+
+
+def pdist_select(points, seg_start, ranks, max_pairs: int = 0, device: int = 0) -> PdistSelect:
+    """``pyqsm_pdist_select``: elements of the sorted ``scipy.spatial.distance.pdist`` of every
+    segment, bit for bit, without the distances being stored. ``points`` float64 [n, 2] or [n, 3];
+    ``seg_start`` [n_seg + 1] splits them into independent clouds (None: one); ``ranks`` int64
+    [n_seg, n_ranks] (or [n_ranks] for one segment), 0-based, a negative rank marks an unused slot.
+    At most 32 ranks per segment. ``max_pairs`` (0: about ten seconds of one MI355X) refuses a call
+    with more point pairs before anything is launched."""
+    pts = np.ascontiguousarray(np.asarray(points), dtype=np.float64)
+    if pts.ndim != 2:
+        raise ValueError(f"expected points of shape [n,dim], got {pts.shape}")
+    n, dim = pts.shape
+    seg = np.array([0, n], np.int64) if seg_start is None else np.ascontiguousarray(seg_start, dtype=np.int64)
+    if seg.ndim != 1 or seg.shape[0] < 1:
+        raise ValueError("seg_start must hold n_seg + 1 offsets")
+    n_seg = seg.shape[0] - 1
+    rk = np.ascontiguousarray(ranks, dtype=np.int64)
+    if rk.ndim == 1 and n_seg == 1:
+        rk = rk.reshape(1, -1)
+    if rk.ndim != 2 or rk.shape[0] != n_seg:
+        raise ValueError(f"expected ranks of shape [{n_seg}, n_ranks], got {rk.shape}")
+    n_ranks = rk.shape[1]
+    values = np.zeros((n_seg, n_ranks), np.float64)
+    n_pairs = np.zeros(max(n_seg, 1), np.int64)
+    far = np.full((max(n_seg, 1), 2), -1, np.int64)
+    st = np.zeros(3, np.int64)
+    check(_lib.load().pyqsm_pdist_select(_p(pts), n, dim, _p(seg), n_seg, _p(rk), n_ranks, int(max_pairs),
+                                         _p(values), _p(n_pairs), _p(far), _p(st), int(device)))
+    stats = dict(zip(("pairs", "pair_evaluations", "passes"), (int(v) for v in st)))
+    return PdistSelect(values, n_pairs[:n_seg], far[:n_seg], stats)
+
+
 # ---------------------------------------------------------------- mesh checks
 
 MESH_PAIRS = 1
