@@ -16,7 +16,8 @@
 // kMaxRing shells (isolated outliers) are retried, one wave per query, on a 4x coarser
 // grid (binned from the points when the fine grid is large, else derived from it:
 // grid.hip: coarsen_grid) with up to kWideRing shells, and on coarser ones still until the
-// shells cover the whole grid.
+// shells cover the whole grid. (If more than half of ALL queries are open after level 0 — coincident
+// points met the planned occupancy — level 0 runs once more on the coarser grid first: knn_device.)
 //
 // (Measured alternative for level 0, MI355X, 1 M points, k = 20: a wave-tiled search like
 // dbscan.hip's k_core_tiled — 64 consecutive queries, candidates broadcast from LDS, the K
@@ -852,11 +853,27 @@ int knn_device(Ctx* c, const double* xyz, int64_t n, int32_t k, int32_t exclude_
   PQ_HIP(hipMemsetAsync(tie_count, 0, 4, c->stream));
   int n_query = N;
   const int32_t* list = nullptr;
+  bool retry_binned = false;  // how this level's grid was made (trace only)
+  bool level0_again = false;  // level 0 has been run a second time (see below)
   for (int level = 0;; ++level) {
     static const int wide = [] { const char* e = getenv("PYQSM_KNN_WIDE"); return e ? atoi(e) : kWideRing; }();
     const int ring = level >= 1 && k <= 64 ? wide : kMaxRing;
     const int last = (g.nx - 2 <= ring && g.ny - 2 <= ring && g.nz - 2 <= ring) ? 1 : 0;
     PQ_HIP(hipMemsetAsync(fail_count, 0, 4, c->stream));
+    if (getenv("PYQSM_KNN_TRACE")) {  // printed for the last level too (the lines below are not)
+      const bool reg = level == 0 && k <= 32, wave = level > 0 && k <= 64;
+      char kern[32];
+      if (reg)
+        snprintf(kern, sizeof kern, "k_knn_reg<%d,%d,%s>", (k + 3) / 4 * 4, knn_buffer_slots() == 0 ? 0 : 4,
+                 knn_buffer_slots() != 0 && knn_strict() ? "true" : "false");
+      else if (wave)
+        snprintf(kern, sizeof kern, "k_knn_wave");
+      else
+        snprintf(kern, sizeof kern, "k_knn<%d>", k <= 48 ? 256 : k <= 96 ? 128 : 64);
+      fprintf(stderr, "knn level %d: grid %d x %d x %d of cell %.4g%s, %s, %s, %d queries%s\n", level, g.nx, g.ny,
+              g.nz, g.cell, level == 0 && !level0_again ? "" : retry_binned ? " binned again" : " coarsened",
+              g.p4 ? "fp32 records" : "fp64 arrays", kern, n_query, last ? ", last level" : "");
+    }
     {
       ProfScope ps(c, level == 0 ? "knn_search" : "knn_retry");
       int32_t* fl = (level & 1) ? fail_b : fail_a;
@@ -925,19 +942,36 @@ int knn_device(Ctx* c, const double* xyz, int64_t n, int32_t k, int32_t exclude_
     }
     // retry the stragglers on a 4x coarser grid
     ProfScope ps(c, "knn_bin");
-    list = (level & 1) ? fail_b : fail_a;
-    n_query = nf;
+    // More than half of ALL queries open after the register kernel's three rings: the occupancy the
+    // cell edge was planned for came from coincident points (a contracted cloud, a lattice with several
+    // points per node: 5.5 per node meet k / 3 at any edge below the lattice step), so the edge says
+    // nothing about the spacing, level 0 answered (nearly) nobody, and a WAVE per query would now serve
+    // the whole cloud. Level 0 once more instead, a lane per query with its tie passes, on the
+    // coarser grid; what is still open after that is retried as usual.
+    const bool again = level == 0 && k <= 32 && !level0_again && nf > N / 2;
+    if (!again) {
+      list = (level & 1) ? fail_b : fail_a;
+      n_query = nf;
+    }
     {
       // Deriving the coarse grid from the fine one reads the fine grid's whole cell array (95 M
       // cells for a million points at k = 20: 0.22 ms); binning the points again at the coarse edge
       // touches 1.5 M cells (0.12 ms). The order inside a cell does not matter to a search. Small
       // fine grids (the later levels) keep the pyramid: no atomics, a few microseconds.
       DevGrid coarse;
-      if (g.ncell > (int64_t(1) << 22))
+      retry_binned = g.ncell > (int64_t(1) << 22);
+      if (retry_binned)
         PQ_TRY(build_grid(c, xyz, n, g.cell * 4.0, max_cells, &coarse, box, all_f32));
       else
         PQ_TRY(coarsen_grid(c, g, n, 4, &coarse));
       g = coarse;
+    }
+    if (again) {
+      if (getenv("PYQSM_KNN_TRACE")) fprintf(stderr, "knn: level 0 once more for every query, on the coarser grid\n");
+      level0_again = true;
+      PQ_HIP(hipMemsetAsync(tie_count, 0, 4, c->stream));
+      --level;
+      continue;
     }
     if (!pos_of) PQ_TRY(c->arena.get(size_t(n), &pos_of));
     hipLaunchKernelGGL(k_invert_order, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, N, g.order,
