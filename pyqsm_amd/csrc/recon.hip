@@ -21,7 +21,7 @@
 //   E <= L^6 = 2^72, 4 rho^2 n2 <= L^6: H < 2^73, |N| <= |u|^2 n2 + |w| |u| <= 3 L^6 < 2^74: __int128;
 //   N^2 < 2^148 against D^2 H <= 2^72 * 2^72 = 2^144: four 64-bit limbs (recon_exact.hpp).
 // int64 w is what sets the bound: L = 2^13 would need 2^66 there.
-// The filter. Each test first runs in fp64: D exactly; Nf = fl(u2 n2 - w.u) from four products with
+// The filter (recon_filter in recon_exact.hpp, so that the host can run it). Each test first runs in fp64: D exactly; Nf = fl(u2 n2 - w.u) from four products with
 // M = |u2 n2| + sum |w_i u_i| (w_i rounded once to fp64, each product once, three additions:
 // |Nf - N| <= 2^-50 M); sH = fl(sqrt(fl(H))) and rhs = fl(sH D) with |rhs - sqrt(H) D| <= 2^-49 |rhs|
 // (H is put together from two halves, two roundings, halved by the root; a root within two units of
@@ -301,7 +301,8 @@ __global__ __launch_bounds__(256) void k_recon_tris(
     const int take = have < 256 ? have : 256;
     const bool mine = t < take;
     int pa = 0, pb = 0, pc = 0;
-    double ax = 0, ay = 0, az = 0, n0 = 0, n1 = 0, n2c = 0, w0 = 0, w1 = 0, w2 = 0, n2 = 0, sH = 0;
+    double ax = 0, ay = 0, az = 0;
+    ReconFilterTri ft = {{0, 0, 0}, {0, 0, 0}, 0, 0};
     if (mine) {
       pa = qa[t];
       pb = qb[t];
@@ -312,14 +313,7 @@ __global__ __launch_bounds__(256) void k_recon_tris(
       ax = double(a[0]);
       ay = double(a[1]);
       az = double(a[2]);
-      n0 = double(tri.n[0]);
-      n1 = double(tri.n[1]);
-      n2c = double(tri.n[2]);
-      w0 = double(tri.w[0]);
-      w1 = double(tri.w[1]);
-      w2 = double(tri.w[2]);
-      n2 = double(tri.n2);
-      sH = sqrt(double(uint64_t(tri.H >> 64)) * 0x1p64 + double(uint64_t(tri.H)));
+      ft = recon_filter_setup(tri);
     }
     bool blocked = !mine, unresolved = false, tie_drop = false;
     for (int k0 = 0; k0 < S; k0 += kReconChunk) {
@@ -339,14 +333,9 @@ __global__ __launch_bounds__(256) void k_recon_tris(
         const double ux = sx[j] - ax, uy = sy[j] - ay, uz = sz[j] - az;
         const double u2 = (ux * ux + uy * uy) + uz * uz;
         if (u2 > four_r2d) continue;  // beyond 2 rho of a: outside every ball through a
-        const double D = (n0 * ux + n1 * uy) + n2c * uz;
-        const double t0 = u2 * n2, t1 = w0 * ux, t2 = w1 * uy, t3 = w2 * uz;
-        const double Nf = ((t0 - t1) - t2) - t3;
-        const double rhs = sH * D;
-        const double diff = Nf - rhs;
-        const double tol = ((((fabs(t0) + fabs(t1)) + fabs(t2)) + fabs(t3)) + fabs(rhs)) * 0x1p-46;
-        if (diff > tol) continue;
-        if (diff < -tol) {
+        const int side = recon_filter(ft, ux, uy, uz);  // recon_exact.hpp: the host checks the same function
+        if (side == kReconFilterOutside) continue;
+        if (side == kReconFilterInside) {
           blocked = true;
           break;
         }

@@ -1,18 +1,22 @@
 // recon_exact.hpp — the integer side of the ball-pivoting predicate (recon.hip): the
 // exact quantities of one oriented candidate triangle and the exact position of a point against its
-// rho-ball. Host- and device-callable and free of any runtime call, so that a stand-alone host program
-// (recon_check.cpp) can run it under the sanitizers.
+// rho-ball, and the fp64 filter the kernel runs in front of it (recon_filter_setup / recon_filter).
+// Host- and device-callable and free of any runtime call, so that a stand-alone host program
+// (recon_check.cpp) can run it under the sanitizers and hold the filter against the integers.
 //
 // Bounds (L = 2 rho <= 2^12, every |e|, |u| <= L): |n_i| <= L^2 = 2^24, n2 <= L^4 = 2^48,
 // |w_i| <= 2 L^5 = 2^61 (int64), E, H <= L^6 = 2^72 and |N| <= 3 L^6 < 2^74 (128 bits),
 // N^2 < 2^148 and D^2 H <= 2^144 (256 bits).
 #pragma once
+#include <cmath>
 #include <cstdint>
 
 #if defined(__HIPCC__)
 #define PQ_HD __host__ __device__
+#define PQ_FORCEINLINE inline __attribute__((always_inline))  // what __forceinline__ stands for
 #else
 #define PQ_HD
+#define PQ_FORCEINLINE inline
 #endif
 
 namespace pyqsm {
@@ -102,6 +106,45 @@ PQ_HD inline int recon_classify(const ReconTri& t, const int64_t u[3]) {
   if (cmp == 0) return kReconTieOffPlane;
   if (D > 0) return cmp < 0 ? kReconInside : kReconOutside;
   return cmp > 0 ? kReconInside : kReconOutside;
+}
+
+// ---- the fp64 filter in front of recon_classify (recon.hip, "The filter") ----------
+// What one candidate keeps in fp64: n, n2 and every |D| are exact, each w_i is rounded once, H is put
+// together from its two 64-bit halves before the root.
+struct ReconFilterTri {
+  double n[3], w[3];
+  double n2, sH;
+};
+
+PQ_HD inline ReconFilterTri recon_filter_setup(const ReconTri& t) {
+  ReconFilterTri f;
+  f.n[0] = double(t.n[0]);
+  f.n[1] = double(t.n[1]);
+  f.n[2] = double(t.n[2]);
+  f.w[0] = double(t.w[0]);
+  f.w[1] = double(t.w[1]);
+  f.w[2] = double(t.w[2]);
+  f.n2 = double(t.n2);
+  f.sH = sqrt(double(uint64_t(t.H >> 64)) * 0x1p64 + double(uint64_t(t.H)));
+  return f;
+}
+
+enum { kReconFilterOutside = 0, kReconFilterInside = 1, kReconFilterUndecided = 2 };
+
+// The sign of N - sqrt(H) D for u = p - a where fp64 is sure of it: |diff| > 2^-46 (M + |rhs|), eight
+// times the rounding of its terms. Everything else, every exact tie among it, is recon_classify's.
+// |u|^2 <= 4 rho^2 is the caller's. No fused multiply-add may be formed here (-ffp-contract=off).
+PQ_HD PQ_FORCEINLINE int recon_filter(const ReconFilterTri& f, double ux, double uy, double uz) {
+  const double u2 = (ux * ux + uy * uy) + uz * uz;
+  const double D = (f.n[0] * ux + f.n[1] * uy) + f.n[2] * uz;
+  const double t0 = u2 * f.n2, t1 = f.w[0] * ux, t2 = f.w[1] * uy, t3 = f.w[2] * uz;
+  const double Nf = ((t0 - t1) - t2) - t3;
+  const double rhs = f.sH * D;
+  const double diff = Nf - rhs;
+  const double tol = ((((fabs(t0) + fabs(t1)) + fabs(t2)) + fabs(t3)) + fabs(rhs)) * 0x1p-46;
+  if (diff > tol) return kReconFilterOutside;
+  if (diff < -tol) return kReconFilterInside;
+  return kReconFilterUndecided;
 }
 
 // ((c - b) x (p - b)) . n < 0: p lies strictly beyond the edge b -> c of the oriented triangle, in its plane

@@ -971,7 +971,8 @@ def ball_pivot(ijk, normals_i16, rho2_list, max_tests: int | None = None, device
         raise ValueError("lattice points must be integers")
     if p.size and (p.min() < -(1 << 31) or p.max() >= (1 << 31)):
         raise ValueError("lattice points must fit int32")
-    if p.size and int(p.max()) - int(p.min()) >= (1 << 31):
+    # per axis, as the library measures it: local coordinates are ijk - min of their own axis
+    if p.size and int((p.max(axis=0).astype(np.int64) - p.min(axis=0).astype(np.int64)).max()) >= (1 << 31):
         raise ValueError("the cloud spans more than 2^31 lattice units")
     p = np.ascontiguousarray(p, dtype=np.int32)
     n = p.shape[0]

@@ -9,6 +9,7 @@ from pyqsm_amd.geometry import mesh_processing as mp
 from pyqsm_amd.geometry import point_cloud_processing as pcp
 from pyqsm_amd.geometry import surf_recon
 from pyqsm_amd.geometry.cloud import PointCloud, TriangleMesh
+from tests import recon_cases as C
 from tests import recon_restatement as R
 
 pytestmark = pytest.mark.gpu
@@ -226,3 +227,103 @@ def test_wrappers_return_a_closed_mesh(gpu):
         assert props["watertight"] and props["edge_manifold"] and props["vertex_manifold"] and props["orientable"]
     vn = mesh2.vertex_normals
     assert vn.shape == (len(F), 3) and ((vn * (F - R.R_SPHERE)).sum(axis=1) > 0).all()   # outward
+
+
+# ---- tie-dense lattices (tests/recon_cases.py; tests/test_recon_host.py proves what each input is for).
+# Random clouds never come within 1e-6 of a tie, against the 2^-46 band of the fp64 filter: these clouds
+# sit on it, up to the largest admitted radius. The reference is R.brute, and only that.
+
+def lowest_first(T, lv):
+    """Rows (a, b, c, level), each cycle turned so that its lowest index comes first, sorted."""
+    T = np.asarray(T)
+    rot = np.argmin(T, axis=1)
+    T = np.stack([T[np.arange(len(T)), (rot + k) % 3] for k in range(3)], axis=1)
+    return sorted(map(tuple, np.concatenate([T, np.asarray(lv)[:, None]], axis=1).tolist()))
+
+
+@pytest.mark.parametrize("key", C.tie_lattice_keys(),
+                         ids=lambda k: "seed%d-m%d-pitch%d-%s" % (k[0], k[1], k[2], "flat" if k[4] else "box"))
+def test_tie_lattices(gpu, key):
+    """Coincident points, half a cloud in one plane, normals exactly perpendicular to triangle normals,
+    cocircular and cospherical ties at every pitch up to the bound (pitch 1182: rho^2 = 3 * 1182^2).
+    The tie rule depends on the numbering of the points by design (the fan from the smallest index; a
+    tie of a lower index than a drops the triple), so a permuted copy gives the renumbered triangles only
+    where nothing ties. Coincident points tie in the plane of each other's triangles, so every case of this
+    table has ties: the permuted copy is held against brute of the permuted copy, and against the
+    renumbered triangles should a case ever be free of ties."""
+    P, Nr, rho2 = C.tie_lattice(*key)
+    ref = C.reference("tie_lattice", *key)
+    res = hip.ball_pivot(P, Nr, rho2)
+    assert_same(res, ref)
+    pitch = key[2]
+    if pitch >= 500:
+        assert res.stats["exact_fallbacks"] > 0
+    shift = np.array([-(1 << 30), (1 << 30) - 99991, 12345], np.int32)
+    assert_same(hip.ball_pivot(P + shift, Nr, rho2), ref)
+    perm = np.random.default_rng(key[0]).permutation(len(P))     # new index i holds old point perm[i]
+    moved = hip.ball_pivot(P[perm], Nr[perm], rho2)
+    assert_same(moved, R.brute(P[perm], Nr[perm], rho2))
+    if ref[2] == 0 and C.census("tie_lattice", *key) == (0, 0):
+        assert lowest_first(perm[moved.triangles], moved.levels) == lowest_first(ref[0], ref[1])
+
+
+@pytest.mark.parametrize("inward", [True, False], ids=["inward", "outward"])
+@pytest.mark.parametrize("r2", sorted(C.SPHERE_POINTS))
+def test_cospherical_at_the_bound(gpu, r2, inward):
+    """18 integer points of a sphere with rho^2 = r^2 just below 2^22: N and sqrt(H) D are about 2^72 and
+    equal. With inward normals every candidate rests on the sphere itself and every other point ties."""
+    P, Nr, rho2 = C.lattice_sphere(r2, 18, inward)
+    res = hip.ball_pivot(P, Nr, rho2)
+    assert_same(res, C.reference("lattice_sphere", r2, 18, inward))
+    if inward:
+        assert res.n_unresolved_ties == len(res.triangles) > 0
+        assert res.stats["exact_fallbacks"] >= res.stats["candidates"] > 0
+
+
+@pytest.mark.parametrize("sign", [1, -1], ids=["up", "down"])
+@pytest.mark.parametrize("height", [50, 49])
+def test_ball_centre_in_the_plane(gpu, height, sign):
+    """H == 0: sqrt(H) = 0, both orientations share one ball; the fifth point ties off the plane or is inside."""
+    P, Nr, rho2 = C.rectangle_h0(height)
+    res = hip.ball_pivot(P, sign * Nr, rho2)
+    assert_same(res, R.brute(P, sign * Nr, rho2))
+    assert (res.n_unresolved_ties > 0) == (height == 50)
+
+
+@pytest.fixture(scope="module")
+def dense_box_reference():
+    return C.reference("dense_box")
+
+
+def test_dense_box_of_ties(gpu, dense_box_reference):
+    P, Nr, rho2 = C.dense_box()
+    res = hip.ball_pivot(P, Nr, rho2)
+    assert_same(res, dense_box_reference)
+    assert res.stats["max_stencil"] > hip.RECON_CHUNK            # the LDS chunk is refilled, on a cloud full of ties
+    assert res.stats["max_cell_points"] > hip.RECON_SLICE
+    assert res.stats["exact_fallbacks"] > 0
+    again = hip.ball_pivot(P, Nr, rho2)
+    assert again.triangles.tobytes() == res.triangles.tobytes() and again.levels.tobytes() == res.levels.tobytes()
+    assert again.n_unresolved_ties == res.n_unresolved_ties
+
+
+@pytest.mark.parametrize("low", C.FAR_LOWS, ids=["centred", "from_int32_min"])
+def test_int32_extremes(gpu, low):
+    """Two tie lattices 2^31 - 1 units apart along x, the largest admitted span, from -2^30 and from
+    INT32_MIN: local coordinates are ijk - min, and the grid's cell count is capped."""
+    P, Nr, rho2 = C.far_apart(low)
+    res = hip.ball_pivot(P, Nr, rho2)
+    assert_same(res, C.reference("far_apart", low))
+    assert_same(res, C.far_apart_from_halves())                  # the halves by themselves, renumbered
+
+
+def test_triangle_cap_is_a_refusal(gpu):
+    """30 cospherical points expose about 4 060 triples against a cap of 8 n + 1024 = 1 264 rows: refused
+    after the pass (the kernel counts every triangle and writes only the rows below the cap), and the
+    next call finds the scratch in order."""
+    P, Nr, rho2 = C.lattice_sphere(C.R2_CUBE, 30, True)
+    with pytest.raises(hip.BallPivotRefused, match=r"more than 8 n \+ 1024 = 1264") as e:
+        hip.ball_pivot(P, Nr, rho2)
+    assert e.value.code == -4 and isinstance(e.value, ValueError)
+    S, Sn, s2 = R.sphere()
+    assert_same(hip.ball_pivot(S, Sn, s2), R.brute(S, Sn, s2))

@@ -1,7 +1,8 @@
 """The ball-pivoting contract on the CPU (tests/recon_restatement.py): the brute-force definition and the
 Delaunay route agree on the clouds in general position the GPU tests use, the degenerate fixtures give
 what the issue's trial gave, and the host side of the wrappers (snapping, refusals, vertex normals, the
-binding's constants, the sanitizer program of the integer predicate) holds without a GPU."""
+binding's constants, the sanitizer program of the integer predicate and of the fp64 filter in front of it)
+holds without a GPU, and the tie-dense inputs of tests/recon_cases.py have the properties they are for."""
 import os
 import re
 import subprocess
@@ -11,6 +12,7 @@ import pytest
 
 from pyqsm_amd import _lib, hip
 from pyqsm_amd.geometry.cloud import PointCloud, TriangleMesh
+from tests import recon_cases as C
 from tests import recon_restatement as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -137,3 +139,110 @@ def test_integer_predicate_under_the_sanitizers():
                          capture_output=True, text=True)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "recon_check: ok" in out.stdout
+    # the fp64 filter against the integers: both signs taken, a hand-over that was used, no disagreement
+    counts = re.search(r"filter: (\d+) inside, (\d+) outside, (\d+) undecided, (\d+) exact ties among them, "
+                       r"0 disagreements", out.stdout)
+    assert counts, out.stdout
+    inside, outside, undecided, ties = map(int, counts.groups())
+    assert inside + outside + undecided >= 1_000_000 and min(inside, outside) > 0 and undecided >= ties > 100_000
+
+
+# ---- the tie-dense inputs of tests/test_gpu_recon.py (tests/recon_cases.py): each has, on the CPU, the
+# property its GPU test depends on, and a reference within the library's triangle cap
+
+def test_cases_snap_normals_as_the_binding_does():
+    assert C.NORMAL_SCALE == hip.RECON_NORMAL_SCALE
+    v = np.random.default_rng(0).normal(size=(50, 3))
+    assert np.array_equal(C.snap(v), hip.snap_normals(v / np.linalg.norm(v, axis=1, keepdims=True)))
+    assert max(r for _, radii in C.TIE_TABLE for r in radii) == C.R2_CUBE <= hip.RECON_MAX_RHO2
+    assert C.R2_CUBE < C.R2_TOP <= hip.RECON_MAX_RHO2
+
+
+@pytest.mark.parametrize("pitch,radii", C.TIE_TABLE)
+def test_tie_lattices_tie_and_fit_the_cap(pitch, radii):
+    off_plane = second_level = 0
+    for key in C.tie_lattice_keys():
+        if key[2] != pitch:
+            continue
+        P, Nr, rho2 = C.tie_lattice(*key)
+        seed, m, _, _, flat = key
+        assert rho2 == radii and P.shape == (C.N_TIE_LATTICE, 3) and P.dtype == np.int32 and Nr.dtype == np.int16
+        sites = (P.astype(np.int64) - P.min(axis=0)) // pitch
+        assert np.array_equal(sites * pitch, P.astype(np.int64) - P.min(axis=0)) and sites.max() <= m - 1
+        assert np.abs(P).max() <= (1 << 20) + (m - 1) * pitch
+        assert len(np.unique(P, axis=0)) < len(P)                        # coincident points
+        if flat:
+            assert max(np.bincount(sites[:, 2])) >= len(P) // 2 - 3      # half the cloud in one plane, but for copies
+        axis = (np.abs(Nr.astype(np.int64)).max(axis=1) == C.NORMAL_SCALE) & ((Nr != 0).sum(axis=1) == 1)
+        assert axis.sum() >= 5
+        assert C.perpendicular_normals(P, Nr, max(rho2)) > 0             # da == 0 in recon_pair
+        T, lv, unresolved = C.reference("tie_lattice", *key)
+        coplanar, off = C.census("tie_lattice", *key)
+        assert 0 < len(T) <= C.triangle_cap(len(P)) and coplanar > 0
+        assert (unresolved > 0) == (off > 0)
+        off_plane += off
+        second_level += int((lv > 0).sum())
+    assert off_plane > 0 and second_level > 0
+
+
+@pytest.mark.parametrize("r2", sorted(C.SPHERE_POINTS))
+def test_lattice_spheres_are_cospherical(r2):
+    assert len(C.sphere_points(r2)) == C.SPHERE_POINTS[r2]               # the counts csrc/recon_check.cpp finds
+    centre = C.lattice_sphere_centre(r2)
+    for inward in (True, False):
+        P, Nr, rho2 = C.lattice_sphere(r2, 18, inward)
+        Q = P.astype(np.int64) - centre
+        assert rho2 == (r2,) and len(np.unique(P, axis=0)) == 18 and ((Q * Q).sum(axis=1) == r2).all()
+        assert (((Q * Nr).sum(axis=1) < 0) == inward).all()
+        T, lv, unresolved = C.reference("lattice_sphere", r2, 18, inward)
+        assert 0 < len(T) <= 816 <= C.triangle_cap(18)
+        if inward:      # every triple rests on the sphere itself, and every other point ties
+            assert unresolved == len(T) >= 800 and sum(C.census("lattice_sphere", r2, 18, inward)) >= 15 * len(T)
+    big = C.lattice_sphere(C.R2_CUBE, 30, True)[0]
+    assert len(np.unique(big, axis=0)) == 30 and 30 * 29 * 28 // 6 > 3 * C.triangle_cap(30)
+
+
+def test_rectangle_has_its_ball_centre_in_the_plane():
+    for height, sign in ((50, 1), (50, -1), (49, 1), (49, -1)):
+        P, Nr, rho2 = C.rectangle_h0(height)
+        Pl = R.as_ints(P)
+        for i, j, k in ((0, 1, 2), (0, 1, 3), (0, 2, 3), (1, 2, 3), (0, 2, 1)):
+            assert R.setup(Pl[i], Pl[j], Pl[k], rho2[0])["H"] == 0
+        t = R.setup(Pl[0], Pl[1], Pl[2], rho2[0])
+        assert R.classify(t, Pl[3]) == R.TIE_COPLANAR
+        assert R.classify(t, Pl[4]) == (R.TIE_OFF_PLANE if height == 50 else R.INSIDE)
+        T, lv, unresolved = R.brute(P, sign * Nr, rho2)
+        in_plane = [row for row in T.tolist() if 4 not in row]
+        # with the tie off the plane both diagonals stay and are counted; with the point inside no
+        # triangle of the rectangle alone is left
+        assert (len(in_plane), unresolved > 0) == ((4, True) if height == 50 else (0, False))
+
+
+def test_dense_box_fills_chunks_and_slices():
+    P, Nr, rho2 = C.dense_box()
+    assert len(P) == 1100 > hip.RECON_CHUNK and len(np.unique(P, axis=0)) == 1090
+    assert P.min() == 0 and P.max() == 11 and rho2 == (1, 2)
+    edge = int(np.ceil(2 * np.sqrt(max(rho2)))) + 1                      # 4: three cells per axis
+    cells = np.unique(P // edge, axis=0, return_counts=True)[1]
+    assert edge == 4 and len(cells) == 27 and cells.min() > hip.RECON_SLICE
+    T, lv, unresolved = C.reference("dense_box")
+    assert 1000 < len(T) <= C.triangle_cap(len(P)) and unresolved > 100 and (lv == 1).sum() > 0
+
+
+@pytest.mark.parametrize("low", C.FAR_LOWS)
+def test_far_apart_spans_the_int32_range(low):
+    P, Nr, rho2 = C.far_apart(low)
+    assert P.dtype == np.int32 and int(P[:, 0].min()) == low and int(P[:, 0].max()) == low + (1 << 31) - 1
+    assert low >= -(1 << 31) and np.abs(P[:, 1:].astype(np.int64)).max() < 1 << 21
+    halves = [C.tie_lattice(*k)[0] for k in C.FAR_HALVES]
+    assert np.array_equal(P[:36, 1:], halves[0][:, 1:]) and np.array_equal(P[36:, 1:], halves[1][:, 1:])   # x only
+    assert np.array_equal(np.diff(P[:36, 0].astype(np.int64)), np.diff(halves[0][:, 0].astype(np.int64)))
+    ref, want = C.reference("far_apart", low), C.far_apart_from_halves()
+    assert np.array_equal(ref[0], want[0]) and np.array_equal(ref[1], want[1]) and ref[2] == want[2] > 0
+    assert (ref[0] < 36).all(axis=1).any() and (ref[0] >= 36).all(axis=1).any()
+    # one unit more on that axis is refused. The span is measured per axis, as the library does: a y or z
+    # above zero lies more than 2^31 above the lowest x of the cloud from INT32_MIN, and that is no span.
+    wide = P.copy()
+    wide[np.argmax(P[:, 0]), 0] += 1
+    with pytest.raises(ValueError, match="spans more than 2\\^31"):
+        hip.ball_pivot(wide, Nr, rho2)
