@@ -29,6 +29,7 @@
 #include "grid.hpp"
 
 #include <cmath>
+#include <type_traits>
 
 #include "raycast.hpp"
 
@@ -143,94 +144,178 @@ __device__ __forceinline__ bool is_hit(float det, float U, float V, float Tn) {
   return pos || neg;
 }
 
-// NP = ray pairs per lane (each lane owns 2*NP rays).
+// Origin (part 0) or direction (part 1) of ray r; zeros for a slot past the end of the batch.
+__device__ __forceinline__ void load_ray(const float* __restrict__ rays, int64_t r, int64_t R,
+                                         int part, float& x, float& y, float& z) {
+  x = y = z = 0.f;
+  if (r < R) {
+    const float* p = rays + 6 * r + 3 * part;
+    x = p[0]; y = p[1]; z = p[2];
+  }
+}
+__device__ __forceinline__ RayPair splat_ray(float o0, float o1, float o2, float d0, float d1,
+                                             float d2) {
+  return RayPair{splat(o0), splat(o1), splat(o2), splat(d0), splat(d1), splat(d2)};
+}
+
+// ---- the ray tile -----------------------------------------------------------------
+// NP = ray pairs per lane: a lane owns 2*NP rays ("slots"), a block 256*2*NP consecutive ones.
+// Slot k of a lane is, in the in-order sweeps, ray block + k*256 + thread (coalesced loads);
+// in the culled walks (BY_WAVE) a wave owns 64*2*NP CONSECUTIVE rays, so that its rectangle
+// on the culling plane is small: ray block + wave*64*2*NP + k*64 + lane.
+template <int NP, bool BY_WAVE>
+__device__ __forceinline__ int64_t slot_ray(int k) {
+  const int64_t block = int64_t(blockIdx.x) * (256 * 2 * NP);
+  return BY_WAVE ? block + int64_t(threadIdx.x >> 6) * (64 * 2 * NP) + (threadIdx.x & 63) + int64_t(k) * 64
+                 : block + int64_t(k) * 256 + threadIdx.x;
+}
+
+// The rays of a lane, slot k in half k & 1 of pair k >> 1: origin and direction per ray ...
+// (Both kinds hand out whole pairs only, pair(q). A read of one half of a packed member followed
+// by a splat is turned into a load that straddles two members while this code is optimised by
+// itself, before it is inlined, and the rays then stay in memory instead of registers:
+// profiles/ray_sweep_resource_usage.txt.)
+template <int NP>
+struct AnyRays {
+  RayPair rp[NP];
+  __device__ __forceinline__ void common(const float* __restrict__) {}
+  __device__ __forceinline__ void load(int k, const float* __restrict__ rays, int64_t r, int64_t R) {
+    float o0, o1, o2, d0, d1, d2;
+    load_ray(rays, r, R, 0, o0, o1, o2);
+    load_ray(rays, r, R, 1, d0, d1, d2);
+    rp[k >> 1].ox[k & 1] = o0; rp[k >> 1].oy[k & 1] = o1; rp[k >> 1].oz[k & 1] = o2;
+    rp[k >> 1].dx[k & 1] = d0; rp[k >> 1].dy[k & 1] = d1; rp[k >> 1].dz[k & 1] = d2;
+  }
+  __device__ __forceinline__ RayPair pair(int q) const { return rp[q]; }
+};
+// ... or origins only, with ray 0's direction for all (wave-uniform: SGPRs).
+template <int NP>
+struct OneDirRays {
+  f2 ox[NP], oy[NP], oz[NP];
+  f2 dx, dy, dz;  // the same in both halves and in every lane
+  __device__ __forceinline__ void common(const float* __restrict__ rays) {
+    dx = splat(rays[3]); dy = splat(rays[4]); dz = splat(rays[5]);
+  }
+  __device__ __forceinline__ void load(int k, const float* __restrict__ rays, int64_t r, int64_t R) {
+    float o0, o1, o2;
+    load_ray(rays, r, R, 0, o0, o1, o2);
+    ox[k >> 1][k & 1] = o0; oy[k >> 1][k & 1] = o1; oz[k >> 1][k & 1] = o2;
+  }
+  __device__ __forceinline__ RayPair pair(int q) const {
+    return RayPair{ox[q], oy[q], oz[q], dx, dy, dz};
+  }
+};
+
+template <int NP>
+struct Best {  // closest hit so far of every slot
+  float t[2 * NP];
+  uint32_t p[2 * NP];
+};
+
+template <int NP, bool BY_WAVE, class RAYS>
+__device__ __forceinline__ void load_tile(const float* __restrict__ rays, int64_t R, RAYS& ry,
+                                          Best<NP>& best) {
+#pragma unroll
+  for (int k = 0; k < 2 * NP; ++k) {
+    ry.load(k, rays, slot_ray<NP, BY_WAVE>(k), R);
+    best.t[k] = __builtin_inff();
+    best.p[k] = PYQSM_MISS_PRIM;
+  }
+  ry.common(rays);
+}
+
+// The closest-hit rule: strictly smaller t wins, and ties go to the lowest triangle id. A sweep
+// in triangle order gets that from `tt < best` alone (BY_ID false); a walk in any other order
+// compares (t, id), so that the processing order does not matter.
+template <bool BY_ID>
+__device__ __forceinline__ void keep_closest(float tt, uint32_t id, float& best_t, uint32_t& best_p) {
+  if (tt < best_t || (BY_ID && tt == best_t && id < best_p)) {
+    best_t = tt;
+    best_p = id;
+  }
+}
+
+// One triangle (id: its index in the mesh) against all ray pairs of this lane.
+template <int NP, bool BY_ID>
+__device__ __forceinline__ void test_tri(const AnyRays<NP>& ry, const Tri t, const uint32_t id,
+                                         Best<NP>& best) {
+#pragma unroll
+  for (int q = 0; q < NP; ++q) {
+    f2 px, py, pz, det, tvx, tvy, tvz, U;
+    mt_front(ry.rp[q], t, px, py, pz, det, tvx, tvy, tvz, U);
+    const f2 key = alive_key(det, U);
+    bool alive = u_alive(key[0], det[0]) || u_alive(key[1], det[1]);
+    if (__builtin_amdgcn_ballot_w64(alive) != 0) {  // wave-uniform branch
+      f2 V, Tn;
+      mt_back(ry.rp[q], t, tvx, tvy, tvz, V, Tn);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        if (is_hit(det[h], U[h], V[h], Tn[h]))
+          keep_closest<BY_ID>(Tn[h] / det[h], id, best.t[2 * q + h], best.p[2 * q + h]);
+      }
+    }
+  }
+}
+
+// Records 0 .. T-1 in order through test(record, j). The addresses are wave-uniform, so the
+// records arrive by scalar loads. Two register sets alternate so that the next record is in
+// flight while this one is consumed and no register copies are needed. T >= 1 is checked by
+// the launcher.
+template <class LOAD, class TEST>
+__device__ __forceinline__ void sweep_in_order(int T, LOAD load, TEST test) {
+  auto a = load(0);
+  int j = 0;
+  for (; j + 1 < T; j += 2) {
+    const auto b = load(j + 1);
+    test(a, j);
+    a = load(j + 2 < T ? j + 2 : j + 1);
+    test(b, j + 1);
+  }
+  if (j < T) test(a, j);
+}
+
+// Stores t and the primitive id of every slot, and u, v of the winner, re-evaluated with the
+// same operation sequence: against both rays of the slot's pair, of which the slot's half is kept.
+template <int NP, bool BY_WAVE, class RAYS>
+__device__ __forceinline__ void store_tile(const TriRec* __restrict__ tri, const RAYS& ry,
+                                           const Best<NP>& best, int64_t R,
+                                           float* __restrict__ t_hit,
+                                           uint32_t* __restrict__ prim_id, float* __restrict__ uv) {
+#pragma unroll
+  for (int k = 0; k < 2 * NP; ++k) {
+    const int64_t r = slot_ray<NP, BY_WAVE>(k);
+    if (r >= R) continue;
+    t_hit[r] = best.t[k];
+    prim_id[r] = best.p[k];
+    if (uv) {
+      float u = 0.f, v = 0.f;
+      if (best.p[k] != PYQSM_MISS_PRIM) {
+        const Tri t = load_tri(tri, int(best.p[k]));
+        const RayPair both = ry.pair(k >> 1);
+        f2 px, py, pz, det, tvx, tvy, tvz, U, V, Tn;
+        mt_front(both, t, px, py, pz, det, tvx, tvy, tvz, U);
+        mt_back(both, t, tvx, tvy, tvz, V, Tn);
+        u = U[k & 1] / det[k & 1];
+        v = V[k & 1] / det[k & 1];
+      }
+      uv[2 * r] = u;
+      uv[2 * r + 1] = v;
+    }
+  }
+}
+
 template <int NP>
 __global__ __launch_bounds__(256) void k_cast_rays(const TriRec* __restrict__ tri, int T,
                                                    const float* __restrict__ rays, int64_t R,
                                                    float* __restrict__ t_hit,
                                                    uint32_t* __restrict__ prim_id,
                                                    float* __restrict__ uv) {
-  constexpr int RPL = 2 * NP;
-  const int64_t block_base = int64_t(blockIdx.x) * (256 * RPL);
-  RayPair rp[NP];
-  float best_t[RPL];
-  uint32_t best_p[RPL];
-#pragma unroll
-  for (int k = 0; k < RPL; ++k) {
-    int64_t r = block_base + int64_t(k) * 256 + threadIdx.x;
-    float o0 = 0.f, o1 = 0.f, o2 = 0.f, d0 = 0.f, d1 = 0.f, d2 = 0.f;
-    if (r < R) {
-      const float* p = rays + 6 * r;
-      o0 = p[0]; o1 = p[1]; o2 = p[2]; d0 = p[3]; d1 = p[4]; d2 = p[5];
-    }
-    rp[k >> 1].ox[k & 1] = o0; rp[k >> 1].oy[k & 1] = o1; rp[k >> 1].oz[k & 1] = o2;
-    rp[k >> 1].dx[k & 1] = d0; rp[k >> 1].dy[k & 1] = d1; rp[k >> 1].dz[k & 1] = d2;
-    best_t[k] = __builtin_inff();
-    best_p[k] = PYQSM_MISS_PRIM;
-  }
-
-  // One triangle against all ray pairs of this lane.
-  auto sweep = [&](const Tri t, const int j) {
-#pragma unroll
-    for (int q = 0; q < NP; ++q) {
-      f2 px, py, pz, det, tvx, tvy, tvz, U;
-      mt_front(rp[q], t, px, py, pz, det, tvx, tvy, tvz, U);
-      const f2 key = alive_key(det, U);
-      bool alive = u_alive(key[0], det[0]) || u_alive(key[1], det[1]);
-      if (__builtin_amdgcn_ballot_w64(alive) != 0) {  // wave-uniform branch
-        f2 V, Tn;
-        mt_back(rp[q], t, tvx, tvy, tvz, V, Tn);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          if (is_hit(det[h], U[h], V[h], Tn[h])) {
-            float tt = Tn[h] / det[h];
-            if (tt < best_t[2 * q + h]) {
-              best_t[2 * q + h] = tt;
-              best_p[2 * q + h] = uint32_t(j);
-            }
-          }
-        }
-      }
-    }
-  };
-  // Wave-uniform addresses: records arrive by scalar loads. Two register sets
-  // alternate so that the next record is in flight while this one is consumed
-  // and no register copies are needed. T >= 1 is checked by the launcher.
-  Tri ta = load_tri(tri, 0);
-  int j = 0;
-  for (; j + 1 < T; j += 2) {
-    const Tri tb = load_tri(tri, j + 1);
-    sweep(ta, j);
-    ta = load_tri(tri, j + 2 < T ? j + 2 : j + 1);
-    sweep(tb, j + 1);
-  }
-  if (j < T) sweep(ta, j);
-
-#pragma unroll
-  for (int k = 0; k < RPL; ++k) {
-    int64_t r = block_base + int64_t(k) * 256 + threadIdx.x;
-    if (r >= R) continue;
-    t_hit[r] = best_t[k];
-    prim_id[r] = best_p[k];
-    if (uv) {
-      float u = 0.f, v = 0.f;
-      if (best_p[k] != PYQSM_MISS_PRIM) {
-        // Re-evaluate the winner with the same operation sequence.
-        const Tri t = load_tri(tri, int(best_p[k]));
-        RayPair one;
-        const int q = k >> 1, h = k & 1;
-        one.ox = splat(rp[q].ox[h]); one.oy = splat(rp[q].oy[h]); one.oz = splat(rp[q].oz[h]);
-        one.dx = splat(rp[q].dx[h]); one.dy = splat(rp[q].dy[h]); one.dz = splat(rp[q].dz[h]);
-        f2 px, py, pz, det, tvx, tvy, tvz, U, V, Tn;
-        mt_front(one, t, px, py, pz, det, tvx, tvy, tvz, U);
-        mt_back(one, t, tvx, tvy, tvz, V, Tn);
-        u = U[0] / det[0];
-        v = V[0] / det[0];
-      }
-      uv[2 * r] = u;
-      uv[2 * r + 1] = v;
-    }
-  }
+  AnyRays<NP> ry;
+  Best<NP> best;
+  load_tile<NP, false>(rays, R, ry, best);
+  sweep_in_order(T, [&](int j) { return load_tri(tri, j); },
+                 [&](const Tri t, int j) { test_tri<NP, false>(ry, t, uint32_t(j), best); });
+  store_tile<NP, false>(tri, ry, best, R, t_hit, prim_id, uv);
 }
 
 // ---- parallel rays (one direction for the whole batch) ---------------------------
@@ -255,19 +340,19 @@ __device__ __forceinline__ Front load_front(const DirRec* __restrict__ rec, int 
   return Front{a.x, a.y, a.z, a.w, b.x, b.y, b.z};
 }
 
+// The per-direction record of one triangle, for the direction of ray 0.
+__device__ __forceinline__ DirRec dir_rec(const Tri t, const float* __restrict__ rays) {
+  const RayPair r = splat_ray(0.f, 0.f, 0.f, rays[3], rays[4], rays[5]);
+  f2 px, py, pz, det, tvx, tvy, tvz, U;
+  mt_front(r, t, px, py, pz, det, tvx, tvy, tvz, U);
+  return DirRec{t.v0x, t.v0y, t.v0z, px[0], py[0], pz[0], det[0], 0.f};
+}
+
 __global__ void k_dir_records(const TriRec* __restrict__ tri, int64_t T,
                               const float* __restrict__ rays, DirRec* __restrict__ out) {
   int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
   if (i >= T) return;
-  const Tri t = load_tri(tri, int(i));
-  RayPair r;
-  r.ox = r.oy = r.oz = splat(0.f);
-  r.dx = splat(rays[3]);
-  r.dy = splat(rays[4]);
-  r.dz = splat(rays[5]);
-  f2 px, py, pz, det, tvx, tvy, tvz, U;
-  mt_front(r, t, px, py, pz, det, tvx, tvy, tvz, U);
-  out[i] = DirRec{t.v0x, t.v0y, t.v0z, px[0], py[0], pz[0], det[0], 0.f};
+  out[i] = dir_rec(load_tri(tri, int(i)), rays);
 }
 
 // flag bit 0: some ray's direction differs (bitwise) from ray 0's; bit 1: some origin does
@@ -286,6 +371,36 @@ __global__ void k_check_uniform(const float* __restrict__ rays, int64_t R,
   if (bits && (threadIdx.x & 63) == 0) atomicOr(flag, bits);
 }
 
+// One front record against all ray pairs of this lane. id_of() names the triangle the record
+// belongs to; it is asked only in the rare branch that fetches the edges and finishes.
+template <int NP, bool BY_ID, class ID>
+__device__ __forceinline__ void test_front(const OneDirRays<NP>& ry, const TriRec* __restrict__ tri,
+                                           const Front f, ID id_of, Best<NP>& best) {
+  const int dbits = __builtin_bit_cast(int, f.det);
+  const bool det_pos = dbits > 0, det_neg = dbits < 0 && dbits != int(0x80000000u);
+#pragma unroll
+  for (int q = 0; q < NP; ++q) {
+    const f2 tvx = ry.ox[q] - splat(f.v0x), tvy = ry.oy[q] - splat(f.v0y), tvz = ry.oz[q] - splat(f.v0z);
+    const f2 U = fma2(tvx, splat(f.px), fma2(tvy, splat(f.py), tvz * splat(f.pz)));
+    const f2 det = splat(f.det);
+    const f2 key = alive_key(det, U);
+    bool alive = u_alive(key[0], f.det) || u_alive(key[1], f.det);
+    if (__builtin_amdgcn_ballot_w64(alive) != 0) {
+      const uint32_t id = id_of();
+      const Tri t = load_tri(tri, int(id));
+      RayPair r;
+      r.dx = ry.dx; r.dy = ry.dy; r.dz = ry.dz;
+      f2 V, Tn;
+      mt_back(r, t, tvx, tvy, tvz, V, Tn);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        if (is_hit_signed(det_pos, det_neg, f.det, U[h], V[h], Tn[h]))
+          keep_closest<BY_ID>(Tn[h] / f.det, id, best.t[2 * q + h], best.p[2 * q + h]);
+      }
+    }
+  }
+}
+
 template <int NP>
 __global__ __launch_bounds__(256) void k_cast_parallel(const TriRec* __restrict__ tri,
                                                        const DirRec* __restrict__ rec, int T,
@@ -293,88 +408,13 @@ __global__ __launch_bounds__(256) void k_cast_parallel(const TriRec* __restrict_
                                                        float* __restrict__ t_hit,
                                                        uint32_t* __restrict__ prim_id,
                                                        float* __restrict__ uv) {
-  constexpr int RPL = 2 * NP;
-  const int64_t block_base = int64_t(blockIdx.x) * (256 * RPL);
-  f2 ox[NP], oy[NP], oz[NP];
-  float best_t[RPL];
-  uint32_t best_p[RPL];
-#pragma unroll
-  for (int k = 0; k < RPL; ++k) {
-    int64_t r = block_base + int64_t(k) * 256 + threadIdx.x;
-    float o0 = 0.f, o1 = 0.f, o2 = 0.f;
-    if (r < R) {
-      const float* p = rays + 6 * r;
-      o0 = p[0]; o1 = p[1]; o2 = p[2];
-    }
-    ox[k >> 1][k & 1] = o0; oy[k >> 1][k & 1] = o1; oz[k >> 1][k & 1] = o2;
-    best_t[k] = __builtin_inff();
-    best_p[k] = PYQSM_MISS_PRIM;
-  }
-  const float d0 = rays[3], d1 = rays[4], d2 = rays[5];  // the common direction
-
-  auto sweep = [&](const Front f, const int j) {
-    const int dbits = __builtin_bit_cast(int, f.det);
-    const bool det_pos = dbits > 0, det_neg = dbits < 0 && dbits != int(0x80000000u);
-#pragma unroll
-    for (int q = 0; q < NP; ++q) {
-      const f2 tvx = ox[q] - splat(f.v0x), tvy = oy[q] - splat(f.v0y), tvz = oz[q] - splat(f.v0z);
-      const f2 U = fma2(tvx, splat(f.px), fma2(tvy, splat(f.py), tvz * splat(f.pz)));
-      const f2 det = splat(f.det);
-      const f2 key = alive_key(det, U);
-      bool alive = u_alive(key[0], f.det) || u_alive(key[1], f.det);
-      if (__builtin_amdgcn_ballot_w64(alive) != 0) {  // rare: fetch the edges and finish
-        const Tri t = load_tri(tri, j);
-        RayPair r;
-        r.dx = splat(d0); r.dy = splat(d1); r.dz = splat(d2);
-        f2 V, Tn;
-        mt_back(r, t, tvx, tvy, tvz, V, Tn);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          if (is_hit_signed(det_pos, det_neg, f.det, U[h], V[h], Tn[h])) {
-            float tt = Tn[h] / f.det;
-            if (tt < best_t[2 * q + h]) {
-              best_t[2 * q + h] = tt;
-              best_p[2 * q + h] = uint32_t(j);
-            }
-          }
-        }
-      }
-    }
-  };
-  Front fa = load_front(rec, 0);
-  int j = 0;
-  for (; j + 1 < T; j += 2) {
-    const Front fb = load_front(rec, j + 1);
-    sweep(fa, j);
-    fa = load_front(rec, j + 2 < T ? j + 2 : j + 1);
-    sweep(fb, j + 1);
-  }
-  if (j < T) sweep(fa, j);
-
-#pragma unroll
-  for (int k = 0; k < RPL; ++k) {
-    int64_t r = block_base + int64_t(k) * 256 + threadIdx.x;
-    if (r >= R) continue;
-    t_hit[r] = best_t[k];
-    prim_id[r] = best_p[k];
-    if (uv) {
-      float u = 0.f, v = 0.f;
-      if (best_p[k] != PYQSM_MISS_PRIM) {
-        const Tri t = load_tri(tri, int(best_p[k]));
-        RayPair one;
-        const int q = k >> 1, h = k & 1;
-        one.ox = splat(ox[q][h]); one.oy = splat(oy[q][h]); one.oz = splat(oz[q][h]);
-        one.dx = splat(d0); one.dy = splat(d1); one.dz = splat(d2);
-        f2 px, py, pz, det, tvx, tvy, tvz, U, V, Tn;
-        mt_front(one, t, px, py, pz, det, tvx, tvy, tvz, U);
-        mt_back(one, t, tvx, tvy, tvz, V, Tn);
-        u = U[0] / det[0];
-        v = V[0] / det[0];
-      }
-      uv[2 * r] = u;
-      uv[2 * r + 1] = v;
-    }
-  }
+  OneDirRays<NP> ry;
+  Best<NP> best;
+  load_tile<NP, false>(rays, R, ry, best);
+  sweep_in_order(T, [&](int j) { return load_front(rec, j); }, [&](const Front f, int j) {
+    test_front<NP, false>(ry, tri, f, [&] { return uint32_t(j); }, best);
+  });
+  store_tile<NP, false>(tri, ry, best, R, t_hit, prim_id, uv);
 }
 
 // ---- parallel rays with conservative cluster culling ---------------------------------
@@ -396,36 +436,68 @@ struct Basis {
   double ux, uy, uz, vx, vy, vz;
 };
 
+// Bounding rectangle of points on the culling plane, folded in fp64 and rounded outwards.
+struct Box2 {
+  double u0 = 1e300, u1 = -1e300, v0 = 1e300, v1 = -1e300;
+  __device__ __forceinline__ void add(double u, double v) {
+    u0 = u < u0 ? u : u0;
+    u1 = u > u1 ? u : u1;
+    v0 = v < v0 ? v : v0;
+    v1 = v > v1 ? v : v1;
+  }
+  __device__ __forceinline__ float4 outward() const {
+    return make_float4(__double2float_rd(u0), __double2float_ru(u1), __double2float_rd(v0),
+                       __double2float_ru(v1));
+  }
+};
+
+// Union of float rectangles (u0, u1, v0, v1).
+__device__ __forceinline__ float4 empty_rect() {
+  return make_float4(__builtin_inff(), -__builtin_inff(), __builtin_inff(), -__builtin_inff());
+}
+__device__ __forceinline__ void rect_add(float4& a, const float4 q) {
+  a.x = fminf(a.x, q.x);
+  a.y = fmaxf(a.y, q.y);
+  a.z = fminf(a.z, q.z);
+  a.w = fmaxf(a.w, q.w);
+}
+
+// The three vertices of a record, in fp64.
+struct Corners {
+  double x[3], y[3], z[3];
+};
+__device__ __forceinline__ Corners corners_of(const Tri t) {
+  return Corners{{double(t.v0x), double(t.v0x) + double(t.e1x), double(t.v0x) + double(t.e2x)},
+                 {double(t.v0y), double(t.v0y) + double(t.e1y), double(t.v0y) + double(t.e2y)},
+                 {double(t.v0z), double(t.v0z) + double(t.e1z), double(t.v0z) + double(t.e2z)}};
+}
+
 // per triangle: centroid on the plane (for sorting) and bounding rectangle
 __global__ __launch_bounds__(256) void k_tri_uv(const TriRec* __restrict__ tri, int64_t T, Basis b,
                                                 double* __restrict__ cen /*[T][3]*/,
                                                 float4* __restrict__ rect /*[T]*/) {
   int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
   if (i >= T) return;
-  const Tri t = load_tri(tri, int(i));
-  const double px[3] = {double(t.v0x), double(t.v0x) + double(t.e1x), double(t.v0x) + double(t.e2x)};
-  const double py[3] = {double(t.v0y), double(t.v0y) + double(t.e1y), double(t.v0y) + double(t.e2y)};
-  const double pz[3] = {double(t.v0z), double(t.v0z) + double(t.e1z), double(t.v0z) + double(t.e2z)};
-  double u0 = 1e300, u1 = -1e300, v0 = 1e300, v1 = -1e300, uc = 0.0, vc = 0.0;
+  const Corners p = corners_of(load_tri(tri, int(i)));
+  Box2 box;
+  double uc = 0.0, vc = 0.0;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    const double u = px[k] * b.ux + py[k] * b.uy + pz[k] * b.uz;
-    const double v = px[k] * b.vx + py[k] * b.vy + pz[k] * b.vz;
-    u0 = u < u0 ? u : u0;
-    u1 = u > u1 ? u : u1;
-    v0 = v < v0 ? v : v0;
-    v1 = v > v1 ? v : v1;
+    const double u = p.x[k] * b.ux + p.y[k] * b.uy + p.z[k] * b.uz;
+    const double v = p.x[k] * b.vx + p.y[k] * b.vy + p.z[k] * b.vz;
+    box.add(u, v);
     uc += u;
     vc += v;
   }
   cen[3 * i] = uc / 3.0;
   cen[3 * i + 1] = vc / 3.0;
   cen[3 * i + 2] = 0.0;
-  rect[i] = make_float4(__double2float_rd(u0), __double2float_ru(u1), __double2float_rd(v0),
-                        __double2float_ru(v1));
+  rect[i] = box.outward();
 }
 
-// sorted front records, original ids, and one grown rectangle per cluster
+// sorted original ids and one grown rectangle per cluster; WITH_REC: also the sorted front
+// records of the direction of ray 0 (tri, rays and srec are not read otherwise)
+template <bool WITH_REC>
 __global__ __launch_bounds__(256) void k_clusters(const TriRec* __restrict__ tri, int T,
                                                   const float* __restrict__ rays,
                                                   const int32_t* __restrict__ order,
@@ -436,26 +508,14 @@ __global__ __launch_bounds__(256) void k_clusters(const TriRec* __restrict__ tri
   const int cl = blockIdx.x * 256 + threadIdx.x;
   const int nclus = (T + kCluster - 1) / kCluster;
   if (cl >= nclus) return;
-  RayPair r;
-  r.ox = r.oy = r.oz = splat(0.f);
-  r.dx = splat(rays[3]);
-  r.dy = splat(rays[4]);
-  r.dz = splat(rays[5]);
-  float u0 = __builtin_inff(), u1 = -__builtin_inff(), v0 = __builtin_inff(), v1 = -__builtin_inff();
+  float4 a = empty_rect();
   for (int s = cl * kCluster; s < (cl + 1) * kCluster && s < T; ++s) {
     const int o = order[s];
-    const Tri t = load_tri(tri, o);
-    f2 px, py, pz, det, tvx, tvy, tvz, U;
-    mt_front(r, t, px, py, pz, det, tvx, tvy, tvz, U);
-    srec[s] = DirRec{t.v0x, t.v0y, t.v0z, px[0], py[0], pz[0], det[0], 0.f};
+    if (WITH_REC) srec[s] = dir_rec(load_tri(tri, o), rays);
     sid[s] = o;
-    const float4 q = rect[o];
-    u0 = fminf(u0, q.x);
-    u1 = fmaxf(u1, q.y);
-    v0 = fminf(v0, q.z);
-    v1 = fmaxf(v1, q.w);
+    rect_add(a, rect[o]);
   }
-  crect[cl] = make_float4(u0 - margin, u1 + margin, v0 - margin, v1 + margin);
+  crect[cl] = make_float4(a.x - margin, a.y + margin, a.z - margin, a.w + margin);
 }
 
 static constexpr int kSuper = 32;  // clusters per super-cluster (second level of rectangles)
@@ -465,15 +525,9 @@ __global__ __launch_bounds__(256) void k_super_rects(int nclus, const float4* __
   const int sc = blockIdx.x * 256 + threadIdx.x;
   const int nsup = (nclus + kSuper - 1) / kSuper;
   if (sc >= nsup) return;
-  float u0 = __builtin_inff(), u1 = -__builtin_inff(), v0 = __builtin_inff(), v1 = -__builtin_inff();
-  for (int cl = sc * kSuper; cl < (sc + 1) * kSuper && cl < nclus; ++cl) {
-    const float4 q = crect[cl];
-    u0 = fminf(u0, q.x);
-    u1 = fmaxf(u1, q.y);
-    v0 = fminf(v0, q.z);
-    v1 = fmaxf(v1, q.w);
-  }
-  srect[sc] = make_float4(u0, u1, v0, v1);
+  float4 a = empty_rect();
+  for (int cl = sc * kSuper; cl < (sc + 1) * kSuper && cl < nclus; ++cl) rect_add(a, crect[cl]);
+  srect[sc] = a;
 }
 
 __device__ __forceinline__ float wave_min_f(float v) {
@@ -486,84 +540,33 @@ __device__ __forceinline__ float wave_max_f(float v) {
   for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
   return v;
 }
+__device__ __forceinline__ float wave_uniform(float v) {  // a value all lanes share, as an SGPR
+  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
 
-template <int NP>
-__global__ __launch_bounds__(256) void k_cast_parallel_culled(
-    const TriRec* __restrict__ tri, const DirRec* __restrict__ srec,
-    const int32_t* __restrict__ sid, const float4* __restrict__ crect,
-    const float4* __restrict__ srect, int T, Basis b,
-    const float* __restrict__ rays, int64_t R, float* __restrict__ t_hit,
-    uint32_t* __restrict__ prim_id, float* __restrict__ uv) {
-  constexpr int RPL = 2 * NP;
-  // a wave owns 64*RPL CONSECUTIVE rays, so that its rectangle on the plane is small
-  const int64_t block_base =
-      int64_t(blockIdx.x) * (256 * RPL) + int64_t(threadIdx.x >> 6) * (64 * RPL) + (threadIdx.x & 63);
-  f2 ox[NP], oy[NP], oz[NP];
-  float best_t[RPL];
-  uint32_t best_p[RPL];
-  double umin = 1e300, umax = -1e300, vmin = 1e300, vmax = -1e300;
+// The culled walk of one wave. uv_of_slot(k, u, v) gives the plane coordinates of the ray in
+// slot k; their rectangle over the wave is tested against the super rectangles and, inside an
+// overlapping one, against its clusters' rectangles; slot(s) runs for every sorted position s
+// of an overlapping cluster. The wave's rectangle is made explicitly uniform, so that the
+// tests are scalar compares of SGPR values.
+template <int NP, class UV, class SLOT>
+__device__ __forceinline__ void walk_clusters(int64_t R, UV uv_of_slot,
+                                              const float4* __restrict__ crect,
+                                              const float4* __restrict__ srect, int T, SLOT slot) {
+  Box2 mine;
 #pragma unroll
-  for (int k = 0; k < RPL; ++k) {
-    int64_t r = block_base + int64_t(k) * 64;
-    float o0 = 0.f, o1 = 0.f, o2 = 0.f;
-    if (r < R) {
-      const float* p = rays + 6 * r;
-      o0 = p[0]; o1 = p[1]; o2 = p[2];
-      const double u = double(o0) * b.ux + double(o1) * b.uy + double(o2) * b.uz;
-      const double v = double(o0) * b.vx + double(o1) * b.vy + double(o2) * b.vz;
-      umin = u < umin ? u : umin;
-      umax = u > umax ? u : umax;
-      vmin = v < vmin ? v : vmin;
-      vmax = v > vmax ? v : vmax;
+  for (int k = 0; k < 2 * NP; ++k) {
+    if (slot_ray<NP, true>(k) < R) {
+      double u, v;
+      uv_of_slot(k, u, v);
+      mine.add(u, v);
     }
-    ox[k >> 1][k & 1] = o0; oy[k >> 1][k & 1] = o1; oz[k >> 1][k & 1] = o2;
-    best_t[k] = __builtin_inff();
-    best_p[k] = PYQSM_MISS_PRIM;
   }
-  // rectangle of this wave's ray origins on the plane (wave-uniform)
-  const float ru0 = wave_min_f(__double2float_rd(umin)), ru1 = wave_max_f(__double2float_ru(umax));
-  const float rv0 = wave_min_f(__double2float_rd(vmin)), rv1 = wave_max_f(__double2float_ru(vmax));
-  const float d0 = rays[3], d1 = rays[4], d2 = rays[5];
-
-  auto sweep = [&](const Front f, const int s) {
-    const int dbits = __builtin_bit_cast(int, f.det);
-    const bool det_pos = dbits > 0, det_neg = dbits < 0 && dbits != int(0x80000000u);
-#pragma unroll
-    for (int q = 0; q < NP; ++q) {
-      const f2 tvx = ox[q] - splat(f.v0x), tvy = oy[q] - splat(f.v0y), tvz = oz[q] - splat(f.v0z);
-      const f2 U = fma2(tvx, splat(f.px), fma2(tvy, splat(f.py), tvz * splat(f.pz)));
-      const f2 det = splat(f.det);
-      const f2 key = alive_key(det, U);
-      bool alive = u_alive(key[0], f.det) || u_alive(key[1], f.det);
-      if (__builtin_amdgcn_ballot_w64(alive) != 0) {
-        const uint32_t id = uint32_t(sid[s]);
-        const Tri t = load_tri(tri, int(id));
-        RayPair r;
-        r.dx = splat(d0); r.dy = splat(d1); r.dz = splat(d2);
-        f2 V, Tn;
-        mt_back(r, t, tvx, tvy, tvz, V, Tn);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          if (is_hit_signed(det_pos, det_neg, f.det, U[h], V[h], Tn[h])) {
-            float tt = Tn[h] / f.det;
-            // same winner as the in-order sweep: smallest t, then smallest triangle id
-            if (tt < best_t[2 * q + h] || (tt == best_t[2 * q + h] && id < best_p[2 * q + h])) {
-              best_t[2 * q + h] = tt;
-              best_p[2 * q + h] = id;
-            }
-          }
-        }
-      }
-    }
-  };
+  const float4 lane = mine.outward();
+  const float su0 = wave_uniform(wave_min_f(lane.x)), su1 = wave_uniform(wave_max_f(lane.y));
+  const float sv0 = wave_uniform(wave_min_f(lane.z)), sv1 = wave_uniform(wave_max_f(lane.w));
   const int nclus = (T + kCluster - 1) / kCluster;
   const int nsup = (nclus + kSuper - 1) / kSuper;
-  // the rectangles are uniform across the wave; make that explicit so that the tests
-  // below are scalar compares of SGPR values
-  const float su0 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, ru0)));
-  const float su1 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, ru1)));
-  const float sv0 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, rv0)));
-  const float sv1 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, rv1)));
   float4 nxt = srect[0];
   for (int sc = 0; sc < nsup; ++sc) {
     const float4 sr = nxt;  // next super rectangle is in flight while this one is tested
@@ -574,34 +577,32 @@ __global__ __launch_bounds__(256) void k_cast_parallel_culled(
       const float4 cr = crect[cl];  // wave-uniform address
       if (su1 < cr.x || su0 > cr.y || sv1 < cr.z || sv0 > cr.w) continue;
       const int s1 = (cl + 1) * kCluster < T ? (cl + 1) * kCluster : T;
-      for (int s = cl * kCluster; s < s1; ++s) sweep(load_front(srec, s), s);
+      for (int s = cl * kCluster; s < s1; ++s) slot(s);
     }
   }
+}
 
-#pragma unroll
-  for (int k = 0; k < RPL; ++k) {
-    int64_t r = block_base + int64_t(k) * 64;
-    if (r >= R) continue;
-    t_hit[r] = best_t[k];
-    prim_id[r] = best_p[k];
-    if (uv) {
-      float u = 0.f, v = 0.f;
-      if (best_p[k] != PYQSM_MISS_PRIM) {
-        const Tri t = load_tri(tri, int(best_p[k]));
-        RayPair one;
-        const int q = k >> 1, h = k & 1;
-        one.ox = splat(ox[q][h]); one.oy = splat(oy[q][h]); one.oz = splat(oz[q][h]);
-        one.dx = splat(d0); one.dy = splat(d1); one.dz = splat(d2);
-        f2 px, py, pz, det, tvx, tvy, tvz, U, V, Tn;
-        mt_front(one, t, px, py, pz, det, tvx, tvy, tvz, U);
-        mt_back(one, t, tvx, tvy, tvz, V, Tn);
-        u = U[0] / det[0];
-        v = V[0] / det[0];
-      }
-      uv[2 * r] = u;
-      uv[2 * r + 1] = v;
-    }
-  }
+template <int NP>
+__global__ __launch_bounds__(256) void k_cast_parallel_culled(
+    const TriRec* __restrict__ tri, const DirRec* __restrict__ srec,
+    const int32_t* __restrict__ sid, const float4* __restrict__ crect,
+    const float4* __restrict__ srect, int T, Basis b,
+    const float* __restrict__ rays, int64_t R, float* __restrict__ t_hit,
+    uint32_t* __restrict__ prim_id, float* __restrict__ uv) {
+  OneDirRays<NP> ry;
+  Best<NP> best;
+  load_tile<NP, true>(rays, R, ry, best);
+  walk_clusters<NP>(
+      R,
+      [&](int k, double& u, double& v) {  // the origin on the plane normal to the direction
+        const double o0 = ry.ox[k >> 1][k & 1], o1 = ry.oy[k >> 1][k & 1], o2 = ry.oz[k >> 1][k & 1];
+        u = o0 * b.ux + o1 * b.uy + o2 * b.uz;
+        v = o0 * b.vx + o1 * b.vy + o2 * b.vz;
+      },
+      crect, srect, T, [&](int s) {
+        test_front<NP, true>(ry, tri, load_front(srec, s), [&] { return uint32_t(sid[s]); }, best);
+      });
+  store_tile<NP, true>(tri, ry, best, R, t_hit, prim_id, uv);
 }
 
 // ---- common-origin batches (the pinhole camera of cast_rays) ----------------------------
@@ -681,15 +682,13 @@ __global__ __launch_bounds__(256) void k_tri_image(const TriRec* __restrict__ tr
                                                    float4* __restrict__ rect /*[T]*/) {
   int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
   if (i >= T) return;
-  const Tri t = load_tri(tri, int(i));
-  const double px[3] = {double(t.v0x), double(t.v0x) + double(t.e1x), double(t.v0x) + double(t.e2x)};
-  const double py[3] = {double(t.v0y), double(t.v0y) + double(t.e1y), double(t.v0y) + double(t.e2y)};
-  const double pz[3] = {double(t.v0z), double(t.v0z) + double(t.e1z), double(t.v0z) + double(t.e2z)};
-  double u0 = 1e300, u1 = -1e300, v0 = 1e300, v1 = -1e300, uc = 0.0, vc = 0.0;
+  const Corners p = corners_of(load_tri(tri, int(i)));
+  Box2 box;
+  double uc = 0.0, vc = 0.0;
   bool front = true;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    const double rx = px[k] - cam.ox, ry = py[k] - cam.oy, rz = pz[k] - cam.oz;
+    const double rx = p.x[k] - cam.ox, ry = p.y[k] - cam.oy, rz = p.z[k] - cam.oz;
     const double x = rx * cam.ax + ry * cam.ay + rz * cam.az;
     const double y = rx * cam.bx + ry * cam.by + rz * cam.bz;
     const double w = rx * cam.nx + ry * cam.ny + rz * cam.nz;
@@ -697,10 +696,7 @@ __global__ __launch_bounds__(256) void k_tri_image(const TriRec* __restrict__ tr
       front = false;
     } else {
       const double u = x / w, v = y / w;
-      u0 = u < u0 ? u : u0;
-      u1 = u > u1 ? u : u1;
-      v0 = v < v0 ? v : v0;
-      v1 = v > v1 ? v : v1;
+      box.add(u, v);
       uc += u;
       vc += v;
     }
@@ -708,8 +704,7 @@ __global__ __launch_bounds__(256) void k_tri_image(const TriRec* __restrict__ tr
   if (front) {
     uc /= 3.0;
     vc /= 3.0;
-    rect[i] = make_float4(__double2float_rd(u0), __double2float_ru(u1), __double2float_rd(v0),
-                          __double2float_ru(v1));
+    rect[i] = box.outward();
   } else {
     uc = vc = 0.0;
     rect[i] = make_float4(-__builtin_inff(), __builtin_inff(), -__builtin_inff(), __builtin_inff());
@@ -719,135 +714,29 @@ __global__ __launch_bounds__(256) void k_tri_image(const TriRec* __restrict__ tr
   cen[3 * i + 2] = 0.0;
 }
 
-// sorted original ids and one grown rectangle per cluster
-__global__ __launch_bounds__(256) void k_clusters_image(int T, const int32_t* __restrict__ order,
-                                                        const float4* __restrict__ rect,
-                                                        float margin, int32_t* __restrict__ sid,
-                                                        float4* __restrict__ crect) {
-  const int cl = blockIdx.x * 256 + threadIdx.x;
-  const int nclus = (T + kCluster - 1) / kCluster;
-  if (cl >= nclus) return;
-  float u0 = __builtin_inff(), u1 = -__builtin_inff(), v0 = __builtin_inff(), v1 = -__builtin_inff();
-  for (int s = cl * kCluster; s < (cl + 1) * kCluster && s < T; ++s) {
-    const int o = order[s];
-    sid[s] = o;
-    const float4 q = rect[o];
-    u0 = fminf(u0, q.x);
-    u1 = fmaxf(u1, q.y);
-    v0 = fminf(v0, q.z);
-    v1 = fmaxf(v1, q.w);
-  }
-  crect[cl] = make_float4(u0 - margin, u1 + margin, v0 - margin, v1 + margin);
-}
-
 template <int NP>
 __global__ __launch_bounds__(256) void k_cast_pinhole_culled(
     const TriRec* __restrict__ tri, const int32_t* __restrict__ sid,
     const float4* __restrict__ crect, const float4* __restrict__ srect, int T, Camera cam,
     const float* __restrict__ rays, int64_t R, float* __restrict__ t_hit,
     uint32_t* __restrict__ prim_id, float* __restrict__ uv) {
-  constexpr int RPL = 2 * NP;
-  // a wave owns 64*RPL CONSECUTIVE rays (a piece of an image row): a small image rectangle
-  const int64_t block_base =
-      int64_t(blockIdx.x) * (256 * RPL) + int64_t(threadIdx.x >> 6) * (64 * RPL) + (threadIdx.x & 63);
-  RayPair rp[NP];
-  float best_t[RPL];
-  uint32_t best_p[RPL];
-  double umin = 1e300, umax = -1e300, vmin = 1e300, vmax = -1e300;
-#pragma unroll
-  for (int k = 0; k < RPL; ++k) {
-    int64_t r = block_base + int64_t(k) * 64;
-    float o0 = 0.f, o1 = 0.f, o2 = 0.f, d0 = 0.f, d1 = 0.f, d2 = 0.f;
-    if (r < R) {
-      const float* p = rays + 6 * r;
-      o0 = p[0]; o1 = p[1]; o2 = p[2]; d0 = p[3]; d1 = p[4]; d2 = p[5];
-      const double w = double(d0) * cam.nx + double(d1) * cam.ny + double(d2) * cam.nz;
-      const double u = (double(d0) * cam.ax + double(d1) * cam.ay + double(d2) * cam.az) / w;
-      const double v = (double(d0) * cam.bx + double(d1) * cam.by + double(d2) * cam.bz) / w;
-      umin = u < umin ? u : umin;
-      umax = u > umax ? u : umax;
-      vmin = v < vmin ? v : vmin;
-      vmax = v > vmax ? v : vmax;
-    }
-    rp[k >> 1].ox[k & 1] = o0; rp[k >> 1].oy[k & 1] = o1; rp[k >> 1].oz[k & 1] = o2;
-    rp[k >> 1].dx[k & 1] = d0; rp[k >> 1].dy[k & 1] = d1; rp[k >> 1].dz[k & 1] = d2;
-    best_t[k] = __builtin_inff();
-    best_p[k] = PYQSM_MISS_PRIM;
-  }
-  const float ru0 = wave_min_f(__double2float_rd(umin)), ru1 = wave_max_f(__double2float_ru(umax));
-  const float rv0 = wave_min_f(__double2float_rd(vmin)), rv1 = wave_max_f(__double2float_ru(vmax));
-
-  auto sweep = [&](const Tri t, const uint32_t id) {
-#pragma unroll
-    for (int q = 0; q < NP; ++q) {
-      f2 px, py, pz, det, tvx, tvy, tvz, U;
-      mt_front(rp[q], t, px, py, pz, det, tvx, tvy, tvz, U);
-      const f2 key = alive_key(det, U);
-      bool alive = u_alive(key[0], det[0]) || u_alive(key[1], det[1]);
-      if (__builtin_amdgcn_ballot_w64(alive) != 0) {
-        f2 V, Tn;
-        mt_back(rp[q], t, tvx, tvy, tvz, V, Tn);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          if (is_hit(det[h], U[h], V[h], Tn[h])) {
-            float tt = Tn[h] / det[h];
-            // same winner as the in-order sweep: smallest t, then smallest triangle id
-            if (tt < best_t[2 * q + h] || (tt == best_t[2 * q + h] && id < best_p[2 * q + h])) {
-              best_t[2 * q + h] = tt;
-              best_p[2 * q + h] = id;
-            }
-          }
-        }
-      }
-    }
-  };
-  const int nclus = (T + kCluster - 1) / kCluster;
-  const int nsup = (nclus + kSuper - 1) / kSuper;
-  const float su0 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, ru0)));
-  const float su1 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, ru1)));
-  const float sv0 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, rv0)));
-  const float sv1 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, rv1)));
-  float4 nxt = srect[0];
-  for (int sc = 0; sc < nsup; ++sc) {
-    const float4 sr = nxt;
-    nxt = srect[sc + 1 < nsup ? sc + 1 : sc];
-    if (su1 < sr.x || su0 > sr.y || sv1 < sr.z || sv0 > sr.w) continue;
-    const int c1 = (sc + 1) * kSuper < nclus ? (sc + 1) * kSuper : nclus;
-    for (int cl = sc * kSuper; cl < c1; ++cl) {
-      const float4 cr = crect[cl];  // wave-uniform address
-      if (su1 < cr.x || su0 > cr.y || sv1 < cr.z || sv0 > cr.w) continue;
-      const int s1 = (cl + 1) * kCluster < T ? (cl + 1) * kCluster : T;
-      for (int s = cl * kCluster; s < s1; ++s) {
+  AnyRays<NP> ry;
+  Best<NP> best;
+  load_tile<NP, true>(rays, R, ry, best);
+  walk_clusters<NP>(
+      R,
+      [&](int k, double& u, double& v) {  // the direction on the image plane (a piece of a row)
+        const RayPair& p = ry.rp[k >> 1];
+        const double d0 = p.dx[k & 1], d1 = p.dy[k & 1], d2 = p.dz[k & 1];
+        const double w = d0 * cam.nx + d1 * cam.ny + d2 * cam.nz;
+        u = (d0 * cam.ax + d1 * cam.ay + d2 * cam.az) / w;
+        v = (d0 * cam.bx + d1 * cam.by + d2 * cam.bz) / w;
+      },
+      crect, srect, T, [&](int s) {
         const int id = __builtin_amdgcn_readfirstlane(sid[s]);
-        sweep(load_tri(tri, id), uint32_t(id));
-      }
-    }
-  }
-
-#pragma unroll
-  for (int k = 0; k < RPL; ++k) {
-    int64_t r = block_base + int64_t(k) * 64;
-    if (r >= R) continue;
-    t_hit[r] = best_t[k];
-    prim_id[r] = best_p[k];
-    if (uv) {
-      float u = 0.f, v = 0.f;
-      if (best_p[k] != PYQSM_MISS_PRIM) {
-        const Tri t = load_tri(tri, int(best_p[k]));
-        RayPair one;
-        const int q = k >> 1, h = k & 1;
-        one.ox = splat(rp[q].ox[h]); one.oy = splat(rp[q].oy[h]); one.oz = splat(rp[q].oz[h]);
-        one.dx = splat(rp[q].dx[h]); one.dy = splat(rp[q].dy[h]); one.dz = splat(rp[q].dz[h]);
-        f2 px, py, pz, det, tvx, tvy, tvz, U, V, Tn;
-        mt_front(one, t, px, py, pz, det, tvx, tvy, tvz, U);
-        mt_back(one, t, tvx, tvy, tvz, V, Tn);
-        u = U[0] / det[0];
-        v = V[0] / det[0];
-      }
-      uv[2 * r] = u;
-      uv[2 * r + 1] = v;
-    }
-  }
+        test_tri<NP, true>(ry, load_tri(tri, id), uint32_t(id), best);
+      });
+  store_tile<NP, true>(tri, ry, best, R, t_hit, prim_id, uv);
 }
 
 // Crossing counts and (optionally) hit records: one ray per lane, all triangles.
@@ -861,14 +750,10 @@ __global__ __launch_bounds__(256) void k_all_hits(const TriRec* __restrict__ tri
                                                   uint32_t* __restrict__ prim_ids,
                                                   float* __restrict__ ts, float* __restrict__ uv) {
   int64_t r = int64_t(blockIdx.x) * 256 + threadIdx.x;
-  RayPair rp;
-  float o0 = 0.f, o1 = 0.f, o2 = 0.f, d0 = 0.f, d1 = 0.f, d2 = 0.f;
-  if (r < R) {
-    const float* p = rays + 6 * r;
-    o0 = p[0]; o1 = p[1]; o2 = p[2]; d0 = p[3]; d1 = p[4]; d2 = p[5];
-  }
-  rp.ox = splat(o0); rp.oy = splat(o1); rp.oz = splat(o2);
-  rp.dx = splat(d0); rp.dy = splat(d1); rp.dz = splat(d2);
+  float o0, o1, o2, d0, d1, d2;
+  load_ray(rays, r, R, 0, o0, o1, o2);
+  load_ray(rays, r, R, 1, d0, d1, d2);
+  const RayPair rp = splat_ray(o0, o1, o2, d0, d1, d2);
   int32_t n = 0;
   int64_t base = (MODE == 1 && r < R) ? offsets[r] : 0;
   Tri nxt = load_tri(tri, 0);
@@ -936,6 +821,95 @@ __global__ void k_fill_miss(int64_t R, float* __restrict__ t_hit, uint32_t* __re
   if (uv) uv[2 * r] = uv[2 * r + 1] = 0.f;
 }
 
+// launch(n, grid) with n an integral_constant: the instantiation for np ray pairs per lane.
+// Six pairs exist for the kernel that says WIDEST = 6 (the brute-force one-direction sweep);
+// the others take four then (the culled kernels are not VALU bound: smaller waves' rectangles
+// win).
+template <int WIDEST, class LAUNCH>
+static int launch_np(int np, int64_t R, LAUNCH launch) {
+  if (np > WIDEST) np = WIDEST;
+  const dim3 grid(ceil_div(R, 256 * 2 * np));
+  if (np == WIDEST)
+    launch(std::integral_constant<int, WIDEST>{}, grid);
+  else if (np == 4)
+    launch(std::integral_constant<int, 4>{}, grid);
+  else if (np == 2)
+    launch(std::integral_constant<int, 2>{}, grid);
+  else
+    launch(std::integral_constant<int, 1>{}, grid);
+  PQ_HIP(hipGetLastError());
+  return 0;
+}
+
+static double norm3(const double a[3]) { return std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]); }
+static void cross3(const double a[3], const double b[3], double out[3]) {
+  out[0] = a[1] * b[2] - a[2] * b[1];
+  out[1] = a[2] * b[0] - a[0] * b[2];
+  out[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// Unit axes a, b = n x a of the plane normal to the unit vector n. a runs along s (made normal
+// to n) when what is left of s is longer than `tiny`; along any vector normal to n otherwise.
+static void plane_axes(const double n[3], const double s[3], double tiny, double a[3], double b[3]) {
+  const double along = s[0] * n[0] + s[1] * n[1] + s[2] * n[2];
+  for (int k = 0; k < 3; ++k) a[k] = s[k] - along * n[k];
+  double an = norm3(a);
+  if (!(an > tiny)) {
+    double h[3] = {0, 0, 0};
+    const double ax = std::fabs(n[0]), ay = std::fabs(n[1]), az = std::fabs(n[2]);
+    h[ax <= ay && ax <= az ? 0 : (ay <= az ? 1 : 2)] = 1.0;
+    cross3(n, h, a);
+    an = norm3(a);
+  }
+  for (int k = 0; k < 3; ++k) a[k] /= an;
+  cross3(n, a, b);
+}
+
+struct Cull {  // what the culled sweeps read
+  float4 *crect = nullptr, *srect = nullptr;
+  int32_t* sid = nullptr;
+  DirRec* srec = nullptr;  // one-direction batches only
+};
+
+// Sorts the triangles by the cell of their centroid on the culling plane and writes the cluster
+// and super rectangles. project(cen, rect) launches the kernel that puts every triangle's
+// centroid and rectangle on the plane; sort_box (min xyz, max xyz) is the box to sort in, the
+// centroids' own when null; dir_rays asks for the sorted front records of ray 0's direction.
+template <class PROJECT>
+static int cull_setup(Ctx* c, const TriRec* tri, int64_t T, const float* dir_rays,
+                      const double* sort_box, PROJECT project, Cull* cu) {
+  double* cen = nullptr;
+  float4* rect = nullptr;
+  const int nclus = int((T + kCluster - 1) / kCluster);
+  const int nsup = (nclus + kSuper - 1) / kSuper;
+  PQ_TRY(c->arena.get(size_t(T) * 3, &cen));
+  PQ_TRY(c->arena.get(size_t(T), &rect));
+  PQ_TRY(c->arena.get(size_t(nclus), &cu->crect));
+  PQ_TRY(c->arena.get(size_t(nsup), &cu->srect));
+  if (dir_rays) PQ_TRY(c->arena.get(size_t(T), &cu->srec));
+  PQ_TRY(c->arena.get(size_t(T), &cu->sid));
+  project(cen, rect);
+  PQ_HIP(hipGetLastError());
+  double box[6];
+  if (sort_box) {
+    for (int k = 0; k < 6; ++k) box[k] = sort_box[k];
+  } else {
+    PQ_TRY(cloud_bbox(c, cen, T, box, box + 3));
+  }
+  double ext = std::max(box[3] - box[0], box[4] - box[1]);
+  if (!(ext > 0)) ext = 1.0;
+  DevGrid g;
+  PQ_TRY(build_grid(c, cen, T, ext / 1024.0, int64_t(1) << 22, &g, box));
+  const float margin = float(1e-4 * ext + 1e-30);
+  hipLaunchKernelGGL(dir_rays ? k_clusters<true> : k_clusters<false>, dim3(ceil_div(nclus, 256)),
+                     dim3(256), 0, c->stream, tri, int(T), dir_rays, g.order, rect, margin, cu->srec,
+                     cu->sid, cu->crect);
+  hipLaunchKernelGGL(k_super_rects, dim3(ceil_div(nsup, 256)), dim3(256), 0, c->stream, nclus,
+                     cu->crect, cu->srect);
+  PQ_HIP(hipGetLastError());
+  return 0;
+}
+
 static int launch_cast(Ctx* c, const TriRec* tri, int64_t T, const float* rays, int64_t R,
                        float* t_hit, uint32_t* prim, float* uv) {
   if (R == 0) return 0;
@@ -966,10 +940,9 @@ static int launch_cast(Ctx* c, const TriRec* tri, int64_t T, const float* rays, 
     if (v == 1 || v == 2 || v == 4 || v == 6) np = v;
   }
   const dim3 block(256);
-  auto grid_for = [&](int npv) { return dim3(ceil_div(R, 256 * 2 * npv)); };
   const char* cull_env = getenv("PYQSM_RAY_CULL");
-  const bool cull = !(cull_env && cull_env[0] == '0');
-  if (!varied && cull && T >= 4 * kCluster) {
+  const bool cull = !(cull_env && cull_env[0] == '0') && T >= 4 * kCluster;
+  if (!varied && cull) {
     // ---- sort triangles on the plane normal to d, build clusters, culled sweep ------
     float hd[3];
     PQ_TRY(fetch(c, hd, rays + 3, 3));
@@ -977,74 +950,28 @@ static int launch_cast(Ctx* c, const TriRec* tri, int64_t T, const float* rays, 
     if (dn > 0.0 && std::isfinite(dn)) {
       const double d[3] = {hd[0] / dn, hd[1] / dn, hd[2] / dn};
       // first plane axis: the direction in which consecutive ray origins advance (ray
-      // grids are stored row by row, so rows become thin rectangles); any vector
-      // normal to d otherwise
-      double u[3] = {0, 0, 0}, un = 0.0;
+      // grids are stored row by row, so rows become thin rectangles)
+      double s0[3] = {0, 0, 0}, u[3], v[3];
       if (R >= 2) {
         float ho[12];
         PQ_TRY(fetch(c, ho, rays, 12));
-        const double s0[3] = {double(ho[6]) - ho[0], double(ho[7]) - ho[1], double(ho[8]) - ho[2]};
-        const double along = s0[0] * d[0] + s0[1] * d[1] + s0[2] * d[2];
-        for (int a = 0; a < 3; ++a) u[a] = s0[a] - along * d[a];
-        un = std::sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+        for (int k = 0; k < 3; ++k) s0[k] = double(ho[6 + k]) - ho[k];
       }
-      if (!(un > 1e-12 * (1.0 + std::fabs(double(hd[0])) + std::fabs(double(hd[1]))))) {
-        double h[3] = {0, 0, 0};
-        const double ax = std::fabs(d[0]), ay = std::fabs(d[1]), az = std::fabs(d[2]);
-        h[ax <= ay && ax <= az ? 0 : (ay <= az ? 1 : 2)] = 1.0;
-        u[0] = d[1] * h[2] - d[2] * h[1];
-        u[1] = d[2] * h[0] - d[0] * h[2];
-        u[2] = d[0] * h[1] - d[1] * h[0];
-        un = std::sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-      }
-      for (double& q : u) q /= un;
-      const double v[3] = {d[1] * u[2] - d[2] * u[1], d[2] * u[0] - d[0] * u[2],
-                           d[0] * u[1] - d[1] * u[0]};
+      plane_axes(d, s0, 1e-12 * (1.0 + std::fabs(double(hd[0])) + std::fabs(double(hd[1]))), u, v);
       const Basis bs{u[0], u[1], u[2], v[0], v[1], v[2]};
-      double* cen = nullptr;
-      float4 *rect = nullptr, *crect = nullptr, *srect = nullptr;
-      DirRec* srec = nullptr;
-      int32_t* sid = nullptr;
-      const int nclus = int((T + kCluster - 1) / kCluster);
-      PQ_TRY(c->arena.get(size_t(T) * 3, &cen));
-      PQ_TRY(c->arena.get(size_t(T), &rect));
-      PQ_TRY(c->arena.get(size_t(nclus), &crect));
-      const int nsup = (nclus + kSuper - 1) / kSuper;
-      PQ_TRY(c->arena.get(size_t(nsup), &srect));
-      PQ_TRY(c->arena.get(size_t(T), &srec));
-      PQ_TRY(c->arena.get(size_t(T), &sid));
-      hipLaunchKernelGGL(k_tri_uv, dim3(ceil_div(T, 256)), dim3(256), 0, c->stream, tri, T, bs, cen,
-                         rect);
-      PQ_HIP(hipGetLastError());
-      double mn[3], mx[3];
-      PQ_TRY(cloud_bbox(c, cen, T, mn, mx));
-      double ext = std::max(mx[0] - mn[0], mx[1] - mn[1]);
-      if (!(ext > 0)) ext = 1.0;
-      double box[6] = {mn[0], mn[1], mn[2], mx[0], mx[1], mx[2]};
-      DevGrid g;
-      PQ_TRY(build_grid(c, cen, T, ext / 1024.0, int64_t(1) << 22, &g, box));
-      const float margin = float(1e-4 * ext + 1e-30);
-      hipLaunchKernelGGL(k_clusters, dim3(ceil_div(nclus, 256)), dim3(256), 0, c->stream, tri, int(T),
-                         rays, g.order, rect, margin, srec, sid, crect);
-      hipLaunchKernelGGL(k_super_rects, dim3(ceil_div(nsup, 256)), dim3(256), 0, c->stream, nclus,
-                         crect, srect);
-      PQ_HIP(hipGetLastError());
+      Cull cu;
+      PQ_TRY(cull_setup(c, tri, T, rays, nullptr, [&](double* cen, float4* rect) {
+        hipLaunchKernelGGL(k_tri_uv, dim3(ceil_div(T, 256)), dim3(256), 0, c->stream, tri, T, bs, cen,
+                           rect);
+      }, &cu));
       ProfScope ps(c, "cast_rays_culled");
-      if (np == 6) np = 4;  // the culled kernel is not VALU bound: smaller waves' rectangles win
-      if (np == 4)
-        hipLaunchKernelGGL(k_cast_parallel_culled<4>, grid_for(4), block, 0, c->stream, tri, srec, sid, crect,
-                           srect, int(T), bs, rays, R, t_hit, prim, uv);
-      else if (np == 2)
-        hipLaunchKernelGGL(k_cast_parallel_culled<2>, grid_for(2), block, 0, c->stream, tri, srec, sid, crect,
-                           srect, int(T), bs, rays, R, t_hit, prim, uv);
-      else
-        hipLaunchKernelGGL(k_cast_parallel_culled<1>, grid_for(1), block, 0, c->stream, tri, srec, sid, crect,
-                           srect, int(T), bs, rays, R, t_hit, prim, uv);
-      PQ_HIP(hipGetLastError());
-      return 0;
+      return launch_np<4>(np, R, [&](auto n, dim3 grid) {
+        hipLaunchKernelGGL(k_cast_parallel_culled<decltype(n)::value>, grid, block, 0, c->stream, tri,
+                           cu.srec, cu.sid, cu.crect, cu.srect, int(T), bs, rays, R, t_hit, prim, uv);
+      });
     }
   }
-  if (varied && one_origin && cull && T >= 4 * kCluster && R >= 2) {
+  if (varied && one_origin && cull && R >= 2) {
     // ---- common origin: project onto the image plane, sort, cluster, culled sweep ------
     double* d_sum = nullptr;
     PQ_TRY(c->arena.get(3, &d_sum));
@@ -1056,35 +983,18 @@ static int launch_cast(Ctx* c, const TriRec* tri, int64_t T, const float* rays, 
     PQ_TRY(download(c, hs, d_sum, 3));
     PQ_TRY(download(c, ho, rays, 12));
     PQ_HIP(hipStreamSynchronize(c->stream));
-    const double nn = std::sqrt(hs[0] * hs[0] + hs[1] * hs[1] + hs[2] * hs[2]);
+    const double nn = norm3(hs);
     if (nn > 1e-3 * double(R) && std::isfinite(nn)) {
       const double n[3] = {hs[0] / nn, hs[1] / nn, hs[2] / nn};
-      // first image axis: the way consecutive rays turn (pixel rows become thin rectangles)
-      double a[3], an = 0.0;
-      {
-        // difference of the two rays' points on the plane n.x = 1 (lies in that plane whatever
-        // the lengths of the direction vectors are)
-        const double w0 = ho[3] * n[0] + ho[4] * n[1] + ho[5] * n[2];
-        const double w1 = ho[9] * n[0] + ho[10] * n[1] + ho[11] * n[2];
-        double s0[3] = {0, 0, 0};
-        if (w0 > 0 && w1 > 0)
-          for (int k = 0; k < 3; ++k) s0[k] = double(ho[9 + k]) / w1 - double(ho[3 + k]) / w0;
-        const double along = s0[0] * n[0] + s0[1] * n[1] + s0[2] * n[2];
-        for (int k = 0; k < 3; ++k) a[k] = s0[k] - along * n[k];
-        an = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
-      }
-      if (!(an > 1e-12)) {
-        double h[3] = {0, 0, 0};
-        const double ax = std::fabs(n[0]), ay = std::fabs(n[1]), az = std::fabs(n[2]);
-        h[ax <= ay && ax <= az ? 0 : (ay <= az ? 1 : 2)] = 1.0;
-        a[0] = n[1] * h[2] - n[2] * h[1];
-        a[1] = n[2] * h[0] - n[0] * h[2];
-        a[2] = n[0] * h[1] - n[1] * h[0];
-        an = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
-      }
-      for (double& q : a) q /= an;
-      const double b[3] = {n[1] * a[2] - n[2] * a[1], n[2] * a[0] - n[0] * a[2],
-                           n[0] * a[1] - n[1] * a[0]};
+      // first image axis: the way consecutive rays turn (pixel rows become thin rectangles):
+      // the difference of the two rays' points on the plane n.x = 1 (lies in that plane whatever
+      // the lengths of the direction vectors are)
+      const double w0 = ho[3] * n[0] + ho[4] * n[1] + ho[5] * n[2];
+      const double w1 = ho[9] * n[0] + ho[10] * n[1] + ho[11] * n[2];
+      double s0[3] = {0, 0, 0}, a[3], b[3];
+      if (w0 > 0 && w1 > 0)
+        for (int k = 0; k < 3; ++k) s0[k] = double(ho[9 + k]) / w1 - double(ho[3 + k]) / w0;
+      plane_axes(n, s0, 1e-12, a, b);
       const Camera cam{ho[0], ho[1], ho[2], a[0], a[1], a[2], b[0], b[1], b[2], n[0], n[1], n[2]};
       double* img = nullptr;
       int* d_bad = nullptr;
@@ -1099,43 +1009,17 @@ static int launch_cast(Ctx* c, const TriRec* tri, int64_t T, const float* rays, 
       int bad = 0;
       PQ_TRY(fetch(c, &bad, d_bad));
       if (!bad) {
-        double ext = std::max(mx[0] - mn[0], mx[1] - mn[1]);
-        if (!(ext > 0)) ext = 1.0;
-        double* cen = nullptr;
-        float4 *rect = nullptr, *crect = nullptr, *srect = nullptr;
-        int32_t* sid = nullptr;
-        const int nclus = int((T + kCluster - 1) / kCluster);
-        const int nsup = (nclus + kSuper - 1) / kSuper;
-        PQ_TRY(c->arena.get(size_t(T) * 3, &cen));
-        PQ_TRY(c->arena.get(size_t(T), &rect));
-        PQ_TRY(c->arena.get(size_t(nclus), &crect));
-        PQ_TRY(c->arena.get(size_t(nsup), &srect));
-        PQ_TRY(c->arena.get(size_t(T), &sid));
-        hipLaunchKernelGGL(k_tri_image, dim3(ceil_div(T, 256)), dim3(256), 0, c->stream, tri, T, cam,
-                           mn[0], mx[0], mn[1], mx[1], cen, rect);
-        PQ_HIP(hipGetLastError());
-        double box[6] = {mn[0], mn[1], 0.0, mx[0], mx[1], 0.0};
-        DevGrid g;
-        PQ_TRY(build_grid(c, cen, T, ext / 1024.0, int64_t(1) << 22, &g, box));
-        const float margin = float(1e-4 * ext + 1e-30);
-        hipLaunchKernelGGL(k_clusters_image, dim3(ceil_div(nclus, 256)), dim3(256), 0, c->stream, int(T),
-                           g.order, rect, margin, sid, crect);
-        hipLaunchKernelGGL(k_super_rects, dim3(ceil_div(nsup, 256)), dim3(256), 0, c->stream, nclus,
-                           crect, srect);
-        PQ_HIP(hipGetLastError());
+        const double box[6] = {mn[0], mn[1], 0.0, mx[0], mx[1], 0.0};  // the rays' image box
+        Cull cu;
+        PQ_TRY(cull_setup(c, tri, T, nullptr, box, [&](double* cen, float4* rect) {
+          hipLaunchKernelGGL(k_tri_image, dim3(ceil_div(T, 256)), dim3(256), 0, c->stream, tri, T, cam,
+                             mn[0], mx[0], mn[1], mx[1], cen, rect);
+        }, &cu));
         ProfScope ps(c, "cast_rays_culled");
-        if (np == 6) np = 4;
-        if (np == 4)
-          hipLaunchKernelGGL(k_cast_pinhole_culled<4>, grid_for(4), block, 0, c->stream, tri, sid, crect,
-                             srect, int(T), cam, rays, R, t_hit, prim, uv);
-        else if (np == 2)
-          hipLaunchKernelGGL(k_cast_pinhole_culled<2>, grid_for(2), block, 0, c->stream, tri, sid, crect,
-                             srect, int(T), cam, rays, R, t_hit, prim, uv);
-        else
-          hipLaunchKernelGGL(k_cast_pinhole_culled<1>, grid_for(1), block, 0, c->stream, tri, sid, crect,
-                             srect, int(T), cam, rays, R, t_hit, prim, uv);
-        PQ_HIP(hipGetLastError());
-        return 0;
+        return launch_np<4>(np, R, [&](auto n, dim3 grid) {
+          hipLaunchKernelGGL(k_cast_pinhole_culled<decltype(n)::value>, grid, block, 0, c->stream, tri,
+                             cu.sid, cu.crect, cu.srect, int(T), cam, rays, R, t_hit, prim, uv);
+        });
       }
     }
   }
@@ -1145,34 +1029,16 @@ static int launch_cast(Ctx* c, const TriRec* tri, int64_t T, const float* rays, 
     hipLaunchKernelGGL(k_dir_records, dim3(ceil_div(T, 256)), dim3(256), 0, c->stream, tri, T, rays,
                        rec);
     ProfScope ps(c, "cast_rays");
-    if (np == 6)
-      hipLaunchKernelGGL(k_cast_parallel<6>, grid_for(6), block, 0, c->stream, tri, rec, int(T), rays, R,
-                         t_hit, prim, uv);
-    else if (np == 4)
-      hipLaunchKernelGGL(k_cast_parallel<4>, grid_for(4), block, 0, c->stream, tri, rec, int(T), rays, R,
-                         t_hit, prim, uv);
-    else if (np == 2)
-      hipLaunchKernelGGL(k_cast_parallel<2>, grid_for(2), block, 0, c->stream, tri, rec, int(T), rays, R,
-                         t_hit, prim, uv);
-    else
-      hipLaunchKernelGGL(k_cast_parallel<1>, grid_for(1), block, 0, c->stream, tri, rec, int(T), rays, R,
-                         t_hit, prim, uv);
-    PQ_HIP(hipGetLastError());
-    return 0;
+    return launch_np<6>(np, R, [&](auto n, dim3 grid) {
+      hipLaunchKernelGGL(k_cast_parallel<decltype(n)::value>, grid, block, 0, c->stream, tri, rec,
+                         int(T), rays, R, t_hit, prim, uv);
+    });
   }
   ProfScope ps(c, "cast_rays");
-  if (np == 6) np = 4;
-  if (np == 4)
-    hipLaunchKernelGGL(k_cast_rays<4>, grid_for(4), block, 0, c->stream, tri, int(T), rays, R, t_hit, prim,
-                       uv);
-  else if (np == 2)
-    hipLaunchKernelGGL(k_cast_rays<2>, grid_for(2), block, 0, c->stream, tri, int(T), rays, R, t_hit, prim,
-                       uv);
-  else
-    hipLaunchKernelGGL(k_cast_rays<1>, grid_for(1), block, 0, c->stream, tri, int(T), rays, R, t_hit, prim,
-                       uv);
-  PQ_HIP(hipGetLastError());
-  return 0;
+  return launch_np<4>(np, R, [&](auto n, dim3 grid) {
+    hipLaunchKernelGGL(k_cast_rays<decltype(n)::value>, grid, block, 0, c->stream, tri, int(T), rays, R,
+                       t_hit, prim, uv);
+  });
 }
 
 static int expand(Ctx* c, const float* verts, int64_t V, const int32_t* tris, int64_t T,

@@ -129,6 +129,78 @@ def test_closest_of_stack_and_tie_break(gpu):
     assert list(p) == [2, 3]                           # lowest triangle id among the tie
 
 
+_WIDTH_CASES = {}
+
+
+def _width_case(family, n_tris, npairs, doubled=False):
+    """Mesh, rays and the oracle's answer of one (family, mesh, width) case, computed once and
+    shared by the cull-on and cull-off runs. R = 2*np*256 + 65 rays: one full block of the
+    np-pair kernel, one full wave and one lane (the pinhole image has 2173 rays; longer batches
+    take all of it, which still ends in a partial block)."""
+    key = (family, n_tris, npairs, doubled)
+    if key not in _WIDTH_CASES:
+        from pyqsm_amd.viz.ray_casting import create_rays_pinhole
+        verts, tris = synth.canopy_mesh(n_tris, seed=2, side=0.5)
+        if doubled:   # every triangle twice, walk order unlike id order: every hit is an exact tie
+            tris = np.concatenate([tris, tris])[np.random.default_rng(7).permutation(2 * n_tris)]
+        n_rays = 2 * npairs * 256 + 65
+        lo, hi = verts.min(0), verts.max(0)
+        if family == "sun":
+            rays = synth.sun_rays(verts, n_rays)
+        elif family == "pinhole":
+            c = 0.5 * (lo.astype(np.float64) + hi)
+            rays = create_rays_pinhole(40.0, c, c + np.array([0.0, 0.0, 10.0]), (0, 1, -1), 53,
+                                       41).reshape(-1, 6)[:n_rays]
+        else:
+            rays = _random_rays(np.random.default_rng(n_rays), n_rays, lo, hi)
+        rays = np.ascontiguousarray(rays)
+        _WIDTH_CASES[key] = (verts, tris, rays, oracle.cast_rays(verts, tris, rays))
+    return _WIDTH_CASES[key]
+
+
+@pytest.mark.parametrize("n_tris", [71, 535])          # 4 clusters of 16 and one of 7, odd (the
+                                                       # in-order loop ends in its tail); 34
+                                                       # clusters: a second, partial super-cluster
+@pytest.mark.parametrize("npairs", [1, 2, 4, 6])
+@pytest.mark.parametrize("cull", ["1", "0"])
+@pytest.mark.parametrize("family", ["sun", "pinhole", "general"])
+def test_every_width_of_every_sweep(gpu, monkeypatch, family, cull, npairs, n_tris):
+    """Every ray-pairs-per-lane instantiation of every closest-hit kernel at a size just above
+    the cull threshold (64 triangles): one direction with and without culling (the brute-force
+    kernel also at 6 pairs), one origin with culling, and the general kernel (one origin
+    without culling, and unrelated rays), against the oracle bit for bit."""
+    verts, tris, rays, (t0, p0, uv0) = _width_case(family, n_tris, npairs)
+    assert 0.05 < np.isfinite(t0).mean() < 0.95        # hits and misses both matter
+    monkeypatch.setenv("PYQSM_RAY_CULL", cull)
+    monkeypatch.setenv("PYQSM_RAY_NP", str(npairs))
+    t, p, uv = hip.cast_rays(verts, tris, rays, device=gpu)
+    assert np.array_equal(t, t0)
+    assert np.array_equal(p, p0)
+    assert np.array_equal(uv, uv0)
+
+
+@pytest.mark.parametrize("npairs", [1, 4])
+@pytest.mark.parametrize("cull", ["1", "0"])
+@pytest.mark.parametrize("family", ["sun", "pinhole"])
+def test_culled_sweeps_keep_the_lowest_id_of_a_tie(gpu, monkeypatch, family, cull, npairs):
+    """The 71-triangle mesh with every triangle listed twice, shuffled: every hit ties exactly
+    with its twin, and the culled kernels meet the two in plane order, not id order. The winner
+    is the lower id, as in the in-order sweep and the oracle."""
+    verts, tris, rays, (t0, p0, uv0) = _width_case(family, 71, npairs, doubled=True)
+    hit = p0 != 0xFFFFFFFF
+    assert 0.05 < hit.mean() < 0.95
+    monkeypatch.setenv("PYQSM_RAY_CULL", cull)
+    monkeypatch.setenv("PYQSM_RAY_NP", str(npairs))
+    t, p, uv = hip.cast_rays(verts, tris, rays, device=gpu)
+    assert np.array_equal(t, t0)
+    assert np.array_equal(p, p0)
+    assert np.array_equal(uv, uv0)
+    first = {}
+    for i, tri in enumerate(map(tuple, tris)):
+        first.setdefault(tri, i)
+    assert all(first[tuple(tris[i])] == i for i in p[hit])
+
+
 def test_empty_inputs(gpu):
     verts, tris = synth.canopy_mesh(10, seed=0)
     t, p, uv = hip.cast_rays(verts, tris, np.zeros((0, 6), np.float32), device=gpu)
