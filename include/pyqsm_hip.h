@@ -240,7 +240,11 @@ int pyqsm_knn_dev(const double* xyz_dev, int64_t n, int32_t k, int32_t exclude_s
  *   center[3], axis[3], *radius: model of the winning hypothesis (first
  *   hypothesis with a strictly larger inlier count wins)
  *   inliers i64 [n] capacity, ascending; *n_inliers = count; *best = winning row
- *   (-1 and n_inliers = 0 when no hypothesis has an inlier).
+ *   (-1 and n_inliers = 0 when no hypothesis has an inlier; center, axis and radius
+ *   are then left as they were).
+ * One call is a batch of one set (pyqsm_ransac_batch below) and has its limit: more
+ * than 65535 tiles of 1024 points (n > 67 107 840) is refused with PYQSM_ERANGE and a
+ * message before anything is copied, as in the batch, the count and the plane calls.
  */
 int pyqsm_ransac(const double* pts, int64_t n, const int64_t* triples, int64_t H,
                  int32_t shape, double thresh, double center[3], double axis[3],

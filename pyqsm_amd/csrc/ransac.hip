@@ -10,7 +10,13 @@
 //              (plane normal, Rodrigues rotation to z, 2-D circumcentre, back)
 //   k_count    lanes = hypotheses, points staged through LDS in SoA tiles and
 //              read as broadcasts; one atomicAdd per (block, hypothesis)
+//   k_best_seg a block per point set: the first hypothesis with the largest count
 //   k_flags    inlier flags of the winning model -> scan -> ascending indices
+//
+// There is one kernel per stage and one driver, fit_sets: pyqsm_ransac_batch runs it over S point
+// sets stacked in one array, pyqsm_ransac over one set. With several sets (MANY) a k_count block looks
+// its tile up in a list and a k_flags lane bisects for its set; with one set a tile is blockIdx.y,
+// the set is the n points, and none of that is built, uploaded or compiled in.
 //
 // The point-to-model distance follows NumPy's operation order exactly (each
 // product and sum rounded separately, sums left to right, IEEE sqrt), so for a
@@ -25,6 +31,7 @@
 // stays in HBM. tests/plane_restatement.py states the contract in NumPy.
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 #include "common.hpp"
@@ -107,24 +114,29 @@ __device__ Model model_of(const double* __restrict__ pts, int64_t n, int64_t i0,
   return m;
 }
 
-__global__ __launch_bounds__(256) void k_models(const double* __restrict__ pts, int64_t n,
+// The point sets of one launch, on the device: S sets stacked in one array of n points. One set
+// (S == 1) is the n points themselves and has no lists: every pointer is null and nothing reads it.
+struct Sets {
+  int64_t S;
+  const int64_t* seg_start;  // [S + 1], from 0 to n
+  const int32_t* tile_set;   // [tiles] the tiles of kTile points of all sets: the set of each ...
+  const int64_t* tile_base;  // [tiles] ... and its first point
+  int64_t tiles;             // k_count's grid.y
+};
+
+// hypothesis h of set s is thread s * H + h, its triple local to the set
+__global__ __launch_bounds__(256) void k_models(const double* __restrict__ pts, int64_t n, Sets sets,
                                                 const int64_t* __restrict__ triples, int64_t H,
                                                 Model* __restrict__ models) {
-  int64_t h = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
-  if (h >= H) return;
-  models[h] = model_of(pts, n, triples[3 * h], triples[3 * h + 1], triples[3 * h + 2]);
-}
-
-// the same for S point sets stacked in one array: hypothesis h of set s is thread s * H + h
-__global__ __launch_bounds__(256) void k_models_seg(const double* __restrict__ pts,
-                                                    const int64_t* __restrict__ seg_start, int64_t S,
-                                                    const int64_t* __restrict__ triples, int64_t H,
-                                                    Model* __restrict__ models) {
   const int64_t t = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
-  if (t >= S * H) return;
-  const int64_t s = t / H;
-  const int64_t b = seg_start[s];
-  models[t] = model_of(pts + 3 * b, seg_start[s + 1] - b, triples[3 * t], triples[3 * t + 1], triples[3 * t + 2]);
+  if (t >= sets.S * H) return;
+  int64_t b = 0, cnt = n;
+  if (sets.seg_start) {
+    const int64_t s = t / H;
+    b = sets.seg_start[s];
+    cnt = sets.seg_start[s + 1] - b;
+  }
+  models[t] = model_of(pts + 3 * b, cnt, triples[3 * t], triples[3 * t + 1], triples[3 * t + 2]);
 }
 
 // |distance| of one point to one model, NumPy operation order (oracle.ransac_distance).
@@ -151,55 +163,15 @@ __device__ __forceinline__ bool is_inlier(double dist, double thresh) {
 
 static constexpr int kTile = 1024;  // points per LDS tile
 
-template <int SHAPE>
-__global__ __launch_bounds__(256) void k_count(const double* __restrict__ pts, int64_t n,
+// blockIdx.y = a tile of kTile points of one set; models and counts are [S, H]
+template <int SHAPE, bool MANY>
+__global__ __launch_bounds__(256) void k_count(const double* __restrict__ pts, int64_t n, Sets sets,
                                                const Model* __restrict__ models, int64_t H,
                                                double thresh, int32_t* __restrict__ counts) {
   __shared__ double lx[kTile], ly[kTile], lz[kTile];
-  const int64_t base = int64_t(blockIdx.y) * kTile;
-  const int cnt = int(n - base < kTile ? n - base : kTile);
-  for (int i = threadIdx.x; i < cnt; i += 256) {
-    lx[i] = pts[3 * (base + i)];
-    ly[i] = pts[3 * (base + i) + 1];
-    lz[i] = pts[3 * (base + i) + 2];
-  }
-  __syncthreads();
-  const int64_t h = int64_t(blockIdx.x) * 256 + threadIdx.x;
-  if (h >= H) return;
-  const Model m = models[h];
-  if (m.valid == 0.0) return;
-  int32_t c = 0;
-  for (int i = 0; i < cnt; ++i) c += is_inlier<SHAPE>(model_dist<SHAPE>(m, lx[i], ly[i], lz[i]), thresh);
-  if (c) atomicAdd(&counts[h], c);
-}
-
-template <int SHAPE>
-__global__ __launch_bounds__(256) void k_flags(const double* __restrict__ pts, int64_t n,
-                                               const Model* __restrict__ models, int64_t best,
-                                               double thresh, int32_t* __restrict__ flags) {
-  int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
-  if (i > n) return;
-  if (i == n) {
-    flags[n] = 0;
-    return;
-  }
-  const Model m = models[best];
-  flags[i] = is_inlier<SHAPE>(model_dist<SHAPE>(m, pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]), thresh);
-}
-
-// ---- many independent fits in one call (pyqsm_ransac_batch) ---------------------------------
-
-// blockIdx.y = a tile of kTile points of one set (tile_set / tile_base list the tiles of all sets)
-template <int SHAPE>
-__global__ __launch_bounds__(256) void k_count_seg(const double* __restrict__ pts,
-                                                   const int64_t* __restrict__ seg_start,
-                                                   const int32_t* __restrict__ tile_set,
-                                                   const int64_t* __restrict__ tile_base,
-                                                   const Model* __restrict__ models, int64_t H,
-                                                   double thresh, int32_t* __restrict__ counts) {
-  __shared__ double lx[kTile], ly[kTile], lz[kTile];
-  const int s = tile_set[blockIdx.y];
-  const int64_t base = tile_base[blockIdx.y], end = seg_start[s + 1];
+  const int s = MANY ? sets.tile_set[blockIdx.y] : 0;
+  const int64_t base = MANY ? sets.tile_base[blockIdx.y] : int64_t(blockIdx.y) * kTile;
+  const int64_t end = MANY ? sets.seg_start[s + 1] : n;
   const int cnt = int(end - base < kTile ? end - base : kTile);
   for (int i = threadIdx.x; i < cnt; i += 256) {
     lx[i] = pts[3 * (base + i)];
@@ -251,34 +223,46 @@ __global__ __launch_bounds__(256) void k_best_seg(const int32_t* __restrict__ co
   }
 }
 
-template <int SHAPE>
-__global__ __launch_bounds__(256) void k_flags_seg(const double* __restrict__ pts, int64_t n,
-                                                   const int64_t* __restrict__ seg_start, int64_t S,
-                                                   const Model* __restrict__ models, int64_t H,
-                                                   const int64_t* __restrict__ best, double thresh,
-                                                   int32_t* __restrict__ flags, int32_t* __restrict__ set_of) {
+// flags [n + 1]: point i is an inlier of its set's winner (none: 0), flags[n] = 0. The winner of
+// set s is best[s], where k_best_seg left it (-1: none); a plane's is chosen on the host
+// (plane_select) and comes as best0.
+template <int SHAPE, bool MANY>
+__global__ __launch_bounds__(256) void k_flags(const double* __restrict__ pts, int64_t n, Sets sets,
+                                               const Model* __restrict__ models, int64_t H,
+                                               const int64_t* __restrict__ best, int64_t best0, double thresh,
+                                               int32_t* __restrict__ flags, int32_t* __restrict__ set_of) {
   const int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
   if (i > n) return;
   if (i == n) {
     flags[n] = 0;
     return;
   }
-  int64_t lo = 0, hi = S - 1;  // the set of point i: the last s with seg_start[s] <= i
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if (seg_start[mid] <= i) lo = mid; else hi = mid - 1;
+  int64_t lo = 0;
+  if (MANY) {
+    int64_t hi = sets.S - 1;  // the set of point i: the last s with seg_start[s] <= i
+    while (lo < hi) {
+      const int64_t mid = (lo + hi + 1) >> 1;
+      if (sets.seg_start[mid] <= i) lo = mid; else hi = mid - 1;
+    }
+    set_of[i] = int32_t(lo);
   }
-  set_of[i] = int32_t(lo);
-  const int64_t b = best[lo];
+  const int64_t b = SHAPE == 2 ? best0 : best[lo];
   int32_t f = 0;
-  if (b >= 0) {
+  if (SHAPE == 2 || b >= 0) {
     const Model m = models[lo * H + b];
     f = is_inlier<SHAPE>(model_dist<SHAPE>(m, pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]), thresh);
   }
   flags[i] = f;
 }
 
-// inliers as indices local to their set, set by set; the winning models gathered per set
+// What a fit returns per set, in one record so that one copy brings it to the host: the winning
+// hypothesis (-1: none has an inlier), its model (zeros when there is none) and its inlier count.
+struct Winner {
+  Model m;
+  int64_t best, count;
+};
+
+// inliers as indices local to their set, set by set
 __global__ __launch_bounds__(256) void k_compact_seg(int64_t n, const int64_t* __restrict__ seg_start,
                                                      const int32_t* __restrict__ set_of,
                                                      const int32_t* __restrict__ pos, int64_t* __restrict__ out) {
@@ -288,27 +272,58 @@ __global__ __launch_bounds__(256) void k_compact_seg(int64_t n, const int64_t* _
 }
 
 __global__ __launch_bounds__(256) void k_gather_best(int64_t S, const Model* __restrict__ models, int64_t H,
-                                                     const int64_t* __restrict__ best, Model* __restrict__ out) {
+                                                     const int64_t* __restrict__ best,
+                                                     const int32_t* __restrict__ best_cnt, Winner* __restrict__ out) {
   const int64_t s = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
   if (s >= S) return;
-  out[s] = best[s] >= 0 ? models[s * H + best[s]] : Model{0, 0, 0, 0, 0, 0, 0, 0};
+  out[s] = Winner{best[s] >= 0 ? models[s * H + best[s]] : Model{0, 0, 0, 0, 0, 0, 0, 0}, best[s], best_cnt[s]};
 }
 
-static int count_on_device(Ctx* c, const double* d_pts, int64_t n, const Model* d_models, int64_t H,
-                           int shape, double thresh, int32_t* d_counts) {
-  PQ_HIP(hipMemsetAsync(d_counts, 0, size_t(H) * 4, c->stream));
+static constexpr int64_t kMaxTiles = 65535;  // k_count's grid.y
+
+static Sets one_set(int64_t n) { return Sets{1, nullptr, nullptr, nullptr, ceil_div(n, kTile)}; }
+
+// Every path that counts refuses an input of more tiles before it stages anything.
+static int check_tiles(const char* who, int64_t tiles) {
+  if (tiles > kMaxTiles) return fail(PYQSM_ERANGE, "%s: more than 65535 tiles of 1024 points per call", who);
+  return 0;
+}
+
+// f(SHAPE, MANY) with the run-time pair as compile-time constants: the one place that turns a shape
+// into a template argument. Planes (shape 2) come one set at a time.
+template <class F>
+static void with_kind(int shape, bool many, F f) {
+  using std::false_type;
+  using std::integral_constant;
+  using std::true_type;
+  if (shape == 2) f(integral_constant<int, 2>{}, false_type{});
+  else if (shape == 0) many ? f(integral_constant<int, 0>{}, true_type{}) : f(integral_constant<int, 0>{}, false_type{});
+  else many ? f(integral_constant<int, 1>{}, true_type{}) : f(integral_constant<int, 1>{}, false_type{});
+}
+
+// counts [S, H] of the models [S, H], each over the points of its set
+static int count_on_device(Ctx* c, const double* d_pts, int64_t n, const Sets& sets, const Model* d_models,
+                           int64_t H, int shape, double thresh, int32_t* d_counts) {
+  PQ_HIP(hipMemsetAsync(d_counts, 0, size_t(sets.S * H) * 4, c->stream));
   if (n == 0 || H == 0) return 0;
   ProfScope ps(c, shape == 2 ? "plane_count" : "ransac_count");
-  const dim3 grid(ceil_div(H, 256), ceil_div(n, kTile));
-  if (shape == 0)
-    hipLaunchKernelGGL(k_count<0>, grid, dim3(256), 0, c->stream, d_pts, n, d_models, H, thresh,
-                       d_counts);
-  else if (shape == 2)
-    hipLaunchKernelGGL(k_count<2>, grid, dim3(256), 0, c->stream, d_pts, n, d_models, H, thresh,
-                       d_counts);
-  else
-    hipLaunchKernelGGL(k_count<1>, grid, dim3(256), 0, c->stream, d_pts, n, d_models, H, thresh,
-                       d_counts);
+  const dim3 grid(ceil_div(H, 256), unsigned(sets.tiles));
+  with_kind(shape, sets.S > 1, [&](auto sh, auto many) {
+    hipLaunchKernelGGL((k_count<decltype(sh)::value, decltype(many)::value>), grid, dim3(256), 0, c->stream, d_pts, n,
+                       sets, d_models, H, thresh, d_counts);
+  });
+  PQ_HIP(hipGetLastError());
+  return 0;
+}
+
+// the inlier flags [n + 1] of every set's winner: d_best [S], or for a plane best0
+static int flags_on_device(Ctx* c, const double* d_pts, int64_t n, const Sets& sets, const Model* d_models,
+                           int64_t H, const int64_t* d_best, int64_t best0, int shape, double thresh,
+                           int32_t* d_flags, int32_t* d_set_of) {
+  with_kind(shape, sets.S > 1, [&](auto sh, auto many) {
+    hipLaunchKernelGGL((k_flags<decltype(sh)::value, decltype(many)::value>), dim3(ceil_div(n + 1, 256)), dim3(256), 0,
+                       c->stream, d_pts, n, sets, d_models, H, d_best, best0, thresh, d_flags, d_set_of);
+  });
   PQ_HIP(hipGetLastError());
   return 0;
 }
@@ -318,6 +333,97 @@ static int check_args(const double* pts, int64_t n, int64_t H, int32_t shape) {
   if (shape != 0 && shape != 1) return fail(PYQSM_EINVAL, "shape must be 0 (circle) or 1 (cylinder)");
   if (n > 0 && !pts) return fail(PYQSM_EINVAL, "pts is NULL");
   if (n > 0x7FFFFF00LL) return fail(PYQSM_ERANGE, "more than 2^31 points per call");
+  return 0;
+}
+
+static void put_model(const Model& m, double center[3], double axis[3], double* radius) {
+  center[0] = m.cx; center[1] = m.cy; center[2] = m.cz;
+  axis[0] = m.ax; axis[1] = m.ay; axis[2] = m.az;
+  *radius = m.r;
+}
+
+// The fit of S point sets stacked in d_pts (seg_start on the host, [S + 1] from 0 to n; S == 1: the n
+// points, seg_start unread), H hypotheses per set from d_tri [S, H, 3]: models, counts, the first
+// hypothesis of the largest count per set, its inlier flags, and the inliers as ascending indices
+// local to their set, set by set. win: [S] on the host. Two synchronisations: before the inlier total
+// is known, and for the inliers. Needs n > 0, H > 0 and at most kMaxTiles tiles.
+static int fit_sets(Ctx* c, const double* d_pts, int64_t n, const int64_t* seg_start, int64_t S,
+                    const int64_t* d_tri, int64_t H, int shape, double thresh, Winner* win, int64_t* inliers) {
+  const int64_t SH = S * H;
+  Sets sets = one_set(n);
+  int32_t* d_set_of = nullptr;
+  if (S > 1) {  // the tiles of all sets
+    std::vector<int32_t> h_tile_set;
+    std::vector<int64_t> h_tile_base;
+    for (int64_t s = 0; s < S; ++s)
+      for (int64_t b = seg_start[s]; b < seg_start[s + 1]; b += kTile) {
+        h_tile_set.push_back(int32_t(s));
+        h_tile_base.push_back(b);
+      }
+    int64_t *d_seg, *d_tile_base;
+    int32_t* d_tile_set;
+    PQ_TRY(upload(c, seg_start, size_t(S) + 1, &d_seg));
+    PQ_TRY(upload(c, h_tile_base.data(), h_tile_base.size(), &d_tile_base));
+    PQ_TRY(upload(c, h_tile_set.data(), h_tile_set.size(), &d_tile_set));
+    PQ_TRY(c->arena.get(size_t(n), &d_set_of));
+    sets = Sets{S, d_seg, d_tile_set, d_tile_base, int64_t(h_tile_set.size())};
+  }
+  Model* d_models;
+  Winner* d_win;
+  int64_t *d_best, *d_out;
+  int32_t *d_counts, *d_best_cnt, *d_flags;
+  PQ_TRY(c->arena.get(size_t(SH), &d_models));
+  PQ_TRY(c->arena.get(size_t(SH), &d_counts));
+  PQ_TRY(c->arena.get(size_t(S), &d_best));
+  PQ_TRY(c->arena.get(size_t(S), &d_best_cnt));
+  PQ_TRY(c->arena.get(size_t(S), &d_win));
+  PQ_TRY(c->arena.get(size_t(n) + 1, &d_flags));
+  PQ_TRY(c->arena.get(size_t(n), &d_out));
+  {
+    ProfScope ps(c, "ransac_models");
+    hipLaunchKernelGGL(k_models, dim3(ceil_div(SH, 256)), dim3(256), 0, c->stream, d_pts, n, sets, d_tri, H,
+                       d_models);
+    PQ_HIP(hipGetLastError());
+  }
+  PQ_TRY(count_on_device(c, d_pts, n, sets, d_models, H, shape, thresh, d_counts));
+  {
+    ProfScope ps(c, "ransac_compact");
+    hipLaunchKernelGGL(k_best_seg, dim3(unsigned(S)), dim3(256), 0, c->stream, d_counts, H, d_best, d_best_cnt);
+    PQ_TRY(flags_on_device(c, d_pts, n, sets, d_models, H, d_best, -1, shape, thresh, d_flags, d_set_of));
+    if (S > 1) {
+      PQ_TRY(exclusive_scan_i32(c, d_flags, n + 1));
+      hipLaunchKernelGGL(k_compact_seg, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, n, sets.seg_start, d_set_of,
+                         d_flags, d_out);
+    } else {
+      PQ_TRY(compact_flagged(c, d_flags, n, d_out));
+    }
+    hipLaunchKernelGGL(k_gather_best, dim3(ceil_div(S, 256)), dim3(256), 0, c->stream, S, d_models, H, d_best,
+                       d_best_cnt, d_win);
+    PQ_HIP(hipGetLastError());
+  }
+  PQ_TRY(fetch(c, win, d_win, size_t(S)));
+  int64_t total = 0;  // a winner's count is the number of its flags: the same predicate on the same points
+  for (int64_t s = 0; s < S; ++s) total += win[s].count;
+  if (total > 0) PQ_TRY(fetch(c, inliers, d_out, size_t(total)));
+  return 0;
+}
+
+// the counts of H models over n points, staged from and fetched to the host
+static int staged_count(int32_t device, const double* pts, int64_t n, const Model* models, int64_t H, int shape,
+                        double thresh, int32_t* counts) {
+  Call call(device);
+  Ctx* c = call.c;
+  if (!c) return PYQSM_ENODEV;
+  double* d_pts;
+  Model* d_models;
+  int32_t* d_counts;
+  PQ_TRY(c->arena.get(size_t(n) * 3 + 1, &d_pts));
+  PQ_TRY(c->arena.get(size_t(H), &d_models));
+  PQ_TRY(c->arena.get(size_t(H), &d_counts));
+  if (n) PQ_TRY(copy_in(c, d_pts, pts, size_t(n) * 3));
+  PQ_TRY(copy_in(c, d_models, models, size_t(H)));
+  PQ_TRY(count_on_device(c, d_pts, n, one_set(n), d_models, H, shape, thresh, d_counts));
+  PQ_TRY(fetch(c, counts, d_counts, size_t(H)));
   return 0;
 }
 
@@ -644,7 +750,7 @@ static void plane_select(const int32_t* cnt, int64_t H, int64_t n, int m, double
 // counts of the H models over the n points, read back once, and the selection
 static int plane_pick(Ctx* c, const double* d_pts, int64_t n, const PlaneScratch& s, int64_t H, int m, double thresh,
                       double probability, int64_t* best, int64_t* best_cnt, int64_t* used) {
-  PQ_TRY(count_on_device(c, d_pts, n, s.models, H, 2, thresh, s.counts));
+  PQ_TRY(count_on_device(c, d_pts, n, one_set(n), s.models, H, 2, thresh, s.counts));
   std::vector<int32_t> h_counts(size_t(H), 0);
   PQ_TRY(fetch(c, h_counts.data(), s.counts, size_t(H)));
   plane_select(h_counts.data(), H, n, m, probability, best, best_cnt, used);
@@ -655,9 +761,8 @@ static int plane_pick(Ctx* c, const double* d_pts, int64_t n, const PlaneScratch
 static int plane_flag(Ctx* c, const double* d_pts, int64_t n, const PlaneScratch& s, int64_t best, double thresh,
                       int64_t* d_idx) {
   ProfScope ps(c, "plane_flag");
-  hipLaunchKernelGGL(k_flags<2>, dim3(ceil_div(n + 1, 256)), dim3(256), 0, c->stream, d_pts, n, s.models, best,
-                     thresh, s.flags);
-  PQ_HIP(hipGetLastError());
+  PQ_TRY(flags_on_device(c, d_pts, n, one_set(n), s.models, 0 /* the row stride, unread with one set */, nullptr, best,
+                         2, thresh, s.flags, nullptr));
   PQ_TRY(compact_flagged(c, s.flags, n, d_idx));
   return 0;
 }
@@ -676,7 +781,7 @@ static int plane_refit(Ctx* c, const double* d_pts, int64_t n, const PlaneScratc
   return 0;
 }
 
-static constexpr int64_t kPlaneMaxN = 65535LL * kTile;  // k_count's grid.y
+static constexpr int64_t kPlaneMaxN = kMaxTiles * kTile;
 
 // the checks every plane call makes before it touches a device
 static int plane_check(const char* who, const double* pts, int64_t n, int64_t H, int64_t m, bool need_m_points,
@@ -728,7 +833,7 @@ int pyqsm_ransac_models(const double* pts, int64_t n, const int64_t* triples, in
   PQ_TRY(c->arena.get(size_t(H), &d_models));
   if (n) PQ_TRY(copy_in(c, d_pts, pts, size_t(n) * 3));
   PQ_TRY(copy_in(c, d_tri, triples, size_t(H) * 3));
-  hipLaunchKernelGGL(k_models, dim3(ceil_div(H, 256)), dim3(256), 0, c->stream, d_pts, n, d_tri, H,
+  hipLaunchKernelGGL(k_models, dim3(ceil_div(H, 256)), dim3(256), 0, c->stream, d_pts, n, one_set(n), d_tri, H,
                      d_models);
   PQ_HIP(hipGetLastError());
   PQ_TRY(fetch(c, reinterpret_cast<Model*>(models), d_models, size_t(H)));
@@ -739,22 +844,10 @@ int pyqsm_ransac_count(const double* pts, int64_t n, const double* models, int64
                        int32_t shape, double thresh, int32_t* counts, int32_t device) {
   PQ_API_RANGE("pyqsm_ransac_count");
   PQ_TRY(check_args(pts, n, H, shape));
+  PQ_TRY(check_tiles("pyqsm_ransac_count", ceil_div(n, kTile)));
   if (H == 0) return 0;
   if (!models || !counts) return fail(PYQSM_EINVAL, "pyqsm_ransac_count: NULL pointer");
-  Call call(device);
-  Ctx* c = call.c;
-  if (!c) return PYQSM_ENODEV;
-  double* d_pts;
-  Model* d_models;
-  int32_t* d_counts;
-  PQ_TRY(c->arena.get(size_t(n) * 3 + 1, &d_pts));
-  PQ_TRY(c->arena.get(size_t(H), &d_models));
-  PQ_TRY(c->arena.get(size_t(H), &d_counts));
-  if (n) PQ_TRY(copy_in(c, d_pts, pts, size_t(n) * 3));
-  PQ_TRY(copy_in(c, d_models, reinterpret_cast<const Model*>(models), size_t(H)));
-  PQ_TRY(count_on_device(c, d_pts, n, d_models, H, shape, thresh, d_counts));
-  PQ_TRY(fetch(c, counts, d_counts, size_t(H)));
-  return 0;
+  return staged_count(device, pts, n, reinterpret_cast<const Model*>(models), H, shape, thresh, counts);
 }
 
 int pyqsm_ransac(const double* pts, int64_t n, const int64_t* triples, int64_t H, int32_t shape,
@@ -762,6 +855,7 @@ int pyqsm_ransac(const double* pts, int64_t n, const int64_t* triples, int64_t H
                  int64_t* inliers, int64_t* n_inliers, int64_t* best_out, int32_t device) {
   PQ_API_RANGE("pyqsm_ransac");
   PQ_TRY(check_args(pts, n, H, shape));
+  PQ_TRY(check_tiles("pyqsm_ransac", ceil_div(n, kTile)));
   if (n_inliers) *n_inliers = 0;
   if (best_out) *best_out = -1;
   if (n == 0 || H == 0) return 0;
@@ -771,55 +865,15 @@ int pyqsm_ransac(const double* pts, int64_t n, const int64_t* triples, int64_t H
   Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
   double* d_pts;
-  int64_t *d_tri, *d_out;
-  Model* d_models;
-  int32_t *d_counts, *d_flags;
-  PQ_TRY(c->arena.get(size_t(n) * 3, &d_pts));
-  PQ_TRY(c->arena.get(size_t(H) * 3, &d_tri));
-  PQ_TRY(c->arena.get(size_t(H), &d_models));
-  PQ_TRY(c->arena.get(size_t(H), &d_counts));
-  PQ_TRY(c->arena.get(size_t(n) + 1, &d_flags));
-  PQ_TRY(c->arena.get(size_t(n), &d_out));
-  PQ_TRY(copy_in(c, d_pts, pts, size_t(n) * 3));
-  PQ_TRY(copy_in(c, d_tri, triples, size_t(H) * 3));
-  {
-    ProfScope ps(c, "ransac_models");
-    hipLaunchKernelGGL(k_models, dim3(ceil_div(H, 256)), dim3(256), 0, c->stream, d_pts, n, d_tri,
-                       H, d_models);
-    PQ_HIP(hipGetLastError());
-  }
-  PQ_TRY(count_on_device(c, d_pts, n, d_models, H, shape, thresh, d_counts));
-  std::vector<int32_t> h_counts(size_t(H), 0);
-  PQ_TRY(fetch(c, h_counts.data(), d_counts, size_t(H)));
-  // first hypothesis with a strictly larger count wins (best starts empty)
-  int64_t best = -1;
-  int32_t best_cnt = 0;
-  for (int64_t h = 0; h < H; ++h)
-    if (h_counts[size_t(h)] > best_cnt) {
-      best_cnt = h_counts[size_t(h)];
-      best = h;
-    }
-  if (best < 0) return 0;
-  {
-    ProfScope ps(c, "ransac_compact");
-    const dim3 grid(ceil_div(n + 1, 256));
-    if (shape == 0)
-      hipLaunchKernelGGL(k_flags<0>, grid, dim3(256), 0, c->stream, d_pts, n, d_models, best,
-                         thresh, d_flags);
-    else
-      hipLaunchKernelGGL(k_flags<1>, grid, dim3(256), 0, c->stream, d_pts, n, d_models, best,
-                         thresh, d_flags);
-    PQ_HIP(hipGetLastError());
-    PQ_TRY(compact_flagged(c, d_flags, n, d_out));
-  }
-  Model m;
-  PQ_TRY(download(c, &m, d_models + best, 1));
-  PQ_TRY(fetch(c, inliers, d_out, size_t(best_cnt)));
-  center[0] = m.cx; center[1] = m.cy; center[2] = m.cz;
-  axis[0] = m.ax; axis[1] = m.ay; axis[2] = m.az;
-  *radius = m.r;
-  *n_inliers = best_cnt;
-  if (best_out) *best_out = best;
+  int64_t* d_tri;
+  PQ_TRY(upload(c, pts, size_t(n) * 3, &d_pts));
+  PQ_TRY(upload(c, triples, size_t(H) * 3, &d_tri));
+  Winner w;
+  PQ_TRY(fit_sets(c, d_pts, n, nullptr, 1, d_tri, H, shape, thresh, &w, inliers));
+  if (w.best < 0) return 0;
+  put_model(w.m, center, axis, radius);
+  *n_inliers = w.count;
+  if (best_out) *best_out = w.best;
   return 0;
 }
 
@@ -850,95 +904,23 @@ int pyqsm_ransac_batch(const double* pts, int64_t n, const int64_t* seg_start, i
   if (n == 0 || H == 0) return 0;
   if (!triples) return fail(PYQSM_EINVAL, "pyqsm_ransac_batch: triples is NULL");
   if (double(n_seg) * double(H) > 2.0e9) return fail(PYQSM_ERANGE, "more than 2^31 hypotheses per call");
+  int64_t tiles = 0;
+  for (int64_t s = 0; s < n_seg; ++s) tiles += ceil_div(seg_start[s + 1] - seg_start[s], kTile);
+  PQ_TRY(check_tiles("pyqsm_ransac_batch", tiles));
   Call call(device);
   Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
-  const int64_t S = n_seg, SH = S * H;
-  // the tiles of all sets
-  std::vector<int32_t> h_tile_set;
-  std::vector<int64_t> h_tile_base;
-  for (int64_t s = 0; s < S; ++s)
-    for (int64_t b = seg_start[s]; b < seg_start[s + 1]; b += kTile) {
-      h_tile_set.push_back(int32_t(s));
-      h_tile_base.push_back(b);
-    }
-  const int64_t tiles = int64_t(h_tile_set.size());
-  if (tiles > 65535) return fail(PYQSM_ERANGE, "more than 65535 point tiles per call: split the batch");
   double* d_pts;
-  int64_t *d_seg, *d_tri, *d_tile_base, *d_best, *d_out;
-  int32_t *d_tile_set, *d_counts, *d_best_cnt, *d_flags, *d_set_of;
-  Model *d_models, *d_win;
-  PQ_TRY(c->arena.get(size_t(n) * 3, &d_pts));
-  PQ_TRY(c->arena.get(size_t(S) + 1, &d_seg));
-  PQ_TRY(c->arena.get(size_t(SH) * 3, &d_tri));
-  PQ_TRY(c->arena.get(size_t(tiles), &d_tile_base));
-  PQ_TRY(c->arena.get(size_t(tiles), &d_tile_set));
-  PQ_TRY(c->arena.get(size_t(SH), &d_models));
-  PQ_TRY(c->arena.get(size_t(SH), &d_counts));
-  PQ_TRY(c->arena.get(size_t(S), &d_best));
-  PQ_TRY(c->arena.get(size_t(S), &d_best_cnt));
-  PQ_TRY(c->arena.get(size_t(S), &d_win));
-  PQ_TRY(c->arena.get(size_t(n) + 1, &d_flags));
-  PQ_TRY(c->arena.get(size_t(n), &d_set_of));
-  PQ_TRY(c->arena.get(size_t(n), &d_out));
-  PQ_TRY(copy_in(c, d_pts, pts, size_t(n) * 3));
-  PQ_TRY(copy_in(c, d_seg, seg_start, size_t(S) + 1));
-  PQ_TRY(copy_in(c, d_tri, triples, size_t(SH) * 3));
-  PQ_TRY(copy_in(c, d_tile_base, h_tile_base.data(), size_t(tiles)));
-  PQ_TRY(copy_in(c, d_tile_set, h_tile_set.data(), size_t(tiles)));
-  PQ_HIP(hipMemsetAsync(d_counts, 0, size_t(SH) * 4, c->stream));
-  {
-    ProfScope ps(c, "ransac_models");
-    hipLaunchKernelGGL(k_models_seg, dim3(ceil_div(SH, 256)), dim3(256), 0, c->stream, d_pts, d_seg, S, d_tri, H,
-                       d_models);
-    PQ_HIP(hipGetLastError());
-  }
-  {
-    ProfScope ps(c, "ransac_count");
-    const dim3 grid(ceil_div(H, 256), unsigned(tiles));
-    if (shape == 0)
-      hipLaunchKernelGGL(k_count_seg<0>, grid, dim3(256), 0, c->stream, d_pts, d_seg, d_tile_set, d_tile_base,
-                         d_models, H, thresh, d_counts);
-    else
-      hipLaunchKernelGGL(k_count_seg<1>, grid, dim3(256), 0, c->stream, d_pts, d_seg, d_tile_set, d_tile_base,
-                         d_models, H, thresh, d_counts);
-    PQ_HIP(hipGetLastError());
-  }
-  {
-    ProfScope ps(c, "ransac_compact");
-    hipLaunchKernelGGL(k_best_seg, dim3(unsigned(S)), dim3(256), 0, c->stream, d_counts, H, d_best, d_best_cnt);
-    const dim3 grid(ceil_div(n + 1, 256));
-    if (shape == 0)
-      hipLaunchKernelGGL(k_flags_seg<0>, grid, dim3(256), 0, c->stream, d_pts, n, d_seg, S, d_models, H, d_best,
-                         thresh, d_flags, d_set_of);
-    else
-      hipLaunchKernelGGL(k_flags_seg<1>, grid, dim3(256), 0, c->stream, d_pts, n, d_seg, S, d_models, H, d_best,
-                         thresh, d_flags, d_set_of);
-    PQ_HIP(hipGetLastError());
-    PQ_TRY(exclusive_scan_i32(c, d_flags, n + 1));
-    hipLaunchKernelGGL(k_compact_seg, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, n, d_seg, d_set_of, d_flags,
-                       d_out);
-    hipLaunchKernelGGL(k_gather_best, dim3(ceil_div(S, 256)), dim3(256), 0, c->stream, S, d_models, H, d_best,
-                       d_win);
-    PQ_HIP(hipGetLastError());
-  }
-  std::vector<Model> h_win(static_cast<size_t>(S), Model{0, 0, 0, 0, 0, 0, 0, 0});
-  std::vector<int32_t> h_cnt(static_cast<size_t>(S), 0);
-  int32_t total = 0;
-  PQ_TRY(download(c, h_win.data(), d_win, size_t(S)));
-  PQ_TRY(download(c, h_cnt.data(), d_best_cnt, size_t(S)));
-  PQ_TRY(download(c, best_out, d_best, size_t(S)));
-  PQ_TRY(download(c, &total, d_flags + n, 1));
-  PQ_HIP(hipStreamSynchronize(c->stream));
-  if (total > 0) {
-    PQ_TRY(fetch(c, inliers, d_out, size_t(total)));
-  }
-  for (int64_t s = 0; s < S; ++s) {
-    const Model& m = h_win[size_t(s)];
-    centers[3 * s] = m.cx; centers[3 * s + 1] = m.cy; centers[3 * s + 2] = m.cz;
-    axes[3 * s] = m.ax; axes[3 * s + 1] = m.ay; axes[3 * s + 2] = m.az;
-    radii[s] = m.r;
-    n_inliers[s] = h_cnt[size_t(s)];
+  int64_t* d_tri;
+  PQ_TRY(upload(c, pts, size_t(n) * 3, &d_pts));
+  PQ_TRY(upload(c, triples, size_t(n_seg * H) * 3, &d_tri));
+  std::vector<Winner> win(static_cast<size_t>(n_seg));
+  PQ_TRY(fit_sets(c, d_pts, n, seg_start, n_seg, d_tri, H, shape, thresh, win.data(), inliers));
+  for (int64_t s = 0; s < n_seg; ++s) {
+    const Winner& w = win[size_t(s)];
+    put_model(w.m, centers + 3 * s, axes + 3 * s, radii + s);
+    n_inliers[s] = w.count;
+    best_out[s] = w.best;
   }
   return 0;
 }
@@ -980,20 +962,7 @@ int pyqsm_plane_count(const double* pts, int64_t n, const double* planes, int64_
     const bool ok = p[0] != 0.0 || p[1] != 0.0 || p[2] != 0.0;
     h_models[size_t(h)] = Model{0.0, 0.0, 0.0, p[0], p[1], p[2], p[3], ok ? 1.0 : 0.0};
   }
-  Call call(device);
-  Ctx* c = call.c;
-  if (!c) return PYQSM_ENODEV;
-  double* d_pts;
-  Model* d_models;
-  int32_t* d_counts;
-  PQ_TRY(c->arena.get(size_t(n) * 3 + 1, &d_pts));
-  PQ_TRY(c->arena.get(size_t(H), &d_models));
-  PQ_TRY(c->arena.get(size_t(H), &d_counts));
-  if (n) PQ_TRY(copy_in(c, d_pts, pts, size_t(n) * 3));
-  PQ_TRY(copy_in(c, d_models, h_models.data(), size_t(H)));
-  PQ_TRY(count_on_device(c, d_pts, n, d_models, H, 2, thresh, d_counts));
-  PQ_TRY(fetch(c, counts, d_counts, size_t(H)));
-  return 0;
+  return staged_count(device, pts, n, h_models.data(), H, 2, thresh, counts);
 }
 
 int pyqsm_segment_plane(const double* pts, int64_t n, const int64_t* samples, int64_t H, int32_t m,

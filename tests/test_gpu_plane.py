@@ -1,6 +1,6 @@
 """Plane segmentation on the GPU against tests/plane_restatement.py.
 
-Shapes: n in {1, 63, 1025, 2500} straddles the 64-lane wave and the 1024-point tile of the count,
+Shapes: n in {1, 63, 1024, 1025, 2500} straddles the 64-lane wave and the 1024-point tile of the count,
 H in {1, 257, 300} the 256-lane block; m = 3 and m = 10 take the two constructions. Tolerances:
 unit normals within 1e-12 and d within 1e-9 * extent (those of test_gpu_ransac.py for axes and
 centres); counts, selections, inlier sets, labels and the order-free refit are compared exactly.
@@ -92,7 +92,7 @@ def test_invalid_hypotheses_give_zero_rows(gpu):
     np.testing.assert_array_equal(hip.plane_count(P, np.zeros((3, 4)), 10.0, device=gpu), [0, 0, 0])
 
 
-@pytest.mark.parametrize("n", [1, 63, 1025, 2500])
+@pytest.mark.parametrize("n", [1, 63, 1024, 1025, 2500])
 @pytest.mark.parametrize("H", [1, 257, 300])
 def test_counts_are_bit_exact(gpu, patch, patch_planes, n, H):
     planes = patch_planes[:H]  # row 7 is invalid

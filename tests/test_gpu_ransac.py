@@ -135,3 +135,40 @@ def test_batch_equals_one_call_per_set(gpu, shape):
         assert np.array_equal(want[2], got[q][2]) and want[3] == got[q][3] and np.array_equal(want[4], got[q][4])
         assert np.array_equal(want[0].center, got[q][0].center) and want[0].height == got[q][0].height
     assert got[5][0] is None                                               # radius 0.6 > max_radius
+
+
+@pytest.mark.parametrize("H", [1, 256, 257])
+@pytest.mark.parametrize("shape", ["circle", "cylinder"])
+def test_batch_matches_numpy_given_models(gpu, shape, H):
+    """pyqsm_ransac_batch and pyqsm_ransac share one path, so the batch is pinned to NumPy here and
+    not to the single call: per set, the models of hip.ransac_models, counted and flagged with
+    oracle.ransac_distance <= thresh, the first row of the largest count winning (none when it is 0).
+    Set sizes sit on the 1024-point tile (1023, 1024, 1025, 2049) and below a sample (0, 2); the
+    collinear set has no valid model; H = 256 is the hypothesis block. No tolerance: the models are
+    the GPU's own and test_counts_bit_exact_given_models holds the distance bit-exact."""
+    thresh = 0.04
+    sets = [synth.ring_cluster(n, seed=20 + q) for q, n in enumerate((0, 2, 3, 1023, 1024, 1025, 2049))]
+    sets.append(np.arange(30.0).reshape(10, 3) * [1.0, 0.0, 0.0])          # collinear: no valid model
+    if shape == "circle":
+        sets = [_flat(p) for p in sets]
+    rng = np.random.default_rng(H)
+    tri = np.stack([_triples(rng, len(p), H) if len(p) >= 3 else np.full((H, 3), -1) for p in sets])
+    seg = np.concatenate([[0], np.cumsum([len(p) for p in sets])])
+    c, a, r, inl, best = hip.ransac_batch(np.concatenate(sets), seg, tri, shape, thresh, device=gpu)
+    for q, p in enumerate(sets):
+        models = hip.ransac_models(p, tri[q], device=gpu)
+        dist = [oracle.ransac_distance(p, m[0:3], m[3:6], m[6], shape) if m[7] else None for m in models]
+        counts = np.array([0 if d is None else int((d <= thresh).sum()) for d in dist])
+        want = int(np.argmax(counts)) if counts.max() > 0 else -1            # argmax: the first of the largest
+        want_inl = np.flatnonzero(dist[want] <= thresh) if want >= 0 else np.zeros(0, np.int64)
+        row = models[want] if want >= 0 else np.zeros(8)
+        assert best[q] == want
+        assert np.array_equal(inl[q], want_inl)
+        assert np.array_equal(c[q], row[0:3]) and np.array_equal(a[q], row[3:6]) and r[q] == row[6]
+        if len(p) >= 3:
+            c1, a1, r1, inl1, b1 = hip.ransac(p, tri[q], shape, thresh, device=gpu)
+            assert b1 == want
+            assert np.array_equal(inl1, want_inl)
+            assert np.array_equal(c1, row[0:3]) and np.array_equal(a1, row[3:6]) and r1 == row[6]
+    assert best[-1] == -1 and best[0] == -1 and best[1] == -1
+    assert H == 1 or (best[3:7] >= 0).all()                # the rings of about a tile and more have a winner
