@@ -80,8 +80,9 @@ void* pyqsm_host_alloc(size_t bytes);
  * the dominant kernel's average launch duration live. on = 1: phase timers and the
  * dominant kernels of each path; on = 2: also single kernels inside the solver's
  * iteration loops (k_bspmv_f, k_down_l0, k_up_l0: adds two event records per launch)
- * and the pair-test counter of the DBSCAN core pass ("core_pair_tests": launches =
- * lane-tests executed, ms = 0). */
+ * and the counters of the DBSCAN core pass ("core_pair_tests": launches =
+ * lane-tests executed, ms = 0; "core_band_lanes": launches = points the fp32 decision
+ * left to the fp64 pass that had a distance in the band around eps^2, ms = 0). */
 int pyqsm_prof_enable(int device, int on);
 int pyqsm_prof_reset(int device);
 /* Sum of elapsed ms and number of launches recorded under `name`

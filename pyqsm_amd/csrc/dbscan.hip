@@ -17,11 +17,16 @@
 // The distance predicate is evaluated in fp64 exactly as scikit-learn does:
 // d2 = ((dx*dx) + dy*dy) + dz*dz with separately rounded products, compared
 // with fl(eps*eps). The library is compiled with -ffp-contract=off.
+// (The core pass over fp32 records decides in fp32 the pairs that fp32 can decide, the others in that same
+// fp64 form: core_band. The verdicts are the fp64 predicate's, pair by pair.)
 #include "grid.hpp"
 
 #include <atomic>
+#include <cfloat>
 #include <chrono>
+#include <cmath>
 #include <optional>
+#include <type_traits>
 #include <vector>
 
 namespace pyqsm {
@@ -53,11 +58,51 @@ __device__ __forceinline__ double sqdist(double ax, double ay, double az, double
 struct TileLds {
   double x[4][64], y[4][64], z[4][64];  // the current chunk of candidates, per wave
 };
+// ... and as floats, for the fp32 decision (k_core_tiled<CoordsF32, true>): read two candidates at a time
+struct TileLdsF32 {
+  alignas(16) float x[4][64], y[4][64], z[4][64];
+};
+typedef float float2v __attribute__((ext_vector_type(2)));
+
+// The two thresholds of the fp32 decision of the core pass. A CoordsF32 grid exists only when every input
+// coordinate IS an fp32 value, so the fp32 chain
+//     d = fl(dx*dx), d = fma(dy, dy, d), d = fma(dz, dz, d)      with dx = fl(x - cx), ...
+// differs from the true squared distance D by a relative (1 + u)^5 - 1 < 5.0001 u, u = 2^-24: one rounding on
+// each difference, doubled by the squaring; one on the product, one on each fma; the partial sums are sums
+// of non-negative terms, so no error is amplified by cancellation. The fp64 chain of the exact predicate is
+// within 2^-50 of D. The margin is 2^-20 = 16 u, more than three times the bound:
+//     d <= lo <= r2 (1 - 16 u)  =>  D <= d / (1 - 5.0001 u) < r2 (1 - 10 u)  =>  the fp64 chain says "in",
+//     d >  hi >= r2 (1 + 16 u)  =>  D >= d / (1 + 5.0001 u) > r2 (1 + 10 u)  =>  the fp64 chain says "out",
+// and only lo < d <= hi is left to fp64 (k_core_rest). Underflow: a difference is exact when it is
+// subnormal, and a flushed difference or a product below 2^-126 moves d by less than 3 * 2^-126 in all,
+// which with lo > 2^-100 is less than 0.75 u of r2: inside the margin (smaller eps: the fp64 kernel).
+// Overflow: a difference or a sum that overflows gives d = +inf > hi, "out", and the true D is then above
+// 2^128 (1 - 6 u) > FLT_MAX / (1 + 16 u) >= r2: the verdict is right (hi not finite: the fp64 kernel).
+// +inf never turns into NaN in the chain (finite coordinates: no inf - inf, no 0 * inf), which is also what
+// makes (+inf, 0, 0) the padding candidate that counts on neither side.
+struct CoreBand {
+  float lo, hi;  // the largest float <= r2 (1 - 2^-20), the smallest float >= r2 (1 + 2^-20)
+  bool usable() const { return lo > 0x1p-100f && std::isfinite(hi); }
+};
+static CoreBand core_band(double r2) {
+  const double a = r2 * (1.0 - 0x1p-20), b = r2 * (1.0 + 0x1p-20);
+  CoreBand t{0.0f, INFINITY};
+  if (!(a > 0.0) || !(b <= double(FLT_MAX))) return t;  // (also NaN)
+  t.lo = float(a);
+  if (double(t.lo) > a) t.lo = nextafterf(t.lo, -INFINITY);
+  t.hi = float(b);
+  if (double(t.hi) < b) t.hi = nextafterf(t.hi, INFINITY);
+  return t;
+}
 
 // (Measured alternatives, MI355X, 1 M-point forest: per-lane gathers 0.72 ms; this
 // LDS-broadcast fp64 loop 0.48 ms; the same with a rigorous fp32 pre-filter and the
 // chunk held in registers / broadcast by v_readlane 0.71 ms — issue-stall bound, see
-// profiles/r01_dbscan_sq_counters.csv. The simplest form won.)
+// profiles/r01_dbscan_sq_counters.csv. The simplest form won. That pre-filter still ran fp64 on whatever
+// passed; the fp32 DECISION of k_core_tiled<CoordsF32, true> keeps the LDS broadcast and runs no fp64 at all:
+// 51.9 -> 36.9 us per launch, 19.2 -> 12.8 M vector instructions, profiles/core_f32_bench_ab.txt. The same
+// with the band lanes kept as a wave mask in scalar registers instead of the second count: one vector
+// instruction per candidate fewer and 1.3 us slower.)
 //
 // Only "at least min_pts" matters, so the wave stops as soon as (almost) all of its
 // points have seen enough neighbours: the runs are visited centre row first, and once
@@ -93,11 +138,19 @@ __device__ __forceinline__ void stencil_bounds(int c, Stencil st, const CellDir&
   }
 }
 
-template <class CO>
+// F32 (CoordsF32 only; core_band above): the tiled path decides in packed fp32 against the two thresholds
+// and counts twice, cnt (d <= lo: certainly within) and cnt_hi (d <= hi: possibly within). cnt takes the
+// place of the exact count everywhere: a lane is core once cnt >= min_pts, the early exit and the hand-off
+// go by it. A lane is non-core when the whole tile was visited and cnt_hi < min_pts; a lane that still
+// straddles then (cnt < min_pts <= cnt_hi) joins the stragglers, and k_core_rest decides it in fp64.
+// Two candidates per step: three v_pk_add_f32, one v_pk_mul_f32 and two v_pk_fma_f32 serve both, no
+// conversion on staging and half the LDS bytes. The per-cell path of the oversized tiles stays fp64.
+template <class CO, bool F32>
 __global__ __launch_bounds__(256) void k_core_tiled(int n, const GridPlan* __restrict__ plan,
                                                     const DirWord* __restrict__ dwords,
                                                     const int32_t* __restrict__ dslots,
                                                     const int32_t* __restrict__ cell_of, CO co, double r2,
+                                                    float r2_lo, float r2_hi /*F32: core_band(r2)*/,
                                                     int min_pts, uint8_t* __restrict__ core,
                                                     int32_t* __restrict__ rest,
                                                     int32_t* __restrict__ rest_cnt /*[kRestSegs]*/, int seg_cap,
@@ -107,9 +160,11 @@ __global__ __launch_bounds__(256) void k_core_tiled(int n, const GridPlan* __res
                                                     int max_chunks,
                                                     unsigned long long* __restrict__ tests /*may be null:
                                                     [256] slots, candidates staged per wave (x 64 lanes
-                                                    = lane-tests executed)*/,
+                                                    = lane-tests executed), then [256] slots, lanes handed
+                                                    on with a distance in the band (F32)*/,
     unsigned long long* __restrict__ st /*stamps or null*/) {
   __shared__ TileLds L;
+  __shared__ TileLdsF32 LF;  // (F32 only: an unused array takes no LDS)
   stamped(st, [&] {
   const CellDir dir{dwords, dslots};
   // wave-uniform quantities are forced into SGPRs so that the loops below are scalar
@@ -121,18 +176,50 @@ __global__ __launch_bounds__(256) void k_core_tiled(int n, const GridPlan* __res
   const int p = p0 + lane;
   const bool live = p < n;
   double x = 0.0, y = 0.0, z = 0.0;
-  if (live) co.get(p, x, y, z);
+  float fx = 0.0f, fy = 0.0f, fz = 0.0f;  // F32: the same point as it is stored
+  if constexpr (F32) {
+    if (live) {
+      const float4 v = co.p[p];
+      fx = v.x, fy = v.y, fz = v.z;
+    }
+  } else {
+    if (live) co.get(p, x, y, z);
+  }
   const Tile t = wave_tile(p0, n, st, ncell, dir, cell_of);
   int cnt = 0;  // (starting lanes of sub-cells with >= min_pts points as "decided" gained nothing)
+  int cnt_hi = 0;  // F32: candidates with d <= hi; cnt those with d <= lo
   bool deferred = false;
   int chunks = 0;
   int staged = 0;  // wave-uniform: candidates this wave tested its 64 lanes against
+  int band = 0;    // wave-uniform, F32: lanes handed on that had a distance in the band (cnt < cnt_hi): all
+                   // that fp32 alone might have decided otherwise
+  // The lanes of `und` (cnt < min_pts) restart on their own in k_core_rest. A wave comes here once.
+  const auto hand_on = [&](unsigned long long und) {
+    if (und != 0) {
+      int slot = 0;
+      const int lead = __ffsll(und) - 1;
+      // kRestSegs counters, a block's stragglers go to segment blockIdx % kRestSegs of the list
+      // (capacity seg_cap: a block has at most 256): thousands of waves adding to ONE counter were
+      // served one at a time (~10 ns each), and every one of them waited for its turn
+      const int seg = blockIdx.x % kRestSegs;
+      if (lane == lead) slot = atomicAdd(rest_cnt + seg, __popcll(und));
+      slot = __shfl(slot, lead, 64);
+      const bool mine = (und >> lane) & 1ull;
+      if constexpr (F32) band += __popcll(__ballot(mine && cnt_hi > cnt));
+      if (mine) {
+        rest[size_t(seg) * seg_cap + slot + __popcll(und & ((1ull << lane) - 1ull))] = p;
+        cnt = -1;
+      }
+    }
+    deferred = true;
+  };
   if (t.total > kTileMax) {
     // The wave's points straddle distant cells (end of one grid layer, start of the next):
     // the linear intervals would sweep whole layers. Take the distinct cells of the wave
     // one at a time instead — exact 27-cell stencil, candidates still staged through LDS,
     // only the lanes of that cell count. (A per-lane walk here made these few waves the
     // 0.25 ms tail of the whole kernel: ~850 dependent gathers per lane.)
+    if constexpr (F32) x = double(fx), y = double(fy), z = double(fz);
     const int mycell = live ? cell_of[p] : -1;
     unsigned long long todo = __ballot(live);
     while (todo) {
@@ -160,42 +247,55 @@ __global__ __launch_bounds__(256) void k_core_tiled(int n, const GridPlan* __res
       }
     }
   } else {
+    const float2v X = {fx, fx}, Y = {fy, fy}, Z = {fz, fz};  // (F32)
 #pragma unroll
     for (int ri = 0; ri < 9; ++ri) {
       const int r = kRunOrder[ri];
       for (int base = t.qb[r]; base < t.qe[r] && !deferred; base += 64) {
         const int q = base + lane;
         const int m = t.qe[r] - base < 64 ? t.qe[r] - base : 64;
-        if (q < t.qe[r]) co.get(q, L.x[w][lane], L.y[w][lane], L.z[w][lane]);
-        __builtin_amdgcn_wave_barrier();
-        staged += m;
+        if constexpr (F32) {
+          // every lane stores: its candidate, or the padding (d = +inf) that makes an odd count even
+          float4 v = make_float4(INFINITY, 0.0f, 0.0f, 0.0f);
+          if (q < t.qe[r]) v = co.p[q];
+          LF.x[w][lane] = v.x, LF.y[w][lane] = v.y, LF.z[w][lane] = v.z;
+          __builtin_amdgcn_wave_barrier();
 #pragma unroll 4
-        for (int j = 0; j < m; ++j)
-          cnt += sqdist(x, y, z, L.x[w][j], L.y[w][j], L.z[w][j]) <= r2;
+          for (int j = 0; j < m; j += 2) {
+            const float2v dx = X - *reinterpret_cast<const float2v*>(&LF.x[w][j]);
+            const float2v dy = Y - *reinterpret_cast<const float2v*>(&LF.y[w][j]);
+            const float2v dz = Z - *reinterpret_cast<const float2v*>(&LF.z[w][j]);
+            float2v d = dx * dx;
+            d = __builtin_elementwise_fma(dy, dy, d);
+            d = __builtin_elementwise_fma(dz, dz, d);
+            cnt += d.x <= r2_lo;
+            cnt += d.y <= r2_lo;
+            cnt_hi += d.x <= r2_hi;
+            cnt_hi += d.y <= r2_hi;
+          }
+        } else {
+          if (q < t.qe[r]) co.get(q, L.x[w][lane], L.y[w][lane], L.z[w][lane]);
+          __builtin_amdgcn_wave_barrier();
+#pragma unroll 4
+          for (int j = 0; j < m; ++j)
+            cnt += sqdist(x, y, z, L.x[w][j], L.y[w][j], L.z[w][j]) <= r2;
+        }
+        staged += m;
         __builtin_amdgcn_wave_barrier();
         const unsigned long long und = __ballot(live && cnt < min_pts);
         ++chunks;
+        // (the tile's last chunk: whoever is still short has seen everything)
         if ((__popcll(und) <= kStragglers || chunks >= max_chunks) &&
             !(ri == 8 && base + 64 >= t.qe[r])) {
-          // the few lanes still short restart on their own in k_core_rest
-          if (und != 0) {
-            int slot = 0;
-            const int lead = __ffsll(und) - 1;
-            // kRestSegs counters, a block's stragglers go to segment blockIdx % kRestSegs of the list
-            // (capacity seg_cap: a block has at most 256): thousands of waves adding to ONE counter were
-            // served one at a time (~10 ns each), and every one of them waited for its turn
-            const int seg = blockIdx.x % kRestSegs;
-            if (lane == lead) slot = atomicAdd(rest_cnt + seg, __popcll(und));
-            slot = __shfl(slot, lead, 64);
-            if (live && cnt < min_pts) {
-              rest[size_t(seg) * seg_cap + slot + __popcll(und & ((1ull << lane) - 1ull))] = p;
-              cnt = -1;
-            }
-          }
-          deferred = true;
+          hand_on(und);  // the few lanes still short
           break;
         }
       }
+    }
+    // F32, the whole tile visited (through its last chunk or through empty trailing runs): a lane short
+    // of min_pts by cnt is non-core only if cnt_hi is short too
+    if constexpr (F32) {
+      if (!deferred) hand_on(__ballot(live && cnt < min_pts && cnt_hi >= min_pts));
     }
   }
   if (live && cnt >= 0) {
@@ -213,7 +313,10 @@ __global__ __launch_bounds__(256) void k_core_tiled(int n, const GridPlan* __res
     if (p == 0) bits[n / 32 + 1] = 0u;
     for (int i = p; i < seam_cap; i += n) seam[i] = 0;
   }
-  if (tests && lane == 0) atomicAdd(tests + (blockIdx.x & 255), static_cast<unsigned long long>(staged));
+  if (tests && lane == 0) {
+    atomicAdd(tests + (blockIdx.x & 255), static_cast<unsigned long long>(staged));
+    if (band) atomicAdd(tests + 256 + (blockIdx.x & 255), static_cast<unsigned long long>(band));
+  }
   });
 }
 
@@ -1460,27 +1563,37 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
     StampScope ps(c, "dbscan_core");
     unsigned long long* d_tests = nullptr;
     if (c->prof >= 2) {
-      PQ_TRY(c->arena.get(256, &d_tests));
-      PQ_HIP(hipMemsetAsync(d_tests, 0, 256 * 8, c->stream));
+      PQ_TRY(c->arena.get(512, &d_tests));  // [256] candidates staged, [256] lanes handed on out of the band
+      PQ_HIP(hipMemsetAsync(d_tests, 0, 512 * 8, c->stream));
     }
     // chunks of 64 candidates a wave of the tiled pass looks at before it hands its short lanes on: three
     // serve min_pts = 10, and in proportion beyond
     const int max_chunks = std::min(32, std::max(kMaxChunks, (kMaxChunks * min_pts + 9) / 10));
     {
       const StampKernel pk(c, "k_core_tiled", grid.x);
+      // fp32 records and an eps whose band neither underflows nor overflows: decide in fp32, fp64 only in the
+      // band (core_band); anything else runs the fp64 kernel
+      const CoreBand cb = core_band(r2);
+      const bool f32 = cb.usable();
       on_coords(g, [&](auto co) {
-        hipLaunchKernelGGL(k_core_tiled<decltype(co)>, grid, block, 0, c->stream, N, d_plan, dir.words, dir.slots, g.cell_of, co, r2,
-                           min_pts, core, rest, rest_segs, seg_cap, parent, min_orig, bits, seam,
-                           g.start ? 0 : int(seam_cap), max_chunks, d_tests,
-                           pk.slots);
+        const auto launch = [&](auto kernel) {
+          hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, N, d_plan, dir.words, dir.slots, g.cell_of, co, r2, cb.lo,
+                             cb.hi, min_pts, core, rest, rest_segs, seg_cap, parent, min_orig, bits, seam,
+                             g.start ? 0 : int(seam_cap), max_chunks, d_tests, pk.slots);
+        };
+        if constexpr (std::is_same_v<decltype(co), CoordsF32>) {
+          if (f32) return launch(k_core_tiled<CoordsF32, true>);
+        }
+        launch(k_core_tiled<decltype(co), false>);
       });
     }
-    if (d_tests) {  // profiling level 2 only: read the counter back (synchronises)
-      unsigned long long h[256];
-      PQ_TRY(fetch(c, h, d_tests, 256));
-      unsigned long long tot = 0;
-      for (unsigned long long v : h) tot += v;
+    if (d_tests) {  // profiling level 2 only: read the counters back (synchronises)
+      unsigned long long h[512];
+      PQ_TRY(fetch(c, h, d_tests, 512));
+      unsigned long long tot = 0, band = 0;
+      for (int i = 0; i < 256; ++i) tot += h[i], band += h[256 + i];
       c->timers["core_pair_tests"].launches += int64_t(tot) * 64;  // lane-tests executed
+      c->timers["core_band_lanes"].launches += int64_t(band);      // lanes handed to fp64 with a distance in the band
     }
     const dim3 gr(std::min<int64_t>(8192, ceil_div(n, 64)));
     unsigned long long* const st_rest = stamp_slots(c, gr.x);
