@@ -215,6 +215,20 @@ int pyqsm_dbscan_dev_ex(const double* xyz_dev, int64_t n, double eps, int32_t mi
  */
 int pyqsm_octant_directory(const double* xyz, int64_t n, double eps, int32_t* dims_out,
                            int32_t* begin_out, int64_t cap, int32_t device);
+/*
+ * The core pass over fp32 records counts neighbours with two clamped fp32 ramps of the squared distance d,
+ * s_in = sat(A - K d) and s_hi = sat(B - K d) (one fma each): s_in > 0 only where d <= lo, s_hi = 1
+ * wherever d <= hi, lo and hi the fp32 thresholds below and above which fp32 decides a pair as fp64 would.
+ * For tests:
+ * pyqsm_core_ramp_constants needs no GPU. out f32 [6]: lo, hi, K, A, B as pyqsm_dbscan_ex derives them
+ *   from eps and the radius rule, and 1 or 0: whether the ramp form runs at this eps (0: the fp64
+ *   kernel does; K, A, B may then be 0).
+ * pyqsm_core_ramp_probe evaluates the ramps on the device, with the function the core pass calls.
+ *   d f32 [n] (host), s_in_out and s_hi_out f32 [n] (host). PYQSM_EINVAL where the ramp form does not run.
+ */
+int pyqsm_core_ramp_constants(double eps, int32_t radius_inclusive, float* out);
+int pyqsm_core_ramp_probe(const float* d, int64_t n, double eps, int32_t radius_inclusive,
+                          float* s_in_out, float* s_hi_out, int32_t device);
 
 /* ---- k nearest neighbours --------------------------------------------- */
 /*

@@ -54,6 +54,8 @@ SIGNATURES = {
     "pyqsm_dbscan_ex": (ctypes.c_int, [vp, i64, dbl, i32, i32, vp, vp, i32]),
     "pyqsm_dbscan_dev_ex": (ctypes.c_int, [vp, i64, dbl, i32, i32, vp, vp, ctypes.POINTER(i64), i32]),
     "pyqsm_octant_directory": (ctypes.c_int, [vp, i64, dbl, vp, vp, i64, i32]),
+    "pyqsm_core_ramp_constants": (ctypes.c_int, [dbl, i32, vp]),
+    "pyqsm_core_ramp_probe": (ctypes.c_int, [vp, i64, dbl, i32, vp, vp, i32]),
     "pyqsm_knn": (ctypes.c_int, [vp, i64, i32, i32, vp, vp, i32]),
     "pyqsm_knn_dev": (ctypes.c_int, [vp, i64, i32, i32, vp, vp, i32]),
     "pyqsm_ransac": (ctypes.c_int, [vp, i64, vp, i64, i32, dbl, vp, vp, ctypes.POINTER(dbl), vp,

@@ -63,6 +63,7 @@ struct TileLdsF32 {
   alignas(16) float x[4][64], y[4][64], z[4][64];
 };
 typedef float float2v __attribute__((ext_vector_type(2)));
+typedef float float4v __attribute__((ext_vector_type(4)));
 
 // The two thresholds of the fp32 decision of the core pass. A CoordsF32 grid exists only when every input
 // coordinate IS an fp32 value, so the fp32 chain
@@ -93,6 +94,76 @@ static CoreBand core_band(double r2) {
   t.hi = float(b);
   if (double(t.hi) < b) t.hi = nextafterf(t.hi, INFINITY);
   return t;
+}
+
+// The fp32 decision COUNTS with two clamped ramps instead of two compares and two integer adds: per
+// candidate pair one packed fma with the clamp modifier and one packed add for each side,
+//     s_in = sat(fma(d, -K, A)),  acc_in += s_in        s_hi = sat(fma(d, -K, B)),  acc_hi += s_hi,
+// with K a power of two, 1/K in [r2 2^-20, r2 2^-19) (scaling by it is exact), A the largest float
+// <= K lo and B the smallest float >= 1 + K hi. The fma rounds once, and a rounding neither changes a
+// sign nor carries a value >= 1 below 1, so
+//     s_in(d) > 0   =>  K d < A <= K lo         =>  d < lo:   only a certainly-inside candidate adds to
+//                                                             acc_in, and at most 1;
+//     d <= hi       =>  B - K d >= B - K hi >= 1 =>  s_hi = 1: every possibly-inside candidate adds
+//                                                             exactly 1 to acc_hi
+// (a flushed result only turns a positive s_in into 0). Fractions arise for d in [lo - 1/K, hi + 1/K] only,
+// inside r2 (1 +- 3 * 2^-20) up to a rounding: that is the zone k_core_rest may be asked about, three times
+// as wide as the band. The sums need no error bound, only that round-to-nearest is monotone and that
+// integers below 2^24 are floats. Induction over the additions: if acc_in <= k, k the number of positive
+// terms so far, then fl(acc_in + s) <= fl(k + 1) = k + 1 for a term 0 < s <= 1, and adding 0 changes
+// nothing: acc_in never exceeds the count of d <= lo. If acc_hi >= k, k the number of terms equal to 1
+// so far, then fl(acc_hi + 1) >= fl(k + 1) = k + 1, and a term >= 0 never lowers a sum: acc_hi is never
+// below the count of d <= hi. Adding the two halves keeps both (the same step with integers on one side).
+// A tile holds at most kTileMax = 16384 candidates, so every integer involved stays below 2^24. Hence
+//     acc_in.x + acc_in.y >= float(min_pts)  =>  at least min_pts candidates certainly within: core,
+//     tile done and acc_hi.x + acc_hi.y < float(min_pts)  =>  fewer than min_pts possibly within: not core,
+// and every other lane goes to k_core_rest, which decides in fp64. NaN: none arises (finite coordinates; the
+// padding candidate gives d = +inf and fma(+inf, -K, .) = -inf, clamped to 0 on both ramps).
+struct CoreRamp {
+  float lo, hi;   // core_band(r2)
+  float K, A, B;  // 0 where the band is not usable
+  // ... and the constants are normal floats, min_pts is a float far below 2^24: anything else runs the fp64 kernel
+  bool usable(int min_pts = 1) const {
+    return CoreBand{lo, hi}.usable() && std::isnormal(K) && std::isnormal(A) && std::isnormal(B) &&
+           min_pts <= (1 << 20);
+  }
+};
+static CoreRamp core_ramp(double r2) {
+  const CoreBand cb = core_band(r2);
+  CoreRamp t{cb.lo, cb.hi, 0.0f, 0.0f, 0.0f};
+  if (!cb.usable()) return t;
+  int x;
+  const double m = frexp(r2, &x);  // r2 = m 2^x, 0.5 <= m < 1: the power of two in [m 2^(x-20), m 2^(x-19))
+  const int e = m == 0.5 ? x - 21 : x - 20;
+  if (e < -126 || e > 126) return t;
+  t.K = float(ldexp(1.0, -e));
+  const double a = ldexp(double(cb.lo), -e), b = 1.0 + ldexp(double(cb.hi), -e);  // exact in fp64
+  t.A = float(a);
+  if (double(t.A) > a) t.A = nextafterf(t.A, -INFINITY);
+  t.B = float(b);
+  if (double(t.B) < b) t.B = nextafterf(t.B, INFINITY);
+  return t;
+}
+// (the compiler folds no clamp into a packed fp32 fma: min(max(fma, 0), 1) becomes the fma and one
+// v_max_f32 ... clamp per element)
+__device__ __forceinline__ float2v core_ramp_sat(float2v d, float2v neg_k, float2v c) {
+  float2v s;
+  asm("v_pk_fma_f32 %0, %1, %2, %3 clamp" : "=v"(s) : "v"(d), "v"(neg_k), "v"(c));
+  return s;
+}
+
+// The two ramps of n squared distances, pair by pair as the core pass forms them (pyqsm_core_ramp_probe).
+__global__ __launch_bounds__(256) void k_core_ramp_probe(const float* __restrict__ d, int64_t n, float neg_k,
+                                                         float ramp_a, float ramp_b, float* __restrict__ s_in,
+                                                         float* __restrict__ s_hi) {
+  const int64_t i = 2 * (int64_t(blockIdx.x) * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  const bool two = i + 1 < n;
+  const float2v v = {d[i], two ? d[i + 1] : INFINITY};  // (the padding candidate)
+  const float2v a = core_ramp_sat(v, float2v{neg_k, neg_k}, float2v{ramp_a, ramp_a});
+  const float2v b = core_ramp_sat(v, float2v{neg_k, neg_k}, float2v{ramp_b, ramp_b});
+  s_in[i] = a.x, s_hi[i] = b.x;
+  if (two) s_in[i + 1] = a.y, s_hi[i + 1] = b.y;
 }
 
 // (Measured alternatives, MI355X, 1 M-point forest: per-lane gathers 0.72 ms; this
@@ -138,19 +209,21 @@ __device__ __forceinline__ void stencil_bounds(int c, Stencil st, const CellDir&
   }
 }
 
-// F32 (CoordsF32 only; core_band above): the tiled path decides in packed fp32 against the two thresholds
-// and counts twice, cnt (d <= lo: certainly within) and cnt_hi (d <= hi: possibly within). cnt takes the
-// place of the exact count everywhere: a lane is core once cnt >= min_pts, the early exit and the hand-off
-// go by it. A lane is non-core when the whole tile was visited and cnt_hi < min_pts; a lane that still
-// straddles then (cnt < min_pts <= cnt_hi) joins the stragglers, and k_core_rest decides it in fp64.
-// Two candidates per step: three v_pk_add_f32, one v_pk_mul_f32 and two v_pk_fma_f32 serve both, no
-// conversion on staging and half the LDS bytes. The per-cell path of the oversized tiles stays fp64.
+// F32 (CoordsF32 only; core_band and core_ramp above): the tiled path decides in packed fp32 against the two
+// thresholds and counts twice with the clamped ramps, acc_in (d <= lo: certainly within, never too many) and
+// acc_hi (d <= hi: possibly within, never too few), two halves each; cnt below means their sums. acc_in takes
+// the place of the exact count everywhere: a lane is core once it reaches min_pts, the early exit and the
+// hand-off go by it. A lane is non-core when the whole tile was visited and acc_hi < min_pts; a lane that still
+// straddles then joins the stragglers, and k_core_rest decides it in fp64.
+// Two candidates per step: three v_pk_add_f32, one v_pk_mul_f32 and two v_pk_fma_f32 for the distances, two
+// v_pk_fma_f32 with clamp and two v_pk_add_f32 for the counts, no conversion on staging and half the LDS
+// bytes. The per-cell path of the oversized tiles stays fp64.
 template <class CO, bool F32>
 __global__ __launch_bounds__(256) void k_core_tiled(int n, const GridPlan* __restrict__ plan,
                                                     const DirWord* __restrict__ dwords,
                                                     const int32_t* __restrict__ dslots,
                                                     const int32_t* __restrict__ cell_of, CO co, double r2,
-                                                    float r2_lo, float r2_hi /*F32: core_band(r2)*/,
+                                                    float neg_k, float ramp_a, float ramp_b /*F32: core_ramp(r2)*/,
                                                     int min_pts, uint8_t* __restrict__ core,
                                                     int32_t* __restrict__ rest,
                                                     int32_t* __restrict__ rest_cnt /*[kRestSegs]*/, int seg_cap,
@@ -187,13 +260,14 @@ __global__ __launch_bounds__(256) void k_core_tiled(int n, const GridPlan* __res
   }
   const Tile t = wave_tile(p0, n, st, ncell, dir, cell_of);
   int cnt = 0;  // (starting lanes of sub-cells with >= min_pts points as "decided" gained nothing)
-  int cnt_hi = 0;  // F32: candidates with d <= hi; cnt those with d <= lo
+  float2v acc_in = {0.0f, 0.0f}, acc_hi = {0.0f, 0.0f};  // F32, the tiled path: the ramps' sums (cnt stays 0)
+  const float fmin_pts = float(min_pts);
   bool deferred = false;
   int chunks = 0;
   int staged = 0;  // wave-uniform: candidates this wave tested its 64 lanes against
-  int band = 0;    // wave-uniform, F32: lanes handed on that had a distance in the band (cnt < cnt_hi): all
+  int band = 0;    // wave-uniform, F32: lanes handed on that had a distance in the band (acc_in < acc_hi): all
                    // that fp32 alone might have decided otherwise
-  // The lanes of `und` (cnt < min_pts) restart on their own in k_core_rest. A wave comes here once.
+  // The lanes of `und` (short of min_pts) restart on their own in k_core_rest. A wave comes here once.
   const auto hand_on = [&](unsigned long long und) {
     if (und != 0) {
       int slot = 0;
@@ -205,7 +279,7 @@ __global__ __launch_bounds__(256) void k_core_tiled(int n, const GridPlan* __res
       if (lane == lead) slot = atomicAdd(rest_cnt + seg, __popcll(und));
       slot = __shfl(slot, lead, 64);
       const bool mine = (und >> lane) & 1ull;
-      if constexpr (F32) band += __popcll(__ballot(mine && cnt_hi > cnt));
+      if constexpr (F32) band += __popcll(__ballot(mine && acc_hi.x + acc_hi.y > acc_in.x + acc_in.y));
       if (mine) {
         rest[size_t(seg) * seg_cap + slot + __popcll(und & ((1ull << lane) - 1ull))] = p;
         cnt = -1;
@@ -213,6 +287,7 @@ __global__ __launch_bounds__(256) void k_core_tiled(int n, const GridPlan* __res
     }
     deferred = true;
   };
+  const bool ramped = F32 && t.total <= kTileMax;  // wave-uniform: the verdict is acc_in's, not cnt's
   if (t.total > kTileMax) {
     // The wave's points straddle distant cells (end of one grid layer, start of the next):
     // the linear intervals would sweep whole layers. Take the distinct cells of the wave
@@ -248,6 +323,7 @@ __global__ __launch_bounds__(256) void k_core_tiled(int n, const GridPlan* __res
     }
   } else {
     const float2v X = {fx, fx}, Y = {fy, fy}, Z = {fz, fz};  // (F32)
+    const float2v NK = {neg_k, neg_k}, RA = {ramp_a, ramp_a}, RB = {ramp_b, ramp_b};
 #pragma unroll
     for (int ri = 0; ri < 9; ++ri) {
       const int r = kRunOrder[ri];
@@ -260,19 +336,32 @@ __global__ __launch_bounds__(256) void k_core_tiled(int n, const GridPlan* __res
           if (q < t.qe[r]) v = co.p[q];
           LF.x[w][lane] = v.x, LF.y[w][lane] = v.y, LF.z[w][lane] = v.z;
           __builtin_amdgcn_wave_barrier();
-#pragma unroll 4
-          for (int j = 0; j < m; j += 2) {
-            const float2v dx = X - *reinterpret_cast<const float2v*>(&LF.x[w][j]);
-            const float2v dy = Y - *reinterpret_cast<const float2v*>(&LF.y[w][j]);
-            const float2v dz = Z - *reinterpret_cast<const float2v*>(&LF.z[w][j]);
+          const auto pair = [&](float2v cx, float2v cy, float2v cz) {
+            const float2v dx = X - cx, dy = Y - cy, dz = Z - cz;
             float2v d = dx * dx;
             d = __builtin_elementwise_fma(dy, dy, d);
             d = __builtin_elementwise_fma(dz, dz, d);
-            cnt += d.x <= r2_lo;
-            cnt += d.y <= r2_lo;
-            cnt_hi += d.x <= r2_hi;
-            cnt_hi += d.y <= r2_hi;
+            acc_in += core_ramp_sat(d, NK, RA);
+            acc_hi += core_ramp_sat(d, NK, RB);
+          };
+          // Four pairs a step and the rest pair by pair, by hand: an asm statement counts as convergent, and a
+          // loop that holds one is not unrolled with a remainder. The step reads 16 bytes at a time
+          // (ds_read_b128; left to itself the compiler pairs the 8-byte reads into ds_read2_b64, which costs the
+          // LDS four times the cycles per byte and made it, not the vector pipe, the loop's limit).
+          int j = 0;
+          for (; j + 8 <= m; j += 8) {
+            const float4v* const lx = reinterpret_cast<const float4v*>(&LF.x[w][j]);
+            const float4v* const ly = reinterpret_cast<const float4v*>(&LF.y[w][j]);
+            const float4v* const lz = reinterpret_cast<const float4v*>(&LF.z[w][j]);
+            const float4v x0 = lx[0], x1 = lx[1], y0 = ly[0], y1 = ly[1], z0 = lz[0], z1 = lz[1];
+            pair(x0.lo, y0.lo, z0.lo);
+            pair(x0.hi, y0.hi, z0.hi);
+            pair(x1.lo, y1.lo, z1.lo);
+            pair(x1.hi, y1.hi, z1.hi);
           }
+          for (; j < m; j += 2)
+            pair(*reinterpret_cast<const float2v*>(&LF.x[w][j]), *reinterpret_cast<const float2v*>(&LF.y[w][j]),
+                 *reinterpret_cast<const float2v*>(&LF.z[w][j]));
         } else {
           if (q < t.qe[r]) co.get(q, L.x[w][lane], L.y[w][lane], L.z[w][lane]);
           __builtin_amdgcn_wave_barrier();
@@ -282,7 +371,8 @@ __global__ __launch_bounds__(256) void k_core_tiled(int n, const GridPlan* __res
         }
         staged += m;
         __builtin_amdgcn_wave_barrier();
-        const unsigned long long und = __ballot(live && cnt < min_pts);
+        const unsigned long long und =
+            F32 ? __ballot(live && acc_in.x + acc_in.y < fmin_pts) : __ballot(live && cnt < min_pts);
         ++chunks;
         // (the tile's last chunk: whoever is still short has seen everything)
         if ((__popcll(und) <= kStragglers || chunks >= max_chunks) &&
@@ -293,14 +383,16 @@ __global__ __launch_bounds__(256) void k_core_tiled(int n, const GridPlan* __res
       }
     }
     // F32, the whole tile visited (through its last chunk or through empty trailing runs): a lane short
-    // of min_pts by cnt is non-core only if cnt_hi is short too
+    // of min_pts by acc_in is non-core only if acc_hi is short too
     if constexpr (F32) {
-      if (!deferred) hand_on(__ballot(live && cnt < min_pts && cnt_hi >= min_pts));
+      if (!deferred)
+        hand_on(__ballot(live && acc_in.x + acc_in.y < fmin_pts && acc_hi.x + acc_hi.y >= fmin_pts));
     }
   }
-  if (live && cnt >= 0) {
-    core[p] = cnt >= min_pts;
-    co.mark_core(p, cnt >= min_pts);
+  if (live && cnt >= 0) {  // (not handed on)
+    const bool is_core = ramped ? acc_in.x + acc_in.y >= fmin_pts : cnt >= min_pts;
+    core[p] = is_core;
+    co.mark_core(p, is_core);
   }
   // the start of the union phase rides along (it was a launch of its own, ~5 us): every point its own
   // parent, no smallest index yet, k_number's bitmap (n / 32 + 1 words: nothing reads more of it) and the
@@ -1500,6 +1592,11 @@ __global__ __launch_bounds__(kLabelThreads) void k_labels(int n, const int32_t* 
   });
 }
 
+// The squared radius every kernel compares with (cluster_binned says why the strict rule is this one).
+static double dbscan_r2(double eps, bool radius_inclusive) {
+  return radius_inclusive ? eps * eps : nextafter(eps * eps, 0.0);
+}
+
 // Core flags, union-find and labels over a binned cloud. The kernels read the grid from d_plan.
 // *count_out: where the number of clusters lies on the device once the step has run.
 static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool radius_inclusive, const DevGrid& g,
@@ -1515,7 +1612,7 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
   // Open3D's cluster_dbscan computes if nanoflann's radius search compares strictly; SURVEY.md
   // §8 a2) is the same test against the double just below eps^2 — no fp64 value lies between
   // the two, so d2 < r2 <=> d2 <= pred(r2) exactly, and the kernels need no second form.
-  const double r2 = radius_inclusive ? eps * eps : nextafter(eps * eps, 0.0);
+  const double r2 = dbscan_r2(eps, radius_inclusive);
   uint8_t* core;
   int *parent, *min_orig;
   // [n / 32 + 1] the bitmap of k_number's large-count numbering, [1] the number of pre-roots (k_flatten_reps,
@@ -1572,13 +1669,13 @@ static int cluster_binned(Ctx* c, int64_t n, double eps, int32_t min_pts, bool r
     {
       const StampKernel pk(c, "k_core_tiled", grid.x);
       // fp32 records and an eps whose band neither underflows nor overflows: decide in fp32, fp64 only in the
-      // band (core_band); anything else runs the fp64 kernel
-      const CoreBand cb = core_band(r2);
-      const bool f32 = cb.usable();
+      // band (core_band), counted with the ramps (core_ramp); anything else runs the fp64 kernel
+      const CoreRamp cr = core_ramp(r2);
+      const bool f32 = cr.usable(min_pts);
       on_coords(g, [&](auto co) {
         const auto launch = [&](auto kernel) {
-          hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, N, d_plan, dir.words, dir.slots, g.cell_of, co, r2, cb.lo,
-                             cb.hi, min_pts, core, rest, rest_segs, seg_cap, parent, min_orig, bits, seam,
+          hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, N, d_plan, dir.words, dir.slots, g.cell_of, co, r2, -cr.K,
+                             cr.A, cr.B, min_pts, core, rest, rest_segs, seg_cap, parent, min_orig, bits, seam,
                              g.start ? 0 : int(seam_cap), max_chunks, d_tests, pk.slots);
         };
         if constexpr (std::is_same_v<decltype(co), CoordsF32>) {
@@ -1865,10 +1962,13 @@ static int dbscan_device(Ctx* c, const double* xyz, int64_t n, double eps, int32
   SubCells sub;
   const int32_t* count = nullptr;
   std::optional<StampScope> bin_scope(std::in_place, c, "dbscan_bin");
-  PQ_TRY(plan_grid_device(c, xyz, n, cell, max_cells, hint, d_plan, h_plan_dev, seq, zeroed, octant_zeroed_ints()));
+  // (speculated: no fold launch; the binning's first kernel plans from the box records and stores the plan)
+  PlanRecords rec{};
+  PQ_TRY(plan_grid_device(c, xyz, n, cell, max_cells, hint, d_plan, h_plan_dev, seq, zeroed, octant_zeroed_ints(),
+                          speculate ? &rec : nullptr));
   const Arena::Mark mark = c->arena.mark();
   if (speculate) {
-    PQ_TRY(bin_octants_planned(c, xyz, n, cell, hint, d_plan, zeroed, &g, &sub));
+    PQ_TRY(bin_octants_planned(c, xyz, n, cell, hint, rec, d_plan, zeroed, &g, &sub));
     bin_scope.reset();
     if (!readout)
       PQ_TRY(cluster_binned(c, n, eps, min_pts, radius_inclusive, g, sub, d_plan, labels, is_core, &count));
@@ -1984,6 +2084,37 @@ int pyqsm_octant_directory(const double* xyz, int64_t n, double eps, int32_t* di
   DirReadout ro{cap, begin_out, {0, 0, 0}};
   PQ_TRY(dbscan_device(c, d_xyz, n, eps, 1, true, nullptr, nullptr, nullptr, &ro));
   for (int a = 0; a < 3; ++a) dims_out[a] = ro.dims[a];
+  return 0;
+}
+
+int pyqsm_core_ramp_constants(double eps, int32_t radius_inclusive, float* out) {
+  if (!out) return fail(PYQSM_EINVAL, "pyqsm_core_ramp_constants: NULL pointer");
+  const CoreRamp cr = core_ramp(dbscan_r2(eps, radius_inclusive != 0));
+  out[0] = cr.lo, out[1] = cr.hi, out[2] = cr.K, out[3] = cr.A, out[4] = cr.B;
+  out[5] = cr.usable() ? 1.0f : 0.0f;
+  return 0;
+}
+
+int pyqsm_core_ramp_probe(const float* d, int64_t n, double eps, int32_t radius_inclusive, float* s_in_out,
+                          float* s_hi_out, int32_t device) {
+  PQ_API_RANGE("pyqsm_core_ramp_probe");
+  if (n < 0) return fail(PYQSM_EINVAL, "negative size");
+  const CoreRamp cr = core_ramp(dbscan_r2(eps, radius_inclusive != 0));
+  if (!cr.usable()) return fail(PYQSM_EINVAL, "pyqsm_core_ramp_probe: no ramp form at this eps");
+  if (n == 0) return 0;
+  if (!d || !s_in_out || !s_hi_out) return fail(PYQSM_EINVAL, "pyqsm_core_ramp_probe: NULL pointer");
+  Call call(device);
+  Ctx* c = call.c;
+  if (!c) return PYQSM_ENODEV;
+  float *d_d, *d_in, *d_hi;
+  PQ_TRY(upload(c, d, size_t(n), &d_d));
+  PQ_TRY(c->arena.get(size_t(n), &d_in));
+  PQ_TRY(c->arena.get(size_t(n), &d_hi));
+  hipLaunchKernelGGL(k_core_ramp_probe, dim3(ceil_div(ceil_div(n, 2), 256)), dim3(256), 0, c->stream, d_d, n, -cr.K,
+                     cr.A, cr.B, d_in, d_hi);
+  PQ_HIP(hipGetLastError());
+  PQ_TRY(fetch(c, s_in_out, d_in, size_t(n)));
+  PQ_TRY(fetch(c, s_hi_out, d_hi, size_t(n)));
   return 0;
 }
 

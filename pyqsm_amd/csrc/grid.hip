@@ -57,18 +57,29 @@ __host__ __device__ static inline bool interior_slabs(const double* mn, const do
 // cost 0.56 ms in the first version of this kernel). Stage 2: one block folds the
 // records.
 // part[block][7]: min keys, max keys, and 1 if every coordinate the block saw is exactly
-// representable in fp32 (double(float(v)) == v: true for PCD / LAS derived clouds), else 0
+// representable in fp32 (double(float(v)) == v: true for PCD / LAS derived clouds), else 0.
+// The kernel also clears `zero_n` ints for the caller, every block a slice (the bucket counters of the
+// binning that follows: two memset launches less on the critical path; the one-block fold did it until it
+// left DBSCAN's speculated step).
 static constexpr int kBoxVals = 7;
+// Two blocks per compute unit at most, 512 records on a MI355X: every block of k_bk_hist folds them all. (Four,
+// as it was while one block folded: k_bbox 9.3 us instead of 8.4 on the 1 M-point forest, and k_bk_hist 0.8 us
+// longer. A thread taking two or four points per sweep, their loads issued together: 7.9 and 8.2 us, less
+// than the 1.5 us the launch varies by from step to step: not kept. profiles/plan_fold_bbox_variants.txt)
+static int bbox_blocks(const Ctx* c, int64_t n) {
+  return int(std::min<int64_t>(ceil_div(n, 256), int64_t(c->cu_count) * 2));
+}
 __global__ __launch_bounds__(256) void k_bbox(const double* __restrict__ xyz, int64_t n,
                                               unsigned long long* __restrict__ part /*[grid][7]*/,
+                                              int32_t* __restrict__ zero_buf, int zero_n,
     unsigned long long* __restrict__ st /*stamps or null*/) {
   __shared__ unsigned long long red[4][6];
   __shared__ int red_f32[4];
   stamped(st, [&] {
   unsigned long long mn[3] = {~0ull, ~0ull, ~0ull}, mx[3] = {0, 0, 0};
   bool f32ok = true;
-  for (int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; i < n;
-       i += int64_t(gridDim.x) * blockDim.x) {
+  const int64_t stride = int64_t(gridDim.x) * blockDim.x;
+  for (int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; i < n; i += stride) {
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       const double v = xyz[3 * i + a];
@@ -78,6 +89,7 @@ __global__ __launch_bounds__(256) void k_bbox(const double* __restrict__ xyz, in
       mx[a] = k > mx[a] ? k : mx[a];
     }
   }
+  for (int64_t q = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; q < zero_n; q += stride) zero_buf[q] = 0;
   const bool wave_ok = __all(f32ok);
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
@@ -113,12 +125,13 @@ __global__ __launch_bounds__(256) void k_bbox(const double* __restrict__ xyz, in
 
 // (Folding in k_bbox itself — the block that counts itself last reads everybody's records — was tried
 // in round 3 to save this launch: the agent-scope release every block needs before it counts itself
-// writes its XCD's L2 back, and the binning went from 0.135 to 0.20 ms.)
-// One block folds the per-block records (the fp32 flag as a minimum: 0 wins) and, while it is
-// there, clears `zero_n` ints for the caller (the bucket counters of the binning that follows:
-// two memset launches less on the critical path).
-// With `plan` (DBSCAN), the fold also writes the grid plan of edge `cell` (see plan_grid_device), and
-// the same plan to `host` (host-mapped, coherent) with the sequence number `seq` stored last.
+// writes its XCD's L2 back, and the binning went from 0.135 to 0.20 ms. DBSCAN's speculated step has no
+// fold launch all the same: every block of k_bk_hist folds the records for itself, behind the kernel
+// boundary, with no ticket and no fence: fold_box_records below.)
+// One block folds the per-block records (the fp32 flag as a minimum: 0 wins).
+// With `plan` (DBSCAN without a hint), the fold also writes the grid plan of edge `cell` (see
+// plan_grid_device), and the same plan to `host` (host-mapped, coherent) with the sequence number `seq`
+// stored last.
 struct PlanIn {
   double cell;
   int64_t max_cells;
@@ -126,47 +139,56 @@ struct PlanIn {
   GridPlan* host;
   unsigned seq;
 };
-__device__ void write_plan(const unsigned long long* box, const PlanIn& in, GridPlan* __restrict__ plan);
+__device__ GridPlan make_plan(const unsigned long long* box, const PlanIn& in);
+__device__ void store_plan(GridPlan p, const PlanIn& in, GridPlan* __restrict__ plan);
 
-__global__ __launch_bounds__(256) void k_bbox_fold(const unsigned long long* __restrict__ part,
-                                                   int nblk, unsigned long long* __restrict__ out,
-                                                   int32_t* __restrict__ zero_buf, int zero_n,
-                                                   PlanIn pin, GridPlan* __restrict__ plan) {
-  __shared__ unsigned long long red[4][kBoxVals];
-  __shared__ unsigned long long fin[kBoxVals];
-  for (int q = threadIdx.x; q < zero_n; q += 256) zero_buf[q] = 0;
+// The records folded by a block of 256 threads into fin[kBoxVals] (shared), which the whole block may read
+// on return. Minima and maxima: every block that folds the same records gets the same box, whatever
+// the order. A thread issues the loads of two records, fourteen, before it waits for the first.
+__device__ __forceinline__ void fold_box_records(const unsigned long long* __restrict__ part, int nblk,
+                                                 unsigned long long (*red)[kBoxVals] /*[4], shared*/,
+                                                 unsigned long long* fin /*[kBoxVals], shared*/) {
+  const auto fold = [](int a, unsigned long long o, unsigned long long v) {
+    return (a < 3 || a == 6) ? (o < v ? o : v) : (o > v ? o : v);
+  };
   unsigned long long v[kBoxVals] = {~0ull, ~0ull, ~0ull, 0, 0, 0, ~0ull};
-  for (int b = threadIdx.x; b < nblk; b += 256)
+  for (int b0 = threadIdx.x; b0 < nblk; b0 += 512) {
+    unsigned long long o[2][kBoxVals];
 #pragma unroll
-    for (int a = 0; a < kBoxVals; ++a) {
-      const unsigned long long o = part[size_t(b) * kBoxVals + a];
-      v[a] = (a < 3 || a == 6) ? (o < v[a] ? o : v[a]) : (o > v[a] ? o : v[a]);
+    for (int u = 0; u < 2; ++u) {
+      const int b = b0 + 256 * u < nblk ? b0 + 256 * u : nblk - 1;  // (past the end: the last record twice)
+#pragma unroll
+      for (int a = 0; a < kBoxVals; ++a) o[u][a] = part[size_t(b) * kBoxVals + a];
     }
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int a = 0; a < kBoxVals; ++a) v[a] = fold(a, o[u][a], v[a]);
+  }
 #pragma unroll
   for (int a = 0; a < kBoxVals; ++a)
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const unsigned long long o = __shfl_down(v[a], off, 64);
-      v[a] = (a < 3 || a == 6) ? (o < v[a] ? o : v[a]) : (o > v[a] ? o : v[a]);
-    }
+    for (int off = 32; off > 0; off >>= 1) v[a] = fold(a, __shfl_down(v[a], off, 64), v[a]);
   if ((threadIdx.x & 63) == 0)
 #pragma unroll
     for (int a = 0; a < kBoxVals; ++a) red[threadIdx.x >> 6][a] = v[a];
   __syncthreads();
   if (threadIdx.x < kBoxVals) {
-    const bool is_min = threadIdx.x < 3 || threadIdx.x == 6;
     unsigned long long r = red[0][threadIdx.x];
-    for (int q = 1; q < 4; ++q) {
-      const unsigned long long o = red[q][threadIdx.x];
-      r = is_min ? (o < r ? o : r) : (o > r ? o : r);
-    }
-    out[threadIdx.x] = r;
+    for (int q = 1; q < 4; ++q) r = fold(int(threadIdx.x), red[q][threadIdx.x], r);
     fin[threadIdx.x] = r;
   }
-  if (plan) {  // kernel-uniform
-    __syncthreads();
-    if (threadIdx.x == 0) write_plan(fin, pin, plan);
-  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void k_bbox_fold(const unsigned long long* __restrict__ part,
+                                                   int nblk, unsigned long long* __restrict__ out,
+                                                   PlanIn pin, GridPlan* __restrict__ plan) {
+  __shared__ unsigned long long red[4][kBoxVals];
+  __shared__ unsigned long long fin[kBoxVals];
+  fold_box_records(part, nblk, red, fin);
+  if (threadIdx.x < kBoxVals) out[threadIdx.x] = fin[threadIdx.x];
+  if (plan && threadIdx.x == 0) store_plan(make_plan(fin, pin), pin, plan);  // (plan: kernel-uniform)
 }
 
 __global__ __launch_bounds__(256) void k_cell_count(const double* __restrict__ xyz, int64_t n,
@@ -374,13 +396,13 @@ int robust_box(Ctx* c, const double* xyz, int64_t n, int budget, double box[6], 
 int cloud_bbox(Ctx* c, const double* xyz, int64_t n, double mn[3], double mx[3], bool* all_f32,
                int32_t* zero_buf, int zero_n) {
   if (n <= 0) return fail(PYQSM_EINVAL, "bounding box of an empty cloud");
-  const int blocks = int(std::min<int64_t>(ceil_div(n, 256), int64_t(c->cu_count) * 4));
+  const int blocks = bbox_blocks(c, n);
   unsigned long long *d_box = nullptr, *d_part = nullptr;
   PQ_TRY(c->arena.get(kBoxVals, &d_box));
   PQ_TRY(c->arena.get(size_t(blocks) * kBoxVals, &d_part));
-  hipLaunchKernelGGL(k_bbox, dim3(blocks), dim3(256), 0, c->stream, xyz, n, d_part,
+  hipLaunchKernelGGL(k_bbox, dim3(blocks), dim3(256), 0, c->stream, xyz, n, d_part, zero_buf, zero_n,
                      static_cast<unsigned long long*>(nullptr));
-  hipLaunchKernelGGL(k_bbox_fold, dim3(1), dim3(256), 0, c->stream, d_part, blocks, d_box, zero_buf, zero_n, PlanIn{},
+  hipLaunchKernelGGL(k_bbox_fold, dim3(1), dim3(256), 0, c->stream, d_part, blocks, d_box, PlanIn{},
                      static_cast<GridPlan*>(nullptr));
   PQ_HIP(hipGetLastError());
   unsigned long long h_box[kBoxVals];
@@ -750,35 +772,79 @@ struct BkRec<false> {
   using type = PointRec;
 };
 
+// DBSCAN's speculated step (MODE 0) has no plan in memory when k_bk_hist starts: the launch takes the fold's
+// place. Every block folds k_bbox's records for itself and computes the plan in registers, all with the same
+// fp64 operations in the same order (make_plan), so the blocks agree with each other and with the host; a
+// block that finds ok == 0 leaves without a write. One block more than the histogram needs, the launch's
+// last, folds once more and stores the plan (store_plan): the kernels behind the next kernel boundary read
+// it from memory as they always did, and the host's slot is written earlier than the fold launch wrote it.
+// (The fold launch was one block of 8.4 us between k_bbox and this kernel.)
+struct PlanFold {
+  const unsigned long long* part = nullptr;  // k_bbox's records, or null: no fold
+  int nblk = 0;
+  PlanIn in{};
+  GridPlan* out = nullptr;
+};
+
 // MODE 0: cell and octant on the raw grid; 1: the same through the axis-compression maps;
 // 2: cell only, clamped into the grid's box (build_grid: what kNN and the radius queries bin with)
 template <int MODE>
 __global__ __launch_bounds__(256) void k_bk_hist(const double* __restrict__ xyz, int64_t n, GridParams g,
                                                  int rx, int ry, int rz, AxisMap am, int nbk, int bits,
                                                  int32_t* __restrict__ key_tmp,
-                                                 int32_t* __restrict__ tot, const GridPlan* __restrict__ plan) {
+                                                 int32_t* __restrict__ tot, const GridPlan* __restrict__ plan,
+                                                 PlanFold pf) {
   extern __shared__ __attribute__((aligned(16))) int32_t h[];
-  if (plan) {  // DBSCAN: the grid comes from the plan (the LDS was sized for at least its nbk)
-    if (!plan->ok) return;
-    g = GridParams{plan->mn[0], plan->mn[1], plan->mn[2], plan->inv_cell, plan->nx, plan->ny, plan->nz};
-    rx = plan->rx;
-    ry = plan->ry;
-    rz = plan->rz;
-    nbk = plan->nbk;
-    bits = plan->bits;
+  __shared__ unsigned long long red[4][kBoxVals];  // (the fold's)
+  __shared__ unsigned long long fin[kBoxVals];
+  const bool folds = MODE == 0 && pf.part != nullptr;        // kernel-uniform
+  const bool stores = folds && blockIdx.x + 1 == gridDim.x;  // block-uniform: the role behind the histogram's blocks
+  // the block's points first (MODE 0: DBSCAN's raw grid): their loads are in flight during the fold. The other
+  // modes load where they use, as they did.
+  const int64_t base = int64_t(blockIdx.x) * kBkPts;
+  double px[kBkPts / 256], py[kBkPts / 256], pz[kBkPts / 256];
+#pragma unroll
+  for (int k = 0; k < kBkPts / 256; ++k) {
+    const int64_t i = base + k * 256 + threadIdx.x;
+    px[k] = py[k] = pz[k] = 0.0;
+    if (MODE == 0 && i < n) {
+      px[k] = xyz[3 * i];
+      py[k] = xyz[3 * i + 1];
+      pz[k] = xyz[3 * i + 2];
+    }
+  }
+  if (folds || plan) {  // DBSCAN: the grid comes from the plan (the LDS was sized for at least its nbk)
+    GridPlan pl;
+    if (folds) {
+      fold_box_records(pf.part, pf.nblk, red, fin);
+      pl = make_plan(fin, pf.in);
+      if (stores) {
+        if (threadIdx.x == 0) store_plan(pl, pf.in, pf.out);
+        return;
+      }
+    } else {
+      pl = *plan;
+    }
+    if (!pl.ok) return;
+    g = GridParams{pl.mn[0], pl.mn[1], pl.mn[2], pl.inv_cell, pl.nx, pl.ny, pl.nz};
+    rx = pl.rx;
+    ry = pl.ry;
+    rz = pl.rz;
+    nbk = pl.nbk;
+    bits = pl.bits;
   }
   for (int b = threadIdx.x; b < nbk; b += 256) h[b] = 0;
   __syncthreads();
-  const int64_t base = int64_t(blockIdx.x) * kBkPts;
 #pragma unroll
   for (int k = 0; k < kBkPts / 256; ++k) {
     const int64_t i = base + k * 256 + threadIdx.x;
     if (i < n) {
       int c, oct = 0;
+      if (MODE != 0) px[k] = xyz[3 * i], py[k] = xyz[3 * i + 1], pz[k] = xyz[3 * i + 2];
       if (MODE == 2) {
-        c = cell_index(g, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
+        c = cell_index(g, px[k], py[k], pz[k]);
       } else {
-        const RawCell r = raw_cell(g, rx, ry, rz, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
+        const RawCell r = raw_cell(g, rx, ry, rz, px[k], py[k], pz[k]);
         const int cx = MODE == 1 ? am.x[r.cx] : r.cx + 1, cy = MODE == 1 ? am.y[r.cy] : r.cy + 1,
                   cz = MODE == 1 ? am.z[r.cz] : r.cz + 1;
         c = (cz * g.ny + cy) * g.nx + cx;
@@ -1428,13 +1494,15 @@ static void on_sort_shape(int bits, bool f32, F&& launch) {
 // the A passes; `bucketed` holds float4 (f32) or PointRec records
 static void enqueue_bk_a(Ctx* c, int mode, bool f32, const double* xyz, int64_t n, const GridParams& gp,
                          const int raw[3], AxisMap am, int64_t nbk, int bits, int32_t* key_tmp, int32_t* tot,
-                         int32_t* cursor, int32_t* bstart, void* bucketed, int32_t* keyb, const GridPlan* d_plan) {
+                         int32_t* cursor, int32_t* bstart, void* bucketed, int32_t* keyb, const GridPlan* d_plan,
+                         const PlanFold& pf = PlanFold{}) {
   const dim3 ga(ceil_div(n, kBkPts)), blk(256);
+  const dim3 gh(ga.x + (pf.part ? 1 : 0));  // (the block that stores the folded plan)
   const size_t lds = size_t(nbk) * 4;
   const int fused = nbk <= kBkFusedScan;
 #define PQ_BK_HIST(MODE)                                                                                         \
-  hipLaunchKernelGGL(k_bk_hist<MODE>, ga, blk, lds, c->stream, xyz, n, gp, raw[0], raw[1], raw[2], am, int(nbk), \
-                     bits, key_tmp, tot, d_plan)
+  hipLaunchKernelGGL(k_bk_hist<MODE>, gh, blk, lds, c->stream, xyz, n, gp, raw[0], raw[1], raw[2], am, int(nbk), \
+                     bits, key_tmp, tot, d_plan, pf)
   if (mode == 0)
     PQ_BK_HIST(0);
   else if (mode == 1)
@@ -1494,7 +1562,7 @@ static int build_grid_bucketed(Ctx* c, const double* xyz, int64_t n, DevGrid* g)
 
 // bin_octants_host's first trial: interior_slabs and bucket_shape are the host's own, so that every
 // point lands in the same cell
-__device__ void write_plan(const unsigned long long* box, const PlanIn& in, GridPlan* __restrict__ plan) {
+__device__ GridPlan make_plan(const unsigned long long* box, const PlanIn& in) {
   GridPlan p;
   bool ok = in.hint.valid != 0;
   for (int a = 0; a < 3; ++a) {
@@ -1525,6 +1593,11 @@ __device__ void write_plan(const unsigned long long* box, const PlanIn& in, Grid
   p.bits = 12;
   p.ok = ok ? 1 : 0;
   p.seq = in.seq;
+  return p;
+}
+
+// ... and where it goes: d_plan for the kernels behind the next kernel boundary, the host's slot for wait_plan
+__device__ void store_plan(GridPlan p, const PlanIn& in, GridPlan* __restrict__ plan) {
   *plan = p;
   if (in.host) {
     // the host polls the sequence number: everything else first, visible to the host before it
@@ -1537,15 +1610,20 @@ __device__ void write_plan(const unsigned long long* box, const PlanIn& in, Grid
 }
 
 int plan_grid_device(Ctx* c, const double* xyz, int64_t n, double cell, int64_t max_cells, const PlanHint& hint,
-                     GridPlan* d_plan, GridPlan* h_plan, unsigned seq, int32_t* zero_buf, int zero_n) {
+                     GridPlan* d_plan, GridPlan* h_plan, unsigned seq, int32_t* zero_buf, int zero_n,
+                     PlanRecords* speculated) {
   if (n <= 0) return fail(PYQSM_EINVAL, "bounding box of an empty cloud");
-  const int blocks = int(std::min<int64_t>(ceil_div(n, 256), int64_t(c->cu_count) * 4));
+  const int blocks = bbox_blocks(c, n);
   unsigned long long *d_box = nullptr, *d_part = nullptr;
   PQ_TRY(c->arena.get(kBoxVals, &d_box));
   PQ_TRY(c->arena.get(size_t(blocks) * kBoxVals, &d_part));
-  hipLaunchKernelGGL(k_bbox, dim3(blocks), dim3(256), 0, c->stream, xyz, n, d_part, stamp_slots(c, blocks));
-  hipLaunchKernelGGL(k_bbox_fold, dim3(1), dim3(256), 0, c->stream, d_part, blocks, d_box, zero_buf, zero_n,
-                     PlanIn{cell, max_cells, hint, h_plan, seq}, d_plan);
+  hipLaunchKernelGGL(k_bbox, dim3(blocks), dim3(256), 0, c->stream, xyz, n, d_part, zero_buf, zero_n,
+                     stamp_slots(c, blocks));
+  if (speculated)
+    *speculated = PlanRecords{d_part, blocks, max_cells, h_plan, seq};
+  else
+    hipLaunchKernelGGL(k_bbox_fold, dim3(1), dim3(256), 0, c->stream, d_part, blocks, d_box,
+                       PlanIn{cell, max_cells, hint, h_plan, seq}, d_plan);
   PQ_HIP(hipGetLastError());
   return 0;
 }
@@ -1559,7 +1637,8 @@ int octant_zeroed_ints() { return 2 * kBkMax + 5 + kZeroedExtra; }
 // read the grid itself from d_plan.
 static int enqueue_bucketed(Ctx* c, const double* xyz, int64_t n, const GridParams& gp, const int raw[3],
                             AxisMap am, bool mapped, int64_t nbk, int bits, bool f32,
-                            int32_t* zeroed, const GridPlan* d_plan, DevGrid* g, SubCells* sub) {
+                            int32_t* zeroed, const GridPlan* d_plan, DevGrid* g, SubCells* sub,
+                            const PlanFold& pf = PlanFold{}) {
   int32_t *cell_tmp, *keyb, *rank_tmp, *bstart;
   uint32_t* word_tmp;
   int32_t *tot = zeroed, *cursor = zeroed + kBkMax;
@@ -1596,7 +1675,7 @@ static int enqueue_bucketed(Ctx* c, const double* xyz, int64_t n, const GridPara
   PQ_TRY(c->arena.get(size_t(n) * 8, &sub->rec));
   PQ_TRY(c->arena.get(size_t(nbk) + 1, &bstart));
   enqueue_bk_a(c, mapped ? 1 : 0, f32, xyz, n, gp, raw, am, nbk, bits, cell_tmp, tot, cursor, bstart, bucketed, keyb,
-               d_plan);
+               d_plan, pf);
   on_sort_shape(bits, f32, [&](auto S) {
     using K = decltype(S);
     unsigned long long* const st_sort = stamp_slots(c, nbk);  // the binning's last kernel
@@ -1651,7 +1730,7 @@ void read_directory(Ctx* c, const DevGrid& g, int64_t ncell, int32_t* begin_out)
 }
 
 int bin_octants_planned(Ctx* c, const double* xyz, int64_t n, double cell, const PlanHint& hint,
-                        const GridPlan* d_plan, int32_t* zeroed, DevGrid* g, SubCells* sub) {
+                        const PlanRecords& rec, GridPlan* d_plan, int32_t* zeroed, DevGrid* g, SubCells* sub) {
   // the host knows the edge (never doubled on this path) and the bounds of the directory, not its shape
   g->minx = g->miny = g->minz = 0.0;
   g->cell = cell;
@@ -1661,7 +1740,8 @@ int bin_octants_planned(Ctx* c, const double* xyz, int64_t n, double cell, const
   sub->zeroed4 = zeroed + 2 * kBkMax + 1;
   const int raw[3] = {0, 0, 0};
   return enqueue_bucketed(c, xyz, n, GridParams{}, raw, AxisMap{nullptr, nullptr, nullptr}, false, hint.nbk, 12,
-                          true, zeroed, d_plan, g, sub);
+                          true, zeroed, d_plan, g, sub,
+                          PlanFold{rec.part, rec.blocks, PlanIn{cell, rec.max_cells, hint, rec.h_plan, rec.seq}, d_plan});
 }
 
 static int upload_plan(Ctx* c, const GridPlan& p, GridPlan* h_up, GridPlan* d_plan) {

@@ -143,7 +143,7 @@ int build_grid(Ctx* c, const double* xyz, int64_t n, double min_cell, int64_t ma
 
 // Bounding box of the cloud (one reduction kernel, a one-block fold, a 56-byte read-back).
 // *all_f32 (optional): every coordinate is exactly representable in fp32. zero_buf / zero_n
-// (optional): ints the fold kernel clears on the way (saves the caller a memset launch).
+// (optional): ints the reduction kernel clears on the way (saves the caller a memset launch).
 int cloud_bbox(Ctx* c, const double* xyz, int64_t n, double mn[3], double mx[3], bool* all_f32 = nullptr,
                int32_t* zero_buf = nullptr, int zero_n = 0);
 // Shrinks box (min xyz, max xyz) to the part of the cloud that is left when at most `budget`
@@ -403,17 +403,29 @@ __device__ __forceinline__ Stencil plan_stencil(const GridPlan* p) { return Sten
 // (PlanHint, the launch shapes a device-planned call is enqueued with, lives in common.hpp: the
 // context keeps the last one.)
 
-// k_bbox + the fold, which writes the plan of a grid of edge `cell` (at most `max_cells` cells)
-// into d_plan and into h_plan (host-mapped, coherent: no copy, no event; h_plan->seq = seq once the
-// rest of it is visible to the host) and clears zero_n ints of zero_buf. Does not synchronise.
+// k_bbox, which also clears zero_n ints of zero_buf, + the fold, which writes the plan of a grid of edge
+// `cell` (at most `max_cells` cells) into d_plan and into h_plan (host-mapped, coherent: no copy, no
+// event; h_plan->seq = seq once the rest of it is visible to the host). Does not synchronise.
+// With `speculated` (there is a hint, and bin_octants_planned follows at once) there is no fold launch: the
+// binning's first kernel folds k_bbox's records, uses the plan and stores it to both places; *speculated is
+// what it needs for that.
+struct PlanRecords {
+  const unsigned long long* part;  // k_bbox's records
+  int blocks;
+  int64_t max_cells;
+  GridPlan* h_plan;
+  unsigned seq;
+};
 int plan_grid_device(Ctx* c, const double* xyz, int64_t n, double cell, int64_t max_cells, const PlanHint& hint,
-                     GridPlan* d_plan, GridPlan* h_plan, unsigned seq, int32_t* zero_buf, int zero_n);
-// Zeroed ints plan_grid_device must clear for the binning below (the bucket totals, reservation
+                     GridPlan* d_plan, GridPlan* h_plan, unsigned seq, int32_t* zero_buf, int zero_n,
+                     PlanRecords* speculated = nullptr);
+// Zeroed ints plan_grid_device (k_bbox) must clear for the binning below (the bucket totals, reservation
 // cursors and the big-cell counter) plus kZeroedExtra + 4 for the caller.
 int octant_zeroed_ints();
-// The octant binning enqueued with the hint's shapes; every kernel reads the grid from d_plan.
+// The octant binning enqueued with the hint's shapes. Its first kernel plans from `rec` and writes d_plan
+// (and the host's slot); every later kernel reads the grid from d_plan.
 int bin_octants_planned(Ctx* c, const double* xyz, int64_t n, double cell, const PlanHint& hint,
-                        const GridPlan* d_plan, int32_t* zeroed, DevGrid* g, SubCells* sub);
+                        const PlanRecords& rec, GridPlan* d_plan, int32_t* zeroed, DevGrid* g, SubCells* sub);
 // The octant binning planned on the host from the box and fp32 flag of `box` (read back from
 // plan_grid_device; finite-checked here: PYQSM_EINVAL). Writes the exact plan to *h_exact, uploads
 // it through h_up (page-locked) to d_plan, and *hint_out = the hint it makes (valid = 0: the grid is

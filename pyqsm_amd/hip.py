@@ -241,6 +241,32 @@ def octant_directory(points, eps: float, device: int = 0, cap: int = 1 << 25):
     return dims, begin[: int(np.prod(dims.astype(np.int64))) + 1].copy()
 
 
+class CoreRamp(NamedTuple):
+    lo: np.float32
+    hi: np.float32
+    K: np.float32
+    A: np.float32
+    B: np.float32
+    usable: bool
+
+
+def core_ramp_constants(eps: float, radius_inclusive: bool = True) -> CoreRamp:
+    """The fp32 thresholds and ramp constants of DBSCAN's core pass at ``eps`` (for tests; no GPU)."""
+    out = np.zeros(6, dtype=np.float32)
+    check(_lib.load().pyqsm_core_ramp_constants(float(eps), int(bool(radius_inclusive)), _p(out)))
+    return CoreRamp(out[0], out[1], out[2], out[3], out[4], bool(out[5] != 0))
+
+
+def core_ramp_probe(d, eps: float, radius_inclusive: bool = True, device: int = 0):
+    """(s_in, s_hi) float32 [n]: the core pass's two ramps of the squared distances ``d``, on the device."""
+    d = np.ascontiguousarray(np.asarray(d), dtype=np.float32).reshape(-1)
+    s_in = np.empty_like(d)
+    s_hi = np.empty_like(d)
+    check(_lib.load().pyqsm_core_ramp_probe(_p(d), d.shape[0], float(eps), int(bool(radius_inclusive)),
+                                            _p(s_in), _p(s_hi), int(device)))
+    return s_in, s_hi
+
+
 def knn(points, k: int, exclude_self: bool = True, device: int = 0):
     """idx int32 [n,k], squared distances float64 [n,k], ascending by (d2, index)."""
     pts = _points(points)
