@@ -1078,6 +1078,88 @@ int pyqsm_pdist_select(const double* pts, int64_t n, int32_t dim, const int64_t*
                        const int64_t* ranks, int32_t n_ranks, int64_t max_pairs, double* values, int64_t* n_pairs,
                        int64_t* max_pair, int64_t* stats, int32_t device);
 
+/* ---- epiphyte split: percentile cuts of a per-row key, k-means++ clumps ------------------- */
+/*
+ * The two stages of pyQSM's canopy_metrics.identify_epiphytes between the contraction's first shift
+ * and the batched alpha-shape area (tests/epiphyte_restatement.py states the
+ * contract in NumPy).
+ *
+ * pyqsm_select_values: the elements of given ranks of the sorted keys of n rows.
+ *   v f64 [n, width], width 1 or 3. key: a component 0 <= key < width, or PYQSM_KEY_NORM (width 3):
+ *   sqrt(((x*x) + (y*y)) + (z*z)), correctly rounded, no contraction. Keys order as the doubles do,
+ *   negative ones included; -0.0 is keyed as +0.0 (and comes back as +0.0). A NaN anywhere in v:
+ *   PYQSM_EINVAL. ranks i64 [n_ranks], 0-based, n_ranks from 0 to PYQSM_PDIST_MAX_RANKS; values f64
+ *   [n_ranks]: values[r] = the key of rank ranks[r] in ascending order. A rank < 0 marks an unused
+ *   slot, which receives 0.0; a rank >= n: PYQSM_EINVAL. n == 0 is answered on the host.
+ *   A radix selection as pyqsm_pdist_select's: keys recomputed from the rows in each of eight 8-bit
+ *   passes, integer histograms, nothing read back between the passes, memory O(n + n_ranks * 256).
+ *   The _dev form takes device rows.
+ * pyqsm_split_above_dev: the rows i with cmp(key(row i), threshold), cmp 0 >, 1 >=, 2 <, 3 <=, of the
+ *   device rows v_dev, selected by scan: idx_dev i64 [capacity n] (may be NULL) their indices,
+ *   ascending; out_rows_dev f64 [capacity n, 3] row i of rows_dev f64 [n, 3] for each of them (both
+ *   may be NULL). *count (host) = how many; reading it synchronises. A NaN threshold: PYQSM_EINVAL.
+ * pyqsm_shift_components: the three-way split of identify_epiphytes in one call. shift f64 [n, 3].
+ *   thresholds[0] = P(q_mag) of the row norms; the rows with norm > thresholds[0] are "high";
+ *   thresholds[1] = P(q_z) of the high rows' z (NaN when there is none). labels u8 [n]: 0 norm not
+ *   above thresholds[0]; 1 high and z > thresholds[1] (leaf); 2 the other high rows (epiphyte).
+ *   counts i64 [3] = rows per label. P(q) is NumPy's default percentile of m values: with
+ *   v = (m - 1) * (q / 100), lo = floor(v), t = v - lo, a and b the order statistics of ranks lo and
+ *   min(lo + 1, m - 1): a + (b - a) * t, b - (b - a) * (1 - t) where t >= 0.5, a where t == 0; taken
+ *   once, on the host, from two selected values. q outside [0, 100] or a NaN in shift: PYQSM_EINVAL.
+ *   n == 0: NaN thresholds, zero counts, no device work. The _dev form takes device shift and labels.
+ */
+#define PYQSM_KEY_NORM (-1)
+int pyqsm_select_values(const double* v, int64_t n, int32_t width, int32_t key, const int64_t* ranks, int32_t n_ranks,
+                        double* values, int32_t device);
+int pyqsm_select_values_dev(const double* v_dev, int64_t n, int32_t width, int32_t key, const int64_t* ranks,
+                            int32_t n_ranks, double* values, int32_t device);
+int pyqsm_split_above_dev(const double* v_dev, int64_t n, int32_t width, int32_t key, int32_t cmp, double threshold,
+                          const double* rows_dev, int64_t* idx_dev, double* out_rows_dev, int64_t* count,
+                          int32_t device);
+int pyqsm_shift_components(const double* shift, int64_t n, double q_mag, double q_z, uint8_t* labels,
+                           double* thresholds, int64_t* counts, int32_t device);
+int pyqsm_shift_components_dev(const double* shift_dev, int64_t n, double q_mag, double q_z, uint8_t* labels_dev,
+                               double* thresholds, int64_t* counts, int32_t device);
+/*
+ * pyqsm_kmeans_pp: k-means of n points x f64 [n, d], d 1, 2 or 3, into 1 <= k <= PYQSM_KMEANSPP_MAX_K
+ *   centres, n >= k (anything else: PYQSM_EINVAL), modelled on scikit-learn 1.7's
+ *   KMeans(init="k-means++", n_init=1, algorithm="lloyd"). "Chunk sum" is the reduction stated above
+ *   pyqsm_kmeans. The coordinates are finite (a precondition, not checked).
+ *   Centring: mu_j = chunk sum of column j / n; all work is on x - mu;
+ *     tol_abs = tol * ((s_0 + s_1 + s_2) / d), s_j = chunk sum of (x_j - mu_j)^2 / n, added in this
+ *     order; mu is added back to the centres at the end.
+ *   Distances: ((dx*dx) + dy*dy) + dz*dz in fp64, d = point - centre, always direct; the nearest
+ *     centre is the argmin, ties to the lowest centre.
+ *   Seeding: greedy k-means++ with T = 2 + int(ln k) trials per step. The caller draws the random
+ *     numbers: `first`, the first centre's point, and u f64 [(k - 1) * T] uniforms in [0, 1), n_u of
+ *     them (PYQSM_EINVAL otherwise). closest_i = the squared distance to the nearest chosen centre;
+ *     a chunk total is the chunk sum of 256 consecutive closest; pot = the chunk totals added one at a
+ *     time from 0.0. Step c = 1 .. k - 1, trial t: r = u[(c - 1) T + t] * pot. The chunk is the first
+ *     whose cumulative total (the totals added in order from 0.0) is >= r, the last chunk if none is;
+ *     inside it closest is added one value at a time to the cumulative total before the chunk, and the
+ *     candidate is the first point at which the sum is >= r, the chunk's last point if none is. A
+ *     trial's potential is the chunk totals of min(closest, squared distance to the candidate) added
+ *     in order; the smallest wins, ties to the earlier trial. pot == 0 thus selects point 0.
+ *   Lloyd: assign; per centre the masked chunk sums of each coordinate (a non-member counts 0.0), the
+ *     chunk totals added in chunk order, over the member count give the new centre; a centre without
+ *     members keeps its place (scikit-learn relocates it). After every update, in this order: labels
+ *     equal to the previous iteration's: stop (strict convergence); the sum over the centres, in order
+ *     from 0.0, of ((ex*ex) + ey*ey) + ez*ez, e = new - old centre, <= tol_abs: stop; max_iter
+ *     iterations done: stop. Unless the stop was strict, the points are assigned once more to the final
+ *     centres. (scikit-learn squares the rounded norm of e and sums pairwise: the same up to rounding.)
+ *   labels i32 [n]; centres f64 [k, d]; *inertia = chunk sum of the squared distances to the labelled
+ *   centres; *n_iter; *n_empty = centres without a member in labels; seeds i64 [k] the seeding's points.
+ *   Iterations are queued in bursts (4, 4, 8, 16, then 32) behind a device-side "done" word, so the
+ *   later ones of a burst are no-ops, and one small record is read per burst. No float atomics: every run gives the same bits. The _dev form takes device points.
+ */
+#define PYQSM_KMEANSPP_MAX_K 64
+int pyqsm_kmeans_pp(const double* x, int64_t n, int32_t d, int32_t k, int64_t first, const double* u, int64_t n_u,
+                    int32_t max_iter, double tol, int32_t* labels, double* centres, double* inertia, int32_t* n_iter,
+                    int32_t* n_empty, int64_t* seeds, int32_t device);
+int pyqsm_kmeans_pp_dev(const double* x_dev, int64_t n, int32_t d, int32_t k, int64_t first, const double* u,
+                        int64_t n_u, int32_t max_iter, double tol, int32_t* labels, double* centres, double* inertia,
+                        int32_t* n_iter, int32_t* n_empty, int64_t* seeds, int32_t device);
+
 #ifdef __cplusplus
 }
 #endif

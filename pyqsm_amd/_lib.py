@@ -84,6 +84,15 @@ SIGNATURES = {
     "pyqsm_alpha_area": (ctypes.c_int, [vp, i64, vp, i64, ctypes.c_uint64, i64, i32, vp, vp, vp,
                                         ctypes.POINTER(vp), vp, i32]),
     "pyqsm_pdist_select": (ctypes.c_int, [vp, i64, i32, vp, i64, vp, i32, i64, vp, vp, vp, vp, i32]),
+    "pyqsm_select_values": (ctypes.c_int, [vp, i64, i32, i32, vp, i32, vp, i32]),
+    "pyqsm_select_values_dev": (ctypes.c_int, [vp, i64, i32, i32, vp, i32, vp, i32]),
+    "pyqsm_split_above_dev": (ctypes.c_int, [vp, i64, i32, i32, i32, dbl, vp, vp, vp, ctypes.POINTER(i64), i32]),
+    "pyqsm_shift_components": (ctypes.c_int, [vp, i64, dbl, dbl, vp, vp, vp, i32]),
+    "pyqsm_shift_components_dev": (ctypes.c_int, [vp, i64, dbl, dbl, vp, vp, vp, i32]),
+    "pyqsm_kmeans_pp": (ctypes.c_int, [vp, i64, i32, i32, i64, vp, i64, i32, dbl, vp, vp, ctypes.POINTER(dbl),
+                                       ctypes.POINTER(i32), ctypes.POINTER(i32), vp, i32]),
+    "pyqsm_kmeans_pp_dev": (ctypes.c_int, [vp, i64, i32, i32, i64, vp, i64, i32, dbl, vp, vp, ctypes.POINTER(dbl),
+                                           ctypes.POINTER(i32), ctypes.POINTER(i32), vp, i32]),
     "pyqsm_mesh_topology": (ctypes.c_int, [vp, i64, i64, vp, ctypes.POINTER(vp), ctypes.POINTER(vp),
                                            ctypes.POINTER(vp), vp, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp,
                                            i32]),

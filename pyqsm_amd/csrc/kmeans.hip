@@ -21,6 +21,7 @@
 // as ((v0 + v1) + v2) + v3, then an xor butterfly over the 64 lanes (pairs of neighbours first);
 // the chunk totals are added one at a time from 0.0 in chunk order.
 #include "grid.hpp"  // sqdist3
+#include "reduce.hpp"  // chunk_wave_sum, kChunk
 
 #include <cmath>
 
@@ -28,16 +29,8 @@ namespace pyqsm {
 
 static constexpr int kKmMaxK = PYQSM_KMEANS_MAX_K;  // centroids per labelling
 static constexpr int kLloydThreads = 1024;          // one workgroup per labelling
-static constexpr int kChunk = 256;                  // values per chunk-sum chunk (one wave)
 static constexpr int kSilTile = 256;                // points staged per LDS tile
 static constexpr int kSilThreads = 64;              // one wave per block of 64 query points
-
-__device__ __forceinline__ double chunk_wave_sum(double v0, double v1, double v2, double v3) {
-  double s = ((v0 + v1) + v2) + v3;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) s = s + __shfl_xor(s, off, 64);
-  return s;  // the same bits in every lane: a + b == b + a
-}
 
 // ---------------------------------------------------------------- Lloyd
 

@@ -10,7 +10,7 @@
 // carries the group's prefix by their next digit; a one-wave kernel per segment then turns each
 // histogram into the next prefix and the remaining rank and regroups the ranks, on the device. All
 // counters are integers summed by integer atomics: the same bits on every run.
-#include "common.hpp"
+#include "reduce.hpp"  // k_radix_select_update: a histogram becomes the next prefix, the ranks regroup
 
 #include <algorithm>
 #include <cmath>
@@ -172,63 +172,6 @@ __global__ __launch_bounds__(kPdTile) void k_pdist_hist(
   if (seg >= 0) flush();
 }
 
-// Between two passes, one wave per segment, lane r for rank slot r: the bin of the group's histogram
-// that holds the rank becomes the next digit of the slot's prefix, the pairs in the bins before it
-// leave the rank. Then the slots are regrouped by their new prefix (the first slot of a prefix leads
-// its group, groups numbered in slot order) and the segment's histograms are cleared for the next pass.
-__global__ __launch_bounds__(64) void k_pdist_update(int n_ranks, u64* __restrict__ hist, u64* __restrict__ prefix,
-                                                     u64* __restrict__ remaining, int32_t* __restrict__ group,
-                                                     int32_t* __restrict__ gcount, u64* __restrict__ gprefix) {
-  __shared__ u64 s_pre[kPdMaxRanks];
-  __shared__ int s_lead[kPdMaxRanks];
-  const int s = blockIdx.x, r = threadIdx.x;
-  const size_t slot = size_t(s) * n_ranks + r;
-  const int old_groups = gcount[s];
-  u64* h = hist + size_t(s) * n_ranks * kPdBins;
-  const int g = r < n_ranks ? group[slot] : -1;
-  u64 pre = 0;
-  if (g >= 0) {
-    const u64* hg = h + size_t(g) * kPdBins;
-    u64 k = remaining[slot], before = 0;
-    int bin = kPdBins - 1;
-    for (int d = 0; d < kPdBins; ++d) {
-      const u64 c = hg[d];
-      if (k < before + c) {
-        bin = d;
-        break;
-      }
-      before += c;
-    }
-    remaining[slot] = k - before;
-    pre = (prefix[slot] << 8) | u64(bin);
-    prefix[slot] = pre;
-  }
-  if (r < kPdMaxRanks) s_pre[r] = pre;
-  __syncthreads();
-  for (int k = r; k < old_groups * kPdBins; k += 64) h[k] = 0;
-  int leader = -1;
-  if (g >= 0) {
-    for (int q = 0; q <= r; ++q)
-      if (group[size_t(s) * n_ranks + q] >= 0 && s_pre[q] == pre) {
-        leader = q;
-        break;
-      }
-  }
-  if (r < kPdMaxRanks) s_lead[r] = leader == r;
-  __syncthreads();  // every slot's group has been read
-  if (g >= 0) {
-    int id = 0;
-    for (int q = 0; q < leader; ++q) id += s_lead[q];
-    group[slot] = id;
-    if (leader == r) gprefix[size_t(s) * n_ranks + id] = pre;
-  }
-  if (r == 0) {
-    int n = 0;
-    for (int q = 0; q < n_ranks; ++q) n += s_lead[q];
-    gcount[s] = n;
-  }
-}
-
 template <int MODE>
 static int pd_launch_hist(Ctx* c, int dim, int grid, size_t lds, const double* pts, const int64_t* seg_start,
                           const int64_t* tile0, int n_seg, int64_t total_tiles, int64_t tiles_per_block, int n_ranks,
@@ -340,7 +283,7 @@ int pyqsm_pdist_select(const double* pts, int64_t n, int32_t dim, const int64_t*
       PQ_TRY(pd_launch_hist<kPdPlain>(c, dim, grid, lds, d_pts, d_seg, d_tile0, int(n_seg), total_tiles,
                                       tiles_per_block, R, p, d_gcount, d_gprefix, d_hist, d_maxkey, d_maxpair));
     if (!any_rank) return 0;
-    hipLaunchKernelGGL(k_pdist_update, dim3(unsigned(n_seg)), dim3(64), 0, c->stream, R, d_hist, d_prefix, d_rem,
+    hipLaunchKernelGGL((k_radix_select_update<kPdBins, kPdMaxRanks>), dim3(unsigned(n_seg)), dim3(64), 0, c->stream, R, d_hist, d_prefix, d_rem,
                        d_group, d_gcount, d_gprefix);
     PQ_HIP(hipGetLastError());
     return 0;

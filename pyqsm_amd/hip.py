@@ -831,6 +831,168 @@ def pdist_select(points, seg_start, ranks, max_pairs: int = 0, device: int = 0) 
     return PdistSelect(values, n_pairs[:n_seg], far[:n_seg], stats)
 
 
+# ---------------------------------------------------------------- epiphyte split: selection, labels, k-means++
+
+KEY_NORM = -1                   # PYQSM_KEY_NORM
+SELECT_MAX_RANKS = PDIST_MAX_RANKS
+COMPARISONS = {"gt": 0, "ge": 1, "lt": 2, "le": 3}
+KMEANSPP_MAX_K = 64             # PYQSM_KMEANSPP_MAX_K
+
+
+def _rows(values):
+    """float64 [n, 1] or [n, 3] rows of a [n] or [n, 3] array."""
+    v = np.ascontiguousarray(np.asarray(values), dtype=np.float64)
+    if v.ndim == 1:
+        v = v.reshape(-1, 1)
+    if v.ndim != 2 or v.shape[1] not in (1, 3):
+        raise ValueError(f"expected values of shape [n] or [n,3], got {v.shape}")
+    return v
+
+
+def _key(key, width: int) -> int:
+    if key == "norm":
+        key = KEY_NORM
+    key = int(key)
+    if key == KEY_NORM and width == 3 or 0 <= key < width:
+        return key
+    raise ValueError(f"key must be a column below {width}" + (" or 'norm'" if width == 3 else "") + f", got {key!r}")
+
+
+def _ranks(ranks, n: int) -> np.ndarray:
+    rk = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
+    if rk.shape[0] > SELECT_MAX_RANKS:
+        raise ValueError(f"at most {SELECT_MAX_RANKS} ranks per call")
+    if (rk >= n).any():
+        raise ValueError(f"a rank beyond the {n} values")
+    return rk
+
+
+def _select_check(code: int) -> None:
+    """A NaN among the values is a ValueError, as np.percentile's callers expect."""
+    if code == -1 and b"NaN" in (_lib.load().pyqsm_last_error() or b""):
+        raise ValueError("the values hold a NaN")
+    check(code)
+
+
+def select_values(values, ranks, key=0, device: int = 0) -> np.ndarray:
+    """``pyqsm_select_values``: ``np.sort(keys)[ranks]`` bit for bit (-0.0 comes back as 0.0), the keys
+    of ``values`` [n] or [n,3] being column ``key`` or, with ``key='norm'``, the row norms
+    ``sqrt(((x*x) + (y*y)) + (z*z))``. At most 32 ranks; a negative rank is an unused slot (0.0)."""
+    v = _rows(values)
+    rk = _ranks(ranks, v.shape[0])
+    out = np.zeros(rk.shape[0])
+    _select_check(_lib.load().pyqsm_select_values(_p(v), v.shape[0], v.shape[1], _key(key, v.shape[1]), _p(rk),
+                                                  rk.shape[0], _p(out), int(device)))
+    return out
+
+
+def select_values_dev(v_ptr: int, n: int, width: int, ranks, key=0, device: int = 0) -> np.ndarray:
+    """:func:`select_values` on ``n`` device-resident rows of ``width`` values."""
+    rk = _ranks(ranks, int(n))
+    out = np.zeros(rk.shape[0])
+    _select_check(_lib.load().pyqsm_select_values_dev(v_ptr, int(n), int(width), _key(key, int(width)), _p(rk),
+                                                      rk.shape[0], _p(out), int(device)))
+    return out
+
+
+def split_above_dev(v_ptr: int, n: int, width: int, threshold: float, key=0, cmp: str = "gt", rows_ptr=None,
+                    idx_ptr=None, out_rows_ptr=None, device: int = 0) -> int:
+    """``pyqsm_split_above_dev``: the device rows with ``cmp(key(row), threshold)`` (``cmp`` one of gt, ge,
+    lt, le), their ascending indices into ``idx_ptr`` (int64) and rows of ``rows_ptr`` [n,3] into
+    ``out_rows_ptr``; returns how many."""
+    cnt = i64(0)
+    check(_lib.load().pyqsm_split_above_dev(v_ptr, int(n), int(width), _key(key, int(width)), COMPARISONS[cmp],
+                                            float(threshold), rows_ptr, idx_ptr, out_rows_ptr, ctypes.byref(cnt),
+                                            int(device)))
+    return int(cnt.value)
+
+
+class ShiftComponents(NamedTuple):
+    """Result of :func:`shift_components`."""
+    labels: np.ndarray       # uint8 [n]: 0 low shift (wood), 1 leaf, 2 epiphyte
+    thresholds: np.ndarray   # float64 [2]: P(q_mag) of the norms, P(q_z) of the high rows' z (NaN without high rows)
+    counts: np.ndarray       # int64 [3] rows per label
+
+
+def shift_components(shift, q_mag: float = 65, q_z: float = 60, device: int = 0) -> ShiftComponents:
+    """``pyqsm_shift_components``: the two percentile splits of ``identify_epiphytes`` on the first
+    contraction step's shift vectors [n,3], in one call."""
+    s = _points(shift)
+    labels = np.zeros(s.shape[0], np.uint8)
+    thr, counts = np.full(2, np.nan), np.zeros(3, np.int64)
+    _select_check(_lib.load().pyqsm_shift_components(_p(s), s.shape[0], float(q_mag), float(q_z), _p(labels), _p(thr),
+                                                     _p(counts), int(device)))
+    return ShiftComponents(labels, thr, counts)
+
+
+def shift_components_dev(shift_ptr: int, n: int, labels_ptr: int, q_mag: float = 65, q_z: float = 60,
+                         device: int = 0):
+    """:func:`shift_components` on device-resident shifts, labels (uint8 [n]) left on the device: returns
+    ``(thresholds, counts)``."""
+    thr, counts = np.full(2, np.nan), np.zeros(3, np.int64)
+    _select_check(_lib.load().pyqsm_shift_components_dev(shift_ptr, int(n), float(q_mag), float(q_z), labels_ptr,
+                                                         _p(thr), _p(counts), int(device)))
+    return thr, counts
+
+
+class KMeansPP(NamedTuple):
+    """Result of :func:`kmeans_pp`."""
+    labels: np.ndarray       # int32 [n]
+    centres: np.ndarray      # float64 [k, d]
+    inertia: float
+    n_iter: int
+    n_empty: int             # centres without a member
+    seeds: np.ndarray        # int64 [k] the points the seeding chose
+
+
+def kmeanspp_trials(k: int) -> int:
+    """Candidates per seeding step: scikit-learn's ``2 + int(log(k))``."""
+    return 2 + int(np.log(k))
+
+
+def _kmeans_pp_args(n, d, k, first, uniforms, max_iter, tol):
+    if d not in (1, 2, 3):
+        raise ValueError(f"points of 1, 2 or 3 columns, got {d}")
+    if not 1 <= k <= KMEANSPP_MAX_K:
+        raise ValueError(f"between 1 and {KMEANSPP_MAX_K} clusters, got {k}")
+    if n < k:
+        raise ValueError(f"n_samples={n} should be >= n_clusters={k}.")
+    u = np.ascontiguousarray(uniforms, dtype=np.float64).reshape(-1)
+    if u.shape[0] != (k - 1) * kmeanspp_trials(k):
+        raise ValueError(f"{(k - 1) * kmeanspp_trials(k)} uniforms are needed, got {u.shape[0]}")
+    return u, (np.empty(n, np.int32), np.empty((k, d)), dbl(0.0), i32(0), i32(0), np.empty(k, np.int64))
+
+
+def _kmeans_pp_call(fn, x, n, d, k, first, u, max_iter, tol, out, device) -> KMeansPP:
+    labels, centres, inertia, n_iter, n_empty, seeds = out
+    check(fn(x, n, d, k, int(first), _p(u), u.shape[0], int(max_iter), float(tol), _p(labels), _p(centres),
+             ctypes.byref(inertia), ctypes.byref(n_iter), ctypes.byref(n_empty), _p(seeds), int(device)))
+    return KMeansPP(labels, centres, inertia.value, int(n_iter.value), int(n_empty.value), seeds)
+
+
+def kmeans_pp(points, k: int, first: int, uniforms, max_iter: int = 300, tol: float = 1e-4,
+              device: int = 0) -> KMeansPP:
+    """``pyqsm_kmeans_pp``: k-means++ seeding and Lloyd iterations of ``points`` [n,d], d <= 3, from the
+    caller's draws: ``first``, the first centre's point, and ``(k - 1) * kmeanspp_trials(k)`` uniforms in
+    [0, 1) (``math_utils.clustering.kmeanspp_draws``)."""
+    x = np.ascontiguousarray(np.asarray(points), dtype=np.float64)
+    if x.ndim == 1:
+        x = x.reshape(-1, 1)
+    if x.ndim != 2:
+        raise ValueError(f"expected points of shape [n,d], got {x.shape}")
+    n, d = x.shape
+    u, out = _kmeans_pp_args(n, d, int(k), first, uniforms, max_iter, tol)
+    return _kmeans_pp_call(_lib.load().pyqsm_kmeans_pp, _p(x), n, d, int(k), first, u, max_iter, tol, out, device)
+
+
+def kmeans_pp_dev(x_ptr: int, n: int, d: int, k: int, first: int, uniforms, max_iter: int = 300, tol: float = 1e-4,
+                  device: int = 0) -> KMeansPP:
+    """:func:`kmeans_pp` on ``n`` device-resident points of ``d`` columns."""
+    u, out = _kmeans_pp_args(int(n), int(d), int(k), first, uniforms, max_iter, tol)
+    return _kmeans_pp_call(_lib.load().pyqsm_kmeans_pp_dev, x_ptr, int(n), int(d), int(k), first, u, max_iter, tol,
+                           out, device)
+
+
 # ---------------------------------------------------------------- mesh checks
 
 MESH_PAIRS = 1

@@ -5,6 +5,11 @@ fit.py:168-214) and the two library calls it makes, ``scipy.cluster.vq.kmeans2``
     kmeans2(data, k, iter=10, seed=None)     scipy kmeans2(data, k, iter), minit='random'
     silhouette_score(points, labels)         sklearn silhouette_score(points, labels)
     kmeans(points, min_clusters, seed=None)  fit.py:168-214
+    kmeans_pp(points, n_clusters, seed=0)    sklearn KMeans(n_clusters, random_state=seed, n_init="auto").fit
+    kmeanspp_draws(n, k, seed)               the random numbers that fit draws, in its order
+    kmeans_feature(smoothed_feature, seed=0) fit.py:160-166 (two clusters of one feature column)
+
+The last three are DESIGN.md §22 (``hip.kmeans_pp``: up to 64 centres, d <= 3, many workgroups).
 
 pyQSM has no module of this name, so nothing is shadowed: ``math_utils.fit.kmeans`` keeps
 resolving to pyQSM's own function through the fall-through (tests/test_dropin.py), and this
@@ -128,6 +133,65 @@ def candidate_ks(min_clusters: int):
     if ks and ks[-1] > hip.KMEANS_MAX_K:
         raise ValueError(f"at most {hip.KMEANS_MAX_K} clusters")
     return ks
+
+
+def kmeanspp_draws(n: int, k: int, seed=0):
+    """The random numbers scikit-learn's ``KMeans(n_clusters=k, random_state=seed, n_init=1)`` draws on
+    ``n`` unweighted samples, in its order, from ``np.random.RandomState(seed)``: the first centre's
+    index by ``choice(n, p=uniform)``, then ``uniform(size=T)`` for each further centre,
+    T = 2 + int(log(k)). They do not depend on the data. Returns ``(first, uniforms [(k-1)*T])``."""
+    rs = seed if isinstance(seed, np.random.RandomState) else np.random.RandomState(seed)
+    weight = np.ones(int(n))
+    first = int(rs.choice(int(n), p=weight / weight.sum()))
+    T = hip.kmeanspp_trials(int(k))
+    draws = [rs.uniform(size=T) for _ in range(int(k) - 1)]
+    return first, (np.concatenate(draws) if draws else np.zeros(0))
+
+
+class KMeansResult:
+    """What the reference reads off a fitted ``sklearn.cluster.KMeans``, and what the kernel adds."""
+
+    def __init__(self, res):
+        self.labels_ = res.labels
+        self.cluster_centers_ = res.centres
+        self.inertia_ = res.inertia
+        self.n_iter_ = res.n_iter
+        self.n_empty_ = res.n_empty            # centres without members (scikit-learn relocates those)
+        self.seed_indices_ = res.seeds         # the points the k-means++ seeding chose
+
+    def __repr__(self):
+        return (f"KMeansResult(n_clusters={len(self.cluster_centers_)}, n_iter_={self.n_iter_}, "
+                f"inertia_={self.inertia_!r})")
+
+
+def kmeans_pp(points, n_clusters: int, seed=0, max_iter: int = 300, tol: float = 1e-4, device: int = 0):
+    """``sklearn.cluster.KMeans(n_clusters, random_state=seed, n_init="auto").fit(points)`` on the GPU
+    (``hip.kmeans_pp``) for ``points`` [n,d], d <= 3, up to 64 clusters: k-means++
+    seeding from scikit-learn's own draws, Lloyd iterations with its stopping rules. Returns a
+    :class:`KMeansResult` with ``labels_``, ``cluster_centers_``, ``inertia_`` and ``n_iter_``.
+
+    Differences from scikit-learn, all deliberate: distances are direct coordinate differences (no
+    dot-product expansion), sums have the kernel's fixed chunk order, and a centre that loses all its
+    members keeps its place (``n_empty_`` says how many; scikit-learn relocates them). On clouds in
+    general position the labels are scikit-learn's; exact distance ties may fall differently."""
+    pts = np.asarray(points.points if hasattr(points, "points") else points, dtype=np.float64)
+    if pts.ndim == 1:
+        pts = pts[:, None]
+    first, uniforms = kmeanspp_draws(len(pts), int(n_clusters), seed)
+    return KMeansResult(hip.kmeans_pp(pts, int(n_clusters), first, uniforms, max_iter=max_iter, tol=tol,
+                                      device=device))
+
+
+def kmeans_feature(smoothed_feature, pcd=None, seed=0, device: int = 0):
+    """pyQSM's ``math_utils.fit.kmeans_feature`` (fit.py:160-166): two clusters of one feature column.
+    Returns ``(cluster_idxs, cluster_features)``, one entry per label that has members. ``pcd`` is
+    accepted and ignored, as there."""
+    feature = np.asarray(smoothed_feature, dtype=np.float64).reshape(-1)
+    fit = kmeans_pp(feature[:, None], 2, seed=seed, device=device)
+    unique_vals, counts = np.unique(fit.labels_, return_counts=True)
+    log.info(f'{unique_vals=} {counts=}')
+    cluster_idxs = [np.where(fit.labels_ == val)[0] for val in unique_vals]
+    return cluster_idxs, [feature[idxs] for idxs in cluster_idxs]
 
 
 def kmeans(points, min_clusters: int, seed=None, device: int = 0):
