@@ -486,6 +486,38 @@ int pyqsm_cluster_adjacency(const double* src, const int32_t* src_label, int64_t
                             double* min_d2, int64_t* pairs, int64_t* src_idx, int64_t* tgt_idx, int64_t* count,
                             int64_t* stats, int32_t device);
 
+/* ---- radius graph: exact degrees and pair list ------------------------------------ */
+/*
+ * The graph whose vertices are the points of a cloud and whose edges join two points within a radius
+ * r of each other: what pyQSM builds with KDTree.query_pairs(r) and a Python loop over the pairs
+ * (pyQSM/utils/lib_integration.py:48-71 get_pairs), thresholds at a percentile of the degree
+ * (scripts/graph_based_leaf_id.py:28-38).
+ * One rule for both calls, cKDTree's at p = 2 and pyqsm_cluster_adjacency's: {i, j}, i != j, is
+ * an edge when d2 = ((dx*dx) + dy*dy) + dz*dz <= r*r, everything in fp64 without contraction; the
+ * bound is inclusive and coincident points are joined.
+ *   xyz f64 [n,3].
+ * pyqsm_radius_degrees: radii f64 [R], 1 <= R <= 8, in any order, repeats allowed; degree i32 [R, n]:
+ *   degree[k * n + i] = the number of edges at point i for radii[k] (the point itself is not counted);
+ *   n_pairs i64 [R] = half the sum of row k, the length of query_pairs(radii[k]). O(n) memory: no pair is
+ *   stored. ONE grid is built, at the largest radius, and every d2 is computed once and compared with
+ *   all R bounds: a radius far below the largest pays for the largest one's candidates (27 cells of
+ *   the largest radius per point); call it on its own when that matters.
+ *   stats i64 [2] or NULL: distance tests evaluated, candidates staged through LDS.
+ * pyqsm_radius_pairs: pairs i32 [capacity, 2]: every edge once as (i, j), i < j in the caller's
+ *   indices, the list ascending by (i, j), the same bits on every run. At most `capacity` rows are
+ *   written (the first of the sorted list), *count is the number found, and a caller who gets
+ *   count > capacity calls again with room (capacity = 0 only counts). More than 2^31 - 256 pairs
+ *   with capacity > 0: PYQSM_ERANGE.
+ * Both: n == 0 is answered on the host, no device is touched (n_pairs = 0, *count = 0). PYQSM_EINVAL: NULL pointers, non-finite coordinates, a radius that is not
+ * positive and finite; PYQSM_ERANGE: R outside [1, 8], n of 2^31 - 256 or more.
+ * Integer atomics only (per-block sums of degrees): every run gives the same bits.
+ * The connected components of this graph are pyqsm_dbscan's clusters at eps = r, min_pts = 1.
+ */
+int pyqsm_radius_degrees(const double* xyz, int64_t n, const double* radii, int32_t R, int32_t* degree,
+                         int64_t* n_pairs, int64_t* stats, int32_t device);
+int pyqsm_radius_pairs(const double* xyz, int64_t n, double radius, int64_t capacity, int32_t* pairs,
+                       int64_t* count, int32_t device);
+
 /* ---- projected area: the exact 2-D alpha shape of lattice points --------------- */
 /*
  * For every segment (an independent cloud) of integer lattice points the total area of the cells of

@@ -93,7 +93,7 @@ HOT_FUNCTIONS = {
     "geometry.reconstruction": ("get_neighbors_kdtree", "overlap_voxel_grid", "get_nbrs_voxel_grid"),
     "viz.ray_casting": ("cast_rays", "sparse_cast_w_intersections", "get_points_inside_mesh",
                         "project_to_image", "raycast_to_pcd", "mri"),
-    "utils.lib_integration": ("find_neighbors_in_ball", "get_neighbors_in_tree"),
+    "utils.lib_integration": ("find_neighbors_in_ball", "get_neighbors_in_tree", "get_pairs"),
     "tree_isolation": ("extend_seed_clusters",),
     "cluster_joining": ("determine_adjacency", "create_kdtrees"),
     "qsm_generation": ("fit_cyl_to_cluster",),

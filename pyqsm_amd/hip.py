@@ -719,6 +719,52 @@ def cluster_adjacency(points, labels, threshold: float, targets=None, target_lab
     return ClusterAdjacency(s_vals[cat[0]], t_vals[cat[1]], np.sqrt(cat[2]), cat[3], cat[4], cat[5])
 
 
+# ---------------------------------------------------------------- radius graph: degrees and pairs
+
+RADIUS_MAX_RADII = 8
+
+
+def radius_degrees(points, radii, device: int = 0, *, stats: dict | None = None):
+    """(degree int32 [R, n], n_pairs int64 [R]) of the radius graph at every radius of ``radii`` (1 to 8,
+    any order, repeats allowed; row k belongs to ``radii[k]``): ``degree[k, i]`` is the number of other
+    points within ``radii[k]`` of point i (d2 <= r*r in fp64, inclusive, coincident points counted), what
+    ``cKDTree.query_ball_point(points, r, return_length=True) - 1`` gives; ``n_pairs`` is the length of
+    ``query_pairs(r)``. One grid at the largest radius serves all of them. ``stats`` (a dict) receives
+    ``distance_tests`` and ``candidates_staged``."""
+    pts = _points(points)
+    rr = np.ascontiguousarray(np.atleast_1d(np.asarray(radii, dtype=np.float64)))
+    if rr.ndim != 1:
+        raise ValueError("radii must be a scalar or one-dimensional")
+    n, R = pts.shape[0], rr.shape[0]
+    degree = np.zeros((R, n), dtype=np.int32)
+    n_pairs = np.zeros(max(R, 1), dtype=np.int64)
+    st = np.zeros(2, dtype=np.int64) if stats is not None else None
+    check(_lib.load().pyqsm_radius_degrees(_p(pts), n, _p(rr), R, _p(degree), _p(n_pairs), _p(st), int(device)))
+    if stats is not None:
+        stats["distance_tests"] = stats.get("distance_tests", 0) + int(st[0])
+        stats["candidates_staged"] = stats.get("candidates_staged", 0) + int(st[1])
+    return degree, n_pairs[:R]
+
+
+def radius_pairs(points, radius: float, n_pairs: int | None = None, device: int = 0) -> np.ndarray:
+    """int32 [m, 2]: every pair of points within ``radius`` once, as (i, j) with i < j, ascending by
+    (i, j): ``cKDTree.query_pairs(radius, output_type='ndarray')``, sorted. ``n_pairs``: the number of
+    pairs when the caller has it from :func:`radius_degrees`; without it the call is repeated once with
+    the room the first one asked for."""
+    pts = _points(points)
+    lib = _lib.load()
+    cap = 0 if n_pairs is None else int(n_pairs)
+    for _ in range(2):
+        out = np.empty((max(cap, 1), 2), dtype=np.int32)
+        found = i64(0)
+        check(lib.pyqsm_radius_pairs(_p(pts), pts.shape[0], float(radius), cap, _p(out), ctypes.byref(found),
+                                     int(device)))
+        if int(found.value) <= cap:
+            return out[: int(found.value)]
+        cap = int(found.value)
+    raise RuntimeError("pyqsm_radius_pairs: the pair count changed between two calls")
+
+
 # ---------------------------------------------------------------- projected area (alpha shape)
 
 ALPHA_BOUNDARY = 1

@@ -3,6 +3,7 @@
     find_neighbors_in_ball(base_pts, points_to_search, points_idxs, radius, center, use_top)
                                                         lib_integration.py:81-137
     get_neighbors_in_tree(sub_pcd_pts, full_tree, radius)      :73-79
+    get_pairs(query_pts, kd_tree, radius, return_line_set)     :48-71
 
 ``find_neighbors_in_ball`` is called once per branch segment by
 ``qsm_generation.sphere_step`` (:220); the reference rebuilds a KD-tree of the whole
@@ -79,3 +80,26 @@ def get_neighbors_in_tree(sub_pcd_pts, full_tree, radius, device: int = 0):
     mask, _ = hip.radius_mark(data, as_points(sub_pcd_pts), np.nextafter(radius, np.inf),
                               k=len(data), device=device)
     return np.flatnonzero(mask)
+
+
+def get_pairs(query_pts=None, kd_tree=None, radius=.2, return_line_set=False, device: int = 0):
+    """lib_integration.py:48-71: ``(degrees, cnts, line_set)`` of the graph whose edges join the points
+    at most ``radius`` apart: the degree of every point (int32 [n]; the reference's Python list), the
+    counts of ``np.unique(degrees, return_counts=True)`` and, with ``return_line_set``, the ``LineSet``
+    of the pairs (i < j, ascending), else None. The degrees come from one counting pass
+    (``hip.radius_degrees``); the pair list is fetched only for the line set. ``kd_tree`` (a SciPy
+    KDTree or an array of points) supplies the points when ``query_pts`` is None; the reference builds
+    its tree from ``query_pts`` whenever both are given."""
+    if query_pts is None:
+        if kd_tree is None:
+            raise ValueError('must pass either query_pts or kd_tree')
+        query_pts = kd_tree.data if hasattr(kd_tree, "data") else kd_tree
+    pts = as_points(query_pts)
+    degree, n_pairs = hip.radius_degrees(pts, [float(radius)], device=device)
+    degrees = degree[0]
+    line_set = None
+    if return_line_set:
+        from ..geometry.skeletonize import LineSet
+        line_set = LineSet(pts, hip.radius_pairs(pts, float(radius), int(n_pairs[0]), device=device))
+    _, cnts = np.unique(degrees, return_counts=True)
+    return degrees, cnts, line_set
