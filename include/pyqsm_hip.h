@@ -511,12 +511,25 @@ int pyqsm_cluster_adjacency(const double* src, const int32_t* src_label, int64_t
  * Both: n == 0 is answered on the host, no device is touched (n_pairs = 0, *count = 0). PYQSM_EINVAL: NULL pointers, non-finite coordinates, a radius that is not
  * positive and finite; PYQSM_ERANGE: R outside [1, 8], n of 2^31 - 256 or more.
  * Integer atomics only (per-block sums of degrees): every run gives the same bits.
- * The connected components of this graph are pyqsm_dbscan's clusters at eps = r, min_pts = 1.
+ * pyqsm_radius_components: the connected components of the graph at every radius of radii f64 [R], 1 <= R <= 8,
+ *   any order, repeats allowed, ranked by (size descending, smallest member ascending): what pyQSM takes
+ *   from sorted(rustworkx.connected_components(g), key=len, reverse=True) over the pair list
+ *   (scripts/graph_based_leaf_id.py:80-97, qsm_generation.py:526-556). Row k of every output is for radii[k]:
+ *   component i32 [R, n] the rank of point i's component; sizes i32 [R, n], the first n_components[k]
+ *   entries of row k valid (the others are left as they were): sizes[k * n + s] = the points of rank s;
+ *   members i32 [R, n] or NULL: the point indices ascending by (component, index), so the points of rank s
+ *   are the slice between the prefix sums of sizes; n_components i64 [R]. No pair is stored: O(n) memory.
+ *   One grid at the largest radius, one union pass and one ranking per radius. The same bits on every run:
+ *   a set's label is its smallest member whatever order the unions arrive in, the sizes are integer sums.
+ *   They are also pyqsm_dbscan's clusters at eps = r, min_pts = 1, numbered differently.
+ *   n == 0: n_components = 0, no device touched; errors as pyqsm_radius_degrees'.
  */
 int pyqsm_radius_degrees(const double* xyz, int64_t n, const double* radii, int32_t R, int32_t* degree,
                          int64_t* n_pairs, int64_t* stats, int32_t device);
 int pyqsm_radius_pairs(const double* xyz, int64_t n, double radius, int64_t capacity, int32_t* pairs,
                        int64_t* count, int32_t device);
+int pyqsm_radius_components(const double* xyz, int64_t n, const double* radii, int32_t R, int32_t* component,
+                            int32_t* sizes, int32_t* members, int64_t* n_components, int32_t device);
 
 /* ---- projected area: the exact 2-D alpha shape of lattice points --------------- */
 /*

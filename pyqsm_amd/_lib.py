@@ -83,6 +83,7 @@ SIGNATURES = {
                                                vp, vp, ctypes.POINTER(i64), vp, i32]),
     "pyqsm_radius_degrees": (ctypes.c_int, [vp, i64, vp, i32, vp, vp, vp, i32]),
     "pyqsm_radius_pairs": (ctypes.c_int, [vp, i64, dbl, i64, vp, ctypes.POINTER(i64), i32]),
+    "pyqsm_radius_components": (ctypes.c_int, [vp, i64, vp, i32, vp, vp, vp, vp, i32]),
     "pyqsm_alpha_area": (ctypes.c_int, [vp, i64, vp, i64, ctypes.c_uint64, i64, i32, vp, vp, vp,
                                         ctypes.POINTER(vp), vp, i32]),
     "pyqsm_pdist_select": (ctypes.c_int, [vp, i64, i32, vp, i64, vp, i32, i64, vp, vp, vp, vp, i32]),

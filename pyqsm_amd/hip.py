@@ -765,6 +765,30 @@ def radius_pairs(points, radius: float, n_pairs: int | None = None, device: int 
     raise RuntimeError("pyqsm_radius_pairs: the pair count changed between two calls")
 
 
+def radius_components(points, radii, device: int = 0, members: bool = False):
+    """The connected components of the radius graph at every radius of ``radii`` (1 to 8, any order,
+    repeats allowed), ranked by (size descending, smallest member ascending):
+    ``sorted(connected_components(g), key=len, reverse=True)`` over ``query_pairs(r)`` with ties in the
+    order of their smallest point, no pair stored. Returns ``(component int32 [R, n], sizes)``,
+    ``sizes`` a list of R int32 arrays (``sizes[k][s]`` = the points of rank ``s`` at ``radii[k]``), and
+    with ``members=True`` a third item, int32 [R, n]: the point indices ascending by (component, index),
+    so the points of rank ``s`` are ``members[k][off[s]:off[s + 1]]`` with ``off`` the prefix sums of
+    ``sizes[k]``."""
+    pts = _points(points)
+    rr = np.ascontiguousarray(np.atleast_1d(np.asarray(radii, dtype=np.float64)))
+    if rr.ndim != 1:
+        raise ValueError("radii must be a scalar or one-dimensional")
+    n, R = pts.shape[0], rr.shape[0]
+    component = np.zeros((R, n), dtype=np.int32)
+    sizes = np.zeros((R, n), dtype=np.int32)
+    mem = np.zeros((R, n), dtype=np.int32) if members else None
+    count = np.zeros(max(R, 1), dtype=np.int64)
+    check(_lib.load().pyqsm_radius_components(_p(pts), n, _p(rr), R, _p(component), _p(sizes), _p(mem), _p(count),
+                                              int(device)))
+    out = (component, [sizes[k, : int(count[k])].copy() for k in range(R)])
+    return out + (mem,) if members else out
+
+
 # ---------------------------------------------------------------- projected area (alpha shape)
 
 ALPHA_BOUNDARY = 1

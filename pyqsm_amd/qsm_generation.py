@@ -15,6 +15,7 @@ try:  # flat import style of the reference (pyqsm_amd on sys.path) or package im
     from ._shadow import fall_through
     from . import hip
     from .geometry.cloud import PointCloud, as_points
+    from .geometry.density import Components
     from .math_utils.fit import fit_shape_RANSAC
     from .math_utils.general import get_center
     from .set_config import config
@@ -25,6 +26,7 @@ except ImportError:  # pragma: no cover
     from pyqsm_amd._shadow import fall_through
     from pyqsm_amd import hip
     from pyqsm_amd.geometry.cloud import PointCloud, as_points
+    from pyqsm_amd.geometry.density import Components
     from pyqsm_amd.math_utils.fit import fit_shape_RANSAC
     from pyqsm_amd.math_utils.general import get_center
     from pyqsm_amd.set_config import config
@@ -64,6 +66,21 @@ def fit_cyl_to_cluster(main_pcd, curr_pts, last_radius, cluster_idxs, cyls=[], c
         cyl_details.append({"center": get_center(curr_pts), "axis": axis,
                             "height": prev_neighbor_height, "radius": fit_radius})
     return good_fit_found
+
+
+def exclude_dense_areas(pcd, radius=.1, top=500, max_size=100, device: int = 0):
+    """qsm_generation.py:526-556: the radius graph of the cloud at ``radius``, its connected
+    components sorted by size, and of the ``top`` largest those with fewer than ``max_size`` points
+    (``[x for x in conn_comps[0:500] if len(x) < 100]``, the selection the reference ends on).
+    Returns ``(sub_cloud, components)``: the points of the selected components as a ``PointCloud``, in
+    rank order, and the :class:`~pyqsm_amd.geometry.density.Components` of the whole cloud. The
+    reference overrides its ``radius`` argument with ``.1``, which is the default here; it draws the
+    line sets and then names undefined variables (``trim``, ``new_pts``): neither is reproduced. No
+    pair list is built."""
+    pts = as_points(pcd)
+    comp, sizes, mem = hip.radius_components(pts, [float(radius)], device=device, members=True)
+    comps = Components(comp[0], sizes[0], mem[0])
+    return PointCloud(pts[comps.select(top=top, max_size=max_size)]), comps
 
 
 _stem = config.get("stem", {})

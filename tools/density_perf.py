@@ -8,7 +8,16 @@ cKDTree.query_ball_point(P, r, return_length=True, workers=W) - 1 on the same cl
 picks for which radii: the large ones take minutes on the host). One JSON line per case, appended to
 --out as well.
 
+--cases components: the components ranked by size (hip.radius_components) at every radius alone and the
+--sweep radii as one call: kernel = the "radius_components_union" scope (init, the two union launches,
+flatten) and the "radius_components_rank" scope (sizes, compaction, sort, labels), wall = the whole call.
+Next to each record its baseline, what the library offered before for the same answer, in the same
+process: hip.dbscan(P, r, 1) and rank_components in NumPy on the host (one dbscan call per radius for the
+sweep); at the smallest radius also the pair-list route, hip.radius_pairs and SciPy's
+connected_components. Every baseline's answer is compared with the call's.
+
     python tools/density_perf.py [--n 1000000] [--radii 0.05 0.1 0.3] [--scipy-radii ...] [--workers 16]
+                                 [--cases degrees components] [--sweep .06 .07 .08 .09]
                                  [--out profiles/density_perf.jsonl]
 """
 import argparse
@@ -29,18 +38,20 @@ def _median_min(v):
     return {"median": round(float(np.median(v)), 4), "min": round(float(min(v)), 4)}
 
 
-def _timed(fn, scope):
+def _timed(fn, *scopes):
+    """(result, wall, device time of scope 0, of scope 1, ...): median and min of REPS after a warm-up."""
     fn()
-    walls, dev = [], []
-    hip.prof_enable(True)
+    walls, dev = [], [[] for _ in scopes]
+    hip.prof_enable(bool(scopes))
     for _ in range(REPS):
         hip.prof_reset()
         t = time.perf_counter()
         out = fn()
         walls.append((time.perf_counter() - t) * 1e3)
-        dev.append(hip.prof_get(scope)[0])
+        for d, scope in zip(dev, scopes):
+            d.append(hip.prof_get(scope)[0])
     hip.prof_enable(False)
-    return out, _median_min(walls), _median_min(dev)
+    return (out, _median_min(walls)) + tuple(_median_min(d) for d in dev)
 
 
 def emit(rec, out):
@@ -64,6 +75,45 @@ def degrees_case(P, radii):
     return rec, deg
 
 
+def rank_components(labels):
+    """(component, sizes) from any labelling: ranks by (size descending, smallest member ascending);
+    tests/density_restatement.py's statement."""
+    _, first, inv, counts = np.unique(labels, return_index=True, return_inverse=True, return_counts=True)
+    order = np.lexsort((first, -counts))
+    rank = np.empty(len(order), dtype=np.int64)
+    rank[order] = np.arange(len(order))
+    return rank[inv].astype(np.int32), counts[order].astype(np.int32)
+
+
+def components_case(P, radii, head, out, pair_route=False):
+    (comp, sizes), wall, union, rank = _timed(lambda: hip.radius_components(P, radii), "radius_components_union",
+                                              "radius_components_rank")
+    emit({**head, "case": "components", "radii": list(radii), "n_components": [len(s) for s in sizes],
+          "largest": [int(s[0]) for s in sizes], "union_kernel_ms": union, "rank_kernel_ms": rank,
+          "wall_ms": wall}, out)
+
+    def dbscan_route():
+        return [rank_components(hip.dbscan(P, r, 1)[0]) for r in radii]
+
+    ref, wall = _timed(dbscan_route)
+    _, dbscan_wall = _timed(lambda: [hip.dbscan(P, r, 1) for r in radii])
+    same = all(np.array_equal(c0, c1) and np.array_equal(s0, s1) for (c0, s0), c1, s1 in zip(ref, comp, sizes))
+    emit({**head, "case": "components_baseline_dbscan_min_pts_1_host_rank", "radii": list(radii), "wall_ms": wall,
+          "dbscan_calls_wall_ms": dbscan_wall, "equals_components": bool(same)}, out)
+    if pair_route:
+        from scipy.sparse import coo_matrix
+        from scipy.sparse.csgraph import connected_components
+
+        def pairs_route():
+            p = hip.radius_pairs(P, radii[0])
+            g = coo_matrix((np.ones(len(p), dtype=np.int8), (p[:, 0], p[:, 1])), shape=(len(P), len(P)))
+            return rank_components(connected_components(g, directed=False)[1])
+
+        (c0, s0), wall = _timed(pairs_route)
+        emit({**head, "case": "components_baseline_radius_pairs_scipy", "radii": list(radii), "wall_ms": wall,
+              "equals_components": bool(np.array_equal(c0, comp[0]) and np.array_equal(s0, sizes[0]))}, out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1_000_000)
@@ -71,9 +121,18 @@ def main():
     ap.add_argument("--scipy-radii", type=float, nargs="*", default=None, help="default: all of --radii")
     ap.add_argument("--workers", type=int, default=16)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--cases", nargs="*", default=["degrees", "components"], choices=["degrees", "components"])
+    ap.add_argument("--sweep", type=float, nargs="*", default=[.06, .07, .08, .09])
     a = ap.parse_args()
     P = np.ascontiguousarray(synth.forest(a.n), dtype=np.float64)
     head = {"n": a.n, "cloud": "synth.forest"}
+    if "components" in a.cases:
+        for r in a.radii:
+            components_case(P, [r], head, a.out, pair_route=(r == min(a.radii)))
+        if a.sweep:
+            components_case(P, a.sweep, head, a.out)
+    if "degrees" not in a.cases:
+        return
     single = {}
     for r in a.radii:
         rec, deg = degrees_case(P, [r])
