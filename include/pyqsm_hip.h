@@ -1205,6 +1205,67 @@ int pyqsm_kmeans_pp_dev(const double* x_dev, int64_t n, int32_t d, int32_t k, in
                         int64_t n_u, int32_t max_iter, double tol, int32_t* labels, double* centres, double* inertia,
                         int32_t* n_iter, int32_t* n_empty, int64_t* seeds, int32_t device);
 
+/* ---- convex hull: exact facets of lattice points, batched ---------------------- */
+/*
+ * The convex hull of every segment (an independent cloud) of integer lattice points, decided by int64
+ * predicates only (csrc/hull_exact.hpp): what scipy.spatial.ConvexHull(points).simplices
+ * and the hull behind pcd.get_oriented_bounding_box() are in pyQSM, with a fixed answer on degenerate input.
+ *   ijk i32 [n,3] lattice coordinates; seg_start i64 [n_seg + 1], ascending from 0 to n. A segment may
+ *   span at most 2^20 units on every axis (PYQSM_EINVAL beyond, before any launch): every orient3d
+ *   determinant of differences is then below 6 * 2^60 < 2^63.
+ * Which triangles: coincident points of a segment are merged, the lowest index takes part. A plane through
+ *   three non-collinear points of the segment with no point strictly outside it is a facet plane; the points
+ *   on it span a convex polygon whose extreme points are its vertices (points inside the polygon or inside
+ *   one of its edges are not). With v0 the vertex of lowest index the facet gives one triangle (v0, x, y)
+ *   for every directed polygon edge x -> y, counter-clockwise seen from outside, that does not contain v0.
+ *   In general position every facet is one triangle and the rows are Qhull's simplices as a set.
+ * Output, allocated by the library and released with pyqsm_free, NULL after an error:
+ *   *tris i32 [T,3]: indices into ijk; in every row (a, b, c) a is the smallest and (b - a) x (c - a)
+ *     points out of the hull; rows ascend by (a, b, c) inside a segment, segments in segment order.
+ *   *tri_ptr i64 [n_seg + 1]: the rows of segment s are tri_ptr[s] .. tri_ptr[s + 1].
+ *   dim i32 [n_seg] (the caller's): the affine dimension of the segment's distinct points, -1 for an empty
+ *     segment. A segment with dim < 3 has no rows; when every segment is like that no device is touched
+ *     (*tris stays NULL, *tri_ptr is all zero).
+ *   The same bytes on every run.
+ * How: in front, the extreme points of a segment along 26 fixed directions and four affinely independent
+ *   points are wrapped into a small polytope, and every point strictly inside it is dropped; the survivors
+ *   are wrapped in rounds of open directed edges, each facet handled as a unit.
+ * max_tests: the running count of orient tests (one per point and pass of an open edge) is checked after every
+ *   round; above max_tests the call ends with PYQSM_ERANGE. <= 0: PYQSM_HULL_DEFAULT_MAX_TESTS, ten seconds at
+ *   the 2.0e11 tests per second measured on one MI355X (profiles/hull_perf.jsonl, the 100 000-point shell), rounded down. The plane tests of
+ *   the prefilter (at most 56 per point) are not counted. The rounds are bounded by the facet count (every
+ *   round with an open edge closes one); beyond 2 C + 8 rounds for C candidates the call returns PYQSM_EHIP.
+ *   A facet polygon with more than PYQSM_HULL_MAX_FACET_VERTS vertices: PYQSM_ERANGE.
+ * stats i64 [PYQSM_HULL_N_STATS] or NULL: candidates left after the prefilter, rounds of the main wrap, orient
+ *   tests run (both wraps), facets with more than three points on their plane, merged duplicates among the
+ *   candidates, rounds of the prefilter's wrap. All of them are the same on every run.
+ */
+#define PYQSM_HULL_N_STATS 6
+#define PYQSM_HULL_MAX_FACET_VERTS 1024
+#define PYQSM_HULL_DEFAULT_MAX_TESTS 2000000000000LL
+int pyqsm_convex_hull(const int32_t* ijk, int64_t n, const int64_t* seg_start, int64_t n_seg, int64_t max_tests,
+                      int32_t** tris, int64_t** tri_ptr, int32_t* dim, int64_t* stats, int32_t device);
+
+/* ---- points in oriented boxes ---------------------------------------------------- */
+/*
+ * OrientedBoundingBox.get_point_indices_within_bounding_box for up to PYQSM_BOXES_MAX boxes in one pass
+ * over the cloud (pyQSM's recover_original_details asks every cluster box of every tile of the scan).
+ *   xyz f64 [n,3]; boxes f64 [B,15]: centre 3, R row-major 9, half-extent 3.
+ *   Point p is in box k iff |t_i| <= half_i for i = 0, 1, 2, with d = p - c and
+ *   t_i = (d.x * R[0][i] + d.y * R[1][i]) + d.z * R[2][i]: fp64 in exactly this order, bounds inclusive,
+ *   no contraction; a NaN is in no box.
+ *   ptr i64 [B + 1] (the caller's); *idx i64 [ptr[B]]: the members of box k, ascending, are
+ *   idx[ptr[k]] .. idx[ptr[k + 1]]; allocated by the library, released with pyqsm_free, NULL when no
+ *   point is in any box. Two passes of 24 B per point (count, scan, fill), no atomics.
+ *   B > PYQSM_BOXES_MAX: PYQSM_EINVAL; n * B above 2^31 - 256: PYQSM_ERANGE (pass fewer boxes per call).
+ * The _dev form takes a cloud that is already in HBM: a tile uploaded once answers any number of calls.
+ */
+#define PYQSM_BOXES_MAX 256
+int pyqsm_points_in_boxes(const double* xyz, int64_t n, const double* boxes, int32_t B, int64_t* ptr,
+                          int64_t** idx, int32_t device);
+int pyqsm_points_in_boxes_dev(const double* xyz_dev, int64_t n, const double* boxes, int32_t B, int64_t* ptr,
+                              int64_t** idx, int32_t device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -86,6 +86,9 @@ SIGNATURES = {
     "pyqsm_radius_components": (ctypes.c_int, [vp, i64, vp, i32, vp, vp, vp, vp, i32]),
     "pyqsm_alpha_area": (ctypes.c_int, [vp, i64, vp, i64, ctypes.c_uint64, i64, i32, vp, vp, vp,
                                         ctypes.POINTER(vp), vp, i32]),
+    "pyqsm_convex_hull": (ctypes.c_int, [vp, i64, vp, i64, i64, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp, i32]),
+    "pyqsm_points_in_boxes": (ctypes.c_int, [vp, i64, vp, i32, vp, ctypes.POINTER(vp), i32]),
+    "pyqsm_points_in_boxes_dev": (ctypes.c_int, [vp, i64, vp, i32, vp, ctypes.POINTER(vp), i32]),
     "pyqsm_pdist_select": (ctypes.c_int, [vp, i64, i32, vp, i64, vp, i32, i64, vp, vp, vp, vp, i32]),
     "pyqsm_select_values": (ctypes.c_int, [vp, i64, i32, i32, vp, i32, vp, i32]),
     "pyqsm_select_values_dev": (ctypes.c_int, [vp, i64, i32, i32, vp, i32, vp, i32]),

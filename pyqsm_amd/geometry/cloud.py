@@ -174,6 +174,24 @@ class PointCloud:
     def get_max_bound(self):
         return self.points.max(axis=0)
 
+    def compute_convex_hull(self, quantum=None, device: int = 0):
+        """Open3D's ``compute_convex_hull``: ``(TriangleMesh, vertex indices)``, the mesh over the
+        hull's vertices only (re-indexed, outward triangles), the indices ascending into this cloud.
+        The hull is the exact one of ``geometry.hull.convex_hull`` (on the GPU, no SciPy)."""
+        from .hull import convex_hull
+        h = convex_hull(self.points, quantum=quantum, device=device)
+        if h.dim < 3:
+            raise ValueError(f"the cloud has no 3-D convex hull (affine dimension {h.dim})")
+        remap = np.full(len(self.points), -1, np.int32)
+        remap[h.vertices] = np.arange(len(h.vertices), dtype=np.int32)
+        return TriangleMesh(self.points[h.vertices], remap[h.simplices]), h.vertices
+
+    def get_oriented_bounding_box(self, quantum=None, device: int = 0):
+        """Open3D's ``get_oriented_bounding_box``: the PCA box of the convex hull's vertices, as a
+        ``geometry.hull.OrientedBoundingBox``."""
+        from .hull import OrientedBoundingBox
+        return OrientedBoundingBox.create_from_points(self.points, quantum=quantum, device=device)
+
     def segment_plane(self, distance_threshold=0.01, ransac_n=3, num_iterations=100, probability=0.99999999,
                       seed=None, samples=None, device: int = 0):
         """Open3D's ``segment_plane`` on the GPU (``hip.segment_plane``): returns ``(plane_model [4],

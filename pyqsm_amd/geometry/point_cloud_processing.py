@@ -86,6 +86,26 @@ def cluster_and_get_largest(pcd, eps=config["trunk"]["cluster_eps"],
     return _select(pcd, pts, np.where(labels == largest)[0])
 
 
+def query_via_bnd_box(pcd, source_pcd, scale=1.1, translation=(0, 0, 1), draw=False, device: int = 0):
+    """point_cloud_processing.py:306-343: neighbours of ``pcd`` in ``source_pcd``, found by moving
+    and growing ``pcd``'s oriented bounding box. Returns ``(nbrs, new_nbr_idxs)``: the points of
+    ``source_pcd`` inside the shifted, scaled box but not inside the box itself, as a cloud, and
+    their indices into ``source_pcd``.
+
+    The reference indexes ``pcd`` with these indices and calls ``source_pcd.points()``; the indices
+    are into ``source_pcd``, so the neighbours are selected from ``source_pcd`` here. ``draw`` is
+    accepted and ignored (no viewer). Both boxes are asked in one pass over the source cloud."""
+    from copy import deepcopy
+    from pyqsm_amd.geometry.hull import point_indices_within_boxes
+    obb = (pcd if isinstance(pcd, PointCloud) else PointCloud(as_points(pcd))).get_oriented_bounding_box(device=device)
+    shifted = deepcopy(obb).translate(translation, relative=True)
+    shifted.scale(scale, center=obb.center)
+    src = as_points(source_pcd)
+    in_shifted, in_box = point_indices_within_boxes(src, [shifted, obb], device=device)
+    new_nbr_idxs = np.setdiff1d(in_shifted, in_box)
+    return _select(source_pcd, src, new_nbr_idxs), new_nbr_idxs
+
+
 def _angles_deg(normals):
     """pyQSM's np.degrees(get_angles(n)) for every row: get_angles returns arctan(nz / sqrt(nx^2 +
     ny^2)) in radians whenever that is non-zero (its ``radians`` flag is overwritten), 0 when it is

@@ -155,28 +155,32 @@ def _hull_vertices(pts, device=None):
     return cand[ConvexHull(pts[cand]).vertices]      # in 3-D Qhull lists vertices in input order
 
 
-def oriented_bounds(pts, device=None):
+def oriented_bounds(pts, device=None, hull="qhull"):
     """Axis-aligned min / max of the 8 corners of the PCA-oriented bounding box of
     the convex hull — what ``pcd.get_oriented_bounding_box().get_min_bound() /
     get_max_bound()`` yield at skeletonize.py:240-241 (Open3D builds the box from a
     PCA of the hull vertices). Falls back to the plain bounding box for clouds
-    that have no 3-D hull. ``device``: see :func:`_hull_vertices` (same result)."""
+    that have no 3-D hull. ``device``: see :func:`_hull_vertices` (same result).
+    ``hull="device"`` takes the vertices from the exact lattice hull of ``geometry.hull`` instead of
+    Qhull (no SciPy): the same vertex set unless the cloud is close to degenerate, where Qhull on raw
+    doubles and the exact hull on the lattice may differ. The PCA is the one helper both share."""
+    from .hull import convex_hull, frame_corners, pca_frame
     pts = np.asarray(pts, dtype=np.float64)
-    try:
-        hull_pts = pts[_hull_vertices(pts, device)]
-    except Exception as e:
-        if type(e).__name__ != "QhullError" and not isinstance(e, ValueError):
-            raise
-        return pts.min(axis=0), pts.max(axis=0)
-    mean = hull_pts.mean(axis=0)
-    cov = np.cov((hull_pts - mean).T, bias=True)
-    w, v = np.linalg.eigh(cov)
-    R = v[:, np.argsort(w)[::-1]]
-    R[:, 0] = np.cross(R[:, 1], R[:, 2])
-    local = (hull_pts - mean) @ R
-    lo, hi = local.min(axis=0), local.max(axis=0)
-    corners = np.array([[x, y, z] for x in (lo[0], hi[0]) for y in (lo[1], hi[1])
-                        for z in (lo[2], hi[2])]) @ R.T + mean
+    if hull == "device":
+        h = convex_hull(pts, device=0 if device is None else device)
+        if h.dim < 3:
+            return pts.min(axis=0), pts.max(axis=0)
+        hull_pts = pts[h.vertices]
+    elif hull == "qhull":
+        try:
+            hull_pts = pts[_hull_vertices(pts, device)]
+        except Exception as e:
+            if type(e).__name__ != "QhullError" and not isinstance(e, ValueError):
+                raise
+            return pts.min(axis=0), pts.max(axis=0)
+    else:
+        raise ValueError("hull must be 'qhull' or 'device'")
+    corners = frame_corners(*pca_frame(hull_pts))
     return corners.min(axis=0), corners.max(axis=0)
 
 

@@ -856,6 +856,99 @@ def alpha_area(ij, a2: int, seg_start=None, return_boundary: bool = False, max_t
     return AlphaArea(twice, live, nb, edges, start, stats)
 
 
+# ---------------------------------------------------------------- convex hull, points in boxes
+
+HULL_MAX_EXTENT = 1 << 20                 # lattice units per axis and segment
+HULL_DEFAULT_MAX_TESTS = 2_000_000_000_000    # PYQSM_HULL_DEFAULT_MAX_TESTS: ten seconds at 2.0e11 tests/s
+HULL_MAX_FACET_VERTS = 1024               # PYQSM_HULL_MAX_FACET_VERTS
+BOXES_MAX = 256                           # PYQSM_BOXES_MAX
+
+
+class ConvexHulls(NamedTuple):
+    """Results of :func:`convex_hull`."""
+    tris: np.ndarray      # int32 [T, 3] indices into ijk; a smallest, outward, ascending by (a, b, c) per segment
+    tri_ptr: np.ndarray   # int64 [n_seg + 1]
+    dim: np.ndarray       # int32 [n_seg] affine dimension of the distinct points, -1 for an empty segment
+    stats: dict
+
+
+def convex_hull(ijk, seg_start=None, max_tests: int | None = None, device: int = 0) -> ConvexHulls:
+    """``pyqsm_convex_hull``: the exact convex hull of integer lattice points, per segment. ``ijk``
+    int32 [n, 3]; ``seg_start`` [n_seg + 1] splits it into independent clouds (default: one), each
+    spanning at most 2^20 units per axis. Coincident points are merged (the lowest index takes part);
+    a facet with more than three points on its plane is a fan from its vertex of lowest index.
+    ``max_tests`` (default: about ten seconds of one MI355X) ends the call once the running count of
+    orient tests exceeds it."""
+    pts = np.asarray(ijk)
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError(f"expected lattice points of shape [n,3], got {pts.shape}")
+    if pts.size and not np.issubdtype(pts.dtype, np.integer):
+        raise ValueError("lattice points must be integers")
+    if pts.size and (pts.min() < -(1 << 31) or pts.max() >= (1 << 31)):
+        raise ValueError("lattice points must fit int32")
+    pts = np.ascontiguousarray(pts, dtype=np.int32)
+    n = pts.shape[0]
+    seg = np.array([0, n], np.int64) if seg_start is None else np.ascontiguousarray(seg_start, dtype=np.int64)
+    if seg.ndim != 1 or seg.shape[0] < 1:
+        raise ValueError("seg_start must hold n_seg + 1 offsets")
+    n_seg = seg.shape[0] - 1
+    dim = np.full(max(n_seg, 1), -1, np.int32)
+    st = np.zeros(6, np.int64)
+    lib = _lib.load()
+    out_t, out_p = vp(), vp()
+    check(lib.pyqsm_convex_hull(_p(pts), n, _p(seg), n_seg, 0 if max_tests is None else int(max_tests),
+                                ctypes.byref(out_t), ctypes.byref(out_p), _p(dim), _p(st), int(device)))
+    tri_ptr = _adopt(lib, out_p, i64, n_seg + 1, np.int64)
+    T = int(tri_ptr[-1])
+    if out_t.value and T > 0:
+        tris = _adopt(lib, out_t, i32, 3 * T, np.int32).reshape(-1, 3)
+    else:
+        if out_t.value:
+            lib.pyqsm_free(out_t)
+        tris = np.zeros((0, 3), np.int32)
+    stats = dict(zip(("candidates", "rounds", "tests", "flat_facets", "merged_duplicates", "prefilter_rounds"),
+                     (int(v) for v in st)))
+    return ConvexHulls(tris, tri_ptr, dim[:n_seg], stats)
+
+
+def _boxes15(boxes) -> np.ndarray:
+    b = np.ascontiguousarray(np.asarray(boxes, dtype=np.float64))
+    if b.ndim != 2 or b.shape[1] != 15:
+        raise ValueError(f"expected boxes of shape [B,15] (centre, R row-major, half-extent), got {b.shape}")
+    return b
+
+
+def points_in_boxes(points, boxes, device: int = 0):
+    """``pyqsm_points_in_boxes``: ``(ptr int64 [B + 1], idx int64)``, the points inside each oriented
+    box, ascending inside a box. ``points`` float64 [n, 3] or a :class:`DeviceBuffer` holding them
+    (then ``pyqsm_points_in_boxes_dev``: a tile uploaded once answers any number of calls);
+    ``boxes`` float64 [B, 15]: centre, R row-major, half-extent. Point p is in a box iff
+    ``|((d.x R[0][i] + d.y R[1][i]) + d.z R[2][i])| <= half_i`` for every axis, d = p - centre, in
+    fp64 and this order. More boxes than one call takes (256, and n * B < 2^31) are chunked here."""
+    b = _boxes15(boxes)
+    lib = _lib.load()
+    if isinstance(points, DeviceBuffer):
+        n, src, fn, device = points.nbytes // 24, points.ptr, lib.pyqsm_points_in_boxes_dev, points.device
+        keep = points
+    else:
+        keep = _points(points)
+        n, src, fn = keep.shape[0], _p(keep), lib.pyqsm_points_in_boxes
+    B = b.shape[0]
+    step = max(1, min(BOXES_MAX, 0x7FFFFF00 // max(n, 1)))
+    ptrs, idxs, base = [np.zeros(1, np.int64)], [], 0
+    for k0 in range(0, B, step):
+        part = np.ascontiguousarray(b[k0:k0 + step])
+        ptr = np.zeros(part.shape[0] + 1, np.int64)
+        out = vp()
+        check(fn(src, n, _p(part), part.shape[0], _p(ptr), ctypes.byref(out), int(device)))
+        if out.value:
+            idxs.append(_adopt(lib, out, i64, int(ptr[-1]), np.int64))
+        ptrs.append(ptr[1:] + base)
+        base += int(ptr[-1])
+    idx = np.concatenate(idxs) if idxs else np.zeros(0, np.int64)
+    return np.concatenate(ptrs), idx
+
+
 # ---------------------------------------------------------------- pairwise-distance order statistics
 
 PDIST_MAX_RANKS = 32                          # PYQSM_PDIST_MAX_RANKS

@@ -41,6 +41,17 @@ class Sphere:
         self.radius = float(radius)
 
 
+def sps_hull_to_mesh(voxel_down_pcd, type="ConvexHull", device: int = 0):
+    """lib_integration.py:31-45: the convex hull of a cloud as a mesh over ALL of its points, the
+    triangles being the hull's simplices. Here the hull is the exact lattice hull of
+    ``geometry.hull`` on the GPU: outward triangles in a fixed order, fans on flat facets. The
+    reference's other ``type`` (a Delaunay tetrahedralisation cut to three columns) is not offered."""
+    if type != "ConvexHull":
+        raise ValueError("only type='ConvexHull' is implemented")
+    from pyqsm_amd.geometry.hull import convex_hull
+    return convex_hull(as_points(voxel_down_pcd), device=device).to_mesh()
+
+
 def find_neighbors_in_ball(base_pts, points_to_search, points_idxs, radius=None, center=None,
                            use_top=None, draw_results=False, device: int = 0):
     """lib_integration.py:81-137: one sphere around the centroid of ``base_pts`` (or of
