@@ -1266,6 +1266,73 @@ int pyqsm_points_in_boxes(const double* xyz, int64_t n, const double* boxes, int
 int pyqsm_points_in_boxes_dev(const double* xyz_dev, int64_t n, const double* boxes, int32_t B, int64_t* ptr,
                               int64_t** idx, int32_t device);
 
+/* ---- colours: exact HSV classes, saturation lift, histogram, masks ---------------- */
+/*
+ * pyQSM's viz/color.py (segment_hues, color_distribution, saturate_colors, get_color_by_hue,
+ * remove_color_pts, get_green_surfaces) on the device. All arithmetic is fp64, one operation at a time in
+ * the order written here, without contraction: the conversions are matplotlib.colors.rgb_to_hsv and
+ * hsv_to_rgb bit for bit (csrc/color_exact.hpp holds the one statement kernels and host share).
+ *
+ * rgb -> hsv, per row (r, g, b) in [0, 1]:
+ *   mx = max, mn = min, d = mx - mn;  v = mx;  s = d / mx if mx > 0, else 0.
+ *   If d > 0 the LAST line that holds wins:  r == mx: x = (g - b) / d;  g == mx: x = 2.0 + (b - r) / d;
+ *   b == mx: x = 4.0 + (r - g) / d.  Otherwise x = 0.
+ *   y = x / 6.0 (a division);  h = y + 1.0 if y < 0, else y: a tiny negative y gives h == 1.0 exactly.
+ * hsv -> rgb:
+ *   h6 = h * 6.0;  i = (int64) h6;  f = h6 - i;
+ *   p = v * (1.0 - s);  q = v * (1.0 - (s * f));  t = v * (1.0 - (s * (1.0 - f)));
+ *   (r, g, b) by i % 6: (v,t,p) (q,v,p) (p,v,t) (p,q,v) (t,p,v) (v,p,q); h == 1.0 gives i = 6, case 0;
+ *   s == 0 gives (v, v, v).
+ * Saturation lift: s' = s + (1.0 - s) / lift_div where s < min_s (strict), else s; lift_div < 1 or NaN:
+ *   PYQSM_EINVAL. The corrected colour is hsv_to_rgb(h, s', v). lift_div = +inf is the identity: no lift and
+ *   no round trip, the corrected colour is the input bit for bit and the class is taken on rgb_to_hsv(rgb)
+ *   (pyQSM's get_color_by_hue; a round trip through hsv moves last bits even when s' == s).
+ * Rules: K <= PYQSM_COLOR_MAX_RULES rows of rules f64 [K,6] = (h_lo, h_hi, s_lo, s_hi, v_lo, v_hi), ±inf for
+ *   "unbounded"; closed i32 [K]: bit 2c makes the lower bound of channel c inclusive, bit 2c + 1 the upper
+ *   one. A NaN bound: PYQSM_EINVAL.
+ * Class: the index of the first rule that holds on rgb_to_hsv(corrected rgb) (the second conversion, after
+ *   the round trip), PYQSM_COLOR_NONE when none holds.
+ *
+ * pyqsm_rgb_to_hsv / pyqsm_hsv_to_rgb: f64 [n,3] to f64 [n,3], host arrays.
+ * pyqsm_hsv_segment: rgb f64 [n,3]; cls u8 [n]; counts i64 [K + 1] rows per class, "none" last;
+ *   members i64 [n] or NULL: the CSR by class (classes 0 .. K-1, then "none"; the offsets are the running
+ *   sums of counts), ascending inside a class; rgb_out / hsv_out f64 [n,3] or NULL: the corrected colours
+ *   and their hsv. One pass over the rows, a scan over [class][wave], one pass over the class bytes for the
+ *   members; no atomics, the same bytes on every run. n == 0 touches no device (zero counts); K == 0 is
+ *   allowed (every row is "none"). n above 2^31 - 256: PYQSM_ERANGE.
+ * pyqsm_hsv_segment_dev: the same with rgb, cls, members, rgb_out and hsv_out in HBM (rules, closed and
+ *   counts on the host).
+ * pyqsm_hsv_histogram: vals f64 [n,3], hsv rows (is_hsv != 0) or rgb rows converted first; bins i32 [3],
+ *   each >= 1 (else PYQSM_EINVAL), product <= PYQSM_COLOR_MAX_BINS (else PYQSM_ERANGE). The edges of a
+ *   channel with b bins are linspace(0, 1, b + 1) (j * (1.0 / b), the last one 1.0) and the bin of x is
+ *   min(searchsorted(edges, x, 'right') - 1, b - 1): np.histogramdd(hsv, bins, range=[(0, 1)] * 3).
+ *   which >= 0: only the rows with cls[i] == which (cls u8 [n]); which == -1: all rows, cls may be NULL.
+ *   hist i64 [bins[0] * bins[1] * bins[2]], row-major. Integer atomics only.
+ * pyqsm_color_mask: the ascending indices idx i64 [n] (the caller's) and their *count of the rows with
+ *   PYQSM_MASK_SUM_GT: ((0.0 + r) + g) + b > param (pyQSM's "white": 2.7);
+ *   PYQSM_MASK_GREEN:  g > r && g > b && 0.5 < r / b && r / b < 2 (b == 0: inf or NaN, false).
+ * Input: the host forms refuse a NaN or a value outside [0, 1] with PYQSM_EINVAL before any launch (matplotlib
+ *   raises there too); the _dev form raises an error word in its kernel and returns PYQSM_EINVAL after it,
+ *   its outputs then unspecified.
+ */
+#define PYQSM_COLOR_MAX_RULES 16
+#define PYQSM_COLOR_MAX_BINS 4096
+#define PYQSM_COLOR_NONE 255
+#define PYQSM_MASK_SUM_GT 0
+#define PYQSM_MASK_GREEN 1
+int pyqsm_rgb_to_hsv(const double* rgb, int64_t n, double* hsv, int32_t device);
+int pyqsm_hsv_to_rgb(const double* hsv, int64_t n, double* rgb, int32_t device);
+int pyqsm_hsv_segment(const double* rgb, int64_t n, double min_s, double lift_div, const double* rules,
+                      const int32_t* closed, int32_t K, uint8_t* cls, int64_t* counts, int64_t* members,
+                      double* rgb_out, double* hsv_out, int32_t device);
+int pyqsm_hsv_segment_dev(const double* rgb_dev, int64_t n, double min_s, double lift_div, const double* rules,
+                          const int32_t* closed, int32_t K, uint8_t* cls_dev, int64_t* counts,
+                          int64_t* members_dev, double* rgb_out_dev, double* hsv_out_dev, int32_t device);
+int pyqsm_hsv_histogram(const double* vals, int64_t n, int32_t is_hsv, const int32_t* bins, const uint8_t* cls,
+                        int32_t which, int64_t* hist, int32_t device);
+int pyqsm_color_mask(const double* rgb, int64_t n, int32_t kind, double param, int64_t* idx, int64_t* count,
+                     int32_t device);
+
 #ifdef __cplusplus
 }
 #endif

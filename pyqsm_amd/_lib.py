@@ -89,6 +89,12 @@ SIGNATURES = {
     "pyqsm_convex_hull": (ctypes.c_int, [vp, i64, vp, i64, i64, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp, i32]),
     "pyqsm_points_in_boxes": (ctypes.c_int, [vp, i64, vp, i32, vp, ctypes.POINTER(vp), i32]),
     "pyqsm_points_in_boxes_dev": (ctypes.c_int, [vp, i64, vp, i32, vp, ctypes.POINTER(vp), i32]),
+    "pyqsm_rgb_to_hsv": (ctypes.c_int, [vp, i64, vp, i32]),
+    "pyqsm_hsv_to_rgb": (ctypes.c_int, [vp, i64, vp, i32]),
+    "pyqsm_hsv_segment": (ctypes.c_int, [vp, i64, dbl, dbl, vp, vp, i32, vp, vp, vp, vp, vp, i32]),
+    "pyqsm_hsv_segment_dev": (ctypes.c_int, [vp, i64, dbl, dbl, vp, vp, i32, vp, vp, vp, vp, vp, i32]),
+    "pyqsm_hsv_histogram": (ctypes.c_int, [vp, i64, i32, vp, vp, i32, vp, i32]),
+    "pyqsm_color_mask": (ctypes.c_int, [vp, i64, i32, dbl, vp, ctypes.POINTER(i64), i32]),
     "pyqsm_pdist_select": (ctypes.c_int, [vp, i64, i32, vp, i64, vp, i32, i64, vp, vp, vp, vp, i32]),
     "pyqsm_select_values": (ctypes.c_int, [vp, i64, i32, i32, vp, i32, vp, i32]),
     "pyqsm_select_values_dev": (ctypes.c_int, [vp, i64, i32, i32, vp, i32, vp, i32]),

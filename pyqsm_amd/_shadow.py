@@ -6,7 +6,7 @@ pyQSM/pipeline.py:8). With this directory AHEAD of pyQSM's on ``sys.path``:
 
 * ``geometry/``, ``math_utils/``, ``viz/`` and ``utils/`` hold no ``__init__.py`` on either side,
   so they are namespace packages whose portions merge: ``math_utils.fit`` is this package's,
-  ``utils.io`` / ``geometry.surf_recon`` / ``viz.color`` are still pyQSM's;
+  ``utils.io`` / ``viz.viz_utils`` / ``viz.plotting`` are still pyQSM's;
 * a module that exists on BOTH sides (``math_utils/fit.py``, ``geometry/point_cloud_processing.py``,
   ``qsm_generation.py`` …) resolves to this package's, which only restates the hot-path functions.
   Every other name of the shadowed module (``kmeans``, ``clean_cloud``, ``crop_by_percentile``,
@@ -99,6 +99,12 @@ HOT_FUNCTIONS = {
     "qsm_generation": ("fit_cyl_to_cluster",),
     "exploration": ("compute_features", "smooth_feature", "random_forest_classification"),
     "utils.algo": ("smooth_feature",),
+    # rgb_to_hsv / hsv_to_rgb are NOT listed: under those names pyQSM's module holds matplotlib's own functions,
+    # and install() would rebind them wherever they are imported, matplotlib.colors included
+    "viz.color": ("segment_hues", "color_distribution", "saturate_colors", "get_color_by_hue", "remove_color_pts",
+                  "get_green_surfaces", "homog_colors", "split_on_percentile",
+                  # without a counterpart in the reference (install() skips them)
+                  "hue_segments", "hsv_histogram"),
 }
 
 

@@ -83,13 +83,20 @@ class PointCloud:
         return f"PointCloud with {len(self.points)} points."
 
     def select_by_index(self, idx, invert: bool = False) -> "PointCloud":
+        """The rows ``idx`` (or the others, in their order); normals and colours are carried when they have
+        the cloud's length, as Open3D carries them."""
         idx = np.asarray(idx, dtype=np.int64)
         nrm = self.normals if self.has_normals() else None
+        col = np.asarray(self.colors) if self.has_colors() else None
         if invert:
             mask = np.ones(len(self.points), dtype=bool)
             mask[idx] = False
-            return PointCloud(self.points[mask], normals=None if nrm is None else nrm[mask])
-        return PointCloud(self.points[idx], normals=None if nrm is None else nrm[idx])
+            idx = mask
+        return PointCloud(self.points[idx], colors=None if col is None else col[idx],
+                          normals=None if nrm is None else nrm[idx])
+
+    def has_colors(self) -> bool:
+        return self.colors is not None and len(self.points) > 0 and len(self.colors) == len(self.points)
 
     def has_normals(self) -> bool:
         return self.normals is not None and len(self.normals) == len(self.points) and len(self.points) > 0

@@ -8,8 +8,9 @@ the contraction's first shift and the projected areas.
     project_components_in_clusters(...)                canopy_metrics.project_components_in_clusters (:370-423)
     area_indices(metrics, pca)                         EAI, LAI and proposed LAI of data/notes/methods.md
 
-pyQSM has no module of this name, so nothing is shadowed: ``canopy_metrics`` and ``viz.color`` keep
-resolving to pyQSM's own files (tests/test_dropin.py); INTEGRATION.md has the one-line edits.
+pyQSM has no module of this name, so nothing is shadowed: ``canopy_metrics`` keeps resolving to pyQSM's
+own file (tests/test_dropin.py; INTEGRATION.md has the one-line edits), and ``viz.color`` of this package
+(the colour path) re-exports ``split_on_percentile`` from here.
 
 The percentiles are exact: an order statistic is a radix selection on the device over keys recomputed
 from the rows (``hip.select_values``), and the percentile is NumPy's linear rule applied on the host

@@ -949,6 +949,130 @@ def points_in_boxes(points, boxes, device: int = 0):
     return np.concatenate(ptrs), idx
 
 
+# ---------------------------------------------------------------- colours: HSV classes, lift, histogram, masks
+
+COLOR_MAX_RULES = 16            # PYQSM_COLOR_MAX_RULES
+COLOR_MAX_BINS = 4096           # PYQSM_COLOR_MAX_BINS
+COLOR_NONE = 255                # PYQSM_COLOR_NONE
+COLOR_MASKS = {"sum_gt": 0, "green": 1}     # PYQSM_MASK_SUM_GT, PYQSM_MASK_GREEN
+
+
+def _colors(colors, what: str = "colors") -> np.ndarray:
+    c = np.ascontiguousarray(np.asarray(colors), dtype=np.float64)
+    if c.ndim != 2 or c.shape[1] != 3:
+        raise ValueError(f"expected {what} of shape [n,3], got {c.shape}")
+    return c
+
+
+def _color_check(code: int) -> None:
+    """A NaN or a value outside [0, 1] is a ValueError, as matplotlib raises one."""
+    if code == -1 and b"outside [0, 1]" in (_lib.load().pyqsm_last_error() or b""):
+        raise ValueError("colour values must be in the range 0 to 1")
+    check(code)
+
+
+def rgb_to_hsv(colors, device: int = 0) -> np.ndarray:
+    """``pyqsm_rgb_to_hsv``: ``matplotlib.colors.rgb_to_hsv`` of float64 [n,3] rows, bit for bit."""
+    c = _colors(colors)
+    out = np.empty_like(c)
+    _color_check(_lib.load().pyqsm_rgb_to_hsv(_p(c), c.shape[0], _p(out), int(device)))
+    return out
+
+
+def hsv_to_rgb(hsv, device: int = 0) -> np.ndarray:
+    """``pyqsm_hsv_to_rgb``: ``matplotlib.colors.hsv_to_rgb`` of float64 [n,3] rows, bit for bit."""
+    c = _colors(hsv, "hsv")
+    out = np.empty_like(c)
+    _color_check(_lib.load().pyqsm_hsv_to_rgb(_p(c), c.shape[0], _p(out), int(device)))
+    return out
+
+
+def _color_rules(rules, closed):
+    r = np.ascontiguousarray(np.asarray(rules, dtype=np.float64).reshape(-1, 6))
+    cl = np.ascontiguousarray(np.asarray(closed, dtype=np.int32).reshape(-1))
+    if r.shape[0] != cl.shape[0]:
+        raise ValueError(f"{r.shape[0]} rules but {cl.shape[0]} closed masks")
+    if r.shape[0] > COLOR_MAX_RULES:
+        raise ValueError(f"at most {COLOR_MAX_RULES} rules per call")
+    return r, cl
+
+
+class HsvSegment(NamedTuple):
+    """Result of :func:`hsv_segment`."""
+    cls: np.ndarray          # uint8 [n]: the first rule that holds, 255 for none
+    counts: np.ndarray       # int64 [K + 1]: rows per class, "none" last
+    members: np.ndarray      # int64 [n] the CSR by class (ascending inside a class), or None
+    rgb: np.ndarray          # float64 [n,3] the corrected colours, or None
+    hsv: np.ndarray          # float64 [n,3] rgb_to_hsv of the corrected colours, or None
+
+
+def hsv_segment(colors, rules, closed, min_s: float = 0.2, lift_div: float = 3.0, members: bool = True,
+                corrected: bool = True, hsv: bool = True, device: int = 0) -> HsvSegment:
+    """``pyqsm_hsv_segment``: saturation lift (``s + (1 - s) / lift_div`` where ``s < min_s``), round trip
+    through rgb and the class of every row, the first of ``rules`` float64 [K,6] = (h_lo, h_hi, s_lo, s_hi,
+    v_lo, v_hi) that holds on the hsv of the corrected colour; ``closed`` int32 [K]: bit 2c / 2c + 1 make
+    the lower / upper bound of channel c inclusive."""
+    c = _colors(colors)
+    r, cl = _color_rules(rules, closed)
+    n, K = c.shape[0], r.shape[0]
+    cls = np.empty(n, np.uint8)
+    counts = np.zeros(K + 1, np.int64)
+    mem = np.empty(n, np.int64) if members else None
+    rgb = np.empty((n, 3)) if corrected else None
+    hs = np.empty((n, 3)) if hsv else None
+    _color_check(_lib.load().pyqsm_hsv_segment(_p(c), n, float(min_s), float(lift_div), _p(r), _p(cl), K, _p(cls),
+                                               _p(counts), _p(mem), _p(rgb), _p(hs), int(device)))
+    return HsvSegment(cls, counts, mem, rgb, hs)
+
+
+def hsv_segment_dev(rgb_ptr: int, n: int, rules, closed, cls_ptr: int, min_s: float = 0.2, lift_div: float = 3.0,
+                    members_ptr=None, rgb_out_ptr=None, hsv_out_ptr=None, device: int = 0) -> np.ndarray:
+    """:func:`hsv_segment` on ``n`` device-resident rows, every output but the counts (returned) left in
+    the caller's device buffers: cls uint8 [n], members int64 [n], rgb_out / hsv_out float64 [n,3]."""
+    r, cl = _color_rules(rules, closed)
+    counts = np.zeros(r.shape[0] + 1, np.int64)
+    _color_check(_lib.load().pyqsm_hsv_segment_dev(rgb_ptr, int(n), float(min_s), float(lift_div), _p(r), _p(cl),
+                                                   r.shape[0], cls_ptr, _p(counts), members_ptr, rgb_out_ptr,
+                                                   hsv_out_ptr, int(device)))
+    return counts
+
+
+def hsv_histogram(values, bins=(20, 1, 1), is_hsv: bool = False, cls=None, which: int = -1,
+                  device: int = 0) -> np.ndarray:
+    """``pyqsm_hsv_histogram``: ``np.histogramdd(hsv, bins, range=[(0, 1)] * 3)[0]`` as int64 [bh, bs, bv] of
+    hsv rows, or of rgb rows converted first; with ``cls`` uint8 [n] and ``which >= 0`` only the rows of
+    that class."""
+    c = _colors(values, "values")
+    b = np.ascontiguousarray(np.asarray(bins, dtype=np.int32).reshape(-1))
+    if b.shape[0] != 3:
+        raise ValueError(f"expected three bin counts, got {b.shape[0]}")
+    if (b < 1).any():
+        raise ValueError("every bin count must be at least 1")
+    k = None
+    if int(which) >= 0:
+        if cls is None:
+            raise ValueError("which needs the class bytes")
+        k = np.ascontiguousarray(np.asarray(cls, dtype=np.uint8).reshape(-1))
+        if k.shape[0] != c.shape[0]:
+            raise ValueError(f"{k.shape[0]} classes for {c.shape[0]} rows")
+    nb = int(b[0]) * int(b[1]) * int(b[2])
+    hist = np.zeros(min(nb, COLOR_MAX_BINS), np.int64)
+    _color_check(_lib.load().pyqsm_hsv_histogram(_p(c), c.shape[0], int(bool(is_hsv)), _p(b), _p(k), int(which),
+                                                 _p(hist), int(device)))
+    return hist.reshape(tuple(int(v) for v in b))
+
+
+def color_mask(colors, kind="sum_gt", param: float = 2.7, device: int = 0) -> np.ndarray:
+    """``pyqsm_color_mask``: the ascending indices of the rows with ``((0.0 + r) + g) + b > param``
+    (``kind='sum_gt'``) or ``g > r and g > b and 0.5 < r / b < 2`` (``kind='green'``)."""
+    c = _colors(colors)
+    idx = np.empty(c.shape[0], np.int64)
+    count = i64(0)
+    _color_check(_lib.load().pyqsm_color_mask(_p(c), c.shape[0], COLOR_MASKS[kind], float(param), _p(idx),
+                                              ctypes.byref(count), int(device)))
+    return idx[:count.value].copy()
+
+
 # ---------------------------------------------------------------- pairwise-distance order statistics
 
 PDIST_MAX_RANKS = 32                          # PYQSM_PDIST_MAX_RANKS
