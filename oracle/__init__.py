@@ -59,6 +59,8 @@ def _lib():
         lib.orc_pc_laplacian.restype = ctypes.c_int
         lib.orc_pc_laplacian.argtypes = [p, i64, i32, dbl, ctypes.POINTER(i64),
                                          ctypes.POINTER(p), ctypes.POINTER(p), ctypes.POINTER(p), p]
+        lib.orc_pc_laplacian_counts.restype = ctypes.c_int
+        lib.orc_pc_laplacian_counts.argtypes = [p, i64, i32, dbl, p, p]
         lib.orc_free.restype = None
         lib.orc_point_mesh_distance.argtypes = [p, i64, p, i64, p, i64, p, p]
         lib.orc_free.argtypes = [p]
@@ -480,6 +482,22 @@ def point_cloud_laplacian(points, n_neighbors=30, mollify_factor=1e-5):
         for q in (ip, ix, dv):
             lib.orc_free(q)
     return csr_matrix((data, indices, indptr), shape=(n, n)), mass
+
+
+def point_cloud_laplacian_counts(points, n_neighbors=30, mollify_factor=1e-5):
+    """(edge-bucket length int32 [n], row contributions int32 [n]) of the build behind
+    :func:`point_cloud_laplacian`: per vertex, the records of the edges whose smaller endpoint it
+    is (before gluing) and the contributions to its row (after the flips, before equal columns
+    are merged) — the two sizes by which laplacian.hip picks its gluing and row-sorting paths."""
+    pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    n = pts.shape[0]
+    bucket = np.zeros(n, dtype=np.int32)
+    rows = np.zeros(n, dtype=np.int32)
+    rc = _lib().orc_pc_laplacian_counts(_ptr(pts), n, int(n_neighbors), float(mollify_factor),
+                                        _ptr(bucket), _ptr(rows))
+    if rc != 0:
+        raise RuntimeError("orc_pc_laplacian_counts failed (k must be in [3, 64])")
+    return bucket, rows
 
 
 # --------------------------------------------------------------------------

@@ -712,9 +712,37 @@ static int try_flip(int h, int32_t* fv, double* fl, int32_t* fn) {
  * CSR out-parameters are malloc'ed (release with orc_free). Returns 0, or -1 on
  * allocation failure / bad k.
  */
+static int pc_laplacian_build(const double* xyz, int64_t n, int32_t k, double moll, int64_t* nnz_out,
+                              int32_t** indptr_out, int32_t** indices_out, double** vals_out,
+                              double* mass, int32_t* bucket_len, int32_t* row_len);
+
 int orc_pc_laplacian(const double* xyz, int64_t n, int32_t k, double moll, int64_t* nnz_out,
                      int32_t** indptr_out, int32_t** indices_out, double** vals_out,
                      double* mass) {
+  return pc_laplacian_build(xyz, n, k, moll, nnz_out, indptr_out, indices_out, vals_out, mass, NULL, NULL);
+}
+
+/*
+ * The sizes that pick the kernel's paths, from the same build: per vertex, the length of its edge
+ * bucket (records of the edges whose SMALLER endpoint it is, before gluing: k_glue_wave up to 64,
+ * k_glue beyond) and the number of contributions in its row after the flips (sort_row_wave<1, 2, 4,
+ * 8> up to 64, 128, 256, 512 entries, the serial sort beyond). Both arrays hold n values.
+ */
+int orc_pc_laplacian_counts(const double* xyz, int64_t n, int32_t k, double moll, int32_t* bucket_len,
+                            int32_t* row_len) {
+  int64_t nnz = 0;
+  int32_t *indptr = NULL, *indices = NULL;
+  double* vals = NULL;
+  double* mass = (double*)malloc((size_t)(n + 1) * sizeof(double));
+  if (!mass) return -1;
+  const int rc = pc_laplacian_build(xyz, n, k, moll, &nnz, &indptr, &indices, &vals, mass, bucket_len, row_len);
+  free(indptr); free(indices); free(vals); free(mass);
+  return rc;
+}
+
+static int pc_laplacian_build(const double* xyz, int64_t n, int32_t k, double moll, int64_t* nnz_out,
+                              int32_t** indptr_out, int32_t** indices_out, double** vals_out,
+                              double* mass, int32_t* bucket_len, int32_t* row_len) {
   if (k < 3 || k > 64) return -1;
   int32_t* nbr = (int32_t*)malloc((size_t)(n * k + 1) * sizeof(int32_t));
   double* d2 = (double*)malloc((size_t)(n * k + 1) * sizeof(double));
@@ -790,6 +818,8 @@ int orc_pc_laplacian(const double* xyz, int64_t n, int32_t k, double moll, int64
     bstart[(v2 < v0 ? v2 : v0) + 1]++;
   }
   for (int64_t i = 0; i < n; ++i) bstart[i + 1] += bstart[i];
+  if (bucket_len)
+    for (int64_t i = 0; i < n; ++i) bucket_len[i] = bstart[i + 1] - bstart[i];
   {
     int32_t* bcur = (int32_t*)calloc((size_t)n + 1, sizeof(int32_t));
     if (!bcur) return -1;
@@ -836,6 +866,8 @@ int orc_pc_laplacian(const double* xyz, int64_t n, int32_t k, double moll, int64
   for (int64_t f = 0; f < F; ++f)
     for (int c = 0; c < 3; ++c) rstart[fv[3 * f + c] + 1] += 2;
   for (int64_t i = 0; i < n; ++i) rstart[i + 1] += rstart[i];
+  if (row_len)
+    for (int64_t i = 0; i < n; ++i) row_len[i] = rstart[i + 1] - rstart[i];
   lap_ent_t* ent = (lap_ent_t*)malloc((size_t)(6 * F + 1) * sizeof(lap_ent_t));
   int32_t* cur = (int32_t*)calloc((size_t)n + 1, sizeof(int32_t));
   if (!ent || !cur) return -1;

@@ -120,6 +120,14 @@ __global__ __launch_bounds__(256) void k_tangent_planes(int n, int k, const doub
 
 __device__ __forceinline__ double bcast(double v, int lane) { return __shfl(v, lane, 64); }
 
+// v of one lane, the same lane for the whole wave (a wave-uniform index): two v_readlane, no LDS crossbar
+__device__ __forceinline__ double readlane_f64(double v, int lane) {
+  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+  const unsigned lo = unsigned(__builtin_amdgcn_readlane(int(unsigned(u)), lane));
+  const unsigned hi = unsigned(__builtin_amdgcn_readlane(int(unsigned(u >> 32)), lane));
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
 // PER = points per wave: 1 (64 lanes for up to 64 neighbours) or 2 (a half-wave of 32 lanes
 // each, for k <= 32 — with pyQSM's 30 neighbours a whole wave per point leaves 34 lanes idle
 // through three k-step loops of fp64 arithmetic). Lane s of a group holds neighbour s; a
@@ -1114,10 +1122,10 @@ __global__ __launch_bounds__(256) void k_rows_wave(int n, const int32_t* __restr
     if (out) emit(col, sum, __popcll(outs & ((1ull << lane) - 1ull)));
     // bookkeeping, the same in every lane
     const unsigned long long lows = __ballot(out && col < i);
-    double dsum = out ? sum : 0.0;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) dsum += __shfl_xor(dsum, off, 64);
-    diag -= dsum;
+    // The diagonal: the merged columns are subtracted one after the other in column order, as k_rows and
+    // the oracle do (a butterfly sum over the lanes, per chunk, left it 1-3 ulp away from theirs in up to a
+    // third of the rows). outs is wave-uniform: a scalar loop of two v_readlane and one subtraction per column.
+    for (unsigned long long o = outs; o; o &= o - 1ull) diag -= readlane_f64(sum, __ffsll(o) - 1);
     written += __popcll(outs);
     below += __popcll(lows);
     const unsigned long long pend = __ballot(pending);
@@ -1284,6 +1292,19 @@ int laplacian_device(Ctx* c, const double* d_xyz, int64_t n, const int64_t* seg_
                        static_cast<const EdgeRec*>(d_rec), d_fn);
     hipLaunchKernelGGL(k_glue, gn, blk, 0, c->stream, N, d_bcount, d_rec, d_fn, 65);
     PQ_HIP(hipGetLastError());
+    if (getenv("PYQSM_LBC_TRACE")) {  // longest edge bucket, and how many k_glue took
+      std::vector<int32_t> bs(size_t(n) + 1);
+      PQ_TRY(fetch(c, bs.data(), d_bcount, size_t(n) + 1));
+      int mx = 0;
+      int64_t over = 0;
+      for (int64_t i = 0; i < n; ++i) {
+        const int len = bs[size_t(i) + 1] - bs[size_t(i)];
+        mx = std::max(mx, len);
+        over += len > 64;
+      }
+      fprintf(stderr, "laplacian edge buckets: %d records at most, %lld buckets beyond the wave path\n", mx,
+              (long long)over);
+    }
     // intrinsic Delaunay flips: rounds of conflict-free flips until none is left
     ProfScope pf(c, "lap_flips");
     PQ_HIP(hipMemsetAsync(d_claim, 0, (size_t(F) + 1) * 8, c->stream));
