@@ -34,6 +34,8 @@
 #include "knn.hpp"
 
 #include <cmath>
+#include <string>
+#include <type_traits>
 
 namespace pyqsm {
 
@@ -397,70 +399,6 @@ __global__ __launch_bounds__(256) void k_knn_reg(int n_query, KnnGrid g,
     }
 }
 
-static int knn_buffer_slots() {  // PYQSM_KNN_BUF=0: direct insertion (the round-1 kernel)
-  static const int v = [] {
-    const char* e = getenv("PYQSM_KNN_BUF");
-    return e ? atoi(e) : 4;
-  }();
-  return v;
-}
-
-template <class CO>
-__global__ void k_knn_wave(int n_query, const int32_t* __restrict__ n_ptr, int n_max,
-                           const int32_t* __restrict__ query_list, const int32_t* __restrict__ pos_of,
-                           KnnGrid g, const int32_t* __restrict__ start, const int32_t* __restrict__ order,
-                           const int32_t* __restrict__ cell_of, CO co, int k,
-                           int exclude_self, int n_total, int last_level, int max_ring,
-                           int32_t* __restrict__ out_idx, double* __restrict__ out_d2,
-                           int32_t* __restrict__ fail_list, int32_t* __restrict__ fail_count);
-
-static bool knn_strict() {  // PYQSM_KNN_STRICT=0: the exact comparison in the first pass already
-  static const bool v = [] {
-    const char* e = getenv("PYQSM_KNN_STRICT");
-    return !(e && e[0] == '0');
-  }();
-  return v;
-}
-
-// tie_list [n] / tie_count [1] (zeroed by the caller): scratch of the strict pass.
-template <int K>
-static int launch_knn_reg(Ctx* c, int n, const DevGrid& g, int k, int excl, int last, int32_t* idx,
-                          double* d2, int32_t* fail_list, int32_t* fail_count, int32_t* tie_list,
-                          int32_t* tie_count) {
-  KnnGrid kg{g.nx, g.ny, g.nz, g.cell, g.minx, g.miny, g.minz};
-  const dim3 grid(ceil_div(n, 256)), blk(256);
-  const int32_t* none = nullptr;
-  on_coords(g, [&](auto co) {
-    using CO = decltype(co);
-    if (knn_buffer_slots() == 0) {
-      hipLaunchKernelGGL((k_knn_reg<K, 0, false, CO>), grid, blk, 0, c->stream, n, kg, none, none, 0, g.start, g.order,
-                         g.cell_of, co, k, excl, n, last, idx, d2, fail_list, fail_count, tie_list, tie_count);
-    } else if (!knn_strict()) {
-      hipLaunchKernelGGL((k_knn_reg<K, 4, false, CO>), grid, blk, 0, c->stream, n, kg, none, none, 0, g.start, g.order,
-                         g.cell_of, co, k, excl, n, last, idx, d2, fail_list, fail_count, tie_list, tie_count);
-    } else {
-      hipLaunchKernelGGL((k_knn_reg<K, 4, true, CO>), grid, blk, 0, c->stream, n, kg, none, none, 0, g.start, g.order,
-                         g.cell_of, co, k, excl, n, last, idx, d2, fail_list, fail_count, tie_list, tie_count);
-      // The queries whose result hung on a tie, by the exact comparison: a WAVE per query (a lane per
-      // query would be one long-running wave of 64 unrelated walks — 0.5 ms for 238 such queries of
-      // a millimetre-quantised million points; this way they cost 20 us). Their number stays on the
-      // device; the waves of a fixed grid stride over them. A cloud on a regular lattice ties nearly
-      // everywhere (760 k of a million queries): past n / 16 the list goes to the per-lane kernel
-      // with the exact comparison instead (both launches are issued, one of them finds nothing to do).
-      const int many = n / 16;
-      hipLaunchKernelGGL(k_knn_wave<CO>, dim3(unsigned(std::min<int64_t>(ceil_div(n, 4), 8192))), blk, 0, c->stream, n,
-                         static_cast<const int32_t*>(tie_count), many, static_cast<const int32_t*>(tie_list),
-                         static_cast<const int32_t*>(nullptr), kg, g.start, g.order, g.cell_of, co, k, excl, n, last,
-                         kMaxRing, idx, d2, fail_list, fail_count);
-      hipLaunchKernelGGL((k_knn_reg<K, 4, false, CO>), grid, blk, 0, c->stream, n, kg,
-                         static_cast<const int32_t*>(tie_list), static_cast<const int32_t*>(tie_count), many, g.start,
-                         g.order, g.cell_of, co, k, excl, n, last, idx, d2, fail_list, fail_count, tie_list, tie_count);
-    }
-  });
-  PQ_HIP(hipGetLastError());
-  return 0;
-}
-
 // Wave-per-query variant for the retry levels (k <= 64): there the cells are
 // coarse and hold thousands of points, so the 64 lanes scan a run together.
 // The sorted best-k list lives in registers, element j in lane j; an insertion
@@ -761,11 +699,140 @@ __global__ __launch_bounds__(256) void k_invert_order(int n, const int32_t* __re
   if (p < n) pos_of[order[p]] = p;
 }
 
+// ---- the host side: switches, the kernel of a level, the steps of knn_device --------------------
+
+struct KnnKnobs {
+  // read once per process
+  int buf;         // PYQSM_KNN_BUF=0: direct insertion (the round-1 kernel)
+  bool strict;     // PYQSM_KNN_STRICT=0: the exact comparison in the first pass already
+  double occ_div;  // PYQSM_KNN_OCC: points per occupied cell = k / this
+  int wide;        // PYQSM_KNN_WIDE: shells a retry level may walk (kWideRing)
+  // read on every call
+  bool robust_box;  // PYQSM_KNN_ROBUST_BOX=0: grids over the full box
+  bool trace;       // PYQSM_KNN_TRACE: what every level did, on stderr
+};
+
+static KnnKnobs read_knobs() {
+  static const KnnKnobs once = [] {
+    KnnKnobs kn{};
+    const char* e = getenv("PYQSM_KNN_BUF");
+    kn.buf = e ? atoi(e) : 4;
+    e = getenv("PYQSM_KNN_STRICT");
+    kn.strict = !(e && e[0] == '0');
+    e = getenv("PYQSM_KNN_OCC");
+    const double v = e ? atof(e) : 3.0;
+    kn.occ_div = v > 0.25 && v < 64.0 ? v : 3.0;
+    e = getenv("PYQSM_KNN_WIDE");
+    kn.wide = e ? atoi(e) : kWideRing;
+    return kn;
+  }();
+  KnnKnobs kn = once;
+  const char* e = getenv("PYQSM_KNN_ROBUST_BOX");
+  kn.robust_box = !(e && e[0] == '0');
+  kn.trace = getenv("PYQSM_KNN_TRACE") != nullptr;
+  return kn;
+}
+
+// The search kernel of one level: what the trace names and what is launched.
+struct KnnKernel {
+  enum Kind { Reg, Wave, Lds } kind;
+  int width;  // Reg: the list length K; Lds: the block size T
+  int buf;    // Reg: BUF
+  bool strict;  // Reg: STRICT, followed by the two tie passes
+};
+
+static KnnKernel pick_kernel(int level, int k, const KnnKnobs& kn) {
+  if (level == 0 && k <= 32) {
+    // list length = k rounded up to a multiple of 4: every slot is ~11 instructions per
+    // insertion, and slots beyond k loosen the acceptance test
+    const int buf = kn.buf == 0 ? 0 : 4;
+    return {KnnKernel::Reg, (k + 3) / 4 * 4, buf, buf != 0 && kn.strict};
+  }
+  if (level > 0 && k <= 64) return {KnnKernel::Wave, 0, 0, false};
+  return {KnnKernel::Lds, k <= 48 ? 256 : k <= 96 ? 128 : 64, 0, false};
+}
+
+static std::string kernel_name(const KnnKernel& kk) {
+  if (kk.kind == KnnKernel::Wave) return "k_knn_wave";
+  char s[32];
+  if (kk.kind == KnnKernel::Reg)
+    snprintf(s, sizeof s, "k_knn_reg<%d,%d,%s>", kk.width, kk.buf, kk.strict ? "true" : "false");
+  else
+    snprintf(s, sizeof s, "k_knn<%d>", kk.width);
+  return s;
+}
+
+// fn(std::integral_constant<int, W>) for the W among Ws that equals `width`; false: there is none.
+template <int... Ws, class F>
+static bool on_width(int width, F&& fn) {
+  return ((width == Ws ? (fn(std::integral_constant<int, Ws>{}), true) : false) || ...);
+}
+
+// What every search launch of one level passes on: the grid, where the results go, and the list of
+// the queries this level leaves open. Built once per level.
+struct KnnArgs {
+  KnnGrid g;
+  const int32_t *start, *order, *cell_of;
+  int k, exclude_self, n_total, last_level;
+  int32_t* out_idx;
+  double* out_d2;
+  int32_t *fail_list, *fail_count;
+};
+static KnnArgs knn_args(const DevGrid& g, int k, int excl, int n_total, int last, int32_t* idx, double* d2,
+                        int32_t* fail_list, int32_t* fail_count) {
+  return KnnArgs{KnnGrid{g.nx, g.ny, g.nz, g.cell, g.minx, g.miny, g.minz}, g.start, g.order, g.cell_of, k, excl,
+                 n_total, last, idx, d2, fail_list, fail_count};
+}
+
+template <class CO>
+static void launch_wave(Ctx* c, unsigned blocks, const KnnArgs& a, CO co, int n_query, const int32_t* n_ptr, int n_max,
+                        const int32_t* list, const int32_t* pos_of, int max_ring) {
+  hipLaunchKernelGGL(k_knn_wave<CO>, dim3(blocks), dim3(256), 0, c->stream, n_query, n_ptr, n_max, list, pos_of, a.g,
+                     a.start, a.order, a.cell_of, co, a.k, a.exclude_self, a.n_total, a.last_level, max_ring, a.out_idx,
+                     a.out_d2, a.fail_list, a.fail_count);
+}
+
+// tie_list [n] / tie_count [1] (zeroed by the caller): scratch of the strict pass.
+template <int K>
+static int launch_knn_reg(Ctx* c, const KnnKernel& kk, const DevGrid& g, const KnnArgs& a, int n, int32_t* tie_list,
+                          int32_t* tie_count) {
+  const dim3 grid(ceil_div(n, 256)), blk(256);
+  const int32_t* none = nullptr;
+  bool known = true;
+  on_coords(g, [&](auto co) {
+    using CO = decltype(co);
+    auto pass = [&](auto kernel, const int32_t* qlist, const int32_t* qcount, int q_min) {
+      hipLaunchKernelGGL(kernel, grid, blk, 0, c->stream, n, a.g, qlist, qcount, q_min, a.start, a.order, a.cell_of, co,
+                         a.k, a.exclude_self, a.n_total, a.last_level, a.out_idx, a.out_d2, a.fail_list, a.fail_count,
+                         tie_list, tie_count);
+    };
+    if (kk.buf == 0 && !kk.strict) {
+      pass(k_knn_reg<K, 0, false, CO>, none, none, 0);
+    } else if (kk.buf == 4 && !kk.strict) {
+      pass(k_knn_reg<K, 4, false, CO>, none, none, 0);
+    } else if (kk.buf == 4) {
+      pass(k_knn_reg<K, 4, true, CO>, none, none, 0);
+      // The queries whose result hung on a tie, by the exact comparison: a WAVE per query (a lane per
+      // query would be one long-running wave of 64 unrelated walks — 0.5 ms for 238 such queries of
+      // a millimetre-quantised million points; this way they cost 20 us). Their number stays on the
+      // device; the waves of a fixed grid stride over them. A cloud on a regular lattice ties nearly
+      // everywhere (760 k of a million queries): past n / 16 the list goes to the per-lane kernel
+      // with the exact comparison instead (both launches are issued, one of them finds nothing to do).
+      const int many = n / 16;
+      launch_wave(c, unsigned(std::min<int64_t>(ceil_div(n, 4), 8192)), a, co, n, tie_count, many, tie_list, none,
+                  kMaxRing);
+      pass(k_knn_reg<K, 4, false, CO>, tie_list, tie_count, many);
+    } else {
+      known = false;  // no such instantiation: pick_kernel and this table disagree
+    }
+  });
+  return known ? 0 : fail(PYQSM_EINVAL, "knn: no kernel %s", kernel_name(kk).c_str());
+}
+
 template <int T>
-static int launch_knn(Ctx* c, int n_query, const int32_t* list, const int32_t* pos_of,
-                      const DevGrid& g, int k, int excl, int n_total, int last, int32_t* idx,
-                      double* d2, int32_t* fail_list, int32_t* fail_count) {
-  const size_t smem = size_t(k) * T * 12;
+static int launch_lds(Ctx* c, const DevGrid& g, const KnnArgs& a, int n_query, const int32_t* list,
+                      const int32_t* pos_of) {
+  const size_t smem = size_t(a.k) * T * 12;
   static std::atomic<uint64_t> attr_set{0};  // one bit per device (the attribute is per device)
   const uint64_t bit = 1ull << (c->device & 63);
   if (!(attr_set.load(std::memory_order_acquire) & bit)) {
@@ -775,13 +842,151 @@ static int launch_knn(Ctx* c, int n_query, const int32_t* list, const int32_t* p
                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr_set.fetch_or(bit, std::memory_order_release);
   }
-  KnnGrid kg{g.nx, g.ny, g.nz, g.cell, g.minx, g.miny, g.minz};
   on_coords(g, [&](auto co) {
     hipLaunchKernelGGL((k_knn<T, decltype(co)>), dim3(ceil_div(n_query, T)), dim3(T), smem, c->stream, n_query, list,
-                       pos_of, kg, g.start, g.order, g.cell_of, co, k, excl, n_total, last, idx, d2, fail_list,
-                       fail_count);
+                       pos_of, a.g, a.start, a.order, a.cell_of, co, a.k, a.exclude_self, a.n_total, a.last_level,
+                       a.out_idx, a.out_d2, a.fail_list, a.fail_count);
   });
+  return 0;
+}
+
+// The queries: every point in sorted order (list null: level 0), or the n_query original indices in
+// `list`, whose sorted positions pos_of gives.
+static int launch_kernel(Ctx* c, const KnnKernel& kk, const DevGrid& g, const KnnArgs& a, int n_query,
+                         const int32_t* list, const int32_t* pos_of, int ring, int32_t* tie_list, int32_t* tie_count) {
+  bool known = true;
+  int rc = 0;
+  switch (kk.kind) {
+    case KnnKernel::Reg:
+      known = on_width<4, 8, 12, 16, 20, 24, 28, 32>(kk.width, [&](auto w) {
+        rc = launch_knn_reg<decltype(w)::value>(c, kk, g, a, n_query, tie_list, tie_count);
+      });
+      break;
+    case KnnKernel::Wave:
+      // (one or two waves per block instead of four: no difference — the launch lasts as long as its
+      // longest waves, 0.34 ms for the forest's 9 864 outliers)
+      on_coords(g, [&](auto co) {
+        launch_wave(c, unsigned(ceil_div(n_query, 4)), a, co, n_query, nullptr, 0, list, pos_of, ring);
+      });
+      break;
+    case KnnKernel::Lds:
+      known = on_width<256, 128, 64>(
+          kk.width, [&](auto w) { rc = launch_lds<decltype(w)::value>(c, g, a, n_query, list, pos_of); });
+      break;
+  }
+  if (!known) return fail(PYQSM_EINVAL, "knn: no kernel %s", kernel_name(kk).c_str());
+  PQ_TRY(rc);
   PQ_HIP(hipGetLastError());
+  return 0;
+}
+
+// One level's search: the kernel picked once, named in the trace and launched. `made`: how the grid
+// came about, if not planned for level 0 (trace only).
+static int search_level(Ctx* c, const KnnKnobs& kn, int level, const DevGrid& g, const char* made, const KnnArgs& a,
+                        int n_query, const int32_t* list, const int32_t* pos_of, int ring, int32_t* tie_list,
+                        int32_t* tie_count) {
+  const KnnKernel kk = pick_kernel(level, a.k, kn);
+  if (kn.trace)  // printed for the last level too (knn_device's own lines are not)
+    fprintf(stderr, "knn level %d: grid %d x %d x %d of cell %.4g%s, %s, %s, %d queries%s\n", level, g.nx, g.ny, g.nz,
+            g.cell, made, g.p4 ? "fp32 records" : "fp64 arrays", kernel_name(kk).c_str(), n_query,
+            a.last_level ? ", last level" : "");
+  ProfScope ps(c, level == 0 ? "knn_search" : "knn_retry");
+  return launch_kernel(c, kk, g, a, n_query, list, pos_of, ring, tie_list, tie_count);
+}
+
+// ---- level-0 cell edge: aim at ~k/3 points per occupied cell -----------
+// Two count-only probes on coarse grids give the local density and how it
+// scales with the edge (exponent ~2 for surfaces, ~3 for volumes); the edge
+// for the target occupancy follows by extrapolation, and one corrective
+// rebuild is allowed if the sorted grid misses the target by more than 2.5x.
+static constexpr int64_t kMaxCells = int64_t(1) << 28;
+struct KnnPlan {
+  DevGrid g;             // the grid of the level at hand
+  double box[6];         // what every grid of the call is built over
+  bool all_f32 = false;  // every coordinate fp32-representable: the grids keep 16-byte fp32 records
+};
+static int plan_level0_grid(Ctx* c, const double* xyz, int64_t n, int k, const KnnKnobs& kn, KnnPlan* p) {
+  ProfScope ps(c, "knn_bin");
+  double* box = p->box;
+  PQ_TRY(cloud_bbox(c, xyz, n, box, box + 3, &p->all_f32));
+  // grids over the cloud without its sparse tails; what is given up is what k_knn_brute can take
+  if (kn.robust_box && k <= 64) {
+    int64_t outside = 0;
+    PQ_TRY(robust_box(c, xyz, n, brute_max(n), box, &outside));
+    if (outside && kn.trace)
+      fprintf(stderr, "knn: grids over the box without its tails, at most %lld points outside\n", (long long)outside);
+  }
+  double ext = std::max(box[3] - box[0], std::max(box[4] - box[1], box[5] - box[2]));
+  if (!(ext > 0)) ext = 1.0;
+  const double target = std::max(2.0, double(k) / kn.occ_div);
+  double c1, per1, c2, per2, dim = 2.0, cell;
+  PQ_TRY(probe_occupancy(c, xyz, n, box, ext / 64.0, &c1, &per1));
+  if (per1 <= 1.5 * target) {
+    cell = c1 * (per1 < 0.5 * target ? 2.0 : 1.0);
+  } else {
+    PQ_TRY(probe_occupancy(c, xyz, n, box, c1 * 0.5, &c2, &per2));
+    if (c2 < c1 && per2 > 0) dim = std::log2(std::max(per1 / per2, 1.0001)) / std::log2(c1 / c2);
+    dim = std::min(3.0, std::max(1.0, dim));
+    cell = c2 * std::pow(target / per2, 1.0 / dim);
+  }
+  cell = std::max(cell, ext / 4096.0);
+  for (int it = 0; it < 2; ++it) {
+    PQ_TRY(build_grid(c, xyz, n, cell, kMaxCells, &p->g, box, p->all_f32));
+    if (it == 1) break;
+    int64_t occ = 0;
+    PQ_TRY(count_occupied(c, p->g, &occ));
+    const double per = double(n) / double(occ > 0 ? occ : 1);
+    if (per <= 2.5 * target && per >= 0.4 * target) break;
+    if (per < target && p->g.nx <= 3 && p->g.ny <= 3 && p->g.nz <= 3) break;  // cannot coarsen further
+    const double f = std::min(4.0, std::max(0.25, std::pow(target / per, 1.0 / dim)));
+    if (f < 1.0 && p->g.cell > cell * 1.0000001) break;  // grid already at its size cap
+    cell = p->g.cell * f;
+  }
+  return 0;
+}
+
+// A few isolated queries (`list`, original indices), one by one over the whole cloud.
+static int brute_rest(Ctx* c, const double* xyz, int n, int k, int exclude_self, const int32_t* list, int n_query,
+                      int32_t* idx, double* d2) {
+  ProfScope pb(c, "knn_brute");
+  const int tiles = ceil_div(n_query, kBruteTile);
+  const int chunks = ceil_div(n, 64);
+  // ~16 waves per CU over all tiles; a slice is at least 32 chunks long
+  const int n_slices = std::max(1, std::min(std::min(256, ceil_div(chunks, 32)), ceil_div(c->cu_count * 16, tiles)));
+  double* part_d = nullptr;
+  int32_t* part_i = nullptr;
+  const size_t slots = size_t(tiles) * n_slices * kBruteTile * size_t(k);
+  PQ_TRY(c->arena.get(slots, &part_d));
+  PQ_TRY(c->arena.get(slots, &part_i));
+  hipLaunchKernelGGL(k_knn_brute, dim3(ceil_div(tiles * n_slices, 4)), dim3(256), 0, c->stream, n_query, list, xyz, n,
+                     k, exclude_self, n_slices, part_d, part_i);
+  hipLaunchKernelGGL(k_knn_brute_merge, dim3(ceil_div(n_query, 4)), dim3(256), 0, c->stream, n_query, list, n, k,
+                     n_slices, static_cast<const double*>(part_d), static_cast<const int32_t*>(part_i), idx, d2);
+  PQ_HIP(hipGetLastError());
+  return 0;
+}
+
+// p->g = the grid of the next level, cells 4x larger; *made = how (trace only). pos_of (or null: the
+// next level serves every point again) = the new grid's order, inverted.
+static int next_grid(Ctx* c, const double* xyz, int64_t n, KnnPlan* p, const char** made, int32_t* pos_of) {
+  ProfScope ps(c, "knn_bin");
+  // Deriving the coarse grid from the fine one reads the fine grid's whole cell array (95 M
+  // cells for a million points at k = 20: 0.22 ms); binning the points again at the coarse edge
+  // touches 1.5 M cells (0.12 ms). The order inside a cell does not matter to a search. Small
+  // fine grids (the later levels) keep the pyramid: no atomics, a few microseconds.
+  DevGrid coarse;
+  if (p->g.ncell > (int64_t(1) << 22)) {
+    PQ_TRY(build_grid(c, xyz, n, p->g.cell * 4.0, kMaxCells, &coarse, p->box, p->all_f32));
+    *made = " binned again";
+  } else {
+    PQ_TRY(coarsen_grid(c, p->g, n, 4, &coarse));
+    *made = " coarsened";
+  }
+  p->g = coarse;
+  if (pos_of) {
+    hipLaunchKernelGGL(k_invert_order, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, int(n), p->g.order, pos_of);
+    PQ_HIP(hipGetLastError());
+  }
   return 0;
 }
 
@@ -790,193 +995,64 @@ int knn_device(Ctx* c, const double* xyz, int64_t n, int32_t k, int32_t exclude_
   if (k <= 0 || k > kKnnMaxK) return fail(PYQSM_ERANGE, "k must be in [1, %d]", kKnnMaxK);
   if (n == 0) return 0;
   const int N = int(n);
-  // ---- level-0 cell edge: aim at ~k/3 points per occupied cell -----------
-  // Two count-only probes on coarse grids give the local density and how it
-  // scales with the edge (exponent ~2 for surfaces, ~3 for volumes); the edge
-  // for the target occupancy follows by extrapolation, and one corrective
-  // rebuild is allowed if the sorted grid misses the target by more than 2.5x.
-  DevGrid g;
-  const int64_t max_cells = int64_t(1) << 28;
-  double box[6];
-  bool all_f32 = false;  // every coordinate fp32-representable: the grids keep 16-byte fp32 records
-  {
-    ProfScope ps(c, "knn_bin");
-    PQ_TRY(cloud_bbox(c, xyz, n, box, box + 3, &all_f32));
-    // grids over the cloud without its sparse tails; what is given up is what k_knn_brute can take
-    const char* rbe = getenv("PYQSM_KNN_ROBUST_BOX");  // "0": grids over the full box
-    const bool robust = !(rbe && rbe[0] == '0');
-    if (robust && k <= 64) {
-      int64_t outside = 0;
-      PQ_TRY(robust_box(c, xyz, n, brute_max(n), box, &outside));
-      if (outside && getenv("PYQSM_KNN_TRACE"))
-        fprintf(stderr, "knn: grids over the box without its tails, at most %lld points outside\n", (long long)outside);
-    }
-    double ext = std::max(box[3] - box[0], std::max(box[4] - box[1], box[5] - box[2]));
-    if (!(ext > 0)) ext = 1.0;
-    static const double occ_div = [] {  // PYQSM_KNN_OCC: points per occupied cell = k / this
-      const char* e = getenv("PYQSM_KNN_OCC");
-      const double v = e ? atof(e) : 3.0;
-      return v > 0.25 && v < 64.0 ? v : 3.0;
-    }();
-    const double target = std::max(2.0, double(k) / occ_div);
-    double c1, per1, c2, per2, dim = 2.0, cell;
-    PQ_TRY(probe_occupancy(c, xyz, n, box, ext / 64.0, &c1, &per1));
-    if (per1 <= 1.5 * target) {
-      cell = c1 * (per1 < 0.5 * target ? 2.0 : 1.0);
-    } else {
-      PQ_TRY(probe_occupancy(c, xyz, n, box, c1 * 0.5, &c2, &per2));
-      if (c2 < c1 && per2 > 0) dim = std::log2(std::max(per1 / per2, 1.0001)) / std::log2(c1 / c2);
-      dim = std::min(3.0, std::max(1.0, dim));
-      cell = c2 * std::pow(target / per2, 1.0 / dim);
-    }
-    cell = std::max(cell, ext / 4096.0);
-    for (int it = 0; it < 2; ++it) {
-      PQ_TRY(build_grid(c, xyz, n, cell, max_cells, &g, box, all_f32));
-      if (it == 1) break;
-      int64_t occ = 0;
-      PQ_TRY(count_occupied(c, g, &occ));
-      const double per = double(n) / double(occ > 0 ? occ : 1);
-      if (per <= 2.5 * target && per >= 0.4 * target) break;
-      if (per < target && g.nx <= 3 && g.ny <= 3 && g.nz <= 3) break;  // cannot coarsen further
-      const double f = std::min(4.0, std::max(0.25, std::pow(target / per, 1.0 / dim)));
-      if (f < 1.0 && g.cell > cell * 1.0000001) break;  // grid already at its size cap
-      cell = g.cell * f;
-    }
-  }
-  int32_t *pos_of = nullptr, *fail_a, *fail_b, *fail_count;
+  const KnnKnobs kn = read_knobs();
+  KnnPlan plan;
+  PQ_TRY(plan_level0_grid(c, xyz, n, k, kn, &plan));
+  const DevGrid& g = plan.g;
+  int32_t *pos_of = nullptr, *fail_a, *fail_b, *fail_count, *tie_list, *tie_count;
   PQ_TRY(c->arena.get(size_t(n), &fail_a));
   PQ_TRY(c->arena.get(size_t(n), &fail_b));
   PQ_TRY(c->arena.get(1, &fail_count));
-  int32_t *tie_list, *tie_count;
   PQ_TRY(c->arena.get(size_t(n), &tie_list));
   PQ_TRY(c->arena.get(1, &tie_count));
   PQ_HIP(hipMemsetAsync(tie_count, 0, 4, c->stream));
   int n_query = N;
-  const int32_t* list = nullptr;
-  bool retry_binned = false;  // how this level's grid was made (trace only)
-  bool level0_again = false;  // level 0 has been run a second time (see below)
-  for (int level = 0;; ++level) {
-    static const int wide = [] { const char* e = getenv("PYQSM_KNN_WIDE"); return e ? atoi(e) : kWideRing; }();
-    const int ring = level >= 1 && k <= 64 ? wide : kMaxRing;
+  const int32_t* list = nullptr;  // the queries of a retry level (original indices); null: every point
+  const char* made = "";
+  bool first_pass_again = false;  // level 0 has been run a second time (see below)
+  for (int level = 0;;) {
+    const int ring = level >= 1 && k <= 64 ? kn.wide : kMaxRing;
     const int last = (g.nx - 2 <= ring && g.ny - 2 <= ring && g.nz - 2 <= ring) ? 1 : 0;
+    int32_t* open = (level & 1) ? fail_b : fail_a;  // the queries this level leaves open
     PQ_HIP(hipMemsetAsync(fail_count, 0, 4, c->stream));
-    if (getenv("PYQSM_KNN_TRACE")) {  // printed for the last level too (the lines below are not)
-      const bool reg = level == 0 && k <= 32, wave = level > 0 && k <= 64;
-      char kern[32];
-      if (reg)
-        snprintf(kern, sizeof kern, "k_knn_reg<%d,%d,%s>", (k + 3) / 4 * 4, knn_buffer_slots() == 0 ? 0 : 4,
-                 knn_buffer_slots() != 0 && knn_strict() ? "true" : "false");
-      else if (wave)
-        snprintf(kern, sizeof kern, "k_knn_wave");
-      else
-        snprintf(kern, sizeof kern, "k_knn<%d>", k <= 48 ? 256 : k <= 96 ? 128 : 64);
-      fprintf(stderr, "knn level %d: grid %d x %d x %d of cell %.4g%s, %s, %s, %d queries%s\n", level, g.nx, g.ny,
-              g.nz, g.cell, level == 0 && !level0_again ? "" : retry_binned ? " binned again" : " coarsened",
-              g.p4 ? "fp32 records" : "fp64 arrays", kern, n_query, last ? ", last level" : "");
-    }
-    {
-      ProfScope ps(c, level == 0 ? "knn_search" : "knn_retry");
-      int32_t* fl = (level & 1) ? fail_b : fail_a;
-      if (level == 0 && k <= 32) {
-        // list length = k rounded up to a multiple of 4: every slot is ~11 instructions per
-        // insertion, and slots beyond k loosen the acceptance test
-        switch ((k + 3) / 4) {
-          case 1: PQ_TRY(launch_knn_reg<4>(c, N, g, k, exclude_self, last, idx, d2, fl, fail_count, tie_list, tie_count)); break;
-          case 2: PQ_TRY(launch_knn_reg<8>(c, N, g, k, exclude_self, last, idx, d2, fl, fail_count, tie_list, tie_count)); break;
-          case 3: PQ_TRY(launch_knn_reg<12>(c, N, g, k, exclude_self, last, idx, d2, fl, fail_count, tie_list, tie_count)); break;
-          case 4: PQ_TRY(launch_knn_reg<16>(c, N, g, k, exclude_self, last, idx, d2, fl, fail_count, tie_list, tie_count)); break;
-          case 5: PQ_TRY(launch_knn_reg<20>(c, N, g, k, exclude_self, last, idx, d2, fl, fail_count, tie_list, tie_count)); break;
-          case 6: PQ_TRY(launch_knn_reg<24>(c, N, g, k, exclude_self, last, idx, d2, fl, fail_count, tie_list, tie_count)); break;
-          case 7: PQ_TRY(launch_knn_reg<28>(c, N, g, k, exclude_self, last, idx, d2, fl, fail_count, tie_list, tie_count)); break;
-          default: PQ_TRY(launch_knn_reg<32>(c, N, g, k, exclude_self, last, idx, d2, fl, fail_count, tie_list, tie_count)); break;
-        }
-      } else if (level > 0 && k <= 64) {
-        KnnGrid kg{g.nx, g.ny, g.nz, g.cell, g.minx, g.miny, g.minz};
-        // (one or two waves per block instead of four: no difference — the launch lasts as long as its
-        // longest waves, 0.34 ms for the forest's 9 864 outliers)
-        on_coords(g, [&](auto co) {
-          hipLaunchKernelGGL(k_knn_wave<decltype(co)>, dim3(ceil_div(n_query, 4)), dim3(256), 0, c->stream, n_query,
-                             static_cast<const int32_t*>(nullptr), 0, list, pos_of, kg, g.start, g.order, g.cell_of, co,
-                             k, exclude_self, N, last, ring, idx, d2, fl, fail_count);
-        });
-        PQ_HIP(hipGetLastError());
-      } else if (k <= 48)
-        PQ_TRY(launch_knn<256>(c, n_query, list, pos_of, g, k, exclude_self, N, last, idx, d2, fl,
-                               fail_count));
-      else if (k <= 96)
-        PQ_TRY(launch_knn<128>(c, n_query, list, pos_of, g, k, exclude_self, N, last, idx, d2, fl,
-                               fail_count));
-      else
-        PQ_TRY(launch_knn<64>(c, n_query, list, pos_of, g, k, exclude_self, N, last, idx, d2, fl,
-                              fail_count));
-    }
+    PQ_TRY(search_level(c, kn, level, g, made, knn_args(g, k, exclude_self, N, last, idx, d2, open, fail_count),
+                        n_query, list, pos_of, ring, tie_list, tie_count));
     if (last) break;
     int32_t nf = 0;
     PQ_TRY(fetch(c, &nf, fail_count));
-    if (level == 0 && getenv("PYQSM_KNN_TRACE")) {
-      int32_t nt = 0;
-      PQ_HIP(hipMemcpy(&nt, tie_count, 4, hipMemcpyDeviceToHost));
-      fprintf(stderr, "knn level 0: %d queries searched again for a tie at the k-th place\n", nt);
+    if (kn.trace) {
+      if (level == 0) {
+        int32_t nt = 0;
+        PQ_HIP(hipMemcpy(&nt, tie_count, 4, hipMemcpyDeviceToHost));
+        fprintf(stderr, "knn level 0: %d queries searched again for a tie at the k-th place\n", nt);
+      }
+      fprintf(stderr, "knn level %d: %d of %d queries stay open (cell %.4g)\n", level, nf, n_query, g.cell);
     }
-    if (getenv("PYQSM_KNN_TRACE")) fprintf(stderr, "knn level %d: %d of %d queries stay open (cell %.4g)\n", level, nf, n_query, g.cell);
     if (nf == 0) break;
-    if (level >= 1 && nf <= 2 * brute_max(n) && k <= 64) {  // a few isolated queries: one by one
-      ProfScope pb(c, "knn_brute");
-      const int32_t* ql = (level & 1) ? fail_b : fail_a;
-      const int tiles = ceil_div(nf, kBruteTile);
-      const int chunks = ceil_div(N, 64);
-      // ~16 waves per CU over all tiles; a slice is at least 32 chunks long
-      const int n_slices = std::max(1, std::min(std::min(256, ceil_div(chunks, 32)), ceil_div(c->cu_count * 16, tiles)));
-      double* part_d = nullptr;
-      int32_t* part_i = nullptr;
-      const size_t slots = size_t(tiles) * n_slices * kBruteTile * size_t(k);
-      PQ_TRY(c->arena.get(slots, &part_d));
-      PQ_TRY(c->arena.get(slots, &part_i));
-      hipLaunchKernelGGL(k_knn_brute, dim3(ceil_div(tiles * n_slices, 4)), dim3(256), 0, c->stream, nf, ql, xyz, N,
-                         k, exclude_self, n_slices, part_d, part_i);
-      hipLaunchKernelGGL(k_knn_brute_merge, dim3(ceil_div(nf, 4)), dim3(256), 0, c->stream, nf, ql, N, k, n_slices,
-                         static_cast<const double*>(part_d), static_cast<const int32_t*>(part_i), idx, d2);
-      PQ_HIP(hipGetLastError());
-      if (getenv("PYQSM_KNN_TRACE")) fprintf(stderr, "knn: %d isolated queries searched over the whole cloud\n", nf);
+    if (level >= 1 && nf <= 2 * brute_max(n) && k <= 64) {
+      PQ_TRY(brute_rest(c, xyz, N, k, exclude_self, open, nf, idx, d2));
+      if (kn.trace) fprintf(stderr, "knn: %d isolated queries searched over the whole cloud\n", nf);
       break;
     }
-    // retry the stragglers on a 4x coarser grid
-    ProfScope ps(c, "knn_bin");
     // More than half of ALL queries open after the register kernel's three rings: the occupancy the
     // cell edge was planned for came from coincident points (a contracted cloud, a lattice with several
     // points per node: 5.5 per node meet k / 3 at any edge below the lattice step), so the edge says
     // nothing about the spacing, level 0 answered (nearly) nobody, and a WAVE per query would now serve
     // the whole cloud. Level 0 once more instead, a lane per query with its tie passes, on the
     // coarser grid; what is still open after that is retried as usual.
-    const bool again = level == 0 && k <= 32 && !level0_again && nf > N / 2;
-    if (!again) {
-      list = (level & 1) ? fail_b : fail_a;
-      n_query = nf;
-    }
-    {
-      // Deriving the coarse grid from the fine one reads the fine grid's whole cell array (95 M
-      // cells for a million points at k = 20: 0.22 ms); binning the points again at the coarse edge
-      // touches 1.5 M cells (0.12 ms). The order inside a cell does not matter to a search. Small
-      // fine grids (the later levels) keep the pyramid: no atomics, a few microseconds.
-      DevGrid coarse;
-      retry_binned = g.ncell > (int64_t(1) << 22);
-      if (retry_binned)
-        PQ_TRY(build_grid(c, xyz, n, g.cell * 4.0, max_cells, &coarse, box, all_f32));
-      else
-        PQ_TRY(coarsen_grid(c, g, n, 4, &coarse));
-      g = coarse;
-    }
-    if (again) {
-      if (getenv("PYQSM_KNN_TRACE")) fprintf(stderr, "knn: level 0 once more for every query, on the coarser grid\n");
-      level0_again = true;
+    if (level == 0 && k <= 32 && !first_pass_again && nf > N / 2) {
+      PQ_TRY(next_grid(c, xyz, n, &plan, &made, nullptr));
+      if (kn.trace) fprintf(stderr, "knn: level 0 once more for every query, on the coarser grid\n");
+      first_pass_again = true;
       PQ_HIP(hipMemsetAsync(tie_count, 0, 4, c->stream));
-      --level;
       continue;
     }
+    // retry the stragglers on a 4x coarser grid
     if (!pos_of) PQ_TRY(c->arena.get(size_t(n), &pos_of));
-    hipLaunchKernelGGL(k_invert_order, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, N, g.order,
-                       pos_of);
-    PQ_HIP(hipGetLastError());
+    PQ_TRY(next_grid(c, xyz, n, &plan, &made, pos_of));
+    list = open;
+    n_query = nf;
+    ++level;
   }
   return 0;
 }

@@ -29,8 +29,8 @@ TIES = re.compile(r"knn level 0: (\d+) queries searched again for a tie at the k
 
 
 def kernel_of(k, level=0, variant="4,true"):
-    """The kernel knn_device picks (knn.hip: the dispatch in its level loop; launch_knn_reg for the
-    buffer slots and the strict first pass of the register kernel)."""
+    """The kernel knn_device picks (knn.hip: pick_kernel, buffer slots and the strict first pass of the
+    register kernel included; kernel_name prints it)."""
     if level == 0 and k <= 32:
         return f"k_knn_reg<{(k + 3) // 4 * 4},{variant}>"
     if level > 0 and k <= 64:
