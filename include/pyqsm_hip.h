@@ -621,6 +621,55 @@ int pyqsm_mesh_self_intersections(const int32_t* ijk, int64_t n_verts, const int
                                   int32_t flags, int64_t max_tests, int64_t* n_pairs, int32_t** pairs,
                                   uint8_t* tri_hit, int64_t* stats, int32_t device);
 
+/* ---- mesh hole filling: boundary loops, minimum-area patches ------------------- */
+/*
+ * What pyQSM's geometry/surf_recon.py meshfix asks of pymeshfix's fill_small_boundaries, by a contract of
+ * its own with a fixed output order; not MeshFix's triangulation. Everything is by
+ * vertex INDEX, nothing is welded, no vertex is added. tris, n_tris, n_verts and their refusals as in
+ * pyqsm_mesh_topology; n_tris == 0 launches nothing; a mesh without a boundary has no loops.
+ *
+ * Half-edge h = 3 t + k runs from corner k of triangle t to corner (k + 1) % 3; it is a boundary half-edge
+ * when its undirected edge has exactly one triangle. succ(h), h = (a -> b): g = next(h) in h's triangle;
+ * while g is not a boundary half-edge, g = next(twin(g)), which leaves b again; the first boundary g. The
+ * walk stops where g's edge has more than two triangles or two that run the same way (no twin): h then
+ * lies on an OPEN CHAIN, as does every half-edge that leads to it or is led to by nothing. The walk is
+ * capped at the number of triangle corners at b. The cycles of succ are the LOOPS.
+ *
+ * A loop of length L is listed v_0 .. v_{L-1} in the fill direction: (v_{m+1} -> v_m) is a boundary
+ * half-edge of the mesh, so a new triangle traverses each boundary edge against the triangle that is
+ * there. v_0 is the loop's smallest vertex index; where it occurs more than once, the occurrence whose
+ * half-edge leaving it has the smaller h. Loops are numbered ascending by (v_0, that h).
+ *   *loop_ptr i32 [n_loops + 1], *loop_verts i32 [loop_ptr[n_loops]]
+ *   *loop_flags u8 [n_loops]: 1 some vertex occurs more than once; 2 L > max_edges; 0: the loop is filled.
+ *     max_edges <= 0: PYQSM_FILL_MAX_LOOP; above it: PYQSM_EINVAL.
+ *
+ * The patch of a filled loop, p_m = verts[v_m] in fp64: W(i, i+1) = 0; for d = 2 .. L-1, i = 0 .. L-1-d,
+ * k = i + d, j ascending in (i, k): w = (W(i,j) + W(j,k)) + A(i,j,k); a later j replaces an earlier one
+ * only when strictly smaller. A = 0.5 * sqrt((cx*cx + cy*cy) + cz*cz), c = (p_j - p_i) x (p_k - p_i),
+ * every component a*b - c*d without fused multiply-adds: the area of pyqsm_mesh_topology. Rows in
+ * pre-order of the split tree: emit(i,k) writes (v_i, v_j, v_k), j = split(i,k), then emit(i,j), then
+ * emit(j,k). L - 2 rows per filled loop, the loops ascending.
+ *   *loop_area f64 [n_loops]: W(0, L-1); 0 where not filled
+ *   *new_tris i32 [*n_new,3], *new_loop i32 [*n_new]: the rows and the loop each belongs to
+ * Loops of at most PYQSM_FILL_WAVE_MAX edges are patched by one wave each, longer ones by one block each;
+ * the result does not depend on the class.
+ *
+ * stats i64 [8]: boundary half-edges, loops, loops filled, loops with a repeated vertex, loops too long,
+ *   half-edges on open chains, new rows of area exactly 0.0, diagonals of the patches that are already
+ *   an edge of the mesh. Neither of the last two changes the result: the caller re-runs the checks.
+ *   pyqsm_mesh_boundary_loops fills the first two and the sixth.
+ * Buffers are allocated by the library, released with pyqsm_free and NULL when empty. The same bytes on
+ * every run.
+ */
+#define PYQSM_FILL_MAX_LOOP 128
+#define PYQSM_FILL_WAVE_MAX 32
+int pyqsm_mesh_boundary_loops(const int32_t* tris, int64_t n_tris, int64_t n_verts, int64_t* n_loops,
+                              int32_t** loop_ptr, int32_t** loop_verts, int64_t* stats, int32_t device);
+int pyqsm_mesh_fill_holes(const int32_t* tris, int64_t n_tris, int64_t n_verts, const double* verts, int32_t max_edges,
+                          int64_t* n_loops, int32_t** loop_ptr, int32_t** loop_verts, uint8_t** loop_flags,
+                          double** loop_area, int64_t* n_new, int32_t** new_tris, int32_t** new_loop, int64_t* stats,
+                          int32_t device);
+
 /* ---- surface reconstruction: exact ball pivoting of lattice points ------------- */
 /*
  * The triangles a ball of radius rho can rest on from the normals' side (the alpha-exposed facets of

@@ -110,6 +110,11 @@ SIGNATURES = {
                                            i32]),
     "pyqsm_mesh_self_intersections": (ctypes.c_int, [vp, i64, vp, i64, i32, i64, ctypes.POINTER(i64),
                                                      ctypes.POINTER(vp), vp, vp, i32]),
+    "pyqsm_mesh_boundary_loops": (ctypes.c_int, [vp, i64, i64, ctypes.POINTER(i64), ctypes.POINTER(vp),
+                                                 ctypes.POINTER(vp), vp, i32]),
+    "pyqsm_mesh_fill_holes": (ctypes.c_int, [vp, i64, i64, vp, i32, ctypes.POINTER(i64), ctypes.POINTER(vp),
+                                             ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
+                                             ctypes.POINTER(i64), ctypes.POINTER(vp), ctypes.POINTER(vp), vp, i32]),
     "pyqsm_ball_pivot": (ctypes.c_int, [vp, vp, i64, vp, i32, i64, ctypes.POINTER(i64), ctypes.POINTER(vp), vp,
                                         i32]),
     "pyqsm_fps": (ctypes.c_int, [vp, i64, i64, i64, vp, i32]),

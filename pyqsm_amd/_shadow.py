@@ -84,7 +84,7 @@ HOT_FUNCTIONS = {
     # module (flat name) -> the names this package replaces there
     "math_utils.fit": ("cluster_DBSCAN", "fit_shape_RANSAC", "z_align_and_fit", "choose_and_cluster"),
     "geometry.point_cloud_processing": ("cluster_plus", "cluster_and_get_largest", "get_ball_mesh"),
-    "geometry.surf_recon": ("pivot_ball_mesh",),
+    "geometry.surf_recon": ("pivot_ball_mesh", "meshfix"),
     "geometry.skeletonize": ("extract_skeleton", "least_squares_sparse", "extract_topology",
                              "extract_skeletal_graph", "simplify_graph", "skeleton_to_QSM",
                              # array-level additions without a counterpart in the reference (install() skips them)

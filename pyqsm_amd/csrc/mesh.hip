@@ -13,6 +13,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "mesh_halfedge.hpp"
 #include "unionfind.hpp"
 
 namespace pyqsm {
@@ -28,51 +29,7 @@ static_assert(kRows == 256, "one thread per row triangle of a 256-thread block")
 
 // ---------------------------------------------------------------- topology
 
-// Half-edge h = 3 t + k runs from corner k of triangle t to corner (k + 1) % 3.
-__device__ __forceinline__ void half_edge(const int32_t* __restrict__ tris, int h, int& u, int& w) {
-  const int t = h / 3, k = h - 3 * t;
-  u = tris[h];
-  w = tris[3 * t + (k == 2 ? 0 : k + 1)];
-}
-
-__global__ __launch_bounds__(256) void k_mesh_he_keys(int n, const int32_t* __restrict__ tris,
-                                                      const int32_t* __restrict__ perm /*may be null*/, int want_min,
-                                                      uint32_t* __restrict__ keys, int32_t* __restrict__ vals) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const int h = perm ? perm[i] : i;
-  int u, w;
-  half_edge(tris, h, u, w);
-  keys[i] = uint32_t(want_min ? min(u, w) : max(u, w));
-  vals[i] = h;
-}
-
-// flags [n + 1]: 1 where a run of equal (min, max) begins, flags[n] = 0
-__global__ __launch_bounds__(256) void k_mesh_he_heads(int n, const int32_t* __restrict__ tris,
-                                                       const int32_t* __restrict__ hs, int32_t* __restrict__ flags) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i > n) return;
-  int f = 0;
-  if (i < n) {
-    f = 1;
-    if (i > 0) {
-      int u0, w0, u1, w1;
-      half_edge(tris, hs[i - 1], u0, w0);
-      half_edge(tris, hs[i], u1, w1);
-      f = (min(u0, w0) != min(u1, w1)) || (max(u0, w0) != max(u1, w1));
-    }
-  }
-  flags[i] = f;
-}
-
-// x: the exclusive scan of the head flags. first [E + 1]: where each run begins, first[E] = n.
-__global__ __launch_bounds__(256) void k_mesh_he_first(int n, const int32_t* __restrict__ x,
-                                                       int32_t* __restrict__ first) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  if (x[i + 1] != x[i]) first[x[i]] = i;
-  if (i == 0) first[x[n]] = n;
-}
+// The half-edge convention, the sort and the runs: mesh_halfedge.hpp, shared with holes.hip.
 
 // One thread per sorted half-edge. The head of a run writes the edge's row; every other half-edge
 // of the run is linked to the head: their triangles, their corners at both end vertices and, on an
@@ -471,15 +428,14 @@ int pyqsm_mesh_topology(const int32_t* tris, int64_t n_tris, int64_t n_verts, co
   Ctx* c = call.c;
   if (!c) return PYQSM_ENODEV;
   const int nt = int(n_tris), nh = 3 * nt, nv = int(n_verts);
-  int32_t *d_tris, *d_vals, *d_flags, *d_par_tri, *d_par_corner, *d_par_cover, *d_vroots, *d_cl;
+  int32_t *d_tris, *d_vals, *d_par_tri, *d_par_corner, *d_par_cover, *d_vroots, *d_cl;
   uint32_t* d_keys;
   double* d_verts = nullptr;
   unsigned long long* d_counters;
   uint8_t* d_vflags;
   PQ_TRY(c->arena.get(size_t(nh), &d_tris));
-  PQ_TRY(c->arena.get(size_t(nh), &d_keys));
-  PQ_TRY(c->arena.get(size_t(nh), &d_vals));
-  PQ_TRY(c->arena.get(size_t(nh) + 1, &d_flags));
+  PQ_TRY(c->arena.get(size_t(nt), &d_keys));
+  PQ_TRY(c->arena.get(size_t(nt), &d_vals));
   PQ_TRY(c->arena.get(size_t(nt), &d_par_tri));
   PQ_TRY(c->arena.get(size_t(nh), &d_par_corner));
   PQ_TRY(c->arena.get(size_t(nt) * 2, &d_par_cover));
@@ -493,41 +449,25 @@ int pyqsm_mesh_topology(const int32_t* tris, int64_t n_tris, int64_t n_verts, co
   PQ_HIP(hipMemsetAsync(d_counters, 0, 64, c->stream));
   PQ_HIP(hipMemsetAsync(d_vroots, 0, size_t(nv) * 4, c->stream));
 
-  // the half-edges sorted by (min, max): a stable pass by max, then one by min. Inside a run the
+  // the half-edges sorted by (min, max) and their runs (mesh_halfedge.hpp). Inside a run the
   // half-edges ascend, so its head is the lowest one.
-  const int vbits = bit_length(uint64_t(nv));
   int32_t e_total = 0;
-  int32_t* d_hs = nullptr;
+  int32_t *d_hs = nullptr, *d_flags = nullptr, *d_first = nullptr;
   {
     ProfScope ps(c, "mesh_edge_sort");
-    PQ_LAUNCH(k_mesh_he_keys, ceil_div(nh, 256), nh, static_cast<const int32_t*>(d_tris),
-              static_cast<const int32_t*>(nullptr), 0, d_keys, d_vals);
-    PQ_TRY(stable_sort_pairs_u32(c, &d_keys, &d_vals, nh, vbits));
-    uint32_t* d_k2;
-    int32_t* d_v2;
-    PQ_TRY(c->arena.get(size_t(nh), &d_k2));
-    PQ_TRY(c->arena.get(size_t(nh), &d_v2));
-    PQ_LAUNCH(k_mesh_he_keys, ceil_div(nh, 256), nh, static_cast<const int32_t*>(d_tris),
-              static_cast<const int32_t*>(d_vals), 1, d_k2, d_v2);
-    PQ_TRY(stable_sort_pairs_u32(c, &d_k2, &d_v2, nh, vbits));
-    d_hs = d_v2;
-    PQ_LAUNCH(k_mesh_he_heads, ceil_div(nh + 1, 256), nh, static_cast<const int32_t*>(d_tris),
-              static_cast<const int32_t*>(d_hs), d_flags);
-    PQ_TRY(exclusive_scan_i32(c, d_flags, int64_t(nh) + 1));
+    PQ_TRY(mesh_half_edge_runs(c, d_tris, nt, nv, &d_hs, &d_flags, &d_first));
     PQ_TRY(fetch(c, &e_total, d_flags + nh));  // E sizes the edge table
   }
   if (e_total < 1 || e_total > nh) return fail(PYQSM_EHIP, "pyqsm_mesh_topology: %d edges counted", e_total);
   const int ne = e_total;
-  int32_t *d_first, *d_edges, *d_ecount;
+  int32_t *d_edges, *d_ecount;
   uint8_t* d_eflags;
-  PQ_TRY(c->arena.get(size_t(ne) + 1, &d_first));
   PQ_TRY(c->arena.get(size_t(ne) * 2, &d_edges));
   PQ_TRY(c->arena.get(size_t(ne), &d_ecount));
   PQ_TRY(c->arena.get(size_t(ne), &d_eflags));
   int32_t n_clusters = 0;
   {
     ProfScope ps(c, "mesh_union");
-    PQ_LAUNCH(k_mesh_he_first, ceil_div(nh, 256), nh, static_cast<const int32_t*>(d_flags), d_first);
     PQ_LAUNCH(k_uf_init, ceil_div(nt, 256), nt, d_par_tri);
     PQ_LAUNCH(k_uf_init, ceil_div(nh, 256), nh, d_par_corner);
     PQ_LAUNCH(k_uf_init, ceil_div(2 * nt, 256), 2 * nt, d_par_cover);
@@ -560,7 +500,6 @@ int pyqsm_mesh_topology(const int32_t* tris, int64_t n_tris, int64_t n_verts, co
   PQ_TRY(c->arena.get(size_t(ncl), &d_carea));
   {
     ProfScope ps(c, "mesh_clusters");
-    // d_keys / d_vals may have been swapped with the sort's own buffers: both are nh >= nt long
     PQ_LAUNCH(k_mesh_tri_cluster, ceil_div(nt, 256), nt, static_cast<const int32_t*>(d_par_tri),
               static_cast<const int32_t*>(d_flags), d_cl, d_keys, d_vals);
     PQ_TRY(stable_sort_pairs_u32(c, &d_keys, &d_vals, nt, bit_length(uint64_t(ncl))));

@@ -492,6 +492,29 @@ class TriangleMesh:
         return (s["over_two_edges"] == 0 and s["boundary_edges"] == 0 and s["non_manifold_vertices"] == 0
                 and not self.is_self_intersecting(max_tests=max_tests, device=device))
 
+    # ---- hole filling on the GPU (hip.mesh_boundary_loops / hip.mesh_fill_holes)
+
+    def get_boundary_loops(self, device: int = 0):
+        """The boundary loops as a list of int32 vertex arrays, each from its smallest vertex in the
+        direction a patch would run, ascending by that vertex (``hip.mesh_boundary_loops``)."""
+        res = _hip().mesh_boundary_loops(self.triangles, len(self.vertices), device=device)
+        return [res.loop(i) for i in range(len(res.ptr) - 1)]
+
+    def fill_holes(self, max_edges=None, device: int = 0) -> "TriangleMesh":
+        """A new mesh with every boundary loop of at most ``max_edges`` edges (None: 128, the kernel's
+        bound) closed by its minimum-area triangulation; the new rows follow the old ones, no vertex
+        is added. Not Open3D's ``fill_holes`` nor MeshFix's patches: a contract of its own (DESIGN.md
+        §26). The result carries ``last_fill`` (``hip.HoleFill``: loops, flags, areas, statistics);
+        ``vertex_normals`` and ``vertex_colors`` carry over. Loops that repeat a vertex stay open."""
+        res = _hip().mesh_fill_holes(self.triangles, np.asarray(self.vertices, dtype=np.float64), max_edges,
+                                     device=device)
+        out = TriangleMesh(self.vertices, np.concatenate([self.triangles, res.new_tris.astype(np.int64)]))
+        for name in ("vertex_normals", "vertex_colors"):
+            if getattr(self, name, None) is not None:
+                setattr(out, name, getattr(self, name))
+        out.last_fill = res
+        return out
+
     def remove_triangles_by_mask(self, mask) -> "TriangleMesh":
         """Open3D's ``remove_triangles_by_mask``: drops the triangles where ``mask`` is true, in
         place; the vertices stay. Host NumPy."""

@@ -13,6 +13,9 @@ Differences from Open3D, all deliberate:
 * Self-intersection is decided exactly, on the mesh SNAPPED to an integer lattice
   (:func:`quantize_mesh`); Open3D tests in floating point.
 * A mesh with an edge of more than two triangles is reported as not orientable.
+* Holes are closed by :func:`fill_small_boundaries` (``hip.mesh_fill_holes``): minimum-area
+  patches over the loops' own vertices in a fixed order, not MeshFix's or Open3D's triangulation; no
+  refinement, no welding, no joining of components, and a patch is not tested against the mesh.
 * ``map_density``, ``subdivide_mesh`` and all drawing are out of scope: nothing is plotted here, and
   with pyQSM behind this package on ``sys.path`` those names still resolve to pyQSM's own file.
 """
@@ -140,6 +143,16 @@ def get_surface_clusters(mesh, top_n_clusters=10, min_cluster_area=None, max_clu
     clusters, n, area = m.cluster_connected_triangles(device=device)
     keep = surface_cluster_mask(n, area, top_n_clusters, min_cluster_area, max_cluster_area)[clusters]
     return (TriangleMesh(m.vertices, m.triangles[keep]), TriangleMesh(m.vertices, m.triangles[~keep]), clusters)
+
+
+def fill_small_boundaries(mesh, nbe=0, device: int = 0):
+    """pymeshfix's ``fill_small_boundaries`` by this package's contract: closes every
+    boundary loop of at most ``nbe`` edges (0: all, which here means up to ``hip.FILL_MAX_LOOP`` = 128)
+    with its minimum-area triangulation, without new vertices or refinement. Returns ``(mesh,
+    n_filled)``: a new mesh (``TriangleMesh.fill_holes``) and the number of loops closed. A larger
+    ``nbe`` than 128 is refused."""
+    m = _as_mesh(mesh).fill_holes(max_edges=None if not nbe else int(nbe), device=device)
+    return m, m.last_fill.stats["loops_filled"]
 
 
 def cluster_and_remove_triangles(mesh, min_triangles=200, device: int = 0) -> TriangleMesh:

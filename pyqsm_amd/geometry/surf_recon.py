@@ -2,9 +2,10 @@
 distances, normals, their orientation and the ball-pivoted mesh all run on the GPU.
 
 The mesh follows this package's order-free contract: exact for the cloud snapped to a
-lattice, the same bits on every run, and not Open3D's triangle list. Nothing is drawn here; pyQSM's
-other reconstructions (``map_density``, the alpha shape of ``get_mesh``, ``meshfix``) are out of
-scope and, with pyQSM behind this package on ``sys.path``, still resolve to pyQSM's own file.
+lattice, the same bits on every run, and not Open3D's triangle list. ``meshfix`` closes its holes on the
+GPU too (minimum-area patches, not MeshFix's). Nothing is drawn here; pyQSM's other
+reconstructions (``map_density``, the alpha shape of ``get_mesh``) are out of scope and, with pyQSM
+behind this package on ``sys.path``, still resolve to pyQSM's own file.
 """
 from __future__ import annotations
 
@@ -46,3 +47,29 @@ def pivot_ball_mesh(pcd, radii_factors=[0.1, 0.2, 0.3, 0.4, 0.5, 0.7, 1, 1.2, 1.
     rec_mesh = TriangleMesh.create_from_point_cloud_ball_pivoting(pcd, radii, device=device)
     rec_mesh.compute_vertex_normals()
     return rec_mesh
+
+
+def meshfix(mesh, algo="pyt", nbe=0, device: int = 0):
+    """surf_recon.py:38-85: close the holes of a reconstructed mesh. pyQSM hands the mesh to pymeshfix
+    (``algo='pyt'``: ``fill_small_boundaries(nbe)``; ``'repair'``: ``MeshFix.repair``); here both run the
+    device fill of DESIGN.md §26 (``TriangleMesh.fill_holes``): every boundary loop of at most ``nbe``
+    edges (0: all, which means up to 128 here) gets its minimum-area triangulation over its own
+    vertices. ``'repair'`` first keeps only the largest triangle cluster, as MeshFix does (the first of
+    several equally large ones). Not MeshFix's triangulation or refinement; nothing is drawn, and no
+    pymeshfix, pyvista or Open3D is needed. Returns the new mesh, with ``last_fill``; re-check it with
+    ``mesh_processing.check_properties``."""
+    if algo not in ("pyt", "repair"):
+        raise ValueError(f"algo must be 'pyt' or 'repair', got {algo!r}")
+    if not isinstance(mesh, TriangleMesh):
+        mesh = TriangleMesh(np.asarray(mesh.vertices), np.asarray(mesh.triangles))
+    if algo == "repair" and len(mesh.triangles):
+        clusters, n, _ = mesh.cluster_connected_triangles(device=device)
+        kept = TriangleMesh(mesh.vertices, mesh.triangles[clusters == int(np.argmax(n))])
+        for name in ("vertex_normals", "vertex_colors"):
+            if getattr(mesh, name, None) is not None:
+                setattr(kept, name, getattr(mesh, name))
+        mesh = kept
+    log.info("Filling holes")
+    out = mesh.fill_holes(max_edges=None if not nbe else int(nbe), device=device)
+    log.info(f"{out.last_fill.stats}")
+    return out

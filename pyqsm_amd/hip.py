@@ -1395,6 +1395,88 @@ def mesh_self_intersections(ijk, tris, return_pairs: bool = True, max_tests: int
     return MeshIntersections(int(n_pairs.value), pairs, hit[:nt], stats)
 
 
+# ---------------------------------------------------------------- mesh hole filling
+
+FILL_MAX_LOOP = 128             # PYQSM_FILL_MAX_LOOP: the longest loop that is patched
+FILL_WAVE_MAX = 32              # PYQSM_FILL_WAVE_MAX: up to here one wave patches a loop, beyond it one block
+LOOP_REPEATED_VERTEX, LOOP_TOO_LONG = 1, 2
+_FILL_STATS = ("boundary_half_edges", "loops", "loops_filled", "loops_repeated_vertex", "loops_too_long",
+               "open_chain_half_edges", "zero_area_rows", "existing_diagonals")
+
+
+class BoundaryLoops(NamedTuple):
+    """Results of :func:`mesh_boundary_loops`."""
+    ptr: np.ndarray                 # int32 [n_loops + 1]
+    verts: np.ndarray               # int32 [ptr[-1]] the loops' vertices in the fill direction
+    stats: dict
+
+    def loop(self, i: int) -> np.ndarray:
+        return self.verts[self.ptr[i]:self.ptr[i + 1]]
+
+
+class HoleFill(NamedTuple):
+    """Results of :func:`mesh_fill_holes`."""
+    ptr: np.ndarray                 # int32 [n_loops + 1]
+    verts: np.ndarray               # int32 [ptr[-1]]
+    flags: np.ndarray               # uint8 [n_loops] LOOP_REPEATED_VERTEX | LOOP_TOO_LONG; 0: filled
+    area: np.ndarray                # float64 [n_loops] the patch's area; 0 where not filled
+    new_tris: np.ndarray            # int32 [n_new, 3]
+    new_loop: np.ndarray            # int32 [n_new] the loop each new row closes
+    stats: dict
+
+    def loop(self, i: int) -> np.ndarray:
+        return self.verts[self.ptr[i]:self.ptr[i + 1]]
+
+
+def _fill_take(lib, ptr, ctype, count, dtype):
+    return _adopt(lib, ptr, ctype, count, dtype) if ptr.value and count else np.zeros(0, dtype)
+
+
+def mesh_boundary_loops(tris, n_verts: int, device: int = 0) -> BoundaryLoops:
+    """The boundary loops of an indexed triangle mesh: the cycles of "next boundary
+    half-edge about the head vertex", each listed from its smallest vertex in the direction a patch
+    would run, the loops ascending by that vertex. Half-edges whose walk meets an edge of more than two
+    triangles or a same-direction pair lie on open chains and are only counted. Decided by vertex index
+    alone; the same bytes on every run."""
+    t = _tris_i32(tris)
+    st = np.zeros(8, np.int64)
+    n_loops, p_ptr, v_ptr = i64(0), vp(), vp()
+    lib = _lib.load()
+    check(lib.pyqsm_mesh_boundary_loops(_p(t), t.shape[0], int(n_verts), ctypes.byref(n_loops), ctypes.byref(p_ptr),
+                                        ctypes.byref(v_ptr), _p(st), int(device)))
+    nl = int(n_loops.value)
+    ptr = _fill_take(lib, p_ptr, i32, nl + 1, np.int32) if nl else np.zeros(1, np.int32)
+    verts = _fill_take(lib, v_ptr, i32, int(ptr[-1]), np.int32)
+    return BoundaryLoops(ptr, verts, dict(zip(_FILL_STATS, (int(x) for x in st))))
+
+
+def mesh_fill_holes(tris, verts, max_edges: int | None = None, device: int = 0) -> HoleFill:
+    """The boundary loops of :func:`mesh_boundary_loops` and, for every loop of at most ``max_edges``
+    edges (None: ``FILL_MAX_LOOP``; more is refused) that repeats no vertex, its minimum-area
+    triangulation in fp64: ``L - 2`` rows over the loop's own vertices, in pre-order of the split tree,
+    ties to the lowest apex. The rows traverse each boundary edge against the triangle that is there;
+    appended to ``tris`` they close the hole. Nothing is welded or refined, and whether a patch
+    intersects the mesh is for ``mesh_self_intersections`` to say."""
+    t = _tris_i32(tris)
+    v = np.ascontiguousarray(np.asarray(verts), dtype=np.float64)
+    if v.ndim != 2 or v.shape[1] != 3:
+        raise ValueError(f"expected vertices of shape [V,3], got {v.shape}")
+    st = np.zeros(8, np.int64)
+    n_loops, n_new = i64(0), i64(0)
+    p_ptr, v_ptr, f_ptr, a_ptr, t_ptr, l_ptr = vp(), vp(), vp(), vp(), vp(), vp()
+    lib = _lib.load()
+    check(lib.pyqsm_mesh_fill_holes(_p(t), t.shape[0], v.shape[0], _p(v), 0 if max_edges is None else int(max_edges),
+                                    ctypes.byref(n_loops), ctypes.byref(p_ptr), ctypes.byref(v_ptr),
+                                    ctypes.byref(f_ptr), ctypes.byref(a_ptr), ctypes.byref(n_new),
+                                    ctypes.byref(t_ptr), ctypes.byref(l_ptr), _p(st), int(device)))
+    nl, nn = int(n_loops.value), int(n_new.value)
+    ptr = _fill_take(lib, p_ptr, i32, nl + 1, np.int32) if nl else np.zeros(1, np.int32)
+    return HoleFill(ptr, _fill_take(lib, v_ptr, i32, int(ptr[-1]), np.int32),
+                    _fill_take(lib, f_ptr, ctypes.c_uint8, nl, np.uint8), _fill_take(lib, a_ptr, dbl, nl, np.float64),
+                    _fill_take(lib, t_ptr, i32, 3 * nn, np.int32).reshape(-1, 3),
+                    _fill_take(lib, l_ptr, i32, nn, np.int32), dict(zip(_FILL_STATS, (int(x) for x in st))))
+
+
 # ---------------------------------------------------------------- surface reconstruction (ball pivoting)
 
 RECON_MAX_RHO2 = 1 << 22        # PYQSM_RECON_MAX_RHO2: rho <= 2^11 lattice units
