@@ -363,6 +363,29 @@ int pyqsm_lbc_solve(const int32_t* indptr, const int32_t* indices, const double*
 /* y = L x for 3 columns at once (x, y f64 [n,3]); the SpMV the solve is built on. */
 int pyqsm_spmv3(const int32_t* indptr, const int32_t* indices, const double* vals,
                 int64_t n, const double* x, double* y, int32_t device);
+/*
+ * For tests: the multigrid hierarchy of B = diag(cw) L + diag(wh) that preconditions the B-solves
+ * of pyqsm_lbc_solve, built by the function the solve calls (same environment switches), and one
+ * cycle of it per right-hand side through both of its interfaces.
+ *   L as CSR (symmetric, diagonal stored); cw, wh f64 [n]; rhs f64 [m, n, 3], m >= 0.
+ *   meta i64 [108]: [0] levels, [1] coarsest solve (0 smoothing sweeps, 1 inverse made on the host,
+ *   2 inverse made on the device), [2] rows of the inverse, [3] its leading dimension, [4..6] the
+ *   elements the hierarchy takes in ibuf / dbuf / fbuf, [7] 1 when they were written; then four per
+ *   level: rows, stored entries, aggregates (-1 on the last level), entries of A P (-1: no table).
+ *   With fewer than two levels (no hierarchy the solve would use) only meta[0] is set.
+ *   ibuf i32 [icap], level by level: indptr [n+1], indices [nnz]; with a coarser level agg [n],
+ *   mptr [aggregates + 1], members [mptr's last]; with an A P table ap_ptr [n+1], ap_idx.
+ *   dbuf f64 [dcap], level by level: vals [nnz], diag [n], dinv [n]; then the inverse as stored
+ *   ([ld, ld]; the host-made one transposed). fbuf f32 [fcap]: ap_val of every level.
+ *   A buffer that is too small: nothing is written or run, meta[4..6] say what to bring.
+ *   x64 f64 [m, n, 3]: the cycle of the fp64 interface; x32 f32 [m, n, 3]: that of the fp32
+ *   interface on the fp32 rounding of rhs; dots f64 [m, 2, 3]: rhs . x per column as the cycles'
+ *   last kernel leaves it (fp64 interface, then fp32), partial slots folded as the solve folds them.
+ */
+int pyqsm_amg_probe(const int32_t* indptr, const int32_t* indices, const double* vals, int64_t n,
+                    const double* cw, const double* wh, const double* rhs, int64_t m, int64_t* meta,
+                    int32_t* ibuf, int64_t icap, double* dbuf, int64_t dcap, float* fbuf,
+                    int64_t fcap, double* x64, float* x32, double* dots, int32_t device);
 /* In-place clamp of every coordinate into [lo, hi] (skeletonize.py:291-296). */
 int pyqsm_clamp(double* pts, int64_t n, const double lo[3], const double hi[3],
                 int32_t device);

@@ -72,6 +72,8 @@ SIGNATURES = {
     "pyqsm_lbc_solve": (ctypes.c_int, [vp, vp, vp, i64, vp, vp, vp, dbl, i32, vp,
                                        ctypes.POINTER(i32), vp, i32]),
     "pyqsm_spmv3": (ctypes.c_int, [vp, vp, vp, i64, vp, vp, i32]),
+    "pyqsm_amg_probe": (ctypes.c_int, [vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, i64, vp, i64, vp, vp,
+                                       vp, i32]),
     "pyqsm_clamp": (ctypes.c_int, [vp, i64, vp, vp, i32]),
     "pyqsm_ball_query": (ctypes.c_int, [vp, i64, vp, dbl, vp, ctypes.POINTER(i64), i32]),
     "pyqsm_radius_mark": (ctypes.c_int, [vp, i64, vp, i64, dbl, i32, vp, vp, i32]),

@@ -286,7 +286,10 @@ __global__ __launch_bounds__(256) void k_sort_members(int nc, const int32_t* __r
 // Galerkin row I = sum over members i of I, entries (i, j): (agg[j], a_ij). One lane per
 // coarse row; the row is kept as a column-sorted list in LDS (slot-major, so the 64
 // lanes of the block touch 64 consecutive words), members and entries are visited in
-// a fixed order: the sums are reproducible and the result is exactly symmetric when A is.
+// a fixed order: the sums are reproducible. Entry (I, J) adds a_ij member by member of I, entry
+// (J, I) the same numbers member by member of J: another order, so the two differ in the last bit
+// or two once three terms meet. k_rows_to_csr therefore stores the sum of the row above the
+// diagonal on both sides, and the coarse matrix is exactly symmetric when A is.
 __global__ __launch_bounds__(64) void k_galerkin_rows(int nc, const int32_t* __restrict__ mptr,
                                                       const int32_t* __restrict__ members,
                                                       const int32_t* __restrict__ indptr,
@@ -344,8 +347,23 @@ __global__ __launch_bounds__(256) void k_rows_to_csr(int nc, const int32_t* __re
   if (I >= nc) return;
   const int b = indptr[I], cnt = indptr[I + 1] - b;
   for (int p = 0; p < cnt; ++p) {
-    indices[b + p] = tkeys[size_t(I) * kRowCap + p];
-    vals[b + p] = tvals[size_t(I) * kRowCap + p];
+    const int J = tkeys[size_t(I) * kRowCap + p];
+    double v = tvals[size_t(I) * kRowCap + p];
+    if (J < I) {  // below the diagonal: the sum of row J (binary search for column I in its sorted keys)
+      const int32_t* kj = tkeys + size_t(J) * kRowCap;
+      const int cj = indptr[J + 1] - indptr[J];
+      int lo = 0, hi = cj;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (kj[mid] < I)
+          lo = mid + 1;
+        else
+          hi = mid;
+      }
+      if (lo < cj && kj[lo] == I) v = tvals[size_t(J) * kRowCap + lo];
+    }
+    indices[b + p] = J;
+    vals[b + p] = v;
   }
 }
 
@@ -1341,6 +1359,78 @@ void amg_fine_matrix(const AmgHierarchy* H, const int32_t** indptr, const int32_
   *indptr = H->lv[0].A.indptr;
   *indices = H->lv[0].A.indices;
   *vals = H->lv[0].valsf;
+}
+
+// The hierarchy as pyqsm_amg_probe hands it out (layout: include/pyqsm_hip.h). The sizes go into
+// meta first; the arrays are copied only when all three buffers hold them (meta[7] = 1).
+int amg_readout(Ctx* c, const AmgHierarchy* H, int64_t* meta, int32_t* ibuf, int64_t icap, double* dbuf,
+                int64_t dcap, float* fbuf, int64_t fcap) {
+  const int nl = int(H->lv.size());
+  meta[0] = nl;
+  static_assert(kMaxLevels == 24, "pyqsm_hip.h: meta holds 8 + 4 * 25 entries (24 coarsenings: 25 levels)");
+  for (int q = 1; q < 8 + 4 * (kMaxLevels + 1); ++q) meta[q] = 0;
+  if (nl < 2) return 0;  // not a hierarchy the solver would use: nothing else to report
+  meta[1] = H->dense_inv ? 1 : H->dense_gj ? 2 : 0;
+  meta[2] = H->nc;
+  meta[3] = H->dense_inv ? H->nc : H->ld;
+  int64_t ni = 0, nd = 0, nf = 0;
+  std::vector<int32_t> nmem(size_t(nl), 0), nap(size_t(nl), 0);
+  for (int l = 0; l < nl; ++l) {
+    const AmgLevel& L = H->lv[size_t(l)];
+    int64_t* ml = meta + 8 + 4 * l;
+    ml[0] = L.n;
+    ml[1] = L.nnz;
+    ml[2] = ml[3] = -1;
+    ni += int64_t(L.n) + 1 + L.nnz;
+    nd += int64_t(L.nnz) + 2 * int64_t(L.n);
+    if (l + 1 < nl) {
+      const int nagg = H->lv[size_t(l) + 1].n;
+      ml[2] = nagg;
+      PQ_TRY(fetch(c, &nmem[size_t(l)], L.mptr + nagg));
+      ni += int64_t(L.n) + nagg + 1 + nmem[size_t(l)];
+      if (L.ap_ptr) {
+        PQ_TRY(fetch(c, &nap[size_t(l)], L.ap_ptr + L.n));
+        ml[3] = nap[size_t(l)];
+        ni += int64_t(L.n) + 1 + nap[size_t(l)];
+        nf += nap[size_t(l)];
+      }
+    }
+  }
+  const int64_t ninv = meta[1] ? meta[3] * meta[3] : 0;
+  nd += ninv;
+  meta[4] = ni;
+  meta[5] = nd;
+  meta[6] = nf;
+  if (ni > icap || nd > dcap || nf > fcap) return 0;
+  if (!ibuf || !dbuf || (nf > 0 && !fbuf)) return fail(PYQSM_EINVAL, "pyqsm_amg_probe: NULL buffer");
+  // (download of `count` elements, then the cursor moves on)
+  auto put = [&](auto*& dst, const auto* src, size_t count) {
+    const int rc = download(c, dst, src, count);
+    dst += count;
+    return rc;
+  };
+  for (int l = 0; l < nl; ++l) {
+    const AmgLevel& L = H->lv[size_t(l)];
+    const size_t n = size_t(L.n), nnz = size_t(L.nnz);
+    PQ_TRY(put(ibuf, L.A.indptr, n + 1));
+    PQ_TRY(put(ibuf, L.A.indices, nnz));
+    PQ_TRY(put(dbuf, L.A.vals, nnz));
+    PQ_TRY(put(dbuf, L.diag, n));
+    PQ_TRY(put(dbuf, L.dinv, n));
+    if (l + 1 == nl) break;
+    const size_t nagg = size_t(H->lv[size_t(l) + 1].n), nm = size_t(nmem[size_t(l)]), na = size_t(nap[size_t(l)]);
+    PQ_TRY(put(ibuf, L.agg, n));
+    PQ_TRY(put(ibuf, L.mptr, nagg + 1));
+    PQ_TRY(put(ibuf, L.members, nm));
+    if (!L.ap_ptr) continue;
+    PQ_TRY(put(ibuf, L.ap_ptr, n + 1));
+    PQ_TRY(put(ibuf, L.ap_idx, na));
+    PQ_TRY(put(fbuf, L.ap_val, na));
+  }
+  if (ninv) PQ_TRY(download(c, dbuf, H->dense_inv ? H->dense_inv : H->dense_gj, size_t(ninv)));
+  PQ_TRY(stream_sync(c));
+  meta[7] = 1;
+  return 0;
 }
 
 }  // namespace pyqsm

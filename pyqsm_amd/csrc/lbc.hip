@@ -1699,6 +1699,63 @@ int pyqsm_lbc_solve(const int32_t* indptr, const int32_t* indices, const double*
   return rc;
 }
 
+int pyqsm_amg_probe(const int32_t* indptr, const int32_t* indices, const double* vals, int64_t n,
+                    const double* cw, const double* wh, const double* rhs, int64_t m, int64_t* meta,
+                    int32_t* ibuf, int64_t icap, double* dbuf, int64_t dcap, float* fbuf, int64_t fcap,
+                    double* x64, float* x32, double* dots, int32_t device) {
+  PQ_API_RANGE("pyqsm_amg_probe");
+  if (n <= 0 || m < 0) return fail(PYQSM_EINVAL, "pyqsm_amg_probe: empty system or negative count");
+  if (!indptr || !indices || !vals || !cw || !wh || !meta)
+    return fail(PYQSM_EINVAL, "pyqsm_amg_probe: NULL pointer");
+  if (m > 0 && (!rhs || !x64 || !x32 || !dots)) return fail(PYQSM_EINVAL, "pyqsm_amg_probe: NULL pointer");
+  Call call(device);
+  Ctx* c = call.c;
+  if (!c) return PYQSM_ENODEV;
+  DevCsr L;
+  int64_t nnz;
+  PQ_TRY(upload_csr(c, indptr, indices, vals, n, &L, &nnz));
+  double *d_cw, *d_wh;
+  PQ_TRY(upload(c, cw, size_t(n), &d_cw));
+  PQ_TRY(upload(c, wh, size_t(n), &d_wh));
+  AmgHierarchy* h = nullptr;
+  PQ_TRY(amg_build(c, L, int(n), d_cw, d_wh, &h));  // as build_hierarchy does
+  AmgGuard guard{h};
+  PQ_TRY(amg_readout(c, h, meta, ibuf, icap, dbuf, dcap, fbuf, fcap));
+  // a single level is no hierarchy (build_hierarchy refuses it: the cycle has no level-0 xb), and a
+  // caller whose buffers were too small comes again
+  if (amg_levels(h) < 2 || meta[7] == 0 || m == 0) return 0;
+  double *d_b, *d_x, *d_dot;
+  float *d_bf, *d_xf;
+  PQ_TRY(c->arena.get(size_t(n) * 3, &d_b));
+  PQ_TRY(c->arena.get(size_t(n) * 3, &d_x));
+  PQ_TRY(c->arena.get(size_t(3) * kPart, &d_dot));
+  PQ_TRY(c->arena.get(size_t(n) * kVecStride, &d_bf));
+  PQ_TRY(c->arena.get(size_t(n) * kVecStride, &d_xf));
+  std::vector<float> hb(size_t(n) * kVecStride, 0.f), hx(size_t(n) * kVecStride);
+  const double* parts[1] = {d_dot};
+  double t[1][3];
+  for (int64_t r = 0; r < m; ++r) {
+    const double* b = rhs + size_t(r) * size_t(n) * 3;
+    double* dr = dots + size_t(r) * 6;
+    PQ_TRY(copy_in(c, d_b, b, size_t(n) * 3));
+    PQ_TRY(amg_vcycle(c, h, d_b, d_x, d_dot));
+    PQ_TRY(part_totals_host(c, parts, 1, t));
+    for (int k = 0; k < 3; ++k) dr[k] = t[0][k];
+    PQ_TRY(fetch(c, x64 + size_t(r) * size_t(n) * 3, d_x, size_t(n) * 3));
+    for (int64_t i = 0; i < n; ++i)
+      for (int k = 0; k < 3; ++k) hb[size_t(i) * kVecStride + k] = float(b[3 * i + k]);
+    PQ_TRY(copy_in(c, d_bf, hb.data(), hb.size()));
+    PQ_TRY(amg_vcycle_f32(c, h, d_bf, d_xf, d_dot));
+    PQ_TRY(part_totals_host(c, parts, 1, t));
+    for (int k = 0; k < 3; ++k) dr[3 + k] = t[0][k];
+    PQ_TRY(fetch(c, hx.data(), d_xf, hx.size()));
+    float* xr = x32 + size_t(r) * size_t(n) * 3;
+    for (int64_t i = 0; i < n; ++i)
+      for (int k = 0; k < 3; ++k) xr[3 * i + k] = hx[size_t(i) * kVecStride + k];
+  }
+  return 0;
+}
+
 int pyqsm_clamp(double* pts, int64_t n, const double lo[3], const double hi[3], int32_t device) {
   PQ_API_RANGE("pyqsm_clamp");
   if (n < 0) return fail(PYQSM_EINVAL, "negative size");

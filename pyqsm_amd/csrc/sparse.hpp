@@ -114,5 +114,8 @@ __device__ __forceinline__ void st4(float* v, int i, float a, float b, float c) 
 int amg_vcycle_f32(Ctx* c, AmgHierarchy* h, const float* b, float* x, double* dot = nullptr);
 void amg_fine_matrix(const AmgHierarchy* h, const int32_t** indptr, const int32_t** indices,
                      const float** vals);
+// The hierarchy's arrays for pyqsm_amg_probe (tests): sizes into meta, arrays when the buffers hold them.
+int amg_readout(Ctx* c, const AmgHierarchy* h, int64_t* meta, int32_t* ibuf, int64_t icap, double* dbuf,
+                int64_t dcap, float* fbuf, int64_t fcap);
 
 }  // namespace pyqsm

@@ -510,6 +510,65 @@ def spmv3(L, x, device: int = 0):
     return y
 
 
+def amg_probe(L, cw, wh, rhs=None, device: int = 0) -> dict:
+    """For tests (``pyqsm_amg_probe``): the multigrid hierarchy of ``B = diag(cw) L + diag(wh)`` as
+    ``lbc_solve`` builds it, and one cycle of it per right-hand side ``rhs[r]`` ([m, n, 3]).
+
+    ``n_levels``; with fewer than two levels nothing else (``levels`` is empty, no cycle is run).
+    ``levels[l]``: ``n, indptr, indices, vals, diag, dinv`` and, where a coarser level follows,
+    ``agg, mptr, members`` and (unless PYQSM_AMG_AP=0) ``ap_ptr, ap_idx, ap_val``; absent ones are None.
+    ``coarse``: "host" / "device" (a dense inverse, ``inverse`` [nc, nc] fp64) or "sweeps".
+    ``x64`` f64 / ``x32`` f32 [m, n, 3]: the fp64 interface's result and the fp32 interface's on
+    ``rhs.astype(float32)``; ``dot64`` / ``dot32`` [m, 3]: the ``rhs . x`` the cycles return."""
+    indptr, indices, data, n = _csr(L)
+    cw = np.ascontiguousarray(np.broadcast_to(np.asarray(cw, dtype=np.float64), (n,)))
+    wh = np.ascontiguousarray(np.broadcast_to(np.asarray(wh, dtype=np.float64), (n,)))
+    rhs = np.zeros((0, n, 3)) if rhs is None else np.ascontiguousarray(rhs, dtype=np.float64)
+    if rhs.ndim != 3 or rhs.shape[1:] != (n, 3):
+        raise ValueError(f"expected right-hand sides of shape [m,{n},3], got {rhs.shape}")
+    m = rhs.shape[0]
+    meta = np.zeros(108, dtype=np.int64)
+    x64, x32, dots = np.zeros((m, n, 3)), np.zeros((m, n, 3), dtype=np.float32), np.zeros((m, 2, 3))
+    cap = [4 * (n + 1) + 3 * len(indices), 4 * n + 2 * len(indices) + 1024 * 1024, len(indices)]
+    for _ in range(2):        # the second time with the sizes the first one reported
+        ibuf, dbuf, fbuf = np.zeros(cap[0], dtype=np.int32), np.zeros(cap[1]), np.zeros(cap[2], dtype=np.float32)
+        check(_lib.load().pyqsm_amg_probe(_p(indptr), _p(indices), _p(data), n, _p(cw), _p(wh), _p(rhs), m,
+                                          _p(meta), _p(ibuf), cap[0], _p(dbuf), cap[1], _p(fbuf), cap[2],
+                                          _p(x64), _p(x32), _p(dots), int(device)))
+        if meta[0] < 2 or meta[7]:
+            break
+        cap = [int(v) for v in meta[4:7]]
+    out = {"n_levels": int(meta[0]), "levels": [], "coarse": None, "inverse": None}
+    if meta[0] < 2:
+        return out
+    cur = {"i": 0, "d": 0, "f": 0}
+
+    def take(which, buf, count):
+        a = buf[cur[which]:cur[which] + count].copy()
+        cur[which] += count
+        return a
+
+    for l in range(int(meta[0])):
+        ln, nnz, nagg, nap = (int(v) for v in meta[8 + 4 * l:12 + 4 * l])
+        lv = dict.fromkeys(("agg", "mptr", "members", "ap_ptr", "ap_idx", "ap_val"))
+        lv["n"] = ln
+        lv["indptr"], lv["indices"] = take("i", ibuf, ln + 1), take("i", ibuf, nnz)
+        lv["vals"], lv["diag"], lv["dinv"] = take("d", dbuf, nnz), take("d", dbuf, ln), take("d", dbuf, ln)
+        if nagg >= 0:
+            lv["agg"], lv["mptr"] = take("i", ibuf, ln), take("i", ibuf, nagg + 1)
+            lv["members"] = take("i", ibuf, int(lv["mptr"][-1]))
+        if nap >= 0:
+            lv["ap_ptr"], lv["ap_idx"], lv["ap_val"] = take("i", ibuf, ln + 1), take("i", ibuf, nap), take("f", fbuf, nap)
+        out["levels"].append(lv)
+    out["coarse"] = ("sweeps", "host", "device")[int(meta[1])]
+    if meta[1]:
+        nc, ld = int(meta[2]), int(meta[3])
+        inv = take("d", dbuf, ld * ld).reshape(ld, ld)
+        out["inverse"] = np.ascontiguousarray(inv.T if meta[1] == 1 else inv[:nc, :nc])   # (the host's is stored transposed)
+    out.update(x64=x64, x32=x32, dot64=dots[:, 0].copy(), dot32=dots[:, 1].copy())
+    return out
+
+
 def clamp(pts: np.ndarray, lo, hi, device: int = 0) -> np.ndarray:
     """In-place clamp of a C-contiguous float64 [n,3] array."""
     if not (isinstance(pts, np.ndarray) and pts.dtype == np.float64 and pts.flags.c_contiguous):
