@@ -733,6 +733,51 @@ int pyqsm_mesh_fill_holes(const int32_t* tris, int64_t n_tris, int64_t n_verts, 
 int pyqsm_ball_pivot(const int32_t* ijk, const int16_t* normals, int64_t n, const uint64_t* rho2, int32_t n_levels,
                      int64_t max_tests, int64_t* n_tris, int32_t** tris, int64_t* stats, int32_t device);
 
+/* ---- 3-D alpha shape: exact boundary triangles and volume of lattice points ------ */
+/*
+ * What Open3D's create_from_point_cloud_alpha_shape extracts from the Delaunay tetrahedra of circumradius
+ * below alpha, by a contract of its own that needs no tetrahedra and no normals.
+ *   ijk i32 [n,3] lattice coordinates (at most 2^31 - 1 units of extent per axis, at most 2^26 points).
+ *   seg_start i64 [n_seg + 1], from 0 to n, ascending, or NULL (one segment, n_seg is ignored): a triple
+ *   and the points that block it belong to one segment; the result equals running every segment alone.
+ *   rho2 = alpha^2 in lattice units^2, in [1, PYQSM_RECON_MAX_RHO2] (PYQSM_EINVAL beyond, with the factor by
+ *   which the quantum must grow).
+ * A triple {a, b, c} of one segment with n = (b - a) x (c - a) != 0 and circumradius <= alpha has two balls
+ * of radius alpha through it, B+ on the +n side and B-. A ball is empty when no other point of the segment
+ * is strictly inside. kind 1 (regular): exactly one ball is empty and they are two (H > 0); the row is
+ * oriented so that n points to the empty ball, out of the solid. kind 2 (singular): both are empty and
+ * H > 0; written only with faces == PYQSM_ALPHA3_ALL, with b < c, and no part of the volume.
+ * Ties are ball pivoting's: a point on a ball does not block; a point on both balls in the triangle's plane
+ * drops the triple when its index is below a's or it lies strictly beyond the edge opposite a; a triple
+ * kept with a point off its plane exactly on an empty ball is counted in stats[4], and the surface may then
+ * fail to close: vol6 means a volume only when that counter is 0. Coincident points are not merged.
+ *   *rows receives i32 [*n_rows,4] rows (a, b, c, kind), a the smallest index, ascending by (a, b, c), hence
+ *   grouped by segment; allocated by the library, released with pyqsm_free; NULL when there is none. More than
+ *   16 n + 1024 rows: PYQSM_ERANGE.
+ *   vol6 u64 [n_seg,2] (low, high half): the sum of det(a - o, b - o, c - o) over the regular rows of the
+ *   segment, o its first point, as a 128-bit two's complement: six times the enclosed volume in lattice
+ *   units^3, from integer sums only. The same bytes on every run, rows and vol6 alike.
+ * max_tests: as pyqsm_ball_pivot's: PYQSM_ERANGE before the triangle pass when the estimate, the sum over
+ *   the points of (points in the 27-cell stencil)^2, exceeds it; <= 0: PYQSM_ALPHA3_DEFAULT_MAX_TESTS = 4e12,
+ *   ten seconds at the 4.1e11 estimated pair tests per second of the triangle pass measured on one MI355X
+ *   (forest cloud, alpha = 2 mean spacings; 4.6e11 at 4 spacings; profiles/alpha3_perf.jsonl, DESIGN.md section
+ *   27), rounded down. The pass lists no stencil^2 pairs, so it serves the same estimate four times as fast as
+ *   pyqsm_ball_pivot's.
+ * stats i64 [8] or NULL: estimated pair tests, ball tests run (candidates x neighbours within 2 alpha), of
+ *   those classified by the wide integers, candidate triples, rows kept with an off-plane tie, the largest
+ *   stencil, the most points in one cell, work items. Only the count of wide-integer classifications may
+ *   differ between runs (a lane stops asking about a ball at the first point inside it).
+ * Fewer than three points: no row, no device work.
+ */
+#define PYQSM_ALPHA3_REGULAR 0
+#define PYQSM_ALPHA3_ALL 1
+#define PYQSM_ALPHA3_CHUNK 1024
+#define PYQSM_ALPHA3_SLICE 16
+#define PYQSM_ALPHA3_DEFAULT_MAX_TESTS 4000000000000LL
+int pyqsm_alpha_shape3(const int32_t* ijk, int64_t n, const int64_t* seg_start, int64_t n_seg, uint64_t rho2,
+                       int32_t faces, int64_t max_tests, int64_t* n_rows, int32_t** rows, uint64_t* vol6,
+                       int64_t* stats, int32_t device);
+
 /* ---- farthest-point down-sampling ---------------------------------------- */
 /*
  * Stands in for open3d PointCloud.farthest_point_down_sample(num_samples) as

@@ -119,6 +119,8 @@ SIGNATURES = {
                                              ctypes.POINTER(i64), ctypes.POINTER(vp), ctypes.POINTER(vp), vp, i32]),
     "pyqsm_ball_pivot": (ctypes.c_int, [vp, vp, i64, vp, i32, i64, ctypes.POINTER(i64), ctypes.POINTER(vp), vp,
                                         i32]),
+    "pyqsm_alpha_shape3": (ctypes.c_int, [vp, i64, vp, i64, ctypes.c_uint64, i32, i64, ctypes.POINTER(i64),
+                                          ctypes.POINTER(vp), vp, vp, i32]),
     "pyqsm_fps": (ctypes.c_int, [vp, i64, i64, i64, vp, i32]),
     "pyqsm_pc_laplacian": (ctypes.c_int, [vp, i64, i32, dbl, ctypes.POINTER(i64),
                                           ctypes.POINTER(vp), ctypes.POINTER(vp),

@@ -53,6 +53,7 @@
 // vertices is inner and none of its three half-edges is in the table; all of a level at once.
 #include "grid.hpp"
 #include "recon_exact.hpp"
+#include "recon_grid.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -71,12 +72,6 @@ struct alignas(8) Normal16 {
   int16_t x, y, z, pad;
 };
 
-__global__ __launch_bounds__(256) void k_recon_to_f64(int64_t n3, const int32_t* __restrict__ ijk,
-                                                      double* __restrict__ xyz) {
-  const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
-  if (i < n3) xyz[i] = double(ijk[i]);
-}
-
 // the points in the grid's order: coordinates relative to the cloud's corner, normals as one 8-byte record
 __global__ __launch_bounds__(256) void k_recon_gather(int n, const int32_t* __restrict__ order,
                                                       const int32_t* __restrict__ ijk,
@@ -90,56 +85,6 @@ __global__ __launch_bounds__(256) void k_recon_gather(int n, const int32_t* __re
   ly[p] = int32_t(int64_t(ijk[3 * i + 1]) - y0);
   lz[p] = int32_t(int64_t(ijk[3 * i + 2]) - z0);
   ln[p] = Normal16{nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2], 0};
-}
-
-struct ReconStencil {
-  int lo[9], n[9];  // the nine (y, z) rows of the 27 cells as ranges of sorted positions
-  int total;
-  __device__ __forceinline__ int at(int j) const {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      if (j < n[k]) return lo[k] + j;
-      j -= n[k];
-    }
-    return lo[8] + j;
-  }
-};
-
-// c is a cell that holds points, hence an interior one: the border cells make every row exist
-__device__ __forceinline__ ReconStencil recon_stencil(int nx, int ny, int c, const int32_t* __restrict__ start) {
-  ReconStencil st;
-  const int cz = c / (nx * ny), r = c - cz * nx * ny, cy = r / nx, cx = r - cy * nx;
-  st.total = 0;
-  int k = 0;
-  for (int dz = -1; dz <= 1; ++dz)
-    for (int dy = -1; dy <= 1; ++dy, ++k) {
-      const int row = ((cz + dz) * ny + cy + dy) * nx + cx;
-      st.lo[k] = start[row - 1];
-      st.n[k] = start[row + 2] - st.lo[k];
-      st.total += st.n[k];
-    }
-  return st;
-}
-
-// nblk[c] = blocks of the triangle pass for cell c, nblk[ncell] = 0 (scanned in place afterwards);
-// est[0] += low 32 bits, est[1] += high bits of (points of the cell) * (stencil count)^2, clamped to
-// 2^62 per cell; est[2] = the largest stencil, est[3] = the most points in one cell.
-__global__ __launch_bounds__(256) void k_recon_plan(int ncell, int nx, int ny, int nz,
-                                                    const int32_t* __restrict__ start, int32_t* __restrict__ nblk,
-                                                    unsigned long long* __restrict__ est) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c > ncell) return;
-  const int m = c < ncell ? start[c + 1] - start[c] : 0;
-  nblk[c] = (m + kReconSlice - 1) / kReconSlice;
-  if (m == 0) return;
-  const ReconStencil st = recon_stencil(nx, ny, c, start);
-  unsigned __int128 v = (unsigned __int128)(unsigned)st.total * (unsigned)st.total * (unsigned)m;
-  const unsigned __int128 cap = (unsigned __int128)1 << 62;
-  const unsigned long long w = (unsigned long long)(v < cap ? v : cap);
-  atomicAdd(&est[0], w & 0xFFFFFFFFull);
-  atomicAdd(&est[1], w >> 32);
-  atomicMax(&est[2], (unsigned long long)st.total);
-  atomicMax(&est[3], (unsigned long long)m);
 }
 
 // is the directed half-edge (u, v) in the table sorted by (u, v)?
@@ -429,23 +374,6 @@ __global__ __launch_bounds__(256) void k_recon_vertex_state(int n_he, const int3
   atomicOr(&state[v], bits);
 }
 
-__global__ __launch_bounds__(256) void k_recon_split_rows(int e, const int4* __restrict__ rows,
-                                                          int32_t* __restrict__ ka, int32_t* __restrict__ kb,
-                                                          int32_t* __restrict__ kc) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= e) return;
-  const int4 r = rows[i];
-  ka[i] = r.x;
-  kb[i] = r.y;
-  kc[i] = r.z;
-}
-
-__global__ __launch_bounds__(256) void k_recon_permute_rows(int e, const int32_t* __restrict__ perm,
-                                                            const int4* __restrict__ rows, int4* __restrict__ out) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < e) out[i] = rows[perm[i]];
-}
-
 }  // namespace pyqsm
 
 using namespace pyqsm;
@@ -554,7 +482,7 @@ int pyqsm_ball_pivot(const int32_t* ijk, const int16_t* normals, int64_t n, cons
       PQ_HIP(hipGetLastError());
     }
     PQ_HIP(hipMemsetAsync(d_est, 0, 32, c->stream));
-    hipLaunchKernelGGL(k_recon_plan, dim3(ceil_div(nc + 1, 256)), dim3(256), 0, c->stream, nc, lp->g.nx, lp->g.ny,
+    hipLaunchKernelGGL(k_recon_plan<kReconSlice>, dim3(ceil_div(nc + 1, 256)), dim3(256), 0, c->stream, nc, lp->g.nx, lp->g.ny,
                        lp->g.nz, static_cast<const int32_t*>(lp->g.start), lp->d_blk, d_est);
     PQ_HIP(hipGetLastError());
     PQ_TRY(exclusive_scan_i32(c, lp->d_blk, int64_t(nc) + 1));

@@ -382,6 +382,35 @@ class TriangleMesh:
         mesh.stats = res.stats
         return mesh
 
+    # ---- the 3-D alpha shape on the GPU (hip.alpha_shape3)
+
+    @staticmethod
+    def create_from_point_cloud_alpha_shape(pcd, alpha, tetra_mesh=None, pt_map=None, quantum=None,
+                                            device: int = 0, *, max_tests=None):
+        """Open3D's ``create_from_point_cloud_alpha_shape`` by a contract of its own: the triangles of cloud
+        points with exactly one empty ball of radius ``alpha`` through them, oriented out of the solid and
+        decided exactly on the cloud SNAPPED to a lattice (``geometry.hull.alpha_shape``). In
+        general position that is the boundary of the Delaunay tetrahedra of circumradius below alpha, which
+        Open3D extracts; triangle-for-triangle parity with it is unverified. ``tetra_mesh`` and ``pt_map``
+        are accepted and ignored: no tetrahedral mesh is built. It needs no normals.
+
+        The result keeps the cloud's points as vertices (all of them, in order) and carries ``volume`` and
+        ``six_volume`` (meaningful only when ``n_unresolved_ties`` is 0), ``n_unresolved_ties``, ``quantum``
+        and ``stats``."""
+        try:
+            from .hull import alpha_shape
+        except ImportError:  # flat import (pyqsm_amd/ on sys.path)
+            _hip()
+            from pyqsm_amd.geometry.hull import alpha_shape
+        shape = alpha_shape(pcd, alpha, quantum=quantum, device=device, max_tests=max_tests)
+        mesh = shape.to_mesh()
+        mesh.volume = shape.volume
+        mesh.six_volume = shape.six_volume
+        mesh.n_unresolved_ties = shape.n_unresolved_ties
+        mesh.quantum = shape.quantum
+        mesh.stats = shape.stats
+        return mesh
+
     def compute_vertex_normals(self, normalized: bool = True) -> "TriangleMesh":
         """Open3D's ``compute_vertex_normals``, minimal: the sum of the (area-weighted) normals of
         the triangles at each vertex, normalised; a vertex without triangles gets (0, 0, 1) as in

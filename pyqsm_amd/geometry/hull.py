@@ -3,6 +3,10 @@
     convex_hull(points)            what scipy.spatial.ConvexHull(points) is to pyQSM: .simplices,
                                    .vertices, .volume, .area (utils/lib_integration.py:31)
     convex_hulls(points, seg_start)    the same for many clouds in one call
+    alpha_shape(points, alpha)     the 3-D alpha shape, what Open3D's create_from_point_cloud_alpha_shape is
+                                   to pyQSM (surf_recon.py get_mesh, skeletonize.py): .triangles, .kinds,
+                                   .vertices, .volume, .area of a surface that follows the concavities
+    alpha_shapes(points, seg_start, alpha)   the same for many clouds in one call
     OrientedBoundingBox            Open3D's PCA box of the hull's vertices, what
                                    pcd.get_oriented_bounding_box() returns (skeletonize.py:240,
                                    point_cloud_processing.py:306, reconstruction.py:56), with
@@ -116,6 +120,102 @@ def convex_hulls(points, seg_start, quantum=None, device: int = 0, max_tests=Non
         t = r.tris[r.tri_ptr[s]:r.tri_ptr[s + 1]] - np.int32(a)
         out.append(ConvexHull(pts[a:b], ijk[a:b], t, r.dim[s], quantum, np.zeros(3), r.stats))
     return out
+
+
+class AlphaShape:
+    """One cloud's alpha shape (``hip.alpha_shape3``). ``triangles`` int32 [T, 3]: the
+    smallest index first, ascending; regular ones (``kinds`` 1) are oriented out of the solid, singular ones
+    (``kinds`` 2, only with ``faces="all"``) are sheets with ``b < c`` and no part of volume or area.
+    ``vertices``: ascending indices of the points some triangle uses; ``six_volume``: Python int in lattice
+    units^3; ``volume`` / ``area`` (of the regular triangles) in the points' units. ``n_unresolved_ties``:
+    triangles kept although a point off their plane lies exactly on their empty ball; the surface may then
+    fail to close, and ``volume`` means something only when it is 0. ``quantum`` / ``rho2``: the lattice and
+    the squared radius on it; ``stats``: the call's counters."""
+
+    def __init__(self, points, ijk, rows, six_volume, quantum, rho2, n_unresolved_ties, stats=None):
+        self.points = points
+        self.ijk = ijk
+        self.triangles = np.ascontiguousarray(rows[:, :3])
+        self.kinds = np.ascontiguousarray(rows[:, 3])
+        self.quantum = float(quantum)
+        self.rho2 = int(rho2)
+        self.n_unresolved_ties = int(n_unresolved_ties)
+        self.stats = stats or {}
+        self.vertices = np.unique(self.triangles).astype(np.int64)
+        self.six_volume = int(six_volume)
+        self.volume = self.six_volume / 6.0 * self.quantum ** 3
+        regular = self.triangles[self.kinds == hip.ALPHA3_REGULAR]
+        nrm = twice_area_normals(ijk, regular) if len(regular) else np.zeros((0, 3), np.int64)
+        n2 = [int(x) * int(x) + int(y) * int(y) + int(z) * int(z) for x, y, z in nrm]     # in row order
+        self.area = 0.5 * self.quantum ** 2 * float(sum(np.sqrt(float(v)) for v in n2))
+
+    def to_mesh(self) -> TriangleMesh:
+        """The regular triangles as a mesh over ALL the points (indices unchanged)."""
+        return TriangleMesh(self.points, self.triangles[self.kinds == hip.ALPHA3_REGULAR])
+
+
+def snap_for_radius(pts, radius, quantum=None):
+    """``(lattice int32 [n,3], quantum, rho2)`` for a ball of ``radius``: ball pivoting's rule (DESIGN section
+    19). The quantum is a power of two, by default the larger of ``quantize_mesh``'s (extent / 2^20) and the
+    smallest at which the radius is at most 2^11 lattice units; ``rho2 = floor((radius / quantum)^2)``. A given
+    quantum that does not fit is refused with the one that would."""
+    import math
+    from .mesh_processing import _check_quantum, _quantum_for
+    radius = float(radius)
+    if not np.isfinite(radius) or radius <= 0:
+        raise ValueError("alpha must be positive and finite")
+    if not np.isfinite(pts).all():
+        raise ValueError("point coordinates must be finite")
+    max_rho = float(1 << 11)
+    m, e = math.frexp(radius / max_rho)                  # the smallest power of two >= radius / 2^11
+    q_fit = math.ldexp(1.0, e - 1 if m == 0.5 else e)
+    if quantum is None:
+        ext = float((pts.max(axis=0) - pts.min(axis=0)).max()) if len(pts) else 0.0
+        q = max(_quantum_for(ext), q_fit)
+    else:
+        q = _check_quantum(quantum)
+        if radius / q > max_rho:
+            raise ValueError(f"alpha {radius!r} is {radius / q:.0f} lattice units at quantum {q!r}, more than 2^11: "
+                             f"a quantum of {q_fit!r} would fit")
+    rho2 = int(np.floor((radius / q) ** 2))
+    if rho2 < 1:
+        raise ValueError(f"alpha {radius!r} is below the quantum {q!r}")
+    scaled = np.rint(pts / q)
+    if len(pts) and np.abs(scaled).max() >= 2.0 ** 62:
+        raise ValueError("quantum is too small for these coordinates")
+    lat = scaled.astype(np.int64)
+    if len(pts):
+        lat -= lat.min(axis=0)
+        if lat.max() >= 1 << 31:
+            raise ValueError(f"the cloud spans {int(lat.max())} lattice units at quantum {q!r}, more than 2^31: "
+                             "use a larger quantum")
+    return lat.astype(np.int32), q, rho2
+
+
+def alpha_shapes(points, seg_start, alpha, quantum=None, faces="regular", device: int = 0, max_tests=None) -> list:
+    """One :class:`AlphaShape` per segment ``points[seg_start[s]:seg_start[s + 1]]`` from a single call on
+    one lattice: a stand of trees gets its crown volumes at once. A triangle and the points that block it
+    belong to one segment; the triangles of each shape index into its own segment."""
+    pts = as_points(points)
+    seg = np.asarray(seg_start, dtype=np.int64)
+    ijk, q, rho2 = snap_for_radius(pts, alpha, quantum)
+    r = hip.alpha_shape3(ijk, rho2, seg_start=seg, faces=faces, max_tests=max_tests, device=device)
+    first = np.searchsorted(r.rows[:, 0], seg)          # rows ascend by a: grouped by segment
+    out = []
+    for s, (a, b) in enumerate(zip(seg[:-1], seg[1:])):
+        rows = r.rows[first[s]:first[s + 1]].copy()
+        rows[:, :3] -= np.int32(a)
+        # the tie counter is the call's, not kept per segment: every shape of the call carries it
+        out.append(AlphaShape(pts[a:b], ijk[a:b], rows, r.vol6[s], q, rho2, r.stats["unresolved_ties"], r.stats))
+    return out
+
+
+def alpha_shape(points, alpha, quantum=None, faces="regular", device: int = 0, max_tests=None) -> AlphaShape:
+    """The 3-D alpha shape of ``points`` ([n, 3], or anything with ``.points``) on the GPU at radius ``alpha``
+    (the points' units), exact for the points snapped to the lattice (:func:`snap_for_radius`): by a contract
+    of its own, NOT Open3D's triangle list, with which parity is unverified."""
+    pts = as_points(points)
+    return alpha_shapes(pts, np.array([0, len(pts)], np.int64), alpha, quantum, faces, device, max_tests)[0]
 
 
 def pca_frame(hull_pts):

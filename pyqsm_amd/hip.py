@@ -1633,6 +1633,92 @@ def ball_pivot(ijk, normals_i16, rho2_list, max_tests: int | None = None, device
                      stats["unresolved_ties"], stats)
 
 
+# ---------------------------------------------------------------- 3-D alpha shape
+
+ALPHA3_CHUNK = 1024             # PYQSM_ALPHA3_CHUNK: neighbours staged in LDS at a time
+ALPHA3_SLICE = 16               # PYQSM_ALPHA3_SLICE: points of a cell one work item serves
+ALPHA3_DEFAULT_MAX_TESTS = 4_000_000_000_000   # PYQSM_ALPHA3_DEFAULT_MAX_TESTS: ten seconds at 4.1e11 pair tests/s
+ALPHA3_REGULAR, ALPHA3_SINGULAR = 1, 2         # the kinds of a row
+_ALPHA3_STATS = ("estimated_tests", "tests", "exact_fallbacks", "candidates", "unresolved_ties", "max_stencil",
+                 "max_cell_points", "work_items")
+
+
+class AlphaShapeRefused(_lib.PyQSMHipError, ValueError):
+    """``pyqsm_alpha_shape3`` refused its input (``PYQSM_EINVAL``, ``PYQSM_ERANGE``: a radius or a cloud outside
+    the bounds, an estimate above ``max_tests``, too many rows). A ``ValueError`` like the refusals
+    :func:`alpha_shape3` raises before it calls the library; ``.stats`` holds the call's counters."""
+
+
+class AlphaShape3(NamedTuple):
+    """Results of :func:`alpha_shape3`."""
+    rows: np.ndarray                # int32 [R, 4]: (a, b, c, kind), a the smallest index, ascending by (a, b, c)
+    vol6: list                      # per segment: six times the enclosed volume in lattice units^3, Python int
+    stats: dict
+
+
+def alpha_shape3(ijk, rho2: int, seg_start=None, faces: str = "regular", max_tests: int | None = None,
+                 device: int = 0) -> AlphaShape3:
+    """The 3-D alpha shape of lattice points at ``alpha^2 = rho2`` lattice units^2, decided by integer
+    predicates only: the triples with exactly one empty ball of radius alpha through them
+    (``kind`` 1, oriented out of the solid) and, with ``faces="all"``, those with two (``kind`` 2, ``b < c``).
+    ``ijk`` int32 [n,3]; ``seg_start`` [n_seg + 1] splits it into independent clouds on one lattice.
+    ``vol6[s]`` is the exact sum of ``det(a - o, b - o, c - o)`` over the regular rows of segment ``s``; it is
+    six times a volume only when ``stats["unresolved_ties"]`` is 0. ``max_tests``: the work cap of
+    :func:`ball_pivot`. Refusals are ``ValueError``s: raised here, or as :class:`AlphaShapeRefused` when the
+    library refuses. ``stats["exact_fallbacks"]`` may differ between runs; nothing else does."""
+    p = np.asarray(ijk)
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise ValueError(f"expected lattice points of shape [n,3], got {p.shape}")
+    if p.size and not np.issubdtype(p.dtype, np.integer):
+        raise ValueError("lattice points must be integers")
+    if p.size and (p.min() < -(1 << 31) or p.max() >= (1 << 31)):
+        raise ValueError("lattice points must fit int32")
+    if p.size and int((p.max(axis=0).astype(np.int64) - p.min(axis=0).astype(np.int64)).max()) >= (1 << 31):
+        raise ValueError("the cloud spans more than 2^31 lattice units")
+    p = np.ascontiguousarray(p, dtype=np.int32)
+    n = p.shape[0]
+    if faces not in ("regular", "all"):
+        raise ValueError(f"faces must be 'regular' or 'all', got {faces!r}")
+    r = int(rho2)
+    if r < 1:
+        raise ValueError("rho^2 must be a positive integer (lattice units^2)")
+    if r > RECON_MAX_RHO2:
+        shift = 1
+        while (r >> (2 * shift)) > RECON_MAX_RHO2:
+            shift += 1
+        raise ValueError(f"rho^2 = {r} exceeds 2^22 lattice units^2 (rho <= 2048): "
+                         f"a quantum 2^{shift} times as large would fit")
+    if seg_start is None:
+        seg, n_seg = None, 1
+    else:
+        seg = np.ascontiguousarray(seg_start, dtype=np.int64)
+        if seg.ndim != 1 or seg.shape[0] < 1 or seg[0] != 0 or seg[-1] != n or (np.diff(seg) < 0).any():
+            raise ValueError("seg_start must hold n_seg + 1 ascending offsets from 0 to n")
+        n_seg = seg.shape[0] - 1
+    st = np.zeros(8, np.int64)
+    halves = np.zeros((max(n_seg, 1), 2), np.uint64)
+    n_rows = i64(0)
+    out = vp()
+    lib = _lib.load()
+    code = lib.pyqsm_alpha_shape3(_p(p), n, None if seg is None else _p(seg), n_seg, r, int(faces == "all"),
+                                  0 if max_tests is None else int(max_tests), ctypes.byref(n_rows),
+                                  ctypes.byref(out), _p(halves), _p(st), int(device))
+    stats = dict(zip(_ALPHA3_STATS, (int(x) for x in st)))
+    if code in (-1, -4):            # PYQSM_EINVAL, PYQSM_ERANGE: a refusal, in ValueError style
+        msg = lib.pyqsm_last_error()
+        err = AlphaShapeRefused(code, msg.decode("utf-8", "replace") if msg else "")
+        err.stats = stats           # what ran before the refusal
+        raise err
+    check(code)
+    rows = _adopt(lib, out, i32, 4 * n_rows.value, np.int32).reshape(-1, 4) if out.value \
+        else np.zeros((0, 4), np.int32)
+    vol6 = []
+    for lo, hi in halves[:n_seg].tolist():
+        v = (int(hi) << 64) | int(lo)
+        vol6.append(v - (1 << 128) if v >> 127 else v)
+    return AlphaShape3(rows, vol6, stats)
+
+
 def fps(points, num_samples: int, start_index: int = 0, device: int = 0) -> np.ndarray:
     """Farthest-point sampling: int32 indices in selection order."""
     pts = _points(points)
